@@ -15,6 +15,15 @@ counts, nnz ~ 1e8, K = 32, S = 1, full batch, row-sharded over the ranks
     python bench.py --gpus 1 --steps 20 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times --steps steps and prints the line: `value`, `ms_per_step`,
+and the kernel taps and roofline of those same steps.  --full adds everything measured beside
+them in runs of their own: the whole VI step (vi_step_ms), the `also` block (S = 20, minibatch,
+the 8-GPU shard, the deterministic mode, the HBM copy ceiling, the layout build, C5 / C2 / K = 128
+/ C1 / the reference harness shape / C4, the step after 50 Adam steps) and the CPU baseline;
+--no-extras and --no-cpu-baseline leave parts of it out.  --dump-outputs DIR writes what the last
+timed step returned (dump_outputs); the inputs are seeded, so runs with the same arguments compare
+output for output.
 """
 import argparse
 import json
@@ -490,6 +499,29 @@ def _pick_collective(model, lib_comm, dev, world, rank, S, want, all_reduce_):
     return lib_comm, (transport_lib if lib_comm is not None else "torch.distributed"), rec
 
 
+DUMP_MAX_ENTRIES = 1 << 20     # per gradient: 12 of them stay under 64 MB in float32
+DUMP_SEED = 20241218
+
+
+def dump_outputs(path, parts, grads, nnf):
+    """What one energy + gradient call returned, as DIR/<name>.npy: part_<name> ([S] float64, the 14 energy
+    parts), grad_<name> (float32, flattened [S,*shape]; above DUMP_MAX_ENTRIES entries the ones at a sorted
+    sample of indices drawn with replacement from default_rng(DUMP_SEED), so the same for every build at the
+    same arguments) and n_nonfinite ([S] float64)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, t in parts.items():
+        np.save(os.path.join(path, f"part_{name}.npy"), t.detach().double().cpu().numpy())
+    for name, t in grads.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_MAX_ENTRIES:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), DUMP_MAX_ENTRIES))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(path, f"grad_{name}.npy"), flat.float().cpu().numpy())
+    np.save(os.path.join(path, "n_nonfinite.npy"), nnf.detach().double().cpu().numpy())
+
+
 def main():
     # The contract is ONE JSON line on stdout.  Libraries below this script print there too
     # (RCCL writes a version banner from C when a communicator is created), so file
@@ -505,8 +537,15 @@ def main():
     ap.add_argument("--rows", type=int, default=None, help="override total rows")
     ap.add_argument("--panel-rows", type=int, default=0,
                     help="rows per panel of the panel-CSC; 0 = spmf_amd.sparse.balanced_panel_rows")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the S=20 / minibatch lines")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the whole VI step, the `also` block "
+                         "(other sizes, configs and modes), the HBM copy ceiling and the CPU baseline; "
+                         "a plain run times the energy + gradient steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (energy parts, gradients, non-finite "
+                         "counts) to DIR/<name>.npy; gradients above 2^20 entries as a fixed seeded sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the `also` block")
     ap.add_argument("--split", action="store_true",
                     help="multi-rank: all-reduce the lower column half while the column pass "
                          "produces the upper one (off by default: on ONE rank it costs 56 us "
@@ -691,12 +730,15 @@ def main():
     if distributed:
         all_reduce_(tmax, dist.ReduceOp.MAX)
     dt = float(tmax[0])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, parts, grads, nnf)
 
-    # extras SURVEY 8(d) asks to report beside the headline (1 GPU only, not `value`):
+    # extras SURVEY 8(d) asks to report beside the headline (--full, 1 GPU only, not `value`):
     # S=20 draws per step (tests/spmf_test.py:39), a B~20000-row minibatch, the 125k-row
     # shard of the 8-GPU configuration with its N-independent part, a one-rank RCCL
     # all-reduce of the packed accumulators, and the step again after 50 seeded Adam steps
     extras = {}
+    with_extras = args.full and not args.no_extras
 
     def timed(fn, n, w):
         for _ in range(w):
@@ -709,7 +751,7 @@ def main():
         return 1e3 * (time.perf_counter() - t_) / n
 
     import ctypes as C
-    if world == 1 and not args.no_extras and not logt and mixed_mask is None:
+    if world == 1 and with_extras and not logt and mixed_mask is None:
         torch.manual_seed(gen_seed)
         p20 = model.surrogate_distribution.sample(20)
         extras["S20_ms_per_step"] = timed(lambda: model.energy_and_grads(batch, p20), 2, 1)
@@ -797,7 +839,7 @@ def main():
         except Exception as e:                      # no librccl on the box: report, do not fail
             extras["allreduce_1rank_us"] = None
             extras["allreduce_error"] = str(e)[:120]
-    if world == 1 and not args.no_extras and not logt and mixed_mask is None:
+    if world == 1 and with_extras and not logt and mixed_mask is None:
         # the deterministic mode (spmf_ctx_set_deterministic) on the same resident workload: ms per step,
         # the kernel taps, and whether two steps give the same bits (parts and all gradients)
         try:
@@ -824,7 +866,7 @@ def main():
             del mdet, pa, ga, pb, gb, pd_, gd_
         except Exception as e:
             extras["det_error"] = str(e)[:200]
-    if world == 1 and not args.no_extras:
+    if world == 1 and with_extras:
         # "measure a copy kernel for the attainable HBM ceiling and report both": one
         # 1 GiB device-to-device copy (read + write bytes), beside the 8 TB/s nominal peak
         try:
@@ -835,7 +877,7 @@ def main():
             del src_, dst_
         except Exception as e:
             extras["hbm_copy_error"] = str(e)[:120]
-    if world == 1 and not args.no_extras:
+    if world == 1 and with_extras:
         # the data-format step in front of the path: the device layout of this whole
         # workload built again from its resident CSR arrays by the library (csrc/layout.hip), and the
         # statistics pre-pass (row sums + column sums of compute_scales)
@@ -863,7 +905,7 @@ def main():
             del sc2, cs2
         except Exception as e:
             extras["layout_error"] = str(e)[:200]
-    if world == 1 and not args.no_extras and args.workload == "c3":
+    if world == 1 and with_extras and args.workload == "c3":
         # a second BASELINE config in the driver-timed record
         try:
             extras.update(c5_extra(dev))
@@ -893,7 +935,7 @@ def main():
                 extras.update(c4_extra(dev))
             except Exception as e:
                 extras["c4_error"] = str(e)[:200]
-    if world == 1 and not args.no_extras:
+    if world == 1 and with_extras:
         # "surrogate at its init values and after 50 seeded Adam steps" -- the same
         # energy + gradient step timed again at draws from the trained surrogate
         from spmf_amd import vi as _vi
@@ -911,23 +953,25 @@ def main():
         extras["after50_loss"] = st50[8]
         del p50
 
-    # extra (not the contract's `value`): the whole VI step -- base noise, surrogate
+    # extra with --full (not the contract's `value`): the whole VI step -- base noise, surrogate
     # transform + log q, energy + gradient, chain to the trainables, Adam -- per step
-    from spmf_amd import vi
-    opt = vi.AdamHIP(model, model.surrogate_distribution.trainable_variables, 1e-3)
-    opt.init_state(3.0)
-    n_vi = max(2, min(5, args.steps))
-    vi_seed = 20241218 + 77          # row shards replicate the surrogate: every rank draws the same noise
-    for it in range(n_vi + 1):
-        if it == 1:
-            torch.cuda.synchronize()
-            tv = time.perf_counter()
-        # what fit() runs, one rank or many: no host read-back (row shards: the reducer's
-        # all-reduce sits inside the device-gated step)
-        vi.vi_step_dev(model, opt, batch, rows_g, S, all_reduce=hook,
-                       seed=vi_seed if hook is not None else None)
-    torch.cuda.synchronize()
-    vi_ms = 1e3 * (time.perf_counter() - tv) / n_vi
+    vi_ms = None
+    if args.full:
+        from spmf_amd import vi
+        opt = vi.AdamHIP(model, model.surrogate_distribution.trainable_variables, 1e-3)
+        opt.init_state(3.0)
+        n_vi = max(2, min(5, args.steps))
+        vi_seed = 20241218 + 77          # row shards replicate the surrogate: every rank draws the same noise
+        for it in range(n_vi + 1):
+            if it == 1:
+                torch.cuda.synchronize()
+                tv = time.perf_counter()
+            # what fit() runs, one rank or many: no host read-back (row shards: the reducer's
+            # all-reduce sits inside the device-gated step)
+            vi.vi_step_dev(model, opt, batch, rows_g, S, all_reduce=hook,
+                           seed=vi_seed if hook is not None else None)
+        torch.cuda.synchronize()
+        vi_ms = 1e3 * (time.perf_counter() - tv) / n_vi
 
     if rank == 0:
         ms_step = 1e3 * dt / args.steps
@@ -1055,7 +1099,7 @@ def main():
             "saturated": sat0,
             "elbo_x": float(parts["x"][0]),
         }
-        if not args.no_cpu_baseline and world == 1 and not logt and mixed_mask is None:
+        if args.full and not args.no_cpu_baseline and world == 1 and not logt and mixed_mask is None:
             n_s, nnz_s, t_s, parity, cores = cpu_baseline(sc, model, params, K)
             out["cpu_baseline"] = {
                 "value": 1.0 / (t_s * nnz_g / nnz_s), "unit": "steps/s", "cores": cores,

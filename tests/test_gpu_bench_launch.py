@@ -70,3 +70,32 @@ def test_torchrun_one_rank_rccl_matches_the_plain_run(transport):
     assert out["config"]["nnz"] == ref["config"]["nnz"]
     assert abs(out["elbo_x"] - ref["elbo_x"]) <= 1e-6 * abs(ref["elbo_x"])
     assert out["n_nonfinite"] == 0
+
+
+@pytest.mark.timeout(600)
+def test_plain_run_times_the_steps_and_dumps_what_the_last_step_returned(tmp_path):
+    """A plain run (no --full) measures the headline only; --dump-outputs writes the last timed step's
+    energy parts and gradients, and two runs with the same arguments see the same inputs."""
+    import numpy as np
+    args = [sys.executable, "bench.py", "--gpus", "1", "--workload", "small", "--steps", "4", "--warmup", "1"]
+    outs = []
+    for tag in ("a", "b"):
+        r = subprocess.run(args + ["--dump-outputs", str(tmp_path / tag)], cwd=ROOT, capture_output=True,
+                           text=True, timeout=280)
+        assert r.returncode == 0, r.stderr[-2000:]
+        outs.append(_last_json(r.stdout))
+    out = outs[0]
+    assert out["steps"] == 4 and out["warmup"] == 1 and math.isfinite(out["ms_per_step"]) and out["ms_per_step"] > 0
+    assert abs(out["value"] - 1e3 / out["ms_per_step"]) <= 1e-9 * out["value"]
+    assert out["also"] == {} and out["cpu_baseline"] is None and out["vi_step_ms"] is None
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert "part_x.npy" in files and "grad_u.npy" in files and "n_nonfinite.npy" in files
+    assert len([f for f in files if f.startswith("grad_")]) == 12
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 * 2 ** 20
+    x = np.load(tmp_path / "a" / "part_x.npy")
+    assert x.dtype == np.float64 and x[0] == out["elbo_x"]
+    assert outs[1]["config"]["nnz"] == out["config"]["nnz"]
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape
+        np.testing.assert_allclose(a, b, rtol=1e-4, atol=1e-5 * float(np.abs(b).max() + 1e-30), err_msg=f)

@@ -14,7 +14,7 @@ import json
 for l in open('$f'):
     d=json.loads(l); r=d['runs'][-1]; print('  ', d['shape'], r)
 "; done
-python bench.py > $o/bench.json 2> $o/bench.err || { tail -5 $o/bench.err; exit 1; }
+python bench.py --full > $o/bench.json 2> $o/bench.err || { tail -5 $o/bench.err; exit 1; }
 SPMF_ROW_DYNAMIC=0 python bench.py --no-cpu-baseline --no-extras > $o/bench_static.json 2> $o/bench_static.err || { tail -5 $o/bench_static.err; exit 1; }
 python3 -c "
 import json

@@ -8,7 +8,7 @@ timeout -k 10 1000 python -m pytest tests -q -m gpu > $o/tests.log 2>&1
 rc=$?; echo "tests rc=$rc" > $o/tests.rc; tail -3 $o/tests.log
 [ $rc -lt 2 ] || exit 1
 grep -E "^(FAILED|ERROR)" $o/tests.log
-python bench.py > $o/bench.json 2> $o/bench.err || { tail -5 $o/bench.err; exit 1; }
+python bench.py --full > $o/bench.json 2> $o/bench.err || { tail -5 $o/bench.err; exit 1; }
 python3 -c "
 import json
 d=json.load(open('$o/bench.json')); a=d['also']

@@ -9,7 +9,7 @@ rc=$?; echo "tests rc=$rc" > $o/tests.rc; tail -3 $o/tests.log
 grep -E "^(FAILED|ERROR)" $o/tests.log
 python -c "import __graft_entry__ as g; g.smoke()" > $o/smoke.log 2>&1 || { tail -5 $o/smoke.log; exit 1; }
 tail -1 $o/smoke.log
-python bench.py > $o/bench.json 2> $o/bench.err || { tail -5 $o/bench.err; exit 1; }
+python bench.py --full > $o/bench.json 2> $o/bench.err || { tail -5 $o/bench.err; exit 1; }
 python3 -c "
 import json
 d=json.load(open('$o/bench.json')); a=d['also']

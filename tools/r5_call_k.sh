@@ -7,7 +7,7 @@ timeout -k 10 600 python -m pytest tests/test_gpu_p2p.py tests/test_gpu_two_rank
 rc=$?; echo "tests rc=$rc" > $o/tests.rc; tail -3 $o/tests.log
 [ $rc -lt 2 ] || exit 1
 grep -E "^(FAILED|ERROR)" $o/tests.log
-python bench.py > $o/bench.json 2> $o/bench.err || { tail -5 $o/bench.err; exit 1; }
+python bench.py --full > $o/bench.json 2> $o/bench.err || { tail -5 $o/bench.err; exit 1; }
 python3 -c "
 import json
 d=json.load(open('$o/bench.json')); a=d['also']

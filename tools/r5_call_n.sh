@@ -22,7 +22,7 @@ d=json.load(open('$o/bench_p2p_w$w.json')); print('world', $w, 'ms', round(d['ms
 done
 bash tools/pmc.sh $o/pmc --workload c3 > $o/pmc_summary.txt 2> $o/pmc.err || { tail -5 $o/pmc.err; exit 1; }
 python3 tools/pmc_traffic.py $o/pmc c3 $o/pmc_traffic.json
-python bench.py > $o/bench.json 2> $o/bench.err || { tail -5 $o/bench.err; exit 1; }
+python bench.py --full > $o/bench.json 2> $o/bench.err || { tail -5 $o/bench.err; exit 1; }
 python3 -c "
 import json
 d=json.load(open('$o/bench.json')); print('C3', d['value'], d['ms_per_step'], d['roofline'], d['roofline_l2'])

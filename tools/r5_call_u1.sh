@@ -9,7 +9,7 @@ tail -1 $o/smoke.log
 timeout -k 10 1000 python -m pytest tests -m gpu -q > $o/tests_gpu.log 2>&1
 rc=$?; echo "gpu tests rc=$rc"; tail -3 $o/tests_gpu.log
 [ $rc -eq 0 ] || { grep -E "^(FAILED|ERROR)|Error" $o/tests_gpu.log | tail; exit 1; }
-( time python bench.py ) > $o/bench.json 2> $o/bench.err || { tail -5 $o/bench.err; exit 1; }
+( time python bench.py --full ) > $o/bench.json 2> $o/bench.err || { tail -5 $o/bench.err; exit 1; }
 tail -4 $o/bench.err
 python3 -c "
 import json

@@ -11,7 +11,7 @@ cp "$(find $out/shard_prof -name '*kernel_stats.csv' | head -1)" $out/${tag}_sha
 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 SPMF_BENCH_COMM=lib rocprofv3 --kernel-trace --stats --output-format csv -d $out/shard_prof1 -- python3 bench.py --gpus 1 --rows 125000 --steps 50 --warmup 5 --no-cpu-baseline --no-extras > $out/shard_1rank_bench.json 2> $out/shard_prof1.err || { tail -5 $out/shard_prof1.err; exit 1; }
 cp "$(find $out/shard_prof1 -name '*kernel_stats.csv' | head -1)" $out/${tag}_shard_1rank_rccl_kernel_stats.csv && rm -rf $out/shard_prof1
 for w in c4 c5 c2; do
-  python bench.py --workload $w > $out/bench_$w.json 2> $out/bench_$w.err || { tail -5 $out/bench_$w.err; exit 1; }
+  python bench.py --full --workload $w > $out/bench_$w.json 2> $out/bench_$w.err || { tail -5 $out/bench_$w.err; exit 1; }
   python -c "
 import json;d=json.load(open('$out/bench_$w.json'));print('$w', round(d['ms_per_step'],4), d['kernel_ms'], d['roofline'], d.get('also'))"
 done
