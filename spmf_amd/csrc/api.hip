@@ -62,12 +62,6 @@ struct spmf_ctx {
   float* est = nullptr;
   int64_t est_rows = 0;           // rows per chunk of the bound workspace
   int e_once = 1;                 // SPMF_DENSE_E_ONCE=0: recompute E in a second launch instead
-  int fuse_rows = -1;             // dense-term contexts: one fused row pass + dense-kernel epilogue instead of
-                                  // encode sweep -> dense -> stored-cell sweep.  -1 = where it measured faster:
-                                  // the sigmoid forms at KP = 32 (C5 row launches 0.97 -> 0.84 ms); NOT the exp
-                                  // decoder at KP = 64, where the two-stream fused kernel (20 spilled registers
-                                  // at four waves per SIMD) ran 13.9 ms against 12.8 for the two launches on C4
-                                  // (profiles/r04_fused_rows_c4.txt).  SPMF_FUSE_ROWS=1 / 0 forces it on / off.
   int dyn_rows = 1;               // the row pass hands the last eighth of its rows out dynamically (row_pass.hip);
                                   // SPMF_ROW_DYNAMIC=0: the fixed stride everywhere
   int dense3 = 1;                 // exp sums on the bf16 matrix cores with three-way split operands
@@ -196,7 +190,7 @@ static bool batched_draws(const spmf_ctx* c, int64_t rows, int S) {
 
 static int fail(spmf_ctx* c, int code, const std::string& msg);
 // a bf16x3 dense launcher answered "shape not covered": the dense term of the step would be missing from
-// gzs / gV' / the softplus sum -- fail instead (the use_* predicates below are meant to make this unreachable)
+// gzs / gV' / the softplus sum -- fail instead (dense_form below is meant to make this unreachable)
 static int dense3_uncovered(spmf_ctx* c) {
   return fail(c, SPMF_E_UNSUPPORTED, "data_pass: the bf16x3 dense kernels do not cover this launch shape "
       "(set SPMF_DENSE_BF16X3=0 for the exact-f32 kernels)");
@@ -217,32 +211,33 @@ static int64_t est_chunk_rows(const spmf_ctx* c, int64_t rows) {
   return rows < cap ? rows : cap;
 }
 
-// The bf16x3 form of the exp sums (dense3.hip) covers the Poisson exp decoder at KP = 64 and
-// recomputes E in its second launch.  The exact-f32 exp and sigmoid forms keep E (exp / sigmoid
-// of the logits) in HBM between their two contractions; Bernoulli + log_transform (code 4: E
-// would have to carry exp(X) too) recomputes.
-static bool uses_dense3(const spmf_ctx* c) {
-  return c->dense3 && likelihood_code(c) == 1 && c->KP == 64;
-}
-// The bf16x3 form of the sigmoid / softplus sums (dense3.hip sigdot3: Bernoulli and mixed contexts with the
-// linear decoder) at KP = 32 and 64; it recomputes the sigmoid in its second launch too.
-static bool uses_sig3(const spmf_ctx* c) {
+// Which dense form a context runs: the workspace carve (the E buffer) and the launch sequence of the row stage
+// (data_pass_impl, dense_rows) both follow this one answer.
+enum DenseForm {
+  kDenseNone,       // Poisson / linear decoder: closed-form dense term, one row pass
+  kDenseSig3Fused,  // Bernoulli / mixed with the linear decoder (dense3.hip sigdot3, ACT 1): ONE fused row pass,
+                    // the (Z, W) launch subtracts the dense row term from gzs in its epilogue
+  kDenseExp3,       // Poisson log_transform at KP = 64 on the bf16x3 exp kernels (dense3.hip expdot3)
+  kDenseSig3,       // KP = 32 on the sigdot3 family: Poisson log_transform (ACT 0, bin/factorize_scrnaseq_counts.py
+                    // runs P = 3) or Bernoulli + log_transform (ACT 2: exp accumulators as ACT 0, sigmoid / softplus
+                    // epilogue as ACT 1, E = sigmoid * exp)
+  kDenseEKept,      // exact-f32 MFMA kernels (dense.hip) keeping E in HBM between their two contractions
+  kDenseRecompute,  // exact-f32 MFMA kernels recomputing E in the second launch
+};
+// The bf16x3 forms recompute E (or the sigmoid) in their second launch.  The fused row pass is the sigmoid
+// forms' only (C5 row launches 0.97 -> 0.84 ms); the exp decoder keeps sweep 1 -> dense -> sweep 2, where the
+// fused two-stream row pass (20 spilled registers at four waves per SIMD) ran 13.9 ms against 12.8 for the two
+// launches on C4 (profiles/r04_fused_rows_c4.txt).  Bernoulli + log_transform (code 4: E would have to carry
+// exp(X) too) never keeps E.
+static DenseForm dense_form(const spmf_ctx* c) {
   const int lik = likelihood_code(c);
-  return c->dense3 && (lik == 2 || lik == 3) && (c->KP == 32 || c->KP == 64);
-}
-// The Poisson exp decoder at KP = 32 (K <= 32: the reference's scRNA script runs P = 3,
-// bin/factorize_scrnaseq_counts.py) on the bf16x3 form as well: dense3.hip's sigdot3 family with ACT 0.
-static bool uses_exp3_32(const spmf_ctx* c) {
-  return c->dense3 && likelihood_code(c) == 1 && c->KP == 32;
-}
-// Bernoulli + log_transform (code 4: logit = exp(<z, V'>) - 1 + phi, bernoulli.py:60-61) at KP = 32 on the same
-// family (ACT 2: exp accumulators as ACT 0, sigmoid / softplus epilogue as ACT 1, E = sigmoid * exp).
-static bool uses_sigexp3(const spmf_ctx* c) {
-  return c->dense3 && likelihood_code(c) == 4 && c->KP == 32;
-}
-static bool uses_e_buffer(const spmf_ctx* c) {
-  return (c->flags & (SPMF_FLAG_LOG_TRANSFORM | SPMF_FLAG_BERNOULLI | SPMF_FLAG_MIXED)) && c->e_once &&
-         likelihood_code(c) != 4 && !uses_dense3(c) && !uses_sig3(c) && !uses_exp3_32(c);
+  if (lik == 0) return kDenseNone;
+  if (c->dense3) {
+    if ((lik == 2 || lik == 3) && (c->KP == 32 || c->KP == 64)) return kDenseSig3Fused;
+    if (lik == 1 && c->KP == 64) return kDenseExp3;
+    if ((lik == 1 || lik == 4) && c->KP == 32) return kDenseSig3;
+  }
+  return c->e_once && lik != 4 ? kDenseEKept : kDenseRecompute;
 }
 
 // Q chunks (gridDim.y) of a P-stationary dense launch of nbx workgroup columns over ntiles Q tiles on
@@ -287,7 +282,7 @@ static Carve carve(const spmf_ctx* c, int64_t rows, int S) {
   k.gzs = o;   o += al(nd * (size_t)rows * KP * sizeof(float));
   k.gzd = o;   if (c->flags & (SPMF_FLAG_LOG_TRANSFORM | SPMF_FLAG_BERNOULLI | SPMF_FLAG_MIXED)) o += al((size_t)rows * KP * sizeof(float));
   k.est = o;
-  if (uses_e_buffer(c))
+  if (dense_form(c) == kDenseEKept)
     o += al((size_t)((D + 31) / 32) * 32 * (size_t)est_chunk_rows(c, rows) * sizeof(float));
   k.total = o;
   return k;
@@ -324,7 +319,6 @@ int spmf_ctx_create(int device, int K, int D, unsigned flags, spmf_ctx** out) {
   c->flags = flags;
   if (const char* e = getenv("SPMF_DENSE_E_ONCE")) c->e_once = e[0] != '0';
   if (const char* e = getenv("SPMF_DENSE_BF16X3")) c->dense3 = e[0] != '0';
-  if (const char* e = getenv("SPMF_FUSE_ROWS")) c->fuse_rows = e[0] != '0' ? 1 : 0;
   if (const char* e = getenv("SPMF_ROW_DYNAMIC")) c->dyn_rows = e[0] != '0' ? 1 : 0;
   *out = c;
   return SPMF_OK;
@@ -447,7 +441,7 @@ static int bind_ws(spmf_ctx* c, int64_t rows, int S) {
   c->z = (float*)(c->ws + k.z);
   c->gzs = (float*)(c->ws + k.gzs);
   c->gzd = (float*)(c->ws + k.gzd);
-  c->est = uses_e_buffer(c) ? (float*)(c->ws + k.est) : nullptr;
+  c->est = dense_form(c) == kDenseEKept ? (float*)(c->ws + k.est) : nullptr;
   c->est_rows = est_chunk_rows(c, rows);
   c->ws_rows = rows;
   c->ws_S = S;
@@ -602,6 +596,147 @@ int spmf_ctx_set_deterministic(spmf_ctx* c, void* scratch, size_t bytes) {
   return SPMF_OK;
 }
 
+// spmf_prior_async, spmf_finish and the step: the finish kernels' arguments without the data half's (acc, dprep,
+// n_nonfinite, B_global, lgamma_sum, acc_stride: the callers that launch it set them)
+static FinishArgs finish_args(const spmf_ctx* c, int S, double prior_weight, const float* const* params,
+    const float* eta, float* const* grads, double* parts) {
+  FinishArgs fa{c->D, c->K, 0, 0.0, c->u_tau_scale, c->s_tau_scale, c->decay, prior_weight, nullptr, nullptr, params,
+      eta, grads, parts, nullptr, likelihood_code(c), c->ctype, c->Dh, S, 0, {},
+      (c->flags & SPMF_FLAG_ABS_HORSESHOE) ? 1 : 0, c->fpart, c->futau};
+  for (int i = 0; i < SPMF_NVARS; ++i) fa.vstride[i] = (int64_t)var_size(c, i);
+  return fa;
+}
+
+// The row stage of one draw of a context with a dense term (form != kDenseNone): the row pass(es) and the two
+// dense launches.  `ra` holds what the row launches share (mode 0, the packed stream, the dynamic tail).
+static int dense_rows(spmf_ctx* c, const spmf_counts* ct, DenseForm form, RowArgs ra, float* acc, const AccLayout& L,
+    bool tm, hipStream_t st) {
+  const int KP = c->KP, lik = ra.logt, B = (int)ct->n_rows;
+  double* dacc = ra.dacc;
+  const bool fused = form == kDenseSig3Fused;
+  RowArgs r1 = ra;
+  if (fused) {
+    // both sweeps read the same counts: ONE row pass (mode 3 leaves xi_b (gz_b - [veta] - z_b) in gzs) and the
+    // (Z, W) launch subtracts the dense row term in its epilogue, gzs_b -= xi_b sum_d sigmoid(l_bd) V'_d, instead
+    // of encode-only sweep -> dense -> stored-cell sweep (two row launches re-stream the entries and pass z
+    // through HBM: DESIGN section 4)
+    r1.mode = 3;
+  } else {
+    // z from g(x) (exp decoders) or the counts (sweep 1); the stored-cell terms with the dense row term follow
+    // the dense launches (sweep 2)
+    r1.mode = 1;
+    r1.dyn_tail = 0;   // (the encode-only launch never touches the counters: sweep 2 has them alone)
+    if (lik_exp(lik)) {
+      r1.val = ct->gval;
+      r1.ent = nullptr;
+    }
+  }
+  launch_row_pass(KP, r1, st);
+  if (tm) HIPCHK(c, hipEventRecord(c->ev[6], st));
+  const int act = lik == 4 ? 2 : (lik >= 2 ? 1 : 0);   // dense.hip / dense3.hip ACT
+  const float* lbias = lik == 3 ? c->dbias : c->phi;   // mixed: -1e30 masks the Poisson columns
+  float* gVp = acc + L.gV_off(0);
+  float* gphi_acc = acc + L.gphi_off(0);
+  // mixed likelihood with the Bernoulli column list set: the dense sums run over those
+  // columns only (compacted V' rows), instead of over all D with the Poisson half masked
+  const float* Wd = c->Vp;
+  int Dd = c->D;
+  const int32_t* orows = nullptr;
+  if (lik == 3 && c->bcols && c->n_bcols > 0) {
+    launch_compact_rows(c->n_bcols, KP, c->bcols, c->Vp, c->phi, c->Vb, c->bb, st);
+    Wd = c->Vb;
+    Dd = c->n_bcols;
+    lbias = c->bb;
+    orows = c->bcols;
+  }
+  switch (form) {
+    case kDenseExp3: {
+      // E is recomputed by the second launch (at this matrix rate a B*D*4-byte round trip through HBM would be
+      // the bound)
+      ExpdotArgs ez{B, Dd, c->z, Wd, c->gzd, 1.f, dacc + 3, 1, 0, 0, nullptr, nullptr, nullptr, nullptr};
+      if (!launch_expdot3(KP, ez, st)) return dense3_uncovered(c);   // gzd_b = sum_d E_bd V'_d ; dacc[3] = sum E
+      // Q chunks of the W-stationary launch: whole rounds of the resident workgroups (one 110 KB
+      // workgroup per CU: 118 column blocks x 13 chunks = 6 rounds of 256 on C4; 5 chunks = 590
+      // workgroups ran 2.3 rounds, the last one a third full)
+      const int ch3 = pick_chunks((Dd + expdot3_rows_per_wg() - 1) / expdot3_rows_per_wg(), (B + 127) / 128,
+                                  256 * expdot3_wgs_per_cu(), 64);
+      ExpdotArgs ew{Dd, B, Wd, c->z, gVp, -1.f, nullptr, ch3, 1, 0, nullptr, nullptr, nullptr, nullptr};
+      if (!launch_expdot3(KP, ew, st)) return dense3_uncovered(c);   // gV'_d -= sum_b E_bd z_b
+      break;
+    }
+    case kDenseSig3Fused:
+    case kDenseSig3: {
+      // Two waves per SIMD by registers: chunk counts that fill whole rounds of the resident workgroups.
+      const int zt = (Dd + 127) / 128, wt = (B + 127) / 128;
+      const int rpw = sigdot3_rows_per_wg(KP), slots = 256 * sigdot3_wgs_per_cu(KP);
+      const int zc = pick_chunks((B + rpw - 1) / rpw, zt, slots, 16), wc = pick_chunks((Dd + rpw - 1) / rpw, wt, slots, 256);
+      // (Z, W), the bias on the Q rows: fused, gzs_b -= xi_b sum_d E_bd V'_d; else gzd_b = sum_d E_bd V'_d for
+      // sweep 2.  dacc[3] = sum E (ACT 0) or sum softplus(l) (ACT 1, 2); E = exp, sigmoid, or sigmoid * exp
+      if (!fused && zc > 1) launch_zero(c->gzd, (size_t)B * KP * sizeof(float), st);
+      ExpdotArgs ez{B, Dd, c->z, Wd, fused ? c->gzs : c->gzd, fused ? -1.f : 1.f, dacc + 3, zc, zc > 1 ? 1 : 0, act,
+          nullptr, act ? lbias : nullptr, nullptr, nullptr};
+      if (act) ez.e_planes = 3;   // V' rows have mixed signs under the Normal priors: third plane of E
+      if (fused) {
+        ez.accumulate = 1;
+        ez.p_scale = ra.row_scale;
+      }
+      if (!launch_sigdot3(KP, ez, st)) return dense3_uncovered(c);
+      // (W, Z), the bias on the P rows: gV'_d -= sum_b E_bd z_b ; gphi_d -= sum_b sigmoid(l_bd) (ACT 1, 2)
+      ExpdotArgs ew{Dd, B, Wd, c->z, gVp, -1.f, nullptr, wc, 1, act, act ? lbias : nullptr, nullptr,
+          act ? gphi_acc : nullptr, orows};
+      if (!launch_sigdot3(KP, ew, st)) return dense3_uncovered(c);
+      break;
+    }
+    case kDenseEKept: {
+      // E once: per row chunk, the Z-stationary kernel keeps E (exp, or the sigmoid of the
+      // Bernoulli logits) and the second contraction (gV'_d -= sum_b E_bd z_b; Bernoulli:
+      // gphi_d -= sum_b E_bd too) reads it back instead of recomputing it
+      // (chunks of equal size, whole 128-row workgroups: a short last chunk would run the
+      //  chip half empty)
+      const int64_t nch = (ct->n_rows + c->est_rows - 1) / c->est_rows;
+      int64_t step = ((ct->n_rows + nch - 1) / nch + 127) / 128 * 128;
+      if (step > c->est_rows) step = c->est_rows;
+      for (int64_t r0 = 0; r0 < ct->n_rows; r0 += step) {
+        const int nr = (int)((ct->n_rows - r0) < step ? (ct->n_rows - r0) : step);
+        ExpdotArgs ez{nr, Dd, c->z + (size_t)r0 * KP, Wd, c->gzd + (size_t)r0 * KP, 1.f, dacc + 3, 1, 0, act,
+            nullptr, act ? lbias : nullptr, nullptr, nullptr, c->est, (int64_t)nr};
+        launch_expdot(KP, ez, st);
+        launch_estdot(KP, Dd, nr, (int64_t)nr, c->est, c->z + (size_t)r0 * KP, gVp, -1.f,
+                      act ? gphi_acc : nullptr, orows, st);
+      }
+      break;
+    }
+    case kDenseRecompute: {
+      // Z-stationary: Q rows are columns d -> bias_q = phi (Bernoulli logits)
+      ExpdotArgs ez{B, Dd, c->z, Wd, c->gzd, 1.f, dacc + 3, 1, 0, act, nullptr, act ? lbias : nullptr, nullptr,
+          nullptr};
+      launch_expdot(KP, ez, st);   // gzd_b = sum_d E_bd V'_d ; dacc[3] = sum E (or sum softplus)
+      // W-stationary launch has only D/128 workgroups: split the row (Q) range
+      // into chunks until ~4 workgroups per CU are in flight
+      const int nbx = (Dd + 127) / 128;
+      const int qtiles = (B + 127) / 128;
+      int chunks = (1024 + nbx - 1) / nbx;
+      if (chunks > qtiles) chunks = qtiles;
+      if (chunks < 1) chunks = 1;
+      // W-stationary: P rows are columns d -> bias_p = phi; Bernoulli also needs the
+      // column sums of sigmoid for d/dphi (subtracted from the gphi accumulators)
+      ExpdotArgs ew{Dd, B, Wd, c->z, gVp, -1.f, nullptr, chunks, 1, act, act ? lbias : nullptr, nullptr,
+          act ? gphi_acc : nullptr, orows};
+      launch_expdot(KP, ew, st);   // gV'_d -= sum_b E_bd z_b
+      break;
+    }
+    case kDenseNone:
+      break;
+  }
+  if (tm) HIPCHK(c, hipEventRecord(c->ev[7], st));
+  if (!fused) {
+    ra.mode = 2;
+    ra.gzd = c->gzd;
+    launch_row_pass(KP, ra, st);
+  }
+  return SPMF_OK;
+}
+
 // parts: bit 0 = zero, prep, row pass and the column pass of the lower column half (all columns
 // without a split); bit 1 = column pass of the upper half and the fp64 pack
 static int data_pass_impl(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS],
@@ -610,6 +745,7 @@ static int data_pass_impl(spmf_ctx* c, const spmf_counts* ct, int S, const float
   if (!so) c->step.active = 0;   // a plain data pass ends a step begun earlier
   // likelihood / decoder code of the kernels: 0 Poisson linear, 1 Poisson log_transform, 2 Bernoulli
   const int logt = likelihood_code(c);
+  const DenseForm form = dense_form(c);
   int rc = check_counts(c, ct);
   if (!rc && logt == 3 && !c->ctype) rc = fail(c, SPMF_E_ARG,
       "mixed likelihood: spmf_ctx_set_column_types was not called");
@@ -656,232 +792,47 @@ static int data_pass_impl(spmf_ctx* c, const spmf_counts* ct, int S, const float
     float* acc = c->acc + (size_t)s * al_;
     double* dacc = c->dacc + (size_t)s * dacc_stride;
     double* dprep = c->dprep + (size_t)s * kPrepSeg * (KP + 1);
-    float* gVp = acc + L.gV_off(0);
     bool packed = false;
     if (first) {
-    if (tm) HIPCHK(c, hipEventRecord(c->ev[0], st));
-    PrepArgs pa{D, c->K, params[2] + s * var_size(c, 2), params[0] + s * var_size(c, 0), params[1] + s * var_size(c,
-        1), params[7] + s * var_size(c, 7), eta, c->Ap, c->Vp, c->phi, dprep, lik_exp(logt) ? 1 : 0,
-        logt == 3 ? c->ctype : nullptr, logt == 3 ? c->dbias : nullptr, nbat};
-    if (s == 0) {
-      pa.zero_p = c->acc;
-      pa.zero_bytes = (size_t)((char*)c->dprep - (char*)c->acc);
-    }
-    if (so && nbat == S) {
-      // spmf_step_begin with every draw in this launch: the prior half of the finish (all twelve prior
-      // log-densities and prior_weight * d prior / d theta: parameters only) runs in the prep launch
-      const bool hsf = (c->flags & SPMF_FLAG_ABS_HORSESHOE) != 0;
-      FinishArgs fa{D, c->K, 0, 0.0, c->u_tau_scale, c->s_tau_scale, c->decay, so->prior_weight, nullptr, nullptr,
-          so->params, so->eta, so->grads, so->parts, nullptr, logt, c->ctype, c->Dh, S, 0, {}, hsf ? 1 : 0,
-          c->fpart, c->futau};
-      for (int i = 0; i < SPMF_NVARS; ++i) fa.vstride[i] = (int64_t)var_size(c, i);
-      launch_step_begin(KP, pa, fa, st);
-      so->fused = 1;
-    } else {
-      launch_prep(KP, pa, st);
-    }
-    if (tm) HIPCHK(c, hipEventRecord(c->ev[1], st));
-    const float* rscale = (c->flags & SPMF_FLAG_SCALE_ROWS) ? ct->row_scale : nullptr;
-    if (ct->n_rows > 0 && !logt) {
-      RowArgs ra{ct->n_rows, ct->row_ptr, ct->col_idx, ct->val, rscale, c->Ap, c->Vp, c->phi, dprep, c->z, c->gzs,
-          dacc, 0, 0, nullptr, nullptr, nbat, D, dacc_stride};
-      ra.ent = ct->ent;
-      ra.dyn_tail = c->dyn_rows;
-      if (det) {
-        ra.det_slots = (double*)(c->det_buf + (size_t)s * det_draw);
-        ra.det_stride = (int64_t)(det_draw / sizeof(double));
+      if (tm) HIPCHK(c, hipEventRecord(c->ev[0], st));
+      PrepArgs pa{D, c->K, params[2] + s * var_size(c, 2), params[0] + s * var_size(c, 0), params[1] + s * var_size(c,
+          1), params[7] + s * var_size(c, 7), eta, c->Ap, c->Vp, c->phi, dprep, lik_exp(logt) ? 1 : 0,
+          logt == 3 ? c->ctype : nullptr, logt == 3 ? c->dbias : nullptr, nbat};
+      if (s == 0) {
+        pa.zero_p = c->acc;
+        pa.zero_bytes = (size_t)((char*)c->dprep - (char*)c->acc);
       }
-      launch_row_pass(KP, ra, st);
-    } else if (ct->n_rows > 0 && uses_sig3(c) && c->fuse_rows != 0) {
-      // (SPMF_FUSE_ROWS=0: the three-launch flow below, sweep 1 -> sigdot3 -> sweep 2)
-      // Bernoulli / mixed columns with the linear decoder on the bf16x3 sigmoid kernels: ONE fused row
-      // pass (both sweeps read the same counts; mode 3 leaves xi_b (gz_b - [veta] - z_b) in gzs), then
-      // the (Z, W) launch subtracts the dense row term in its epilogue, gzs_b -= xi_b sum_d sigmoid(l_bd) V'_d,
-      // instead of encode-only sweep -> dense -> stored-cell sweep (two row launches re-stream the
-      // entries and pass z through HBM: DESIGN section 4)
-      RowArgs rf{ct->n_rows, ct->row_ptr, ct->col_idx, ct->val, rscale, c->Ap, c->Vp, c->phi, dprep, c->z, c->gzs,
-          dacc, 3, logt, nullptr, c->ctype, 1, D, dacc_stride};
-      rf.ent = ct->ent;
-      rf.dyn_tail = c->dyn_rows;
-      launch_row_pass(KP, rf, st);
-      if (tm) HIPCHK(c, hipEventRecord(c->ev[6], st));
-      const float* lbias = logt == 3 ? c->dbias : c->phi;   // mixed: -1e30 masks the Poisson columns
-      float* gphi_acc = acc + L.gphi_off(0);
-      const bool compact = logt == 3 && c->bcols && c->n_bcols > 0;
-      const float* Wd = c->Vp;
-      int Dd = D;
-      const int32_t* orows = nullptr;
-      if (compact) {
-        launch_compact_rows(c->n_bcols, KP, c->bcols, c->Vp, c->phi, c->Vb, c->bb, st);
-        Wd = c->Vb;
-        Dd = c->n_bcols;
-        lbias = c->bb;
-        orows = c->bcols;
-      }
-      // Two waves per SIMD by registers: chunk counts that fill whole rounds of the resident workgroups.
-      const int zt = (Dd + 127) / 128, wt = (int)((ct->n_rows + 127) / 128);
-      const int rpw = sigdot3_rows_per_wg(KP), slots = 256 * sigdot3_wgs_per_cu(KP);
-      const int znb = (int)((ct->n_rows + rpw - 1) / rpw), wnb = (Dd + rpw - 1) / rpw;
-      const int zc = pick_chunks(znb, zt, slots, 16), wc = pick_chunks(wnb, wt, slots, 256);
-      ExpdotArgs ez{(int)ct->n_rows, Dd, c->z, Wd, c->gzs, -1.f, dacc + 3, zc, zc > 1 ? 1 : 0, 1, nullptr, lbias,
-          nullptr, nullptr};
-      ez.e_planes = 3;              // V' rows have mixed signs under the Normal priors: third plane of E
-      ez.accumulate = 1;
-      ez.p_scale = rscale;
-      if (!launch_sigdot3(KP, ez, st)) return dense3_uncovered(c);   // gzs_b -= xi_b sum_d sigmoid(l_bd) V'_d ; dacc[3] = sum softplus
-      ExpdotArgs ew{Dd, (int)ct->n_rows, Wd, c->z, gVp, -1.f, nullptr, wc, 1, 1, lbias, nullptr, gphi_acc, orows};
-      if (!launch_sigdot3(KP, ew, st)) return dense3_uncovered(c);   // gV'_d -= sum_b sigmoid z_b ; gphi_d -= sum_b sigmoid
-      if (tm) HIPCHK(c, hipEventRecord(c->ev[7], st));
-    } else if (ct->n_rows > 0 && [&]() {
-      // Poisson log_transform on the bf16x3 exp kernels with a packed entry stream: ONE fused row pass
-      // too -- sweep 1 reads g(x) (counts.gval), sweep 2 takes the count out of the packed word
-      // (RowArgs.dual: the register cost of the canonical (col, val) pair) -- and the (Z, W) launch
-      // subtracts xi_b sum_d E_bd V'_d from gzs in its epilogue.  Only the LDS-phi launch shapes
-      // have the two-stream form: false = nothing was launched, take the three-launch flow below.
-      if (!uses_dense3(c) || !ct->ent || !ct->gval || c->fuse_rows != 1) return false;
-      RowArgs rf{ct->n_rows, ct->row_ptr, ct->col_idx, ct->gval, rscale, c->Ap, c->Vp, c->phi, dprep, c->z, c->gzs,
-          dacc, 3, logt, nullptr, c->ctype, 1, D, dacc_stride};
-      rf.ent = ct->ent;
-      rf.dual = 1;
-      return launch_row_pass(KP, rf, st);
-    }()) {
-      if (tm) HIPCHK(c, hipEventRecord(c->ev[6], st));
-      ExpdotArgs ez{(int)ct->n_rows, D, c->z, c->Vp, c->gzs, -1.f, dacc + 3, 1, 0, 0, nullptr, nullptr, nullptr, nullptr};
-      ez.accumulate = 1;
-      ez.p_scale = rscale;
-      if (!launch_expdot3(KP, ez, st)) return dense3_uncovered(c);   // gzs_b -= xi_b sum_d E_bd V'_d ; dacc[3] = sum E
-      const int ch3 = pick_chunks((D + expdot3_rows_per_wg() - 1) / expdot3_rows_per_wg(),
-                                  (int)((ct->n_rows + 127) / 128), 256 * expdot3_wgs_per_cu(), 64);
-      ExpdotArgs ew{D, (int)ct->n_rows, c->Vp, c->z, gVp, -1.f, nullptr, ch3, 1, 0, nullptr, nullptr, nullptr, nullptr};
-      if (!launch_expdot3(KP, ew, st)) return dense3_uncovered(c);   // gV'_d -= sum_b E_bd z_b
-      if (tm) HIPCHK(c, hipEventRecord(c->ev[7], st));
-    } else if (ct->n_rows > 0) {
-      // log_transform: z from g(x) (sweep 1), dense exp terms on the matrix
-      // cores, then the stored-cell terms (sweep 2) with the dense row term.
-      RowArgs r1{ct->n_rows, ct->row_ptr, ct->col_idx, lik_exp(logt) ? ct->gval : ct->val, rscale, c->Ap, c->Vp, c->phi,
-          dprep, c->z, c->gzs, dacc, 1, logt, nullptr, c->ctype, 1, D, dacc_stride};
-      if (!lik_exp(logt)) r1.ent = ct->ent;   // (the exp encoders read g(x), not the counts)
-      launch_row_pass(KP, r1, st);
-      if (tm) HIPCHK(c, hipEventRecord(c->ev[6], st));
-      const int act = logt == 4 ? 2 : (logt >= 2 ? 1 : 0);   // dense.hip ACT
-      const float* lbias = logt == 3 ? c->dbias : c->phi;   // mixed: -1e30 masks the Poisson columns
-      float* gphi_acc = acc + L.gphi_off(0);
-      // mixed likelihood with the Bernoulli column list set: the dense sums run over those
-      // columns only (compacted V' rows), instead of over all D with the Poisson half masked
-      const bool compact = logt == 3 && c->bcols && c->n_bcols > 0;
-      const float* Wd = c->Vp;
-      int Dd = D;
-      const int32_t* orows = nullptr;
-      if (compact) {
-        launch_compact_rows(c->n_bcols, KP, c->bcols, c->Vp, c->phi, c->Vb, c->bb, st);
-        Wd = c->Vb;
-        Dd = c->n_bcols;
-        lbias = c->bb;
-        orows = c->bcols;
-      }
-      if (uses_dense3(c) && !compact) {
-        // bf16x3: E is recomputed by the second launch (at this matrix rate a B*D*4-byte round
-        // trip through HBM would be the bound)
-        ExpdotArgs ez{(int)ct->n_rows, Dd, c->z, Wd, c->gzd, 1.f, dacc + 3, 1, 0, 0, nullptr, nullptr, nullptr,
-            nullptr};
-        if (!launch_expdot3(KP, ez, st)) return dense3_uncovered(c);   // gzd_b = sum_d E_bd V'_d ; dacc[3] = sum E
-        // Q chunks of the W-stationary launch: whole rounds of the resident workgroups (one 110 KB
-        // workgroup per CU: 118 column blocks x 13 chunks = 6 rounds of 256 on C4; 5 chunks = 590
-        // workgroups ran 2.3 rounds, the last one a third full)
-        const int ch3 = pick_chunks((Dd + expdot3_rows_per_wg() - 1) / expdot3_rows_per_wg(),
-                                    (int)((ct->n_rows + 127) / 128), 256 * expdot3_wgs_per_cu(), 64);
-        ExpdotArgs ew{Dd, (int)ct->n_rows, Wd, c->z, gVp, -1.f, nullptr, ch3, 1, 0, nullptr, nullptr, nullptr,
-            nullptr};
-        if (!launch_expdot3(KP, ew, st)) return dense3_uncovered(c);   // gV'_d -= sum_b E_bd z_b
-      } else if (uses_exp3_32(c) && !compact) {
-        // the same two launches at K padded to 32 (sigdot3 family, ACT 0); chunk counts that fill whole
-        // rounds of the resident workgroups
-        const int zt = (Dd + 127) / 128, wt = (int)((ct->n_rows + 127) / 128);
-        const int rpw = sigdot3_rows_per_wg(KP), slots = 256 * sigdot3_wgs_per_cu(KP);
-        const int zc = pick_chunks((int)((ct->n_rows + rpw - 1) / rpw), zt, slots, 16);
-        const int wc = pick_chunks((Dd + rpw - 1) / rpw, wt, slots, 256);
-        if (zc > 1) launch_zero(c->gzd, (size_t)ct->n_rows * KP * sizeof(float), st);
-        ExpdotArgs ez{(int)ct->n_rows, Dd, c->z, Wd, c->gzd, 1.f, dacc + 3, zc, zc > 1 ? 1 : 0, 0, nullptr, nullptr,
-            nullptr, nullptr};
-        if (!launch_sigdot3(KP, ez, st)) return dense3_uncovered(c);   // gzd_b = sum_d E_bd V'_d ; dacc[3] = sum E ; dacc[4]: saturation
-        ExpdotArgs ew{Dd, (int)ct->n_rows, Wd, c->z, gVp, -1.f, nullptr, wc, 1, 0, nullptr, nullptr, nullptr, nullptr};
-        if (!launch_sigdot3(KP, ew, st)) return dense3_uncovered(c);   // gV'_d -= sum_b E_bd z_b
-      } else if (uses_sig3(c)) {
-        // the sigmoid / softplus sums on the bf16x3 kernels without the fused row pass (SPMF_FUSE_ROWS=0):
-        // (Z, W) writes gzd_b = sum_d sigmoid(l_bd) V'_d for the stored-cell sweep, (W, Z) as in the fused flow
-        const int zt = (Dd + 127) / 128, wt = (int)((ct->n_rows + 127) / 128);
-        const int rpw = sigdot3_rows_per_wg(KP), slots = 256 * sigdot3_wgs_per_cu(KP);
-        const int zc = pick_chunks((int)((ct->n_rows + rpw - 1) / rpw), zt, slots, 16);
-        const int wc = pick_chunks((Dd + rpw - 1) / rpw, wt, slots, 256);
-        if (zc > 1) launch_zero(c->gzd, (size_t)ct->n_rows * KP * sizeof(float), st);
-        ExpdotArgs ez{(int)ct->n_rows, Dd, c->z, Wd, c->gzd, 1.f, dacc + 3, zc, zc > 1 ? 1 : 0, 1, nullptr, lbias,
-            nullptr, nullptr};
-        ez.e_planes = 3;
-        if (!launch_sigdot3(KP, ez, st)) return dense3_uncovered(c);
-        ExpdotArgs ew{Dd, (int)ct->n_rows, Wd, c->z, gVp, -1.f, nullptr, wc, 1, 1, lbias, nullptr, gphi_acc, orows};
-        if (!launch_sigdot3(KP, ew, st)) return dense3_uncovered(c);
-      } else if (uses_sigexp3(c) && !compact) {
-        // Bernoulli + log_transform at K padded to 32: (Z, W) with the bias on the Q rows, the softplus sum and
-        // three planes of E = sigmoid exp (V' has mixed signs), (W, Z) with the bias on the P rows and the
-        // sigmoid row sums for d/dphi
-        const int zt = (Dd + 127) / 128, wt = (int)((ct->n_rows + 127) / 128);
-        const int rpw = sigdot3_rows_per_wg(KP), slots = 256 * sigdot3_wgs_per_cu(KP);
-        const int zc = pick_chunks((int)((ct->n_rows + rpw - 1) / rpw), zt, slots, 16);
-        const int wc = pick_chunks((Dd + rpw - 1) / rpw, wt, slots, 256);
-        if (zc > 1) launch_zero(c->gzd, (size_t)ct->n_rows * KP * sizeof(float), st);
-        ExpdotArgs ez{(int)ct->n_rows, Dd, c->z, Wd, c->gzd, 1.f, dacc + 3, zc, zc > 1 ? 1 : 0, 2, nullptr, lbias,
-            nullptr, nullptr};
-        ez.e_planes = 3;
-        if (!launch_sigdot3(KP, ez, st)) return dense3_uncovered(c);   // gzd_b = sum_d sigmoid(l) exp(X) V'_d ; dacc[3] = sum softplus(l)
-        ExpdotArgs ew{Dd, (int)ct->n_rows, Wd, c->z, gVp, -1.f, nullptr, wc, 1, 2, lbias, nullptr, gphi_acc, orows};
-        if (!launch_sigdot3(KP, ew, st)) return dense3_uncovered(c);   // gV'_d -= sum_b E_bd z_b ; gphi_d -= sum_b sigmoid(l)
-      } else if (c->est && act != 2) {   // (act 2: E carries exp(X) too, its row sums are not the d/dphi sums)
-        // E once: per row chunk, the Z-stationary kernel keeps E (exp, or the sigmoid of the
-        // Bernoulli logits) and the second contraction (gV'_d -= sum_b E_bd z_b; Bernoulli:
-        // gphi_d -= sum_b E_bd too) reads it back instead of recomputing it
-        // (chunks of equal size, whole 128-row workgroups: a short last chunk would run the
-        //  chip half empty)
-        const int64_t nch = (ct->n_rows + c->est_rows - 1) / c->est_rows;
-        int64_t step = ((ct->n_rows + nch - 1) / nch + 127) / 128 * 128;
-        if (step > c->est_rows) step = c->est_rows;
-        for (int64_t r0 = 0; r0 < ct->n_rows; r0 += step) {
-          const int nr = (int)((ct->n_rows - r0) < step ? (ct->n_rows - r0) : step);
-          ExpdotArgs ez{nr, Dd, c->z + (size_t)r0 * KP, Wd, c->gzd + (size_t)r0 * KP, 1.f, dacc + 3, 1, 0, act,
-              nullptr, act ? lbias : nullptr, nullptr, nullptr, c->est, (int64_t)nr};
-          launch_expdot(KP, ez, st);
-          launch_estdot(KP, Dd, nr, (int64_t)nr, c->est, c->z + (size_t)r0 * KP, gVp, -1.f,
-                        act ? gphi_acc : nullptr, orows, st);
-        }
+      if (so && nbat == S) {
+        // spmf_step_begin with every draw in this launch: the prior half of the finish (all twelve prior
+        // log-densities and prior_weight * d prior / d theta: parameters only) runs in the prep launch
+        launch_step_begin(KP, pa, finish_args(c, S, so->prior_weight, so->params, so->eta, so->grads, so->parts), st);
+        so->fused = 1;
       } else {
-      // Z-stationary: Q rows are columns d -> bias_q = phi (Bernoulli logits)
-      ExpdotArgs ez{(int)ct->n_rows, Dd, c->z, Wd, c->gzd, 1.f, dacc + 3, 1, 0, act, nullptr,
-          act ? lbias : nullptr, nullptr, nullptr};
-      launch_expdot(KP, ez, st);   // gzd_b = sum_d E_bd V'_d ; dacc[3] = sum E (or sum softplus)
-      // W-stationary launch has only D/128 workgroups: split the row (Q) range
-      // into chunks until ~4 workgroups per CU are in flight
-      const int nbx = (Dd + 127) / 128;
-      const int qtiles = (int)((ct->n_rows + 127) / 128);
-      int chunks = (1024 + nbx - 1) / nbx;
-      if (chunks > qtiles) chunks = qtiles;
-      if (chunks < 1) chunks = 1;
-      // W-stationary: P rows are columns d -> bias_p = phi; Bernoulli also needs the
-      // column sums of sigmoid for d/dphi (subtracted from the gphi accumulators)
-      ExpdotArgs ew{Dd, (int)ct->n_rows, Wd, c->z, gVp, -1.f, nullptr, chunks, 1, act, act ? lbias : nullptr,
-          nullptr, act ? gphi_acc : nullptr, orows};
-      launch_expdot(KP, ew, st);   // gV'_d -= sum_b E_bd z_b
+        launch_prep(KP, pa, st);
       }
-      if (tm) HIPCHK(c, hipEventRecord(c->ev[7], st));
-      RowArgs r2{ct->n_rows, ct->row_ptr, ct->col_idx, ct->val, rscale, c->Ap, c->Vp, c->phi, dprep, c->z, c->gzs,
-          dacc, 2, logt, c->gzd, c->ctype, 1, D, dacc_stride};
-      r2.ent = ct->ent;
-      r2.dyn_tail = c->dyn_rows;   // (the encode-only launch above never touches the counters: this one has them alone)
-      launch_row_pass(KP, r2, st);
+      if (tm) HIPCHK(c, hipEventRecord(c->ev[1], st));
+      if (ct->n_rows > 0) {
+        RowArgs ra{ct->n_rows, ct->row_ptr, ct->col_idx, ct->val,
+            (c->flags & SPMF_FLAG_SCALE_ROWS) ? ct->row_scale : nullptr, c->Ap, c->Vp, c->phi, dprep, c->z, c->gzs,
+            dacc, 0, logt, nullptr, c->ctype, nbat, D, dacc_stride};
+        ra.ent = ct->ent;
+        ra.dyn_tail = c->dyn_rows;
+        if (form != kDenseNone) {
+          rc = dense_rows(c, ct, form, ra, acc, L, tm, st);
+          if (rc) return rc;
+        } else {
+          if (det) {
+            ra.det_slots = (double*)(c->det_buf + (size_t)s * det_draw);
+            ra.det_stride = (int64_t)(det_draw / sizeof(double));
+          }
+          launch_row_pass(KP, ra, st);
+        }
+      }
+      if (tm) HIPCHK(c, hipEventRecord(c->ev[2], st));
+      // the caller's marker "the row stage of the last draw has been issued": what it makes wait for this event
+      // runs beside the column pass instead of beside the resident-set row launch (spmf_ctx_set_rows_event)
+      if (c->rows_event && s + nbat == S) HIPCHK(c, hipEventRecord(c->rows_event, st));
     }
-    if (tm) HIPCHK(c, hipEventRecord(c->ev[2], st));
-    // the caller's marker "the row stage of the last draw has been issued": what it makes wait for this event
-    // runs beside the column pass instead of beside the resident-set row launch (spmf_ctx_set_rows_event)
-    if (c->rows_event && s + nbat == S) HIPCHK(c, hipEventRecord(c->rows_event, st));
-    }   // first
     if (ct->n_rows > 0 && ct->nnz > 0) {
       for (int hf = 0; hf < 2; ++hf) {
         if (!(hf == 0 ? first : second)) continue;
@@ -974,13 +925,33 @@ int spmf_acc_split(const spmf_ctx* c, int64_t off[2], int64_t len[2]) {
 }
 
 
-int spmf_prior_async(spmf_ctx* c, int S, double prior_weight, const float* const params[SPMF_NVARS],
-    const float* eta, double* parts, float* const grads[SPMF_NVARS], void* stream) {
-  if (!c || !params || !grads || !eta || !parts || S < 1) return fail(c, SPMF_E_ARG, "prior_async: bad arguments");
+// all twelve params / grads non-null; with ABS_HORSESHOE only v, w, u, s (0, 1, 2, 7) are used
+static int check_params_grads(spmf_ctx* c, const char* fn, const float* const params[SPMF_NVARS],
+    float* const grads[SPMF_NVARS]) {
   const bool hsf = (c->flags & SPMF_FLAG_ABS_HORSESHOE) != 0;
   for (int i = 0; i < SPMF_NVARS; ++i)
     if ((!params[i] || !grads[i]) && !(hsf && i != 0 && i != 1 && i != 2 && i != 7))
-      return fail(c, SPMF_E_ARG, "prior_async: params/grads must be non-null (all 12; v,w,u,s with ABS_HORSESHOE)");
+      return fail(c, SPMF_E_ARG, std::string(fn) +
+          ": params/grads must be non-null (all 12; v,w,u,s with ABS_HORSESHOE)");
+  return SPMF_OK;
+}
+
+// the timing tap behind the step's last launch: the event set is complete once the data pass recorded its part
+static int timing_close(spmf_ctx* c, hipStream_t st) {
+  if (!c->timing) return SPMF_OK;
+  HIPCHK(c, hipEventRecord(c->ev[5], st));
+  if (c->ev_valid == 1) {
+    c->ev_valid = 3;
+    c->ev_count++;
+  }
+  return SPMF_OK;
+}
+
+int spmf_prior_async(spmf_ctx* c, int S, double prior_weight, const float* const params[SPMF_NVARS],
+    const float* eta, double* parts, float* const grads[SPMF_NVARS], void* stream) {
+  if (!c || !params || !grads || !eta || !parts || S < 1) return fail(c, SPMF_E_ARG, "prior_async: bad arguments");
+  int rc = check_params_grads(c, "prior_async", params, grads);
+  if (rc) return rc;
   if (!c->fpart) return fail(c, SPMF_E_WORKSPACE, "prior_async: no data pass has bound the workspace yet");
   hipStream_t st = (hipStream_t)stream;
   if (!c->side) {
@@ -991,14 +962,8 @@ int spmf_prior_async(spmf_ctx* c, int S, double prior_weight, const float* const
   // the side stream forks off `stream` (outputs need no zero fill: single writers)
   HIPCHK(c, hipEventRecord(c->ev_fork, st));
   HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
-  {
-    // one launch for all S draws (gridDim.y)
-    FinishArgs fa{c->D, c->K, 0, 0.0, c->u_tau_scale, c->s_tau_scale, c->decay, prior_weight, nullptr, nullptr,
-        params, eta, grads, parts, nullptr, likelihood_code(c), c->ctype, c->Dh, S, 0, {}, hsf ? 1 : 0,
-        c->fpart, c->futau};
-    for (int i = 0; i < SPMF_NVARS; ++i) fa.vstride[i] = (int64_t)var_size(c, i);
-    launch_finish(c->KP, fa, 1, c->side);
-  }
+  // one launch for all S draws (gridDim.y)
+  launch_finish(c->KP, finish_args(c, S, prior_weight, params, eta, grads, parts), 1, c->side);
   HIPCHK(c, hipEventRecord(c->ev_join, c->side));
   HIPCHK(c, hipGetLastError());
   c->prior_pending = S;
@@ -1011,13 +976,9 @@ int spmf_finish(spmf_ctx* c, int S, int64_t n_rows_global, double lgamma_sum_glo
     double* n_nonfinite, void* stream) {
   if (!c || !params || !grads || !eta || !parts || S < 1) return fail(c, SPMF_E_ARG, "finish: bad arguments");
   if (!c->acc || c->ws_S < S) return fail(c, SPMF_E_ARG, "finish: no data pass precedes it for this S");
-  const bool hsf = (c->flags & SPMF_FLAG_ABS_HORSESHOE) != 0;
-  for (int i = 0; i < SPMF_NVARS; ++i)
-    if ((!params[i] || !grads[i]) && !(hsf && i != 0 && i != 1 && i != 2 && i != 7))
-      return fail(c, SPMF_E_ARG, "finish: params/grads must be non-null (all 12; v,w,u,s with ABS_HORSESHOE)");
+  int rc = check_params_grads(c, "finish", params, grads);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  const int KP = c->KP, D = c->D;
-  const size_t al_ = acc_len(D, KP);
   // the prior half may already be running on the side stream (spmf_prior_async
   // with these outputs): join it and add the data half only
   const bool joined = c->prior_pending == S && c->prior_parts == parts;
@@ -1028,23 +989,18 @@ int spmf_finish(spmf_ctx* c, int S, int64_t n_rows_global, double lgamma_sum_glo
   }
   // (no zero fill: finish_reduce_kernel writes the twelve prior parts and the u_tau gradient
   //  whole, the data half stores parts 12 and 13 -- single writers)
-  {
-    // one launch for all S draws (gridDim.y)
-    const bool tm = c->timing;
-    FinishArgs fa{D, c->K, n_rows_global, lgamma_sum_global, c->u_tau_scale, c->s_tau_scale, c->decay, prior_weight,
-        c->acc, c->dprep, params, eta, grads, parts, n_nonfinite, likelihood_code(c), c->ctype, c->Dh, S,
-        (int64_t)al_, {}, hsf ? 1 : 0, c->fpart, c->futau};
-    for (int i = 0; i < SPMF_NVARS; ++i) fa.vstride[i] = (int64_t)var_size(c, i);
-    if (tm) HIPCHK(c, hipEventRecord(c->ev[4], st));
-    launch_finish(KP, fa, joined ? 2 : 0, st);
-    if (tm) {
-      HIPCHK(c, hipEventRecord(c->ev[5], st));
-      if (c->ev_valid == 1) {
-        c->ev_valid = 3;
-        c->ev_count++;
-      }
-    }
-  }
+  // one launch for all S draws (gridDim.y)
+  FinishArgs fa = finish_args(c, S, prior_weight, params, eta, grads, parts);
+  fa.B_global = n_rows_global;
+  fa.lgamma_sum = lgamma_sum_global;
+  fa.acc = c->acc;
+  fa.dprep = c->dprep;
+  fa.n_nonfinite = n_nonfinite;
+  fa.acc_stride = (int64_t)acc_len(c->D, c->KP);
+  if (c->timing) HIPCHK(c, hipEventRecord(c->ev[4], st));
+  launch_finish(c->KP, fa, joined ? 2 : 0, st);
+  rc = timing_close(c, st);
+  if (rc) return rc;
   HIPCHK(c, hipGetLastError());
   return SPMF_OK;
 }
@@ -1054,10 +1010,8 @@ int spmf_step_begin(spmf_ctx* c, const spmf_counts* ct, int S, double prior_weig
     const float* const params[SPMF_NVARS], const float* eta, double* parts, float* const grads[SPMF_NVARS],
     double* n_nonfinite, void* stream) {
   if (!c || !params || !grads || !eta || !parts || S < 1) return fail(c, SPMF_E_ARG, "step_begin: bad arguments");
-  const bool hsf = (c->flags & SPMF_FLAG_ABS_HORSESHOE) != 0;
-  for (int i = 0; i < SPMF_NVARS; ++i)
-    if ((!params[i] || !grads[i]) && !(hsf && i != 0 && i != 1 && i != 2 && i != 7))
-      return fail(c, SPMF_E_ARG, "step_begin: params/grads must be non-null (all 12; v,w,u,s with ABS_HORSESHOE)");
+  int rc = check_params_grads(c, "step_begin", params, grads);
+  if (rc) return rc;
   spmf_ctx::StepOut so;
   so.S = S;
   so.prior_weight = prior_weight;
@@ -1069,7 +1023,7 @@ int spmf_step_begin(spmf_ctx* c, const spmf_counts* ct, int S, double prior_weig
   so.parts = parts;
   so.nnf = n_nonfinite;
   c->step.active = 0;
-  const int rc = data_pass_impl(c, ct, S, params, eta, 3, stream, &so);
+  rc = data_pass_impl(c, ct, S, params, eta, 3, stream, &so);
   if (rc) return rc;
   so.active = 1;
   c->step = so;
@@ -1085,21 +1039,17 @@ int spmf_step_end(spmf_ctx* c, int64_t n_rows_global, double lgamma_sum_global, 
     return spmf_finish(c, so.S, n_rows_global, lgamma_sum_global, so.prior_weight, so.params, so.eta, so.parts,
                        so.grads, so.nnf, stream);
   hipStream_t st = (hipStream_t)stream;
-  const bool hsf = (c->flags & SPMF_FLAG_ABS_HORSESHOE) != 0;
-  const bool tm = c->timing;
-  FinishArgs fa{c->D, c->K, n_rows_global, lgamma_sum_global, c->u_tau_scale, c->s_tau_scale, c->decay,
-      so.prior_weight, c->acc, c->dprep, so.params, so.eta, so.grads, so.parts, so.nnf, likelihood_code(c),
-      c->ctype, c->Dh, so.S, (int64_t)acc_len(c->D, c->KP), {}, hsf ? 1 : 0, c->fpart, c->futau};
-  for (int i = 0; i < SPMF_NVARS; ++i) fa.vstride[i] = (int64_t)var_size(c, i);
-  if (tm) HIPCHK(c, hipEventRecord(c->ev[4], st));
+  FinishArgs fa = finish_args(c, so.S, so.prior_weight, so.params, so.eta, so.grads, so.parts);
+  fa.B_global = n_rows_global;
+  fa.lgamma_sum = lgamma_sum_global;
+  fa.acc = c->acc;
+  fa.dprep = c->dprep;
+  fa.n_nonfinite = so.nnf;
+  fa.acc_stride = (int64_t)acc_len(c->D, c->KP);
+  if (c->timing) HIPCHK(c, hipEventRecord(c->ev[4], st));
   launch_step_end(c->KP, fa, st);   // data half + the fold of the prior half's per-block sums
-  if (tm) {
-    HIPCHK(c, hipEventRecord(c->ev[5], st));
-    if (c->ev_valid == 1) {
-      c->ev_valid = 3;
-      c->ev_count++;
-    }
-  }
+  const int rc = timing_close(c, st);
+  if (rc) return rc;
   HIPCHK(c, hipGetLastError());
   return SPMF_OK;
 }
@@ -1112,24 +1062,33 @@ int spmf_elbo_fwd_bwd(spmf_ctx* c, const spmf_counts* ct, int S, double prior_we
   return spmf_step_end(c, ct->n_rows, ct->lgamma_sum, stream);
 }
 
-int spmf_encode(spmf_ctx* c, const spmf_counts* ct, const float* u, const float* s, const float* eta, float* z_out,
-    void* stream) {
-  if (!c || !u || !s || !eta || !z_out) return fail(c, SPMF_E_ARG, "encode: bad arguments");
-  const int logt = (c->flags & SPMF_FLAG_LOG_TRANSFORM) ? 1 : 0;
+// spmf_encode / spmf_dense_ll: the checks, the prep launch and the encode sweep (z of every row into the
+// workspace).  Nothing is launched for an empty batch.
+static int encode_rows(spmf_ctx* c, const char* fn, const spmf_counts* ct, const float* u, const float* v,
+    const float* w, const float* s, const float* eta, hipStream_t st) {
+  const int logt = lik_exp(likelihood_code(c)) ? 1 : 0;
   int rc = check_counts(c, ct);
-  if (!rc && logt && ct->nnz > 0 && !ct->gval) rc = fail(c, SPMF_E_ARG, "encode: log_transform needs counts.gval");
-  if (rc) return rc;
-  if (ct->n_rows == 0) return SPMF_OK;
+  if (!rc && logt && ct->nnz > 0 && !ct->gval) rc = fail(c, SPMF_E_ARG,
+      std::string(fn) + ": log_transform needs counts.gval");
+  if (rc || ct->n_rows == 0) return rc;
   rc = bind_ws(c, ct->n_rows, 1);
   if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  PrepArgs pa{c->D, c->K, u, nullptr, nullptr, s, eta, c->Ap, c->Vp, c->phi, c->dprep, logt, nullptr, nullptr};
+  PrepArgs pa{c->D, c->K, u, v, w, s, eta, c->Ap, c->Vp, c->phi, c->dprep, logt, nullptr, nullptr};
   launch_prep(c->KP, pa, st);
   RowArgs ra{ct->n_rows, ct->row_ptr, ct->col_idx, logt ? ct->gval : ct->val,
       (c->flags & SPMF_FLAG_SCALE_ROWS) ? ct->row_scale : nullptr, c->Ap, c->Vp, c->phi, c->dprep, c->z, c->gzs,
       c->dacc, 1, logt, nullptr, nullptr, 1, c->D, 0};
   if (!logt) ra.ent = ct->ent;
   launch_row_pass(c->KP, ra, st);
+  return SPMF_OK;
+}
+
+int spmf_encode(spmf_ctx* c, const spmf_counts* ct, const float* u, const float* s, const float* eta, float* z_out,
+    void* stream) {
+  if (!c || !u || !s || !eta || !z_out) return fail(c, SPMF_E_ARG, "encode: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = encode_rows(c, "encode", ct, u, nullptr, nullptr, s, eta, st);
+  if (rc || ct->n_rows == 0) return rc;
   HIPCHK(c, hipMemcpy2DAsync(z_out, (size_t)c->K * sizeof(float), c->z, (size_t)c->KP * sizeof(float),
       (size_t)c->K * sizeof(float), (size_t)ct->n_rows, hipMemcpyDeviceToDevice, st));
   HIPCHK(c, hipGetLastError());
@@ -1142,21 +1101,9 @@ int spmf_dense_ll(spmf_ctx* c, const spmf_counts* ct, const float* u, const floa
       "dense_ll: bad arguments");
   const int lik = likelihood_code(c);
   if (lik == 3 && !c->ctype) return fail(c, SPMF_E_ARG, "dense_ll: spmf_ctx_set_column_types was not called");
-  const int logt = lik_exp(lik) ? 1 : 0;
-  int rc = check_counts(c, ct);
-  if (!rc && logt && ct->nnz > 0 && !ct->gval) rc = fail(c, SPMF_E_ARG, "dense_ll: log_transform needs counts.gval");
-  if (rc) return rc;
-  if (ct->n_rows == 0) return SPMF_OK;
-  rc = bind_ws(c, ct->n_rows, 1);
-  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  PrepArgs pa{c->D, c->K, u, v, w, s, eta, c->Ap, c->Vp, c->phi, c->dprep, logt, nullptr, nullptr};
-  launch_prep(c->KP, pa, st);
-  RowArgs ra{ct->n_rows, ct->row_ptr, ct->col_idx, logt ? ct->gval : ct->val,
-      (c->flags & SPMF_FLAG_SCALE_ROWS) ? ct->row_scale : nullptr, c->Ap, c->Vp, c->phi, c->dprep, c->z, c->gzs,
-      c->dacc, 1, logt, nullptr, nullptr, 1, c->D, 0};
-  if (!logt) ra.ent = ct->ent;
-  launch_row_pass(c->KP, ra, st);
+  const int rc = encode_rows(c, "dense_ll", ct, u, v, w, s, eta, st);
+  if (rc || ct->n_rows == 0) return rc;
   DenseLLArgs da{ct->n_rows, c->D, lik, c->z, c->Vp, c->phi, c->ctype, ct->row_ptr, ct->col_idx, ct->val, rate_out,
       ll_out};
   launch_dense_ll(c->KP, da, st);
@@ -1482,26 +1429,61 @@ static void ensure_scratch(spmf_ctx* c, hipStream_t st) {
   }
 }
 
-int spmf_sample_transform(spmf_ctx* c, const spmf_sur_var* vars, int nvars, int S, uint64_t seed, uint64_t counter,
-    const double* state, double* logq, void* stream) {
-  if (!c || !vars || nvars < 1 || nvars > 12 || S < 1 || S > 65535 || !logq) return fail(c, SPMF_E_ARG,
-      "sample_transform: bad arguments");
-  SurTable T;
-  int max_n = 0;
+// The buffers of a spmf_sur_var an entry point needs besides t0 and noise (sur_table)
+enum : unsigned {
+  kSurT1 = 1,      // t1
+  kSurTheta = 2,   // theta
+  kSurGrad = 4,    // gtheta
+  kSurG01 = 8,     // g0, g1
+  kSurDgda = 16,   // dgda of the kind-2 variables
+  kSurSkip = 32,   // n = 0 skips the variable (its slot keeps its index: the RNG counter, the logq slots)
+};
+// vars[0, nvars) into T, max_n = the largest n; a variable without a buffer in `need` fails as
+// "<fn>: bad variable<detail>"
+static int sur_table(spmf_ctx* c, const char* fn, const char* detail, const spmf_sur_var* vars, int nvars,
+    unsigned need, SurTable& T, int& max_n) {
+  max_n = 0;
   for (int i = 0; i < nvars; ++i) {
     const spmf_sur_var& v = vars[i];
-    if (v.n == 0) {
+    if (v.n == 0 && (need & kSurSkip)) {
       T.v[i] = SurVar{};
       continue;
     }
-    if (!v.t0 || !v.t1 || !v.noise || !v.theta || v.n < 1 || v.kind < 0 || v.kind > 2 || (v.kind == 2 && !v.dgda))
-      return fail(c, SPMF_E_ARG, "sample_transform: bad variable (t0 / t1 / noise / dgda / theta buffers)");
+    if (!v.t0 || !v.noise || v.n < 1 || v.kind < 0 || v.kind > 2 || ((need & kSurT1) && !v.t1) ||
+        ((need & kSurTheta) && !v.theta) || ((need & kSurGrad) && !v.gtheta) ||
+        ((need & kSurG01) && (!v.g0 || !v.g1)) || ((need & kSurDgda) && v.kind == 2 && !v.dgda))
+      return fail(c, SPMF_E_ARG, std::string(fn) + ": bad variable" + detail);
     if (v.noise_ld != 0 && v.noise_ld < v.n) return fail(c, SPMF_E_ARG, "surrogate: noise_ld < n");
     T.v[i] = SurVar{v.t0, v.t1, v.noise, v.dgda, v.theta, v.gtheta, v.g0, v.g1, v.n, v.kind, v.ident,
         v.noise_ld ? v.noise_ld : (int64_t)v.n};
     if (v.n > max_n) max_n = v.n;
   }
-  if (max_n < 1) return fail(c, SPMF_E_ARG, "sample_transform: every variable is skipped (n = 0)");
+  if ((need & kSurSkip) && max_n < 1)
+    return fail(c, SPMF_E_ARG, std::string(fn) + ": every variable is skipped (n = 0)");
+  return SPMF_OK;
+}
+
+// tensors[0, n) into T, max_n = the largest n
+static int adam_table(spmf_ctx* c, const char* fn, const spmf_adam_var* tensors, int n, AdamTable& T, int& max_n) {
+  max_n = 0;
+  for (int i = 0; i < n; ++i) {
+    const spmf_adam_var& a = tensors[i];
+    if (!a.p || !a.m || !a.v || !a.g || a.n < 1) return fail(c, SPMF_E_ARG, std::string(fn) + ": bad tensor");
+    T.v[i] = AdamVar{a.p, a.m, a.v, a.g, a.n};
+    if (a.n > max_n) max_n = a.n;
+  }
+  return SPMF_OK;
+}
+
+int spmf_sample_transform(spmf_ctx* c, const spmf_sur_var* vars, int nvars, int S, uint64_t seed, uint64_t counter,
+    const double* state, double* logq, void* stream) {
+  if (!c || !vars || nvars < 1 || nvars > 12 || S < 1 || S > 65535 || !logq) return fail(c, SPMF_E_ARG,
+      "sample_transform: bad arguments");
+  SurTable T;
+  int max_n;
+  const int rc = sur_table(c, "sample_transform", " (t0 / t1 / noise / dgda / theta buffers)", vars, nvars,
+      kSurT1 | kSurTheta | kSurDgda | kSurSkip, T, max_n);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   ensure_scratch(c, st);
   if (!launch_sample_fwd(T, nvars, max_n, S, seed, counter, state, logq, c->scratch, spmf_ctx::kScratchDoubles, st)) {
@@ -1517,21 +1499,9 @@ int spmf_surrogate_fwd(spmf_ctx* c, const spmf_sur_var* vars, int nvars, int S, 
   if (!c || !vars || nvars < 1 || nvars > 12 || S < 1 || !logq) return fail(c, SPMF_E_ARG,
       "surrogate_fwd: bad arguments");
   SurTable T;
-  int max_n = 0;
-  for (int i = 0; i < nvars; ++i) {
-    const spmf_sur_var& v = vars[i];
-    if (v.n == 0) {                 // skipped variable (its slot keeps its index: the RNG counter, the logq slots)
-      T.v[i] = SurVar{};
-      continue;
-    }
-    if (!v.t0 || !v.t1 || !v.noise || !v.theta || v.n < 1 || v.kind < 0 || v.kind > 2) return fail(c, SPMF_E_ARG,
-        "surrogate_fwd: bad variable");
-    if (v.noise_ld != 0 && v.noise_ld < v.n) return fail(c, SPMF_E_ARG, "surrogate: noise_ld < n");
-    T.v[i] = SurVar{v.t0, v.t1, v.noise, v.dgda, v.theta, v.gtheta, v.g0, v.g1, v.n, v.kind, v.ident,
-        v.noise_ld ? v.noise_ld : (int64_t)v.n};
-    if (v.n > max_n) max_n = v.n;
-  }
-  if (max_n < 1) return fail(c, SPMF_E_ARG, "surrogate_fwd: every variable is skipped (n = 0)");
+  int max_n;
+  const int rc = sur_table(c, "surrogate_fwd", "", vars, nvars, kSurT1 | kSurTheta | kSurSkip, T, max_n);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   ensure_scratch(c, st);
   launch_surrogate_fwd(T, nvars, max_n, S, logq, c->scratch, spmf_ctx::kScratchDoubles, st);
@@ -1544,21 +1514,10 @@ int spmf_sample_noise(spmf_ctx* c, const spmf_sur_var* vars, int nvars, int S, u
   if (!c || !vars || nvars < 1 || nvars > 12 || S < 1 || S > 65535) return fail(c, SPMF_E_ARG,
       "sample_noise: bad arguments");
   SurTable T;
-  int max_n = 0;
-  for (int i = 0; i < nvars; ++i) {
-    const spmf_sur_var& v = vars[i];
-    if (v.n == 0) {                 // skipped variable: nothing is drawn for it, the others keep their indices
-      T.v[i] = SurVar{};
-      continue;
-    }
-    if (!v.t0 || !v.noise || v.n < 1 || v.kind < 0 || v.kind > 2 || (v.kind == 2 && !v.dgda)) return fail(c,
-        SPMF_E_ARG, "sample_noise: bad variable (t0 / noise / dgda buffers)");
-    if (v.noise_ld != 0 && v.noise_ld < v.n) return fail(c, SPMF_E_ARG, "surrogate: noise_ld < n");
-    T.v[i] = SurVar{v.t0, v.t1, v.noise, v.dgda, v.theta, v.gtheta, v.g0, v.g1, v.n, v.kind, v.ident,
-        v.noise_ld ? v.noise_ld : (int64_t)v.n};
-    if (v.n > max_n) max_n = v.n;
-  }
-  if (max_n < 1) return fail(c, SPMF_E_ARG, "sample_noise: every variable is skipped (n = 0)");
+  int max_n;
+  const int rc = sur_table(c, "sample_noise", " (t0 / noise / dgda buffers)", vars, nvars, kSurDgda | kSurSkip, T,
+      max_n);
+  if (rc) return rc;
   launch_sample_noise(T, nvars, max_n, S, seed, counter, state, (hipStream_t)stream);
   HIPCHK(c, hipGetLastError());
   return SPMF_OK;
@@ -1568,15 +1527,9 @@ int spmf_surrogate_bwd(spmf_ctx* c, const spmf_sur_var* vars, int nvars, int S, 
     void* stream) {
   if (!c || !vars || nvars < 1 || nvars > 12 || S < 1) return fail(c, SPMF_E_ARG, "surrogate_bwd: bad arguments");
   SurTable T;
-  int max_n = 0;
-  for (int i = 0; i < nvars; ++i) {
-    const spmf_sur_var& v = vars[i];
-    if (!v.t0 || !v.t1 || !v.noise || !v.gtheta || !v.g0 || !v.g1 || v.n < 1 || v.kind < 0 || v.kind > 2 || (v.kind == 2 && !v.dgda)) return fail(c, SPMF_E_ARG, "surrogate_bwd: bad variable");
-    if (v.noise_ld != 0 && v.noise_ld < v.n) return fail(c, SPMF_E_ARG, "surrogate: noise_ld < n");
-    T.v[i] = SurVar{v.t0, v.t1, v.noise, v.dgda, v.theta, v.gtheta, v.g0, v.g1, v.n, v.kind, v.ident,
-        v.noise_ld ? v.noise_ld : (int64_t)v.n};
-    if (v.n > max_n) max_n = v.n;
-  }
+  int max_n;
+  const int rc = sur_table(c, "surrogate_bwd", "", vars, nvars, kSurT1 | kSurGrad | kSurG01 | kSurDgda, T, max_n);
+  if (rc) return rc;
   launch_surrogate_bwd(T, nvars, max_n, S, (float)inv_sb, (float)cw, (hipStream_t)stream);
   HIPCHK(c, hipGetLastError());
   return SPMF_OK;
@@ -1587,13 +1540,9 @@ int spmf_adam_step(spmf_ctx* c, const spmf_adam_var* tensors, int ntensors, doub
   if (!c || !tensors || ntensors < 1 || ntensors > 24 || step < 1) return fail(c, SPMF_E_ARG,
       "adam_step: bad arguments");
   AdamTable T;
-  int max_n = 0;
-  for (int i = 0; i < ntensors; ++i) {
-    const spmf_adam_var& a = tensors[i];
-    if (!a.p || !a.m || !a.v || !a.g || a.n < 1) return fail(c, SPMF_E_ARG, "adam_step: bad tensor");
-    T.v[i] = AdamVar{a.p, a.m, a.v, a.g, a.n};
-    if (a.n > max_n) max_n = a.n;
-  }
+  int max_n;
+  const int rc = adam_table(c, "adam_step", tensors, ntensors, T, max_n);
+  if (rc) return rc;
   const double c1 = 1.0 - pow(beta1, step), c2 = 1.0 - pow(beta2, step);
   launch_adam(T, ntensors, max_n, (float)lr, (float)beta1, (float)beta2, (float)eps, (float)c1, (float)c2,
       (float)clip, (hipStream_t)stream);
@@ -1613,13 +1562,9 @@ int spmf_adam_step_dev(spmf_ctx* c, const spmf_adam_var* tensors, int ntensors, 
   if (!c || !tensors || ntensors < 1 || ntensors > 24 || !state) return fail(c, SPMF_E_ARG,
       "adam_step_dev: bad arguments");
   AdamTable T;
-  int max_n = 0;
-  for (int i = 0; i < ntensors; ++i) {
-    const spmf_adam_var& a = tensors[i];
-    if (!a.p || !a.m || !a.v || !a.g || a.n < 1) return fail(c, SPMF_E_ARG, "adam_step_dev: bad tensor");
-    T.v[i] = AdamVar{a.p, a.m, a.v, a.g, a.n};
-    if (a.n > max_n) max_n = a.n;
-  }
+  int max_n;
+  const int rc = adam_table(c, "adam_step_dev", tensors, ntensors, T, max_n);
+  if (rc) return rc;
   launch_adam_dev(T, ntensors, max_n, state, (hipStream_t)stream);
   HIPCHK(c, hipGetLastError());
   return SPMF_OK;
@@ -1631,22 +1576,16 @@ int spmf_surrogate_bwd_adam_dev(spmf_ctx* c, const spmf_sur_var* vars, int nvars
       "surrogate_bwd_adam_dev: bad arguments");
   SurTable T;
   AdamTable A;
-  int max_n = 0;
-  for (int i = 0; i < nvars; ++i) {
-    const spmf_sur_var& v = vars[i];
-    if (!v.t0 || !v.t1 || !v.noise || !v.gtheta || v.n < 1 || v.kind < 0 || v.kind > 2 || (v.kind == 2 && !v.dgda))
-      return fail(c, SPMF_E_ARG, "surrogate_bwd_adam_dev: bad variable");
-    if (v.noise_ld != 0 && v.noise_ld < v.n) return fail(c, SPMF_E_ARG, "surrogate: noise_ld < n");
-    T.v[i] = SurVar{v.t0, v.t1, v.noise, v.dgda, v.theta, v.gtheta, nullptr, nullptr, v.n, v.kind, v.ident,
-        v.noise_ld ? v.noise_ld : (int64_t)v.n};
-    if (v.n > max_n) max_n = v.n;
-    // tensors[2i], tensors[2i+1]: the Adam records of this variable's t0 / t1
-    for (int j = 0; j < 2; ++j) {
-      const spmf_adam_var& a = tensors[2 * i + j];
-      if (!a.p || !a.m || !a.v || a.n != v.n || a.p != (j ? v.t1 : v.t0)) return fail(c, SPMF_E_ARG,
-          "surrogate_bwd_adam_dev: tensors[2i+j] must be the Adam record (p, m, v, n) of vars[i].t{j}");
-      A.v[2 * i + j] = AdamVar{a.p, a.m, a.v, nullptr, a.n};
-    }
+  int max_n;
+  const int rc = sur_table(c, "surrogate_bwd_adam_dev", "", vars, nvars, kSurT1 | kSurGrad | kSurDgda, T, max_n);
+  if (rc) return rc;
+  // tensors[2i], tensors[2i+1]: the Adam records of vars[i].t0 / t1 (the gradients come from the fused kernel)
+  for (int i = 0; i < 2 * nvars; ++i) {
+    const spmf_adam_var& a = tensors[i];
+    const spmf_sur_var& v = vars[i / 2];
+    if (!a.p || !a.m || !a.v || a.n != v.n || a.p != (i % 2 ? v.t1 : v.t0)) return fail(c, SPMF_E_ARG,
+        "surrogate_bwd_adam_dev: tensors[2i+j] must be the Adam record (p, m, v, n) of vars[i].t{j}");
+    A.v[i] = AdamVar{a.p, a.m, a.v, nullptr, a.n};
   }
   launch_surrogate_bwd_adam(T, A, nvars, max_n, S, (float)inv_sb, (float)cw, state, (hipStream_t)stream);
   HIPCHK(c, hipGetLastError());

@@ -43,9 +43,6 @@ struct RowArgs {
   int S, D;
   int64_t dacc_stride;
   const uint32_t* ent = nullptr;   // packed col << 16 | count copy of (col, val), or null (spmf_counts.ent)
-  // mode 3 with the exp decoder (LIK 1): `val` is g(x) (sweep 1) and the counts of sweep 2 come out of `ent`
-  // (must be non-null); only the LDS-phi launch shapes have this form: launch_row_pass returns false otherwise
-  int dual = 0;
   // deterministic mode: the workgroups' scalar sums go to their own slots (kDetMeta + kDetMaxBlocks *
   // (kDaccHead + KP) doubles per draw, stride det_stride) instead of the fp64 atomics on dacc
   double* det_slots = nullptr;
@@ -55,7 +52,7 @@ struct RowArgs {
   // full row launch of a step (modes 0 and 3), ignored in the deterministic mode
   int dyn_tail = 0;
 };
-bool launch_row_pass(int KP, const RowArgs& a, hipStream_t st);   // false: a.dual asked for a form this shape lacks (nothing launched)
+bool launch_row_pass(int KP, const RowArgs& a, hipStream_t st);   // false: KP is not built (nothing launched)
 bool launch_row_widek(int KP, const RowArgs& a, hipStream_t st);  // KP = 128, 256 (widek.hip): Poisson / linear decoder, modes 0 and 1
 
 struct ColArgs {

@@ -71,9 +71,7 @@ __device__ __forceinline__ float* lds_dyn() {
 // kernel (the resident-set launches have both forms).  load_entry only LOADS (into the pipeline registers of the row prefetch);
 // unpack_entry turns them into (column, count) where they are used, one row later -- arithmetic
 // on the loaded word right away would put the wait for the prefetch in front of it.
-// FMT 0: canonical (col, val).  FMT 1: packed word.  FMT 2: packed word + a second value stream
-// (`val` = g(x) of the log_transform encoder, poisson.py:41-42): the fused pass of the exp decoders
-// reads g(x) in sweep 1 and the count out of the word in sweep 2 -- the register cost of the canonical pair.
+// FMT 0: canonical (col, val).  FMT 1: packed word.
 template <int FMT, bool NT>
 __device__ __forceinline__ void load_entry(const int32_t* __restrict__ col, const float* __restrict__ val,
                                            const uint32_t* __restrict__ ent, int i, bool ok, int& ra,
@@ -81,23 +79,16 @@ __device__ __forceinline__ void load_entry(const int32_t* __restrict__ col, cons
   if (FMT == 1) {
     ra = ok ? (int)(NT ? __builtin_nontemporal_load(&ent[i]) : ent[i]) : (int)kPadWord;
     rb = 0.f;
-  } else if (FMT == 2) {
-    ra = ok ? (int)(NT ? __builtin_nontemporal_load(&ent[i]) : ent[i]) : (int)kPadWord;
-    rb = ok ? (NT ? __builtin_nontemporal_load(&val[i]) : val[i]) : 0.f;
   } else {
     ra = ok ? (NT ? __builtin_nontemporal_load(&col[i]) : col[i]) : kPadRow;
     rb = ok ? (NT ? __builtin_nontemporal_load(&val[i]) : val[i]) : 0.f;
   }
 }
-// SWEEP 1: the encoder's value (g(x) under FMT 2); SWEEP 2: the count
-template <int FMT, int SWEEP = 2>
+template <int FMT>
 __device__ __forceinline__ void unpack_entry(int ra, float rb, int& c, float& x) {
-  if (FMT == 1 || (FMT == 2 && SWEEP == 2)) {
+  if (FMT == 1) {
     c = (int)((uint32_t)ra >> 16);
     x = (float)((uint32_t)ra & 0xffffu);
-  } else if (FMT == 2) {
-    c = (int)((uint32_t)ra >> 16);
-    x = rb;
   } else {
     c = ra;
     x = rb;
@@ -484,13 +475,8 @@ __global__ __launch_bounds__(BT, BT == 256 ? ROW_WAVES_PER_SIMD : 4) void row_pa
         if (!encode_only) cx.s2_load(c0, n0, vv0);
       }
       if (mode != 2) {
-        if (PACKED == 2) {              // sweep 1 reads the encoder's values, not the counts
-          cx.sweep1(c0, px0, n0, zacc);
-          if (n1 > 0) cx.sweep1(c1, px1, n1, zacc);
-        } else {
-          cx.sweep1(c0, x0, n0, zacc);
-          if (n1 > 0) cx.sweep1(c1, x1, n1, zacc);
-        }
+        cx.sweep1(c0, x0, n0, zacc);
+        if (n1 > 0) cx.sweep1(c1, x1, n1, zacc);
         if constexpr (VAHEAD == 3) {
           if (!encode_only) cx.s2_load(c0, n0, vv0);
         }
@@ -531,7 +517,7 @@ __global__ __launch_bounds__(BT, BT == 256 ? ROW_WAVES_PER_SIMD : 4) void row_pa
           load_entry<PACKED, false>(col, val, ent, i2, i2 < end, ra2, rb2);
           int c;
           float x;
-          unpack_entry<PACKED, 1>(ra, rb, c, x);
+          unpack_entry<PACKED>(ra, rb, c, x);
           cx.sweep1(c, x, min(64, end - base), zacc);
           ra = ra1; rb = rb1; ra1 = ra2; rb1 = rb2;
         }
@@ -689,10 +675,6 @@ static bool launch_row_lds_t(const RowArgs& a, hipStream_t st) {
 // packed entry stream (spmf_counts.ent) when the batch carries one
 template <int KP, int LIK, int BT>
 static bool launch_row_lds(const RowArgs& a, hipStream_t st) {
-  if constexpr (LIK == 1) {
-    // fused pass of the exp decoder: packed word + the g(x) stream (RowArgs.dual)
-    if (a.dual) return a.ent ? launch_row_lds_t<KP, LIK, BT, 2>(a, st) : false;
-  }
   return a.ent ? launch_row_lds_t<KP, LIK, BT, 1>(a, st) : launch_row_lds_t<KP, LIK, BT, 0>(a, st);
 }
 
@@ -732,7 +714,6 @@ static bool launch_row_t(const RowArgs& a, hipStream_t st) {
       if (done) return true;
     }
   }
-  if (a.dual) return false;      // only the LDS-phi shapes have the two-stream form
 #define SPMF_ROW_LAUNCH(L_)                                                                    \
   hipLaunchKernelGGL((row_pass_kernel<KP, L_>), dim3(nb, a.S > 1 ? a.S : 1), dim3(256), 0, st, \
                      a.B, a.row_ptr, a.col, a.val, a.row_scale, a.Ap, a.Vp, a.phi, a.dprep, a.z, \

@@ -509,7 +509,7 @@ __global__ __launch_bounds__(256) void col_widek128_kernel(
 
 // false: not a shape this file covers (nothing launched)
 bool launch_row_widek(int KP, const RowArgs& a, hipStream_t st) {
-  if (a.logt != 0 || (a.mode != 0 && a.mode != 1) || a.det_slots || a.dual) return false;
+  if (a.logt != 0 || (a.mode != 0 && a.mode != 1) || a.det_slots) return false;
   const int64_t want = (a.B + 3) / 4;
   const int nb = (int)(want < 1 ? 1 : (want > 2048 ? 2048 : want));
 #define SPMF_ROWW(KP_)                                                                                     \
