@@ -47,9 +47,6 @@
 
 namespace spmf {
 
-#ifndef COL_WIDE
-#define COL_WIDE 1
-#endif
 #ifndef COL_WIDE_WAVES
 #define COL_WIDE_WAVES 4
 #endif
@@ -95,16 +92,7 @@ __device__ __forceinline__ void pack_block(const double* __restrict__ dacc, floa
     return;
   }
   const int i = threadIdx.x;
-  if (i < kDaccHead + KP) {
-    double v = 0.0;
-    {
-#pragma unroll
-      for (int r = 0; r < kDaccRep; ++r) v += dacc[(size_t)r * (kDaccHead + KP) + i];
-    }
-    const float hi = (float)v;
-    tail[2 * i] = hi;
-    tail[2 * i + 1] = (float)(v - (double)hi);
-  }
+  if (i < kDaccHead + KP) fold_dacc(i, dacc, tail, KP);
 }
 
 // ONE kernel body for both fetch shapes (the round-3 file carried it twice):
@@ -280,7 +268,7 @@ __global__ __launch_bounds__(256, EPL == 4 ? COL_WIDE_WAVES : 1) void col_pass_k
         for (int j = 0; j < GRP; ++j) {
           const int q = g0 + j;                       // entry q of the fetch: lane q / EPL, component q % EPL
           // (source lane grp * LPN + q / EPL: the lane-dependent part is one byte-address register of the kernel,
-          //  the compile-time part an add -- __shfl shifts the index per call; row_pass.hip ROW_BPERM_IMM)
+          //  the compile-time part an add -- __shfl shifts the index per call; row_pass.hip bperm_i)
           const int sa = bp_row + (q / EPL) * 4;
           const int b = __builtin_amdgcn_ds_bpermute(sa, rr0[q % EPL]);
           xv[j] = __int_as_float(__builtin_amdgcn_ds_bpermute(sa, __float_as_int(xx0[q % EPL])));
@@ -374,7 +362,7 @@ static bool launch_col_t(const ColArgs& a, hipStream_t st) {
       a.item_ptr, items, a.pc_row, a.pc_val, a.pc_gval, a.Vp, a.phi, a.z, a.gzs, a.gAp, a.gVp, \
       a.gphi, a.ctype, a.item_mid, a.half_sel, a.B, a.acc_stride, a.pack_dacc, a.pack_tail,     \
       a.dacc_stride, a.pc_ent, a.panel_rows, a.det_part, a.det_part_stride, a.det_slots, a.det_stride
-  const bool wide = COL_WIDE && a.pc_pad >= KP - 1;   // 4*LPN - 1 entries of readable padding
+  const bool wide = a.pc_pad >= KP - 1;   // 4*LPN - 1 entries of readable padding
   // packed lists (spmf_counts.pc_ent: row in panel << 16 | count) when the batch carries them
   const bool packed = wide && a.pc_ent && a.panel_rows > 0 && a.panel_rows <= 65536;
 #define SPMF_COL_LAUNCH(L_)                                                                        \

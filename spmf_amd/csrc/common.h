@@ -14,8 +14,10 @@ constexpr double kLog2 = 0.69314718055994530942;
 // Layout of the fp64 scalar block a data pass accumulates per draw.
 //   [0] sum_nnz x*log r   [1] sum z^2   [2] non-finite stored cells
 //   [3] dense sum (sum E / sum softplus)   [4] saturated cells (log_transform)
-//   [5] reserved          [6 .. 6+KP)   sum_b z_b
+//   [5] not a sum: the row pass's dynamic-tail counter of this replica (a uint32 in the slot's low word)
+//   [6 .. 6+KP)   sum_b z_b
 constexpr int kDaccHead = 6;
+constexpr int kDaccDynSlot = 5;
 // log_transform decoder (poisson.py:52-53): f(y) = exp(y) - 1 is evaluated as
 // exp(min(y, kYSat)) - 1.  fp32 cannot hold exp(y) beyond y ~ 88.7 (the fp64
 // reference overflows at 709); saturating keeps every sum and gradient of a
@@ -64,7 +66,7 @@ constexpr int kPrepSeg = 8;
 constexpr int kFinishCols = FINISH_FTD;
 // the block sums land in one of kDaccRep replicas (blockIdx % kDaccRep) so the
 // fp64 atomics of thousands of blocks do not serialise on 4+KP addresses;
-// the pack kernel folds the replicas.
+// fold_dacc (below) sums the replicas into the accumulator tail.
 constexpr int kDaccRep = 16;
 // Deterministic mode (spmf_ctx_set_deterministic): per-workgroup scalar slots of the row pass instead of
 // its fp64 atomics -- at most this many workgroups (ROW_MAX_BLOCKS), slot -1 = the launch's workgroup count;
@@ -97,6 +99,20 @@ struct AccLayout {
 };
 __host__ __device__ inline int64_t acc_len(int D, int KP) {
   return (int64_t)2 * D * KP + D + acc_tail_len(KP);
+}
+
+// Element i of a draw's scalar block, summed over the kDaccRep replicas, as the (hi, lo) float pair of the
+// accumulator tail.  kDaccDynSlot holds counters, not a sum: the fold skips it and its pair (tail floats 10 / 11)
+// is always zero.
+__device__ __forceinline__ void fold_dacc(int i, const double* __restrict__ dacc, float* __restrict__ tail, int KP) {
+  double v = 0.0;
+  if (i != kDaccDynSlot) {
+#pragma unroll
+    for (int r = 0; r < kDaccRep; ++r) v += dacc[(size_t)r * (kDaccHead + KP) + i];
+  }
+  const float hi = (float)v;
+  tail[2 * i] = hi;
+  tail[2 * i + 1] = (float)(v - (double)hi);
 }
 
 __device__ __forceinline__ double prep_sum(const double* __restrict__ dprep, int KP, int i) {
@@ -142,10 +158,7 @@ __device__ __forceinline__ float4 gather4(const float* __restrict__ base, int ro
 // DESIGN.md section 4, round 5 (e)) cost an issue slot and nothing else, with no branch and no exec mask in
 // the straight-line groups of loads.  A padded slot asks for row kPadRow: -1 wraps to the last KP*4 bytes
 // below 4 GiB, behind every table the host admits (api.hip checks rows*KP*4 < 4 GiB - KP*4).
-#ifndef SPMF_OOB_PAD
-#define SPMF_OOB_PAD 1
-#endif
-#if SPMF_OOB_PAD
+// (measured against padded slots that read row 0: profiles/r05_oob_pad_ab.txt)
 constexpr int kPadRow = -1;
 constexpr uint32_t kPadWord = 0xffff0000u;     // packed entry (column or panel row 65 535, count 0)
 struct GTable {
@@ -165,18 +178,6 @@ __device__ __forceinline__ float4 gather4(const GTable& t, int row, int sub) {
   const u4 v = __builtin_amdgcn_raw_buffer_load_b128(t.r, (int)off, 0, 0);
   return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
 }
-#else
-constexpr int kPadRow = 0;
-constexpr uint32_t kPadWord = 0u;
-struct GTable {
-  const float* p;
-};
-__device__ __forceinline__ GTable gtable(const float* base, int64_t, int) { return GTable{base}; }
-template <int LPN>
-__device__ __forceinline__ float4 gather4(const GTable& t, int row, int sub) {
-  return gather4<LPN>(t.p, row, sub);
-}
-#endif
 
 // ---- DPP cross-lane adds (no LDS traffic, fold into v_add_f32_dpp) --------
 // ctrl: quad_perm[1,0,3,2]=0xB1 (xor 1), quad_perm[2,3,0,1]=0x4E (xor 2),
@@ -186,19 +187,6 @@ template <int CTRL>
 __device__ __forceinline__ float dpp_add(float v) {
   const int t = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true);
   return v + __int_as_float(t);
-}
-// keep + (send of the DPP partner)
-template <int CTRL>
-__device__ __forceinline__ float dpp_add_to(float keep, float send) {
-  const int t = __builtin_amdgcn_update_dpp(0, __float_as_int(send), CTRL, 0xF, 0xF, true);
-  return keep + __int_as_float(t);
-}
-// <a, b> with the packed forms (v_pk_mul_f32, v_pk_fma_f32, one add: three instructions instead of four)
-__device__ __forceinline__ float dot4p(const float4& a, const float4& b) {
-  typedef float f2 __attribute__((ext_vector_type(2)));
-  f2 p = f2{a.x, a.y} * f2{b.x, b.y};
-  p = __builtin_elementwise_fma(f2{a.z, a.w}, f2{b.z, b.w}, p);
-  return p.x + p.y;
 }
 // Sum over the aligned group of N lanes (N = 1,2,4,8,16); every lane of the
 // group ends up with the total.

@@ -71,13 +71,7 @@ __global__ void pack_kernel(int KP, const double* __restrict__ dacc, float* __re
   dacc += (size_t)blockIdx.y * dacc_stride;     // draw of this block
   tail += (size_t)blockIdx.y * acc_stride;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < kDaccHead + KP) {
-    double v = 0.0;
-    for (int r = 0; r < kDaccRep; ++r) v += dacc[(size_t)r * (kDaccHead + KP) + i];
-    const float hi = (float)v;
-    tail[2 * i] = hi;
-    tail[2 * i + 1] = (float)(v - (double)hi);
-  }
+  if (i < kDaccHead + KP) fold_dacc(i, dacc, tail, KP);
 }
 
 void launch_pack(const PackArgs& a, hipStream_t st) {

@@ -65,9 +65,6 @@ __device__ __attribute__((noinline, cold)) static double slow_log(double x) { re
 // fp32 reciprocal of the prior's gradient terms: v_rcp_f32 (1 ulp) instead of the IEEE division sequence
 // (ten instructions each, three per element in the [D,K] loop)
 __device__ __forceinline__ float frcp(float x) { return __builtin_amdgcn_rcpf(x); }
-#ifndef FIN_ABL
-#define FIN_ABL 0   // timing-only ablations of the prior half (tools/build_variant.sh): 1 main, 2 vectors, 4 v, 8 sums
-#endif
 __device__ __forceinline__ double fast_log(double x) {
   if (__builtin_expect(!(x > 0.0) || x > 1.7e308, 0)) return slow_log(x);
   const long long bits = __double_as_longlong(x);
@@ -413,7 +410,7 @@ __device__ __forceinline__ void finish_body(const FinishK& a_, const int bx, con
         abs_horseshoe((double)u, scd_s[k], lp, dlp);
         part[U_] += lp;
         G.p[U_][i] = du + pw * (float)dlp;
-      } else if (PRIOR && !(FIN_ABL & 1)) {
+      } else if (PRIOR) {
         const float ue = in_ue[it], ua = in_ua[it];
         const float sc = utau_s[k] * dec_s[k];
         // the three log-densities share their fp64 logs (software fp64 log is what
@@ -489,7 +486,7 @@ __device__ __forceinline__ void finish_body(const FinishK& a_, const int bx, con
     if (k < K && d < D) {
       const size_t i = (size_t)k * D + d;
       const float dv = DATA ? tile[k][dl] : 0.f;
-      if (PRIOR && !(FIN_ABL & 4)) {
+      if (PRIOR) {
         const float v = in_v[it];
         double lp;
         float gy, gs;
@@ -505,7 +502,7 @@ __device__ __forceinline__ void finish_body(const FinishK& a_, const int bx, con
   // ---- [.,D] vectors: w, s, s_eta, s_tau, s_eta_a, s_tau_a ---------------
   __shared__ float xs_s[2][FTD];
   if (VSPREAD) {
-    if (von && !(FIN_ABL & 2)) {
+    if (von) {
       double lp, a_lp, c_lp;
       float gy, gs, a_gy, a_ga, c_ga;
       if (vg < 2) {                    // row vg of s, s_eta, s_eta_a
@@ -549,7 +546,7 @@ __device__ __forceinline__ void finish_body(const FinishK& a_, const int bx, con
       ds0 = (GA - Gphi) * s1 * iT2;
       ds1 = (Gphi - GA) * s0 * iT2;
     }
-    if (PRIOR && !(FIN_ABL & 2)) {
+    if (PRIOR) {
       double lp;
       float gy, gs;
       halfnormal(w, 1.f, lp, gy, gs);
@@ -599,7 +596,7 @@ __device__ __forceinline__ void finish_body(const FinishK& a_, const int bx, con
     }
   }
   __syncthreads();
-  if (VSPREAD && von && vg == 2 && !(FIN_ABL & 2)) G.p[STAU_][vd] = pw * (xs_s[0][vdl] + xs_s[1][vdl] + v_keep);
+  if (VSPREAD && von && vg == 2) G.p[STAU_][vd] = pw * (xs_s[0][vdl] + xs_s[1][vdl] + v_keep);
   if (PRIOR) {
     // ---- [1,K] vectors: u_tau, u_tau_a (block 0 adds their own prior) ------
     if (t < K && !hs) {
@@ -621,13 +618,7 @@ __device__ __forceinline__ void finish_body(const FinishK& a_, const int bx, con
     // ---- energy parts ------------------------------------------------------
     __shared__ double pred[12][4];
     const int wid = t >> 6, lane = t & 63;
-    if (FIN_ABL & 8) {
-#pragma unroll
-      for (int i = 0; i < 12; ++i)
-        if (lane == 0) pred[i][wid] = part[i];
-    } else {
-      parts_wave_sums(part, lane, wid, pred);
-    }
+    parts_wave_sums(part, lane, wid, pred);
     __syncthreads();
     if (t < 12) ppart[t] = pred[t][0] + pred[t][1] + pred[t][2] + pred[t][3];
   }

@@ -47,8 +47,9 @@ struct RowArgs {
   // (kDaccHead + KP) doubles per draw, stride det_stride) instead of the fp64 atomics on dacc
   double* det_slots = nullptr;
   int64_t det_stride = 0;
-  // 1: the last eighth of every wave's rows is handed out by counters (the spare slot [5] of the kDaccRep replicas
-  // of `dacc`, zeroed by the caller with the rest of it) instead of by the fixed stride; only for the ONE
+  // 1: the last eighth of every wave's rows is handed out by counters (slot kDaccDynSlot of the kDaccRep replicas
+  // of `dacc`, zeroed by the caller with the rest of it; the fold into the accumulator tail skips it, so tail
+  // pair 10 / 11 is always zero) instead of by the fixed stride; only for the ONE
   // full row launch of a step (modes 0 and 3), ignored in the deterministic mode
   int dyn_tail = 0;
 };

@@ -97,21 +97,7 @@ __device__ __forceinline__ void unpack_entry(int ra, float rb, int& c, float& x)
 
 // Lane `base/4 + IMM` 's value: ds_bpermute with the compile-time part of the source lane in the instruction's
 // offset field (the row pass broadcasts from lanes (g0 + j) * NPI + grp and grp * LPN + g0 + j: one base
-// register per form for the whole kernel instead of a shift / add per broadcast -- ROW_BPERM_IMM)
-// sweep 2 at K = 32: the chunk's eight dot products through one transpose-reduce (RowCtx::sweep2_loaded)
-// (measured: 1.443 against 1.411 ms on C3 -- the fourteen selects and two spilled registers cost more than the
-//  seventeen folds they replace; built, parity-tested, off: profiles/r05_row_valu_ab.txt)
-#ifndef ROW_DOT_BUTTERFLY
-#define ROW_DOT_BUTTERFLY 0
-#endif
-// sweep 2's dot products with the packed multiply / fma (three instructions instead of four): measured, no
-// difference (1.409 against 1.402 ms): off
-#ifndef ROW_DOT_PK
-#define ROW_DOT_PK 0
-#endif
-#ifndef ROW_BPERM_IMM
-#define ROW_BPERM_IMM 1
-#endif
+// register per form for the whole kernel instead of a shift / add per broadcast)
 // (imm_lanes is a constant after the unrolled callers are inlined.  BASE false = the __shfl form: at K = 64 the
 //  sixteen base + constant sums of a chunk get hoisted into registers the kernel does not have -- 132 instead of
 //  76 bytes of scratch, C4's row launches 12.7 -> 13.2 ms -- so that instantiation keeps the shift per call)
@@ -134,7 +120,7 @@ struct RowCtx {
   static constexpr int GRP = LPN < ROW_GRP ? LPN : ROW_GRP;  // gathers issued back to back
   // broadcasts through a base register: K <= 32; not the exp decoder's instantiations (they have no register to
   // spare either: 12 - 20 bytes of scratch with it)
-  static constexpr bool BPI = ROW_BPERM_IMM && LPN <= 8 && LIK != 1;
+  static constexpr bool BPI = LPN <= 8 && LIK != 1;
   GTable Ap, Vp;          // the gathered tables (common.h: slots behind a row's end are dropped by the range check)
   const float* phi;
   const uint8_t* ctype;   // LIK 3 (mixed): 1 = Bernoulli column
@@ -179,13 +165,12 @@ struct RowCtx {
 #pragma unroll
     for (int j = CNT; j < GRP; ++j) vv[g0 + j] = make_float4(0.f, 0.f, 0.f, 0.f);
   }
-  template <int CNT, bool PERM = false>
+  template <int CNT>
   __device__ __forceinline__ void s2_back(float cc, int g0, const float4 (&vv)[LPN],
                                           float4& gz) const {
 #pragma unroll
     for (int j = 0; j < CNT; ++j) {
-      const int q = g0 + j;                                  // the lane of the group that owns gather q's weight
-      const float cb = bperm_f<BPI>(bp_row, PERM ? (q < 4 ? q : 11 - q) : q, cc);
+      const float cb = bperm_f<BPI>(bp_row, g0 + j, cc);    // the lane of the group that owns this gather's weight
       gz = fma4(cb, vv[g0 + j], gz);
     }
   }
@@ -210,43 +195,17 @@ struct RowCtx {
     }
   }
   // sweep 2 of a chunk whose V' rows were asked for by s2_load
+  // (one fold per dot product: a transpose-reduce of the chunk's eight at K = 32 and the packed multiply / fma
+  //  forms both measured no faster, profiles/r05_row_valu_ab.txt)
   __device__ __forceinline__ void sweep2_loaded(int c, float x, int nchunk, const float4& z, float4& gz, float& ll,
                                                 double& nnf, const float4 (&vv)[LPN]) const {
-    if constexpr (LPN == 8 && ROW_DOT_BUTTERFLY) {
-      // Eight dot products over eight lanes as ONE transpose-reduce instead of eight three-step folds + eight
-      // selects: at every step a lane keeps half of its values and hands the other half to its partner, so it
-      // ends with the ONE total it owns (7 exchanges + 14 selects against 24 + 8; the row pass is as close
-      // to its VALU issue rate as to its request rate: DESIGN section 4 "Round 5 (g)").  Partners: lane ^ 1, lane ^ 2
-      // (quad_perm), then 7 - lane (row_half_mirror: the upper quad therefore keeps by the complement of its lane
-      // bits, eff), so lane `sub` ends with the total of gather own(sub) = sub < 4 ? sub : 11 - sub.
-      float d[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) d[j] = dot4p(z, vv[j]);
-      const int eff = sub < 4 ? sub : 7 - sub;
-      const bool m0 = (eff & 1) != 0, m1 = (eff & 2) != 0, hi = sub >= 4;
-      float r4[4], q2[2];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float keep = m0 ? d[2 * i + 1] : d[2 * i], send = m0 ? d[2 * i] : d[2 * i + 1];
-        r4[i] = dpp_add_to<0xB1>(keep, send);
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const float keep = m1 ? r4[2 * i + 1] : r4[2 * i], send = m1 ? r4[2 * i] : r4[2 * i + 1];
-        q2[i] = dpp_add_to<0x4E>(keep, send);
-      }
-      const float keep = hi ? q2[1] : q2[0], send = hi ? q2[0] : q2[1];
-      const float rmine = dpp_add_to<0x141>(keep, send);
-      s2_cells<true>(c, x, nchunk, rmine, vv, gz, ll, nnf);
-      return;
-    }
     float rmine = 0.f;
 #pragma unroll
     for (int g0 = 0; g0 < LPN; g0 += GRP) {
       if (g0 * NPI < nchunk) {
 #pragma unroll
         for (int j = 0; j < GRP; ++j) {
-          const float dot = group_sum<LPN>(ROW_DOT_PK ? dot4p(z, vv[g0 + j]) : dot4(z, vv[g0 + j]));
+          const float dot = group_sum<LPN>(dot4(z, vv[g0 + j]));
           if (sub == g0 + j) rmine = dot;
         }
       }
@@ -267,13 +226,10 @@ struct RowCtx {
     s2_cells(c, x, nchunk, rmine, vv, gz, ll, nnf);
   }
   // the per-cell part of sweep 2 (one entry per lane) and the gz partial
-  // PERM: the lane owns gather own(sub) = sub < 4 ? sub : 11 - sub (what the transpose-reduce of sweep2_loaded leaves)
-  template <bool PERM = false>
   __device__ __forceinline__ void s2_cells(int c, float x, int nchunk, float rmine, const float4 (&vv)[LPN],
                                            float4& gz, float& ll, double& nnf) const {
-    // one entry per lane: lane (grp,sub) owns slot own*NPI+grp
-    const int own = PERM ? (sub < 4 ? sub : 11 - sub) : sub;
-    const int slot = own * NPI + grp;
+    // one entry per lane: lane (grp,sub) owns slot sub*NPI+grp
+    const int slot = sub * NPI + grp;
     const float xs = __shfl(x, slot);
     const int cs = __shfl(c, slot);
     float cc = 0.f;
@@ -312,7 +268,7 @@ struct RowCtx {
     }
 #pragma unroll
     for (int g0 = 0; g0 < LPN; g0 += GRP) {
-      if (g0 * NPI < nchunk) s2_back<GRP, PERM>(cc, g0, vv, gz);
+      if (g0 * NPI < nchunk) s2_back<GRP>(cc, g0, vv, gz);
     }
   }
 };
@@ -376,8 +332,9 @@ __global__ __launch_bounds__(BT, BT == 256 ? ROW_WAVES_PER_SIMD : 4) void row_pa
   // range), so a wave that fell behind -- longer rows, a slower corner of the chip -- takes fewer of them and
   // the launch no longer ends with most waves waiting for the unluckiest one (the stored entries of a wave's
   // fixed share scatter by sqrt(rows per wave): +6.7 % at the largest of 4096 waves on the 8-GPU shard of
-  // C3, +2.4 % on the whole matrix).  The counters are the spare fp64 slot [5] of the sixteen replicas of the
-  // scalar block (common.h: zeroed by the prep launch with everything else in it, never read as a sum).
+  // C3, +2.4 % on the whole matrix).  The counters are fp64 slot [kDaccDynSlot] of the sixteen replicas of the
+  // scalar block (common.h: zeroed by the prep launch with everything else in it; the fold of the replicas skips
+  // the slot, so its tail pair is always zero).
   // Off (B_static = B) in the deterministic mode -- which workgroup sums which rows must not depend on timing
   // there -- and for launches that share a step's scalar block with another row launch (dyn_tail = 0).
   int64_t B_static = B;
@@ -394,7 +351,7 @@ __global__ __launch_bounds__(BT, BT == 256 ? ROW_WAVES_PER_SIMD : 4) void row_pa
       dyn_lo = B_static + r * each;
       dyn_hi = dyn_lo + each < B ? dyn_lo + each : B;
       if (dyn_lo > B) dyn_lo = B;
-      dyn_ctr = reinterpret_cast<unsigned int*>(dacc + (size_t)r * (kDaccHead + KP) + 5);
+      dyn_ctr = reinterpret_cast<unsigned int*>(dacc + (size_t)r * (kDaccHead + KP) + kDaccDynSlot);
     }
   }
   // the row after `cur` in this wave's sequence when it is a fixed one, else -1 (ask the counter)
@@ -678,10 +635,6 @@ static bool launch_row_lds(const RowArgs& a, hipStream_t st) {
   return a.ent ? launch_row_lds_t<KP, LIK, BT, 1>(a, st) : launch_row_lds_t<KP, LIK, BT, 0>(a, st);
 }
 
-#ifndef ROW_LDS_PHI
-#define ROW_LDS_PHI 1
-#endif
-
 template <int KP>
 static bool launch_row_t(const RowArgs& a, hipStream_t st) {
   int64_t want = (a.B + 3) / 4;  // 4 waves (rows in flight) per 256-thread block
@@ -689,13 +642,13 @@ static bool launch_row_t(const RowArgs& a, hipStream_t st) {
   // phi from LDS: the sweep-2 forms of the Poisson likelihoods at the K of the named
   // configs, when 4*D bytes fit (and the batch is big enough to fill the wider blocks)
   if constexpr (KP >= 16) {
-    if (ROW_LDS_PHI && a.mode == 1 && a.B >= 4096) {
+    if (a.mode == 1 && a.B >= 4096) {
       // sweep 1 alone (z from the encoder side) does not depend on the likelihood: the
       // resident-set launch of the 512-thread form, without the phi copy.  C4: 8.6 -> 6.4 ms
       // against the 256-thread grid (profiles/r03_sparse_pass_attempts.txt e25)
       if (launch_row_lds<KP, 0, 512>(a, st)) return true;
     }
-    if (ROW_LDS_PHI && a.mode != 1 && a.logt >= 0 && a.logt <= 3 && a.B >= 4096) {
+    if (a.mode != 1 && a.logt >= 0 && a.logt <= 3 && a.B >= 4096) {
       // (likelihood codes 2 and 3, Bernoulli and mixed, since the end of round 3: their
       //  stored-cell sweep read phi one entry per lane from global memory, C5 0.61 ms)
       const size_t need = (size_t)a.D * 4;
