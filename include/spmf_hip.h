@@ -507,6 +507,30 @@ int spmf_dense_ll(spmf_ctx* ctx, const spmf_counts* counts, const float* u,
                   const float* v, const float* w, const float* s,
                   const float* eta, float* rate_out, float* ll_out, void* stream);
 
+/* ---- streaming WAIC (added within ABI 6: two new entry points, no struct changed) ----
+ * The pointwise criterion over the cells (b, d) of `counts` for S >= 2 draws, without a
+ * [S,B,D] or [B,D] tensor (csrc/waic.hip).  With ll_s = log p(x_bd | theta_s), by the per-cell
+ * formulas of spmf_dense_ll:
+ *   lppd_i = logsumexp_s(ll_s) - log S,  pwaic_i = unbiased var_s(ll_s),  elpd_i = lppd_i - pwaic_i
+ * ADDED to the caller's sums6 = double[6] (zero it before the first call; batches and row shards
+ * add up):  [0] cells counted  [1] sum lppd_i  [2] sum pwaic_i  [3] sum elpd_i^2
+ *           [4] cells excluded  [5] spare.
+ * A cell is excluded, and counted in [4] instead of [0..3], when any of its S values is not
+ * finite (a NaN count, a rate of 0 under a positive count).  row_out (NULL = skip) = double
+ * [n_rows][2], ADDED to: (sum_d lppd_i, sum_d pwaic_i) of every row over its counted cells.
+ * params: only u, v, w, s (slots 2, 0, 1, 7) are read, each with the leading axis S.
+ * scratch: 256-byte aligned, at least spmf_waic_scratch_bytes(ctx, counts->n_rows, S) bytes
+ * (the S draws' tables, 2 * S * D * KP floats, and encoded rows, S * n_rows * KP floats: call it
+ * over row chunks to bound it); SPMF_E_WORKSPACE when short.  SPMF_E_ARG for S < 2, NULL pointers
+ * or a struct_size mismatch.  The context's workspace is not touched: the call may sit between
+ * other calls on the context, a spmf_step_begin .. spmf_step_end pair included.  Stream-ordered,
+ * synchronises nowhere; the fp64 sums are atomics (not bit-reproducible). */
+size_t spmf_waic_scratch_bytes(const spmf_ctx* ctx, int64_t n_rows, int S);
+int spmf_waic_accumulate(spmf_ctx* ctx, const spmf_counts* counts, int S,
+                         const float* const params[SPMF_NVARS], const float* eta,
+                         double* sums6, double* row_out, void* scratch,
+                         size_t scratch_bytes, void* stream);
+
 /* Reductions of the non-finite rule (poisson.py:606-616) over a dense ll
  * buffer of n cells; io = double[3] on the device.
  *   pass 0: io[0] = min(io[0], min over finite cells)  (initialise io[0]=0:

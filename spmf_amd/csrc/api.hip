@@ -1111,6 +1111,81 @@ int spmf_dense_ll(spmf_ctx* c, const spmf_counts* ct, const float* u, const floa
   return SPMF_OK;
 }
 
+// ---- streaming WAIC (waic.hip) ------------------------------------------------------------
+// Scratch of one call: the S draws' tables and encoded rows.  The context's workspace is not used, so
+// a step that is bound (or half way: spmf_step_begin .. spmf_step_end) keeps everything it has.
+struct WaicCarve {
+  size_t Ap, Vp, phi, dprep, dacc, z, total;
+};
+static WaicCarve waic_carve(const spmf_ctx* c, int64_t rows, int S) {
+  WaicCarve k;
+  size_t o = 0;
+  const size_t KP = c->KP, D = c->D, nS = S;
+  k.Ap = o;    o += al(nS * D * KP * sizeof(float));
+  k.Vp = o;    o += al(nS * D * KP * sizeof(float));
+  k.phi = o;   o += al(nS * D * sizeof(float));
+  k.dprep = o; o += al(nS * kPrepSeg * (KP + 1) * sizeof(double));
+  k.dacc = o;  o += al((size_t)kDaccRep * (kDaccHead + KP) * sizeof(double));
+  k.z = o;     o += al(nS * (size_t)rows * KP * sizeof(float));
+  k.total = o;
+  return k;
+}
+
+size_t spmf_waic_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S) {
+  if (!c || n_rows < 0 || S < 2) return 0;
+  return waic_carve(c, n_rows, S).total;
+}
+
+int spmf_waic_accumulate(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS],
+    const float* eta, double* sums6, double* row_out, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!c) return SPMF_E_ARG;
+  if (S < 2 || S > 65535) return fail(c, SPMF_E_ARG, "waic_accumulate: S must be in 2..65535 (the variance over "
+      "the draws needs two)");
+  if (!params || !eta || !sums6 || !scratch) return fail(c, SPMF_E_ARG, "waic_accumulate: null argument");
+  const float *u = params[2], *v = params[0], *w = params[1], *s = params[7];
+  if (!u || !v || !w || !s) return fail(c, SPMF_E_ARG, "waic_accumulate: params u, v, w, s (slots 2, 0, 1, 7) "
+      "must be set, each [S, ...]");
+  if ((uintptr_t)scratch & 255) return fail(c, SPMF_E_ARG, "waic_accumulate: scratch must be 256-byte aligned");
+  const int lik = likelihood_code(c);
+  if (lik == 3 && !c->ctype) return fail(c, SPMF_E_ARG, "waic_accumulate: spmf_ctx_set_column_types was not called");
+  const int logt = lik_exp(lik) ? 1 : 0;
+  int rc = check_counts(c, ct);
+  if (!rc && logt && ct->nnz > 0 && !ct->gval) rc = fail(c, SPMF_E_ARG, "waic_accumulate: log_transform needs counts.gval");
+  if (rc) return rc;
+  if ((int64_t)(c->D + 63) / 64 > 65535) return fail(c, SPMF_E_UNSUPPORTED, "waic_accumulate: D above 65535 * 64");
+  // the encode sweep of S draws gathers z with 32-bit byte offsets per draw; the dense kernel's row blocks
+  // are a 31-bit grid extent
+  if (ct->n_rows > ((int64_t)1 << 31) - 64) return fail(c, SPMF_E_ARG, "waic_accumulate: too many rows in one call");
+  const WaicCarve k = waic_carve(c, ct->n_rows, S);
+  if (k.total > scratch_bytes) {
+    char b[160];
+    snprintf(b, sizeof b, "waic_accumulate: scratch too small: need %zu bytes for rows=%lld S=%d, have %zu", k.total,
+        (long long)ct->n_rows, S, scratch_bytes);
+    return fail(c, SPMF_E_WORKSPACE, b);
+  }
+  if (ct->n_rows == 0) return SPMF_OK;
+  hipStream_t st = (hipStream_t)stream;
+  char* base = (char*)scratch;
+  float* Ap = (float*)(base + k.Ap);
+  float* Vp = (float*)(base + k.Vp);
+  float* phi = (float*)(base + k.phi);
+  float* z = (float*)(base + k.z);
+  PrepArgs pa{c->D, c->K, u, v, w, s, eta, Ap, Vp, phi, (double*)(base + k.dprep), logt, nullptr, nullptr};
+  pa.S = S;
+  launch_prep(c->KP, pa, st);
+  // the encode-only sweep (mode 1) writes z and nothing else: gzs and the scalar block are never touched
+  RowArgs ra{ct->n_rows, ct->row_ptr, ct->col_idx, logt ? ct->gval : ct->val,
+      (c->flags & SPMF_FLAG_SCALE_ROWS) ? ct->row_scale : nullptr, Ap, Vp, phi, (const double*)(base + k.dprep), z, z,
+      (double*)(base + k.dacc), 1, logt, nullptr, nullptr, S, c->D, 0};
+  if (!logt) ra.ent = ct->ent;
+  if (!launch_row_pass(c->KP, ra, st)) return fail(c, SPMF_E_UNSUPPORTED, "waic_accumulate: no encode kernel for this K");
+  WaicArgs wa{ct->n_rows, ct->nnz, c->D, c->KP, S, lik, z, Vp, phi, c->ctype, ct->row_ptr, ct->col_idx, ct->val,
+      sums6, row_out};
+  if (!launch_waic(wa, st)) return fail(c, SPMF_E_UNSUPPORTED, "waic_accumulate: no kernel for this K / likelihood");
+  HIPCHK(c, hipGetLastError());
+  return SPMF_OK;
+}
+
 int spmf_nonfinite_reduce(spmf_ctx* c, int64_t n, const float* ll, int pass, double* io, void* stream) {
   if (!c || !ll || !io || n < 0 || (pass != 0 && pass != 1)) return fail(c, SPMF_E_ARG,
       "nonfinite_reduce: bad arguments");

@@ -173,6 +173,20 @@ struct NfPatchArgs {
 };
 void launch_nonfinite_patch(int KP, const NfPatchArgs& a, hipStream_t st);
 void launch_nonfinite_lgamma(const DenseLLArgs& a, double* out, hipStream_t st);   // uses B, D, logt, ctype, CSR, rate
+// waic.hip: per-cell lppd / pwaic over S draws, summed over the cells of the batch (sums6: [0] cells counted,
+// [1] sum lppd, [2] sum pwaic, [3] sum elpd^2, [4] excluded cells; accumulated).  false: KP / lik not built.
+struct WaicArgs {
+  int64_t B, nnz;
+  int D, KP, S, lik;               // lik = likelihood code 0..4 (common.h)
+  const float *z, *Vp, *phi;       // [S,B,KP], [S,D,KP], [S,D]
+  const uint8_t* ctype;
+  const int32_t* row_ptr;
+  const int32_t* col;
+  const float* val;
+  double* sums;                    // [6]
+  double* row_out;                 // [B][2] (sum_d lppd, sum_d pwaic), accumulated; may be null
+};
+bool launch_waic(const WaicArgs& a, hipStream_t st);
 bool launch_col_pass(int KP, const ColArgs& a, hipStream_t st);   // true: launched, with the pack block if asked
 bool launch_col_widek(int KP, const ColArgs& a, hipStream_t st);  // KP = 128, 256 (widek.hip)
 

@@ -1,0 +1,335 @@
+// waic.hip -- streaming WAIC: per-cell lppd / pwaic over S draws, summed over the cells of a
+// batch, without a [S,B,D] (or [B,D]) tensor.
+//
+// A point is one cell (b, d).  With ll_s = log p(x_bd | theta_s), s = 0 .. S-1:
+//   lppd_i  = logsumexp_s(ll_s) - log S
+//   pwaic_i = unbiased var_s(ll_s)
+//   elpd_i  = lppd_i - pwaic_i
+// and the call adds  #cells, sum lppd_i, sum pwaic_i, sum elpd_i^2, #excluded cells  to a
+// caller-owned double[6] (a cell with a non-finite ll_s in any draw is excluded and counted).
+//
+// Two launches over the per-draw tables z[S,B,KP] (encode sweep), V'[S,D,KP], phi[S,D] (prep):
+//   waic_dense_kernel : EVERY cell as if x = 0.  A workgroup owns a 64 x 64 block of cells, a
+//     wave a 32 x 32 tile: y_s = <z_sb, V'_sd> on the exact-f32 matrix cores
+//     (v_mfma_f32_32x32x2_f32, the accumulator layout of dense.hip), the four statistics of a
+//     cell -- running maximum, rescaled sum of exp, running mean, sum of squared deviations --
+//     stay in registers across the loop over draws (16 cells per lane), operand tiles of the
+//     next (draw, K chunk) are fetched while the current one is multiplied.
+//   waic_fix_kernel   : the stored cells, one wave per row, one lane per entry: the same
+//     statistics for the x = 0 value and for the true count, both by fp32 FMA from the same
+//     tables; the x = 0 contribution is taken out of the sums and the true one put in (the
+//     sums are additive over cells).  lgamma(x+1) does not depend on the draw: it cancels in
+//     the variance and is subtracted from lppd_i once, behind the loop.
+// The log-mean-exp carries a running maximum, so a cell whose every ll_s is below -1000 is as
+// exact as any other.
+#include "common.h"
+#include "kernels.h"
+
+namespace spmf {
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// running statistics of one cell over the draws
+__device__ __forceinline__ void stat_update(float ll, float inv_n, float& m, float& se, float& mu, float& q) {
+  const float d = ll - m;
+  const float e = expf(-fabsf(d));
+  se = d > 0.f ? fmaf(se, e, 1.f) : se + e;    // first draw: m = -inf, d = +inf, e = 0 -> se = 1
+  m = fmaxf(m, ll);
+  const float dl = ll - mu;                    // Welford; a non-finite ll leaves q non-finite for good
+  mu = fmaf(dl, inv_n, mu);
+  q = fmaf(dl, ll - mu, q);
+}
+
+__device__ __forceinline__ float softplusf(float r) { return fmaxf(r, 0.f) + log1pf(expf(-fabsf(r))); }
+
+template <int LIK>
+__device__ __forceinline__ float rate_of(float y, float ph) {
+  float ey;
+  return (lik_exp(LIK) ? expm1_dec(fminf(y, kYSat), ey) : y) + ph;
+}
+
+__device__ __forceinline__ double half_sum(double v) {   // over the 32 lanes of a wave half
+#pragma unroll
+  for (int m = 16; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+  return v;
+}
+
+}  // namespace
+
+// KC: floats of the K axis per LDS tile (8, 16, 32); KP > KC runs KP / KC chunks per draw
+template <int KC, int LIK>
+__global__ __launch_bounds__(256) void waic_dense_kernel(int64_t B, int D, int KP, int S,
+                                                         const float* __restrict__ z,
+                                                         const float* __restrict__ Vp,
+                                                         const float* __restrict__ phi,
+                                                         const uint8_t* __restrict__ ctype,
+                                                         double* __restrict__ sums,
+                                                         double* __restrict__ row_out) {
+  constexpr int PITCH = KC + 4;
+  constexpr int NLD = KC / 8;          // float4 per thread and (draw, chunk): 2 tiles x 64 rows x KC floats
+  constexpr int TQ = 16 * KC;          // float4 per tile
+  __shared__ float tiles[2][2][64][PITCH];
+  __shared__ double red[16];
+  const int t = threadIdx.x;
+  const int lane = t & 63, wv = t >> 6;
+  const int i32 = lane & 31, h = lane >> 5;
+  const int wr = wv >> 1, wc = wv & 1;
+  const int64_t b0 = (int64_t)blockIdx.x * 64;
+  const int d0 = blockIdx.y * 64;
+  const int NCH = KP > KC ? KP / KC : 1;
+  const int NIT = S * NCH;
+  const int d = d0 + wc * 32 + i32;
+  const bool bern = lik_bern(LIK) || (LIK == 3 && d < D && ctype[d]);
+
+  auto fetch = [&](int it, float4* pre) {
+    const int s = it / NCH, kc0 = (it % NCH) * KC;
+#pragma unroll
+    for (int j = 0; j < NLD; ++j) {
+      const int idx = t + 256 * j;
+      const int tile = idx / TQ, rem = idx % TQ;
+      const int row = rem / (KC / 4), k = kc0 + 4 * (rem % (KC / 4));
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (k < KP) {
+        if (tile == 0) {
+          if (b0 + row < B) v = *reinterpret_cast<const float4*>(z + ((size_t)s * B + b0 + row) * KP + k);
+        } else {
+          if (d0 + row < D) v = *reinterpret_cast<const float4*>(Vp + ((size_t)s * D + d0 + row) * KP + k);
+        }
+      }
+      pre[j] = v;
+    }
+  };
+  auto stash = [&](int buf, const float4* pre) {
+#pragma unroll
+    for (int j = 0; j < NLD; ++j) {
+      const int idx = t + 256 * j;
+      const int tile = idx / TQ, rem = idx % TQ;
+      *reinterpret_cast<float4*>(&tiles[buf][tile][rem / (KC / 4)][4 * (rem % (KC / 4))]) = pre[j];
+    }
+  };
+
+  float m[16], se[16], mu[16], q[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    m[r] = -INFINITY;
+    se[r] = 0.f;
+    mu[r] = 0.f;
+    q[r] = 0.f;
+  }
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+
+  float4 pre[NLD];
+  fetch(0, pre);
+  stash(0, pre);
+  __syncthreads();
+  float ph = 0.f;
+  for (int it = 0; it < NIT; ++it) {
+    const int buf = it & 1;
+    const int s = it / NCH, ch = it % NCH;
+    if (it + 1 < NIT) fetch(it + 1, pre);
+    if (ch == 0) ph = d < D ? phi[(size_t)s * D + d] : 0.f;
+    // lane half h takes k = 8 q + 4 h + e of the chunk for both operands: the pairing of the k
+    // values inside a step is free as long as A and B agree
+    const float* ar = &tiles[buf][0][wr * 32 + i32][4 * h];
+    const float* br = &tiles[buf][1][wc * 32 + i32][4 * h];
+#pragma unroll
+    for (int qk = 0; qk < KC / 8; ++qk) {
+      const float4 a = *reinterpret_cast<const float4*>(ar + 8 * qk);
+      const float4 b = *reinterpret_cast<const float4*>(br + 8 * qk);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
+    }
+    if (ch == NCH - 1) {
+      const float inv_n = 1.f / (float)(s + 1);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float rt = rate_of<LIK>(acc[r], ph);
+        const float ll = bern ? -softplusf(rt) : -rt;     // x = 0: 0 * log r := 0
+        stat_update(ll, inv_n, m[r], se[r], mu[r], q[r]);
+        acc[r] = 0.f;
+      }
+    }
+    if (it + 1 < NIT) stash(buf ^ 1, pre);
+    __syncthreads();
+  }
+
+  const double logS = log((double)S), inv_sm1 = 1.0 / (double)(S - 1);
+  double an = 0.0, aL = 0.0, aP = 0.0, aE = 0.0, ax = 0.0;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int64_t b = b0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+    const bool in = b < B && d < D;
+    const double lp = (double)m[r] + (double)logf(se[r]) - logS;
+    const double pw = (double)q[r] * inv_sm1;
+    const bool fin = isfinite(lp) && isfinite(pw);
+    if (in && fin) {
+      const double e = lp - pw;
+      an += 1.0;
+      aL += lp;
+      aP += pw;
+      aE += e * e;
+    } else if (in) {
+      ax += 1.0;
+    }
+    if (row_out) {                                        // block-uniform
+      const double rl = half_sum(in && fin ? lp : 0.0);
+      const double rp = half_sum(in && fin ? pw : 0.0);
+      if (i32 == 0 && b < B) {
+        atomicAdd(&row_out[2 * b], rl);
+        atomicAdd(&row_out[2 * b + 1], rp);
+      }
+    }
+  }
+  const double tn = block_sum(an, red);
+  const double tL = block_sum(aL, red);
+  const double tP = block_sum(aP, red);
+  const double tE = block_sum(aE, red);
+  const double tx = block_sum(ax, red);
+  if (t == 0) {
+    atomicAdd(&sums[0], tn);
+    atomicAdd(&sums[1], tL);
+    atomicAdd(&sums[2], tP);
+    atomicAdd(&sums[3], tE);
+    if (tx != 0.0) atomicAdd(&sums[4], tx);
+  }
+}
+
+// stored cells: x = 0 statistics out, true statistics in.  One wave per row, one lane per entry.
+__global__ __launch_bounds__(256) void waic_fix_kernel(int64_t B, int D, int KP, int S, int lik,
+                                                       const int32_t* __restrict__ row_ptr,
+                                                       const int32_t* __restrict__ col,
+                                                       const float* __restrict__ val,
+                                                       const float* __restrict__ z,
+                                                       const float* __restrict__ Vp,
+                                                       const float* __restrict__ phi,
+                                                       const uint8_t* __restrict__ ctype,
+                                                       double* __restrict__ sums,
+                                                       double* __restrict__ row_out) {
+  __shared__ double red[16];
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  const double logS = log((double)S), inv_sm1 = 1.0 / (double)(S - 1);
+  const int K4 = KP / 4;
+  double an = 0.0, aL = 0.0, aP = 0.0, aE = 0.0, ax = 0.0;
+  for (int64_t b = wave; b < B; b += nwaves) {
+    const int start = row_ptr[b], end = row_ptr[b + 1];
+    double rl = 0.0, rp = 0.0;
+    for (int i = start + lane; i < end; i += 64) {
+      const float x = val[i];
+      const int d = col[i];
+      const bool bern = lik_bern(lik) || (lik == 3 && ctype[d]);
+      float m0 = -INFINITY, e0 = 0.f, u0 = 0.f, q0 = 0.f;
+      float m1 = -INFINITY, e1 = 0.f, u1 = 0.f, q1 = 0.f;
+      for (int s = 0; s < S; ++s) {
+        const float4* zr = reinterpret_cast<const float4*>(z + ((size_t)s * B + b) * KP);
+        const float4* vr = reinterpret_cast<const float4*>(Vp + ((size_t)s * D + d) * KP);
+        float y = 0.f;
+        for (int k = 0; k < K4; ++k) {
+          const float4 a = zr[k], v = vr[k];
+          y = fmaf(a.x, v.x, y);
+          y = fmaf(a.y, v.y, y);
+          y = fmaf(a.z, v.z, y);
+          y = fmaf(a.w, v.w, y);
+        }
+        float ey;
+        const float rt = (lik_exp(lik) ? expm1_dec(fminf(y, kYSat), ey) : y) + phi[(size_t)s * D + d];
+        float l0, l1;
+        if (bern) {
+          // tfd.Bernoulli(logits).log_prob(x) = x*l - softplus(l)
+          const float sp = softplusf(rt);
+          l0 = -sp;
+          l1 = x * rt - sp;
+        } else {
+          // tfd.Poisson.log_prob without lgamma(x+1): multiply_no_nan(log r, x) - r
+          l0 = -rt;
+          l1 = (x == 0.f ? 0.f : x * logf(rt)) - rt;
+        }
+        const float inv_n = 1.f / (float)(s + 1);
+        stat_update(l0, inv_n, m0, e0, u0, q0);
+        stat_update(l1, inv_n, m1, e1, u1, q1);
+      }
+      const double lg = bern ? 0.0 : (double)lgammaf(x + 1.f);
+      const double lp0 = (double)m0 + (double)logf(e0) - logS, pw0 = (double)q0 * inv_sm1;
+      const double lp1 = (double)m1 + (double)logf(e1) - logS - lg, pw1 = (double)q1 * inv_sm1;
+      if (isfinite(lp0) && isfinite(pw0)) {
+        const double e = lp0 - pw0;
+        an -= 1.0; aL -= lp0; aP -= pw0; aE -= e * e;
+        rl -= lp0; rp -= pw0;
+      } else {
+        ax -= 1.0;
+      }
+      if (isfinite(lp1) && isfinite(pw1)) {
+        const double e = lp1 - pw1;
+        an += 1.0; aL += lp1; aP += pw1; aE += e * e;
+        rl += lp1; rp += pw1;
+      } else {
+        ax += 1.0;
+      }
+    }
+    if (row_out && end > start) {                          // wave-uniform
+      rl = wave_sum(rl);
+      rp = wave_sum(rp);
+      if (lane == 0) {
+        atomicAdd(&row_out[2 * b], rl);
+        atomicAdd(&row_out[2 * b + 1], rp);
+      }
+    }
+  }
+  const double tn = block_sum(an, red);
+  const double tL = block_sum(aL, red);
+  const double tP = block_sum(aP, red);
+  const double tE = block_sum(aE, red);
+  const double tx = block_sum(ax, red);
+  if (threadIdx.x == 0) {
+    if (tn != 0.0) atomicAdd(&sums[0], tn);
+    atomicAdd(&sums[1], tL);
+    atomicAdd(&sums[2], tP);
+    atomicAdd(&sums[3], tE);
+    if (tx != 0.0) atomicAdd(&sums[4], tx);
+  }
+}
+
+template <int KC>
+static bool launch_dense_kc(const WaicArgs& a, hipStream_t st) {
+  const dim3 grid((unsigned)((a.B + 63) / 64), (unsigned)((a.D + 63) / 64));
+#define SPMF_WAIC(L_)                                                                                    \
+  hipLaunchKernelGGL((waic_dense_kernel<KC, L_>), grid, dim3(256), 0, st, a.B, a.D, a.KP, a.S, a.z, a.Vp, \
+                     a.phi, a.ctype, a.sums, a.row_out)
+  switch (a.lik) {
+    case 0: SPMF_WAIC(0); break;
+    case 1: SPMF_WAIC(1); break;
+    case 2: SPMF_WAIC(2); break;
+    case 3: SPMF_WAIC(3); break;
+    case 4: SPMF_WAIC(4); break;
+    default: return false;
+  }
+#undef SPMF_WAIC
+  return true;
+}
+
+bool launch_waic(const WaicArgs& a, hipStream_t st) {
+  bool ok;
+  switch (a.KP) {
+    case 4: case 8: ok = launch_dense_kc<8>(a, st); break;
+    case 16: ok = launch_dense_kc<16>(a, st); break;
+    case 32: case 64: case 128: case 256: ok = launch_dense_kc<32>(a, st); break;
+    default: return false;
+  }
+  if (!ok) return false;
+  if (a.nnz > 0) {
+    const int64_t want = (a.B + 3) / 4;
+    const int nb = (int)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
+    hipLaunchKernelGGL(waic_fix_kernel, dim3(nb), dim3(256), 0, st, a.B, a.D, a.KP, a.S, a.lik, a.row_ptr, a.col,
+                       a.val, a.z, a.Vp, a.phi, a.ctype, a.sums, a.row_out);
+  }
+  return true;
+}
+
+}  // namespace spmf

@@ -592,7 +592,9 @@ class PoissonFactorization:
         [UNVERIFIED-3P]; this is the standard pointwise definition over the
         cells of the batch: lppd_i = log mean_s p(x_i|theta_s),
         pwaic_i = var_s log p(x_i|theta_s), waic = -2 sum_i (lppd_i - pwaic_i),
-        se = 2 sqrt(n var_i(lppd_i - pwaic_i))."""
+        se = 2 sqrt(n var_i(lppd_i - pwaic_i)).  It materialises the [S,B,D]
+        log-likelihood (16 bytes per cell and draw); ``waic_streaming`` computes
+        the same sums at any size."""
         if data is None:
             src = getattr(self, "data", None)
             if src is None:
@@ -609,6 +611,78 @@ class PoissonFactorization:
         return {"waic": float(-2.0 * elpd_i.sum()),
                 "se": float(2.0 * torch.sqrt(n * elpd_i.var(unbiased=True))),
                 "lppd": float(lppd_i.sum()), "pwaic": float(pwaic_i.sum())}
+
+    def waic_streaming(self, data, nsamples=100, draws=None, row_scores=False, max_rows=None):
+        """``waic`` at any size: per-cell lppd_i / pwaic_i over the draws are formed in
+        registers (csrc/waic.hip) and only their sums over the cells leave the kernel, so
+        nothing of size S*B*D or B*D is written.
+
+        ``data``: one batch (dict / counts), an iterable of batches or a data-factory
+        callable; the sums are added across batches.  ``draws``: dict with 's','u','v','w' of
+        shape [S,...] (default: ``surrogate_distribution.sample(nsamples)``), the same for every
+        batch.  ``row_scores=True`` adds 'row_lppd' / 'row_pwaic', fp64 tensors concatenated
+        over the batches.  ``max_rows`` caps the rows of one kernel call (whole panels), which
+        bounds the scratch of the encoded rows (S * rows * K floats; default 1 GiB of them).
+
+        Returns {'waic','se','lppd','pwaic','n','n_excluded'} (spmf_amd.waic.combine): a cell
+        with a non-finite log-pmf in any draw (NaN count, rate 0 under a positive count) is
+        left out of the sums and counted in 'n_excluded', where ``waic`` returns NaN / -inf."""
+        from . import waic as _waic
+        if self._custom_codec is not None:
+            raise NotImplementedError("waic_streaming: custom encoder/decoder callables have no kernel "
+                                      "(use waic(), which evaluates them densely)")
+        if draws is None:
+            if int(nsamples) < 2:
+                raise ValueError("waic_streaming needs nsamples >= 2 (the variance over the draws)")
+            draws = self.surrogate_distribution.sample(int(nsamples))
+        S, P = self._pack_params(draws, names=("s", "u", "v", "w"))
+        if S < 2:
+            raise ValueError("waic_streaming needs at least 2 draws (the variance over the draws)")
+        if callable(data):
+            batches = data()
+        elif isinstance(data, (dict, SparseCounts)) or hasattr(data, "shape"):
+            batches = (data,)
+        else:
+            batches = data
+        lib, h = _lib.load(), self._handle()
+        eta = self._eta_device()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        pin = _lib.PtrArray(*[P[n].data_ptr() if n in P else None for n in VAR_ORDER])
+        sums = torch.zeros(_waic.NSUMS, dtype=torch.float64, device=self.device)
+        KP = int(lib.spmf_padded_k(h))
+        scratch, rows_out = None, []
+        for batch in batches:
+            sc, cs = self._batch(batch)
+            pr = batch.get("panels") if isinstance(batch, dict) else None
+            p0, p1 = (pr or (0, None))
+            p1 = sc.n_panels if p1 is None else min(int(p1), sc.n_panels)
+            cap = int(max_rows) if max_rows else max(1, (1 << 28) // (S * KP))
+            step = max(1, cap // sc.panel_rows)
+            rows = torch.zeros(cs.n_rows, 2, dtype=torch.float64, device=self.device) if row_scores else None
+            key = (sc._xi_key, sc._g_key)
+            for q0 in range(int(p0), p1, step):
+                q1 = min(q0 + step, p1)
+                sub = sc.__dict__.setdefault("_struct_cache", {}).setdefault(
+                    ((q0, q1),) + key, sc.batch_struct(q0, q1))
+                if sub.n_rows == 0:
+                    continue
+                need = int(lib.spmf_waic_scratch_bytes(h, int(sub.n_rows), S)) + 256
+                if scratch is None or scratch.numel() < need:
+                    scratch = None
+                    scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+                off = (-scratch.data_ptr()) % 256
+                r0 = (q0 - int(p0)) * sc.panel_rows
+                _lib.check(h, lib.spmf_waic_accumulate(
+                    h, C.byref(sub), S, pin, eta.data_ptr(), sums.data_ptr(),
+                    rows[r0:].data_ptr() if rows is not None else None,
+                    scratch.data_ptr() + off, scratch.numel() - off, stream), "spmf_waic_accumulate")
+            if rows is not None:
+                rows_out.append(rows)
+        out = _waic.combine(sums)
+        if row_scores:
+            allrows = torch.cat(rows_out) if rows_out else torch.zeros(0, 2, dtype=torch.float64, device=self.device)
+            out["row_lppd"], out["row_pwaic"] = allrows[:, 0].contiguous(), allrows[:, 1].contiguous()
+        return out
 
     def _nonfinite_scan(self, sc, cs, data, S, P, max_cells=1 << 27):
         """Dense part of the replacement rule (poisson.py:606-616): the minimum
