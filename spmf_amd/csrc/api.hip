@@ -62,8 +62,6 @@ struct spmf_ctx {
   float* est = nullptr;
   int64_t est_rows = 0;           // rows per chunk of the bound workspace
   int e_once = 1;                 // SPMF_DENSE_E_ONCE=0: recompute E in a second launch instead
-  int dyn_rows = 1;               // the row pass hands the last eighth of its rows out dynamically (row_pass.hip);
-                                  // SPMF_ROW_DYNAMIC=0: the fixed stride everywhere
   int dense3 = 1;                 // exp sums on the bf16 matrix cores with three-way split operands
                                   // (dense3.hip; Poisson log_transform at KP = 64 only);
                                   // SPMF_DENSE_BF16X3=0 selects the exact-f32 MFMA kernels (dense.hip)
@@ -319,7 +317,6 @@ int spmf_ctx_create(int device, int K, int D, unsigned flags, spmf_ctx** out) {
   c->flags = flags;
   if (const char* e = getenv("SPMF_DENSE_E_ONCE")) c->e_once = e[0] != '0';
   if (const char* e = getenv("SPMF_DENSE_BF16X3")) c->dense3 = e[0] != '0';
-  if (const char* e = getenv("SPMF_ROW_DYNAMIC")) c->dyn_rows = e[0] != '0' ? 1 : 0;
   *out = c;
   return SPMF_OK;
 }
@@ -596,14 +593,89 @@ int spmf_ctx_set_deterministic(spmf_ctx* c, void* scratch, size_t bytes) {
   return SPMF_OK;
 }
 
-// spmf_prior_async, spmf_finish and the step: the finish kernels' arguments without the data half's (acc, dprep,
-// n_nonfinite, B_global, lgamma_sum, acc_stride: the callers that launch it set them)
+// ---- the launches' argument blocks, each built in one place and by name ----------------------
+// The per-draw tables and row outputs a launch sequence works on: those of the bound workspace (draw 0), or the
+// caller's scratch (spmf_waic_accumulate)
+struct Tables {
+  float *Ap, *Vp, *phi;
+  double *dprep, *dacc;
+  float *z, *gzs;
+};
+static Tables ws_tables(const spmf_ctx* c) { return Tables{c->Ap, c->Vp, c->phi, c->dprep, c->dacc, c->z, c->gzs}; }
+
+static const float* row_scale_of(const spmf_ctx* c, const spmf_counts* ct) {
+  return (c->flags & SPMF_FLAG_SCALE_ROWS) ? ct->row_scale : nullptr;
+}
+
+// S draws per launch; u, v, w, s are those of the launch's first draw.  (The mixed likelihood's ctype / dbias
+// and the zero fill are the data pass's own.)
+static PrepArgs prep_args(const spmf_ctx* c, int S, const Tables& T, const float* u, const float* v, const float* w,
+    const float* s, const float* eta) {
+  PrepArgs pa{};
+  pa.D = c->D; pa.K = c->K; pa.S = S;
+  pa.u = u; pa.v = v; pa.w = w; pa.s = s; pa.eta = eta;
+  pa.Ap = T.Ap; pa.Vp = T.Vp; pa.phi = T.phi; pa.dprep = T.dprep;
+  pa.logt = lik_exp(likelihood_code(c)) ? 1 : 0;
+  return pa;
+}
+
+// The full row launch (mode 0) over the counts; `lik` is the likelihood code the kernel is built for.
+static RowArgs row_args(const spmf_ctx* c, const spmf_counts* ct, int S, const Tables& T, int lik,
+    int64_t dacc_stride) {
+  RowArgs ra{};
+  ra.B = ct->n_rows; ra.D = c->D; ra.S = S;
+  ra.row_ptr = ct->row_ptr; ra.col = ct->col_idx; ra.val = ct->val; ra.ent = ct->ent;
+  ra.row_scale = row_scale_of(c, ct);
+  ra.Ap = T.Ap; ra.Vp = T.Vp; ra.phi = T.phi; ra.dprep = T.dprep;
+  ra.z = T.z; ra.gzs = T.gzs; ra.dacc = T.dacc; ra.dacc_stride = dacc_stride;
+  ra.mode = 0; ra.logt = lik; ra.ctype = lik == 3 ? c->ctype : nullptr;
+  return ra;
+}
+// The encode-only sweep (mode 1) of `ra`: z from g(x) under the exp decoders (g has no packed stream), and
+// never the dynamic tail -- its counters are the full launch's alone.
+static RowArgs encode_sweep(RowArgs ra, const spmf_counts* ct) {
+  ra.mode = 1;
+  ra.dyn_tail = 0;
+  if (lik_exp(ra.logt)) {
+    ra.val = ct->gval;
+    ra.ent = nullptr;
+  }
+  return ra;
+}
+
+// The column pass over column half hf of the accumulators `acc` (hf = 0 without a split: all columns); the
+// pack block and the deterministic scratch are the data pass's own.
+static ColArgs col_args(const spmf_ctx* c, const spmf_counts* ct, int S, const Tables& T, float* acc,
+    const AccLayout& L, int hf) {
+  const bool split = c->Dh > 0;
+  ColArgs ca{};
+  ca.D = c->D; ca.B = ct->n_rows; ca.S = S;
+  ca.n_panels = ct->n_panels; ca.row_base = ct->row_base; ca.panel_rows = ct->panel_rows;
+  ca.item_ptr = ct->item_ptr; ca.items = ct->items;
+  ca.max_items_per_panel = split ? ct->max_items_half[hf] : ct->max_items_per_panel;
+  ca.item_mid = split ? ct->item_mid : nullptr; ca.half_sel = split ? hf + 1 : 0;
+  ca.pc_row = ct->pc_row; ca.pc_val = ct->pc_val; ca.pc_gval = ct->pc_gval; ca.pc_ent = ct->pc_ent;
+  ca.pc_pad = ct->pc_pad;
+  ca.Vp = T.Vp; ca.phi = T.phi; ca.z = T.z; ca.gzs = T.gzs;
+  ca.gAp = acc + L.gA_off(hf); ca.gVp = acc + L.gV_off(hf); ca.gphi = acc + L.gphi_off(hf);
+  ca.acc_stride = acc_len(c->D, c->KP);
+  ca.logt = likelihood_code(c); ca.ctype = c->ctype;
+  return ca;
+}
+
+// spmf_prior_async, spmf_finish and the step: the finish kernels' arguments without the data half's
+// (finish_data_half sets them)
 static FinishArgs finish_args(const spmf_ctx* c, int S, double prior_weight, const float* const* params,
     const float* eta, float* const* grads, double* parts) {
-  FinishArgs fa{c->D, c->K, 0, 0.0, c->u_tau_scale, c->s_tau_scale, c->decay, prior_weight, nullptr, nullptr, params,
-      eta, grads, parts, nullptr, likelihood_code(c), c->ctype, c->Dh, S, 0, {},
-      (c->flags & SPMF_FLAG_ABS_HORSESHOE) ? 1 : 0, c->fpart, c->futau};
+  FinishArgs fa{};
+  fa.D = c->D; fa.K = c->K; fa.Dh = c->Dh; fa.S = S;
+  fa.u_tau_scale = c->u_tau_scale; fa.s_tau_scale = c->s_tau_scale; fa.decay = c->decay;
+  fa.prior_weight = prior_weight;
+  fa.params = params; fa.eta = eta; fa.grads = grads; fa.parts = parts;
+  fa.logt = likelihood_code(c); fa.ctype = c->ctype;
+  fa.abs_horseshoe = (c->flags & SPMF_FLAG_ABS_HORSESHOE) ? 1 : 0;
   for (int i = 0; i < SPMF_NVARS; ++i) fa.vstride[i] = (int64_t)var_size(c, i);
+  fa.ppart = c->fpart; fa.putau = c->futau;
   return fa;
 }
 
@@ -614,23 +686,13 @@ static int dense_rows(spmf_ctx* c, const spmf_counts* ct, DenseForm form, RowArg
   const int KP = c->KP, lik = ra.logt, B = (int)ct->n_rows;
   double* dacc = ra.dacc;
   const bool fused = form == kDenseSig3Fused;
-  RowArgs r1 = ra;
-  if (fused) {
-    // both sweeps read the same counts: ONE row pass (mode 3 leaves xi_b (gz_b - [veta] - z_b) in gzs) and the
-    // (Z, W) launch subtracts the dense row term in its epilogue, gzs_b -= xi_b sum_d sigmoid(l_bd) V'_d, instead
-    // of encode-only sweep -> dense -> stored-cell sweep (two row launches re-stream the entries and pass z
-    // through HBM: DESIGN section 4)
-    r1.mode = 3;
-  } else {
-    // z from g(x) (exp decoders) or the counts (sweep 1); the stored-cell terms with the dense row term follow
-    // the dense launches (sweep 2)
-    r1.mode = 1;
-    r1.dyn_tail = 0;   // (the encode-only launch never touches the counters: sweep 2 has them alone)
-    if (lik_exp(lik)) {
-      r1.val = ct->gval;
-      r1.ent = nullptr;
-    }
-  }
+  // fused: both sweeps read the same counts: ONE row pass (mode 3 leaves xi_b (gz_b - [veta] - z_b) in gzs) and the
+  // (Z, W) launch subtracts the dense row term in its epilogue, gzs_b -= xi_b sum_d sigmoid(l_bd) V'_d, instead
+  // of encode-only sweep -> dense -> stored-cell sweep (two row launches re-stream the entries and pass z
+  // through HBM: DESIGN section 4).  Else z from g(x) (exp decoders) or the counts (sweep 1); the stored-cell
+  // terms with the dense row term follow the dense launches (sweep 2)
+  RowArgs r1 = fused ? ra : encode_sweep(ra, ct);
+  if (fused) r1.mode = 3;
   launch_row_pass(KP, r1, st);
   if (tm) HIPCHK(c, hipEventRecord(c->ev[6], st));
   const int act = lik == 4 ? 2 : (lik >= 2 ? 1 : 0);   // dense.hip / dense3.hip ACT
@@ -649,19 +711,29 @@ static int dense_rows(spmf_ctx* c, const spmf_counts* ct, DenseForm form, RowArg
     lbias = c->bb;
     orows = c->bcols;
   }
+  // The two products every form runs.  (Z, W): rows b against columns d, the bias on the Q rows:
+  // gzd_b = sum_d E_bd V'_d for sweep 2, dacc[3] = sum E (ACT 0) or sum softplus(l) (ACT 1, 2); E = exp, sigmoid,
+  // or sigmoid * exp.  (W, Z): the bias on the P rows: gV'_d -= sum_b E_bd z_b ; gphi_d -= sum_b sigmoid(l_bd)
+  // (ACT 1, 2), added with float atomics.
+  ExpdotArgs ez, ew;
+  ez.NP = B; ez.P = c->z; ez.NQ = Dd; ez.Q = Wd;
+  ez.out = c->gzd; ez.sign = 1.f; ez.esum = dacc + 3;
+  ez.act = act; ez.bias_q = act ? lbias : nullptr;
+  ew.NP = Dd; ew.P = Wd; ew.NQ = B; ew.Q = c->z;
+  ew.out = gVp; ew.sign = -1.f; ew.atomic_out = 1;
+  ew.act = act; ew.bias_p = act ? lbias : nullptr;
+  ew.out2 = act ? gphi_acc : nullptr; ew.out_rows = orows;
   switch (form) {
     case kDenseExp3: {
       // E is recomputed by the second launch (at this matrix rate a B*D*4-byte round trip through HBM would be
       // the bound)
-      ExpdotArgs ez{B, Dd, c->z, Wd, c->gzd, 1.f, dacc + 3, 1, 0, 0, nullptr, nullptr, nullptr, nullptr};
-      if (!launch_expdot3(KP, ez, st)) return dense3_uncovered(c);   // gzd_b = sum_d E_bd V'_d ; dacc[3] = sum E
+      if (!launch_expdot3(KP, ez, st)) return dense3_uncovered(c);
       // Q chunks of the W-stationary launch: whole rounds of the resident workgroups (one 110 KB
       // workgroup per CU: 118 column blocks x 13 chunks = 6 rounds of 256 on C4; 5 chunks = 590
       // workgroups ran 2.3 rounds, the last one a third full)
-      const int ch3 = pick_chunks((Dd + expdot3_rows_per_wg() - 1) / expdot3_rows_per_wg(), (B + 127) / 128,
-                                  256 * expdot3_wgs_per_cu(), 64);
-      ExpdotArgs ew{Dd, B, Wd, c->z, gVp, -1.f, nullptr, ch3, 1, 0, nullptr, nullptr, nullptr, nullptr};
-      if (!launch_expdot3(KP, ew, st)) return dense3_uncovered(c);   // gV'_d -= sum_b E_bd z_b
+      ew.q_chunks = pick_chunks((Dd + expdot3_rows_per_wg() - 1) / expdot3_rows_per_wg(), (B + 127) / 128,
+                                256 * expdot3_wgs_per_cu(), 64);
+      if (!launch_expdot3(KP, ew, st)) return dense3_uncovered(c);
       break;
     }
     case kDenseSig3Fused:
@@ -669,21 +741,18 @@ static int dense_rows(spmf_ctx* c, const spmf_counts* ct, DenseForm form, RowArg
       // Two waves per SIMD by registers: chunk counts that fill whole rounds of the resident workgroups.
       const int zt = (Dd + 127) / 128, wt = (B + 127) / 128;
       const int rpw = sigdot3_rows_per_wg(KP), slots = 256 * sigdot3_wgs_per_cu(KP);
-      const int zc = pick_chunks((B + rpw - 1) / rpw, zt, slots, 16), wc = pick_chunks((Dd + rpw - 1) / rpw, wt, slots, 256);
-      // (Z, W), the bias on the Q rows: fused, gzs_b -= xi_b sum_d E_bd V'_d; else gzd_b = sum_d E_bd V'_d for
-      // sweep 2.  dacc[3] = sum E (ACT 0) or sum softplus(l) (ACT 1, 2); E = exp, sigmoid, or sigmoid * exp
-      if (!fused && zc > 1) launch_zero(c->gzd, (size_t)B * KP * sizeof(float), st);
-      ExpdotArgs ez{B, Dd, c->z, Wd, fused ? c->gzs : c->gzd, fused ? -1.f : 1.f, dacc + 3, zc, zc > 1 ? 1 : 0, act,
-          nullptr, act ? lbias : nullptr, nullptr, nullptr};
+      ez.q_chunks = pick_chunks((B + rpw - 1) / rpw, zt, slots, 16);
+      ew.q_chunks = pick_chunks((Dd + rpw - 1) / rpw, wt, slots, 256);
+      ez.atomic_out = ez.q_chunks > 1 ? 1 : 0;
       if (act) ez.e_planes = 3;   // V' rows have mixed signs under the Normal priors: third plane of E
       if (fused) {
-        ez.accumulate = 1;
-        ez.p_scale = ra.row_scale;
+        // gzs_b -= xi_b sum_d E_bd V'_d in the launch's epilogue
+        ez.out = c->gzs; ez.sign = -1.f;
+        ez.accumulate = 1; ez.p_scale = ra.row_scale;
+      } else if (ez.q_chunks > 1) {
+        launch_zero(c->gzd, (size_t)B * KP * sizeof(float), st);
       }
       if (!launch_sigdot3(KP, ez, st)) return dense3_uncovered(c);
-      // (W, Z), the bias on the P rows: gV'_d -= sum_b E_bd z_b ; gphi_d -= sum_b sigmoid(l_bd) (ACT 1, 2)
-      ExpdotArgs ew{Dd, B, Wd, c->z, gVp, -1.f, nullptr, wc, 1, act, act ? lbias : nullptr, nullptr,
-          act ? gphi_acc : nullptr, orows};
       if (!launch_sigdot3(KP, ew, st)) return dense3_uncovered(c);
       break;
     }
@@ -696,21 +765,18 @@ static int dense_rows(spmf_ctx* c, const spmf_counts* ct, DenseForm form, RowArg
       const int64_t nch = (ct->n_rows + c->est_rows - 1) / c->est_rows;
       int64_t step = ((ct->n_rows + nch - 1) / nch + 127) / 128 * 128;
       if (step > c->est_rows) step = c->est_rows;
+      ez.est = c->est;
       for (int64_t r0 = 0; r0 < ct->n_rows; r0 += step) {
         const int nr = (int)((ct->n_rows - r0) < step ? (ct->n_rows - r0) : step);
-        ExpdotArgs ez{nr, Dd, c->z + (size_t)r0 * KP, Wd, c->gzd + (size_t)r0 * KP, 1.f, dacc + 3, 1, 0, act,
-            nullptr, act ? lbias : nullptr, nullptr, nullptr, c->est, (int64_t)nr};
+        ez.NP = nr; ez.ldE = nr;
+        ez.P = c->z + (size_t)r0 * KP; ez.out = c->gzd + (size_t)r0 * KP;
         launch_expdot(KP, ez, st);
-        launch_estdot(KP, Dd, nr, (int64_t)nr, c->est, c->z + (size_t)r0 * KP, gVp, -1.f,
-                      act ? gphi_acc : nullptr, orows, st);
+        launch_estdot(KP, Dd, nr, ez.ldE, c->est, ez.P, ew.out, ew.sign, ew.out2, ew.out_rows, st);
       }
       break;
     }
     case kDenseRecompute: {
-      // Z-stationary: Q rows are columns d -> bias_q = phi (Bernoulli logits)
-      ExpdotArgs ez{B, Dd, c->z, Wd, c->gzd, 1.f, dacc + 3, 1, 0, act, nullptr, act ? lbias : nullptr, nullptr,
-          nullptr};
-      launch_expdot(KP, ez, st);   // gzd_b = sum_d E_bd V'_d ; dacc[3] = sum E (or sum softplus)
+      launch_expdot(KP, ez, st);
       // W-stationary launch has only D/128 workgroups: split the row (Q) range
       // into chunks until ~4 workgroups per CU are in flight
       const int nbx = (Dd + 127) / 128;
@@ -718,11 +784,8 @@ static int dense_rows(spmf_ctx* c, const spmf_counts* ct, DenseForm form, RowArg
       int chunks = (1024 + nbx - 1) / nbx;
       if (chunks > qtiles) chunks = qtiles;
       if (chunks < 1) chunks = 1;
-      // W-stationary: P rows are columns d -> bias_p = phi; Bernoulli also needs the
-      // column sums of sigmoid for d/dphi (subtracted from the gphi accumulators)
-      ExpdotArgs ew{Dd, B, Wd, c->z, gVp, -1.f, nullptr, chunks, 1, act, act ? lbias : nullptr, nullptr,
-          act ? gphi_acc : nullptr, orows};
-      launch_expdot(KP, ew, st);   // gV'_d -= sum_b E_bd z_b
+      ew.q_chunks = chunks;
+      launch_expdot(KP, ew, st);
       break;
     }
     case kDenseNone:
@@ -790,14 +853,19 @@ static int data_pass_impl(spmf_ctx* c, const spmf_counts* ct, int S, const float
   for (int s = 0; s < S; s += nbat) {
     const bool tm = c->timing && s + nbat == S;
     float* acc = c->acc + (size_t)s * al_;
-    double* dacc = c->dacc + (size_t)s * dacc_stride;
-    double* dprep = c->dprep + (size_t)s * kPrepSeg * (KP + 1);
+    Tables T = ws_tables(c);   // (the scalar blocks are draw s's)
+    T.dacc += (size_t)s * dacc_stride;
+    T.dprep += (size_t)s * kPrepSeg * (KP + 1);
+    char* det_draw_buf = det ? c->det_buf + (size_t)s * det_draw : nullptr;
     bool packed = false;
     if (first) {
       if (tm) HIPCHK(c, hipEventRecord(c->ev[0], st));
-      PrepArgs pa{D, c->K, params[2] + s * var_size(c, 2), params[0] + s * var_size(c, 0), params[1] + s * var_size(c,
-          1), params[7] + s * var_size(c, 7), eta, c->Ap, c->Vp, c->phi, dprep, lik_exp(logt) ? 1 : 0,
-          logt == 3 ? c->ctype : nullptr, logt == 3 ? c->dbias : nullptr, nbat};
+      PrepArgs pa = prep_args(c, nbat, T, params[2] + s * var_size(c, 2), params[0] + s * var_size(c, 0),
+          params[1] + s * var_size(c, 1), params[7] + s * var_size(c, 7), eta);
+      if (logt == 3) {
+        pa.ctype = c->ctype;
+        pa.dbias = c->dbias;
+      }
       if (s == 0) {
         pa.zero_p = c->acc;
         pa.zero_bytes = (size_t)((char*)c->dprep - (char*)c->acc);
@@ -812,17 +880,14 @@ static int data_pass_impl(spmf_ctx* c, const spmf_counts* ct, int S, const float
       }
       if (tm) HIPCHK(c, hipEventRecord(c->ev[1], st));
       if (ct->n_rows > 0) {
-        RowArgs ra{ct->n_rows, ct->row_ptr, ct->col_idx, ct->val,
-            (c->flags & SPMF_FLAG_SCALE_ROWS) ? ct->row_scale : nullptr, c->Ap, c->Vp, c->phi, dprep, c->z, c->gzs,
-            dacc, 0, logt, nullptr, c->ctype, nbat, D, dacc_stride};
-        ra.ent = ct->ent;
-        ra.dyn_tail = c->dyn_rows;
+        RowArgs ra = row_args(c, ct, nbat, T, logt, dacc_stride);
+        ra.dyn_tail = 1;   // the step's ONE full row launch hands its last rows out dynamically (row_pass.hip)
         if (form != kDenseNone) {
           rc = dense_rows(c, ct, form, ra, acc, L, tm, st);
           if (rc) return rc;
         } else {
           if (det) {
-            ra.det_slots = (double*)(c->det_buf + (size_t)s * det_draw);
+            ra.det_slots = (double*)det_draw_buf;
             ra.det_stride = (int64_t)(det_draw / sizeof(double));
           }
           launch_row_pass(KP, ra, st);
@@ -837,22 +902,17 @@ static int data_pass_impl(spmf_ctx* c, const spmf_counts* ct, int S, const float
       for (int hf = 0; hf < 2; ++hf) {
         if (!(hf == 0 ? first : second)) continue;
         if (!split && hf == 1) continue;
-        ColArgs ca{D, ct->n_panels, ct->row_base, split ? ct->max_items_half[hf] : ct->max_items_per_panel,
-            ct->item_ptr, ct->items, ct->pc_row, ct->pc_val, c->Vp, c->phi, c->z, c->gzs, acc + L.gA_off(hf),
-            acc + L.gV_off(hf), acc + L.gphi_off(hf), logt, ct->pc_gval, c->ctype, split ? ct->item_mid : nullptr,
-            split ? hf + 1 : 0, nbat, ct->n_rows, (int64_t)al_, ct->pc_pad};
-        ca.pc_ent = ct->pc_ent;
-        ca.panel_rows = ct->panel_rows;
+        ColArgs ca = col_args(c, ct, nbat, T, acc, L, hf);
         if (det) {
-          ca.det_slots = (const double*)(c->det_buf + (size_t)s * det_draw);
+          ca.det_slots = (const double*)det_draw_buf;
           ca.det_stride = (int64_t)(det_draw / sizeof(double));
-          ca.det_part = (float*)(c->det_buf + (size_t)s * det_draw + det_slots_bytes(KP));
+          ca.det_part = (float*)(det_draw_buf + det_slots_bytes(KP));
           ca.det_part_stride = (int64_t)(det_draw / sizeof(float));
         }
         if (hf == (split ? 1 : 0)) {
           // the fp64 scalars of the row pass are complete before this launch starts: its
           // extra first block folds them into the accumulator tail (the former pack launch)
-          ca.pack_dacc = dacc;
+          ca.pack_dacc = T.dacc;
           ca.pack_tail = acc + L.tail_off();
           ca.dacc_stride = dacc_stride;
           packed = launch_col_pass(KP, ca, st);
@@ -864,13 +924,13 @@ static int data_pass_impl(spmf_ctx* c, const spmf_counts* ct, int S, const float
     if (det && ct->n_rows > 0 && ct->nnz > 0) {
       // the per-item partial sums, column by column in (panel, segment) order, into the zeroed accumulators
       DetReduceArgs dr{D, KP, ct->n_panels, nbat, ct->list_first, ct->item_pos, ct->item_ptr,
-          (const float*)(c->det_buf + (size_t)s * det_draw + det_slots_bytes(KP)), (int64_t)(det_draw / sizeof(float)),
+          (const float*)(det_draw_buf + det_slots_bytes(KP)), (int64_t)(det_draw / sizeof(float)),
           acc + L.gA_off(0), acc + L.gV_off(0), acc + L.gphi_off(0), (int64_t)al_};
       launch_det_reduce(dr, st);
     }
     if (second) {
       if (!packed) {
-        PackArgs pk{KP, dacc, acc + L.tail_off(), nbat, dacc_stride, (int64_t)al_};
+        PackArgs pk{KP, T.dacc, acc + L.tail_off(), nbat, dacc_stride, (int64_t)al_};
         launch_pack(pk, st);
       }
       if (tm) {
@@ -947,6 +1007,25 @@ static int timing_close(spmf_ctx* c, hipStream_t st) {
   return SPMF_OK;
 }
 
+// The data half of the finish over the bound accumulators: the step's last launch.  phase 0 / 2: launch_finish
+// (whole finish / data half behind a prior half that ran on the side stream); kStepEnd: launch_step_end (data half
+// + the fold of the per-block sums the prep launch's prior half left).
+// (no zero fill: the fold writes the twelve prior parts and the u_tau gradient whole, the data half stores
+//  parts 12 and 13 -- single writers)
+constexpr int kStepEnd = -1;
+static int finish_data_half(spmf_ctx* c, FinishArgs fa, int64_t n_rows_global, double lgamma_sum_global,
+    double* n_nonfinite, int phase, hipStream_t st) {
+  fa.B_global = n_rows_global; fa.lgamma_sum = lgamma_sum_global; fa.n_nonfinite = n_nonfinite;
+  fa.acc = c->acc; fa.acc_stride = (int64_t)acc_len(c->D, c->KP); fa.dprep = c->dprep;
+  if (c->timing) HIPCHK(c, hipEventRecord(c->ev[4], st));
+  if (phase == kStepEnd) launch_step_end(c->KP, fa, st);
+  else launch_finish(c->KP, fa, phase, st);
+  const int rc = timing_close(c, st);
+  if (rc) return rc;
+  HIPCHK(c, hipGetLastError());
+  return SPMF_OK;
+}
+
 int spmf_prior_async(spmf_ctx* c, int S, double prior_weight, const float* const params[SPMF_NVARS],
     const float* eta, double* parts, float* const grads[SPMF_NVARS], void* stream) {
   if (!c || !params || !grads || !eta || !parts || S < 1) return fail(c, SPMF_E_ARG, "prior_async: bad arguments");
@@ -987,22 +1066,9 @@ int spmf_finish(spmf_ctx* c, int S, int64_t n_rows_global, double lgamma_sum_glo
   if (joined) {
     HIPCHK(c, hipStreamWaitEvent(st, c->ev_join, 0));
   }
-  // (no zero fill: finish_reduce_kernel writes the twelve prior parts and the u_tau gradient
-  //  whole, the data half stores parts 12 and 13 -- single writers)
   // one launch for all S draws (gridDim.y)
-  FinishArgs fa = finish_args(c, S, prior_weight, params, eta, grads, parts);
-  fa.B_global = n_rows_global;
-  fa.lgamma_sum = lgamma_sum_global;
-  fa.acc = c->acc;
-  fa.dprep = c->dprep;
-  fa.n_nonfinite = n_nonfinite;
-  fa.acc_stride = (int64_t)acc_len(c->D, c->KP);
-  if (c->timing) HIPCHK(c, hipEventRecord(c->ev[4], st));
-  launch_finish(c->KP, fa, joined ? 2 : 0, st);
-  rc = timing_close(c, st);
-  if (rc) return rc;
-  HIPCHK(c, hipGetLastError());
-  return SPMF_OK;
+  return finish_data_half(c, finish_args(c, S, prior_weight, params, eta, grads, parts), n_rows_global,
+                          lgamma_sum_global, n_nonfinite, joined ? 2 : 0, st);
 }
 
 // ---- the step with its outputs known up front (ABI 6) -------------------------
@@ -1038,20 +1104,8 @@ int spmf_step_end(spmf_ctx* c, int64_t n_rows_global, double lgamma_sum_global, 
   if (!so.fused)   // the draws ran in turn (S > 1 on a large batch): the whole finish, as spmf_finish runs it
     return spmf_finish(c, so.S, n_rows_global, lgamma_sum_global, so.prior_weight, so.params, so.eta, so.parts,
                        so.grads, so.nnf, stream);
-  hipStream_t st = (hipStream_t)stream;
-  FinishArgs fa = finish_args(c, so.S, so.prior_weight, so.params, so.eta, so.grads, so.parts);
-  fa.B_global = n_rows_global;
-  fa.lgamma_sum = lgamma_sum_global;
-  fa.acc = c->acc;
-  fa.dprep = c->dprep;
-  fa.n_nonfinite = so.nnf;
-  fa.acc_stride = (int64_t)acc_len(c->D, c->KP);
-  if (c->timing) HIPCHK(c, hipEventRecord(c->ev[4], st));
-  launch_step_end(c->KP, fa, st);   // data half + the fold of the prior half's per-block sums
-  const int rc = timing_close(c, st);
-  if (rc) return rc;
-  HIPCHK(c, hipGetLastError());
-  return SPMF_OK;
+  return finish_data_half(c, finish_args(c, so.S, so.prior_weight, so.params, so.eta, so.grads, so.parts),
+                          n_rows_global, lgamma_sum_global, so.nnf, kStepEnd, (hipStream_t)stream);
 }
 
 int spmf_elbo_fwd_bwd(spmf_ctx* c, const spmf_counts* ct, int S, double prior_weight,
@@ -1062,24 +1116,27 @@ int spmf_elbo_fwd_bwd(spmf_ctx* c, const spmf_counts* ct, int S, double prior_we
   return spmf_step_end(c, ct->n_rows, ct->lgamma_sum, stream);
 }
 
-// spmf_encode / spmf_dense_ll: the checks, the prep launch and the encode sweep (z of every row into the
-// workspace).  Nothing is launched for an empty batch.
-static int encode_rows(spmf_ctx* c, const char* fn, const spmf_counts* ct, const float* u, const float* v,
-    const float* w, const float* s, const float* eta, hipStream_t st) {
+// spmf_encode / spmf_dense_ll / spmf_waic_accumulate: the checks, the prep launch and the encode sweep: z of every
+// row under each of S draws into T->z.  T == nullptr: the tables of the workspace, bound here (one draw).
+// Nothing is launched for an empty batch.
+static int encode_rows(spmf_ctx* c, const char* fn, const spmf_counts* ct, int S, const Tables* T, const float* u,
+    const float* v, const float* w, const float* s, const float* eta, hipStream_t st) {
   const int logt = lik_exp(likelihood_code(c)) ? 1 : 0;
   int rc = check_counts(c, ct);
   if (!rc && logt && ct->nnz > 0 && !ct->gval) rc = fail(c, SPMF_E_ARG,
       std::string(fn) + ": log_transform needs counts.gval");
   if (rc || ct->n_rows == 0) return rc;
-  rc = bind_ws(c, ct->n_rows, 1);
-  if (rc) return rc;
-  PrepArgs pa{c->D, c->K, u, v, w, s, eta, c->Ap, c->Vp, c->phi, c->dprep, logt, nullptr, nullptr};
-  launch_prep(c->KP, pa, st);
-  RowArgs ra{ct->n_rows, ct->row_ptr, ct->col_idx, logt ? ct->gval : ct->val,
-      (c->flags & SPMF_FLAG_SCALE_ROWS) ? ct->row_scale : nullptr, c->Ap, c->Vp, c->phi, c->dprep, c->z, c->gzs,
-      c->dacc, 1, logt, nullptr, nullptr, 1, c->D, 0};
-  if (!logt) ra.ent = ct->ent;
-  launch_row_pass(c->KP, ra, st);
+  Tables ws;
+  if (!T) {
+    rc = bind_ws(c, ct->n_rows, S);
+    if (rc) return rc;
+    ws = ws_tables(c);
+    T = &ws;
+  }
+  launch_prep(c->KP, prep_args(c, S, *T, u, v, w, s, eta), st);
+  // (sweep 1 does not depend on the likelihood; it writes z and nothing else: one scalar block for all draws)
+  if (!launch_row_pass(c->KP, encode_sweep(row_args(c, ct, S, *T, logt, 0), ct), st)) return fail(c,
+      SPMF_E_UNSUPPORTED, std::string(fn) + ": no encode kernel for this K");
   return SPMF_OK;
 }
 
@@ -1087,7 +1144,7 @@ int spmf_encode(spmf_ctx* c, const spmf_counts* ct, const float* u, const float*
     void* stream) {
   if (!c || !u || !s || !eta || !z_out) return fail(c, SPMF_E_ARG, "encode: bad arguments");
   hipStream_t st = (hipStream_t)stream;
-  const int rc = encode_rows(c, "encode", ct, u, nullptr, nullptr, s, eta, st);
+  const int rc = encode_rows(c, "encode", ct, 1, nullptr, u, nullptr, nullptr, s, eta, st);
   if (rc || ct->n_rows == 0) return rc;
   HIPCHK(c, hipMemcpy2DAsync(z_out, (size_t)c->K * sizeof(float), c->z, (size_t)c->KP * sizeof(float),
       (size_t)c->K * sizeof(float), (size_t)ct->n_rows, hipMemcpyDeviceToDevice, st));
@@ -1102,7 +1159,7 @@ int spmf_dense_ll(spmf_ctx* c, const spmf_counts* ct, const float* u, const floa
   const int lik = likelihood_code(c);
   if (lik == 3 && !c->ctype) return fail(c, SPMF_E_ARG, "dense_ll: spmf_ctx_set_column_types was not called");
   hipStream_t st = (hipStream_t)stream;
-  const int rc = encode_rows(c, "dense_ll", ct, u, v, w, s, eta, st);
+  const int rc = encode_rows(c, "dense_ll", ct, 1, nullptr, u, v, w, s, eta, st);
   if (rc || ct->n_rows == 0) return rc;
   DenseLLArgs da{ct->n_rows, c->D, lik, c->z, c->Vp, c->phi, c->ctype, ct->row_ptr, ct->col_idx, ct->val, rate_out,
       ll_out};
@@ -1148,9 +1205,7 @@ int spmf_waic_accumulate(spmf_ctx* c, const spmf_counts* ct, int S, const float*
   if ((uintptr_t)scratch & 255) return fail(c, SPMF_E_ARG, "waic_accumulate: scratch must be 256-byte aligned");
   const int lik = likelihood_code(c);
   if (lik == 3 && !c->ctype) return fail(c, SPMF_E_ARG, "waic_accumulate: spmf_ctx_set_column_types was not called");
-  const int logt = lik_exp(lik) ? 1 : 0;
-  int rc = check_counts(c, ct);
-  if (!rc && logt && ct->nnz > 0 && !ct->gval) rc = fail(c, SPMF_E_ARG, "waic_accumulate: log_transform needs counts.gval");
+  int rc = check_counts(c, ct);   // (the scratch is sized by the batch; encode_rows checks the rest)
   if (rc) return rc;
   if ((int64_t)(c->D + 63) / 64 > 65535) return fail(c, SPMF_E_UNSUPPORTED, "waic_accumulate: D above 65535 * 64");
   // the encode sweep of S draws gathers z with 32-bit byte offsets per draw; the dense kernel's row blocks
@@ -1163,23 +1218,16 @@ int spmf_waic_accumulate(spmf_ctx* c, const spmf_counts* ct, int S, const float*
         (long long)ct->n_rows, S, scratch_bytes);
     return fail(c, SPMF_E_WORKSPACE, b);
   }
-  if (ct->n_rows == 0) return SPMF_OK;
   hipStream_t st = (hipStream_t)stream;
   char* base = (char*)scratch;
-  float* Ap = (float*)(base + k.Ap);
-  float* Vp = (float*)(base + k.Vp);
-  float* phi = (float*)(base + k.phi);
-  float* z = (float*)(base + k.z);
-  PrepArgs pa{c->D, c->K, u, v, w, s, eta, Ap, Vp, phi, (double*)(base + k.dprep), logt, nullptr, nullptr};
-  pa.S = S;
-  launch_prep(c->KP, pa, st);
-  // the encode-only sweep (mode 1) writes z and nothing else: gzs and the scalar block are never touched
-  RowArgs ra{ct->n_rows, ct->row_ptr, ct->col_idx, logt ? ct->gval : ct->val,
-      (c->flags & SPMF_FLAG_SCALE_ROWS) ? ct->row_scale : nullptr, Ap, Vp, phi, (const double*)(base + k.dprep), z, z,
-      (double*)(base + k.dacc), 1, logt, nullptr, nullptr, S, c->D, 0};
-  if (!logt) ra.ent = ct->ent;
-  if (!launch_row_pass(c->KP, ra, st)) return fail(c, SPMF_E_UNSUPPORTED, "waic_accumulate: no encode kernel for this K");
-  WaicArgs wa{ct->n_rows, ct->nnz, c->D, c->KP, S, lik, z, Vp, phi, c->ctype, ct->row_ptr, ct->col_idx, ct->val,
+  // the encode-only sweep writes z and nothing else: gzs and the scalar block are never touched
+  Tables T{};
+  T.Ap = (float*)(base + k.Ap); T.Vp = (float*)(base + k.Vp); T.phi = (float*)(base + k.phi);
+  T.dprep = (double*)(base + k.dprep); T.dacc = (double*)(base + k.dacc);
+  T.z = T.gzs = (float*)(base + k.z);
+  rc = encode_rows(c, "waic_accumulate", ct, S, &T, u, v, w, s, eta, st);
+  if (rc || ct->n_rows == 0) return rc;
+  WaicArgs wa{ct->n_rows, ct->nnz, c->D, c->KP, S, lik, T.z, T.Vp, T.phi, c->ctype, ct->row_ptr, ct->col_idx, ct->val,
       sums6, row_out};
   if (!launch_waic(wa, st)) return fail(c, SPMF_E_UNSUPPORTED, "waic_accumulate: no kernel for this K / likelihood");
   HIPCHK(c, hipGetLastError());
@@ -1479,8 +1527,7 @@ int spmf_nonfinite_patch(spmf_ctx* c, const spmf_counts* ct, int S, const float*
     if (!params[i]) return fail(c, SPMF_E_ARG, "nonfinite_patch: params v,w,u,s must be non-null");
   const int logt = likelihood_code(c);
   if (lik_exp(logt) && ct->nnz > 0 && !ct->gval) return fail(c, SPMF_E_ARG, "nonfinite_patch: log_transform needs counts.gval");
-  NfPatchArgs a{c->D, c->K, logt, ct->row_ptr, ct->col_idx, ct->val,
-      (c->flags & SPMF_FLAG_SCALE_ROWS) ? ct->row_scale : nullptr, params[2], params[0], params[1], params[7], eta,
+  NfPatchArgs a{c->D, c->K, logt, ct->row_ptr, ct->col_idx, ct->val, row_scale_of(c, ct), params[2], params[0], params[1], params[7], eta,
       c->ctype, c->acc, (int64_t)acc_len(c->D, c->KP), c->Dh > 0 ? c->Dh : c->D, io, nlg, ct->n_rows, S};
   launch_nonfinite_patch(c->KP, a, (hipStream_t)stream);
   HIPCHK(c, hipGetLastError());

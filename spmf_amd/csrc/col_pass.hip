@@ -454,32 +454,19 @@ __global__ __launch_bounds__(256) void det_reduce_kernel(int D, int n_panels, co
 
 void launch_det_reduce(const DetReduceArgs& a, hipStream_t st) {
   if (a.D <= 0 || a.n_panels <= 0) return;
-#define SPMF_DET(KP_)                                                                                        \
-  hipLaunchKernelGGL((det_reduce_kernel<KP_>), dim3((a.D + 256 / (KP_ / 4) - 1) / (256 / (KP_ / 4)),          \
-                                                    a.S > 1 ? a.S : 1),                                       \
-                     dim3(256), 0, st, a.D, a.n_panels, a.list_first, a.item_pos, a.item_ptr, a.part,        \
-                     a.part_stride, a.gAp, a.gVp, a.gphi, a.acc_stride)
-  switch (a.KP) {
-    case 4: SPMF_DET(4); break;
-    case 8: SPMF_DET(8); break;
-    case 16: SPMF_DET(16); break;
-    case 32: SPMF_DET(32); break;
-    case 64: SPMF_DET(64); break;
-    default: break;
-  }
-#undef SPMF_DET
+  // (the deterministic mode stops at 64 latent dimensions: spmf_ctx_set_deterministic)
+  with_kp<64>(a.KP, [&](auto kp) {
+    constexpr int KP = decltype(kp)::value, cols = 256 / (KP / 4);   // columns per workgroup
+    hipLaunchKernelGGL((det_reduce_kernel<KP>), dim3((a.D + cols - 1) / cols, a.S > 1 ? a.S : 1), dim3(256), 0, st,
+                       a.D, a.n_panels, a.list_first, a.item_pos, a.item_ptr, a.part, a.part_stride, a.gAp, a.gVp,
+                       a.gphi, a.acc_stride);
+  });
 }
 
 bool launch_col_pass(int KP, const ColArgs& a, hipStream_t st) {
-  switch (KP) {
-    case 4: return launch_col_t<4>(a, st);
-    case 8: return launch_col_t<8>(a, st);
-    case 16: return launch_col_t<16>(a, st);
-    case 32: return launch_col_t<32>(a, st);
-    case 64: return launch_col_t<64>(a, st);
-    case 128: case 256: return launch_col_widek(KP, a, st);   // widek.hip
-    default: return false;
-  }
+  if (KP > 64) return launch_col_widek(KP, a, st);   // widek.hip
+  bool ok = false;
+  return with_kp<64>(KP, [&](auto kp) { ok = launch_col_t<decltype(kp)::value>(a, st); }) && ok;
 }
 
 }  // namespace spmf

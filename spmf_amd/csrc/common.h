@@ -55,6 +55,30 @@ __device__ __forceinline__ float expm1_dec(float y, float& ey) {
   return em1;
 }
 
+// ---- the likelihood of one cell, as every per-cell kernel evaluates it (dense_ll.hip, waic.hip) ----
+// (the sparse passes have their own fused forms: row_pass.hip, col_pass.hip)
+__device__ __forceinline__ float cell_softplus(float r) { return fmaxf(r, 0.f) + log1pf(expf(-fabsf(r))); }
+// Bernoulli cell (its "rate" is the logit)?  Likelihood code 3 asks the column's type.
+__device__ __forceinline__ bool cell_is_bern(int lik, const uint8_t* __restrict__ ctype, int d) {
+  return lik_bern(lik) || (lik == 3 && ctype[d]);
+}
+// rate (Bernoulli: logit) f(y) + phi of a cell with y = <z_b, V'_d>; ey = f'(y).  (phi by reference: a caller's
+// phi[d] is read where it is added, behind the exponential)
+__device__ __forceinline__ float cell_rate(int lik, float y, const float& phi, float& ey) {
+  ey = 1.f;
+  return (lik_exp(lik) ? expm1_dec(fminf(y, kYSat), ey) : y) + phi;
+}
+// log-pmf of an x = 0 cell.  Poisson: 0 * log r := 0 (multiply_no_nan) -> -r.  Bernoulli: -softplus(logit)
+__device__ __forceinline__ float cell_ll0(bool bern, float r) { return bern ? -cell_softplus(r) : -r; }
+// log-pmf of a stored cell.  tfd.Bernoulli(logits).log_prob(x) = x*l - softplus(l) (bernoulli.py:147-155);
+// tfd.Poisson.log_prob: multiply_no_nan(log r, x) - lgamma(x+1) - r, LGAMMA = false without the lgamma term
+template <bool LGAMMA>
+__device__ __forceinline__ float cell_ll(bool bern, float x, float r) {
+  if (bern) return x * r - cell_softplus(r);
+  const float xl = x == 0.f ? 0.f : x * logf(r);
+  return LGAMMA ? xl - lgammaf(x + 1.f) - r : xl - r;
+}
+
 // The prep kernel's closed-form column sums (veta[KP], phisum) are written as kPrepSeg
 // partial sums over column segments, dprep[seg][KP+1]: one writer per slot (no atomics,
 // no zero fill), and every reader folds the segments in index order (prep_sum).

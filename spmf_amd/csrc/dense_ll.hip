@@ -47,11 +47,9 @@ __global__ __launch_bounds__(256) void dense_rate_kernel(int64_t B, int D, int l
 #pragma unroll 8
     for (int k = 0; k < KP; ++k) y = fmaf(zs[r][k], vs[dl][k], y);
     float ey_;
-    const float rt = (lik_exp(logt) ? expm1_dec(fminf(y, kYSat), ey_) : y) + phi[d];
+    const float rt = cell_rate(logt, y, phi[d], ey_);
     rate[(size_t)b * D + d] = rt;
-    const bool bern = lik_bern(logt) || (logt == 3 && ctype[d]);
-    // x = 0 cell.  Poisson: 0*log r := 0 (multiply_no_nan) -> -r.  Bernoulli: -softplus(logit)
-    ll[(size_t)b * D + d] = bern ? -(fmaxf(rt, 0.f) + log1pf(expf(-fabsf(rt)))) : -rt;
+    ll[(size_t)b * D + d] = cell_ll0(cell_is_bern(logt, ctype, d), rt);
   }
 }
 
@@ -71,15 +69,7 @@ __global__ __launch_bounds__(256) void dense_fix_kernel(int64_t B, int D, int lo
       const float x = val[i];
       const int d = col[i];
       const size_t o = (size_t)b * D + d;
-      const float r = rate[o];
-      if (lik_bern(logt) || (logt == 3 && ctype[d])) {
-        // tfd.Bernoulli(logits).log_prob(x) = x*l - softplus(l)  (bernoulli.py:147-155)
-        ll[o] = x * r - (fmaxf(r, 0.f) + log1pf(expf(-fabsf(r))));
-      } else {
-        // tfd.Poisson.log_prob: multiply_no_nan(log r, x) - lgamma(x+1) - r
-        const float xl = x == 0.f ? 0.f : x * logf(r);
-        ll[o] = xl - lgammaf(x + 1.f) - r;
-      }
+      ll[o] = cell_ll<true>(cell_is_bern(logt, ctype, d), x, rate[o]);
     }
   }
 }
@@ -185,7 +175,7 @@ __global__ __launch_bounds__(256) void nonfinite_lgamma_kernel(int64_t B, int D,
     const int start = row_ptr[b], end = row_ptr[b + 1];
     for (int i = start + lane; i < end; i += 64) {
       const int d = col[i];
-      if (lik_bern(logt) || (logt == 3 && ctype[d])) continue;      // Bernoulli cell: no lgamma term
+      if (cell_is_bern(logt, ctype, d)) continue;                   // Bernoulli cell: no lgamma term
       const float r = rate[(size_t)b * D + d];
       const float x = val[i];
       if (x > 0.f && !(r > 0.f && r < INFINITY)) acc += (double)lgammaf(x + 1.f);
@@ -280,14 +270,14 @@ __global__ __launch_bounds__(256) void nonfinite_patch_kernel(
   const float phi = eta[dstar] * (s1 / (s0 + s1)) * w[dstar];
   const float x = xstar_s;
   float cy, cphi;
-  if (lik_bern(logt) || (logt == 3 && ctype[dstar])) {
+  if (cell_is_bern(logt, ctype, dstar)) {
     const float ey = logt == 4 ? expf(fminf(y, kYSat)) : 1.f;
     const float sg = 1.f / (1.f + expf(-((logt == 4 ? ey - 1.f : y) + phi)));
     cphi = x - sg;
     cy = cphi * ey;
   } else {
-    float ey = 1.f;
-    const float r = (logt == 1 ? expm1_dec(fminf(y, kYSat), ey) : y) + phi;
+    float ey;
+    const float r = cell_rate(logt, y, phi, ey);
     cphi = x / r - 1.f;
     cy = cphi * ey;
   }
@@ -322,41 +312,20 @@ void launch_nonfinite_lgamma(const DenseLLArgs& a, double* out, hipStream_t st) 
 }
 
 void launch_nonfinite_patch(int KP, const NfPatchArgs& a, hipStream_t st) {
-#define SPMF_NFP(KP_)                                                                            \
-  hipLaunchKernelGGL(nonfinite_patch_kernel<KP_>, dim3(a.S), dim3(256), 0, st, a.D, a.K, a.logt,  \
-                     a.row_ptr, a.col, a.val, a.row_scale, a.u, a.v, a.w, a.s, a.eta, a.ctype,     \
-                     a.acc, a.acc_stride, a.Dh, a.io, a.nlg, a.rows_batch, a.S)
-  switch (KP) {
-    case 4: SPMF_NFP(4); break;
-    case 8: SPMF_NFP(8); break;
-    case 16: SPMF_NFP(16); break;
-    case 32: SPMF_NFP(32); break;
-    case 64: SPMF_NFP(64); break;
-    case 128: SPMF_NFP(128); break;
-    case 256: SPMF_NFP(256); break;
-    default: break;
-  }
-#undef SPMF_NFP
-}
-
-template <int KP>
-static void launch_dense_t(const DenseLLArgs& a, hipStream_t st) {
-  dim3 grid((a.D + 63) / 64, (unsigned)((a.B + 3) / 4));
-  hipLaunchKernelGGL(dense_rate_kernel<KP>, grid, dim3(256), 0, st, a.B, a.D, a.logt, a.z, a.Vp,
-                     a.phi, a.ctype, a.rate, a.ll);
+  with_kp<256>(KP, [&](auto kp) {
+    hipLaunchKernelGGL(nonfinite_patch_kernel<decltype(kp)::value>, dim3(a.S), dim3(256), 0, st, a.D, a.K, a.logt,
+                       a.row_ptr, a.col, a.val, a.row_scale, a.u, a.v, a.w, a.s, a.eta, a.ctype, a.acc, a.acc_stride,
+                       a.Dh, a.io, a.nlg, a.rows_batch, a.S);
+  });
 }
 
 void launch_dense_ll(int KP, const DenseLLArgs& a, hipStream_t st) {
-  switch (KP) {
-    case 4: launch_dense_t<4>(a, st); break;
-    case 8: launch_dense_t<8>(a, st); break;
-    case 16: launch_dense_t<16>(a, st); break;
-    case 32: launch_dense_t<32>(a, st); break;
-    case 64: launch_dense_t<64>(a, st); break;
-    case 128: launch_dense_t<128>(a, st); break;
-    case 256: launch_dense_t<256>(a, st); break;
-    default: return;
-  }
+  const dim3 grid((a.D + 63) / 64, (unsigned)((a.B + 3) / 4));
+  const bool built = with_kp<256>(KP, [&](auto kp) {
+    hipLaunchKernelGGL(dense_rate_kernel<decltype(kp)::value>, grid, dim3(256), 0, st, a.B, a.D, a.logt, a.z, a.Vp,
+                       a.phi, a.ctype, a.rate, a.ll);
+  });
+  if (!built) return;
   int64_t want = (a.B + 3) / 4;
   int nb = (int)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
   hipLaunchKernelGGL(dense_fix_kernel, dim3(nb), dim3(256), 0, st, a.B, a.D, a.logt, a.ctype,

@@ -106,16 +106,7 @@ static void launch_finish_t(const FinishArgs& a, int phase, hipStream_t st) {
 
 // phase 0: whole finish; 1: prior half (no accumulators read); 2: data half (adds to G)
 void launch_finish(int KP, const FinishArgs& a, int phase, hipStream_t st) {
-  switch (KP) {
-    case 4: launch_finish_t<4>(a, phase, st); break;
-    case 8: launch_finish_t<8>(a, phase, st); break;
-    case 16: launch_finish_t<16>(a, phase, st); break;
-    case 32: launch_finish_t<32>(a, phase, st); break;
-    case 64: launch_finish_t<64>(a, phase, st); break;
-    case 128: launch_finish_t<128>(a, phase, st); break;
-    case 256: launch_finish_t<256>(a, phase, st); break;
-    default: break;
-  }
+  with_kp<256>(KP, [&](auto kp) { launch_finish_t<decltype(kp)::value>(a, phase, st); });
 }
 
 // the step's last launch: data half + the fold of the prior half's per-block sums (end_kernel)
@@ -127,16 +118,7 @@ static void launch_step_end_t(const FinishArgs& a, hipStream_t st) {
   hipLaunchKernelGGL((end_kernel<KP>), dim3(nb + nred, a.S > 1 ? a.S : 1), dim3(256), 0, st, k, nb, a.vstride[4]);
 }
 void launch_step_end(int KP, const FinishArgs& a, hipStream_t st) {
-  switch (KP) {
-    case 4: launch_step_end_t<4>(a, st); break;
-    case 8: launch_step_end_t<8>(a, st); break;
-    case 16: launch_step_end_t<16>(a, st); break;
-    case 32: launch_step_end_t<32>(a, st); break;
-    case 64: launch_step_end_t<64>(a, st); break;
-    case 128: launch_step_end_t<128>(a, st); break;
-    case 256: launch_step_end_t<256>(a, st); break;
-    default: break;
-  }
+  with_kp<256>(KP, [&](auto kp) { launch_step_end_t<decltype(kp)::value>(a, st); });
 }
 
 }  // namespace spmf

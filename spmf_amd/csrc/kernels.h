@@ -3,7 +3,21 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace spmf {
+
+// The latent widths the kernels are built for, MINKP, 2 MINKP, .., MAXKP: calls f with KP as a
+// std::integral_constant.  false: KP is not one of them (f is not called, nothing is launched).
+template <int MAXKP, int MINKP = 4, class F>
+inline bool with_kp(int KP, F&& f) {
+  if (KP == MINKP) {
+    f(std::integral_constant<int, MINKP>{});
+    return true;
+  }
+  if constexpr (MINKP < MAXKP) return with_kp<MAXKP, 2 * MINKP>(KP, f);
+  return false;
+}
 
 struct PrepArgs {
   int D, K;
@@ -104,17 +118,17 @@ struct DetReduceArgs {
 void launch_det_reduce(const DetReduceArgs& a, hipStream_t st);
 
 struct ExpdotArgs {
-  int NP, NQ;
-  const float *P, *Q;  // [NP,KD], [NQ,KD]
-  float* out;          // [NP,KD]
-  float sign;
-  double* esum;        // may be null
-  int q_chunks;        // gridDim.y; >1 needs atomic_out
-  int atomic_out;
-  int act;             // 0 exp (Poisson log_transform), 1 sigmoid/softplus (Bernoulli)
-  const float *bias_p, *bias_q;  // act 1: logit bias per P row / per Q row (one of them)
-  float* out2;         // act 1: out2[p] += sign * sum_q sigmoid (may be null)
-  const int32_t* out_rows;   // P is a compacted row subset: out / out2 rows to write (may be null)
+  int NP = 0, NQ = 0;
+  const float *P = nullptr, *Q = nullptr;  // [NP,KD], [NQ,KD]
+  float* out = nullptr;      // [NP,KD]
+  float sign = 1.f;
+  double* esum = nullptr;    // may be null
+  int q_chunks = 1;          // gridDim.y; >1 needs atomic_out
+  int atomic_out = 0;
+  int act = 0;               // 0 exp (Poisson log_transform), 1 sigmoid/softplus (Bernoulli)
+  const float *bias_p = nullptr, *bias_q = nullptr;  // act 1: logit bias per P row / per Q row (one of them)
+  float* out2 = nullptr;     // act 1: out2[p] += sign * sum_q sigmoid (may be null)
+  const int32_t* out_rows = nullptr;   // P is a compacted row subset: out / out2 rows to write (may be null)
   float* est = nullptr;      // keep E (exp or sigmoid) for launch_estdot (layout: dense.hip), ldE = its P extent
   int64_t ldE = 0;
   int e_planes = 2;          // launch_sigdot3: bf16 planes of E in the second product (3 where the Q rows have mixed signs)

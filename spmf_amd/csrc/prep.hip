@@ -195,30 +195,12 @@ static void launch_begin_t(const PrepArgs& a, const FinishArgs& f, hipStream_t s
 }
 
 void launch_prep(int KP, const PrepArgs& a, hipStream_t st) {
-  switch (KP) {
-    case 4: launch_prep_t<4>(a, st); break;
-    case 8: launch_prep_t<8>(a, st); break;
-    case 16: launch_prep_t<16>(a, st); break;
-    case 32: launch_prep_t<32>(a, st); break;
-    case 64: launch_prep_t<64>(a, st); break;
-    case 128: launch_prep_t<128>(a, st); break;
-    case 256: launch_prep_t<256>(a, st); break;
-    default: break;
-  }
+  with_kp<256>(KP, [&](auto kp) { launch_prep_t<decltype(kp)::value>(a, st); });
 }
 
 // prep + the prior half of the finish in one launch (begin_kernel); f.S must equal a.S (or both 1)
 void launch_step_begin(int KP, const PrepArgs& a, const FinishArgs& f, hipStream_t st) {
-  switch (KP) {
-    case 4: launch_begin_t<4>(a, f, st); break;
-    case 8: launch_begin_t<8>(a, f, st); break;
-    case 16: launch_begin_t<16>(a, f, st); break;
-    case 32: launch_begin_t<32>(a, f, st); break;
-    case 64: launch_begin_t<64>(a, f, st); break;
-    case 128: launch_begin_t<128>(a, f, st); break;
-    case 256: launch_begin_t<256>(a, f, st); break;
-    default: break;
-  }
+  with_kp<256>(KP, [&](auto kp) { launch_begin_t<decltype(kp)::value>(a, f, st); });
 }
 
 }  // namespace spmf

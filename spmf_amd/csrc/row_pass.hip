@@ -681,15 +681,9 @@ static bool launch_row_t(const RowArgs& a, hipStream_t st) {
 }
 
 bool launch_row_pass(int KP, const RowArgs& a, hipStream_t st) {
-  switch (KP) {
-    case 4: return launch_row_t<4>(a, st);
-    case 8: return launch_row_t<8>(a, st);
-    case 16: return launch_row_t<16>(a, st);
-    case 32: return launch_row_t<32>(a, st);
-    case 64: return launch_row_t<64>(a, st);
-    case 128: case 256: return launch_row_widek(KP, a, st);   // widek.hip: a factor row is the whole wave
-    default: return false;
-  }
+  if (KP > 64) return launch_row_widek(KP, a, st);   // widek.hip: a factor row is the whole wave
+  bool ok = false;
+  return with_kp<64>(KP, [&](auto kp) { ok = launch_row_t<decltype(kp)::value>(a, st); }) && ok;
 }
 
 }  // namespace spmf

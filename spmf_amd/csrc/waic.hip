@@ -42,14 +42,6 @@ __device__ __forceinline__ void stat_update(float ll, float inv_n, float& m, flo
   q = fmaf(dl, ll - mu, q);
 }
 
-__device__ __forceinline__ float softplusf(float r) { return fmaxf(r, 0.f) + log1pf(expf(-fabsf(r))); }
-
-template <int LIK>
-__device__ __forceinline__ float rate_of(float y, float ph) {
-  float ey;
-  return (lik_exp(LIK) ? expm1_dec(fminf(y, kYSat), ey) : y) + ph;
-}
-
 __device__ __forceinline__ double half_sum(double v) {   // over the 32 lanes of a wave half
 #pragma unroll
   for (int m = 16; m >= 1; m >>= 1) v += __shfl_xor(v, m);
@@ -81,7 +73,7 @@ __global__ __launch_bounds__(256) void waic_dense_kernel(int64_t B, int D, int K
   const int NCH = KP > KC ? KP / KC : 1;
   const int NIT = S * NCH;
   const int d = d0 + wc * 32 + i32;
-  const bool bern = lik_bern(LIK) || (LIK == 3 && d < D && ctype[d]);
+  const bool bern = lik_bern(LIK) || (LIK == 3 && d < D && cell_is_bern(LIK, ctype, d));   // (no type behind D)
 
   auto fetch = [&](int it, float4* pre) {
     const int s = it / NCH, kc0 = (it % NCH) * KC;
@@ -149,9 +141,9 @@ __global__ __launch_bounds__(256) void waic_dense_kernel(int64_t B, int D, int K
       const float inv_n = 1.f / (float)(s + 1);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float rt = rate_of<LIK>(acc[r], ph);
-        const float ll = bern ? -softplusf(rt) : -rt;     // x = 0: 0 * log r := 0
-        stat_update(ll, inv_n, m[r], se[r], mu[r], q[r]);
+        float ey;
+        const float rt = cell_rate(LIK, acc[r], ph, ey);
+        stat_update(cell_ll0(bern, rt), inv_n, m[r], se[r], mu[r], q[r]);
         acc[r] = 0.f;
       }
     }
@@ -224,7 +216,7 @@ __global__ __launch_bounds__(256) void waic_fix_kernel(int64_t B, int D, int KP,
     for (int i = start + lane; i < end; i += 64) {
       const float x = val[i];
       const int d = col[i];
-      const bool bern = lik_bern(lik) || (lik == 3 && ctype[d]);
+      const bool bern = cell_is_bern(lik, ctype, d);
       float m0 = -INFINITY, e0 = 0.f, u0 = 0.f, q0 = 0.f;
       float m1 = -INFINITY, e1 = 0.f, u1 = 0.f, q1 = 0.f;
       for (int s = 0; s < S; ++s) {
@@ -239,19 +231,18 @@ __global__ __launch_bounds__(256) void waic_fix_kernel(int64_t B, int D, int KP,
           y = fmaf(a.w, v.w, y);
         }
         float ey;
-        const float rt = (lik_exp(lik) ? expm1_dec(fminf(y, kYSat), ey) : y) + phi[(size_t)s * D + d];
+        const float rt = cell_rate(lik, y, phi[(size_t)s * D + d], ey);
+        const float inv_n = 1.f / (float)(s + 1);
+        // the cell as the dense kernel counted it (x = 0) and as it is, without lgamma(x+1) (once, behind the
+        // loop); one branch on the cell's type for both
         float l0, l1;
         if (bern) {
-          // tfd.Bernoulli(logits).log_prob(x) = x*l - softplus(l)
-          const float sp = softplusf(rt);
-          l0 = -sp;
-          l1 = x * rt - sp;
+          l0 = cell_ll0(true, rt);
+          l1 = cell_ll<false>(true, x, rt);
         } else {
-          // tfd.Poisson.log_prob without lgamma(x+1): multiply_no_nan(log r, x) - r
-          l0 = -rt;
-          l1 = (x == 0.f ? 0.f : x * logf(rt)) - rt;
+          l0 = cell_ll0(false, rt);
+          l1 = cell_ll<false>(false, x, rt);
         }
-        const float inv_n = 1.f / (float)(s + 1);
         stat_update(l0, inv_n, m0, e0, u0, q0);
         stat_update(l1, inv_n, m1, e1, u1, q1);
       }

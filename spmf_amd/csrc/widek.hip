@@ -300,11 +300,7 @@ bool launch_row_widek(int KP, const RowArgs& a, hipStream_t st) {
   if (a.logt != 0 || (a.mode != 0 && a.mode != 1) || a.det_slots) return false;
   const int64_t want = (a.B + 3) / 4;
   const int nb = (int)(want < 1 ? 1 : (want > 2048 ? 2048 : want));
-  switch (KP) {
-    case 128: row_widek<128>(nb, a, st); return true;
-    case 256: row_widek<256>(nb, a, st); return true;
-    default: return false;
-  }
+  return with_kp<256, 128>(KP, [&](auto kp) { row_widek<decltype(kp)::value>(nb, a, st); });
 }
 
 bool launch_col_widek(int KP, const ColArgs& a, hipStream_t st) {
@@ -312,11 +308,7 @@ bool launch_col_widek(int KP, const ColArgs& a, hipStream_t st) {
   const int bpp = (a.max_items_per_panel + 3) / 4;
   if (bpp < 1) return false;
   const int64_t nb = (int64_t)a.n_panels * bpp + (a.pack_dacc ? 1 : 0);
-  switch (KP) {
-    case 128: col_widek<128>(nb, bpp, a, st); return true;
-    case 256: col_widek<256>(nb, bpp, a, st); return true;
-    default: return false;
-  }
+  return with_kp<256, 128>(KP, [&](auto kp) { col_widek<decltype(kp)::value>(nb, bpp, a, st); });
 }
 
 }  // namespace spmf

@@ -210,10 +210,10 @@ class ShardReducer:
         self.lgamma_global = None
         self.dataset_rows = None       # set by reduce_stats
         self.dataset_lgamma = None
-        # the prior half of the finish on the library's side stream, under the collective
-        # (spmf_prior_async): worth its fork/join only when the collective takes time, i.e.
-        # with more than one rank (one rank, measured: the fork/join costs what the 22 us
-        # prior half saves)
+        # kept for its callers: it asked for the prior half of the finish on the library's side
+        # stream under a one-piece collective (spmf_prior_async).  The ABI-6 step runs the prior
+        # half inside its first launch, so nothing is left to fork and the step reads this no more
+        # 
         self.overlap_prior = (self.world > 1) if overlap_prior is None else bool(overlap_prior)
         self._totals_cache = {}        # id(batch struct) -> (struct, (rows, lgamma)) for batch_totals
 

@@ -12,7 +12,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 from typing import Dict
 
 import numpy as np
@@ -422,9 +421,6 @@ class PoissonFactorization:
         nnf2 = torch.empty(2 * S, dtype=torch.float64, device=self.device)
         nnf = nnf2[:S]
         rows_g, lg_g = cs.n_rows, cs.lgamma_sum
-        # SPMF_LEGACY_STEP=1: the version-5 call sequence (spmf_data_pass [+ spmf_prior_async] + spmf_finish),
-        # kept for A/B timing and for callers built against it; the results are the same
-        legacy = os.environ.get("SPMF_LEGACY_STEP", "0") == "1"
         split = (all_reduce is not None and S == 1 and getattr(self, "column_split", 0) > 0
                  and sc.col_split == self.column_split and hasattr(all_reduce, "start"))
         if split:
@@ -448,8 +444,8 @@ class PoissonFactorization:
             if r is not None:
                 rows_g, lg_g = r
         elif beside_columns is not None:
+            # version-5 calls: data pass, prior half on the side stream, finish joins it
             (side, ev_rows), fill = beside_columns
-            legacy = True                    # data pass, prior half on the side stream, finish joins it
             _lib.check(h, lib.spmf_ctx_set_rows_event(h, ev_rows.cuda_event), "spmf_ctx_set_rows_event")
             try:
                 _lib.check(h, lib.spmf_data_pass(h, C.byref(cs), S, pin, eta.data_ptr(), stream),
@@ -462,9 +458,6 @@ class PoissonFactorization:
                 _lib.check(h, lib.spmf_prior_async(h, S, float(prior_weight), pin, eta.data_ptr(),
                                                    parts.data_ptr(), gout, side.cuda_stream),
                            "spmf_prior_async")
-        elif legacy:
-            _lib.check(h, lib.spmf_data_pass(h, C.byref(cs), S, pin, eta.data_ptr(), stream),
-                       "spmf_data_pass")
         else:
             # ABI 6: the outputs go in with the step's first call, so the prior half of the finish
             # (parameters only) runs inside the data pass's first launch
@@ -472,17 +465,12 @@ class PoissonFactorization:
                                               parts.data_ptr(), gout, nnf.data_ptr(), stream),
                        "spmf_step_begin")
         if all_reduce is not None and not split:
-            # (version-5 flow only: the prior half of the finish on the library's side stream
-            # while the collective has the GPU mostly idle; ShardReducer.overlap_prior)
-            if legacy and beside_columns is None and getattr(all_reduce, "overlap_prior", True):
-                _lib.check(h, lib.spmf_prior_async(h, S, float(prior_weight), pin, eta.data_ptr(),
-                                                   parts.data_ptr(), gout, stream), "spmf_prior_async")
             n = lib.spmf_acc_len(h, S)
             acc = _wrap_f32(lib.spmf_acc_ptr(h), n, self.device, self._ws)
             r = all_reduce(acc, cs.n_rows, cs.lgamma_sum)
             if r is not None:
                 rows_g, lg_g = r
-        if split or legacy:
+        if split or beside_columns is not None:
             _lib.check(h, lib.spmf_finish(h, S, int(rows_g), float(lg_g), float(prior_weight), pin,
                                           eta.data_ptr(), parts.data_ptr(), gout, nnf.data_ptr(), stream),
                        "spmf_finish")

@@ -3,13 +3,12 @@
 Three shapes: the 122 880-row shard of C3's 8-GPU run (D = 20 000, K = 32), a 22 784-row minibatch of
 it (two 11 392-row panels), and C2 as bench.py's c2_extra runs it (100k x 5k, 1 %, K = 16, one batch).  Per shape:
 ms per step without the hipEvent taps, then with them (prep / row / col / finish) and
-fixed_us = step - row - col.  SPMF_LEGACY_STEP=1 runs the version-5 call sequence for comparison.
+fixed_us = step - row - col.
 usage: fixed_cost_probe.py [reps]      (under rocprofv3 --kernel-trace --stats for per-kernel times)
 """
 import contextlib
 import ctypes as C
 import json
-import os
 import sys
 import time
 
@@ -40,7 +39,7 @@ def run(name, m, batch, n=100):
     torch.manual_seed(7)
     params = m.surrogate_distribution.sample(1)
     h = m._handle()
-    out = {"shape": name, "legacy": os.environ.get("SPMF_LEGACY_STEP", "0") == "1", "runs": []}
+    out = {"shape": name, "runs": []}
     for _ in range(reps):
         for _ in range(10):
             m.energy_and_grads(batch, params)
