@@ -531,6 +531,33 @@ int spmf_waic_accumulate(spmf_ctx* ctx, const spmf_counts* counts, int S,
                          double* sums6, double* row_out, void* scratch,
                          size_t scratch_bytes, void* stream);
 
+/* ---- streaming per-row top-k (added within ABI 6: two new entry points, no struct changed) ----
+ * For every row of `counts` the k cells with the largest posterior predictive mean over S >= 1
+ * draws, without a [B,D] array (csrc/topk.hip):
+ *   score_bd = (1/S) sum_s m_s,  m_s = rate_s on a Poisson column, sigmoid(logit_s) on a Bernoulli
+ *   column (a Bernoulli context, the Bernoulli columns of a mixed one),
+ * rate_s / logit_s being what spmf_dense_ll writes as `rate` for draw s.  A cell is a candidate
+ * when its score is finite (a NaN count makes its whole row's z NaN: that row has none) and, with
+ * bit 0 of `flags` (exclude stored cells), when `counts` holds no entry for it.  cols_out / score_out
+ * = [n_rows][k] int32 / fp32: the row's best k candidates, score descending, equal scores by
+ * ascending column; a row with fewer candidates is padded with column -1 / score -inf.  The result
+ * is the exact top k under that order of the fp32 scores (the mean is taken in draw order), so two
+ * calls on the same inputs return the same bits.
+ * params: only u, v, w, s (slots 2, 0, 1, 7) are read, each with the leading axis S.
+ * scratch: 256-byte aligned, at least spmf_topk_scratch_bytes(ctx, counts->n_rows, S) bytes (the
+ * scratch of the WAIC call, a bitmap of the stored cells, n_rows * ceil(D/32) words, and for a
+ * batch too small to fill the device the partial results of its column slices: call it over row
+ * chunks to bound it); SPMF_E_WORKSPACE when short.  SPMF_E_ARG for S outside 1..65535, k outside
+ * 1..64, unknown flag bits, NULL pointers, a misaligned scratch, a mixed context without column
+ * types or a struct_size mismatch.  n_rows == 0 returns SPMF_OK.  The context's workspace is not
+ * touched: the call may sit between other calls on the context, a spmf_step_begin .. spmf_step_end
+ * pair included.  Stream-ordered, synchronises nowhere.  K as for spmf_waic_accumulate. */
+size_t spmf_topk_scratch_bytes(const spmf_ctx* ctx, int64_t n_rows, int S);
+int spmf_topk_rows(spmf_ctx* ctx, const spmf_counts* counts, int S,
+                   const float* const params[SPMF_NVARS], const float* eta, int k,
+                   unsigned flags, int32_t* cols_out, float* score_out, void* scratch,
+                   size_t scratch_bytes, void* stream);
+
 /* Reductions of the non-finite rule (poisson.py:606-616) over a dense ll
  * buffer of n cells; io = double[3] on the device.
  *   pass 0: io[0] = min(io[0], min over finite cells)  (initialise io[0]=0:

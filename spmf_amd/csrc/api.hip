@@ -595,7 +595,7 @@ int spmf_ctx_set_deterministic(spmf_ctx* c, void* scratch, size_t bytes) {
 
 // ---- the launches' argument blocks, each built in one place and by name ----------------------
 // The per-draw tables and row outputs a launch sequence works on: those of the bound workspace (draw 0), or the
-// caller's scratch (spmf_waic_accumulate)
+// caller's scratch (spmf_waic_accumulate, spmf_topk_rows)
 struct Tables {
   float *Ap, *Vp, *phi;
   double *dprep, *dacc;
@@ -1116,7 +1116,7 @@ int spmf_elbo_fwd_bwd(spmf_ctx* c, const spmf_counts* ct, int S, double prior_we
   return spmf_step_end(c, ct->n_rows, ct->lgamma_sum, stream);
 }
 
-// spmf_encode / spmf_dense_ll / spmf_waic_accumulate: the checks, the prep launch and the encode sweep: z of every
+// spmf_encode / spmf_dense_ll / spmf_waic_accumulate / spmf_topk_rows: the checks, the prep launch and the encode sweep: z of every
 // row under each of S draws into T->z.  T == nullptr: the tables of the workspace, bound here (one draw).
 // Nothing is launched for an empty batch.
 static int encode_rows(spmf_ctx* c, const char* fn, const spmf_counts* ct, int S, const Tables* T, const float* u,
@@ -1230,6 +1230,103 @@ int spmf_waic_accumulate(spmf_ctx* c, const spmf_counts* ct, int S, const float*
   WaicArgs wa{ct->n_rows, ct->nnz, c->D, c->KP, S, lik, T.z, T.Vp, T.phi, c->ctype, ct->row_ptr, ct->col_idx, ct->val,
       sums6, row_out};
   if (!launch_waic(wa, st)) return fail(c, SPMF_E_UNSUPPORTED, "waic_accumulate: no kernel for this K / likelihood");
+  HIPCHK(c, hipGetLastError());
+  return SPMF_OK;
+}
+
+// ---- streaming per-row top-k of the posterior predictive mean (topk.hip) ---------------------
+static int device_cus(const spmf_ctx* c) {
+  int n = 0;
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || n < 1) {
+    (void)hipGetLastError();
+    n = 256;   // no device to ask (a host-only caller sizing a scratch): an MI355X
+  }
+  return n;
+}
+// Column slices (gridDim.y) of the select launch.  A workgroup owns 64 rows and sweeps the column blocks of its
+// slice, and two workgroups are resident per CU at the widest candidate buffer: with fewer than 2 * CUs row
+// blocks the columns are split until the grid has that many workgroups -- never into more slices than column
+// blocks or than the merge kernel holds (kTopkMaxSlices) -- and the count is then lowered to the slices that
+// ceil(blocks / slices) blocks each leave non-empty.  At 2 * CUs row blocks and above: one slice, no merge.
+static int topk_slices(int64_t n_rows, int D, int cus) {
+  const int64_t rb = (n_rows + 63) / 64, cb = ((int64_t)D + 63) / 64;
+  if (rb < 1 || rb >= 2 * (int64_t)cus) return 1;
+  int64_t nsl = (2 * (int64_t)cus + rb - 1) / rb;
+  if (nsl > kTopkMaxSlices) nsl = kTopkMaxSlices;
+  if (nsl > cb) nsl = cb;
+  const int64_t per = (cb + nsl - 1) / nsl;
+  return (int)((cb + per - 1) / per);
+}
+// Scratch of one call: the carve of the WAIC call, the bitmap of the stored cells and the slices' results
+// (sized for k = kTopkMaxK: the size does not depend on the call's k or flags)
+struct TopkCarve {
+  WaicCarve w;
+  size_t bits, pcols, pscores, total;
+  int slices;
+};
+static TopkCarve topk_carve(const spmf_ctx* c, int64_t rows, int S) {
+  TopkCarve k;
+  k.w = waic_carve(c, rows, S);
+  k.slices = topk_slices(rows, c->D, device_cus(c));
+  size_t o = k.w.total;
+  k.bits = o;    o += al((size_t)rows * ((c->D + 31) / 32) * sizeof(uint32_t));
+  const size_t part = k.slices > 1 ? (size_t)k.slices * rows * kTopkMaxK : 0;
+  k.pcols = o;   o += al(part * sizeof(int32_t));
+  k.pscores = o; o += al(part * sizeof(float));
+  k.total = o;
+  return k;
+}
+
+size_t spmf_topk_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S) {
+  if (!c || n_rows < 0 || S < 1) return 0;
+  return topk_carve(c, n_rows, S).total;
+}
+
+int spmf_topk_rows(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS], const float* eta,
+    int k, unsigned flags, int32_t* cols_out, float* score_out, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!c) return SPMF_E_ARG;
+  if (S < 1 || S > 65535) return fail(c, SPMF_E_ARG, "topk_rows: S must be in 1..65535");
+  if (k < 1 || k > kTopkMaxK) return fail(c, SPMF_E_ARG, "topk_rows: k must be in 1..64");
+  if (flags & ~1u) return fail(c, SPMF_E_ARG, "topk_rows: unknown flag (bit 0: exclude stored cells)");
+  if (!params || !eta || !cols_out || !score_out || !scratch) return fail(c, SPMF_E_ARG, "topk_rows: null argument");
+  const float *u = params[2], *v = params[0], *w = params[1], *s = params[7];
+  if (!u || !v || !w || !s) return fail(c, SPMF_E_ARG, "topk_rows: params u, v, w, s (slots 2, 0, 1, 7) "
+      "must be set, each [S, ...]");
+  if ((uintptr_t)scratch & 255) return fail(c, SPMF_E_ARG, "topk_rows: scratch must be 256-byte aligned");
+  const int lik = likelihood_code(c);
+  if (lik == 3 && !c->ctype) return fail(c, SPMF_E_ARG, "topk_rows: spmf_ctx_set_column_types was not called");
+  int rc = check_counts(c, ct);   // (the scratch is sized by the batch; encode_rows checks the rest)
+  if (rc) return rc;
+  // the encode sweep of S draws gathers z with 32-bit byte offsets per draw; the select kernel's row blocks
+  // are a 31-bit grid extent
+  if (ct->n_rows > ((int64_t)1 << 31) - 64) return fail(c, SPMF_E_ARG, "topk_rows: too many rows in one call");
+  const TopkCarve tc = topk_carve(c, ct->n_rows, S);
+  if (tc.total > scratch_bytes) {
+    char b[160];
+    snprintf(b, sizeof b, "topk_rows: scratch too small: need %zu bytes for rows=%lld S=%d, have %zu", tc.total,
+        (long long)ct->n_rows, S, scratch_bytes);
+    return fail(c, SPMF_E_WORKSPACE, b);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  char* base = (char*)scratch;
+  Tables T{};
+  T.Ap = (float*)(base + tc.w.Ap); T.Vp = (float*)(base + tc.w.Vp); T.phi = (float*)(base + tc.w.phi);
+  T.dprep = (double*)(base + tc.w.dprep); T.dacc = (double*)(base + tc.w.dacc);
+  T.z = T.gzs = (float*)(base + tc.w.z);
+  rc = encode_rows(c, "topk_rows", ct, S, &T, u, v, w, s, eta, st);
+  if (rc || ct->n_rows == 0) return rc;
+  TopkArgs ta{};
+  ta.B = ct->n_rows; ta.nnz = ct->nnz; ta.D = c->D; ta.KP = c->KP; ta.S = S; ta.lik = lik; ta.k = k;
+  ta.slices = tc.slices;
+  ta.z = T.z; ta.Vp = T.Vp; ta.phi = T.phi; ta.ctype = c->ctype;
+  ta.row_ptr = ct->row_ptr; ta.col = ct->col_idx;
+  if (flags & 1u) {
+    ta.stored = (uint32_t*)(base + tc.bits);
+    HIPCHK(c, hipMemsetAsync(ta.stored, 0, (size_t)ct->n_rows * ((c->D + 31) / 32) * sizeof(uint32_t), st));
+  }
+  ta.part_cols = (int32_t*)(base + tc.pcols); ta.part_scores = (float*)(base + tc.pscores);
+  ta.cols = cols_out; ta.scores = score_out;
+  if (!launch_topk(ta, st)) return fail(c, SPMF_E_UNSUPPORTED, "topk_rows: no kernel for this K / likelihood");
   HIPCHK(c, hipGetLastError());
   return SPMF_OK;
 }

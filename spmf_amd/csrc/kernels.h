@@ -201,6 +201,26 @@ struct WaicArgs {
   double* row_out;                 // [B][2] (sum_d lppd, sum_d pwaic), accumulated; may be null
 };
 bool launch_waic(const WaicArgs& a, hipStream_t st);
+// topk.hip: per row the k cells with the largest posterior predictive mean over S draws (mean of the rate on a
+// Poisson column, of sigmoid(logit) on a Bernoulli one), ordered by (score descending, column ascending) and
+// padded with column -1 / score -inf.  false: KP / lik / k / slices not built (nothing launched).
+constexpr int kTopkMaxK = 64;
+constexpr int kTopkMaxSlices = 16;   // column slices of one launch (the merge kernel's LDS holds their candidates)
+struct TopkArgs {
+  int64_t B, nnz;
+  int D, KP, S, lik, k;
+  int slices;                      // gridDim.y of the select launch, 1 .. min(kTopkMaxSlices, column blocks)
+  const float *z, *Vp, *phi;       // [S,B,KP], [S,D,KP], [S,D]
+  const uint8_t* ctype;
+  const int32_t* row_ptr;
+  const int32_t* col;
+  uint32_t* stored;                // zeroed bitmap [B][ceil(D/32)] of the cells to exclude (filled here), or null
+  int32_t* part_cols;              // slices > 1: [slices][B][k] each
+  float* part_scores;
+  int32_t* cols;                   // [B][k]
+  float* scores;                   // [B][k]
+};
+bool launch_topk(const TopkArgs& a, hipStream_t st);
 bool launch_col_pass(int KP, const ColArgs& a, hipStream_t st);   // true: launched, with the pack block if asked
 bool launch_col_widek(int KP, const ColArgs& a, hipStream_t st);  // KP = 128, 256 (widek.hip)
 

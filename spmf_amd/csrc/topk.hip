@@ -1,0 +1,365 @@
+// topk.hip -- streaming per-row top-k of the posterior predictive mean, without a [B,D] array.
+//
+// The score of a cell (b, d) over the draws s = 0 .. S-1 is
+//   score_bd = (1/S) sum_s m_s,   m_s = rate_s (Poisson column) | sigmoid(logit_s) (Bernoulli column)
+// with rate_s / logit_s = cell_rate(<z_sb, V'_sd>, phi_sd) exactly as dense_ll.hip and waic.hip form it.
+// Per row the k candidates with the largest score leave the kernel, ordered by (score descending,
+// column ascending); a candidate is a cell with a finite score that is not stored in the batch (when
+// stored cells are excluded).  Missing candidates are padded with column -1 / score -inf.
+//
+// Launches over the per-draw tables z[S,B,KP] (encode sweep), V'[S,D,KP], phi[S,D] (prep):
+//   topk_mark_kernel   : (stored cells excluded) one wave per row ORs a bit per CSR entry into a zeroed
+//     bitmap [B][ceil(D/32)]: CSR columns are not sorted inside a row, so a block of cells cannot find
+//     its stored entries by search.
+//   topk_select_kernel : a workgroup owns 64 rows and sweeps 64-column blocks.  Per block the scores are
+//     formed like the statistics of waic_dense_kernel: 32 x 32 wave tiles of <z, V'> on the exact-f32
+//     matrix cores (v_mfma_f32_32x32x2_f32), double-buffered LDS operand tiles over (draw, K chunk), m_s
+//     added in draw order to 16 accumulators per lane.  Selection: LDS holds per row the k-th best
+//     candidate so far (score, column) and a buffer of CAP candidates.  A cell that beats its row's
+//     threshold -- and only such a cell looks up its bit -- is appended through an LDS counter; a row
+//     whose buffer is full is compacted to its best k by rank (every lane counts the entries that
+//     precede its own in the (score, column) order, which is strict since columns are distinct) and the
+//     threshold moves up.  Cells that found the buffer full try again behind the compaction if they still
+//     beat the new threshold.  What is dropped is never among the best k of what was seen, so the result
+//     is the exact top k under that order whatever the order of the appends: bit-reproducible.
+//     After the first blocks a cell beats the threshold with probability ~ k / (columns seen).
+//   topk_merge_kernel  : with few row blocks the columns are split over gridDim.y slices (api.hip
+//     topk_slices), each writing its k per row; one wave per row ranks the slices' candidates.
+//
+// LDS and occupancy (160 KiB per CU): operand tiles 2 x 2 x 64 x (KC+4) floats = 36 864 B at KC = 32,
+// thresholds and counters 768 B, candidates 64 x CAP x 8 B.  CAP = 32 (k <= 16): 54 272 B with alignment,
+// CAP = 80 (k <= 64): 78 848 B: two workgroups fit at the widest buffer, three at the narrow one.  The
+// registers set the occupancy reached: 171 .. 202 VGPRs + 16 AGPRs at KC = 32, no spills, which is two
+// waves per SIMD = two workgroups (8 waves) per CU for every k (three at KC = 8 / 16 on the Poisson codes).
+// All arithmetic is fp32 FMA.
+#include "common.h"
+#include "kernels.h"
+
+namespace spmf {
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// the order of the result: score descending, ties by ascending column
+__device__ __forceinline__ bool precedes(float s, int c, float s2, int c2) { return s > s2 || (s == s2 && c < c2); }
+
+// predictive mean of a cell from its rate (Poisson) or logit (Bernoulli)
+__device__ __forceinline__ float cell_mean(bool bern, float r) {
+  if (!bern) return r;
+  const float e = expf(-fabsf(r));
+  const float p = 1.f / (1.f + e);   // sigmoid(|r|)
+  return r >= 0.f ? p : e * p;
+}
+
+// One wave sorts the first n (<= CAP) candidates of a row by rank, keeps min(n, k) and, with k of them,
+// sets the row's threshold to the k-th.  Every lane reads all entries before any lane writes one.
+template <int CAP>
+__device__ __forceinline__ void compact_row(float* cs, int* cc, int n, int k, int lane, int* cnt, float* ts, int* tc) {
+  const bool h0 = lane < n, h1 = CAP > 64 && lane + 64 < n;
+  const float s0 = h0 ? cs[lane] : 0.f, s1 = h1 ? cs[lane + 64] : 0.f;
+  const int c0 = h0 ? cc[lane] : 0, c1 = h1 ? cc[lane + 64] : 0;
+  int r0 = 0, r1 = 0;
+  for (int j = 0; j < n; ++j) {
+    const float sj = cs[j];
+    const int cj = cc[j];
+    r0 += precedes(sj, cj, s0, c0) ? 1 : 0;
+    if (CAP > 64) r1 += precedes(sj, cj, s1, c1) ? 1 : 0;
+  }
+  __builtin_amdgcn_wave_barrier();
+  if (h0 && r0 < k) {
+    cs[r0] = s0;
+    cc[r0] = c0;
+    if (r0 == k - 1) {
+      *ts = s0;
+      *tc = c0;
+    }
+  }
+  if (h1 && r1 < k) {
+    cs[r1] = s1;
+    cc[r1] = c1;
+    if (r1 == k - 1) {
+      *ts = s1;
+      *tc = c1;
+    }
+  }
+  if (lane == 0) *cnt = n < k ? n : k;
+}
+
+}  // namespace
+
+// one wave per row: a bit per stored cell
+__global__ __launch_bounds__(256) void topk_mark_kernel(int64_t B, int D, int W, const int32_t* __restrict__ row_ptr,
+                                                        const int32_t* __restrict__ col, uint32_t* __restrict__ bits) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  for (int64_t b = wave; b < B; b += nwaves) {
+    const int start = row_ptr[b], end = row_ptr[b + 1];
+    for (int i = start + lane; i < end; i += 64) {
+      const int d = col[i];
+      if ((unsigned)d < (unsigned)D) atomicOr(&bits[(size_t)b * W + (d >> 5)], 1u << (d & 31));
+    }
+  }
+}
+
+// KC: floats of the K axis per LDS tile (8, 16, 32); KP > KC runs KP / KC chunks per draw.  CAP: candidates
+// buffered per row (k <= CAP - 16).  Grid (row blocks, column slices); slice y writes cols / scores [y][B][k].
+template <int KC, int LIK, int CAP>
+__global__ __launch_bounds__(256) void topk_select_kernel(int64_t B, int D, int KP, int S, int k, int cb_per_slice, int W,
+                                                          const float* __restrict__ z, const float* __restrict__ Vp,
+                                                          const float* __restrict__ phi,
+                                                          const uint8_t* __restrict__ ctype,
+                                                          const uint32_t* __restrict__ stored,
+                                                          int32_t* __restrict__ cols, float* __restrict__ scores) {
+  constexpr int PITCH = KC + 4;
+  constexpr int NLD = KC / 8;          // float4 per thread and (draw, chunk): 2 tiles x 64 rows x KC floats
+  constexpr int TQ = 16 * KC;          // float4 per tile
+  __shared__ float tiles[2][2][64][PITCH];
+  __shared__ float cand_s[64][CAP];
+  __shared__ int cand_c[64][CAP];
+  __shared__ float thr_s[64];
+  __shared__ int thr_c[64];
+  __shared__ int cnt[64];
+  const int t = threadIdx.x;
+  const int lane = t & 63, wv = t >> 6;
+  const int i32 = lane & 31, h = lane >> 5;
+  const int wr = wv >> 1, wc = wv & 1;
+  const int64_t b0 = (int64_t)blockIdx.x * 64;
+  const int NCH = KP > KC ? KP / KC : 1;
+  const int NIT = S * NCH;
+  const int CB = (D + 63) / 64;
+  const int cb0 = blockIdx.y * cb_per_slice;
+  const int cb1 = cb0 + cb_per_slice < CB ? cb0 + cb_per_slice : CB;
+  const float inv_s = 1.f / (float)S;
+  if (t < 64) {
+    thr_s[t] = -INFINITY;
+    thr_c[t] = 0x7fffffff;
+    cnt[t] = 0;
+  }
+  __syncthreads();
+
+  for (int cb = cb0; cb < cb1; ++cb) {
+    const int d0 = cb * 64;
+    const int d = d0 + wc * 32 + i32;
+    const bool bern = lik_bern(LIK) || (LIK == 3 && d < D && cell_is_bern(LIK, ctype, d));   // (no type behind D)
+
+    auto fetch = [&](int it, float4* pre) {
+      const int s = it / NCH, kc0 = (it % NCH) * KC;
+#pragma unroll
+      for (int j = 0; j < NLD; ++j) {
+        const int idx = t + 256 * j;
+        const int tile = idx / TQ, rem = idx % TQ;
+        const int row = rem / (KC / 4), kk = kc0 + 4 * (rem % (KC / 4));
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (kk < KP) {
+          if (tile == 0) {
+            if (b0 + row < B) v = *reinterpret_cast<const float4*>(z + ((size_t)s * B + b0 + row) * KP + kk);
+          } else {
+            if (d0 + row < D) v = *reinterpret_cast<const float4*>(Vp + ((size_t)s * D + d0 + row) * KP + kk);
+          }
+        }
+        pre[j] = v;
+      }
+    };
+    auto stash = [&](int buf, const float4* pre) {
+#pragma unroll
+      for (int j = 0; j < NLD; ++j) {
+        const int idx = t + 256 * j;
+        const int tile = idx / TQ, rem = idx % TQ;
+        *reinterpret_cast<float4*>(&tiles[buf][tile][rem / (KC / 4)][4 * (rem % (KC / 4))]) = pre[j];
+      }
+    };
+
+    float sc[16];
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      sc[r] = 0.f;
+      acc[r] = 0.f;
+    }
+    float4 pre[NLD];
+    fetch(0, pre);
+    stash(0, pre);   // (the last barrier of the block before released both buffers)
+    __syncthreads();
+    float ph = 0.f;
+    for (int it = 0; it < NIT; ++it) {
+      const int buf = it & 1;
+      const int s = it / NCH, ch = it % NCH;
+      if (it + 1 < NIT) fetch(it + 1, pre);
+      if (ch == 0) ph = d < D ? phi[(size_t)s * D + d] : 0.f;
+      // lane half h takes k = 8 q + 4 h + e of the chunk for both operands (waic.hip)
+      const float* ar = &tiles[buf][0][wr * 32 + i32][4 * h];
+      const float* br = &tiles[buf][1][wc * 32 + i32][4 * h];
+#pragma unroll
+      for (int qk = 0; qk < KC / 8; ++qk) {
+        const float4 a = *reinterpret_cast<const float4*>(ar + 8 * qk);
+        const float4 b = *reinterpret_cast<const float4*>(br + 8 * qk);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
+      }
+      if (ch == NCH - 1) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          float ey;
+          sc[r] += cell_mean(bern, cell_rate(LIK, acc[r], ph, ey));
+          acc[r] = 0.f;
+        }
+      }
+      if (it + 1 < NIT) stash(buf ^ 1, pre);
+      __syncthreads();
+    }
+
+    // ---- selection: the lane's 16 cells are column d of 16 different rows
+    unsigned pend = 0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int rl = wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+      const int64_t b = b0 + rl;
+      const float v = sc[r] * inv_s;
+      sc[r] = v;
+      bool in = b < B && d < D && isfinite(v) && precedes(v, d, thr_s[rl], thr_c[rl]);
+      if (in && stored) in = !((stored[(size_t)b * W + (d >> 5)] >> (d & 31)) & 1u);
+      pend |= in ? 1u << r : 0u;
+    }
+    while (true) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        if (pend >> r & 1u) {
+          const int rl = wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+          const int slot = atomicAdd(&cnt[rl], 1);
+          if (slot < CAP) {
+            cand_s[rl][slot] = sc[r];
+            cand_c[rl][slot] = d;
+            pend &= ~(1u << r);
+          }
+        }
+      }
+      __syncthreads();
+      for (int i = 0; i < 16; ++i) {        // wave wv keeps rows 16 wv .. 16 wv + 15
+        const int rl = wv * 16 + i;
+        const int n = cnt[rl];              // (wave-uniform)
+        if (n >= CAP) compact_row<CAP>(cand_s[rl], cand_c[rl], CAP, k, lane, &cnt[rl], &thr_s[rl], &thr_c[rl]);
+      }
+      // a cell is still pending only where its row was full, and that row now has CAP - k free slots
+      if (!__syncthreads_or(pend != 0)) break;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int rl = wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        if ((pend >> r & 1u) && !precedes(sc[r], d, thr_s[rl], thr_c[rl])) pend &= ~(1u << r);
+      }
+    }
+  }
+
+  // ---- the rows' best k, in order
+  for (int i = 0; i < 16; ++i) {
+    const int rl = wv * 16 + i;
+    const int n = cnt[rl];                  // (< CAP: a full row was compacted where it filled up)
+    if (n > 0) compact_row<CAP>(cand_s[rl], cand_c[rl], n, k, lane, &cnt[rl], &thr_s[rl], &thr_c[rl]);
+  }
+  __syncthreads();
+  for (int i = 0; i < 16; ++i) {
+    const int rl = wv * 16 + i;
+    const int64_t b = b0 + rl;
+    if (b < B && lane < k) {
+      const bool have = lane < cnt[rl];
+      const size_t o = ((size_t)blockIdx.y * B + b) * k + lane;
+      cols[o] = have ? cand_c[rl][lane] : -1;
+      scores[o] = have ? cand_s[rl][lane] : -INFINITY;
+    }
+  }
+}
+
+constexpr int kMergeMax = kTopkMaxSlices * kTopkMaxK;
+
+// one wave per row: the best k of the slices' candidates pc / ps [nsl][B][k] (padding: column -1)
+__global__ __launch_bounds__(64) void topk_merge_kernel(int64_t B, int k, int nsl, const int32_t* __restrict__ pc,
+                                                        const float* __restrict__ ps, int32_t* __restrict__ cols,
+                                                        float* __restrict__ scores) {
+  __shared__ float s[kMergeMax];
+  __shared__ int c[kMergeMax];
+  const int lane = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const int n = nsl * k;
+  for (int i = lane; i < n; i += 64) {
+    const size_t o = ((size_t)(i / k) * B + b) * k + (i % k);
+    c[i] = pc[o];
+    s[i] = ps[o];
+  }
+  __syncthreads();
+  int nv = 0;
+  for (int i = lane; i < n; i += 64) {
+    const int ci = c[i];
+    if (ci < 0) continue;
+    const float si = s[i];
+    ++nv;
+    int rank = 0;
+    for (int j = 0; j < n; ++j) rank += (c[j] >= 0 && precedes(s[j], c[j], si, ci)) ? 1 : 0;
+    if (rank < k) {
+      cols[(size_t)b * k + rank] = ci;
+      scores[(size_t)b * k + rank] = si;
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) nv += __shfl_xor(nv, m);
+  if (lane < k && lane >= nv) {
+    cols[(size_t)b * k + lane] = -1;
+    scores[(size_t)b * k + lane] = -INFINITY;
+  }
+}
+
+template <int KC, int CAP>
+static bool launch_select(const TopkArgs& a, int32_t* cols, float* scores, hipStream_t st) {
+  const int CB = (a.D + 63) / 64;
+  const int per = (CB + a.slices - 1) / a.slices;
+  const dim3 grid((unsigned)((a.B + 63) / 64), (unsigned)a.slices);
+  const int W = (a.D + 31) / 32;
+#define SPMF_TOPK(L_)                                                                                         \
+  hipLaunchKernelGGL((topk_select_kernel<KC, L_, CAP>), grid, dim3(256), 0, st, a.B, a.D, a.KP, a.S, a.k, per, W, \
+                     a.z, a.Vp, a.phi, a.ctype, a.stored, cols, scores)
+  switch (a.lik) {
+    case 0: SPMF_TOPK(0); break;
+    case 1: SPMF_TOPK(1); break;
+    case 2: SPMF_TOPK(2); break;
+    case 3: SPMF_TOPK(3); break;
+    case 4: SPMF_TOPK(4); break;
+    default: return false;
+  }
+#undef SPMF_TOPK
+  return true;
+}
+
+template <int KC>
+static bool launch_select_kc(const TopkArgs& a, int32_t* cols, float* scores, hipStream_t st) {
+  return a.k <= 16 ? launch_select<KC, 32>(a, cols, scores, st) : launch_select<KC, 80>(a, cols, scores, st);
+}
+
+bool launch_topk(const TopkArgs& a, hipStream_t st) {
+  const int CB = (a.D + 63) / 64;
+  if (a.k < 1 || a.k > kTopkMaxK || a.slices < 1 || a.slices > kTopkMaxSlices || a.slices > CB) return false;
+  if (a.KP != 4 && a.KP != 8 && a.KP != 16 && a.KP != 32 && a.KP != 64 && a.KP != 128 && a.KP != 256) return false;
+  if (a.lik < 0 || a.lik > 4) return false;
+  if (a.stored && a.nnz > 0) {
+    const int64_t want = (a.B + 3) / 4;
+    const int nb = (int)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
+    hipLaunchKernelGGL(topk_mark_kernel, dim3(nb), dim3(256), 0, st, a.B, a.D, (a.D + 31) / 32, a.row_ptr, a.col,
+                       a.stored);
+  }
+  int32_t* cols = a.slices > 1 ? a.part_cols : a.cols;
+  float* scores = a.slices > 1 ? a.part_scores : a.scores;
+  bool ok;
+  switch (a.KP) {
+    case 4: case 8: ok = launch_select_kc<8>(a, cols, scores, st); break;
+    case 16: ok = launch_select_kc<16>(a, cols, scores, st); break;
+    default: ok = launch_select_kc<32>(a, cols, scores, st); break;
+  }
+  if (!ok) return false;
+  if (a.slices > 1)
+    hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)a.B), dim3(64), 0, st, a.B, a.k, a.slices, a.part_cols,
+                       a.part_scores, a.cols, a.scores);
+  return true;
+}
+
+}  // namespace spmf

@@ -626,12 +626,6 @@ class PoissonFactorization:
         S, P = self._pack_params(draws, names=("s", "u", "v", "w"))
         if S < 2:
             raise ValueError("waic_streaming needs at least 2 draws (the variance over the draws)")
-        if callable(data):
-            batches = data()
-        elif isinstance(data, (dict, SparseCounts)) or hasattr(data, "shape"):
-            batches = (data,)
-        else:
-            batches = data
         lib, h = _lib.load(), self._handle()
         eta = self._eta_device()
         stream = torch.cuda.current_stream(self.device).cuda_stream
@@ -639,27 +633,14 @@ class PoissonFactorization:
         sums = torch.zeros(_waic.NSUMS, dtype=torch.float64, device=self.device)
         KP = int(lib.spmf_padded_k(h))
         scratch, rows_out = None, []
-        for batch in batches:
-            sc, cs = self._batch(batch)
-            pr = batch.get("panels") if isinstance(batch, dict) else None
-            p0, p1 = (pr or (0, None))
-            p1 = sc.n_panels if p1 is None else min(int(p1), sc.n_panels)
-            cap = int(max_rows) if max_rows else max(1, (1 << 28) // (S * KP))
-            step = max(1, cap // sc.panel_rows)
-            rows = torch.zeros(cs.n_rows, 2, dtype=torch.float64, device=self.device) if row_scores else None
-            key = (sc._xi_key, sc._g_key)
-            for q0 in range(int(p0), p1, step):
-                q1 = min(q0 + step, p1)
-                sub = sc.__dict__.setdefault("_struct_cache", {}).setdefault(
-                    ((q0, q1),) + key, sc.batch_struct(q0, q1))
-                if sub.n_rows == 0:
-                    continue
+        for n_rows, chunks in self._row_chunks(data, S * KP * 4, max_rows):
+            rows = torch.zeros(n_rows, 2, dtype=torch.float64, device=self.device) if row_scores else None
+            for r0, sub in chunks:
                 need = int(lib.spmf_waic_scratch_bytes(h, int(sub.n_rows), S)) + 256
                 if scratch is None or scratch.numel() < need:
                     scratch = None
                     scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
                 off = (-scratch.data_ptr()) % 256
-                r0 = (q0 - int(p0)) * sc.panel_rows
                 _lib.check(h, lib.spmf_waic_accumulate(
                     h, C.byref(sub), S, pin, eta.data_ptr(), sums.data_ptr(),
                     rows[r0:].data_ptr() if rows is not None else None,
@@ -671,6 +652,93 @@ class PoissonFactorization:
             allrows = torch.cat(rows_out) if rows_out else torch.zeros(0, 2, dtype=torch.float64, device=self.device)
             out["row_lppd"], out["row_pwaic"] = allrows[:, 0].contiguous(), allrows[:, 1].contiguous()
         return out
+
+    def _row_chunks(self, data, row_bytes, max_rows):
+        """The batch and row-chunk iteration of the streaming calls (waic_streaming, top_k).
+        ``data``: one batch (dict / counts), an iterable of batches or a data-factory callable; a
+        ``{"counts": sc, "panels": (p0, p1)}`` batch is the rows of those panels.  Yields
+        ``(n_rows, chunks)`` per batch; ``chunks`` yields ``(r0, sub)``: the batch struct of the
+        next non-empty chunk of whole panels and its first row inside the batch.  A chunk has at
+        most ``max_rows`` rows (default: 1 GiB of scratch at ``row_bytes`` per row)."""
+        if callable(data):
+            batches = data()
+        elif isinstance(data, (dict, SparseCounts)) or hasattr(data, "shape"):
+            batches = (data,)
+        else:
+            batches = data
+        for batch in batches:
+            sc, cs = self._batch(batch)
+            pr = batch.get("panels") if isinstance(batch, dict) else None
+            p0, p1 = (pr or (0, None))
+            p1 = sc.n_panels if p1 is None else min(int(p1), sc.n_panels)
+            cap = int(max_rows) if max_rows else max(1, (1 << 30) // int(row_bytes))
+            step = max(1, cap // sc.panel_rows)
+
+            def chunks(sc=sc, p0=int(p0), p1=p1, step=step):
+                key = (sc._xi_key, sc._g_key)
+                for q0 in range(p0, p1, step):
+                    q1 = min(q0 + step, p1)
+                    sub = sc.__dict__.setdefault("_struct_cache", {}).setdefault(
+                        ((q0, q1),) + key, sc.batch_struct(q0, q1))
+                    if sub.n_rows == 0:
+                        continue
+                    yield (q0 - p0) * sc.panel_rows, sub
+            yield int(cs.n_rows), chunks()
+
+    def top_k(self, data, k=10, nsamples=32, draws=None, exclude_stored=True, max_rows=None):
+        """Per row the ``k`` columns with the largest posterior predictive mean
+        score_bd = mean_s m_s(b, d), m_s = the rate of draw s on a Poisson column and
+        sigmoid(logit) on a Bernoulli one, without a [B,D] array: the scores are formed and
+        selected in csrc/topk.hip and only [B,k] leaves the kernel.
+
+        ``data``, ``draws`` and ``max_rows`` as in ``waic_streaming`` (``draws`` may hold a single
+        draw, e.g. a point estimate from ``calibrated_expectations``; ``max_rows`` also bounds the
+        bitmap of the stored cells, rows * D / 8 bytes).  ``exclude_stored``: cells the batch
+        stores are no candidates.  A cell with a non-finite score is none either (a NaN count
+        takes its whole row out).
+
+        Returns {'columns': int32 [B,k], 'scores': float32 [B,k]} on the device, the rows of all
+        batches concatenated: score descending, equal scores by ascending column, a row with
+        fewer than k candidates padded with column -1 / score -inf.  Bit-reproducible."""
+        if self._custom_codec is not None:
+            raise NotImplementedError("top_k: custom encoder/decoder callables have no kernel "
+                                      "(use log_likelihood_components, which evaluates them densely)")
+        k = int(k)
+        if not 1 <= k <= 64:
+            raise ValueError("top_k needs 1 <= k <= 64")
+        if draws is None:
+            if int(nsamples) < 1:
+                raise ValueError("top_k needs nsamples >= 1")
+            draws = self.surrogate_distribution.sample(int(nsamples))
+        S, P = self._pack_params(draws, names=("s", "u", "v", "w"))
+        lib, h = _lib.load(), self._handle()
+        eta = self._eta_device()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        pin = _lib.PtrArray(*[P[n].data_ptr() if n in P else None for n in VAR_ORDER])
+        KP = int(lib.spmf_padded_k(h))
+        flags = 1 if exclude_stored else 0
+        scratch, cols_out, scores_out = None, [], []
+        for n_rows, chunks in self._row_chunks(data, S * KP * 4 + (self.feature_dim + 31) // 32 * 4, max_rows):
+            cols = torch.empty(n_rows, k, dtype=torch.int32, device=self.device)
+            scores = torch.empty(n_rows, k, dtype=torch.float32, device=self.device)
+            for r0, sub in chunks:
+                need = int(lib.spmf_topk_scratch_bytes(h, int(sub.n_rows), S)) + 256
+                if scratch is None or scratch.numel() < need:
+                    scratch = None
+                    scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+                off = (-scratch.data_ptr()) % 256
+                _lib.check(h, lib.spmf_topk_rows(
+                    h, C.byref(sub), S, pin, eta.data_ptr(), k, flags, cols[r0:].data_ptr(),
+                    scores[r0:].data_ptr(), scratch.data_ptr() + off, scratch.numel() - off, stream),
+                    "spmf_topk_rows")
+            cols_out.append(cols)
+            scores_out.append(scores)
+        if len(cols_out) == 1:
+            return {"columns": cols_out[0], "scores": scores_out[0]}
+        if not cols_out:
+            return {"columns": torch.empty(0, k, dtype=torch.int32, device=self.device),
+                    "scores": torch.empty(0, k, dtype=torch.float32, device=self.device)}
+        return {"columns": torch.cat(cols_out), "scores": torch.cat(scores_out)}
 
     def _nonfinite_scan(self, sc, cs, data, S, P, max_cells=1 << 27):
         """Dense part of the replacement rule (poisson.py:606-616): the minimum
