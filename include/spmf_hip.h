@@ -558,6 +558,40 @@ int spmf_topk_rows(spmf_ctx* ctx, const spmf_counts* counts, int S,
                    unsigned flags, int32_t* cols_out, float* score_out, void* scratch,
                    size_t scratch_bytes, void* stream);
 
+/* ---- scores of listed cells (added within ABI 6: two new entry points, no struct changed) ----
+ * Held-out evaluation: for n_cells cells (cell_row[i], cell_col[i]) of the batch `counts`, over
+ * S >= 1 draws, without a [S,B,D] tensor (csrc/cells.hip):
+ *   mean_out[i] = (1/S) sum_s m_s, m_s as spmf_topk_rows defines its score (rate_s on a Poisson
+ *                 column, sigmoid(logit_s) on a Bernoulli one), added in draw order;
+ *   lppd_out[i] = logsumexp_s(ll_s) - log S,  ll_s = log p(cell_val[i] | theta_s) by the per-cell
+ *                 formulas of spmf_dense_ll (0 * log 0 := 0), lgamma(x+1) subtracted once.
+ * `counts` conditions the scores: its stored entries encode the rows (z of every row under each
+ * draw), as in every other call; the listed values are never stored by this call.  cell_row is
+ * relative to the first row of `counts`.  The list may be in any order, may repeat cells and may
+ * list cells that `counts` stores or does not store (zeros included).  cell_val == NULL and
+ * lppd_out == NULL together: the mean only.  lppd_out[i] is NaN when any ll_s is not finite (a NaN
+ * value, a rate of 0 under a positive value: the exclusion rule of spmf_waic_accumulate); a NaN
+ * count in `counts` makes its row's z NaN and with it both outputs of the row's cells.  An index
+ * outside [0, n_rows) x [0, D) reads no memory; both outputs of that cell are NaN.  A cell's
+ * outputs depend on the cell alone: not on its place in the list, on the other cells or on how the
+ * rows are cut into calls (no atomics, one summation order), so equal cells get equal bits.
+ * params: only u, v, w, s (slots 2, 0, 1, 7) are read, each with the leading axis S.
+ * scratch: 256-byte aligned, at least spmf_cells_scratch_bytes(ctx, counts->n_rows, S) bytes (the
+ * scratch of the WAIC call: call it over row chunks, each with its own cells, to bound it);
+ * SPMF_E_WORKSPACE when short.  SPMF_E_ARG for S outside 1..65535, a negative n_cells, NULL
+ * params / eta / scratch, NULL cell_row / cell_col / mean_out with n_cells > 0, cell_val and
+ * lppd_out not both NULL or both set, a misaligned scratch, a mixed context without column types or
+ * a struct_size mismatch; every error returns before any launch.  n_cells == 0 or n_rows == 0
+ * returns SPMF_OK without work.  The context's workspace is not touched: the call may sit between
+ * other calls on the context, a spmf_step_begin .. spmf_step_end pair included.  Stream-ordered,
+ * synchronises nowhere.  K as for spmf_waic_accumulate. */
+size_t spmf_cells_scratch_bytes(const spmf_ctx* ctx, int64_t n_rows, int S);
+int spmf_score_cells(spmf_ctx* ctx, const spmf_counts* counts, int S,
+                     const float* const params[SPMF_NVARS], const float* eta, int64_t n_cells,
+                     const int32_t* cell_row, const int32_t* cell_col, const float* cell_val,
+                     float* mean_out, float* lppd_out, void* scratch, size_t scratch_bytes,
+                     void* stream);
+
 /* Reductions of the non-finite rule (poisson.py:606-616) over a dense ll
  * buffer of n cells; io = double[3] on the device.
  *   pass 0: io[0] = min(io[0], min over finite cells)  (initialise io[0]=0:

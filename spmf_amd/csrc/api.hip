@@ -1116,8 +1116,9 @@ int spmf_elbo_fwd_bwd(spmf_ctx* c, const spmf_counts* ct, int S, double prior_we
   return spmf_step_end(c, ct->n_rows, ct->lgamma_sum, stream);
 }
 
-// spmf_encode / spmf_dense_ll / spmf_waic_accumulate / spmf_topk_rows: the checks, the prep launch and the encode sweep: z of every
-// row under each of S draws into T->z.  T == nullptr: the tables of the workspace, bound here (one draw).
+// spmf_encode / spmf_dense_ll / spmf_waic_accumulate / spmf_topk_rows / spmf_score_cells: the checks, the prep
+// launch and the encode sweep: z of every row under each of S draws into T->z.  T == nullptr: the tables of
+// the workspace, bound here (one draw).
 // Nothing is launched for an empty batch.
 static int encode_rows(spmf_ctx* c, const char* fn, const spmf_counts* ct, int S, const Tables* T, const float* u,
     const float* v, const float* w, const float* s, const float* eta, hipStream_t st) {
@@ -1188,6 +1189,19 @@ static WaicCarve waic_carve(const spmf_ctx* c, int64_t rows, int S) {
   return k;
 }
 
+// The tables of a streaming call (spmf_waic_accumulate, spmf_topk_rows, spmf_score_cells) inside its scratch,
+// carved by `k`, filled by the prep launch (S draws) and the encode sweep.  The encode-only sweep writes z and
+// nothing else: gzs and the scalar block are never touched.  Nothing is launched for an empty batch.
+static int scratch_tables(spmf_ctx* c, const char* fn, const spmf_counts* ct, int S, const WaicCarve& k, void* scratch,
+    const float* u, const float* v, const float* w, const float* s, const float* eta, hipStream_t st, Tables& T) {
+  char* base = (char*)scratch;
+  T = Tables{};
+  T.Ap = (float*)(base + k.Ap); T.Vp = (float*)(base + k.Vp); T.phi = (float*)(base + k.phi);
+  T.dprep = (double*)(base + k.dprep); T.dacc = (double*)(base + k.dacc);
+  T.z = T.gzs = (float*)(base + k.z);
+  return encode_rows(c, fn, ct, S, &T, u, v, w, s, eta, st);
+}
+
 size_t spmf_waic_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S) {
   if (!c || n_rows < 0 || S < 2) return 0;
   return waic_carve(c, n_rows, S).total;
@@ -1219,13 +1233,8 @@ int spmf_waic_accumulate(spmf_ctx* c, const spmf_counts* ct, int S, const float*
     return fail(c, SPMF_E_WORKSPACE, b);
   }
   hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)scratch;
-  // the encode-only sweep writes z and nothing else: gzs and the scalar block are never touched
-  Tables T{};
-  T.Ap = (float*)(base + k.Ap); T.Vp = (float*)(base + k.Vp); T.phi = (float*)(base + k.phi);
-  T.dprep = (double*)(base + k.dprep); T.dacc = (double*)(base + k.dacc);
-  T.z = T.gzs = (float*)(base + k.z);
-  rc = encode_rows(c, "waic_accumulate", ct, S, &T, u, v, w, s, eta, st);
+  Tables T;
+  rc = scratch_tables(c, "waic_accumulate", ct, S, k, scratch, u, v, w, s, eta, st, T);
   if (rc || ct->n_rows == 0) return rc;
   WaicArgs wa{ct->n_rows, ct->nnz, c->D, c->KP, S, lik, T.z, T.Vp, T.phi, c->ctype, ct->row_ptr, ct->col_idx, ct->val,
       sums6, row_out};
@@ -1309,11 +1318,8 @@ int spmf_topk_rows(spmf_ctx* c, const spmf_counts* ct, int S, const float* const
   }
   hipStream_t st = (hipStream_t)stream;
   char* base = (char*)scratch;
-  Tables T{};
-  T.Ap = (float*)(base + tc.w.Ap); T.Vp = (float*)(base + tc.w.Vp); T.phi = (float*)(base + tc.w.phi);
-  T.dprep = (double*)(base + tc.w.dprep); T.dacc = (double*)(base + tc.w.dacc);
-  T.z = T.gzs = (float*)(base + tc.w.z);
-  rc = encode_rows(c, "topk_rows", ct, S, &T, u, v, w, s, eta, st);
+  Tables T;
+  rc = scratch_tables(c, "topk_rows", ct, S, tc.w, scratch, u, v, w, s, eta, st, T);
   if (rc || ct->n_rows == 0) return rc;
   TopkArgs ta{};
   ta.B = ct->n_rows; ta.nnz = ct->nnz; ta.D = c->D; ta.KP = c->KP; ta.S = S; ta.lik = lik; ta.k = k;
@@ -1327,6 +1333,55 @@ int spmf_topk_rows(spmf_ctx* c, const spmf_counts* ct, int S, const float* const
   ta.part_cols = (int32_t*)(base + tc.pcols); ta.part_scores = (float*)(base + tc.pscores);
   ta.cols = cols_out; ta.scores = score_out;
   if (!launch_topk(ta, st)) return fail(c, SPMF_E_UNSUPPORTED, "topk_rows: no kernel for this K / likelihood");
+  HIPCHK(c, hipGetLastError());
+  return SPMF_OK;
+}
+
+// ---- posterior predictive mean / lppd of a list of cells (cells.hip) --------------------------
+// Scratch of one call: the carve of the WAIC call (the S draws' tables and encoded rows).
+size_t spmf_cells_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S) {
+  if (!c || n_rows < 0 || S < 1) return 0;
+  return waic_carve(c, n_rows, S).total;
+}
+
+int spmf_score_cells(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS], const float* eta,
+    int64_t n_cells, const int32_t* cell_row, const int32_t* cell_col, const float* cell_val, float* mean_out,
+    float* lppd_out, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!c) return SPMF_E_ARG;
+  if (S < 1 || S > 65535) return fail(c, SPMF_E_ARG, "score_cells: S must be in 1..65535");
+  if (n_cells < 0) return fail(c, SPMF_E_ARG, "score_cells: n_cells is negative");
+  if (!params || !eta || !scratch) return fail(c, SPMF_E_ARG, "score_cells: null argument");
+  if (n_cells > 0 && (!cell_row || !cell_col || !mean_out)) return fail(c, SPMF_E_ARG, "score_cells: cell_row, "
+      "cell_col and mean_out must be set for a non-empty list");
+  if ((cell_val == nullptr) != (lppd_out == nullptr)) return fail(c, SPMF_E_ARG, "score_cells: cell_val and lppd_out "
+      "go together (both NULL: the mean only)");
+  const float *u = params[2], *v = params[0], *w = params[1], *s = params[7];
+  if (!u || !v || !w || !s) return fail(c, SPMF_E_ARG, "score_cells: params u, v, w, s (slots 2, 0, 1, 7) "
+      "must be set, each [S, ...]");
+  if ((uintptr_t)scratch & 255) return fail(c, SPMF_E_ARG, "score_cells: scratch must be 256-byte aligned");
+  const int lik = likelihood_code(c);
+  if (lik == 3 && !c->ctype) return fail(c, SPMF_E_ARG, "score_cells: spmf_ctx_set_column_types was not called");
+  int rc = check_counts(c, ct);   // (the scratch is sized by the batch; encode_rows checks the rest)
+  if (rc) return rc;
+  // the encode sweep of S draws gathers z with 32-bit byte offsets per draw; a cell's row is an int32; the
+  // cell kernel's grid is a 31-bit extent of 256-cell workgroups
+  if (ct->n_rows > ((int64_t)1 << 31) - 64) return fail(c, SPMF_E_ARG, "score_cells: too many rows in one call");
+  if (n_cells > ((int64_t)1 << 38)) return fail(c, SPMF_E_ARG, "score_cells: too many cells in one call");
+  const WaicCarve k = waic_carve(c, ct->n_rows, S);
+  if (k.total > scratch_bytes) {
+    char b[160];
+    snprintf(b, sizeof b, "score_cells: scratch too small: need %zu bytes for rows=%lld S=%d, have %zu", k.total,
+        (long long)ct->n_rows, S, scratch_bytes);
+    return fail(c, SPMF_E_WORKSPACE, b);
+  }
+  if (n_cells == 0 || ct->n_rows == 0) return SPMF_OK;   // (no row: no valid cell; the Python surface lists none)
+  hipStream_t st = (hipStream_t)stream;
+  Tables T;
+  rc = scratch_tables(c, "score_cells", ct, S, k, scratch, u, v, w, s, eta, st, T);
+  if (rc) return rc;
+  CellsArgs ca{ct->n_rows, n_cells, c->D, c->KP, S, lik, T.z, T.Vp, T.phi, c->ctype, cell_row, cell_col, cell_val,
+      mean_out, lppd_out};
+  if (!launch_cells(ca, st)) return fail(c, SPMF_E_UNSUPPORTED, "score_cells: no kernel for this K / likelihood");
   HIPCHK(c, hipGetLastError());
   return SPMF_OK;
 }

@@ -78,6 +78,21 @@ __device__ __forceinline__ float cell_ll(bool bern, float x, float r) {
   const float xl = x == 0.f ? 0.f : x * logf(r);
   return LGAMMA ? xl - lgammaf(x + 1.f) - r : xl - r;
 }
+// predictive mean of a cell from its rate (Poisson) or logit (Bernoulli) (topk.hip, cells.hip)
+__device__ __forceinline__ float cell_mean(bool bern, float r) {
+  if (!bern) return r;
+  const float e = expf(-fabsf(r));
+  const float p = 1.f / (1.f + e);   // sigmoid(|r|)
+  return r >= 0.f ? p : e * p;
+}
+// running log-sum-exp over the draws of a cell: maximum m (start: -inf) and sum se of exp(ll - m) (start: 0),
+// rescaled when m moves (waic.hip, cells.hip)
+__device__ __forceinline__ void lse_update(float ll, float& m, float& se) {
+  const float d = ll - m;
+  const float e = expf(-fabsf(d));
+  se = d > 0.f ? fmaf(se, e, 1.f) : se + e;    // first draw: m = -inf, d = +inf, e = 0 -> se = 1
+  m = fmaxf(m, ll);
+}
 
 // The prep kernel's closed-form column sums (veta[KP], phisum) are written as kPrepSeg
 // partial sums over column segments, dprep[seg][KP+1]: one writer per slot (no atomics,

@@ -221,6 +221,20 @@ struct TopkArgs {
   float* scores;                   // [B][k]
 };
 bool launch_topk(const TopkArgs& a, hipStream_t st);
+// cells.hip: posterior predictive mean (and, with values, lppd) of a list of cells over S draws; an index
+// outside [0,B) x [0,D) reads nothing and gets NaN.  false: KP / lik not built or too many cells (nothing launched).
+struct CellsArgs {
+  int64_t B, n_cells;
+  int D, KP, S, lik;
+  const float *z, *Vp, *phi;       // [S,B,KP], [S,D,KP], [S,D]
+  const uint8_t* ctype;
+  const int32_t* row;              // [n_cells], relative to the first row of z
+  const int32_t* col;              // [n_cells]
+  const float* val;                // [n_cells] or null (mean only)
+  float* mean;                     // [n_cells]
+  float* lppd;                     // [n_cells]; null iff val is null
+};
+bool launch_cells(const CellsArgs& a, hipStream_t st);
 bool launch_col_pass(int KP, const ColArgs& a, hipStream_t st);   // true: launched, with the pack block if asked
 bool launch_col_widek(int KP, const ColArgs& a, hipStream_t st);  // KP = 128, 256 (widek.hip)
 

@@ -44,14 +44,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // the order of the result: score descending, ties by ascending column
 __device__ __forceinline__ bool precedes(float s, int c, float s2, int c2) { return s > s2 || (s == s2 && c < c2); }
 
-// predictive mean of a cell from its rate (Poisson) or logit (Bernoulli)
-__device__ __forceinline__ float cell_mean(bool bern, float r) {
-  if (!bern) return r;
-  const float e = expf(-fabsf(r));
-  const float p = 1.f / (1.f + e);   // sigmoid(|r|)
-  return r >= 0.f ? p : e * p;
-}
-
 // One wave sorts the first n (<= CAP) candidates of a row by rank, keeps min(n, k) and, with k of them,
 // sets the row's threshold to the k-th.  Every lane reads all entries before any lane writes one.
 template <int CAP>

@@ -33,10 +33,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // running statistics of one cell over the draws
 __device__ __forceinline__ void stat_update(float ll, float inv_n, float& m, float& se, float& mu, float& q) {
-  const float d = ll - m;
-  const float e = expf(-fabsf(d));
-  se = d > 0.f ? fmaf(se, e, 1.f) : se + e;    // first draw: m = -inf, d = +inf, e = 0 -> se = 1
-  m = fmaxf(m, ll);
+  lse_update(ll, m, se);
   const float dl = ll - mu;                    // Welford; a non-finite ll leaves q non-finite for good
   mu = fmaf(dl, inv_n, mu);
   q = fmaf(dl, ll - mu, q);

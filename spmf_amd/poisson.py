@@ -344,6 +344,20 @@ class PoissonFactorization:
             cache[key] = sc.batch_struct(*(pr or (0, None)))
         return sc, cache[key]
 
+    def _batch_rows(self, data):
+        """Rows of one batch (of its panel range), read off the counts' shape alone: what
+        ``_batch(data)[1].n_rows`` gives, without building the batch."""
+        x = data[self.count_key] if isinstance(data, dict) else data
+        pr = data.get("panels") if isinstance(data, dict) else None
+        if not isinstance(x, SparseCounts):
+            # counts that are not resident choose their panels when they are laid out
+            return int(self._batch(data)[1].n_rows) if pr else int(x.shape[0])
+        if not pr:
+            return x.n_rows
+        n, rows_per, n_panels = x.n_rows, x.panel_rows, x.n_panels
+        p0, p1 = int(pr[0]), n_panels if pr[1] is None else min(int(pr[1]), n_panels)
+        return max(0, min(p1 * rows_per, n) - p0 * rows_per)
+
     def _pack_params(self, params, names=None):
         """dict name -> tensor  =>  (S, {name: contiguous fp32 [S,*shape]})."""
         D, K = self.feature_dim, self.latent_dim
@@ -739,6 +753,119 @@ class PoissonFactorization:
             return {"columns": torch.empty(0, k, dtype=torch.int32, device=self.device),
                     "scores": torch.empty(0, k, dtype=torch.float32, device=self.device)}
         return {"columns": torch.cat(cols_out), "scores": torch.cat(scores_out)}
+
+    def score_cells(self, data, rows, cols, values=None, nsamples=32, draws=None, max_rows=None):
+        """Held-out evaluation: the posterior predictive mean and, with ``values``, the log
+        pointwise predictive density lppd_i = log mean_s p(value_i | theta_s) of the listed cells
+        ``(rows[i], cols[i])``, without a [S,B,D] array (csrc/cells.hip).  'mean' is the score of
+        ``top_k``: the mean over the draws of the rate on a Poisson column and of sigmoid(logit) on
+        a Bernoulli one.
+
+        ``data`` is ONE batch (dict / counts; ``{"counts": sc, "panels": (p0, p1)}`` is the rows
+        of those panels).  The batch conditions the scores: its stored counts encode the rows, as
+        everywhere else, and the listed values are only scored.  A held-out cell should therefore
+        not also be stored in ``data`` with its true value, or it informs its own row's encoding;
+        that is the caller's split and is not checked.  ``rows`` are relative to the first row of
+        the batch (of the panel range); ``rows``, ``cols``, ``values`` are 1-D and of equal length,
+        numpy or torch on any device, in any order, duplicates and zeros allowed.  ``draws`` /
+        ``nsamples`` as in ``top_k`` (a single draw is allowed), ``max_rows`` as in
+        ``waic_streaming``.
+
+        Returns {'mean': float32 [N]} on the device in the caller's order and, with values,
+        'lppd': float32 [N] plus the summary of ``spmf_amd.heldout.summarize``: 'lppd_sum',
+        'lppd_mean', 'se', 'n', 'n_excluded'.  A cell with a non-finite log-pmf in any draw (NaN
+        value, rate 0 under a positive value) has lppd NaN and is counted in 'n_excluded'; a NaN
+        count in the batch makes every score of its row NaN.  A cell's scores do not depend on
+        the order of the list or on ``max_rows``.  Bit-reproducible."""
+        from . import heldout as _heldout
+        if self._custom_codec is not None:
+            raise NotImplementedError("score_cells: custom encoder/decoder callables have no kernel "
+                                      "(use log_likelihood_components, which evaluates them densely)")
+        if callable(data) or not (isinstance(data, (dict, SparseCounts)) or hasattr(data, "shape")):
+            raise ValueError("score_cells takes ONE batch (a dict or counts), not an iterable or a factory")
+
+        def vector(name, t, floating):
+            if not isinstance(t, torch.Tensor):
+                t = np.asarray(t)
+                if t.size == 0 and not floating:        # [] has no dtype of its own
+                    t = t.astype(np.int64)
+                t = torch.as_tensor(t)
+            if t.dim() != 1:
+                raise ValueError(f"score_cells: {name} must be 1-D, got shape {tuple(t.shape)}")
+            if floating:
+                return t.to(device=self.device, dtype=torch.float32)
+            if t.dtype.is_floating_point or t.dtype == torch.bool:
+                raise ValueError(f"score_cells: {name} must hold integers, got {t.dtype}")
+            return t.to(device=self.device)
+        rows, cols = vector("rows", rows, False), vector("cols", cols, False)
+        vals = vector("values", values, True) if values is not None else None
+        N = int(rows.numel())
+        if cols.numel() != N or (vals is not None and vals.numel() != N):
+            raise ValueError(f"score_cells: rows, cols and values must have equal length, got {N}, "
+                             f"{int(cols.numel())}" + (f", {int(vals.numel())}" if vals is not None else ""))
+        # the index check: one device-side min / max and one read-back, before any library call
+        # (the batch's row count is read off its shape, not off the library's descriptor)
+        n_rows = self._batch_rows(data)
+        if n_rows > 2 ** 31 - 1:
+            raise ValueError(f"score_cells: a batch of {n_rows} rows is beyond the int32 row index of the list; "
+                             "score it by panel ranges")
+        if N:
+            r_lo, r_hi, c_lo, c_hi = torch.stack(
+                [t.to(torch.int64) for t in (rows.min(), rows.max(), cols.min(), cols.max())]).tolist()
+            if r_lo < 0 or r_hi >= n_rows:
+                raise ValueError(f"score_cells: rows must lie in [0, {n_rows}), got {r_lo} .. {r_hi}")
+            if c_lo < 0 or c_hi >= self.feature_dim:
+                raise ValueError(f"score_cells: cols must lie in [0, {self.feature_dim}), got {c_lo} .. {c_hi}")
+        if draws is None:
+            if int(nsamples) < 1:
+                raise ValueError("score_cells needs nsamples >= 1")
+            draws = self.surrogate_distribution.sample(int(nsamples))
+        S, P = self._pack_params(draws, names=("s", "u", "v", "w"))
+        lib, h = _lib.load(), self._handle()
+        eta = self._eta_device()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        pin = _lib.PtrArray(*[P[n].data_ptr() if n in P else None for n in VAR_ORDER])
+        KP = int(lib.spmf_padded_k(h))
+        (lib_rows, chunks), = self._row_chunks(data, S * KP * 4, max_rows)
+        assert lib_rows == n_rows, (lib_rows, n_rows)
+        # cells sorted by row (stable): a row chunk's cells are one contiguous segment
+        rows, order = torch.sort(rows.to(torch.int32), stable=True)
+        cols = cols.to(torch.int32)[order]
+        if vals is not None:
+            vals = vals[order]
+        chunks = list(chunks)
+        # a chunk's segment, from its first and its last row: both fit the int32 of the list
+        first = torch.tensor([r0 for r0, _ in chunks] or [0], dtype=torch.int32, device=self.device)
+        last = torch.tensor([r0 + int(sub.n_rows) - 1 for r0, sub in chunks] or [0], dtype=torch.int32,
+                            device=self.device)
+        edges = torch.stack([torch.searchsorted(rows, first), torch.searchsorted(rows, last, right=True)],
+                            1).tolist() if N else []
+        nan = float("nan")
+        mean = torch.full((N,), nan, dtype=torch.float32, device=self.device)
+        lppd = torch.full((N,), nan, dtype=torch.float32, device=self.device) if vals is not None else None
+        scratch = None
+        for (r0, sub), (lo, hi) in zip(chunks, edges):
+            if hi == lo:
+                continue
+            need = int(lib.spmf_cells_scratch_bytes(h, int(sub.n_rows), S)) + 256
+            if scratch is None or scratch.numel() < need:
+                scratch = None
+                scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+            off = (-scratch.data_ptr()) % 256
+            rel = rows[lo:hi] - r0 if r0 else rows[lo:hi]
+            _lib.check(h, lib.spmf_score_cells(
+                h, C.byref(sub), S, pin, eta.data_ptr(), hi - lo, rel.data_ptr(), cols[lo:hi].data_ptr(),
+                vals[lo:hi].data_ptr() if vals is not None else None, mean[lo:hi].data_ptr(),
+                lppd[lo:hi].data_ptr() if lppd is not None else None,
+                scratch.data_ptr() + off, scratch.numel() - off, stream), "spmf_score_cells")
+        del rows, cols, vals, scratch
+        out = {"mean": torch.empty_like(mean).index_copy_(0, order, mean)}
+        del mean
+        if lppd is not None:
+            out["lppd"] = torch.empty_like(lppd).index_copy_(0, order, lppd)
+            del lppd, order
+            out.update(_heldout.summarize(out["lppd"]))
+        return out
 
     def _nonfinite_scan(self, sc, cs, data, S, P, max_cells=1 << 27):
         """Dense part of the replacement rule (poisson.py:606-616): the minimum
