@@ -594,8 +594,8 @@ int spmf_ctx_set_deterministic(spmf_ctx* c, void* scratch, size_t bytes) {
 }
 
 // ---- the launches' argument blocks, each built in one place and by name ----------------------
-// The per-draw tables and row outputs a launch sequence works on: those of the bound workspace (draw 0), or the
-// caller's scratch (spmf_waic_accumulate, spmf_topk_rows)
+// The per-draw tables and row outputs a launch sequence works on: those of the bound workspace (draw 0), or
+// those of the draw stage inside a streaming call's scratch (draw_stage)
 struct Tables {
   float *Ap, *Vp, *phi;
   double *dprep, *dacc;
@@ -1116,9 +1116,9 @@ int spmf_elbo_fwd_bwd(spmf_ctx* c, const spmf_counts* ct, int S, double prior_we
   return spmf_step_end(c, ct->n_rows, ct->lgamma_sum, stream);
 }
 
-// spmf_encode / spmf_dense_ll / spmf_waic_accumulate / spmf_topk_rows / spmf_score_cells: the checks, the prep
-// launch and the encode sweep: z of every row under each of S draws into T->z.  T == nullptr: the tables of
-// the workspace, bound here (one draw).
+// The checks, the prep launch and the encode sweep: z of every row under each of S draws into T->z.
+// T == nullptr (spmf_encode, spmf_dense_ll): the tables of the workspace, bound here (one draw); otherwise
+// those of the draw stage.
 // Nothing is launched for an empty batch.
 static int encode_rows(spmf_ctx* c, const char* fn, const spmf_counts* ct, int S, const Tables* T, const float* u,
     const float* v, const float* w, const float* s, const float* eta, hipStream_t st) {
@@ -1169,14 +1169,17 @@ int spmf_dense_ll(spmf_ctx* c, const spmf_counts* ct, const float* u, const floa
   return SPMF_OK;
 }
 
-// ---- streaming WAIC (waic.hip) ------------------------------------------------------------
-// Scratch of one call: the S draws' tables and encoded rows.  The context's workspace is not used, so
+// ---- the draw stage of the streaming calls ---------------------------------------------------
+// spmf_waic_accumulate, spmf_topk_rows and spmf_score_cells are one stage and a consumer each.  The stage: for
+// S draws the per-draw tables (prep) and the encoded rows z[S,B,KP] go into the caller's scratch; the consumer
+// kernel then reads z, V' and phi of every draw (kernels.h DrawTables).  The context's workspace is not used, so
 // a step that is bound (or half way: spmf_step_begin .. spmf_step_end) keeps everything it has.
-struct WaicCarve {
+// Scratch of a call = the draw carve + the consumer's own buffers behind it.
+struct DrawCarve {
   size_t Ap, Vp, phi, dprep, dacc, z, total;
 };
-static WaicCarve waic_carve(const spmf_ctx* c, int64_t rows, int S) {
-  WaicCarve k;
+static DrawCarve draw_carve(const spmf_ctx* c, int64_t rows, int S) {
+  DrawCarve k;
   size_t o = 0;
   const size_t KP = c->KP, D = c->D, nS = S;
   k.Ap = o;    o += al(nS * D * KP * sizeof(float));
@@ -1189,55 +1192,69 @@ static WaicCarve waic_carve(const spmf_ctx* c, int64_t rows, int S) {
   return k;
 }
 
-// The tables of a streaming call (spmf_waic_accumulate, spmf_topk_rows, spmf_score_cells) inside its scratch,
-// carved by `k`, filled by the prep launch (S draws) and the encode sweep.  The encode-only sweep writes z and
-// nothing else: gzs and the scalar block are never touched.  Nothing is launched for an empty batch.
-static int scratch_tables(spmf_ctx* c, const char* fn, const spmf_counts* ct, int S, const WaicCarve& k, void* scratch,
-    const float* u, const float* v, const float* w, const float* s, const float* eta, hipStream_t st, Tables& T) {
+// What every streaming call `fn` checks before anything is launched: S in min_S..65535, the shared pointers, the
+// scratch's alignment, the column types of a mixed context, the counts, and the scratch size against
+// need(c, rows, S), the call's own spmf_*_scratch_bytes.
+static int draw_check(spmf_ctx* c, const char* fn, const spmf_counts* ct, int S, int min_S,
+    const float* const params[SPMF_NVARS], const float* eta, const void* scratch, size_t scratch_bytes,
+    size_t (*need)(const spmf_ctx*, int64_t, int)) {
+  if (!c) return SPMF_E_ARG;
+  const std::string f = std::string(fn) + ": ";
+  if (S < min_S || S > 65535) return fail(c, SPMF_E_ARG, f + (min_S == 2 ? "S must be in 2..65535 (the variance "
+      "over the draws needs two)" : "S must be in 1..65535"));
+  if (!params || !eta || !scratch) return fail(c, SPMF_E_ARG, f + "null argument");
+  if (!params[2] || !params[0] || !params[1] || !params[7]) return fail(c, SPMF_E_ARG, f + "params u, v, w, s "
+      "(slots 2, 0, 1, 7) must be set, each [S, ...]");
+  if ((uintptr_t)scratch & 255) return fail(c, SPMF_E_ARG, f + "scratch must be 256-byte aligned");
+  if (likelihood_code(c) == 3 && !c->ctype) return fail(c, SPMF_E_ARG, f + "spmf_ctx_set_column_types was not "
+      "called");
+  const int rc = check_counts(c, ct);   // (the scratch is sized by the batch; encode_rows checks the rest)
+  if (rc) return rc;
+  // the encode sweep of S draws gathers z with 32-bit byte offsets per draw; the consumers' row blocks are a
+  // 31-bit grid extent, a listed cell's row an int32
+  if (ct->n_rows > ((int64_t)1 << 31) - 64) return fail(c, SPMF_E_ARG, f + "too many rows in one call");
+  const size_t total = need(c, ct->n_rows, S);
+  if (total > scratch_bytes) {
+    char b[160];
+    snprintf(b, sizeof b, "%s: scratch too small: need %zu bytes for rows=%lld S=%d, have %zu", fn, total,
+        (long long)ct->n_rows, S, scratch_bytes);
+    return fail(c, SPMF_E_WORKSPACE, b);
+  }
+  return SPMF_OK;
+}
+
+// The stage of a checked call: the tables inside its scratch (draw_carve), filled by the prep launch (S draws)
+// and the encode sweep, which writes z and nothing else: gzs and the scalar block are never touched.  `dt` is
+// what the consumer reads.  Nothing is launched for an empty batch.
+static int draw_stage(spmf_ctx* c, const char* fn, const spmf_counts* ct, int S,
+    const float* const params[SPMF_NVARS], const float* eta, void* scratch, hipStream_t st, DrawTables& dt) {
+  const DrawCarve k = draw_carve(c, ct->n_rows, S);
   char* base = (char*)scratch;
-  T = Tables{};
+  Tables T{};
   T.Ap = (float*)(base + k.Ap); T.Vp = (float*)(base + k.Vp); T.phi = (float*)(base + k.phi);
   T.dprep = (double*)(base + k.dprep); T.dacc = (double*)(base + k.dacc);
   T.z = T.gzs = (float*)(base + k.z);
-  return encode_rows(c, fn, ct, S, &T, u, v, w, s, eta, st);
+  dt = DrawTables{ct->n_rows, c->D, c->KP, S, likelihood_code(c), T.z, T.Vp, T.phi, c->ctype};
+  return encode_rows(c, fn, ct, S, &T, params[2], params[0], params[1], params[7], eta, st);
 }
 
+// ---- streaming WAIC (waic.hip) ------------------------------------------------------------
 size_t spmf_waic_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S) {
   if (!c || n_rows < 0 || S < 2) return 0;
-  return waic_carve(c, n_rows, S).total;
+  return draw_carve(c, n_rows, S).total;
 }
 
 int spmf_waic_accumulate(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS],
     const float* eta, double* sums6, double* row_out, void* scratch, size_t scratch_bytes, void* stream) {
-  if (!c) return SPMF_E_ARG;
-  if (S < 2 || S > 65535) return fail(c, SPMF_E_ARG, "waic_accumulate: S must be in 2..65535 (the variance over "
-      "the draws needs two)");
-  if (!params || !eta || !sums6 || !scratch) return fail(c, SPMF_E_ARG, "waic_accumulate: null argument");
-  const float *u = params[2], *v = params[0], *w = params[1], *s = params[7];
-  if (!u || !v || !w || !s) return fail(c, SPMF_E_ARG, "waic_accumulate: params u, v, w, s (slots 2, 0, 1, 7) "
-      "must be set, each [S, ...]");
-  if ((uintptr_t)scratch & 255) return fail(c, SPMF_E_ARG, "waic_accumulate: scratch must be 256-byte aligned");
-  const int lik = likelihood_code(c);
-  if (lik == 3 && !c->ctype) return fail(c, SPMF_E_ARG, "waic_accumulate: spmf_ctx_set_column_types was not called");
-  int rc = check_counts(c, ct);   // (the scratch is sized by the batch; encode_rows checks the rest)
+  int rc = draw_check(c, "waic_accumulate", ct, S, 2, params, eta, scratch, scratch_bytes, spmf_waic_scratch_bytes);
   if (rc) return rc;
+  if (!sums6) return fail(c, SPMF_E_ARG, "waic_accumulate: null argument");
   if ((int64_t)(c->D + 63) / 64 > 65535) return fail(c, SPMF_E_UNSUPPORTED, "waic_accumulate: D above 65535 * 64");
-  // the encode sweep of S draws gathers z with 32-bit byte offsets per draw; the dense kernel's row blocks
-  // are a 31-bit grid extent
-  if (ct->n_rows > ((int64_t)1 << 31) - 64) return fail(c, SPMF_E_ARG, "waic_accumulate: too many rows in one call");
-  const WaicCarve k = waic_carve(c, ct->n_rows, S);
-  if (k.total > scratch_bytes) {
-    char b[160];
-    snprintf(b, sizeof b, "waic_accumulate: scratch too small: need %zu bytes for rows=%lld S=%d, have %zu", k.total,
-        (long long)ct->n_rows, S, scratch_bytes);
-    return fail(c, SPMF_E_WORKSPACE, b);
-  }
   hipStream_t st = (hipStream_t)stream;
-  Tables T;
-  rc = scratch_tables(c, "waic_accumulate", ct, S, k, scratch, u, v, w, s, eta, st, T);
+  DrawTables dt;
+  rc = draw_stage(c, "waic_accumulate", ct, S, params, eta, scratch, st, dt);
   if (rc || ct->n_rows == 0) return rc;
-  WaicArgs wa{ct->n_rows, ct->nnz, c->D, c->KP, S, lik, T.z, T.Vp, T.phi, c->ctype, ct->row_ptr, ct->col_idx, ct->val,
-      sums6, row_out};
+  WaicArgs wa{dt, ct->nnz, ct->row_ptr, ct->col_idx, ct->val, sums6, row_out};
   if (!launch_waic(wa, st)) return fail(c, SPMF_E_UNSUPPORTED, "waic_accumulate: no kernel for this K / likelihood");
   HIPCHK(c, hipGetLastError());
   return SPMF_OK;
@@ -1266,18 +1283,16 @@ static int topk_slices(int64_t n_rows, int D, int cus) {
   const int64_t per = (cb + nsl - 1) / nsl;
   return (int)((cb + per - 1) / per);
 }
-// Scratch of one call: the carve of the WAIC call, the bitmap of the stored cells and the slices' results
+// Scratch of one call: the draw carve, the bitmap of the stored cells and the slices' results
 // (sized for k = kTopkMaxK: the size does not depend on the call's k or flags)
 struct TopkCarve {
-  WaicCarve w;
   size_t bits, pcols, pscores, total;
   int slices;
 };
 static TopkCarve topk_carve(const spmf_ctx* c, int64_t rows, int S) {
   TopkCarve k;
-  k.w = waic_carve(c, rows, S);
   k.slices = topk_slices(rows, c->D, device_cus(c));
-  size_t o = k.w.total;
+  size_t o = draw_carve(c, rows, S).total;
   k.bits = o;    o += al((size_t)rows * ((c->D + 31) / 32) * sizeof(uint32_t));
   const size_t part = k.slices > 1 ? (size_t)k.slices * rows * kTopkMaxK : 0;
   k.pcols = o;   o += al(part * sizeof(int32_t));
@@ -1293,38 +1308,18 @@ size_t spmf_topk_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S) {
 
 int spmf_topk_rows(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS], const float* eta,
     int k, unsigned flags, int32_t* cols_out, float* score_out, void* scratch, size_t scratch_bytes, void* stream) {
-  if (!c) return SPMF_E_ARG;
-  if (S < 1 || S > 65535) return fail(c, SPMF_E_ARG, "topk_rows: S must be in 1..65535");
+  int rc = draw_check(c, "topk_rows", ct, S, 1, params, eta, scratch, scratch_bytes, spmf_topk_scratch_bytes);
+  if (rc) return rc;
   if (k < 1 || k > kTopkMaxK) return fail(c, SPMF_E_ARG, "topk_rows: k must be in 1..64");
   if (flags & ~1u) return fail(c, SPMF_E_ARG, "topk_rows: unknown flag (bit 0: exclude stored cells)");
-  if (!params || !eta || !cols_out || !score_out || !scratch) return fail(c, SPMF_E_ARG, "topk_rows: null argument");
-  const float *u = params[2], *v = params[0], *w = params[1], *s = params[7];
-  if (!u || !v || !w || !s) return fail(c, SPMF_E_ARG, "topk_rows: params u, v, w, s (slots 2, 0, 1, 7) "
-      "must be set, each [S, ...]");
-  if ((uintptr_t)scratch & 255) return fail(c, SPMF_E_ARG, "topk_rows: scratch must be 256-byte aligned");
-  const int lik = likelihood_code(c);
-  if (lik == 3 && !c->ctype) return fail(c, SPMF_E_ARG, "topk_rows: spmf_ctx_set_column_types was not called");
-  int rc = check_counts(c, ct);   // (the scratch is sized by the batch; encode_rows checks the rest)
-  if (rc) return rc;
-  // the encode sweep of S draws gathers z with 32-bit byte offsets per draw; the select kernel's row blocks
-  // are a 31-bit grid extent
-  if (ct->n_rows > ((int64_t)1 << 31) - 64) return fail(c, SPMF_E_ARG, "topk_rows: too many rows in one call");
-  const TopkCarve tc = topk_carve(c, ct->n_rows, S);
-  if (tc.total > scratch_bytes) {
-    char b[160];
-    snprintf(b, sizeof b, "topk_rows: scratch too small: need %zu bytes for rows=%lld S=%d, have %zu", tc.total,
-        (long long)ct->n_rows, S, scratch_bytes);
-    return fail(c, SPMF_E_WORKSPACE, b);
-  }
+  if (!cols_out || !score_out) return fail(c, SPMF_E_ARG, "topk_rows: null argument");
   hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)scratch;
-  Tables T;
-  rc = scratch_tables(c, "topk_rows", ct, S, tc.w, scratch, u, v, w, s, eta, st, T);
-  if (rc || ct->n_rows == 0) return rc;
   TopkArgs ta{};
-  ta.B = ct->n_rows; ta.nnz = ct->nnz; ta.D = c->D; ta.KP = c->KP; ta.S = S; ta.lik = lik; ta.k = k;
-  ta.slices = tc.slices;
-  ta.z = T.z; ta.Vp = T.Vp; ta.phi = T.phi; ta.ctype = c->ctype;
+  rc = draw_stage(c, "topk_rows", ct, S, params, eta, scratch, st, ta.t);
+  if (rc || ct->n_rows == 0) return rc;
+  const TopkCarve tc = topk_carve(c, ct->n_rows, S);
+  char* base = (char*)scratch;
+  ta.nnz = ct->nnz; ta.k = k; ta.slices = tc.slices;
   ta.row_ptr = ct->row_ptr; ta.col = ct->col_idx;
   if (flags & 1u) {
     ta.stored = (uint32_t*)(base + tc.bits);
@@ -1338,49 +1333,30 @@ int spmf_topk_rows(spmf_ctx* c, const spmf_counts* ct, int S, const float* const
 }
 
 // ---- posterior predictive mean / lppd of a list of cells (cells.hip) --------------------------
-// Scratch of one call: the carve of the WAIC call (the S draws' tables and encoded rows).
+// Scratch of one call: the draw carve alone.
 size_t spmf_cells_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S) {
   if (!c || n_rows < 0 || S < 1) return 0;
-  return waic_carve(c, n_rows, S).total;
+  return draw_carve(c, n_rows, S).total;
 }
 
 int spmf_score_cells(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS], const float* eta,
     int64_t n_cells, const int32_t* cell_row, const int32_t* cell_col, const float* cell_val, float* mean_out,
     float* lppd_out, void* scratch, size_t scratch_bytes, void* stream) {
-  if (!c) return SPMF_E_ARG;
-  if (S < 1 || S > 65535) return fail(c, SPMF_E_ARG, "score_cells: S must be in 1..65535");
+  int rc = draw_check(c, "score_cells", ct, S, 1, params, eta, scratch, scratch_bytes, spmf_cells_scratch_bytes);
+  if (rc) return rc;
   if (n_cells < 0) return fail(c, SPMF_E_ARG, "score_cells: n_cells is negative");
-  if (!params || !eta || !scratch) return fail(c, SPMF_E_ARG, "score_cells: null argument");
   if (n_cells > 0 && (!cell_row || !cell_col || !mean_out)) return fail(c, SPMF_E_ARG, "score_cells: cell_row, "
       "cell_col and mean_out must be set for a non-empty list");
   if ((cell_val == nullptr) != (lppd_out == nullptr)) return fail(c, SPMF_E_ARG, "score_cells: cell_val and lppd_out "
       "go together (both NULL: the mean only)");
-  const float *u = params[2], *v = params[0], *w = params[1], *s = params[7];
-  if (!u || !v || !w || !s) return fail(c, SPMF_E_ARG, "score_cells: params u, v, w, s (slots 2, 0, 1, 7) "
-      "must be set, each [S, ...]");
-  if ((uintptr_t)scratch & 255) return fail(c, SPMF_E_ARG, "score_cells: scratch must be 256-byte aligned");
-  const int lik = likelihood_code(c);
-  if (lik == 3 && !c->ctype) return fail(c, SPMF_E_ARG, "score_cells: spmf_ctx_set_column_types was not called");
-  int rc = check_counts(c, ct);   // (the scratch is sized by the batch; encode_rows checks the rest)
-  if (rc) return rc;
-  // the encode sweep of S draws gathers z with 32-bit byte offsets per draw; a cell's row is an int32; the
-  // cell kernel's grid is a 31-bit extent of 256-cell workgroups
-  if (ct->n_rows > ((int64_t)1 << 31) - 64) return fail(c, SPMF_E_ARG, "score_cells: too many rows in one call");
+  // the cell kernel's grid is a 31-bit extent of 256-cell workgroups
   if (n_cells > ((int64_t)1 << 38)) return fail(c, SPMF_E_ARG, "score_cells: too many cells in one call");
-  const WaicCarve k = waic_carve(c, ct->n_rows, S);
-  if (k.total > scratch_bytes) {
-    char b[160];
-    snprintf(b, sizeof b, "score_cells: scratch too small: need %zu bytes for rows=%lld S=%d, have %zu", k.total,
-        (long long)ct->n_rows, S, scratch_bytes);
-    return fail(c, SPMF_E_WORKSPACE, b);
-  }
   if (n_cells == 0 || ct->n_rows == 0) return SPMF_OK;   // (no row: no valid cell; the Python surface lists none)
   hipStream_t st = (hipStream_t)stream;
-  Tables T;
-  rc = scratch_tables(c, "score_cells", ct, S, k, scratch, u, v, w, s, eta, st, T);
+  DrawTables dt;
+  rc = draw_stage(c, "score_cells", ct, S, params, eta, scratch, st, dt);
   if (rc) return rc;
-  CellsArgs ca{ct->n_rows, n_cells, c->D, c->KP, S, lik, T.z, T.Vp, T.phi, c->ctype, cell_row, cell_col, cell_val,
-      mean_out, lppd_out};
+  CellsArgs ca{dt, n_cells, cell_row, cell_col, cell_val, mean_out, lppd_out};
   if (!launch_cells(ca, st)) return fail(c, SPMF_E_UNSUPPORTED, "score_cells: no kernel for this K / likelihood");
   HIPCHK(c, hipGetLastError());
   return SPMF_OK;

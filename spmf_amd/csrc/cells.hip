@@ -115,14 +115,15 @@ __global__ __launch_bounds__(256) void cells_kernel(int64_t n_cells, int64_t B, 
 }
 
 bool launch_cells(const CellsArgs& a, hipStream_t st) {
-  if (a.lik < 0 || a.lik > 4 || a.n_cells < 1) return false;
+  const DrawTables& t = a.t;
+  if (t.lik < 0 || t.lik > 4 || a.n_cells < 1) return false;
   const int64_t per_block = 4 * kCellsPerWave;
   const int64_t nb = (a.n_cells + per_block - 1) / per_block;
   if (nb > 0x7fffffff) return false;
 #define SPMF_CELLS(G_)                                                                                       \
-  hipLaunchKernelGGL((cells_kernel<G_>), dim3((unsigned)nb), dim3(256), 0, st, a.n_cells, a.B, a.D, a.S, a.lik, \
-                     a.row, a.col, a.val, a.z, a.Vp, a.phi, a.ctype, a.mean, a.lppd)
-  switch (a.KP) {
+  hipLaunchKernelGGL((cells_kernel<G_>), dim3((unsigned)nb), dim3(256), 0, st, a.n_cells, t.B, t.D, t.S, t.lik, \
+                     a.row, a.col, a.val, t.z, t.Vp, t.phi, t.ctype, a.mean, a.lppd)
+  switch (t.KP) {
     case 4: SPMF_CELLS(1); break;
     case 8: SPMF_CELLS(2); break;
     case 16: SPMF_CELLS(4); break;

@@ -187,13 +187,19 @@ struct NfPatchArgs {
 };
 void launch_nonfinite_patch(int KP, const NfPatchArgs& a, hipStream_t st);
 void launch_nonfinite_lgamma(const DenseLLArgs& a, double* out, hipStream_t st);   // uses B, D, logt, ctype, CSR, rate
-// waic.hip: per-cell lppd / pwaic over S draws, summed over the cells of the batch (sums6: [0] cells counted,
-// [1] sum lppd, [2] sum pwaic, [3] sum elpd^2, [4] excluded cells; accumulated).  false: KP / lik not built.
-struct WaicArgs {
-  int64_t B, nnz;
+// What the consumer kernel of a streaming call reads: the draw stage's output for S draws over B rows (api.hip
+// draw_stage).
+struct DrawTables {
+  int64_t B;
   int D, KP, S, lik;               // lik = likelihood code 0..4 (common.h)
   const float *z, *Vp, *phi;       // [S,B,KP], [S,D,KP], [S,D]
   const uint8_t* ctype;
+};
+// waic.hip: per-cell lppd / pwaic over S draws, summed over the cells of the batch (sums6: [0] cells counted,
+// [1] sum lppd, [2] sum pwaic, [3] sum elpd^2, [4] excluded cells; accumulated).  false: KP / lik not built.
+struct WaicArgs {
+  DrawTables t;
+  int64_t nnz;
   const int32_t* row_ptr;
   const int32_t* col;
   const float* val;
@@ -207,11 +213,10 @@ bool launch_waic(const WaicArgs& a, hipStream_t st);
 constexpr int kTopkMaxK = 64;
 constexpr int kTopkMaxSlices = 16;   // column slices of one launch (the merge kernel's LDS holds their candidates)
 struct TopkArgs {
-  int64_t B, nnz;
-  int D, KP, S, lik, k;
+  DrawTables t;
+  int64_t nnz;
+  int k;
   int slices;                      // gridDim.y of the select launch, 1 .. min(kTopkMaxSlices, column blocks)
-  const float *z, *Vp, *phi;       // [S,B,KP], [S,D,KP], [S,D]
-  const uint8_t* ctype;
   const int32_t* row_ptr;
   const int32_t* col;
   uint32_t* stored;                // zeroed bitmap [B][ceil(D/32)] of the cells to exclude (filled here), or null
@@ -224,11 +229,9 @@ bool launch_topk(const TopkArgs& a, hipStream_t st);
 // cells.hip: posterior predictive mean (and, with values, lppd) of a list of cells over S draws; an index
 // outside [0,B) x [0,D) reads nothing and gets NaN.  false: KP / lik not built or too many cells (nothing launched).
 struct CellsArgs {
-  int64_t B, n_cells;
-  int D, KP, S, lik;
-  const float *z, *Vp, *phi;       // [S,B,KP], [S,D,KP], [S,D]
-  const uint8_t* ctype;
-  const int32_t* row;              // [n_cells], relative to the first row of z
+  DrawTables t;
+  int64_t n_cells;
+  const int32_t* row;              // [n_cells], relative to the first row of t.z
   const int32_t* col;              // [n_cells]
   const float* val;                // [n_cells] or null (mean only)
   float* mean;                     // [n_cells]

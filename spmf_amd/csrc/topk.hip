@@ -304,14 +304,15 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(int64_t B, int k, int ns
 
 template <int KC, int CAP>
 static bool launch_select(const TopkArgs& a, int32_t* cols, float* scores, hipStream_t st) {
-  const int CB = (a.D + 63) / 64;
+  const DrawTables& t = a.t;
+  const int CB = (t.D + 63) / 64;
   const int per = (CB + a.slices - 1) / a.slices;
-  const dim3 grid((unsigned)((a.B + 63) / 64), (unsigned)a.slices);
-  const int W = (a.D + 31) / 32;
+  const dim3 grid((unsigned)((t.B + 63) / 64), (unsigned)a.slices);
+  const int W = (t.D + 31) / 32;
 #define SPMF_TOPK(L_)                                                                                         \
-  hipLaunchKernelGGL((topk_select_kernel<KC, L_, CAP>), grid, dim3(256), 0, st, a.B, a.D, a.KP, a.S, a.k, per, W, \
-                     a.z, a.Vp, a.phi, a.ctype, a.stored, cols, scores)
-  switch (a.lik) {
+  hipLaunchKernelGGL((topk_select_kernel<KC, L_, CAP>), grid, dim3(256), 0, st, t.B, t.D, t.KP, t.S, a.k, per, W, \
+                     t.z, t.Vp, t.phi, t.ctype, a.stored, cols, scores)
+  switch (t.lik) {
     case 0: SPMF_TOPK(0); break;
     case 1: SPMF_TOPK(1); break;
     case 2: SPMF_TOPK(2); break;
@@ -329,27 +330,28 @@ static bool launch_select_kc(const TopkArgs& a, int32_t* cols, float* scores, hi
 }
 
 bool launch_topk(const TopkArgs& a, hipStream_t st) {
-  const int CB = (a.D + 63) / 64;
+  const DrawTables& t = a.t;
+  const int CB = (t.D + 63) / 64;
   if (a.k < 1 || a.k > kTopkMaxK || a.slices < 1 || a.slices > kTopkMaxSlices || a.slices > CB) return false;
-  if (a.KP != 4 && a.KP != 8 && a.KP != 16 && a.KP != 32 && a.KP != 64 && a.KP != 128 && a.KP != 256) return false;
-  if (a.lik < 0 || a.lik > 4) return false;
+  if (t.KP != 4 && t.KP != 8 && t.KP != 16 && t.KP != 32 && t.KP != 64 && t.KP != 128 && t.KP != 256) return false;
+  if (t.lik < 0 || t.lik > 4) return false;
   if (a.stored && a.nnz > 0) {
-    const int64_t want = (a.B + 3) / 4;
+    const int64_t want = (t.B + 3) / 4;
     const int nb = (int)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
-    hipLaunchKernelGGL(topk_mark_kernel, dim3(nb), dim3(256), 0, st, a.B, a.D, (a.D + 31) / 32, a.row_ptr, a.col,
+    hipLaunchKernelGGL(topk_mark_kernel, dim3(nb), dim3(256), 0, st, t.B, t.D, (t.D + 31) / 32, a.row_ptr, a.col,
                        a.stored);
   }
   int32_t* cols = a.slices > 1 ? a.part_cols : a.cols;
   float* scores = a.slices > 1 ? a.part_scores : a.scores;
   bool ok;
-  switch (a.KP) {
+  switch (t.KP) {
     case 4: case 8: ok = launch_select_kc<8>(a, cols, scores, st); break;
     case 16: ok = launch_select_kc<16>(a, cols, scores, st); break;
     default: ok = launch_select_kc<32>(a, cols, scores, st); break;
   }
   if (!ok) return false;
   if (a.slices > 1)
-    hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)a.B), dim3(64), 0, st, a.B, a.k, a.slices, a.part_cols,
+    hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)t.B), dim3(64), 0, st, t.B, a.k, a.slices, a.part_cols,
                        a.part_scores, a.cols, a.scores);
   return true;
 }

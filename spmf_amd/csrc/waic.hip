@@ -286,11 +286,12 @@ __global__ __launch_bounds__(256) void waic_fix_kernel(int64_t B, int D, int KP,
 
 template <int KC>
 static bool launch_dense_kc(const WaicArgs& a, hipStream_t st) {
-  const dim3 grid((unsigned)((a.B + 63) / 64), (unsigned)((a.D + 63) / 64));
+  const DrawTables& t = a.t;
+  const dim3 grid((unsigned)((t.B + 63) / 64), (unsigned)((t.D + 63) / 64));
 #define SPMF_WAIC(L_)                                                                                    \
-  hipLaunchKernelGGL((waic_dense_kernel<KC, L_>), grid, dim3(256), 0, st, a.B, a.D, a.KP, a.S, a.z, a.Vp, \
-                     a.phi, a.ctype, a.sums, a.row_out)
-  switch (a.lik) {
+  hipLaunchKernelGGL((waic_dense_kernel<KC, L_>), grid, dim3(256), 0, st, t.B, t.D, t.KP, t.S, t.z, t.Vp, \
+                     t.phi, t.ctype, a.sums, a.row_out)
+  switch (t.lik) {
     case 0: SPMF_WAIC(0); break;
     case 1: SPMF_WAIC(1); break;
     case 2: SPMF_WAIC(2); break;
@@ -303,8 +304,9 @@ static bool launch_dense_kc(const WaicArgs& a, hipStream_t st) {
 }
 
 bool launch_waic(const WaicArgs& a, hipStream_t st) {
+  const DrawTables& t = a.t;
   bool ok;
-  switch (a.KP) {
+  switch (t.KP) {
     case 4: case 8: ok = launch_dense_kc<8>(a, st); break;
     case 16: ok = launch_dense_kc<16>(a, st); break;
     case 32: case 64: case 128: case 256: ok = launch_dense_kc<32>(a, st); break;
@@ -312,10 +314,10 @@ bool launch_waic(const WaicArgs& a, hipStream_t st) {
   }
   if (!ok) return false;
   if (a.nnz > 0) {
-    const int64_t want = (a.B + 3) / 4;
+    const int64_t want = (t.B + 3) / 4;
     const int nb = (int)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
-    hipLaunchKernelGGL(waic_fix_kernel, dim3(nb), dim3(256), 0, st, a.B, a.D, a.KP, a.S, a.lik, a.row_ptr, a.col,
-                       a.val, a.z, a.Vp, a.phi, a.ctype, a.sums, a.row_out);
+    hipLaunchKernelGGL(waic_fix_kernel, dim3(nb), dim3(256), 0, st, t.B, t.D, t.KP, t.S, t.lik, a.row_ptr, a.col,
+                       a.val, t.z, t.Vp, t.phi, t.ctype, a.sums, a.row_out);
   }
   return true;
 }

@@ -134,11 +134,8 @@ class PoissonFactorization:
             raise NotImplementedError("custom encoder/decoder callables: row shards need a dist.ShardReducer "
                                       "as the all_reduce hook (a bare callable only sees the kernels' accumulators)")
         sc, cs = self._batch(data)
-        x = sc.to_dense()
-        pr = data.get("panels") if isinstance(data, dict) else None
-        if pr is not None:
-            r0 = pr[0] * sc.panel_rows
-            x = x[r0:r0 + cs.n_rows]
+        r0 = sc.panel_range(data.get("panels") if isinstance(data, dict) else None)[0] * sc.panel_rows
+        x = sc.to_dense()[r0:r0 + cs.n_rows]
         parts, grads, nbad = custom_codec.energy_and_grads(self, x, params, prior_weight, shard=all_reduce)
         S = nbad.shape[0]
         zero = torch.zeros(S, dtype=torch.float64, device=self.device)
@@ -338,11 +335,7 @@ class PoissonFactorization:
         shard (minibatching without re-sorting)."""
         sc = self._counts(data)
         pr = data.get("panels") if isinstance(data, dict) else None
-        key = (pr, sc._xi_key, sc._g_key)
-        cache = sc.__dict__.setdefault("_struct_cache", {})
-        if key not in cache:
-            cache[key] = sc.batch_struct(*(pr or (0, None)))
-        return sc, cache[key]
+        return sc, (sc.struct(*pr) if pr else sc.struct())
 
     def _batch_rows(self, data):
         """Rows of one batch (of its panel range), read off the counts' shape alone: what
@@ -354,9 +347,8 @@ class PoissonFactorization:
             return int(self._batch(data)[1].n_rows) if pr else int(x.shape[0])
         if not pr:
             return x.n_rows
-        n, rows_per, n_panels = x.n_rows, x.panel_rows, x.n_panels
-        p0, p1 = int(pr[0]), n_panels if pr[1] is None else min(int(pr[1]), n_panels)
-        return max(0, min(p1 * rows_per, n) - p0 * rows_per)
+        p0, p1 = x.panel_range(pr)
+        return max(0, min(p1 * x.panel_rows, x.n_rows) - p0 * x.panel_rows)
 
     def _pack_params(self, params, names=None):
         """dict name -> tensor  =>  (S, {name: contiguous fp32 [S,*shape]})."""
@@ -552,11 +544,8 @@ class PoissonFactorization:
         if self._custom_codec is not None:
             from . import custom_codec
             sc, cs = self._batch(data)
-            xd = sc.to_dense()
-            pr = data.get("panels") if isinstance(data, dict) else None
-            if pr is not None:
-                r0 = pr[0] * sc.panel_rows
-                xd = xd[r0:r0 + cs.n_rows]
+            r0 = sc.panel_range(data.get("panels") if isinstance(data, dict) else None)[0] * sc.panel_rows
+            xd = sc.to_dense()[r0:r0 + cs.n_rows]
             return custom_codec.log_likelihood_components(self, xd, s, u, v, w)
         lib, h = _lib.load(), self._handle()
         sc, cs = self._batch(data)
@@ -614,6 +603,28 @@ class PoissonFactorization:
                 "se": float(2.0 * torch.sqrt(n * elpd_i.var(unbiased=True))),
                 "lppd": float(lppd_i.sum()), "pwaic": float(pwaic_i.sum())}
 
+    def _draw_call(self, name, draws, nsamples, min_draws, dense_alternative):
+        """What the streaming calls (waic_streaming, top_k, score_cells) hand the library's draw stage:
+        ``(S, pin, eta_ptr, stream, KP, lib, h)``.  ``draws``: dict with 's','u','v','w' of shape [S,...]
+        (None: ``surrogate_distribution.sample(nsamples)``), at least ``min_draws`` of them; ``pin`` is the
+        C-ABI's twelve parameter slots and keeps the packed tensors it points into alive."""
+        if self._custom_codec is not None:
+            raise NotImplementedError(f"{name}: custom encoder/decoder callables have no kernel "
+                                      f"(use {dense_alternative}, which evaluates them densely)")
+        why = " (the variance over the draws)" if min_draws > 1 else ""
+        if draws is None:
+            if int(nsamples) < min_draws:
+                raise ValueError(f"{name} needs nsamples >= {min_draws}{why}")
+            draws = self.surrogate_distribution.sample(int(nsamples))
+        S, P = self._pack_params(draws, names=("s", "u", "v", "w"))
+        if S < min_draws:
+            raise ValueError(f"{name} needs at least {min_draws} draws{why}")
+        lib, h = _lib.load(), self._handle()
+        pin = _lib.PtrArray(*[P[n].data_ptr() if n in P else None for n in VAR_ORDER])
+        pin.tensors = P
+        return (S, pin, self._eta_device().data_ptr(), torch.cuda.current_stream(self.device).cuda_stream,
+                int(lib.spmf_padded_k(h)), lib, h)
+
     def waic_streaming(self, data, nsamples=100, draws=None, row_scores=False, max_rows=None):
         """``waic`` at any size: per-cell lppd_i / pwaic_i over the draws are formed in
         registers (csrc/waic.hip) and only their sums over the cells leave the kernel, so
@@ -630,35 +641,17 @@ class PoissonFactorization:
         with a non-finite log-pmf in any draw (NaN count, rate 0 under a positive count) is
         left out of the sums and counted in 'n_excluded', where ``waic`` returns NaN / -inf."""
         from . import waic as _waic
-        if self._custom_codec is not None:
-            raise NotImplementedError("waic_streaming: custom encoder/decoder callables have no kernel "
-                                      "(use waic(), which evaluates them densely)")
-        if draws is None:
-            if int(nsamples) < 2:
-                raise ValueError("waic_streaming needs nsamples >= 2 (the variance over the draws)")
-            draws = self.surrogate_distribution.sample(int(nsamples))
-        S, P = self._pack_params(draws, names=("s", "u", "v", "w"))
-        if S < 2:
-            raise ValueError("waic_streaming needs at least 2 draws (the variance over the draws)")
-        lib, h = _lib.load(), self._handle()
-        eta = self._eta_device()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        pin = _lib.PtrArray(*[P[n].data_ptr() if n in P else None for n in VAR_ORDER])
+        S, pin, eta, stream, KP, lib, h = self._draw_call("waic_streaming", draws, nsamples, 2, "waic()")
         sums = torch.zeros(_waic.NSUMS, dtype=torch.float64, device=self.device)
-        KP = int(lib.spmf_padded_k(h))
-        scratch, rows_out = None, []
+        scratch, rows_out = _Scratch(self.device), []
         for n_rows, chunks in self._row_chunks(data, S * KP * 4, max_rows):
             rows = torch.zeros(n_rows, 2, dtype=torch.float64, device=self.device) if row_scores else None
             for r0, sub in chunks:
-                need = int(lib.spmf_waic_scratch_bytes(h, int(sub.n_rows), S)) + 256
-                if scratch is None or scratch.numel() < need:
-                    scratch = None
-                    scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-                off = (-scratch.data_ptr()) % 256
                 _lib.check(h, lib.spmf_waic_accumulate(
-                    h, C.byref(sub), S, pin, eta.data_ptr(), sums.data_ptr(),
+                    h, C.byref(sub), S, pin, eta, sums.data_ptr(),
                     rows[r0:].data_ptr() if rows is not None else None,
-                    scratch.data_ptr() + off, scratch.numel() - off, stream), "spmf_waic_accumulate")
+                    *scratch.fit(lib.spmf_waic_scratch_bytes(h, int(sub.n_rows), S)), stream),
+                    "spmf_waic_accumulate")
             if rows is not None:
                 rows_out.append(rows)
         out = _waic.combine(sums)
@@ -668,7 +661,7 @@ class PoissonFactorization:
         return out
 
     def _row_chunks(self, data, row_bytes, max_rows):
-        """The batch and row-chunk iteration of the streaming calls (waic_streaming, top_k).
+        """The batch and row-chunk iteration of the streaming calls.
         ``data``: one batch (dict / counts), an iterable of batches or a data-factory callable; a
         ``{"counts": sc, "panels": (p0, p1)}`` batch is the rows of those panels.  Yields
         ``(n_rows, chunks)`` per batch; ``chunks`` yields ``(r0, sub)``: the batch struct of the
@@ -682,18 +675,13 @@ class PoissonFactorization:
             batches = data
         for batch in batches:
             sc, cs = self._batch(batch)
-            pr = batch.get("panels") if isinstance(batch, dict) else None
-            p0, p1 = (pr or (0, None))
-            p1 = sc.n_panels if p1 is None else min(int(p1), sc.n_panels)
+            p0, p1 = sc.panel_range(batch.get("panels") if isinstance(batch, dict) else None)
             cap = int(max_rows) if max_rows else max(1, (1 << 30) // int(row_bytes))
             step = max(1, cap // sc.panel_rows)
 
-            def chunks(sc=sc, p0=int(p0), p1=p1, step=step):
-                key = (sc._xi_key, sc._g_key)
+            def chunks(sc=sc, p0=p0, p1=p1, step=step):
                 for q0 in range(p0, p1, step):
-                    q1 = min(q0 + step, p1)
-                    sub = sc.__dict__.setdefault("_struct_cache", {}).setdefault(
-                        ((q0, q1),) + key, sc.batch_struct(q0, q1))
+                    sub = sc.struct(q0, min(q0 + step, p1))
                     if sub.n_rows == 0:
                         continue
                     yield (q0 - p0) * sc.panel_rows, sub
@@ -714,36 +702,19 @@ class PoissonFactorization:
         Returns {'columns': int32 [B,k], 'scores': float32 [B,k]} on the device, the rows of all
         batches concatenated: score descending, equal scores by ascending column, a row with
         fewer than k candidates padded with column -1 / score -inf.  Bit-reproducible."""
-        if self._custom_codec is not None:
-            raise NotImplementedError("top_k: custom encoder/decoder callables have no kernel "
-                                      "(use log_likelihood_components, which evaluates them densely)")
         k = int(k)
         if not 1 <= k <= 64:
             raise ValueError("top_k needs 1 <= k <= 64")
-        if draws is None:
-            if int(nsamples) < 1:
-                raise ValueError("top_k needs nsamples >= 1")
-            draws = self.surrogate_distribution.sample(int(nsamples))
-        S, P = self._pack_params(draws, names=("s", "u", "v", "w"))
-        lib, h = _lib.load(), self._handle()
-        eta = self._eta_device()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        pin = _lib.PtrArray(*[P[n].data_ptr() if n in P else None for n in VAR_ORDER])
-        KP = int(lib.spmf_padded_k(h))
+        S, pin, eta, stream, KP, lib, h = self._draw_call("top_k", draws, nsamples, 1, "log_likelihood_components")
         flags = 1 if exclude_stored else 0
-        scratch, cols_out, scores_out = None, [], []
+        scratch, cols_out, scores_out = _Scratch(self.device), [], []
         for n_rows, chunks in self._row_chunks(data, S * KP * 4 + (self.feature_dim + 31) // 32 * 4, max_rows):
             cols = torch.empty(n_rows, k, dtype=torch.int32, device=self.device)
             scores = torch.empty(n_rows, k, dtype=torch.float32, device=self.device)
             for r0, sub in chunks:
-                need = int(lib.spmf_topk_scratch_bytes(h, int(sub.n_rows), S)) + 256
-                if scratch is None or scratch.numel() < need:
-                    scratch = None
-                    scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-                off = (-scratch.data_ptr()) % 256
                 _lib.check(h, lib.spmf_topk_rows(
-                    h, C.byref(sub), S, pin, eta.data_ptr(), k, flags, cols[r0:].data_ptr(),
-                    scores[r0:].data_ptr(), scratch.data_ptr() + off, scratch.numel() - off, stream),
+                    h, C.byref(sub), S, pin, eta, k, flags, cols[r0:].data_ptr(), scores[r0:].data_ptr(),
+                    *scratch.fit(lib.spmf_topk_scratch_bytes(h, int(sub.n_rows), S)), stream),
                     "spmf_topk_rows")
             cols_out.append(cols)
             scores_out.append(scores)
@@ -778,9 +749,6 @@ class PoissonFactorization:
         count in the batch makes every score of its row NaN.  A cell's scores do not depend on
         the order of the list or on ``max_rows``.  Bit-reproducible."""
         from . import heldout as _heldout
-        if self._custom_codec is not None:
-            raise NotImplementedError("score_cells: custom encoder/decoder callables have no kernel "
-                                      "(use log_likelihood_components, which evaluates them densely)")
         if callable(data) or not (isinstance(data, (dict, SparseCounts)) or hasattr(data, "shape")):
             raise ValueError("score_cells takes ONE batch (a dict or counts), not an iterable or a factory")
 
@@ -816,16 +784,8 @@ class PoissonFactorization:
                 raise ValueError(f"score_cells: rows must lie in [0, {n_rows}), got {r_lo} .. {r_hi}")
             if c_lo < 0 or c_hi >= self.feature_dim:
                 raise ValueError(f"score_cells: cols must lie in [0, {self.feature_dim}), got {c_lo} .. {c_hi}")
-        if draws is None:
-            if int(nsamples) < 1:
-                raise ValueError("score_cells needs nsamples >= 1")
-            draws = self.surrogate_distribution.sample(int(nsamples))
-        S, P = self._pack_params(draws, names=("s", "u", "v", "w"))
-        lib, h = _lib.load(), self._handle()
-        eta = self._eta_device()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        pin = _lib.PtrArray(*[P[n].data_ptr() if n in P else None for n in VAR_ORDER])
-        KP = int(lib.spmf_padded_k(h))
+        S, pin, eta, stream, KP, lib, h = self._draw_call("score_cells", draws, nsamples, 1,
+                                                          "log_likelihood_components")
         (lib_rows, chunks), = self._row_chunks(data, S * KP * 4, max_rows)
         assert lib_rows == n_rows, (lib_rows, n_rows)
         # cells sorted by row (stable): a row chunk's cells are one contiguous segment
@@ -843,21 +803,16 @@ class PoissonFactorization:
         nan = float("nan")
         mean = torch.full((N,), nan, dtype=torch.float32, device=self.device)
         lppd = torch.full((N,), nan, dtype=torch.float32, device=self.device) if vals is not None else None
-        scratch = None
+        scratch = _Scratch(self.device)
         for (r0, sub), (lo, hi) in zip(chunks, edges):
             if hi == lo:
                 continue
-            need = int(lib.spmf_cells_scratch_bytes(h, int(sub.n_rows), S)) + 256
-            if scratch is None or scratch.numel() < need:
-                scratch = None
-                scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-            off = (-scratch.data_ptr()) % 256
             rel = rows[lo:hi] - r0 if r0 else rows[lo:hi]
             _lib.check(h, lib.spmf_score_cells(
-                h, C.byref(sub), S, pin, eta.data_ptr(), hi - lo, rel.data_ptr(), cols[lo:hi].data_ptr(),
+                h, C.byref(sub), S, pin, eta, hi - lo, rel.data_ptr(), cols[lo:hi].data_ptr(),
                 vals[lo:hi].data_ptr() if vals is not None else None, mean[lo:hi].data_ptr(),
                 lppd[lo:hi].data_ptr() if lppd is not None else None,
-                scratch.data_ptr() + off, scratch.numel() - off, stream), "spmf_score_cells")
+                *scratch.fit(lib.spmf_cells_scratch_bytes(h, int(sub.n_rows), S)), stream), "spmf_score_cells")
         del rows, cols, vals, scratch
         out = {"mean": torch.empty_like(mean).index_copy_(0, order, mean)}
         del mean
@@ -880,9 +835,7 @@ class PoissonFactorization:
         eta = self._eta_device()
         stream = torch.cuda.current_stream(self.device).cuda_stream
         D = self.feature_dim
-        pr = data.get("panels") if isinstance(data, dict) else None
-        p0, p1 = (pr or (0, None))
-        p1 = sc.n_panels if p1 is None else min(int(p1), sc.n_panels)
+        p0, p1 = sc.panel_range(data.get("panels") if isinstance(data, dict) else None)
         step = max(1, max_cells // max(1, sc.panel_rows * D))
         h = self._aux(min(cs.n_rows, step * sc.panel_rows))
         io = torch.zeros(4, dtype=torch.float64, device=self.device)
@@ -891,19 +844,16 @@ class PoissonFactorization:
         buf_rows = min(cs.n_rows, step * sc.panel_rows)
         rate = torch.empty(buf_rows * D, dtype=torch.float32, device=self.device)
         ll = torch.empty(buf_rows * D, dtype=torch.float32, device=self.device)
-        key = (sc._xi_key, sc._g_key)
 
         def sweep(fn):
             for i in range(S):
-                for q0 in range(int(p0), p1, step):
-                    q1 = min(q0 + step, p1)
-                    sub = sc.__dict__.setdefault("_struct_cache", {}).setdefault(
-                        ((q0, q1),) + key, sc.batch_struct(q0, q1))
+                for q0 in range(p0, p1, step):
+                    sub = sc.struct(q0, min(q0 + step, p1))
                     _lib.check(h, lib.spmf_dense_ll(
                         h, C.byref(sub), P["u"][i].data_ptr(), P["v"][i].data_ptr(),
                         P["w"][i].data_ptr(), P["s"][i].data_ptr(), eta.data_ptr(),
                         rate.data_ptr(), ll.data_ptr(), stream), "spmf_dense_ll")
-                    r0 = (q0 - int(p0)) * sc.panel_rows
+                    r0 = (q0 - p0) * sc.panel_rows
                     fn(sub, i, sub.n_rows * D, float(i) * cs.n_rows * D + float(r0) * D)
 
         def first(sub, i, n, base):
@@ -1085,6 +1035,22 @@ def _wrap_f32(ptr, n, device, owner):
     off = ptr - base
     assert off >= 0 and off % 4 == 0
     return owner[off:off + 4 * n].view(torch.float32)
+
+
+class _Scratch:
+    """The grow-only device scratch of one streaming call."""
+
+    def __init__(self, device):
+        self.device, self.buf = device, None
+
+    def fit(self, need_bytes):
+        """-> (256-byte aligned pointer, usable bytes >= need_bytes).  An outgrown buffer is dropped
+        before the larger one is allocated."""
+        if self.buf is None or self.buf.numel() < need_bytes + 256:
+            self.buf = None
+            self.buf = torch.empty(need_bytes + 256, dtype=torch.uint8, device=self.device)
+        off = (-self.buf.data_ptr()) % 256
+        return self.buf.data_ptr() + off, self.buf.numel() - off
 
 
 class PoissonMatrixFactorization(PoissonFactorization):

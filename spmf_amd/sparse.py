@@ -135,6 +135,7 @@ class SparseCounts:
         self.gval = None           # g(x) = log(x/eta+1) per entry (log_transform only)
         self.pc_gval = None
         self._g_key = None
+        self._struct_cache = {}    # ((p0, p1), _xi_key, _g_key) -> descriptor (struct)
         self._keep = []
 
     # ---- construction ----------------------------------------------------
@@ -389,10 +390,8 @@ class SparseCounts:
     _MAX_G_KEYS = 2          # gval + pc_gval are nnz sized
 
     def _drop_structs(self, pos, key):
-        cache = self.__dict__.get("_struct_cache")
-        if cache:
-            for k in [k for k in cache if k[pos] == key]:
-                del cache[k]
+        for k in [k for k in self._struct_cache if k[pos] == key]:
+            del self._struct_cache[k]
 
     def set_row_scale(self, xi_u_global, scale_rows):
         """xi_b = rowsum_b / xi_u_global (poisson.py:644-649)."""
@@ -484,6 +483,20 @@ class SparseCounts:
             hp["lg"] = lg.view(nP, P).sum(1).cpu().numpy() if self.n_rows else np.zeros(nP)
             hp["lg_of"] = self.row_lgamma
         return hp
+
+    def panel_range(self, pr):
+        """A batch's ``'panels'`` entry (None: every panel) as ``(p0, p1)``, p1 clipped to the panels there are."""
+        p0, p1 = pr or (0, None)
+        return int(p0), self.n_panels if p1 is None else min(int(p1), self.n_panels)
+
+    def struct(self, p0=0, p1=None):
+        """``batch_struct(p0, p1)`` under the current row scale and g(x), built once per key and
+        kept until that row scale or g(x) is evicted (``_drop_structs``)."""
+        key = ((p0, p1), self._xi_key, self._g_key)
+        cs = self._struct_cache.get(key)
+        if cs is None:
+            cs = self._struct_cache[key] = self.batch_struct(p0, p1)
+        return cs
 
     def batch_struct(self, p0=0, p1=None):
         """spmf_counts descriptor of panels [p0, p1)."""

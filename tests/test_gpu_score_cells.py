@@ -14,7 +14,7 @@ The second carries the bar on each ll_s over because log-mean-exp is 1-Lipschitz
 _check asserts on the oracle alone what the case expects to be finite before the GPU result is
 looked at, and prints the largest observed error of each output before asserting.
 
-Bernoulli damping as in test_gpu_topk (its _problem is shared: same seeds, same cached inputs)."""
+Bernoulli damping as in test_gpu_topk (_stream_cases._problem is shared: same seeds, same cached inputs)."""
 import ctypes as C
 import functools
 import math
@@ -24,9 +24,9 @@ import pytest
 import torch
 
 from oracle import spmf_oracle as O
+from _stream_cases import _bern_cols, _problem
 from test_gpu_dense import LIKELIHOODS, _dense_model, _dense_problem
 from test_gpu_parity import build_model, make_problem
-from test_gpu_topk import _bern_cols, _problem
 
 pytestmark = pytest.mark.gpu
 T = torch.as_tensor

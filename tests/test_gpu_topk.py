@@ -15,8 +15,8 @@ test_gpu_dense._assert_cells.  One helper (_check) holds a result against the or
 The share of clear-cut rows is asserted on the oracle alone before the GPU result is looked at.
 
 Bernoulli damping: with the parameters of _dense_problem the Bernoulli probabilities saturate
-and tie, so u and w of the two Bernoulli cases are scaled by BERN_DAMP (a power of two: the
-values stay fp32-exact).  Clear-cut rows on the CPU oracle with seed 9100+B+K at the three
+and tie, so u and w of the two Bernoulli cases are scaled by _stream_cases.BERN_DAMP (a power of
+two: the values stay fp32-exact).  Clear-cut rows on the CPU oracle with seed 9100+B+K at the three
 shapes of SHAPES: CLEAR_ROWS below (asserted on the oracle in the test)."""
 import ctypes as C
 import functools
@@ -26,7 +26,8 @@ import pytest
 import torch
 
 from oracle import spmf_oracle as O
-from test_gpu_dense import LIKELIHOODS, _dense_model, _dense_problem
+from _stream_cases import _bern_cols, _oracle_scores, _problem
+from test_gpu_dense import LIKELIHOODS, _dense_model
 from test_gpu_parity import build_model, make_problem
 
 pytestmark = pytest.mark.gpu
@@ -38,7 +39,6 @@ T = torch.as_tensor
 # block): 1, 4 and, for the 5-row batch, 6.  The rule is a static function of the library, not reachable
 # from Python.
 SHAPES = [(70, 45, 3, 2, 5), (131, 197, 16, 7, 10), (5, 333, 33, 3, 64)]
-BERN_DAMP = {"bernoulli": 1.0 / 64.0, "bernoulli_log": 1.0 / 8.0}
 # Clear-cut rows of the CPU oracle at SHAPES (seed 9100+B+K): the counts recorded for poisson, mixed and
 # poisson_log when the cases were set, and for the two Bernoulli cases when their damping was chosen.  A case
 # asserts, on the oracle alone, that its shape has at least its recorded count and that the likelihood's share
@@ -47,34 +47,6 @@ BERN_DAMP = {"bernoulli": 1.0 / 64.0, "bernoulli_log": 1.0 / 8.0}
 CLEAR_ROWS = {"poisson": (70, 131, 5), "mixed": (70, 131, 5), "poisson_log": (62, 126, 4),
               "bernoulli": (65, 130, 5), "bernoulli_log": (70, 129, 5)}
 MIN_CLEAR = {"poisson": 1.0, "mixed": 1.0, "poisson_log": 0.85, "bernoulli": 0.90, "bernoulli_log": 0.90}
-
-
-def _bern_cols(lik, mask, D):
-    if lik.startswith("bernoulli"):
-        return np.ones(D, dtype=bool)
-    return np.asarray(mask, dtype=bool) if mask is not None else np.zeros(D, dtype=bool)
-
-
-def _oracle_scores(cfg, x, params, bern):
-    """fp64 [B,D]: mean over the draws of the rate (Poisson column) / sigmoid(logit) (Bernoulli)."""
-    rate = O.log_likelihood_components(cfg, T(x), T(params["s"]), T(params["u"]), T(params["v"]),
-                                       T(params["w"]))["rate"]
-    if rate.dim() == 2:
-        rate = rate.unsqueeze(0)
-    m = torch.where(T(bern), torch.sigmoid(rate), rate)
-    return m.mean(0).numpy()
-
-
-@functools.lru_cache(maxsize=None)
-def _problem(lik, B, D, K, S, seed=None, density=0.3):
-    """The problem of a case and its oracle scores, computed once and shared (read-only)."""
-    cfg, x, params, mask = _dense_problem(lik, B, D, K, S, 9100 + B + K if seed is None else seed,
-                                          density=density)
-    if lik in BERN_DAMP:
-        params["u"] = params["u"] * BERN_DAMP[lik]
-        params["w"] = params["w"] * BERN_DAMP[lik]
-    score = _oracle_scores(cfg, x, params, _bern_cols(lik, mask, D))
-    return cfg, x, params, mask, score
 
 
 def _bar(v, smax):

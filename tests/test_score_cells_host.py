@@ -1,45 +1,10 @@
-"""CPU-side tests of score_cells: the two entry points in the header, the export list and the
-binding, the method on the class surface, the argument checks that need no device and the
-summary of spmf_amd.heldout."""
-import fnmatch
+"""CPU-side tests of score_cells: the argument checks that need no device and the summary of
+spmf_amd.heldout.  (The entry points and the method on the class surface: test_stream_host.py.)"""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ("spmf_cells_scratch_bytes", "spmf_score_cells")
-
-
-def _header_args(hdr, name):
-    """Number of arguments of the declaration of `name` in the header."""
-    m = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", hdr, re.S)
-    assert m, f"{name} is not declared in include/spmf_hip.h"
-    return len([a for a in m.group(1).split(",") if a.strip()])
-
-
-def test_entry_points_are_declared_exported_and_bound():
-    from spmf_amd import _lib
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "spmf_hip.h")).read(), flags=re.S)
-    exports = open(os.path.join(ROOT, "spmf_amd", "csrc", "exports.map")).read()
-    exports = re.sub(r"/\*.*?\*/", "", exports, flags=re.S)
-    globs = re.search(r"global:\s*([^}]*?)local:", exports, re.S).group(1)
-    patterns = [p.strip() for p in globs.split(";") if p.strip()]
-    for name in NAMES:
-        assert any(fnmatch.fnmatchcase(name, p) for p in patterns), (name, patterns)
-        assert name in _lib.SIGNATURES, name
-        assert len(_lib.SIGNATURES[name][1]) == _header_args(hdr, name), name
-    assert _header_args(hdr, "spmf_cells_scratch_bytes") == 3 and _header_args(hdr, "spmf_score_cells") == 14
-    assert "define SPMF_ABI_VERSION 6" in hdr and _lib.ABI_VERSION == 6
-
-
-def test_score_cells_is_on_all_three_classes():
-    from spmf_amd import BernoulliFactorization, MixedFactorization, PoissonFactorization
-    for cls in (PoissonFactorization, BernoulliFactorization, MixedFactorization):
-        assert callable(getattr(cls, "score_cells", None)), cls.__name__
 
 
 def _cpu_model():

@@ -1,12 +1,8 @@
-"""CPU-side tests of the streaming WAIC: the combination of the six sums, the two
-entry points in the header and the binding, the method on the class surface."""
+"""CPU-side tests of the streaming WAIC: the combination of the six sums.  (The entry points and the
+method on the class surface: test_stream_host.py.)"""
 import math
-import os
-import re
 
 import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _sums(lppd, pwaic, n_excluded=0):
@@ -40,18 +36,3 @@ def test_sums_of_two_parts_combine_to_the_whole():
     assert merged["n"] == whole["n"] == 1500 and merged["n_excluded"] == 2
     for k in ("waic", "se", "lppd", "pwaic"):
         assert math.isclose(merged[k], whole[k], rel_tol=1e-11), k
-
-
-def test_entry_points_are_declared_and_bound():
-    from spmf_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "spmf_hip.h")).read()
-    declared = set(re.findall(r"\b(spmf_[a-z0-9_]+)\s*\(", hdr))
-    for name in ("spmf_waic_scratch_bytes", "spmf_waic_accumulate"):
-        assert name in declared and name in _lib.SIGNATURES, name
-    assert "define SPMF_ABI_VERSION 6" in hdr
-
-
-def test_waic_streaming_is_on_all_three_classes():
-    from spmf_amd import BernoulliFactorization, MixedFactorization, PoissonFactorization
-    for cls in (PoissonFactorization, BernoulliFactorization, MixedFactorization):
-        assert callable(getattr(cls, "waic_streaming", None)), cls.__name__
