@@ -592,6 +592,41 @@ int spmf_score_cells(spmf_ctx* ctx, const spmf_counts* counts, int S,
                      float* mean_out, float* lppd_out, void* scratch, size_t scratch_bytes,
                      void* stream);
 
+/* ---- rank of listed cells (added within ABI 6: two new entry points, no struct changed) ----
+ * Where held-out cells land in the ranking of spmf_topk_rows: for n_cells cells (cell_row[i],
+ * cell_col[i]) of the batch `counts`, over S >= 1 draws, without a [B,D] array (csrc/rank.hip).
+ * Score, order and candidates are those of spmf_topk_rows: the fp32 mean over the draws of the rate
+ * (Poisson column) or sigmoid(logit) (Bernoulli column); score descending, equal scores by ascending
+ * column; a candidate of a row is a column with a finite score that, with bit 0 of `flags` (exclude
+ * stored cells), `counts` does not store.  For cell i = (b, d), a candidate itself or not:
+ *   score_out[i] = score_bd, bit for bit what spmf_topk_rows reports for that cell;
+ *   cand_out[i]  = the number of candidates d' != d of row b;
+ *   rank_out[i]  = the number of them that precede (b, d) in the order (0 = best), -1 when the
+ *                  score is not finite (a NaN count makes its whole row NaN: 0 candidates there).
+ * So for a cell that is not stored and has a finite score: rank_out[i] < k <=> entry rank_out[i]
+ * of the row's spmf_topk_rows result is column d.  cell_row is relative to the first row of
+ * `counts` and must be non-decreasing (the kernel finds a row block's cells by binary search; an
+ * unsorted list gives wrong ranks but no access outside the list); cells may repeat.  An index
+ * outside [0, n_rows) x [0, D) reads nothing: rank -1, 0 candidates, score NaN.  A row may list any
+ * number of cells; the kernel serves 32 per row and round, so a row with n listed cells costs its block
+ * of 64 rows ceil(n/32) double sweeps of the columns (about two spmf_topk_rows sweeps up to 32 per row).  All counts are integers added by
+ * integer atomics: a cell's outputs do not depend on the list's other cells, on duplicates, on how
+ * the rows are cut into calls or on the column slices of the launch; two calls return the same bits.
+ * params: only u, v, w, s (slots 2, 0, 1, 7) are read, each with the leading axis S.
+ * scratch: 256-byte aligned, at least spmf_rank_scratch_bytes(ctx, counts->n_rows, S) bytes (the
+ * scratch of the WAIC call and the bitmap of the stored cells, n_rows * ceil(D/32) words);
+ * SPMF_E_WORKSPACE when short.  SPMF_E_ARG for S outside 1..65535, a negative n_cells, NULL params /
+ * eta / scratch, a NULL list or output with n_cells > 0, unknown flag bits, a misaligned scratch, a
+ * mixed context without column types or a struct_size mismatch; every error returns before any
+ * launch.  n_cells == 0 or n_rows == 0 returns SPMF_OK without work.  The context's workspace is not
+ * touched.  Stream-ordered, synchronises nowhere.  K as for spmf_waic_accumulate. */
+size_t spmf_rank_scratch_bytes(const spmf_ctx* ctx, int64_t n_rows, int S);
+int spmf_rank_cells(spmf_ctx* ctx, const spmf_counts* counts, int S,
+                    const float* const params[SPMF_NVARS], const float* eta, int64_t n_cells,
+                    const int32_t* cell_row, const int32_t* cell_col, unsigned flags,
+                    int32_t* rank_out, int32_t* cand_out, float* score_out, void* scratch,
+                    size_t scratch_bytes, void* stream);
+
 /* Reductions of the non-finite rule (poisson.py:606-616) over a dense ll
  * buffer of n cells; io = double[3] on the device.
  *   pass 0: io[0] = min(io[0], min over finite cells)  (initialise io[0]=0:

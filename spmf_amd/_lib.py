@@ -148,6 +148,10 @@ SIGNATURES = {
     "spmf_score_cells": (C.c_int, [C.c_void_p, C.POINTER(CountsStruct), C.c_int, PtrArray, C.c_void_p,
                                    C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spmf_rank_scratch_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int]),
+    "spmf_rank_cells": (C.c_int, [C.c_void_p, C.POINTER(CountsStruct), C.c_int, PtrArray, C.c_void_p,
+                                  C.c_int64, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "spmf_nonfinite_reduce": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
                                         C.c_void_p, C.c_void_p]),
     "spmf_comm_unique_id": (C.c_int, [C.c_void_p]),

@@ -1170,8 +1170,8 @@ int spmf_dense_ll(spmf_ctx* c, const spmf_counts* ct, const float* u, const floa
 }
 
 // ---- the draw stage of the streaming calls ---------------------------------------------------
-// spmf_waic_accumulate, spmf_topk_rows and spmf_score_cells are one stage and a consumer each.  The stage: for
-// S draws the per-draw tables (prep) and the encoded rows z[S,B,KP] go into the caller's scratch; the consumer
+// spmf_waic_accumulate, spmf_topk_rows, spmf_score_cells and spmf_rank_cells are one stage and a consumer each.
+// The stage: for S draws the per-draw tables (prep) and the encoded rows z[S,B,KP] go into the caller's scratch; the consumer
 // kernel then reads z, V' and phi of every draw (kernels.h DrawTables).  The context's workspace is not used, so
 // a step that is bound (or half way: spmf_step_begin .. spmf_step_end) keeps everything it has.
 // Scratch of a call = the draw carve + the consumer's own buffers behind it.
@@ -1358,6 +1358,52 @@ int spmf_score_cells(spmf_ctx* c, const spmf_counts* ct, int S, const float* con
   if (rc) return rc;
   CellsArgs ca{dt, n_cells, cell_row, cell_col, cell_val, mean_out, lppd_out};
   if (!launch_cells(ca, st)) return fail(c, SPMF_E_UNSUPPORTED, "score_cells: no kernel for this K / likelihood");
+  HIPCHK(c, hipGetLastError());
+  return SPMF_OK;
+}
+
+// ---- rank of listed cells among their row's candidates (rank.hip) ------------------------------
+// Scratch of one call: the draw carve and the bitmap of the stored cells (the size does not depend on the flags);
+// the kernel keeps everything else in LDS and in the caller's outputs.
+struct RankCarve {
+  size_t bits, total;
+};
+static RankCarve rank_carve(const spmf_ctx* c, int64_t rows, int S) {
+  RankCarve k;
+  size_t o = draw_carve(c, rows, S).total;
+  k.bits = o;  o += al((size_t)rows * ((c->D + 31) / 32) * sizeof(uint32_t));
+  k.total = o;
+  return k;
+}
+
+size_t spmf_rank_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S) {
+  if (!c || n_rows < 0 || S < 1) return 0;
+  return rank_carve(c, n_rows, S).total;
+}
+
+int spmf_rank_cells(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS], const float* eta,
+    int64_t n_cells, const int32_t* cell_row, const int32_t* cell_col, unsigned flags, int32_t* rank_out,
+    int32_t* cand_out, float* score_out, void* scratch, size_t scratch_bytes, void* stream) {
+  int rc = draw_check(c, "rank_cells", ct, S, 1, params, eta, scratch, scratch_bytes, spmf_rank_scratch_bytes);
+  if (rc) return rc;
+  if (n_cells < 0) return fail(c, SPMF_E_ARG, "rank_cells: n_cells is negative");
+  if (n_cells > 0 && (!cell_row || !cell_col || !rank_out || !cand_out || !score_out)) return fail(c, SPMF_E_ARG,
+      "rank_cells: cell_row, cell_col, rank_out, cand_out and score_out must be set for a non-empty list");
+  if (flags & ~1u) return fail(c, SPMF_E_ARG, "rank_cells: unknown flag (bit 0: exclude stored cells)");
+  if (n_cells == 0 || ct->n_rows == 0) return SPMF_OK;   // (no row: no valid cell; the Python surface lists none)
+  hipStream_t st = (hipStream_t)stream;
+  RankArgs ra{};
+  rc = draw_stage(c, "rank_cells", ct, S, params, eta, scratch, st, ra.t);
+  if (rc) return rc;
+  ra.nnz = ct->nnz; ra.slices = topk_slices(ct->n_rows, c->D, device_cus(c));
+  ra.row_ptr = ct->row_ptr; ra.col = ct->col_idx;
+  if (flags & 1u) {
+    ra.stored = (uint32_t*)((char*)scratch + rank_carve(c, ct->n_rows, S).bits);
+    HIPCHK(c, hipMemsetAsync(ra.stored, 0, (size_t)ct->n_rows * ((c->D + 31) / 32) * sizeof(uint32_t), st));
+  }
+  ra.n_cells = n_cells; ra.cell_row = cell_row; ra.cell_col = cell_col;
+  ra.rank = rank_out; ra.cand = cand_out; ra.score = score_out;
+  if (!launch_rank(ra, st)) return fail(c, SPMF_E_UNSUPPORTED, "rank_cells: no kernel for this K / likelihood");
   HIPCHK(c, hipGetLastError());
   return SPMF_OK;
 }

@@ -226,6 +226,29 @@ struct TopkArgs {
   float* scores;                   // [B][k]
 };
 bool launch_topk(const TopkArgs& a, hipStream_t st);
+// topk.hip: ORs a bit per CSR entry of the B rows into the zeroed bitmap bits[B][ceil(D/32)] (launch_topk runs it
+// itself; rank.hip reads the same bitmap)
+void launch_topk_mark(int64_t B, int D, const int32_t* row_ptr, const int32_t* col, uint32_t* bits, hipStream_t st);
+// rank.hip: for a list of cells sorted by row, the rank of each among its row's candidates under the order of
+// launch_topk (score descending, equal scores by ascending column), the number of candidates beside it, and its
+// score with the bits of launch_topk.  rank / cand / score are initialised here; a cell outside [0,B) x [0,D)
+// gets rank -1, 0 candidates, score NaN.  false: KP / lik / slices not built, or no cells or rows (nothing launched).
+constexpr int kRankMaxPerRow = 32;   // listed cells of one row that one round of the kernel takes (T)
+struct RankArgs {
+  DrawTables t;
+  int64_t nnz;
+  int slices;                      // gridDim.y, as TopkArgs.slices
+  const int32_t* row_ptr;
+  const int32_t* col;
+  uint32_t* stored;                // as TopkArgs.stored
+  int64_t n_cells;
+  const int32_t* cell_row;         // [n_cells] non-decreasing, relative to the first row of t.z
+  const int32_t* cell_col;         // [n_cells]
+  int32_t* rank;                   // [n_cells]
+  int32_t* cand;                   // [n_cells]
+  float* score;                    // [n_cells]
+};
+bool launch_rank(const RankArgs& a, hipStream_t st);
 // cells.hip: posterior predictive mean (and, with values, lppd) of a list of cells over S draws; an index
 // outside [0,B) x [0,D) reads nothing and gets NaN.  false: KP / lik not built or too many cells (nothing launched).
 struct CellsArgs {

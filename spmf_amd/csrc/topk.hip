@@ -12,9 +12,9 @@
 //     bitmap [B][ceil(D/32)]: CSR columns are not sorted inside a row, so a block of cells cannot find
 //     its stored entries by search.
 //   topk_select_kernel : a workgroup owns 64 rows and sweeps 64-column blocks.  Per block the scores are
-//     formed like the statistics of waic_dense_kernel: 32 x 32 wave tiles of <z, V'> on the exact-f32
-//     matrix cores (v_mfma_f32_32x32x2_f32), double-buffered LDS operand tiles over (draw, K chunk), m_s
-//     added in draw order to 16 accumulators per lane.  Selection: LDS holds per row the k-th best
+//     formed like the statistics of waic_dense_kernel (score_block.h, shared with rank.hip): 32 x 32 wave
+//     tiles of <z, V'> on the exact-f32 matrix cores (v_mfma_f32_32x32x2_f32), double-buffered LDS operand
+//     tiles over (draw, K chunk), m_s added in draw order to 16 accumulators per lane.  Selection: LDS holds per row the k-th best
 //     candidate so far (score, column) and a buffer of CAP candidates.  A cell that beats its row's
 //     threshold -- and only such a cell looks up its bit -- is appended through an LDS counter; a row
 //     whose buffer is full is compacted to its best k by rank (every lane counts the entries that
@@ -34,15 +34,13 @@
 // All arithmetic is fp32 FMA.
 #include "common.h"
 #include "kernels.h"
+#include "score_block.h"
 
 namespace spmf {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// the order of the result: score descending, ties by ascending column
-__device__ __forceinline__ bool precedes(float s, int c, float s2, int c2) { return s > s2 || (s == s2 && c < c2); }
+__device__ __forceinline__ bool precedes(float s, int c, float s2, int c2) { return score_precedes(s, c, s2, c2); }
 
 // One wave sorts the first n (<= CAP) candidates of a row by rank, keeps min(n, k) and, with k of them,
 // sets the row's threshold to the k-th.  Every lane reads all entries before any lane writes one.
@@ -105,8 +103,6 @@ __global__ __launch_bounds__(256) void topk_select_kernel(int64_t B, int D, int 
                                                           const uint32_t* __restrict__ stored,
                                                           int32_t* __restrict__ cols, float* __restrict__ scores) {
   constexpr int PITCH = KC + 4;
-  constexpr int NLD = KC / 8;          // float4 per thread and (draw, chunk): 2 tiles x 64 rows x KC floats
-  constexpr int TQ = 16 * KC;          // float4 per tile
   __shared__ float tiles[2][2][64][PITCH];
   __shared__ float cand_s[64][CAP];
   __shared__ int cand_c[64][CAP];
@@ -118,8 +114,6 @@ __global__ __launch_bounds__(256) void topk_select_kernel(int64_t B, int D, int 
   const int i32 = lane & 31, h = lane >> 5;
   const int wr = wv >> 1, wc = wv & 1;
   const int64_t b0 = (int64_t)blockIdx.x * 64;
-  const int NCH = KP > KC ? KP / KC : 1;
-  const int NIT = S * NCH;
   const int CB = (D + 63) / 64;
   const int cb0 = blockIdx.y * cb_per_slice;
   const int cb1 = cb0 + cb_per_slice < CB ? cb0 + cb_per_slice : CB;
@@ -134,75 +128,8 @@ __global__ __launch_bounds__(256) void topk_select_kernel(int64_t B, int D, int 
   for (int cb = cb0; cb < cb1; ++cb) {
     const int d0 = cb * 64;
     const int d = d0 + wc * 32 + i32;
-    const bool bern = lik_bern(LIK) || (LIK == 3 && d < D && cell_is_bern(LIK, ctype, d));   // (no type behind D)
-
-    auto fetch = [&](int it, float4* pre) {
-      const int s = it / NCH, kc0 = (it % NCH) * KC;
-#pragma unroll
-      for (int j = 0; j < NLD; ++j) {
-        const int idx = t + 256 * j;
-        const int tile = idx / TQ, rem = idx % TQ;
-        const int row = rem / (KC / 4), kk = kc0 + 4 * (rem % (KC / 4));
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (kk < KP) {
-          if (tile == 0) {
-            if (b0 + row < B) v = *reinterpret_cast<const float4*>(z + ((size_t)s * B + b0 + row) * KP + kk);
-          } else {
-            if (d0 + row < D) v = *reinterpret_cast<const float4*>(Vp + ((size_t)s * D + d0 + row) * KP + kk);
-          }
-        }
-        pre[j] = v;
-      }
-    };
-    auto stash = [&](int buf, const float4* pre) {
-#pragma unroll
-      for (int j = 0; j < NLD; ++j) {
-        const int idx = t + 256 * j;
-        const int tile = idx / TQ, rem = idx % TQ;
-        *reinterpret_cast<float4*>(&tiles[buf][tile][rem / (KC / 4)][4 * (rem % (KC / 4))]) = pre[j];
-      }
-    };
-
     float sc[16];
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      sc[r] = 0.f;
-      acc[r] = 0.f;
-    }
-    float4 pre[NLD];
-    fetch(0, pre);
-    stash(0, pre);   // (the last barrier of the block before released both buffers)
-    __syncthreads();
-    float ph = 0.f;
-    for (int it = 0; it < NIT; ++it) {
-      const int buf = it & 1;
-      const int s = it / NCH, ch = it % NCH;
-      if (it + 1 < NIT) fetch(it + 1, pre);
-      if (ch == 0) ph = d < D ? phi[(size_t)s * D + d] : 0.f;
-      // lane half h takes k = 8 q + 4 h + e of the chunk for both operands (waic.hip)
-      const float* ar = &tiles[buf][0][wr * 32 + i32][4 * h];
-      const float* br = &tiles[buf][1][wc * 32 + i32][4 * h];
-#pragma unroll
-      for (int qk = 0; qk < KC / 8; ++qk) {
-        const float4 a = *reinterpret_cast<const float4*>(ar + 8 * qk);
-        const float4 b = *reinterpret_cast<const float4*>(br + 8 * qk);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
-      }
-      if (ch == NCH - 1) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          float ey;
-          sc[r] += cell_mean(bern, cell_rate(LIK, acc[r], ph, ey));
-          acc[r] = 0.f;
-        }
-      }
-      if (it + 1 < NIT) stash(buf ^ 1, pre);
-      __syncthreads();
-    }
+    score_block<KC, LIK>(tiles, B, D, KP, S, b0, d0, z, Vp, phi, ctype, inv_s, sc);
 
     // ---- selection: the lane's 16 cells are column d of 16 different rows
     unsigned pend = 0;
@@ -210,8 +137,7 @@ __global__ __launch_bounds__(256) void topk_select_kernel(int64_t B, int D, int 
     for (int r = 0; r < 16; ++r) {
       const int rl = wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
       const int64_t b = b0 + rl;
-      const float v = sc[r] * inv_s;
-      sc[r] = v;
+      const float v = sc[r];
       bool in = b < B && d < D && isfinite(v) && precedes(v, d, thr_s[rl], thr_c[rl]);
       if (in && stored) in = !((stored[(size_t)b * W + (d >> 5)] >> (d & 31)) & 1u);
       pend |= in ? 1u << r : 0u;
@@ -329,18 +255,19 @@ static bool launch_select_kc(const TopkArgs& a, int32_t* cols, float* scores, hi
   return a.k <= 16 ? launch_select<KC, 32>(a, cols, scores, st) : launch_select<KC, 80>(a, cols, scores, st);
 }
 
+void launch_topk_mark(int64_t B, int D, const int32_t* row_ptr, const int32_t* col, uint32_t* bits, hipStream_t st) {
+  const int64_t want = (B + 3) / 4;
+  const int nb = (int)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
+  hipLaunchKernelGGL(topk_mark_kernel, dim3(nb), dim3(256), 0, st, B, D, (D + 31) / 32, row_ptr, col, bits);
+}
+
 bool launch_topk(const TopkArgs& a, hipStream_t st) {
   const DrawTables& t = a.t;
   const int CB = (t.D + 63) / 64;
   if (a.k < 1 || a.k > kTopkMaxK || a.slices < 1 || a.slices > kTopkMaxSlices || a.slices > CB) return false;
   if (t.KP != 4 && t.KP != 8 && t.KP != 16 && t.KP != 32 && t.KP != 64 && t.KP != 128 && t.KP != 256) return false;
   if (t.lik < 0 || t.lik > 4) return false;
-  if (a.stored && a.nnz > 0) {
-    const int64_t want = (t.B + 3) / 4;
-    const int nb = (int)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
-    hipLaunchKernelGGL(topk_mark_kernel, dim3(nb), dim3(256), 0, st, t.B, t.D, (t.D + 31) / 32, a.row_ptr, a.col,
-                       a.stored);
-  }
+  if (a.stored && a.nnz > 0) launch_topk_mark(t.B, t.D, a.row_ptr, a.col, a.stored, st);
   int32_t* cols = a.slices > 1 ? a.part_cols : a.cols;
   float* scores = a.slices > 1 ? a.part_scores : a.scores;
   bool ok;

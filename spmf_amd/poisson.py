@@ -604,7 +604,7 @@ class PoissonFactorization:
                 "lppd": float(lppd_i.sum()), "pwaic": float(pwaic_i.sum())}
 
     def _draw_call(self, name, draws, nsamples, min_draws, dense_alternative):
-        """What the streaming calls (waic_streaming, top_k, score_cells) hand the library's draw stage:
+        """What the streaming calls (waic_streaming, top_k, score_cells, rank_cells) hand the library's draw stage:
         ``(S, pin, eta_ptr, stream, KP, lib, h)``.  ``draws``: dict with 's','u','v','w' of shape [S,...]
         (None: ``surrogate_distribution.sample(nsamples)``), at least ``min_draws`` of them; ``pin`` is the
         C-ABI's twelve parameter slots and keeps the packed tensors it points into alive."""
@@ -749,46 +749,80 @@ class PoissonFactorization:
         count in the batch makes every score of its row NaN.  A cell's scores do not depend on
         the order of the list or on ``max_rows``.  Bit-reproducible."""
         from . import heldout as _heldout
-        if callable(data) or not (isinstance(data, (dict, SparseCounts)) or hasattr(data, "shape")):
-            raise ValueError("score_cells takes ONE batch (a dict or counts), not an iterable or a factory")
+        rows, cols, vals, n_rows = self._cell_list("score_cells", data, rows, cols, values)
+        N = int(rows.numel())
+        S, pin, eta, stream, KP, lib, h = self._draw_call("score_cells", draws, nsamples, 1,
+                                                          "log_likelihood_components")
+        rows, cols, vals, order, segments = self._cell_segments(data, rows, cols, vals, n_rows, S * KP * 4, max_rows)
+        nan = float("nan")
+        mean = torch.full((N,), nan, dtype=torch.float32, device=self.device)
+        lppd = torch.full((N,), nan, dtype=torch.float32, device=self.device) if vals is not None else None
+        scratch = _Scratch(self.device)
+        for sub, rel, lo, hi in segments:
+            _lib.check(h, lib.spmf_score_cells(
+                h, C.byref(sub), S, pin, eta, hi - lo, rel.data_ptr(), cols[lo:hi].data_ptr(),
+                vals[lo:hi].data_ptr() if vals is not None else None, mean[lo:hi].data_ptr(),
+                lppd[lo:hi].data_ptr() if lppd is not None else None,
+                *scratch.fit(lib.spmf_cells_scratch_bytes(h, int(sub.n_rows), S)), stream), "spmf_score_cells")
+        del rows, cols, vals, scratch, segments
+        out = {"mean": torch.empty_like(mean).index_copy_(0, order, mean)}
+        del mean
+        if lppd is not None:
+            out["lppd"] = torch.empty_like(lppd).index_copy_(0, order, lppd)
+            del lppd, order
+            out.update(_heldout.summarize(out["lppd"]))
+        return out
 
-        def vector(name, t, floating):
+    def _cell_list(self, name, data, rows, cols, values=None):
+        """The cell list of ``score_cells`` / ``rank_cells`` (``name``), checked before any library call:
+        ``data`` is one batch, ``rows`` / ``cols`` (/ ``values``) are 1-D and of equal length, the indices
+        integers inside the batch.  -> (rows, cols, values or None, rows of the batch), on the device."""
+        if callable(data) or not (isinstance(data, (dict, SparseCounts)) or hasattr(data, "shape")):
+            raise ValueError(f"{name} takes ONE batch (a dict or counts), not an iterable or a factory")
+
+        def vector(what, t, floating):
             if not isinstance(t, torch.Tensor):
                 t = np.asarray(t)
                 if t.size == 0 and not floating:        # [] has no dtype of its own
                     t = t.astype(np.int64)
                 t = torch.as_tensor(t)
             if t.dim() != 1:
-                raise ValueError(f"score_cells: {name} must be 1-D, got shape {tuple(t.shape)}")
+                raise ValueError(f"{name}: {what} must be 1-D, got shape {tuple(t.shape)}")
             if floating:
                 return t.to(device=self.device, dtype=torch.float32)
             if t.dtype.is_floating_point or t.dtype == torch.bool:
-                raise ValueError(f"score_cells: {name} must hold integers, got {t.dtype}")
+                raise ValueError(f"{name}: {what} must hold integers, got {t.dtype}")
             return t.to(device=self.device)
         rows, cols = vector("rows", rows, False), vector("cols", cols, False)
         vals = vector("values", values, True) if values is not None else None
         N = int(rows.numel())
         if cols.numel() != N or (vals is not None and vals.numel() != N):
-            raise ValueError(f"score_cells: rows, cols and values must have equal length, got {N}, "
+            raise ValueError(f"{name}: rows, cols and values must have equal length, got {N}, "
                              f"{int(cols.numel())}" + (f", {int(vals.numel())}" if vals is not None else ""))
         # the index check: one device-side min / max and one read-back, before any library call
         # (the batch's row count is read off its shape, not off the library's descriptor)
         n_rows = self._batch_rows(data)
         if n_rows > 2 ** 31 - 1:
-            raise ValueError(f"score_cells: a batch of {n_rows} rows is beyond the int32 row index of the list; "
+            raise ValueError(f"{name}: a batch of {n_rows} rows is beyond the int32 row index of the list; "
                              "score it by panel ranges")
         if N:
             r_lo, r_hi, c_lo, c_hi = torch.stack(
                 [t.to(torch.int64) for t in (rows.min(), rows.max(), cols.min(), cols.max())]).tolist()
             if r_lo < 0 or r_hi >= n_rows:
-                raise ValueError(f"score_cells: rows must lie in [0, {n_rows}), got {r_lo} .. {r_hi}")
+                raise ValueError(f"{name}: rows must lie in [0, {n_rows}), got {r_lo} .. {r_hi}")
             if c_lo < 0 or c_hi >= self.feature_dim:
-                raise ValueError(f"score_cells: cols must lie in [0, {self.feature_dim}), got {c_lo} .. {c_hi}")
-        S, pin, eta, stream, KP, lib, h = self._draw_call("score_cells", draws, nsamples, 1,
-                                                          "log_likelihood_components")
-        (lib_rows, chunks), = self._row_chunks(data, S * KP * 4, max_rows)
+                raise ValueError(f"{name}: cols must lie in [0, {self.feature_dim}), got {c_lo} .. {c_hi}")
+        return rows, cols, vals, n_rows
+
+    def _cell_segments(self, data, rows, cols, vals, n_rows, row_bytes, max_rows):
+        """The checked list of ``_cell_list`` cut along the row chunks of ``_row_chunks``: the cells sorted by
+        row (stable), so that a chunk's cells are one contiguous segment.  -> (rows, cols, vals as int32 / int32 /
+        float32 in sorted order, order, segments); ``order[i]`` is the caller's position of sorted cell i and
+        ``segments`` lists ``(sub, rel, lo, hi)`` per chunk with cells: the chunk's batch struct, its cells' rows
+        relative to the chunk's first row, and its slice of the sorted list."""
+        (lib_rows, chunks), = self._row_chunks(data, row_bytes, max_rows)
         assert lib_rows == n_rows, (lib_rows, n_rows)
-        # cells sorted by row (stable): a row chunk's cells are one contiguous segment
+        N = int(rows.numel())
         rows, order = torch.sort(rows.to(torch.int32), stable=True)
         cols = cols.to(torch.int32)[order]
         if vals is not None:
@@ -800,26 +834,58 @@ class PoissonFactorization:
                             device=self.device)
         edges = torch.stack([torch.searchsorted(rows, first), torch.searchsorted(rows, last, right=True)],
                             1).tolist() if N else []
-        nan = float("nan")
-        mean = torch.full((N,), nan, dtype=torch.float32, device=self.device)
-        lppd = torch.full((N,), nan, dtype=torch.float32, device=self.device) if vals is not None else None
+        segments = [(sub, rows[lo:hi] - r0 if r0 else rows[lo:hi], lo, hi)
+                    for (r0, sub), (lo, hi) in zip(chunks, edges) if hi > lo]
+        return rows, cols, vals, order, segments
+
+    def rank_cells(self, data, rows, cols, k=(1, 5, 10, 20, 50), nsamples=32, draws=None, exclude_stored=True,
+                   max_rows=None):
+        """Held-out ranking: where the listed cells ``(rows[i], cols[i])`` land in the ranking of ``top_k``,
+        without a [B,D] array (csrc/rank.hip).  Score, order and candidates are ``top_k``'s: the mean over the
+        draws of the rate on a Poisson column and of sigmoid(logit) on a Bernoulli one; score descending, equal
+        scores by ascending column; the candidates of a row are its columns with a finite score that, with
+        ``exclude_stored``, the batch does not store.  A listed cell may or may not be a candidate itself.
+
+        ``data`` is ONE batch and ``rows`` / ``cols`` are as in ``score_cells`` (any order, duplicates allowed,
+        any number of cells per row); ``draws`` / ``nsamples`` as in ``top_k``, ``max_rows`` as in ``top_k``.
+        ``k``: the cut-offs of the summary's hit rates (an int or a sequence of ints).
+
+        Returns, on the device and in the caller's order, 'rank': int32 [N], the number of the row's other
+        candidates that precede the cell (0 is the best; -1 for a non-finite score, e.g. a row with a NaN
+        count), 'candidates': int32 [N], the number of the row's candidates beside the cell, and 'score':
+        float32 [N], bit for bit the score ``top_k`` reports for that cell -- so for a cell that is not stored,
+        ``rank < k`` exactly when ``top_k(k)["columns"][row, rank]`` is its column.  Plus the summary of
+        ``spmf_amd.heldout.rank_summary``: 'n', 'n_excluded', 'hit_rate' {k: share}, 'mrr', 'auc'.  A cell's
+        result does not depend on the order of the list, on its other cells or on ``max_rows``.
+        Bit-reproducible.  Cost: about two ``top_k`` sweeps while no row lists more than 32 cells; the kernel
+        serves 32 listed cells per row and round, so a row with n listed cells costs its block of 64 rows
+        ceil(n / 32) such double sweeps (listing every column of a row is correct but slow)."""
+        from . import heldout as _heldout
+        rows, cols, _, n_rows = self._cell_list("rank_cells", data, rows, cols)
+        ks = (int(k),) if isinstance(k, (int, np.integer)) else tuple(int(v) for v in k)
+        if any(v < 1 for v in ks):
+            raise ValueError(f"rank_cells: the cut-offs k must be >= 1, got {ks}")
+        N = int(rows.numel())
+        S, pin, eta, stream, KP, lib, h = self._draw_call("rank_cells", draws, nsamples, 1,
+                                                          "log_likelihood_components")
+        rows, cols, _, order, segments = self._cell_segments(
+            data, rows, cols, None, n_rows, S * KP * 4 + (self.feature_dim + 31) // 32 * 4, max_rows)
+        rank = torch.full((N,), -1, dtype=torch.int32, device=self.device)
+        cand = torch.zeros(N, dtype=torch.int32, device=self.device)
+        score = torch.full((N,), float("nan"), dtype=torch.float32, device=self.device)
         scratch = _Scratch(self.device)
-        for (r0, sub), (lo, hi) in zip(chunks, edges):
-            if hi == lo:
-                continue
-            rel = rows[lo:hi] - r0 if r0 else rows[lo:hi]
-            _lib.check(h, lib.spmf_score_cells(
-                h, C.byref(sub), S, pin, eta, hi - lo, rel.data_ptr(), cols[lo:hi].data_ptr(),
-                vals[lo:hi].data_ptr() if vals is not None else None, mean[lo:hi].data_ptr(),
-                lppd[lo:hi].data_ptr() if lppd is not None else None,
-                *scratch.fit(lib.spmf_cells_scratch_bytes(h, int(sub.n_rows), S)), stream), "spmf_score_cells")
-        del rows, cols, vals, scratch
-        out = {"mean": torch.empty_like(mean).index_copy_(0, order, mean)}
-        del mean
-        if lppd is not None:
-            out["lppd"] = torch.empty_like(lppd).index_copy_(0, order, lppd)
-            del lppd, order
-            out.update(_heldout.summarize(out["lppd"]))
+        flags = 1 if exclude_stored else 0
+        for sub, rel, lo, hi in segments:
+            _lib.check(h, lib.spmf_rank_cells(
+                h, C.byref(sub), S, pin, eta, hi - lo, rel.data_ptr(), cols[lo:hi].data_ptr(), flags,
+                rank[lo:hi].data_ptr(), cand[lo:hi].data_ptr(), score[lo:hi].data_ptr(),
+                *scratch.fit(lib.spmf_rank_scratch_bytes(h, int(sub.n_rows), S)), stream), "spmf_rank_cells")
+        del rows, cols, scratch, segments
+        out = {"rank": torch.empty_like(rank).index_copy_(0, order, rank),
+               "candidates": torch.empty_like(cand).index_copy_(0, order, cand),
+               "score": torch.empty_like(score).index_copy_(0, order, score)}
+        del rank, cand, score, order
+        out.update(_heldout.rank_summary(out["rank"], out["candidates"], ks))
         return out
 
     def _nonfinite_scan(self, sc, cs, data, S, P, max_cells=1 << 27):

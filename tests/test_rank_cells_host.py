@@ -1,0 +1,262 @@
+"""CPU-side tests of rank_cells (PoissonFactorization.rank_cells, spmf_rank_cells, csrc/rank.hip): the two
+entry points in the header, the export list and the binding, the method on the class surface, the error
+contract of the draw stage and the entry's own argument errors -- all refused before anything touches a
+device -- the summary of spmf_amd.heldout.rank_summary on hand cases, and the argument checks of the method
+that need no device.  (The valid call: tests/test_gpu_rank_cells.py.)"""
+import ctypes as C
+import fnmatch
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CALL, SIZE = "spmf_rank_cells", "spmf_rank_scratch_bytes"
+HEADER_ARGS = {SIZE: 3, CALL: 15}
+# the arguments between `eta` and `scratch` in the header's order
+OWN = (("n", C.c_int64), ("row", C.c_void_p), ("col", C.c_void_p), ("flags", C.c_uint), ("rank", C.c_void_p),
+       ("cand", C.c_void_p), ("score", C.c_void_p))
+B, D, K, S = 70, 45, 3, 2
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as ge
+    from spmf_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        ge.build()
+    return _lib.load()
+
+
+def _header_args(hdr, name):
+    m = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", hdr, re.S)
+    assert m, f"{name} is not declared in include/spmf_hip.h"
+    return len([a for a in m.group(1).split(",") if a.strip()])
+
+
+def test_entry_points_are_declared_exported_and_bound():
+    from spmf_amd import _lib
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "spmf_hip.h")).read(), flags=re.S)
+    exports = open(os.path.join(ROOT, "spmf_amd", "csrc", "exports.map")).read()
+    exports = re.sub(r"/\*.*?\*/", "", exports, flags=re.S)
+    globs = re.search(r"global:\s*([^}]*?)local:", exports, re.S).group(1)
+    patterns = [p.strip() for p in globs.split(";") if p.strip()]
+    for name, nargs in HEADER_ARGS.items():
+        assert any(fnmatch.fnmatchcase(name, p) for p in patterns), (name, patterns)
+        assert name in _lib.SIGNATURES, name
+        assert len(_lib.SIGNATURES[name][1]) == _header_args(hdr, name) == nargs, name
+    assert "define SPMF_ABI_VERSION 6" in hdr and _lib.ABI_VERSION == 6
+
+
+def test_symbols_are_in_the_built_library(lib):
+    assert callable(getattr(lib, CALL)) and callable(getattr(lib, SIZE))
+
+
+def test_method_is_on_all_three_classes():
+    from spmf_amd import BernoulliFactorization, MixedFactorization, PoissonFactorization
+    for cls in (PoissonFactorization, BernoulliFactorization, MixedFactorization):
+        assert callable(getattr(cls, "rank_cells", None)), cls.__name__
+
+
+def _ctx(lib, k, flags=0):
+    h = C.c_void_p()
+    assert lib.spmf_ctx_create(0, k, D, flags, C.byref(h)) == 0
+    return h
+
+
+def _raw_call(good):
+    """-> call(**overrides): spmf_rank_cells through a binding of its own with plain pointers, so that NULL can
+    stand for `params` and `counts` too (what _stream_cases.abi_call does for the entries of its table)."""
+    from spmf_amd import _lib
+    fn = getattr(C.CDLL(_lib.LIB_PATH), CALL)
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [t for _, t in OWN] + [
+        C.c_void_p, C.c_size_t, C.c_void_p]
+
+    def call(**kw):
+        a = dict(good, **kw)
+        return fn(a["h"], C.byref(a["ct"]) if a["ct"] is not None else None, a["S"], a["pin"], a["eta"],
+                  *[a[n] for n, _ in OWN], a["ptr"], a["nbytes"], a["stream"])
+    return call
+
+
+def test_shared_and_own_errors_return_before_any_device_call(lib):
+    """A context of spmf_ctx_create, a hand-filled descriptor of 70 empty rows and dummy aligned addresses: the
+    error cases of the draw stage (the list of _stream_cases.assert_shared_errors) and the entry's own are
+    refused with their codes; nothing here is a valid call, so nothing may be launched or dereferenced."""
+    from spmf_amd import _lib
+    from spmf_amd._lib import VAR_ORDER
+    h, raw = _ctx(lib, K), _ctx(lib, K, _lib.FLAG_MIXED)
+    try:
+        cs = _lib.CountsStruct()
+        cs.struct_size = C.sizeof(_lib.CountsStruct)
+        cs.n_cols, cs.n_rows, cs.nnz, cs.row_ptr = D, B, 0, 0x10000
+        slots = {n: 0x100000 * (i + 1) for i, n in enumerate(VAR_ORDER) if n in ("s", "u", "v", "w")}
+        need = int(lib.spmf_rank_scratch_bytes(h, B, S))
+        assert need > 0 and need % 256 == 0
+        good = dict(h=h, ct=cs, S=S, pin=_lib.PtrArray(*[slots.get(n) for n in VAR_ORDER]), eta=0x7000000,
+                    ptr=0x8000000, nbytes=need, stream=None, n=4, row=0x2000000, col=0x3000000, flags=1,
+                    rank=0x4000000, cand=0x5000000, score=0x6000000)
+        no_u = _lib.PtrArray(*[slots.get(n) if n != "u" else None for n in VAR_ORDER])
+        call = _raw_call(good)
+        # the draw stage's contract
+        assert call(S=0) == -1, "S below the minimum"
+        assert call(S=65536) == -1
+        assert call(pin=None) == -1 and call(eta=None) == -1 and call(ptr=None) == -1 and call(ct=None) == -1
+        assert call(pin=no_u) == -1, "slot u missing"
+        assert call(ptr=good["ptr"] + 4) == -1, "scratch off by 4 bytes"
+        bad = type(cs).from_buffer_copy(cs)
+        bad.struct_size += 8
+        assert call(ct=bad) == -1, "struct_size + 8"
+        assert call(h=raw) == -1
+        assert "column_types" in lib.spmf_last_error(raw).decode()
+        assert call(nbytes=need - 256) == -3
+        msg = lib.spmf_last_error(h).decode()
+        assert str(need) in msg, msg
+        # the entry's own
+        assert call(n=-1) == -1
+        assert "n_cells" in lib.spmf_last_error(h).decode()
+        for name in ("row", "col", "rank", "cand", "score"):
+            assert call(**{name: None}) == -1, name
+        assert call(flags=2) == -1 and call(flags=3) == -1
+        assert "flag" in lib.spmf_last_error(h).decode()
+        assert call(n=0, flags=4) == -1, "an unknown flag is refused for an empty list too"
+        assert call(n=0, nbytes=need - 256) == -3, "errors come before the empty-list return"
+        # an empty list is served without a launch: no pointer here could be dereferenced
+        assert call(n=0) == 0 and call(n=0, row=None, col=None, rank=None, cand=None, score=None) == 0
+        empty = type(cs).from_buffer_copy(cs)
+        empty.n_rows = 0
+        assert call(ct=empty) == 0, "an empty batch"
+    finally:
+        lib.spmf_ctx_destroy(h)
+        lib.spmf_ctx_destroy(raw)
+
+
+@pytest.mark.parametrize("k", [3, 16, 64, 128])
+def test_scratch_size(lib, k):
+    """A multiple of 256: the draw stage's scratch and the bitmap of the stored cells (at most the top-k call's,
+    which adds its slices' partial results); 0 for S < 1, for negative rows and without a context."""
+    h = _ctx(lib, k)
+    try:
+        for s in (1, 2, 7):
+            rank, cells, topk = (int(getattr(lib, f)(h, B, s)) for f in
+                                 (SIZE, "spmf_cells_scratch_bytes", "spmf_topk_scratch_bytes"))
+            bitmap = B * ((D + 31) // 32) * 4
+            assert rank % 256 == 0 and cells + bitmap <= rank <= cells + bitmap + 255 and rank <= topk
+        assert int(lib.spmf_rank_scratch_bytes(h, B, 0)) == 0
+        assert int(lib.spmf_rank_scratch_bytes(h, -1, 2)) == 0
+        assert int(lib.spmf_rank_scratch_bytes(None, B, 2)) == 0
+    finally:
+        lib.spmf_ctx_destroy(h)
+
+
+# ---- heldout.rank_summary ----------------------------------------------------------------------
+
+def test_rank_summary_hand_case():
+    from spmf_amd.heldout import rank_summary
+    rank = torch.tensor([0, 3, -1, 9], dtype=torch.int32)
+    cand = torch.tensor([10, 10, 0, 10], dtype=torch.int32)
+    out = rank_summary(rank, cand, (1, 5))
+    assert set(out) == {"n", "n_excluded", "hit_rate", "mrr", "auc"}
+    assert out["n"] == 3 and out["n_excluded"] == 1
+    assert set(out["hit_rate"]) == {1, 5}
+    assert out["hit_rate"][1] == 1 / 3 and out["hit_rate"][5] == 2 / 3
+    assert abs(out["mrr"] - (1 + 1 / 4 + 1 / 10) / 3) <= 1e-15
+    assert abs(out["auc"] - (1 + 0.7 + 0.1) / 3) <= 1e-15
+    assert rank_summary(rank.numpy(), cand.numpy(), (1, 5)) == out               # numpy in
+    assert rank_summary(rank, cand, 5)["hit_rate"] == {5: 2 / 3}                 # a single cut-off
+
+
+def test_rank_summary_auc_leaves_out_cells_without_other_candidates():
+    from spmf_amd.heldout import rank_summary
+    out = rank_summary([0, 0, 2], [0, 4, 4], (1,))
+    assert out["n"] == 3 and out["n_excluded"] == 0 and out["hit_rate"][1] == 2 / 3
+    assert out["auc"] == (1.0 + 0.5) / 2
+    assert abs(out["mrr"] - (1 + 1 + 1 / 3) / 3) <= 1e-15
+
+
+def test_rank_summary_does_not_depend_on_the_order_of_the_list():
+    from spmf_amd.heldout import rank_summary
+    rng = np.random.default_rng(5)
+    cand = rng.integers(0, 20_000, size=26_000)
+    rank = np.where(cand > 0, rng.integers(0, np.maximum(cand, 1) + 1), 0)
+    rank[::13] = -1
+    one = rank_summary(torch.as_tensor(rank), torch.as_tensor(cand))
+    assert one["n"] == 24_000 and one["n_excluded"] == 2_000 and 0.0 < one["auc"] < 1.0 and 0.0 < one["mrr"] < 1.0
+    assert sorted(one["hit_rate"]) == [1, 5, 10, 20, 50]
+    for seed in (1, 2, 3):
+        p = np.random.default_rng(seed).permutation(rank.size)
+        assert rank_summary(torch.as_tensor(rank[p]), torch.as_tensor(cand[p])) == one
+
+
+def test_rank_summary_of_an_empty_list_and_of_unranked_cells():
+    from spmf_amd.heldout import rank_summary
+    for rank, cand, excl in (([], [], 0), ([-1, -1], [0, 0], 2)):
+        out = rank_summary(torch.tensor(rank, dtype=torch.int32), torch.tensor(cand, dtype=torch.int32), (1, 5))
+        assert out["n"] == 0 and out["n_excluded"] == excl
+        assert math.isnan(out["mrr"]) and math.isnan(out["auc"])
+        assert set(out["hit_rate"]) == {1, 5} and all(math.isnan(v) for v in out["hit_rate"].values())
+    with pytest.raises(ValueError):
+        rank_summary([0, 1], [3])
+
+
+# ---- the method's argument checks ---------------------------------------------------------------
+
+def _cpu_model():
+    from spmf_amd import PoissonFactorization
+    m = PoissonFactorization(latent_dim=2, feature_dim=6, initialize_distributions=False, device="cpu")
+    rng = np.random.default_rng(0)
+    x = rng.poisson(1.0, size=(8, 6)).astype(np.float64)
+    draws = {"u": rng.random((2, 6, 2)), "v": rng.random((2, 2, 6)), "w": rng.random((2, 1, 6)),
+             "s": rng.random((2, 2, 6))}
+    return m, x, draws
+
+
+def test_bad_lists_raise_value_error_without_a_device():
+    m, x, draws = _cpu_model()
+    data = {"counts": x}
+    with pytest.raises(ValueError, match="1-D"):
+        m.rank_cells(data, np.zeros((2, 1), dtype=np.int64), [1, 5], draws=draws)
+    with pytest.raises(ValueError, match="integers"):
+        m.rank_cells(data, [0, 3], [1.0, 5.0], draws=draws)
+    with pytest.raises(ValueError, match="equal length"):
+        m.rank_cells(data, [0, 3], [1], draws=draws)
+    for rows, cols in (([0, 8], [0, 1]), ([0, -1], [0, 1]), ([0, 1], [6, 1]), ([0, 1], [3, -1])):
+        with pytest.raises(ValueError, match="must lie in"):
+            m.rank_cells(data, rows, cols, draws=draws)
+    with pytest.raises(ValueError, match="ONE batch"):
+        m.rank_cells([data], [0], [1], draws=draws)
+    with pytest.raises(ValueError, match="ONE batch"):
+        m.rank_cells(lambda: iter([data]), [0], [1], draws=draws)
+    with pytest.raises(ValueError, match="cut-offs"):
+        m.rank_cells(data, [0], [1], k=(1, 0), draws=draws)
+
+
+def test_a_valid_list_on_a_cpu_model_fails_like_top_k():
+    """Past the argument checks the call needs the library's context, as top_k does: the same failure, and not a
+    ValueError."""
+    m, x, draws = _cpu_model()
+    with pytest.raises(Exception) as e_topk:
+        m.top_k({"counts": x}, k=3, draws=draws)
+    with pytest.raises(Exception) as e_rank:
+        m.rank_cells({"counts": x}, [0, 3], [1, 5], draws=draws)
+    assert type(e_rank.value) is type(e_topk.value), (e_rank.value, e_topk.value)
+    assert not isinstance(e_rank.value, ValueError)
+
+
+def test_score_cells_keeps_its_error_messages():
+    """The two methods share their list handling; each names itself."""
+    m, x, draws = _cpu_model()
+    with pytest.raises(ValueError, match=r"^score_cells: rows must be 1-D, got shape \(2, 1\)$"):
+        m.score_cells({"counts": x}, np.zeros((2, 1), dtype=np.int64), [1, 5], draws=draws)
+    with pytest.raises(ValueError, match=r"^score_cells: rows, cols and values must have equal length, got 2, 2, 1$"):
+        m.score_cells({"counts": x}, [0, 3], [1, 5], values=[1.0], draws=draws)
+    with pytest.raises(ValueError, match=r"^score_cells: cols must lie in \[0, 6\), got 1 \.\. 6$"):
+        m.score_cells({"counts": x}, [0, 3], [1, 6], draws=draws)
+    with pytest.raises(ValueError, match=r"^score_cells takes ONE batch"):
+        m.score_cells([{"counts": x}], [0], [1], draws=draws)
+    with pytest.raises(ValueError, match=r"^rank_cells: cols must lie in \[0, 6\), got 1 \.\. 6$"):
+        m.rank_cells({"counts": x}, [0, 3], [1, 6], draws=draws)
