@@ -627,6 +627,56 @@ int spmf_rank_cells(spmf_ctx* ctx, const spmf_counts* counts, int S,
                     int32_t* rank_out, int32_t* cand_out, float* score_out, void* scratch,
                     size_t scratch_bytes, void* stream);
 
+/* ---- posterior mean encoding (added within ABI 6: two new entry points, no struct changed) ----
+ * The rows of the batch `counts` in the latent space: mean_out[b][k] = (1/S) sum_s z_sb[k], k < K,
+ * where z_sb is the encode sweep of draw s (what spmf_encode computes from u_s, s_s), fp32, the sum in
+ * draw order times 1/S; with sd_out the unbiased standard deviation over the draws (Welford in draw
+ * order), which needs S >= 2.  mean_out / sd_out: [n_rows][K], unpadded.  A NaN count makes its whole
+ * row NaN.  (csrc/knn.hip)
+ * params: only u, v, w, s (slots 2, 0, 1, 7) are read, each with the leading axis S.
+ * scratch: 256-byte aligned, at least spmf_embed_scratch_bytes(ctx, counts->n_rows, S) bytes (the
+ * draw stage's scratch alone); SPMF_E_WORKSPACE when short.  SPMF_E_ARG for S outside 1..65535, NULL
+ * params / eta / scratch / mean_out, sd_out with S < 2, a misaligned scratch, a mixed context without
+ * column types or a struct_size mismatch; every error returns before any launch.  The context's
+ * workspace is not touched.  Stream-ordered, synchronises nowhere.  Bit-reproducible, and a row's
+ * result does not depend on how the rows are cut into calls. */
+size_t spmf_embed_scratch_bytes(const spmf_ctx* ctx, int64_t n_rows, int S);
+int spmf_embed_rows(spmf_ctx* ctx, const spmf_counts* counts, int S,
+                    const float* const params[SPMF_NVARS], const float* eta, float* mean_out,
+                    float* sd_out, void* scratch, size_t scratch_bytes, void* stream);
+
+/* ---- exact k nearest rows (added within ABI 6: two new entry points, no struct changed) ----
+ * For every row of q [n_query][row_len] the k nearest rows of r [n_ref][row_len] (fp32, device,
+ * 1 <= row_len <= 256 whatever the context's K, 1 <= k <= 64), without an array of size
+ * n_query * n_ref (csrc/knn.hip).  The context serves the error message and the device only.
+ * flags bit 0: cosine distance 1 - cos instead of the Euclidean distance.  self_offset >= 0: query i
+ * IS reference row self_offset + i and is no candidate of its own; -1: no exclusion.
+ *   Working rows: Euclidean q' = q - c, r' = r - c with c the mean of the finite reference rows
+ * (fixed-order sums, no float atomics; distances do not depend on c, it removes the cancellation
+ * of the expansion below for clouds far from the origin); cosine q' = q/|q|, r' = r/|r|.  They are
+ * zero-padded to KP = 4 .. 256 in the scratch; q == r with n_query == n_ref is prepared once.
+ *   Selection score s_ij = <q'_i, r'_j> - 1/2 |r'_j|^2 on the exact-f32 matrix cores: the larger
+ * score is the nearer row, equal scores go to the smaller index.  A candidate has a finite score
+ * and is not the excluded self: a non-finite reference row is none, a non-finite query row (or a
+ * zero row under cosine) has none.  The best k candidates are then refined from the caller's rows:
+ * Euclidean dist = sqrt(sum_k (q_ik - r_jk)^2) by fmaf in ascending k, cosine
+ * dist = 1/2 sum_k (q'_ik - r'_jk)^2 = 1 - cos, and ordered by (dist ascending, index ascending).
+ * The expansion only decides membership at near-ties; the distances carry no cancellation.
+ *   idx_out int32 [n_query][k], dist_out fp32 [n_query][k]; fewer than k candidates are padded
+ * with -1 / +inf at the tail.  Bit-reproducible; a query's result does not depend on the other
+ * queries or on its position in the list.
+ * scratch: 256-byte aligned, at least spmf_knn_scratch_bytes(ctx, n_query, n_ref, row_len) bytes
+ * (it does not depend on k); SPMF_E_WORKSPACE when short, naming the need.  SPMF_E_ARG for
+ * n_ref > 2^31 - 1, a negative count, k outside 1..64, row_len outside 1..256, unknown flag bits,
+ * self_offset < -1, NULL q / idx_out / dist_out with n_query > 0, NULL r with n_ref > 0, a NULL or
+ * misaligned scratch; every error returns before any launch with "knn: " in front of the message.
+ * n_query == 0 returns SPMF_OK without work; n_ref == 0 fills the padding.  Stream-ordered,
+ * synchronises nowhere. */
+size_t spmf_knn_scratch_bytes(const spmf_ctx* ctx, int64_t n_query, int64_t n_ref, int row_len);
+int spmf_knn(spmf_ctx* ctx, const float* q, int64_t n_query, const float* r, int64_t n_ref,
+             int row_len, int k, unsigned flags, int64_t self_offset, int32_t* idx_out,
+             float* dist_out, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Reductions of the non-finite rule (poisson.py:606-616) over a dense ll
  * buffer of n cells; io = double[3] on the device.
  *   pass 0: io[0] = min(io[0], min over finite cells)  (initialise io[0]=0:

@@ -1170,7 +1170,8 @@ int spmf_dense_ll(spmf_ctx* c, const spmf_counts* ct, const float* u, const floa
 }
 
 // ---- the draw stage of the streaming calls ---------------------------------------------------
-// spmf_waic_accumulate, spmf_topk_rows, spmf_score_cells and spmf_rank_cells are one stage and a consumer each.
+// spmf_waic_accumulate, spmf_topk_rows, spmf_score_cells, spmf_rank_cells and spmf_embed_rows are one stage and a
+// consumer each.
 // The stage: for S draws the per-draw tables (prep) and the encoded rows z[S,B,KP] go into the caller's scratch; the consumer
 // kernel then reads z, V' and phi of every draw (kernels.h DrawTables).  The context's workspace is not used, so
 // a step that is bound (or half way: spmf_step_begin .. spmf_step_end) keeps everything it has.
@@ -1404,6 +1405,110 @@ int spmf_rank_cells(spmf_ctx* c, const spmf_counts* ct, int S, const float* cons
   ra.n_cells = n_cells; ra.cell_row = cell_row; ra.cell_col = cell_col;
   ra.rank = rank_out; ra.cand = cand_out; ra.score = score_out;
   if (!launch_rank(ra, st)) return fail(c, SPMF_E_UNSUPPORTED, "rank_cells: no kernel for this K / likelihood");
+  HIPCHK(c, hipGetLastError());
+  return SPMF_OK;
+}
+
+// ---- posterior mean encoding of a batch (knn.hip) ---------------------------------------------
+// Scratch of one call: the draw carve alone.
+size_t spmf_embed_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S) {
+  if (!c || n_rows < 0 || S < 1) return 0;
+  return draw_carve(c, n_rows, S).total;
+}
+
+int spmf_embed_rows(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS], const float* eta,
+    float* mean_out, float* sd_out, void* scratch, size_t scratch_bytes, void* stream) {
+  int rc = draw_check(c, "embed_rows", ct, S, 1, params, eta, scratch, scratch_bytes, spmf_embed_scratch_bytes);
+  if (rc) return rc;
+  if (!mean_out) return fail(c, SPMF_E_ARG, "embed_rows: null argument");
+  if (sd_out && S < 2) return fail(c, SPMF_E_ARG, "embed_rows: sd_out needs S >= 2 (the deviation over the draws)");
+  if (ct->n_rows == 0) return SPMF_OK;
+  hipStream_t st = (hipStream_t)stream;
+  DrawTables dt;
+  rc = draw_stage(c, "embed_rows", ct, S, params, eta, scratch, st, dt);
+  if (rc) return rc;
+  launch_embed(dt, c->K, mean_out, sd_out, st);
+  HIPCHK(c, hipGetLastError());
+  return SPMF_OK;
+}
+
+// ---- exact k nearest rows (knn.hip) -----------------------------------------------------------
+// Scratch of one call: the working rows of the reference set and of the queries (sized for both, whether or not
+// the call passes one array as both), the biases, the centre and its per-block partial sums, and the slices'
+// results (sized for k = kTopkMaxK: the size does not depend on the call's k).
+static int knn_padded(int row_len) {
+  int kp = 4;
+  while (kp < row_len) kp *= 2;
+  return kp;
+}
+struct KnnCarve {
+  size_t rw, bias, qw, cpart, ccnt, centre, pidx, pscore, total;
+  int KP, slices;
+};
+static KnnCarve knn_carve(const spmf_ctx* c, int64_t nq, int64_t nr, int row_len) {
+  KnnCarve k;
+  k.KP = knn_padded(row_len);
+  k.slices = nr > 0 ? topk_slices(nq, (int)nr, device_cus(c)) : 1;
+  size_t o = 0;
+  k.rw = o;     o += al((size_t)nr * k.KP * sizeof(float));
+  k.bias = o;   o += al((size_t)nr * sizeof(float));
+  k.qw = o;     o += al((size_t)nq * k.KP * sizeof(float));
+  k.cpart = o;  o += al((size_t)kKnnCentreBlocks * k.KP * sizeof(float));
+  k.ccnt = o;   o += al((size_t)kKnnCentreBlocks * sizeof(int32_t));
+  k.centre = o; o += al((size_t)k.KP * sizeof(float));
+  const size_t part = k.slices > 1 ? (size_t)k.slices * nq * kTopkMaxK : 0;
+  k.pidx = o;   o += al(part * sizeof(int32_t));
+  k.pscore = o; o += al(part * sizeof(float));
+  k.total = o;
+  return k;
+}
+
+size_t spmf_knn_scratch_bytes(const spmf_ctx* c, int64_t n_query, int64_t n_ref, int row_len) {
+  if (!c || n_query < 0 || n_ref < 0 || n_ref > 0x7fffffffLL || row_len < 1 || row_len > 256) return 0;
+  return knn_carve(c, n_query, n_ref, row_len).total;
+}
+
+// SPMF_KNN_TILE = 0 | 1 picks the tile function of the select kernel (knn.hip); both give the same bits
+static int knn_tile() {
+  const char* e = getenv("SPMF_KNN_TILE");
+  return e && e[0] == '1' ? 1 : (e && e[0] == '0' ? 0 : kKnnDefaultTile);
+}
+
+int spmf_knn(spmf_ctx* c, const float* q, int64_t n_query, const float* r, int64_t n_ref, int row_len, int k,
+    unsigned flags, int64_t self_offset, int32_t* idx_out, float* dist_out, void* scratch, size_t scratch_bytes,
+    void* stream) {
+  if (!c) return SPMF_E_ARG;
+  if (n_query < 0 || n_ref < 0) return fail(c, SPMF_E_ARG, "knn: n_query and n_ref must not be negative");
+  if (n_ref > 0x7fffffffLL) return fail(c, SPMF_E_ARG, "knn: n_ref above 2^31 - 1 (the indices are int32)");
+  if (n_query > ((int64_t)1 << 31) - 64) return fail(c, SPMF_E_ARG, "knn: too many queries in one call");
+  if (row_len < 1 || row_len > 256) return fail(c, SPMF_E_ARG, "knn: row_len must be in 1..256");
+  if (k < 1 || k > kTopkMaxK) return fail(c, SPMF_E_ARG, "knn: k must be in 1..64");
+  if (flags & ~1u) return fail(c, SPMF_E_ARG, "knn: unknown flag (bit 0: cosine)");
+  if (self_offset < -1) return fail(c, SPMF_E_ARG, "knn: self_offset must be -1 (none) or the reference row of "
+      "query 0");
+  if (!scratch) return fail(c, SPMF_E_ARG, "knn: null argument");
+  if ((n_query > 0 && (!q || !idx_out || !dist_out)) || (n_ref > 0 && !r)) return fail(c, SPMF_E_ARG,
+      "knn: null argument");
+  if ((uintptr_t)scratch & 255) return fail(c, SPMF_E_ARG, "knn: scratch must be 256-byte aligned");
+  const KnnCarve kc = knn_carve(c, n_query, n_ref, row_len);
+  if (kc.total > scratch_bytes) {
+    char b[200];
+    snprintf(b, sizeof b, "knn: scratch too small: need %zu bytes for n_query=%lld n_ref=%lld row_len=%d, have %zu",
+        kc.total, (long long)n_query, (long long)n_ref, row_len, scratch_bytes);
+    return fail(c, SPMF_E_WORKSPACE, b);
+  }
+  if (n_query == 0) return SPMF_OK;
+  char* base = (char*)scratch;
+  KnnArgs ka{};
+  ka.n_query = n_query; ka.n_ref = n_ref; ka.row_len = row_len; ka.KP = kc.KP; ka.k = k; ka.slices = kc.slices;
+  ka.cosine = (flags & 1u) != 0; ka.tile = knn_tile(); ka.self_offset = self_offset;
+  ka.q = q; ka.r = r;
+  ka.rw = (float*)(base + kc.rw); ka.bias = (float*)(base + kc.bias);
+  ka.qw = (q == r && n_query == n_ref) ? ka.rw : (float*)(base + kc.qw);
+  ka.cpart = (float*)(base + kc.cpart); ka.ccnt = (int32_t*)(base + kc.ccnt); ka.centre = (float*)(base + kc.centre);
+  ka.part_idx = (int32_t*)(base + kc.pidx); ka.part_score = (float*)(base + kc.pscore);
+  ka.idx = idx_out; ka.dist = dist_out;
+  if (!launch_knn(ka, (hipStream_t)stream)) return fail(c, SPMF_E_UNSUPPORTED, "knn: no kernel for this row_len / k");
   HIPCHK(c, hipGetLastError());
   return SPMF_OK;
 }

@@ -229,6 +229,35 @@ bool launch_topk(const TopkArgs& a, hipStream_t st);
 // topk.hip: ORs a bit per CSR entry of the B rows into the zeroed bitmap bits[B][ceil(D/32)] (launch_topk runs it
 // itself; rank.hip reads the same bitmap)
 void launch_topk_mark(int64_t B, int D, const int32_t* row_ptr, const int32_t* col, uint32_t* bits, hipStream_t st);
+// topk.hip: one wave per row ranks the candidates pc / ps [nsl][B][k] of nsl slices (padding: column -1) into
+// cols / scores [B][k] (launch_topk runs it itself; knn.hip merges its reference slices with it)
+void launch_topk_merge(int64_t B, int k, int nsl, const int32_t* pc, const float* ps, int32_t* cols, float* scores,
+                       hipStream_t st);
+// knn.hip: the mean (and, with sd, the unbiased standard deviation) over the S draws of the encoded rows
+// t.z[S,B,KP], unpadded: mean / sd [B][K].  Nothing is launched for B == 0.
+void launch_embed(const DrawTables& t, int K, float* mean, float* sd, hipStream_t st);
+// knn.hip: exact k nearest rows of r [n_ref][row_len] for every row of q [n_query][row_len] (include/spmf_hip.h
+// spmf_knn has the definition).  The scratch pointers are api.hip's carve; qw == rw when q == r.  false: KP / k /
+// slices not built (nothing launched).
+constexpr int kKnnCentreBlocks = 512;   // most per-block partial sums of the centre
+constexpr int kKnnDefaultTile = 1;      // the tile function without SPMF_KNN_TILE: the faster one
+struct KnnArgs {
+  int64_t n_query, n_ref;
+  int row_len, KP, k, slices;
+  bool cosine;
+  int tile;                        // 0: score_block, 1: the query-resident tile (KP <= 64)
+  int64_t self_offset;             // query i is reference row self_offset + i (no candidate of its own); -1: none
+  const float *q, *r;              // the caller's rows
+  float *qw, *rw, *bias;           // working rows [n][KP], bias [n_ref]
+  float* cpart;                    // [kKnnCentreBlocks][KP] partial sums of the finite reference rows
+  int32_t* ccnt;                   // [kKnnCentreBlocks] their counts
+  float* centre;                   // [KP]
+  int32_t* part_idx;               // slices > 1: [slices][n_query][k] each
+  float* part_score;
+  int32_t* idx;                    // [n_query][k]
+  float* dist;                     // [n_query][k]
+};
+bool launch_knn(const KnnArgs& a, hipStream_t st);
 // rank.hip: for a list of cells sorted by row, the rank of each among its row's candidates under the order of
 // launch_topk (score descending, equal scores by ascending column), the number of candidates beside it, and its
 // score with the bits of launch_topk.  rank / cand / score are initialised here; a cell outside [0,B) x [0,D)

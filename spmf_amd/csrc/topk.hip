@@ -14,14 +14,10 @@
 //   topk_select_kernel : a workgroup owns 64 rows and sweeps 64-column blocks.  Per block the scores are
 //     formed like the statistics of waic_dense_kernel (score_block.h, shared with rank.hip): 32 x 32 wave
 //     tiles of <z, V'> on the exact-f32 matrix cores (v_mfma_f32_32x32x2_f32), double-buffered LDS operand
-//     tiles over (draw, K chunk), m_s added in draw order to 16 accumulators per lane.  Selection: LDS holds per row the k-th best
-//     candidate so far (score, column) and a buffer of CAP candidates.  A cell that beats its row's
-//     threshold -- and only such a cell looks up its bit -- is appended through an LDS counter; a row
-//     whose buffer is full is compacted to its best k by rank (every lane counts the entries that
-//     precede its own in the (score, column) order, which is strict since columns are distinct) and the
-//     threshold moves up.  Cells that found the buffer full try again behind the compaction if they still
-//     beat the new threshold.  What is dropped is never among the best k of what was seen, so the result
-//     is the exact top k under that order whatever the order of the appends: bit-reproducible.
+//     tiles over (draw, K chunk), m_s added in draw order to 16 accumulators per lane.  Selection
+//     (select_rows.h, shared with knn.hip): per row a threshold and a buffer of CAP candidates in LDS; a cell
+//     that beats its row's threshold -- and only such a cell looks up its bit -- is appended, a full row is
+//     compacted to its best k by rank: the exact top k whatever the order of the appends, bit-reproducible.
 //     After the first blocks a cell beats the threshold with probability ~ k / (columns seen).
 //   topk_merge_kernel  : with few row blocks the columns are split over gridDim.y slices (api.hip
 //     topk_slices), each writing its k per row; one wave per row ranks the slices' candidates.
@@ -35,46 +31,13 @@
 #include "common.h"
 #include "kernels.h"
 #include "score_block.h"
+#include "select_rows.h"
 
 namespace spmf {
 
 namespace {
 
 __device__ __forceinline__ bool precedes(float s, int c, float s2, int c2) { return score_precedes(s, c, s2, c2); }
-
-// One wave sorts the first n (<= CAP) candidates of a row by rank, keeps min(n, k) and, with k of them,
-// sets the row's threshold to the k-th.  Every lane reads all entries before any lane writes one.
-template <int CAP>
-__device__ __forceinline__ void compact_row(float* cs, int* cc, int n, int k, int lane, int* cnt, float* ts, int* tc) {
-  const bool h0 = lane < n, h1 = CAP > 64 && lane + 64 < n;
-  const float s0 = h0 ? cs[lane] : 0.f, s1 = h1 ? cs[lane + 64] : 0.f;
-  const int c0 = h0 ? cc[lane] : 0, c1 = h1 ? cc[lane + 64] : 0;
-  int r0 = 0, r1 = 0;
-  for (int j = 0; j < n; ++j) {
-    const float sj = cs[j];
-    const int cj = cc[j];
-    r0 += precedes(sj, cj, s0, c0) ? 1 : 0;
-    if (CAP > 64) r1 += precedes(sj, cj, s1, c1) ? 1 : 0;
-  }
-  __builtin_amdgcn_wave_barrier();
-  if (h0 && r0 < k) {
-    cs[r0] = s0;
-    cc[r0] = c0;
-    if (r0 == k - 1) {
-      *ts = s0;
-      *tc = c0;
-    }
-  }
-  if (h1 && r1 < k) {
-    cs[r1] = s1;
-    cc[r1] = c1;
-    if (r1 == k - 1) {
-      *ts = s1;
-      *tc = c1;
-    }
-  }
-  if (lane == 0) *cnt = n < k ? n : k;
-}
 
 }  // namespace
 
@@ -104,90 +67,24 @@ __global__ __launch_bounds__(256) void topk_select_kernel(int64_t B, int D, int 
                                                           int32_t* __restrict__ cols, float* __restrict__ scores) {
   constexpr int PITCH = KC + 4;
   __shared__ float tiles[2][2][64][PITCH];
-  __shared__ float cand_s[64][CAP];
-  __shared__ int cand_c[64][CAP];
-  __shared__ float thr_s[64];
-  __shared__ int thr_c[64];
-  __shared__ int cnt[64];
-  const int t = threadIdx.x;
-  const int lane = t & 63, wv = t >> 6;
-  const int i32 = lane & 31, h = lane >> 5;
-  const int wr = wv >> 1, wc = wv & 1;
+  SPMF_SELECT_ROWS_LDS(CAP, sel);
   const int64_t b0 = (int64_t)blockIdx.x * 64;
   const int CB = (D + 63) / 64;
   const int cb0 = blockIdx.y * cb_per_slice;
   const int cb1 = cb0 + cb_per_slice < CB ? cb0 + cb_per_slice : CB;
   const float inv_s = 1.f / (float)S;
-  if (t < 64) {
-    thr_s[t] = -INFINITY;
-    thr_c[t] = 0x7fffffff;
-    cnt[t] = 0;
-  }
-  __syncthreads();
-
+  // only a cell that beats its row's threshold looks up its bit
+  const auto not_stored = [=](int64_t b, int d) {
+    return !stored || !((stored[(size_t)b * W + (d >> 5)] >> (d & 31)) & 1u);
+  };
+  select_begin(sel);
   for (int cb = cb0; cb < cb1; ++cb) {
     const int d0 = cb * 64;
-    const int d = d0 + wc * 32 + i32;
     float sc[16];
     score_block<KC, LIK>(tiles, B, D, KP, S, b0, d0, z, Vp, phi, ctype, inv_s, sc);
-
-    // ---- selection: the lane's 16 cells are column d of 16 different rows
-    unsigned pend = 0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int rl = wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-      const int64_t b = b0 + rl;
-      const float v = sc[r];
-      bool in = b < B && d < D && isfinite(v) && precedes(v, d, thr_s[rl], thr_c[rl]);
-      if (in && stored) in = !((stored[(size_t)b * W + (d >> 5)] >> (d & 31)) & 1u);
-      pend |= in ? 1u << r : 0u;
-    }
-    while (true) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        if (pend >> r & 1u) {
-          const int rl = wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-          const int slot = atomicAdd(&cnt[rl], 1);
-          if (slot < CAP) {
-            cand_s[rl][slot] = sc[r];
-            cand_c[rl][slot] = d;
-            pend &= ~(1u << r);
-          }
-        }
-      }
-      __syncthreads();
-      for (int i = 0; i < 16; ++i) {        // wave wv keeps rows 16 wv .. 16 wv + 15
-        const int rl = wv * 16 + i;
-        const int n = cnt[rl];              // (wave-uniform)
-        if (n >= CAP) compact_row<CAP>(cand_s[rl], cand_c[rl], CAP, k, lane, &cnt[rl], &thr_s[rl], &thr_c[rl]);
-      }
-      // a cell is still pending only where its row was full, and that row now has CAP - k free slots
-      if (!__syncthreads_or(pend != 0)) break;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int rl = wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if ((pend >> r & 1u) && !precedes(sc[r], d, thr_s[rl], thr_c[rl])) pend &= ~(1u << r);
-      }
-    }
+    select_block(sel, sc, B, D, b0, d0, k, not_stored);
   }
-
-  // ---- the rows' best k, in order
-  for (int i = 0; i < 16; ++i) {
-    const int rl = wv * 16 + i;
-    const int n = cnt[rl];                  // (< CAP: a full row was compacted where it filled up)
-    if (n > 0) compact_row<CAP>(cand_s[rl], cand_c[rl], n, k, lane, &cnt[rl], &thr_s[rl], &thr_c[rl]);
-  }
-  __syncthreads();
-  for (int i = 0; i < 16; ++i) {
-    const int rl = wv * 16 + i;
-    const int64_t b = b0 + rl;
-    if (b < B && lane < k) {
-      const bool have = lane < cnt[rl];
-      const size_t o = ((size_t)blockIdx.y * B + b) * k + lane;
-      cols[o] = have ? cand_c[rl][lane] : -1;
-      scores[o] = have ? cand_s[rl][lane] : -INFINITY;
-    }
-  }
+  select_end(sel, B, b0, k, (int)blockIdx.y, cols, scores);
 }
 
 constexpr int kMergeMax = kTopkMaxSlices * kTopkMaxK;
@@ -261,6 +158,11 @@ void launch_topk_mark(int64_t B, int D, const int32_t* row_ptr, const int32_t* c
   hipLaunchKernelGGL(topk_mark_kernel, dim3(nb), dim3(256), 0, st, B, D, (D + 31) / 32, row_ptr, col, bits);
 }
 
+void launch_topk_merge(int64_t B, int k, int nsl, const int32_t* pc, const float* ps, int32_t* cols, float* scores,
+                       hipStream_t st) {
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)B), dim3(64), 0, st, B, k, nsl, pc, ps, cols, scores);
+}
+
 bool launch_topk(const TopkArgs& a, hipStream_t st) {
   const DrawTables& t = a.t;
   const int CB = (t.D + 63) / 64;
@@ -277,9 +179,7 @@ bool launch_topk(const TopkArgs& a, hipStream_t st) {
     default: ok = launch_select_kc<32>(a, cols, scores, st); break;
   }
   if (!ok) return false;
-  if (a.slices > 1)
-    hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)t.B), dim3(64), 0, st, t.B, a.k, a.slices, a.part_cols,
-                       a.part_scores, a.cols, a.scores);
+  if (a.slices > 1) launch_topk_merge(t.B, a.k, a.slices, a.part_cols, a.part_scores, a.cols, a.scores, st);
   return true;
 }
 

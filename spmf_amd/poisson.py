@@ -604,7 +604,7 @@ class PoissonFactorization:
                 "lppd": float(lppd_i.sum()), "pwaic": float(pwaic_i.sum())}
 
     def _draw_call(self, name, draws, nsamples, min_draws, dense_alternative):
-        """What the streaming calls (waic_streaming, top_k, score_cells, rank_cells) hand the library's draw stage:
+        """What the streaming calls (waic_streaming, top_k, score_cells, rank_cells, embed) hand the library's draw stage:
         ``(S, pin, eta_ptr, stream, KP, lib, h)``.  ``draws``: dict with 's','u','v','w' of shape [S,...]
         (None: ``surrogate_distribution.sample(nsamples)``), at least ``min_draws`` of them; ``pin`` is the
         C-ABI's twelve parameter slots and keeps the packed tensors it points into alive."""
@@ -887,6 +887,133 @@ class PoissonFactorization:
         del rank, cand, score, order
         out.update(_heldout.rank_summary(out["rank"], out["candidates"], ks))
         return out
+
+    def embed(self, data, nsamples=32, draws=None, sd=False, max_rows=None):
+        """The rows of ``data`` in the latent space, at any size: the posterior mean encoding
+        e_b = (1/S) sum_s z_sb, where z_sb is what ``encode(x, u_s, s_s)`` returns for draw s (the
+        draw stage's encode sweep; csrc/knn.hip reduces it over the draws, so [S,B,K] never leaves
+        the scratch).
+
+        ``data``, ``draws`` and ``max_rows`` as in ``waic_streaming`` (``draws`` may hold a single
+        draw); the rows of all batches are concatenated.  Returns {'mean': float32 [N, latent_dim]}
+        on the device and, with ``sd=True``, 'sd': the unbiased standard deviation over the draws
+        (at least two draws).  fp32: the sum in draw order times 1/S, Welford in draw order for the
+        deviation.  A row with a NaN count is NaN.  Bit-reproducible and independent of
+        ``max_rows``."""
+        S, pin, eta, stream, KP, lib, h = self._draw_call("embed", draws, nsamples, 2 if sd else 1, "encode")
+        K = self.latent_dim
+        scratch, means, sds = _Scratch(self.device), [], []
+        for n_rows, chunks in self._row_chunks(data, S * KP * 4, max_rows):
+            mean = torch.empty(n_rows, K, dtype=torch.float32, device=self.device)
+            dev = torch.empty(n_rows, K, dtype=torch.float32, device=self.device) if sd else None
+            for r0, sub in chunks:
+                _lib.check(h, lib.spmf_embed_rows(
+                    h, C.byref(sub), S, pin, eta, mean[r0:].data_ptr(),
+                    dev[r0:].data_ptr() if dev is not None else None,
+                    *scratch.fit(lib.spmf_embed_scratch_bytes(h, int(sub.n_rows), S)), stream),
+                    "spmf_embed_rows")
+            means.append(mean)
+            sds.append(dev)
+
+        def cat(parts):
+            if len(parts) == 1:
+                return parts[0]
+            return torch.cat(parts) if parts else torch.empty(0, K, dtype=torch.float32, device=self.device)
+        out = {"mean": cat(means)}
+        if sd:
+            out["sd"] = cat(sds)
+        return out
+
+    @staticmethod
+    def _knn_args(name, k, metric):
+        """k and the metric of ``knn`` / ``neighbors``, checked before any library call -> (k, flags)."""
+        from . import neighbors as _neighbors
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise ValueError(f"{name}: k must be an integer, got {k!r}")
+        if not 1 <= int(k) <= 64:
+            raise ValueError(f"{name} needs 1 <= k <= 64, got {k}")
+        if metric not in _neighbors.METRICS:
+            raise ValueError(f"{name}: metric must be one of {_neighbors.METRICS}, got {metric!r}")
+        return int(k), 1 if metric == "cosine" else 0
+
+    @staticmethod
+    def _knn_rows(name, what, t):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name}: {what} must be a torch tensor, got {type(t).__name__}")
+        if t.dim() != 2:
+            raise ValueError(f"{name}: {what} must be 2-D [rows, width], got shape {tuple(t.shape)}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name}: {what} must be float32, got {t.dtype}")
+        if not 1 <= t.shape[1] <= 256:
+            raise ValueError(f"{name}: the width of {what} must be in 1..256, got {t.shape[1]}")
+        return t
+
+    def knn(self, points, k=15, queries=None, metric="euclidean", include_self=False):
+        """The exact ``k`` nearest rows of ``points`` [Nr, Kx] for every row of ``queries`` [Nq, Kx]
+        (default: ``points`` itself), without an [Nq, Nr] array (csrc/knn.hip).  Both are float32
+        tensors on the model's device, 1 <= Kx <= 256 whatever the model's latent_dim, 1 <= k <= 64.
+        ``metric``: 'euclidean' or 'cosine' (the distance 1 - cos).  Without ``queries`` (or with
+        ``queries=points``) a row is no neighbour of its own unless ``include_self``.
+
+        Returns {'indices': int32 [Nq,k], 'distances': float32 [Nq,k]} on the device: distance
+        ascending, equal distances by ascending index, a query with fewer than k candidates padded
+        with -1 / +inf at the tail.  A non-finite row of ``points`` is nobody's neighbour; a non-finite
+        query (or a zero row under 'cosine') has none.  The selection runs on the matrix cores over
+        centred (or unit) rows; the reported distances are recomputed from the rows as given
+        (include/spmf_hip.h spmf_knn has the definition).  Bit-reproducible; a query's result does
+        not depend on the other queries.  ``spmf_amd.neighbors.to_csr`` turns the result into the
+        CSR arrays of a neighbour graph."""
+        k, flags = self._knn_args("knn", k, metric)
+        pts = self._knn_rows("knn", "points", points)
+        same = queries is None or queries is points or (
+            isinstance(queries, torch.Tensor) and queries.shape == points.shape and queries.dtype == points.dtype
+            and queries.device == points.device and queries.data_ptr() == points.data_ptr()
+            and queries.stride() == points.stride())
+        qry = pts if same else self._knn_rows("knn", "queries", queries)
+        if qry.shape[1] != pts.shape[1]:
+            raise ValueError(f"knn: queries have width {qry.shape[1]}, points {pts.shape[1]}")
+        if pts.shape[0] > 2 ** 31 - 1:
+            raise ValueError(f"knn: {pts.shape[0]} points are beyond the int32 index of the result")
+        dev = torch.device(self.device)
+        for what, t in (("points", pts), ("queries", qry)):
+            if t.device.type != "cuda" or (dev.index is not None and t.device != dev):
+                raise ValueError(f"knn: {what} must be on the model's device {self.device}, got {t.device}")
+        pts = pts.contiguous()
+        qry = pts if same else qry.contiguous()
+        nq, nr, width = int(qry.shape[0]), int(pts.shape[0]), int(pts.shape[1])
+        lib, h = _lib.load(), self._handle()
+        idx = torch.empty(nq, k, dtype=torch.int32, device=pts.device)
+        dist = torch.empty(nq, k, dtype=torch.float32, device=pts.device)
+        scratch = _Scratch(pts.device)
+        _lib.check(h, lib.spmf_knn(
+            h, qry.data_ptr(), nq, pts.data_ptr(), nr, width, k, flags, 0 if same and not include_self else -1,
+            idx.data_ptr(), dist.data_ptr(), *scratch.fit(lib.spmf_knn_scratch_bytes(h, nq, nr, width)),
+            torch.cuda.current_stream(pts.device).cuda_stream), "spmf_knn")
+        return {"indices": idx, "distances": dist}
+
+    def neighbors(self, data, k=15, query=None, metric="euclidean", include_self=False, nsamples=32, draws=None,
+                  max_rows=None):
+        """The neighbour graph of the rows of ``data`` in the model's latent space: ``embed`` on
+        ``data`` -- and on ``query``, when given, with the SAME draws -- then ``knn`` on the posterior
+        mean encodings.  Without ``query`` every row of ``data`` gets its k nearest other rows (itself
+        too with ``include_self``); with ``query`` every row of ``query`` gets its k nearest rows of
+        ``data``.  ``data`` / ``query``, ``nsamples`` / ``draws`` and ``max_rows`` as in ``embed``;
+        ``k`` and ``metric`` as in ``knn``.
+
+        Returns {'indices': int32 [Nq,k], 'distances': float32 [Nq,k]} on the device, bit for bit
+        ``knn(embed(data, draws=draws)["mean"], k, ...)``."""
+        self._knn_args("neighbors", k, metric)
+        if not 1 <= self.latent_dim <= 256:
+            raise ValueError(f"neighbors: latent_dim {self.latent_dim} is beyond the 256 columns of knn")
+        if draws is None and self._custom_codec is None:
+            if int(nsamples) < 1:
+                raise ValueError("neighbors needs nsamples >= 1")
+            draws = self.surrogate_distribution.sample(int(nsamples))      # once: data and query share them
+        ref = self.embed(data, nsamples=nsamples, draws=draws, max_rows=max_rows)["mean"]
+        if query is None:
+            return self.knn(ref, k=k, metric=metric, include_self=include_self)
+        qry = self.embed(query, nsamples=nsamples, draws=draws, max_rows=max_rows)["mean"]
+        return self.knn(ref, k=k, queries=qry, metric=metric, include_self=True)
 
     def _nonfinite_scan(self, sc, cs, data, S, P, max_cells=1 << 27):
         """Dense part of the replacement rule (poisson.py:606-616): the minimum

@@ -1,6 +1,6 @@
 """Do two builds of the library return the same bits from the streaming calls?
 
-    stream_bits.py dump FILE          run top_k, score_cells and waic_streaming at four small cases with the
+    stream_bits.py dump FILE          run top_k, score_cells, rank_cells and waic_streaming at four small cases with the
                                       library that SPMF_LIB_PATH names (default: the tree's own) and save every
                                       output to FILE
     stream_bits.py compare A B [OUT]  compare two dumps tensor by tensor with torch.equal -> one JSON line,
@@ -9,12 +9,13 @@
 The cases are problems of tests/_stream_cases.py, (likelihood, B, D, K, S): poisson (131, 197, 16, 7), mixed
 (65, 130, 40, 3), bernoulli_log (70, 150, 3, 2) and poisson (40, 70, 128, 3), i.e. KP 16, 64, 4 and 128.
 top_k: k = 10 and 64, stored cells excluded and not, columns and scores.  score_cells: every cell listed in a
-seeded random order with values 0 .. 3: mean and lppd.  waic_streaming (row scores included) is called
+seeded random order with values 0 .. 3: mean and lppd.  rank_cells: the same list, stored cells excluded: rank,
+candidates and score.  waic_streaming (row scores included) is called
 TWICE in each dump: its fp64 sums are atomics, so `compare` also reports whether the two calls of one build
 agree, which is the bar a comparison across builds has to be read against.
 
 A dump is made in a process of its own per build (a library is loaded once per process); a build from before
-rank_cells lacks its two entry points, which nothing here calls."""
+embed / knn lacks their entry points, which nothing here calls."""
 import ctypes as C
 import json
 import os
@@ -53,6 +54,9 @@ def dump(path):
         sc = m.score_cells(batch, cell // D, cell % D, values=(cell % 4).astype(np.float32), draws=params)
         out[f"score_cells/{tag}/mean"] = sc["mean"].cpu()
         out[f"score_cells/{tag}/lppd"] = sc["lppd"].cpu()
+        rk = m.rank_cells(batch, cell // D, cell % D, draws=params)
+        for name in ("rank", "candidates", "score"):
+            out[f"rank_cells/{tag}/{name}"] = rk[name].cpu()
         for call in (0, 1):
             w = m.waic_streaming(batch, draws=params, row_scores=True)
             for name, v in w.items():
@@ -74,7 +78,7 @@ def compare(a_path, b_path, out_path=None):
     keys = sorted(k for k in a if torch.is_tensor(a[k]))
     assert keys == sorted(k for k in b if torch.is_tensor(b[k])), "the two dumps hold different outputs"
     res = {"a": a["lib"], "b": b["lib"], "device": a["device"], "cases": ["%s %dx%d K=%d S=%d" % c for c in CASES]}
-    for call in ("top_k", "score_cells"):
+    for call in ("top_k", "score_cells", "rank_cells"):
         mine = [k for k in keys if k.startswith(call + "/")]
         differ = [k for k in mine if not torch.equal(_bits(a[k]), _bits(b[k]))]
         res[call] = {"tensors": len(mine), "equal": len(mine) - len(differ), "differ": differ}
@@ -99,7 +103,7 @@ def compare(a_path, b_path, out_path=None):
         os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
         with open(out_path, "w") as f:
             f.write(line + "\n")
-    return 0 if not res["top_k"]["differ"] and not res["score_cells"]["differ"] else 1
+    return 0 if not any(res[c]["differ"] for c in ("top_k", "score_cells", "rank_cells")) else 1
 
 
 if __name__ == "__main__":
