@@ -1284,17 +1284,22 @@ static int topk_slices(int64_t n_rows, int D, int cus) {
   const int64_t per = (cb + nsl - 1) / nsl;
   return (int)((cb + per - 1) / per);
 }
+// the bitmap of the stored cells of `rows` rows, a bit per column in 32-bit words (topk_mark_kernel)
+static size_t stored_bits_bytes(const spmf_ctx* c, int64_t rows) {
+  return (size_t)rows * ((c->D + 31) / 32) * sizeof(uint32_t);
+}
 // Scratch of one call: the draw carve, the bitmap of the stored cells and the slices' results
 // (sized for k = kTopkMaxK: the size does not depend on the call's k or flags)
 struct TopkCarve {
-  size_t bits, pcols, pscores, total;
+  size_t bits, bits_end, pcols, pscores, total;   // bits_end: the carve without the slices' results (rank_cells)
   int slices;
 };
 static TopkCarve topk_carve(const spmf_ctx* c, int64_t rows, int S) {
   TopkCarve k;
   k.slices = topk_slices(rows, c->D, device_cus(c));
   size_t o = draw_carve(c, rows, S).total;
-  k.bits = o;    o += al((size_t)rows * ((c->D + 31) / 32) * sizeof(uint32_t));
+  k.bits = o;    o += al(stored_bits_bytes(c, rows));
+  k.bits_end = o;
   const size_t part = k.slices > 1 ? (size_t)k.slices * rows * kTopkMaxK : 0;
   k.pcols = o;   o += al(part * sizeof(int32_t));
   k.pscores = o; o += al(part * sizeof(float));
@@ -1324,7 +1329,7 @@ int spmf_topk_rows(spmf_ctx* c, const spmf_counts* ct, int S, const float* const
   ta.row_ptr = ct->row_ptr; ta.col = ct->col_idx;
   if (flags & 1u) {
     ta.stored = (uint32_t*)(base + tc.bits);
-    HIPCHK(c, hipMemsetAsync(ta.stored, 0, (size_t)ct->n_rows * ((c->D + 31) / 32) * sizeof(uint32_t), st));
+    HIPCHK(c, hipMemsetAsync(ta.stored, 0, stored_bits_bytes(c, ct->n_rows), st));
   }
   ta.part_cols = (int32_t*)(base + tc.pcols); ta.part_scores = (float*)(base + tc.pscores);
   ta.cols = cols_out; ta.scores = score_out;
@@ -1365,21 +1370,10 @@ int spmf_score_cells(spmf_ctx* c, const spmf_counts* ct, int S, const float* con
 
 // ---- rank of listed cells among their row's candidates (rank.hip) ------------------------------
 // Scratch of one call: the draw carve and the bitmap of the stored cells (the size does not depend on the flags);
-// the kernel keeps everything else in LDS and in the caller's outputs.
-struct RankCarve {
-  size_t bits, total;
-};
-static RankCarve rank_carve(const spmf_ctx* c, int64_t rows, int S) {
-  RankCarve k;
-  size_t o = draw_carve(c, rows, S).total;
-  k.bits = o;  o += al((size_t)rows * ((c->D + 31) / 32) * sizeof(uint32_t));
-  k.total = o;
-  return k;
-}
-
+// the kernel keeps everything else in LDS and in the caller's outputs.  That is topk_carve up to the slices' results.
 size_t spmf_rank_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S) {
   if (!c || n_rows < 0 || S < 1) return 0;
-  return rank_carve(c, n_rows, S).total;
+  return topk_carve(c, n_rows, S).bits_end;
 }
 
 int spmf_rank_cells(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS], const float* eta,
@@ -1396,11 +1390,12 @@ int spmf_rank_cells(spmf_ctx* c, const spmf_counts* ct, int S, const float* cons
   RankArgs ra{};
   rc = draw_stage(c, "rank_cells", ct, S, params, eta, scratch, st, ra.t);
   if (rc) return rc;
-  ra.nnz = ct->nnz; ra.slices = topk_slices(ct->n_rows, c->D, device_cus(c));
+  const TopkCarve tc = topk_carve(c, ct->n_rows, S);
+  ra.nnz = ct->nnz; ra.slices = tc.slices;
   ra.row_ptr = ct->row_ptr; ra.col = ct->col_idx;
   if (flags & 1u) {
-    ra.stored = (uint32_t*)((char*)scratch + rank_carve(c, ct->n_rows, S).bits);
-    HIPCHK(c, hipMemsetAsync(ra.stored, 0, (size_t)ct->n_rows * ((c->D + 31) / 32) * sizeof(uint32_t), st));
+    ra.stored = (uint32_t*)((char*)scratch + tc.bits);
+    HIPCHK(c, hipMemsetAsync(ra.stored, 0, stored_bits_bytes(c, ct->n_rows), st));
   }
   ra.n_cells = n_cells; ra.cell_row = cell_row; ra.cell_col = cell_col;
   ra.rank = rank_out; ra.cand = cand_out; ra.score = score_out;

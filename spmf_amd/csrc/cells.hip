@@ -120,21 +120,10 @@ bool launch_cells(const CellsArgs& a, hipStream_t st) {
   const int64_t per_block = 4 * kCellsPerWave;
   const int64_t nb = (a.n_cells + per_block - 1) / per_block;
   if (nb > 0x7fffffff) return false;
-#define SPMF_CELLS(G_)                                                                                       \
-  hipLaunchKernelGGL((cells_kernel<G_>), dim3((unsigned)nb), dim3(256), 0, st, a.n_cells, t.B, t.D, t.S, t.lik, \
-                     a.row, a.col, a.val, t.z, t.Vp, t.phi, t.ctype, a.mean, a.lppd)
-  switch (t.KP) {
-    case 4: SPMF_CELLS(1); break;
-    case 8: SPMF_CELLS(2); break;
-    case 16: SPMF_CELLS(4); break;
-    case 32: SPMF_CELLS(8); break;
-    case 64: SPMF_CELLS(16); break;
-    case 128: SPMF_CELLS(32); break;
-    case 256: SPMF_CELLS(64); break;
-    default: return false;
-  }
-#undef SPMF_CELLS
-  return true;
+  return with_kp<256>(t.KP, [&](auto kp) {
+    hipLaunchKernelGGL((cells_kernel<decltype(kp)::value / 4>), dim3((unsigned)nb), dim3(256), 0, st, a.n_cells, t.B,
+                       t.D, t.S, t.lik, a.row, a.col, a.val, t.z, t.Vp, t.phi, t.ctype, a.mean, a.lppd);
+  });
 }
 
 }  // namespace spmf

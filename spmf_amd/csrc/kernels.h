@@ -19,6 +19,30 @@ inline bool with_kp(int KP, F&& f) {
   return false;
 }
 
+// The streaming kernels' K chunk, the floats of the K axis per LDS tile (score_block.h): calls f with KC as a
+// std::integral_constant for KP = 4, 8, .., 256.  false: KP is not one of them (f is not called).
+template <class F>
+inline bool with_kc(int KP, F&& f) {
+  switch (KP) {
+    case 4: case 8: f(std::integral_constant<int, 8>{}); return true;
+    case 16: f(std::integral_constant<int, 16>{}); return true;
+    case 32: case 64: case 128: case 256: f(std::integral_constant<int, 32>{}); return true;
+    default: return false;
+  }
+}
+
+// The likelihood codes 0 .. 4 (common.h): calls f with the code as a std::integral_constant.  false: lik is
+// none of them (f is not called).
+template <int LIK = 0, class F>
+inline bool with_lik(int lik, F&& f) {
+  if (lik == LIK) {
+    f(std::integral_constant<int, LIK>{});
+    return true;
+  }
+  if constexpr (LIK < 4) return with_lik<LIK + 1>(lik, f);
+  return false;
+}
+
 struct PrepArgs {
   int D, K;
   const float *u, *v, *w, *s, *eta;

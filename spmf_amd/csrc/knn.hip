@@ -14,7 +14,8 @@
 //     The selection is select_rows.h, shared with topk.hip; the candidate test is "not the query itself".  With
 //     few queries the reference blocks split over gridDim.y slices and topk.hip's merge kernel ranks them.
 //     TILE = 1 (KP <= 64) keeps the 64 x KP query tile in LDS for the whole sweep and double-buffers only the
-//     reference tile, across block boundaries too; it issues score_block's MFMA sequence: the same bits.
+//     reference tile, across block boundaries too; its loop is its own, the MFMA step per 8 floats of K is the
+//     tile loop's (score_mfma8): the same bits.
 //   knn_refine_kernel  : a wave per query recomputes the distances of the k selected rows from the caller's rows
 //     (Euclidean: sqrt of the fmaf chain of squared differences in ascending k; cosine: half that chain over the
 //     unit rows) and orders them by (distance ascending, index ascending).  The expansion above only ever
@@ -171,9 +172,8 @@ __global__ __launch_bounds__(256) void knn_select_kernel(int64_t NQ, int NR, int
                                                          float* __restrict__ score) {
   SPMF_SELECT_ROWS_LDS(CAP, sel);
   const int64_t b0 = (int64_t)blockIdx.x * 64;
-  const int CB = (int)(((int64_t)NR + 63) / 64);
-  const int cb0 = blockIdx.y * cb_per_slice;
-  const int cb1 = cb0 + cb_per_slice < CB ? cb0 + cb_per_slice : CB;
+  int cb0, cb1;
+  slice_blocks((int64_t)NR, cb_per_slice, cb0, cb1);
   const auto not_self = [=](int64_t b, int d) { return self_off < 0 || (int64_t)d != self_off + b; };
   if constexpr (TILE == 0) {
     __shared__ float tiles[2][2][64][KC + 4];
@@ -243,14 +243,7 @@ __global__ __launch_bounds__(256) void knn_select_kernel(int64_t NQ, int NR, int
       const float* ar = &qt[wr * 32 + i32][ch * KC + 4 * h];
       const float* br = &rt[buf][wc * 32 + i32][4 * h];
 #pragma unroll
-      for (int qk = 0; qk < KC / 8; ++qk) {
-        const float4 a = *reinterpret_cast<const float4*>(ar + 8 * qk);
-        const float4 b = *reinterpret_cast<const float4*>(br + 8 * qk);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
-      }
+      for (int qk = 0; qk < KC / 8; ++qk) score_mfma8(ar + 8 * qk, br + 8 * qk, acc);
       if (it + 1 < NIT) stash(buf ^ 1, pre);
       __syncthreads();
       if (ch == NCH - 1) {
@@ -312,61 +305,50 @@ __global__ __launch_bounds__(256) void knn_pad_kernel(int64_t n, int32_t* __rest
 
 template <int KC, int CAP, int TILE>
 static void launch_select(const KnnArgs& a, int32_t* idx, float* score, hipStream_t st) {
-  const int64_t CB = (a.n_ref + 63) / 64;
-  const int per = (int)((CB + a.slices - 1) / a.slices);
-  const dim3 grid((unsigned)((a.n_query + 63) / 64), (unsigned)a.slices);
-  hipLaunchKernelGGL((knn_select_kernel<KC, CAP, TILE>), grid, dim3(256), 0, st, a.n_query, (int)a.n_ref, a.KP, a.k, per,
-                     a.self_offset, a.qw, a.rw, a.bias, idx, score);
-}
-
-template <int KC>
-static void launch_select_kc(const KnnArgs& a, int32_t* idx, float* score, hipStream_t st) {
-  const bool wide = a.k > 16;
-  if (a.tile == 1 && a.KP <= 64) {
-    if (wide) launch_select<KC, 80, 1>(a, idx, score, st);
-    else launch_select<KC, 32, 1>(a, idx, score, st);
-  } else {
-    if (wide) launch_select<KC, 80, 0>(a, idx, score, st);
-    else launch_select<KC, 32, 0>(a, idx, score, st);
-  }
+  const SliceGeom g(a.n_ref, a.slices);
+  hipLaunchKernelGGL((knn_select_kernel<KC, CAP, TILE>), g.grid(a.n_query), dim3(256), 0, st, a.n_query, (int)a.n_ref,
+                     a.KP, a.k, g.per, a.self_offset, a.qw, a.rw, a.bias, idx, score);
 }
 
 bool launch_knn(const KnnArgs& a, hipStream_t st) {
-  const int64_t CB = (a.n_ref + 63) / 64;
   if (a.k < 1 || a.k > kTopkMaxK || a.row_len < 1 || a.row_len > a.KP) return false;
-  if (a.KP != 4 && a.KP != 8 && a.KP != 16 && a.KP != 32 && a.KP != 64 && a.KP != 128 && a.KP != 256) return false;
-  if (a.n_ref > 0 && (a.slices < 1 || a.slices > kTopkMaxSlices || a.slices > CB)) return false;
-  if (a.n_query <= 0) return true;
-  if (a.n_ref <= 0) {
-    const int64_t n = a.n_query * a.k;
-    hipLaunchKernelGGL(knn_pad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, a.idx, a.dist);
-    return true;
-  }
-  if (!a.cosine) {
-    int64_t nb = (a.n_ref + 255) / 256;
-    if (nb > kKnnCentreBlocks) nb = kKnnCentreBlocks;
-    const int64_t per = (a.n_ref + nb - 1) / nb;
-    nb = (a.n_ref + per - 1) / per;
-    hipLaunchKernelGGL(knn_centre_kernel, dim3((unsigned)nb), dim3(256), 0, st, a.n_ref, a.row_len, a.KP, per, a.r,
-                       a.cpart, a.ccnt);
-    hipLaunchKernelGGL(knn_centre_finish_kernel, dim3(1), dim3(256), 0, st, (int)nb, a.KP, a.cpart, a.ccnt, a.centre);
-  }
-  hipLaunchKernelGGL(knn_prepare_kernel, dim3((unsigned)((a.n_ref + 3) / 4)), dim3(256), 0, st, a.n_ref, a.row_len, a.KP,
-                     a.cosine ? 1 : 0, a.r, a.centre, a.rw, a.bias);
-  if (a.qw != a.rw)
-    hipLaunchKernelGGL(knn_prepare_kernel, dim3((unsigned)((a.n_query + 3) / 4)), dim3(256), 0, st, a.n_query, a.row_len,
-                       a.KP, a.cosine ? 1 : 0, a.q, a.centre, a.qw, (float*)nullptr);
-  int32_t* idx = a.slices > 1 ? a.part_idx : a.idx;
-  float* score = a.slices > 1 ? a.part_score : a.dist;
-  switch (a.KP) {
-    case 4: case 8: launch_select_kc<8>(a, idx, score, st); break;
-    case 16: launch_select_kc<16>(a, idx, score, st); break;
-    default: launch_select_kc<32>(a, idx, score, st); break;
-  }
-  if (a.slices > 1) launch_topk_merge(a.n_query, a.k, a.slices, a.part_idx, a.part_score, a.idx, a.dist, st);
-  hipLaunchKernelGGL(knn_refine_kernel, dim3((unsigned)((a.n_query + 3) / 4)), dim3(256), 0, st, a.n_query, a.row_len, a.KP,
-                     a.k, a.cosine ? 1 : 0, a.q, a.r, a.qw, a.rw, a.idx, a.dist);
-  return true;
+  if (a.n_ref > 0 && (a.slices < 1 || a.slices > kTopkMaxSlices || a.slices > SliceGeom(a.n_ref, a.slices).CB)) return false;
+  return with_kc(a.KP, [&](auto kc) {
+    constexpr int KC = decltype(kc)::value;
+    if (a.n_query <= 0) return;
+    if (a.n_ref <= 0) {
+      const int64_t n = a.n_query * a.k;
+      hipLaunchKernelGGL(knn_pad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, a.idx, a.dist);
+      return;
+    }
+    if (!a.cosine) {
+      int64_t nb = (a.n_ref + 255) / 256;
+      if (nb > kKnnCentreBlocks) nb = kKnnCentreBlocks;
+      const int64_t per = (a.n_ref + nb - 1) / nb;
+      nb = (a.n_ref + per - 1) / per;
+      hipLaunchKernelGGL(knn_centre_kernel, dim3((unsigned)nb), dim3(256), 0, st, a.n_ref, a.row_len, a.KP, per, a.r,
+                         a.cpart, a.ccnt);
+      hipLaunchKernelGGL(knn_centre_finish_kernel, dim3(1), dim3(256), 0, st, (int)nb, a.KP, a.cpart, a.ccnt, a.centre);
+    }
+    hipLaunchKernelGGL(knn_prepare_kernel, dim3((unsigned)((a.n_ref + 3) / 4)), dim3(256), 0, st, a.n_ref, a.row_len,
+                       a.KP, a.cosine ? 1 : 0, a.r, a.centre, a.rw, a.bias);
+    if (a.qw != a.rw)
+      hipLaunchKernelGGL(knn_prepare_kernel, dim3((unsigned)((a.n_query + 3) / 4)), dim3(256), 0, st, a.n_query,
+                         a.row_len, a.KP, a.cosine ? 1 : 0, a.q, a.centre, a.qw, (float*)nullptr);
+    int32_t* idx = a.slices > 1 ? a.part_idx : a.idx;
+    float* score = a.slices > 1 ? a.part_score : a.dist;
+    const bool wide = a.k > 16;
+    if (a.tile == 1 && a.KP <= 64) {
+      if (wide) launch_select<KC, 80, 1>(a, idx, score, st);
+      else launch_select<KC, 32, 1>(a, idx, score, st);
+    } else {
+      if (wide) launch_select<KC, 80, 0>(a, idx, score, st);
+      else launch_select<KC, 32, 0>(a, idx, score, st);
+    }
+    if (a.slices > 1) launch_topk_merge(a.n_query, a.k, a.slices, a.part_idx, a.part_score, a.idx, a.dist, st);
+    hipLaunchKernelGGL(knn_refine_kernel, dim3((unsigned)((a.n_query + 3) / 4)), dim3(256), 0, st, a.n_query, a.row_len,
+                       a.KP, a.k, a.cosine ? 1 : 0, a.q, a.r, a.qw, a.rw, a.idx, a.dist);
+  });
 }
 
 }  // namespace spmf

@@ -2,7 +2,8 @@
 // [B,D] array.
 //
 // Score, order and candidates are those of topk.hip: score_bd = the fp32 mean over the draws of the rate
-// (Poisson column) or sigmoid(logit) (Bernoulli column), formed by score_block.h; (score descending, column
+// (Poisson column) or sigmoid(logit) (Bernoulli column), formed by score_block (score_block.h, which also holds
+// the slice geometry and the bitmap lookup of the two kernels); (score descending, column
 // ascending); a candidate of row b is a column with a finite score that the batch does not store (when stored
 // cells are excluded).  For a listed cell i = (b, d):
 //   score_i = score_bd, with the bits the select kernel gives that cell,
@@ -80,8 +81,7 @@ __global__ __launch_bounds__(256) void rank_kernel(int64_t B, int D, int KP, int
                                                    const int32_t* __restrict__ cell_row,
                                                    const int32_t* __restrict__ cell_col, int32_t* __restrict__ rank_out,
                                                    int32_t* __restrict__ cand_out, float* __restrict__ score_out) {
-  constexpr int PITCH = KC + 4;
-  __shared__ float tiles[2][2][64][PITCH];
+  __shared__ float tiles[2][2][64][KC + 4];
   __shared__ float bs[64][64];          // phase 1: the scores of one block
   __shared__ Target tg[64][T];
   __shared__ int64_t rstart[65];        // first listed cell of row b0 + t (t = 64: one past the block's last)
@@ -96,8 +96,8 @@ __global__ __launch_bounds__(256) void rank_kernel(int64_t B, int D, int KP, int
   const int wr = wv >> 1, wc = wv & 1;
   const int64_t b0 = (int64_t)blockIdx.x * 64;
   const int CB = (D + 63) / 64;
-  const int cb0 = blockIdx.y * cb_per_slice;
-  const int cb1 = cb0 + cb_per_slice < CB ? cb0 + cb_per_slice : CB;
+  int cb0, cb1;
+  slice_blocks(D, cb_per_slice, cb0, cb1);
   const float inv_s = 1.f / (float)S;
   const bool first_slice = blockIdx.y == 0;
 
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256) void rank_kernel(int64_t B, int D, int KP, int
             score_out[idx] = v;
             if (!fin) {
               atomicAdd(&rank_out[idx], -1);
-            } else if (!stored || !((stored[(size_t)(b0 + rl) * W + (c >> 5)] >> (c & 31)) & 1u)) {
+            } else if (not_stored(stored, W, b0 + rl, c)) {
               atomicAdd(&cand_out[idx], -1);     // a candidate itself: not among the candidates beside it
             }
           }
@@ -200,8 +200,7 @@ __global__ __launch_bounds__(256) void rank_kernel(int64_t B, int D, int KP, int
         const int n = ntr[rl];                       // (wave-uniform)
         const int64_t b = b0 + rl;
         const float v = bs[rl][lane];
-        bool is_cand = b < B && d < D && isfinite(v);
-        if (is_cand && stored) is_cand = !((stored[(size_t)b * W + (d >> 5)] >> (d & 31)) & 1u);
+        const bool is_cand = b < B && d < D && isfinite(v) && not_stored(stored, W, b, d);
         const int pc = __popcll(__ballot(is_cand));
         if (pc == 0) continue;
         if (lane == 0) rowcand[rl] += pc;
@@ -231,43 +230,24 @@ __global__ __launch_bounds__(256) void rank_kernel(int64_t B, int D, int KP, int
   }
 }
 
-template <int KC>
-static bool launch_rank_kc(const RankArgs& a, hipStream_t st) {
-  const DrawTables& t = a.t;
-  const int CB = (t.D + 63) / 64;
-  const int per = (CB + a.slices - 1) / a.slices;
-  const dim3 grid((unsigned)((t.B + 63) / 64), (unsigned)a.slices);
-  const int W = (t.D + 31) / 32;
-#define SPMF_RANK(L_)                                                                                          \
-  hipLaunchKernelGGL((rank_kernel<KC, L_>), grid, dim3(256), 0, st, t.B, t.D, t.KP, t.S, per, W, t.z, t.Vp, t.phi, \
-                     t.ctype, a.stored, a.n_cells, a.cell_row, a.cell_col, a.rank, a.cand, a.score)
-  switch (t.lik) {
-    case 0: SPMF_RANK(0); break;
-    case 1: SPMF_RANK(1); break;
-    case 2: SPMF_RANK(2); break;
-    case 3: SPMF_RANK(3); break;
-    case 4: SPMF_RANK(4); break;
-    default: return false;
-  }
-#undef SPMF_RANK
-  return true;
-}
-
 bool launch_rank(const RankArgs& a, hipStream_t st) {
   const DrawTables& t = a.t;
-  const int CB = (t.D + 63) / 64;
-  if (a.n_cells < 1 || t.B < 1 || a.slices < 1 || a.slices > kTopkMaxSlices || a.slices > CB) return false;
-  if (t.KP != 4 && t.KP != 8 && t.KP != 16 && t.KP != 32 && t.KP != 64 && t.KP != 128 && t.KP != 256) return false;
-  if (t.lik < 0 || t.lik > 4) return false;
-  if (a.stored && a.nnz > 0) launch_topk_mark(t.B, t.D, a.row_ptr, a.col, a.stored, st);
-  const int64_t want = (a.n_cells + 255) / 256;
-  hipLaunchKernelGGL(rank_init_kernel, dim3((unsigned)(want > 4096 ? 4096 : want)), dim3(256), 0, st, a.n_cells, t.B,
-                     t.D, a.cell_row, a.cell_col, a.rank, a.cand, a.score);
-  switch (t.KP) {
-    case 4: case 8: return launch_rank_kc<8>(a, st);
-    case 16: return launch_rank_kc<16>(a, st);
-    default: return launch_rank_kc<32>(a, st);
-  }
+  if (a.n_cells < 1 || t.B < 1 || a.slices < 1 || a.slices > kTopkMaxSlices) return false;
+  const SliceGeom g(t.D, a.slices);
+  if (a.slices > g.CB) return false;
+  bool ok = false;
+  with_kc(t.KP, [&](auto kc) {
+    ok = with_lik(t.lik, [&](auto lik) {
+      if (a.stored && a.nnz > 0) launch_topk_mark(t.B, t.D, a.row_ptr, a.col, a.stored, st);
+      const int64_t want = (a.n_cells + 255) / 256;
+      hipLaunchKernelGGL(rank_init_kernel, dim3((unsigned)(want > 4096 ? 4096 : want)), dim3(256), 0, st, a.n_cells,
+                         t.B, t.D, a.cell_row, a.cell_col, a.rank, a.cand, a.score);
+      hipLaunchKernelGGL((rank_kernel<decltype(kc)::value, decltype(lik)::value>), g.grid(t.B), dim3(256), 0, st, t.B,
+                         t.D, t.KP, t.S, g.per, g.W, t.z, t.Vp, t.phi, t.ctype, a.stored, a.n_cells, a.cell_row,
+                         a.cell_col, a.rank, a.cand, a.score);
+    });
+  });
+  return ok;
 }
 
 }  // namespace spmf

@@ -11,10 +11,10 @@
 //   topk_mark_kernel   : (stored cells excluded) one wave per row ORs a bit per CSR entry into a zeroed
 //     bitmap [B][ceil(D/32)]: CSR columns are not sorted inside a row, so a block of cells cannot find
 //     its stored entries by search.
-//   topk_select_kernel : a workgroup owns 64 rows and sweeps 64-column blocks.  Per block the scores are
-//     formed like the statistics of waic_dense_kernel (score_block.h, shared with rank.hip): 32 x 32 wave
-//     tiles of <z, V'> on the exact-f32 matrix cores (v_mfma_f32_32x32x2_f32), double-buffered LDS operand
-//     tiles over (draw, K chunk), m_s added in draw order to 16 accumulators per lane.  Selection
+//   topk_select_kernel : a workgroup owns 64 rows and sweeps the 64-column blocks of its slice.  Per block the
+//     scores are formed by score_block (score_block.h: the tile loop that waic.hip, rank.hip and knn.hip run
+//     too): 32 x 32 wave tiles of <z, V'> on the exact-f32 matrix cores (v_mfma_f32_32x32x2_f32),
+//     double-buffered LDS operand tiles over (draw, K chunk), m_s added in draw order to 16 sums per lane.  Selection
 //     (select_rows.h, shared with knn.hip): per row a threshold and a buffer of CAP candidates in LDS; a cell
 //     that beats its row's threshold -- and only such a cell looks up its bit -- is appended, a full row is
 //     compacted to its best k by rank: the exact top k whatever the order of the appends, bit-reproducible.
@@ -25,8 +25,9 @@
 // LDS and occupancy (160 KiB per CU): operand tiles 2 x 2 x 64 x (KC+4) floats = 36 864 B at KC = 32,
 // thresholds and counters 768 B, candidates 64 x CAP x 8 B.  CAP = 32 (k <= 16): 54 272 B with alignment,
 // CAP = 80 (k <= 64): 78 848 B: two workgroups fit at the widest buffer, three at the narrow one.  The
-// registers set the occupancy reached: 171 .. 202 VGPRs + 16 AGPRs at KC = 32, no spills, which is two
-// waves per SIMD = two workgroups (8 waves) per CU for every k (three at KC = 8 / 16 on the Poisson codes).
+// registers set the occupancy reached: 171 .. 220 VGPRs + 16 AGPRs at KC = 32, no spills, which is two
+// waves per SIMD = two workgroups (8 waves) per CU for every k (three at KC = 8 / 16, k <= 16 on the Poisson
+// and mixed codes).
 // All arithmetic is fp32 FMA.
 #include "common.h"
 #include "kernels.h"
@@ -34,12 +35,6 @@
 #include "select_rows.h"
 
 namespace spmf {
-
-namespace {
-
-__device__ __forceinline__ bool precedes(float s, int c, float s2, int c2) { return score_precedes(s, c, s2, c2); }
-
-}  // namespace
 
 // one wave per row: a bit per stored cell
 __global__ __launch_bounds__(256) void topk_mark_kernel(int64_t B, int D, int W, const int32_t* __restrict__ row_ptr,
@@ -65,24 +60,20 @@ __global__ __launch_bounds__(256) void topk_select_kernel(int64_t B, int D, int 
                                                           const uint8_t* __restrict__ ctype,
                                                           const uint32_t* __restrict__ stored,
                                                           int32_t* __restrict__ cols, float* __restrict__ scores) {
-  constexpr int PITCH = KC + 4;
-  __shared__ float tiles[2][2][64][PITCH];
+  __shared__ float tiles[2][2][64][KC + 4];
   SPMF_SELECT_ROWS_LDS(CAP, sel);
   const int64_t b0 = (int64_t)blockIdx.x * 64;
-  const int CB = (D + 63) / 64;
-  const int cb0 = blockIdx.y * cb_per_slice;
-  const int cb1 = cb0 + cb_per_slice < CB ? cb0 + cb_per_slice : CB;
+  int cb0, cb1;
+  slice_blocks(D, cb_per_slice, cb0, cb1);
   const float inv_s = 1.f / (float)S;
   // only a cell that beats its row's threshold looks up its bit
-  const auto not_stored = [=](int64_t b, int d) {
-    return !stored || !((stored[(size_t)b * W + (d >> 5)] >> (d & 31)) & 1u);
-  };
+  const auto cand = [=](int64_t b, int d) { return not_stored(stored, W, b, d); };
   select_begin(sel);
   for (int cb = cb0; cb < cb1; ++cb) {
     const int d0 = cb * 64;
     float sc[16];
     score_block<KC, LIK>(tiles, B, D, KP, S, b0, d0, z, Vp, phi, ctype, inv_s, sc);
-    select_block(sel, sc, B, D, b0, d0, k, not_stored);
+    select_block(sel, sc, B, D, b0, d0, k, cand);
   }
   select_end(sel, B, b0, k, (int)blockIdx.y, cols, scores);
 }
@@ -111,7 +102,7 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(int64_t B, int k, int ns
     const float si = s[i];
     ++nv;
     int rank = 0;
-    for (int j = 0; j < n; ++j) rank += (c[j] >= 0 && precedes(s[j], c[j], si, ci)) ? 1 : 0;
+    for (int j = 0; j < n; ++j) rank += (c[j] >= 0 && score_precedes(s[j], c[j], si, ci)) ? 1 : 0;
     if (rank < k) {
       cols[(size_t)b * k + rank] = ci;
       scores[(size_t)b * k + rank] = si;
@@ -125,37 +116,17 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(int64_t B, int k, int ns
   }
 }
 
-template <int KC, int CAP>
-static bool launch_select(const TopkArgs& a, int32_t* cols, float* scores, hipStream_t st) {
+template <int KC, int LIK, int CAP>
+static void launch_select(const TopkArgs& a, const SliceGeom& g, int32_t* cols, float* scores, hipStream_t st) {
   const DrawTables& t = a.t;
-  const int CB = (t.D + 63) / 64;
-  const int per = (CB + a.slices - 1) / a.slices;
-  const dim3 grid((unsigned)((t.B + 63) / 64), (unsigned)a.slices);
-  const int W = (t.D + 31) / 32;
-#define SPMF_TOPK(L_)                                                                                         \
-  hipLaunchKernelGGL((topk_select_kernel<KC, L_, CAP>), grid, dim3(256), 0, st, t.B, t.D, t.KP, t.S, a.k, per, W, \
-                     t.z, t.Vp, t.phi, t.ctype, a.stored, cols, scores)
-  switch (t.lik) {
-    case 0: SPMF_TOPK(0); break;
-    case 1: SPMF_TOPK(1); break;
-    case 2: SPMF_TOPK(2); break;
-    case 3: SPMF_TOPK(3); break;
-    case 4: SPMF_TOPK(4); break;
-    default: return false;
-  }
-#undef SPMF_TOPK
-  return true;
-}
-
-template <int KC>
-static bool launch_select_kc(const TopkArgs& a, int32_t* cols, float* scores, hipStream_t st) {
-  return a.k <= 16 ? launch_select<KC, 32>(a, cols, scores, st) : launch_select<KC, 80>(a, cols, scores, st);
+  hipLaunchKernelGGL((topk_select_kernel<KC, LIK, CAP>), g.grid(t.B), dim3(256), 0, st, t.B, t.D, t.KP, t.S, a.k, g.per,
+                     g.W, t.z, t.Vp, t.phi, t.ctype, a.stored, cols, scores);
 }
 
 void launch_topk_mark(int64_t B, int D, const int32_t* row_ptr, const int32_t* col, uint32_t* bits, hipStream_t st) {
   const int64_t want = (B + 3) / 4;
   const int nb = (int)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
-  hipLaunchKernelGGL(topk_mark_kernel, dim3(nb), dim3(256), 0, st, B, D, (D + 31) / 32, row_ptr, col, bits);
+  hipLaunchKernelGGL(topk_mark_kernel, dim3(nb), dim3(256), 0, st, B, D, SliceGeom(D, 1).W, row_ptr, col, bits);
 }
 
 void launch_topk_merge(int64_t B, int k, int nsl, const int32_t* pc, const float* ps, int32_t* cols, float* scores,
@@ -165,22 +136,22 @@ void launch_topk_merge(int64_t B, int k, int nsl, const int32_t* pc, const float
 
 bool launch_topk(const TopkArgs& a, hipStream_t st) {
   const DrawTables& t = a.t;
-  const int CB = (t.D + 63) / 64;
-  if (a.k < 1 || a.k > kTopkMaxK || a.slices < 1 || a.slices > kTopkMaxSlices || a.slices > CB) return false;
-  if (t.KP != 4 && t.KP != 8 && t.KP != 16 && t.KP != 32 && t.KP != 64 && t.KP != 128 && t.KP != 256) return false;
-  if (t.lik < 0 || t.lik > 4) return false;
-  if (a.stored && a.nnz > 0) launch_topk_mark(t.B, t.D, a.row_ptr, a.col, a.stored, st);
+  if (a.k < 1 || a.k > kTopkMaxK || a.slices < 1 || a.slices > kTopkMaxSlices) return false;
+  const SliceGeom g(t.D, a.slices);
+  if (a.slices > g.CB) return false;
   int32_t* cols = a.slices > 1 ? a.part_cols : a.cols;
   float* scores = a.slices > 1 ? a.part_scores : a.scores;
-  bool ok;
-  switch (t.KP) {
-    case 4: case 8: ok = launch_select_kc<8>(a, cols, scores, st); break;
-    case 16: ok = launch_select_kc<16>(a, cols, scores, st); break;
-    default: ok = launch_select_kc<32>(a, cols, scores, st); break;
-  }
-  if (!ok) return false;
-  if (a.slices > 1) launch_topk_merge(t.B, a.k, a.slices, a.part_cols, a.part_scores, a.cols, a.scores, st);
-  return true;
+  bool ok = false;
+  with_kc(t.KP, [&](auto kc) {
+    ok = with_lik(t.lik, [&](auto lik) {
+      constexpr int KC = decltype(kc)::value, LIK = decltype(lik)::value;
+      if (a.stored && a.nnz > 0) launch_topk_mark(t.B, t.D, a.row_ptr, a.col, a.stored, st);
+      if (a.k <= 16) launch_select<KC, LIK, 32>(a, g, cols, scores, st);
+      else launch_select<KC, LIK, 80>(a, g, cols, scores, st);
+      if (a.slices > 1) launch_topk_merge(t.B, a.k, a.slices, a.part_cols, a.part_scores, a.cols, a.scores, st);
+    });
+  });
+  return ok;
 }
 
 }  // namespace spmf

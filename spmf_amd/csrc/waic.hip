@@ -10,11 +10,11 @@
 //
 // Two launches over the per-draw tables z[S,B,KP] (encode sweep), V'[S,D,KP], phi[S,D] (prep):
 //   waic_dense_kernel : EVERY cell as if x = 0.  A workgroup owns a 64 x 64 block of cells, a
-//     wave a 32 x 32 tile: y_s = <z_sb, V'_sd> on the exact-f32 matrix cores
-//     (v_mfma_f32_32x32x2_f32, the accumulator layout of dense.hip), the four statistics of a
-//     cell -- running maximum, rescaled sum of exp, running mean, sum of squared deviations --
-//     stay in registers across the loop over draws (16 cells per lane), operand tiles of the
-//     next (draw, K chunk) are fetched while the current one is multiplied.
+//     wave a 32 x 32 tile: y_s = <z_sb, V'_sd> by score_tile_loop (score_block.h: the one
+//     double-buffered MFMA loop over (draw, K chunk) of all streaming kernels), whose per-draw
+//     callback here updates the four statistics of a cell -- running maximum, rescaled sum of
+//     exp, running mean, sum of squared deviations -- which stay in registers across the loop
+//     over draws (16 cells per lane).
 //   waic_fix_kernel   : the stored cells, one wave per row, one lane per entry: the same
 //     statistics for the x = 0 value and for the true count, both by fp32 FMA from the same
 //     tables; the x = 0 contribution is taken out of the sums and the true one put in (the
@@ -24,12 +24,11 @@
 // exact as any other.
 #include "common.h"
 #include "kernels.h"
+#include "score_block.h"
 
 namespace spmf {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // running statistics of one cell over the draws
 __device__ __forceinline__ void stat_update(float ll, float inv_n, float& m, float& se, float& mu, float& q) {
@@ -56,48 +55,16 @@ __global__ __launch_bounds__(256) void waic_dense_kernel(int64_t B, int D, int K
                                                          const uint8_t* __restrict__ ctype,
                                                          double* __restrict__ sums,
                                                          double* __restrict__ row_out) {
-  constexpr int PITCH = KC + 4;
-  constexpr int NLD = KC / 8;          // float4 per thread and (draw, chunk): 2 tiles x 64 rows x KC floats
-  constexpr int TQ = 16 * KC;          // float4 per tile
-  __shared__ float tiles[2][2][64][PITCH];
+  __shared__ float tiles[2][2][64][KC + 4];
   __shared__ double red[16];
   const int t = threadIdx.x;
   const int lane = t & 63, wv = t >> 6;
   const int i32 = lane & 31, h = lane >> 5;
-  const int wr = wv >> 1, wc = wv & 1;
+  const int wr = wv >> 1;
   const int64_t b0 = (int64_t)blockIdx.x * 64;
   const int d0 = blockIdx.y * 64;
-  const int NCH = KP > KC ? KP / KC : 1;
-  const int NIT = S * NCH;
-  const int d = d0 + wc * 32 + i32;
-  const bool bern = lik_bern(LIK) || (LIK == 3 && d < D && cell_is_bern(LIK, ctype, d));   // (no type behind D)
-
-  auto fetch = [&](int it, float4* pre) {
-    const int s = it / NCH, kc0 = (it % NCH) * KC;
-#pragma unroll
-    for (int j = 0; j < NLD; ++j) {
-      const int idx = t + 256 * j;
-      const int tile = idx / TQ, rem = idx % TQ;
-      const int row = rem / (KC / 4), k = kc0 + 4 * (rem % (KC / 4));
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (k < KP) {
-        if (tile == 0) {
-          if (b0 + row < B) v = *reinterpret_cast<const float4*>(z + ((size_t)s * B + b0 + row) * KP + k);
-        } else {
-          if (d0 + row < D) v = *reinterpret_cast<const float4*>(Vp + ((size_t)s * D + d0 + row) * KP + k);
-        }
-      }
-      pre[j] = v;
-    }
-  };
-  auto stash = [&](int buf, const float4* pre) {
-#pragma unroll
-    for (int j = 0; j < NLD; ++j) {
-      const int idx = t + 256 * j;
-      const int tile = idx / TQ, rem = idx % TQ;
-      *reinterpret_cast<float4*>(&tiles[buf][tile][rem / (KC / 4)][4 * (rem % (KC / 4))]) = pre[j];
-    }
-  };
+  const int d = score_tile_col(d0);
+  const bool bern = score_col_bern<LIK>(ctype, D, d);
 
   float m[16], se[16], mu[16], q[16];
 #pragma unroll
@@ -107,52 +74,21 @@ __global__ __launch_bounds__(256) void waic_dense_kernel(int64_t B, int D, int K
     mu[r] = 0.f;
     q[r] = 0.f;
   }
-  f32x16 acc;
+  score_tile_loop<KC>(tiles, B, D, KP, S, b0, d0, z, Vp, phi, [&](int s, const score_f32x16& acc, float ph) {
+    const float inv_n = 1.f / (float)(s + 1);
 #pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-
-  float4 pre[NLD];
-  fetch(0, pre);
-  stash(0, pre);
-  __syncthreads();
-  float ph = 0.f;
-  for (int it = 0; it < NIT; ++it) {
-    const int buf = it & 1;
-    const int s = it / NCH, ch = it % NCH;
-    if (it + 1 < NIT) fetch(it + 1, pre);
-    if (ch == 0) ph = d < D ? phi[(size_t)s * D + d] : 0.f;
-    // lane half h takes k = 8 q + 4 h + e of the chunk for both operands: the pairing of the k
-    // values inside a step is free as long as A and B agree
-    const float* ar = &tiles[buf][0][wr * 32 + i32][4 * h];
-    const float* br = &tiles[buf][1][wc * 32 + i32][4 * h];
-#pragma unroll
-    for (int qk = 0; qk < KC / 8; ++qk) {
-      const float4 a = *reinterpret_cast<const float4*>(ar + 8 * qk);
-      const float4 b = *reinterpret_cast<const float4*>(br + 8 * qk);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
+    for (int r = 0; r < 16; ++r) {
+      float ey;
+      const float rt = cell_rate(LIK, acc[r], ph, ey);
+      stat_update(cell_ll0(bern, rt), inv_n, m[r], se[r], mu[r], q[r]);
     }
-    if (ch == NCH - 1) {
-      const float inv_n = 1.f / (float)(s + 1);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float ey;
-        const float rt = cell_rate(LIK, acc[r], ph, ey);
-        stat_update(cell_ll0(bern, rt), inv_n, m[r], se[r], mu[r], q[r]);
-        acc[r] = 0.f;
-      }
-    }
-    if (it + 1 < NIT) stash(buf ^ 1, pre);
-    __syncthreads();
-  }
+  });
 
   const double logS = log((double)S), inv_sm1 = 1.0 / (double)(S - 1);
   double an = 0.0, aL = 0.0, aP = 0.0, aE = 0.0, ax = 0.0;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int64_t b = b0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+    const int64_t b = b0 + score_tile_row(wr, r, h);
     const bool in = b < B && d < D;
     const double lp = (double)m[r] + (double)logf(se[r]) - logS;
     const double pw = (double)q[r] * inv_sm1;
@@ -284,34 +220,16 @@ __global__ __launch_bounds__(256) void waic_fix_kernel(int64_t B, int D, int KP,
   }
 }
 
-template <int KC>
-static bool launch_dense_kc(const WaicArgs& a, hipStream_t st) {
-  const DrawTables& t = a.t;
-  const dim3 grid((unsigned)((t.B + 63) / 64), (unsigned)((t.D + 63) / 64));
-#define SPMF_WAIC(L_)                                                                                    \
-  hipLaunchKernelGGL((waic_dense_kernel<KC, L_>), grid, dim3(256), 0, st, t.B, t.D, t.KP, t.S, t.z, t.Vp, \
-                     t.phi, t.ctype, a.sums, a.row_out)
-  switch (t.lik) {
-    case 0: SPMF_WAIC(0); break;
-    case 1: SPMF_WAIC(1); break;
-    case 2: SPMF_WAIC(2); break;
-    case 3: SPMF_WAIC(3); break;
-    case 4: SPMF_WAIC(4); break;
-    default: return false;
-  }
-#undef SPMF_WAIC
-  return true;
-}
-
 bool launch_waic(const WaicArgs& a, hipStream_t st) {
   const DrawTables& t = a.t;
-  bool ok;
-  switch (t.KP) {
-    case 4: case 8: ok = launch_dense_kc<8>(a, st); break;
-    case 16: ok = launch_dense_kc<16>(a, st); break;
-    case 32: case 64: case 128: case 256: ok = launch_dense_kc<32>(a, st); break;
-    default: return false;
-  }
+  const dim3 grid((unsigned)((t.B + 63) / 64), (unsigned)((t.D + 63) / 64));
+  bool ok = false;
+  with_kc(t.KP, [&](auto kc) {
+    ok = with_lik(t.lik, [&](auto lik) {
+      hipLaunchKernelGGL((waic_dense_kernel<decltype(kc)::value, decltype(lik)::value>), grid, dim3(256), 0, st, t.B,
+                         t.D, t.KP, t.S, t.z, t.Vp, t.phi, t.ctype, a.sums, a.row_out);
+    });
+  });
   if (!ok) return false;
   if (a.nnz > 0) {
     const int64_t want = (t.B + 3) / 4;

@@ -1,8 +1,8 @@
 """Do two builds of the library return the same bits from the streaming calls?
 
-    stream_bits.py dump FILE          run top_k, score_cells, rank_cells and waic_streaming at four small cases with the
-                                      library that SPMF_LIB_PATH names (default: the tree's own) and save every
-                                      output to FILE
+    stream_bits.py dump FILE          run top_k, score_cells, rank_cells, embed and waic_streaming at four small
+                                      cases, and knn at two shapes, with the library that SPMF_LIB_PATH names
+                                      (default: the tree's own) and save every output to FILE
     stream_bits.py compare A B [OUT]  compare two dumps tensor by tensor with torch.equal -> one JSON line,
                                       also written to OUT
 
@@ -10,12 +10,14 @@ The cases are problems of tests/_stream_cases.py, (likelihood, B, D, K, S): pois
 (65, 130, 40, 3), bernoulli_log (70, 150, 3, 2) and poisson (40, 70, 128, 3), i.e. KP 16, 64, 4 and 128.
 top_k: k = 10 and 64, stored cells excluded and not, columns and scores.  score_cells: every cell listed in a
 seeded random order with values 0 .. 3: mean and lppd.  rank_cells: the same list, stored cells excluded: rank,
-candidates and score.  waic_streaming (row scores included) is called
+candidates and score.  embed: mean and (S >= 2) deviation.  knn: two of tests/test_gpu_knn.py's SHAPES with its
+points, (nq, nr, K, k) = (131, 197, 16, 10) Euclidean under both SPMF_KNN_TILE values and (5, 333, 33, 64) cosine:
+indices and distances.  waic_streaming (row scores included) is called
 TWICE in each dump: its fp64 sums are atomics, so `compare` also reports whether the two calls of one build
 agree, which is the bar a comparison across builds has to be read against.
 
 A dump is made in a process of its own per build (a library is loaded once per process); a build from before
-embed / knn lacks their entry points, which nothing here calls."""
+embed / knn lacks their entry points and dumps no embed / knn tensor."""
 import ctypes as C
 import json
 import os
@@ -27,6 +29,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 CASES = [("poisson", 131, 197, 16, 7), ("mixed", 65, 130, 40, 3), ("bernoulli_log", 70, 150, 3, 2),
          ("poisson", 40, 70, 128, 3)]
+KNN_CASES = [(131, 197, 16, 10, "euclidean", ("0", "1")), (5, 333, 33, 64, "cosine", (None,))]
+CALLS = ("top_k", "score_cells", "rank_cells", "embed", "knn")
 
 
 def dump(path):
@@ -39,6 +43,7 @@ def dump(path):
         del _lib.SIGNATURES[name]
     from _stream_cases import _problem
     from test_gpu_dense import _dense_model
+    with_knn = "spmf_knn" in _lib.SIGNATURES and "spmf_embed_rows" in _lib.SIGNATURES
     out = {"lib": os.path.relpath(_lib.LIB_PATH, ROOT), "device": torch.cuda.get_device_name(0)}
     for lik, B, D, K, S in CASES:
         cfg, x, params, mask, _ = _problem(lik, B, D, K, S)
@@ -57,11 +62,27 @@ def dump(path):
         rk = m.rank_cells(batch, cell // D, cell % D, draws=params)
         for name in ("rank", "candidates", "score"):
             out[f"rank_cells/{tag}/{name}"] = rk[name].cpu()
+        if with_knn:
+            for name, v in m.embed(batch, draws=params, sd=S >= 2).items():
+                out[f"embed/{tag}/{name}"] = v.cpu()
         for call in (0, 1):
             w = m.waic_streaming(batch, draws=params, row_scores=True)
             for name, v in w.items():
                 v = v.cpu() if torch.is_tensor(v) else torch.tensor(float(v), dtype=torch.float64)
                 out[f"waic_streaming/{tag}/{name}/call{call}"] = v
+    if with_knn:
+        from test_gpu_knn import _points
+        for nq, nr, K, k, metric, tiles in KNN_CASES:
+            Q, R = _points(nq, nr, K, False)
+            for tile in tiles:
+                if tile is not None:
+                    os.environ["SPMF_KNN_TILE"] = tile
+                try:
+                    nn = m.knn(torch.as_tensor(R).cuda(), k=k, queries=torch.as_tensor(Q).cuda(), metric=metric)
+                finally:
+                    os.environ.pop("SPMF_KNN_TILE", None)
+                for name in ("indices", "distances"):
+                    out[f"knn/{nq}x{nr}_K{K}_k{k}_{metric}/tile{tile}/{name}"] = nn[name].cpu()
     torch.cuda.synchronize()
     torch.save(out, path)
     print(f"{sum(torch.is_tensor(v) for v in out.values())} tensors of {out['lib']} -> {path}")
@@ -77,8 +98,10 @@ def compare(a_path, b_path, out_path=None):
     a, b = torch.load(a_path), torch.load(b_path)
     keys = sorted(k for k in a if torch.is_tensor(a[k]))
     assert keys == sorted(k for k in b if torch.is_tensor(b[k])), "the two dumps hold different outputs"
-    res = {"a": a["lib"], "b": b["lib"], "device": a["device"], "cases": ["%s %dx%d K=%d S=%d" % c for c in CASES]}
-    for call in ("top_k", "score_cells", "rank_cells"):
+    res = {"a": a["lib"], "b": b["lib"], "device": a["device"], "cases": ["%s %dx%d K=%d S=%d" % c for c in CASES],
+           "knn_cases": ["%dx%d K=%d k=%d %s, SPMF_KNN_TILE %s" % (*c[:5], " and ".join(t or "unset" for t in c[5]))
+                         for c in KNN_CASES]}
+    for call in CALLS:
         mine = [k for k in keys if k.startswith(call + "/")]
         differ = [k for k in mine if not torch.equal(_bits(a[k]), _bits(b[k]))]
         res[call] = {"tensors": len(mine), "equal": len(mine) - len(differ), "differ": differ}
@@ -103,7 +126,7 @@ def compare(a_path, b_path, out_path=None):
         os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
         with open(out_path, "w") as f:
             f.write(line + "\n")
-    return 0 if not any(res[c]["differ"] for c in ("top_k", "score_cells", "rank_cells")) else 1
+    return 0 if not any(res[c]["differ"] for c in CALLS) else 1
 
 
 if __name__ == "__main__":
