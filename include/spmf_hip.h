@@ -627,6 +627,43 @@ int spmf_rank_cells(spmf_ctx* ctx, const spmf_counts* counts, int S,
                     int32_t* rank_out, int32_t* cand_out, float* score_out, void* scratch,
                     size_t scratch_bytes, void* stream);
 
+/* ---- predictions of a column panel (added within ABI 6: two new entry points, no struct changed) ----
+ * The reconstruction as a dense block: for every row of the batch `counts` and every column of a panel,
+ * over S >= 1 draws, without a [S,B,D] tensor (csrc/panel.hip).  With r_s what spmf_dense_ll writes as
+ * `rate` for draw s (the rate of a Poisson column, the logit of a Bernoulli one) and m_s = r_s |
+ * sigmoid(r_s):
+ *   mean_out[b][j] = (1/S) sum_s m_s, added in draw order: bit for bit the score of spmf_topk_rows and
+ *                    spmf_rank_cells for that cell;
+ *   sd_out[b][j]   = the unbiased standard deviation of m_s over the draws (Welford in draw order),
+ *                    which needs S >= 2;
+ *   pnz_out[b][j]  = P(x > 0) under the predictive mixture: (1/S) sum_s -expm1(-r_s) on a Poisson column
+ *                    (no cancellation at small rates), the mean itself, the same bits, on a Bernoulli one.
+ * Each output is [n_rows][n_cols] fp32, row-major; sd_out and pnz_out may be NULL; nothing outside
+ * [n_rows][n_cols] is written.  cols == NULL: all columns, n_cols must be D.  Otherwise cols lists
+ * 0 <= n_cols <= D columns (int32, device) in any order, repeats allowed; output column j is column
+ * cols[j].  A listed column outside [0, D) reads nothing: its output column is NaN in every output.  A
+ * NaN count makes its row NaN in all outputs.  An element depends on its cell alone: not on the list,
+ * on the other outputs asked for or on how the rows are cut into calls (no atomics, one summation
+ * order); two calls return the same bits.
+ * params: only u, v, w, s (slots 2, 0, 1, 7) are read, each with the leading axis S.
+ * scratch: 256-byte aligned, at least spmf_predict_scratch_bytes(ctx, counts->n_rows, S) bytes: the
+ * scratch of the WAIC call and, in a region of their own behind it (the draw stage's A' region is not
+ * reused), the compacted tables of a listed panel sized for n_cols = D, S * D * (KP + 1) floats and D
+ * bytes -- the size does not depend on the list; SPMF_E_WORKSPACE when short.  SPMF_E_ARG for S outside
+ * 1..65535, NULL params / eta / scratch, a misaligned scratch, a mixed context without column types, a
+ * struct_size mismatch, n_cols outside 0..D, cols == NULL with n_cols != D, sd_out with S < 2, a NULL
+ * mean_out with n_rows > 0 and n_cols > 0; SPMF_E_UNSUPPORTED for ceil(n_cols / 64) > 65535; every
+ * error returns before any launch.  n_cols == 0 or n_rows == 0 returns SPMF_OK without work.  The
+ * context's workspace is not touched: the call may sit between other calls on the context, a
+ * spmf_step_begin .. spmf_step_end pair included.  Stream-ordered, synchronises nowhere.  K as for
+ * spmf_waic_accumulate. */
+size_t spmf_predict_scratch_bytes(const spmf_ctx* ctx, int64_t n_rows, int S);
+int spmf_predict_columns(spmf_ctx* ctx, const spmf_counts* counts, int S,
+                         const float* const params[SPMF_NVARS], const float* eta,
+                         int32_t n_cols, const int32_t* cols,
+                         float* mean_out, float* sd_out, float* pnz_out,
+                         void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- posterior mean encoding (added within ABI 6: two new entry points, no struct changed) ----
  * The rows of the batch `counts` in the latent space: mean_out[b][k] = (1/S) sum_s z_sb[k], k < K,
  * where z_sb is the encode sweep of draw s (what spmf_encode computes from u_s, s_s), fp32, the sum in

@@ -1170,8 +1170,8 @@ int spmf_dense_ll(spmf_ctx* c, const spmf_counts* ct, const float* u, const floa
 }
 
 // ---- the draw stage of the streaming calls ---------------------------------------------------
-// spmf_waic_accumulate, spmf_topk_rows, spmf_score_cells, spmf_rank_cells and spmf_embed_rows are one stage and a
-// consumer each.
+// spmf_waic_accumulate, spmf_topk_rows, spmf_score_cells, spmf_rank_cells, spmf_predict_columns and
+// spmf_embed_rows are one stage and a consumer each.
 // The stage: for S draws the per-draw tables (prep) and the encoded rows z[S,B,KP] go into the caller's scratch; the consumer
 // kernel then reads z, V' and phi of every draw (kernels.h DrawTables).  The context's workspace is not used, so
 // a step that is bound (or half way: spmf_step_begin .. spmf_step_end) keeps everything it has.
@@ -1400,6 +1400,57 @@ int spmf_rank_cells(spmf_ctx* c, const spmf_counts* ct, int S, const float* cons
   ra.n_cells = n_cells; ra.cell_row = cell_row; ra.cell_col = cell_col;
   ra.rank = rank_out; ra.cand = cand_out; ra.score = score_out;
   if (!launch_rank(ra, st)) return fail(c, SPMF_E_UNSUPPORTED, "rank_cells: no kernel for this K / likelihood");
+  HIPCHK(c, hipGetLastError());
+  return SPMF_OK;
+}
+
+// ---- predictions of a panel of columns (panel.hip) ---------------------------------------------
+// Scratch of one call: the draw carve and, behind it, the compacted tables of a listed panel in a region of
+// their own (the carve's Ap is not reused), sized for n_cols = D: the size does not depend on the list.
+struct PanelCarve {
+  size_t Vc, phic, ctc, total;
+};
+static PanelCarve panel_carve(const spmf_ctx* c, int64_t rows, int S) {
+  PanelCarve k;
+  const size_t KP = c->KP, D = c->D, nS = S;
+  size_t o = draw_carve(c, rows, S).total;
+  k.Vc = o;   o += al(nS * D * KP * sizeof(float));
+  k.phic = o; o += al(nS * D * sizeof(float));
+  k.ctc = o;  o += al(D);
+  k.total = o;
+  return k;
+}
+
+size_t spmf_predict_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S) {
+  if (!c || n_rows < 0 || S < 1) return 0;
+  return panel_carve(c, n_rows, S).total;
+}
+
+int spmf_predict_columns(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS],
+    const float* eta, int32_t n_cols, const int32_t* cols, float* mean_out, float* sd_out, float* pnz_out,
+    void* scratch, size_t scratch_bytes, void* stream) {
+  int rc = draw_check(c, "predict_columns", ct, S, 1, params, eta, scratch, scratch_bytes, spmf_predict_scratch_bytes);
+  if (rc) return rc;
+  if (n_cols < 0 || n_cols > c->D) return fail(c, SPMF_E_ARG, "predict_columns: n_cols must be in 0..D");
+  if (!cols && n_cols != c->D) return fail(c, SPMF_E_ARG, "predict_columns: cols == NULL is all columns: n_cols "
+      "must be D");
+  if (sd_out && S < 2) return fail(c, SPMF_E_ARG, "predict_columns: sd_out needs S >= 2 (the deviation over the "
+      "draws)");
+  const bool work = n_cols > 0 && ct->n_rows > 0;
+  if (work && !mean_out) return fail(c, SPMF_E_ARG, "predict_columns: mean_out must be set");
+  if (((int64_t)n_cols + 63) / 64 > 65535) return fail(c, SPMF_E_UNSUPPORTED, "predict_columns: n_cols above "
+      "65535 * 64");
+  if (!work) return SPMF_OK;
+  hipStream_t st = (hipStream_t)stream;
+  PanelArgs pa{};
+  rc = draw_stage(c, "predict_columns", ct, S, params, eta, scratch, st, pa.t);
+  if (rc) return rc;
+  const PanelCarve pc = panel_carve(c, ct->n_rows, S);
+  char* base = (char*)scratch;
+  pa.n_cols = n_cols; pa.cols = cols;
+  pa.Vc = (float*)(base + pc.Vc); pa.phic = (float*)(base + pc.phic); pa.ctc = (uint8_t*)(base + pc.ctc);
+  pa.mean = mean_out; pa.sd = sd_out; pa.pnz = pnz_out;
+  if (!launch_panel(pa, st)) return fail(c, SPMF_E_UNSUPPORTED, "predict_columns: no kernel for this K / likelihood");
   HIPCHK(c, hipGetLastError());
   return SPMF_OK;
 }

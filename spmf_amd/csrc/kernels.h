@@ -314,6 +314,19 @@ struct CellsArgs {
   float* lppd;                     // [n_cells]; null iff val is null
 };
 bool launch_cells(const CellsArgs& a, hipStream_t st);
+// panel.hip: posterior predictive mean and, where asked for, standard deviation and P(x > 0) over S draws of
+// every cell of B rows x n_cols columns, as dense [B][n_cols] arrays.  cols: the listed columns of the draw
+// tables t (any order, repeats allowed; one outside [0, t.D) gives NaN), compacted into Vc / phic / ctc first;
+// null: the tables' own columns, n_cols == t.D, no gather.  false: KP / lik not built (nothing launched).
+struct PanelArgs {
+  DrawTables t;
+  int n_cols;
+  const int32_t* cols;             // [n_cols] or null
+  float *Vc, *phic;                // [S][n_cols][KP], [S][n_cols] (cols set)
+  uint8_t* ctc;                    // [n_cols] (cols set, mixed contexts)
+  float *mean, *sd, *pnz;          // [B][n_cols]; sd (S >= 2) and pnz may be null
+};
+bool launch_panel(const PanelArgs& a, hipStream_t st);
 bool launch_col_pass(int KP, const ColArgs& a, hipStream_t st);   // true: launched, with the pack block if asked
 bool launch_col_widek(int KP, const ColArgs& a, hipStream_t st);  // KP = 128, 256 (widek.hip)
 

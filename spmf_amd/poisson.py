@@ -604,7 +604,7 @@ class PoissonFactorization:
                 "lppd": float(lppd_i.sum()), "pwaic": float(pwaic_i.sum())}
 
     def _draw_call(self, name, draws, nsamples, min_draws, dense_alternative):
-        """What the streaming calls (waic_streaming, top_k, score_cells, rank_cells, embed) hand the library's draw stage:
+        """What the streaming calls (waic_streaming, top_k, score_cells, rank_cells, predict, embed) hand the library's draw stage:
         ``(S, pin, eta_ptr, stream, KP, lib, h)``.  ``draws``: dict with 's','u','v','w' of shape [S,...]
         (None: ``surrogate_distribution.sample(nsamples)``), at least ``min_draws`` of them; ``pin`` is the
         C-ABI's twelve parameter slots and keeps the packed tensors it points into alive."""
@@ -887,6 +887,75 @@ class PoissonFactorization:
         del rank, cand, score, order
         out.update(_heldout.rank_summary(out["rank"], out["candidates"], ks))
         return out
+
+    def _column_list(self, name, cols):
+        """The column list of ``predict`` (``name``), checked before any library call: None (all columns) or
+        1-D integers inside [0, D), at most D of them, duplicates kept.  -> int32 on the device, or None."""
+        if cols is None:
+            return None
+        D = self.feature_dim
+        if not isinstance(cols, torch.Tensor):
+            cols = np.asarray(cols)
+            if cols.size == 0 and cols.ndim == 1:         # [] has no dtype of its own
+                cols = cols.astype(np.int64)
+            cols = torch.as_tensor(cols)
+        if cols.dim() != 1:
+            raise ValueError(f"{name}: cols must be 1-D, got shape {tuple(cols.shape)}")
+        if cols.dtype.is_floating_point or cols.dtype == torch.bool:
+            raise ValueError(f"{name}: cols must hold integers, got {cols.dtype}")
+        if cols.numel() > D:
+            raise ValueError(f"{name}: cols lists {int(cols.numel())} columns, more than the {D} there are")
+        if cols.numel():
+            lo, hi = int(cols.min()), int(cols.max())
+            if lo < 0 or hi >= D:
+                raise ValueError(f"{name}: cols must lie in [0, {D}), got {lo} .. {hi}")
+        return cols.to(device=self.device, dtype=torch.int32).contiguous()
+
+    def predict(self, data, cols=None, nsamples=32, draws=None, sd=False, p_nonzero=False, max_rows=None):
+        """The reconstruction: the posterior predictive mean of every cell of the rows of ``data`` and the
+        columns ``cols`` as a dense block, without a [S,B,D] array (csrc/panel.hip).  'mean' is the score of
+        ``top_k`` / ``rank_cells``, bit for bit: the mean over the draws of m_s, the rate on a Poisson column
+        and sigmoid(logit) on a Bernoulli one.
+
+        ``data``, ``draws`` and ``max_rows`` as in ``top_k`` (``draws`` may hold a single draw); the rows of
+        all batches are concatenated.  ``cols``: None (all D columns) or 1-D integers in [0, D), numpy or
+        torch on any device, at most D of them, in any order, duplicates kept: output column j is column
+        ``cols[j]``.  ``sd=True`` adds the unbiased standard deviation of m_s over the draws (at least two
+        draws; Welford in draw order).  ``p_nonzero=True`` adds P(x > 0) under the predictive mixture:
+        mean_s (1 - exp(-rate_s)) on a Poisson column, formed as -expm1(-rate_s) so that small rates keep
+        their digits, and the mean itself on a Bernoulli column.
+
+        Returns device tensors {'mean': float32 [B, C]} plus 'sd' and 'p_nonzero' when asked for and, with a
+        list, 'columns': the int32 list as used.  Memory: every output is B * C * 4 bytes and is allocated
+        whole -- bound it with the column list or, over the rows, with a ``{"counts": sc, "panels": (p0, p1)}``
+        range per call; the scratch is bounded by ``max_rows`` as in ``top_k``.  A row with a NaN count is NaN.
+        A value depends on its cell alone: not on the list, on the other outputs asked for or on
+        ``max_rows``.  Bit-reproducible."""
+        cols = self._column_list("predict", cols)
+        S, pin, eta, stream, KP, lib, h = self._draw_call("predict", draws, nsamples, 2 if sd else 1,
+                                                          "log_likelihood_components")
+        n_cols = self.feature_dim if cols is None else int(cols.numel())
+        names = ("mean",) + (("sd",) if sd else ()) + (("p_nonzero",) if p_nonzero else ())
+        scratch, parts = _Scratch(self.device), {n: [] for n in names}
+        for n_rows, chunks in self._row_chunks(data, S * KP * 4, max_rows):
+            out = {n: torch.empty(n_rows, n_cols, dtype=torch.float32, device=self.device) for n in names}
+            for r0, sub in chunks if n_cols else ():       # (an empty list has no pointer to pass)
+                _lib.check(h, lib.spmf_predict_columns(
+                    h, C.byref(sub), S, pin, eta, n_cols, cols.data_ptr() if cols is not None else None,
+                    *[out[n][r0:].data_ptr() if n in out else None for n in ("mean", "sd", "p_nonzero")],
+                    *scratch.fit(lib.spmf_predict_scratch_bytes(h, int(sub.n_rows), S)), stream),
+                    "spmf_predict_columns")
+            for n in names:
+                parts[n].append(out[n])
+
+        def cat(p):
+            if len(p) == 1:
+                return p[0]
+            return torch.cat(p) if p else torch.empty(0, n_cols, dtype=torch.float32, device=self.device)
+        res = {n: cat(parts[n]) for n in names}
+        if cols is not None:
+            res["columns"] = cols
+        return res
 
     def embed(self, data, nsamples=32, draws=None, sd=False, max_rows=None):
         """The rows of ``data`` in the latent space, at any size: the posterior mean encoding

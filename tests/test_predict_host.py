@@ -1,0 +1,225 @@
+"""CPU-side tests of predict (PoissonFactorization.predict, spmf_predict_columns, csrc/panel.hip): the two
+entry points in the header, the export list and the binding, the method on the class surface, the error
+contract of the draw stage and the entry's own argument errors -- all refused before anything touches a
+device -- the empty cases, the scratch size, and the argument checks of the method that need no device.
+(The valid call: tests/test_gpu_predict.py.)"""
+import ctypes as C
+import fnmatch
+import os
+import re
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CALL, SIZE = "spmf_predict_columns", "spmf_predict_scratch_bytes"
+HEADER_ARGS = {SIZE: 3, CALL: 13}
+# the arguments between `eta` and `scratch` in the header's order
+OWN = (("n", C.c_int32), ("cols", C.c_void_p), ("mean", C.c_void_p), ("sd", C.c_void_p), ("pnz", C.c_void_p))
+B, D, K, S = 70, 45, 3, 2
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as ge
+    from spmf_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        ge.build()
+    return _lib.load()
+
+
+def _header_args(hdr, name):
+    m = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", hdr, re.S)
+    assert m, f"{name} is not declared in include/spmf_hip.h"
+    return len([a for a in m.group(1).split(",") if a.strip()])
+
+
+def test_entry_points_are_declared_exported_and_bound():
+    from spmf_amd import _lib
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "spmf_hip.h")).read(), flags=re.S)
+    exports = open(os.path.join(ROOT, "spmf_amd", "csrc", "exports.map")).read()
+    exports = re.sub(r"/\*.*?\*/", "", exports, flags=re.S)
+    globs = re.search(r"global:\s*([^}]*?)local:", exports, re.S).group(1)
+    patterns = [p.strip() for p in globs.split(";") if p.strip()]
+    for name, nargs in HEADER_ARGS.items():
+        assert any(fnmatch.fnmatchcase(name, p) for p in patterns), (name, patterns)
+        assert name in _lib.SIGNATURES, name
+        assert len(_lib.SIGNATURES[name][1]) == _header_args(hdr, name) == nargs, name
+    assert "define SPMF_ABI_VERSION 6" in hdr and _lib.ABI_VERSION == 6
+
+
+def test_symbols_are_in_the_built_library(lib):
+    assert callable(getattr(lib, CALL)) and callable(getattr(lib, SIZE))
+    assert lib.spmf_version() == 6
+
+
+def test_method_is_on_all_three_classes():
+    from spmf_amd import BernoulliFactorization, MixedFactorization, PoissonFactorization
+    for cls in (PoissonFactorization, BernoulliFactorization, MixedFactorization):
+        assert callable(getattr(cls, "predict", None)), cls.__name__
+
+
+def _ctx(lib, k, flags=0, d=D):
+    h = C.c_void_p()
+    assert lib.spmf_ctx_create(0, k, d, flags, C.byref(h)) == 0
+    return h
+
+
+def _raw_call(good):
+    """-> call(**overrides): spmf_predict_columns through a binding of its own with plain pointers, so that
+    NULL can stand for `params` and `counts` too."""
+    from spmf_amd import _lib
+    fn = getattr(C.CDLL(_lib.LIB_PATH), CALL)
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [t for _, t in OWN] + [
+        C.c_void_p, C.c_size_t, C.c_void_p]
+
+    def call(**kw):
+        a = dict(good, **kw)
+        return fn(a["h"], C.byref(a["ct"]) if a["ct"] is not None else None, a["S"], a["pin"], a["eta"],
+                  *[a[n] for n, _ in OWN], a["ptr"], a["nbytes"], a["stream"])
+    return call
+
+
+def test_shared_and_own_errors_return_before_any_device_call(lib):
+    """A context of spmf_ctx_create (K = 3, D = 45), a hand-filled descriptor of 70 empty rows and dummy aligned
+    addresses: the error cases of the draw stage (the list of _stream_cases.assert_shared_errors) and the
+    entry's own are refused with their codes, before the empty returns; nothing here is a valid call with
+    work to do, so nothing may be launched or dereferenced."""
+    from spmf_amd import _lib
+    from spmf_amd._lib import VAR_ORDER
+    h, raw = _ctx(lib, K), _ctx(lib, K, _lib.FLAG_MIXED)
+    try:
+        cs = _lib.CountsStruct()
+        cs.struct_size = C.sizeof(_lib.CountsStruct)
+        cs.n_cols, cs.n_rows, cs.nnz, cs.row_ptr = D, B, 0, 0x10000
+        slots = {n: 0x100000 * (i + 1) for i, n in enumerate(VAR_ORDER) if n in ("s", "u", "v", "w")}
+        need = int(lib.spmf_predict_scratch_bytes(h, B, S))
+        assert need > 0 and need % 256 == 0
+        good = dict(h=h, ct=cs, S=S, pin=_lib.PtrArray(*[slots.get(n) for n in VAR_ORDER]), eta=0x7000000,
+                    ptr=0x8000000, nbytes=need, stream=None, n=4, cols=0x2000000, mean=0x3000000,
+                    sd=0x4000000, pnz=0x5000000)
+        no_u = _lib.PtrArray(*[slots.get(n) if n != "u" else None for n in VAR_ORDER])
+        call = _raw_call(good)
+        # the draw stage's contract (min_S = 1)
+        assert call(S=0) == -1, "S below the minimum"
+        assert call(S=65536) == -1
+        assert call(pin=None) == -1 and call(eta=None) == -1 and call(ptr=None) == -1 and call(ct=None) == -1
+        assert call(pin=no_u) == -1, "slot u missing"
+        assert call(ptr=good["ptr"] + 4) == -1, "scratch off by 4 bytes"
+        bad = type(cs).from_buffer_copy(cs)
+        bad.struct_size += 8
+        assert call(ct=bad) == -1, "struct_size + 8"
+        assert call(h=raw) == -1
+        assert "column_types" in lib.spmf_last_error(raw).decode()
+        assert call(nbytes=need - 256) == -3
+        msg = lib.spmf_last_error(h).decode()
+        assert str(need) in msg, msg
+        # the entry's own
+        assert call(mean=None) == -1, "no mean_out with work to do"
+        assert "mean_out" in lib.spmf_last_error(h).decode()
+        need1 = int(lib.spmf_predict_scratch_bytes(h, B, 1))
+        assert call(S=1, nbytes=need1) == -1, "sd_out with one draw"
+        assert "sd_out" in lib.spmf_last_error(h).decode()
+        assert call(n=-1) == -1 and call(n=D + 1) == -1
+        assert "n_cols" in lib.spmf_last_error(h).decode()
+        assert call(cols=None) == -1 and call(cols=None, n=D - 1) == -1 and call(cols=None, n=0) == -1, \
+            "no list: n_cols must be D"
+        # errors come before the empty returns
+        empty = type(cs).from_buffer_copy(cs)
+        empty.n_rows = 0
+        need0 = int(lib.spmf_predict_scratch_bytes(h, 0, S))
+        assert call(n=0, nbytes=need - 256) == -3 and call(ct=empty, nbytes=need0 - 256) == -3
+        assert call(n=0, S=1, nbytes=need1) == -1 and call(ct=empty, S=1) == -1, "sd_out with one draw, no work"
+        assert call(ct=empty, n=D + 1) == -1 and call(ct=empty, cols=None) == -1
+        assert call(n=0, S=0) == -1 and call(n=0, ptr=good["ptr"] + 4) == -1
+        # the empty cases are served without a launch: no pointer here could be dereferenced
+        assert call(n=0) == 0 and call(n=0, mean=None, sd=None, pnz=None) == 0
+        assert call(ct=empty) == 0 and call(ct=empty, cols=None, n=D) == 0 and call(ct=empty, mean=None) == 0, \
+            "an empty batch"
+        assert call(n=0, S=1, sd=None, nbytes=need1) == 0
+    finally:
+        lib.spmf_ctx_destroy(h)
+        lib.spmf_ctx_destroy(raw)
+
+
+@pytest.mark.parametrize("k", [3, 16, 64, 128])
+def test_scratch_size(lib, k):
+    """A multiple of 256: the draw stage's scratch plus the compacted tables of a listed panel sized for
+    n_cols = D (V' rows, phi and the column types, three regions of their own); 0 for S < 1, for negative
+    rows and without a context; a function of (rows, S) alone."""
+    h, h2 = _ctx(lib, k), _ctx(lib, k)
+    try:
+        kp = int(lib.spmf_padded_k(h))
+        for rows in (0, 1, B, 1000):
+            for s in (1, 2, 7):
+                size, cells = (int(getattr(lib, f)(h, rows, s)) for f in (SIZE, "spmf_cells_scratch_bytes"))
+                tables = s * D * kp * 4 + s * D * 4 + D
+                assert size % 256 == 0 and cells + tables <= size <= cells + tables + 3 * 255, (rows, s, size)
+                assert int(lib.spmf_predict_scratch_bytes(h, rows, s)) == size
+                assert int(lib.spmf_predict_scratch_bytes(h2, rows, s)) == size
+        assert int(lib.spmf_predict_scratch_bytes(h, B, 0)) == 0
+        assert int(lib.spmf_predict_scratch_bytes(h, -1, 2)) == 0
+        assert int(lib.spmf_predict_scratch_bytes(None, B, 2)) == 0
+    finally:
+        lib.spmf_ctx_destroy(h)
+        lib.spmf_ctx_destroy(h2)
+
+
+# ---- the method's argument checks ---------------------------------------------------------------
+
+def _cpu_model(**kw):
+    from spmf_amd import PoissonFactorization
+    m = PoissonFactorization(latent_dim=2, feature_dim=6, initialize_distributions=False, device="cpu", **kw)
+    rng = np.random.default_rng(0)
+    x = rng.poisson(1.0, size=(8, 6)).astype(np.float64)
+    draws = {"u": rng.random((2, 6, 2)), "v": rng.random((2, 2, 6)), "w": rng.random((2, 1, 6)),
+             "s": rng.random((2, 2, 6))}
+    return m, x, draws
+
+
+def test_bad_column_lists_raise_value_error_without_a_device():
+    import torch
+    m, x, draws = _cpu_model()
+    data = {"counts": x}
+    with pytest.raises(ValueError, match=r"^predict: cols must be 1-D, got shape \(2, 1\)$"):
+        m.predict(data, np.zeros((2, 1), dtype=np.int64), draws=draws)
+    with pytest.raises(ValueError, match="1-D"):
+        m.predict(data, torch.tensor(3), draws=draws)
+    with pytest.raises(ValueError, match="integers"):
+        m.predict(data, [1.0, 5.0], draws=draws)
+    for cols in ([0, 6], [-1, 0], torch.tensor([5, 2, 7]), np.array([3, -2], dtype=np.int32)):
+        with pytest.raises(ValueError, match=r"must lie in \[0, 6\)"):
+            m.predict(data, cols, draws=draws)
+    with pytest.raises(ValueError, match="more than the 6"):
+        m.predict(data, [0, 1, 2, 3, 4, 5, 0], draws=draws)
+
+
+def test_sd_needs_two_draws():
+    m, x, draws = _cpu_model()
+    one = {n: v[:1] for n, v in draws.items()}
+    with pytest.raises(ValueError, match="at least 2 draws"):
+        m.predict({"counts": x}, [0, 1], draws=one, sd=True)
+    with pytest.raises(ValueError, match="nsamples >= 2"):
+        m.predict({"counts": x}, [0, 1], nsamples=1, sd=True)
+
+
+def test_custom_codec_raises_after_the_argument_checks():
+    m, x, draws = _cpu_model(encoder_function=lambda t: t, decoder_function=lambda t: t)
+    with pytest.raises(ValueError, match="must lie in"):
+        m.predict({"counts": x}, [0, 6], draws=draws)
+    with pytest.raises(NotImplementedError, match="predict"):
+        m.predict({"counts": x}, [0, 5], draws=draws)
+
+
+def test_a_valid_list_on_a_cpu_model_fails_like_top_k():
+    """Past the argument checks the call needs the library's context, as top_k does: the same failure, and not a
+    ValueError."""
+    m, x, draws = _cpu_model()
+    with pytest.raises(Exception) as e_topk:
+        m.top_k({"counts": x}, k=3, draws=draws)
+    for cols in (None, [5, 0, 0]):
+        with pytest.raises(Exception) as e_pred:
+            m.predict({"counts": x}, cols, draws=draws, sd=True, p_nonzero=True)
+        assert type(e_pred.value) is type(e_topk.value), (e_pred.value, e_topk.value)
+        assert not isinstance(e_pred.value, ValueError)
