@@ -21,6 +21,10 @@ Outputs next to --counts (reference :124-130), <stem> = the counts file minus
   <stem>_cellscore_<P>.npy       Z * row size factors        (:113-114)
   <stem>_genescore_<P>.npy       V * gene means              (:118-119)
   <stem>_interceptscore_<P>.npy  W * gene means              (:108-109)
+With --labels FILE.npy (one integer per cell, -1 = no group; e.g. a clustering of the neighbour graph):
+  <stem>_groupmean_<P>.npy       [groups, genes] posterior predictive mean expression per group
+and, per group, the --top genes by log2 fold change against the rest (mean over the draws, with its sd and the
+share of draws beyond one doubling).  Without the flag nothing changes.
 """
 import argparse
 import os
@@ -46,6 +50,9 @@ def build_parser():
     p.add_argument("--rel-tol", type=float, default=1e-3)
     p.add_argument("--top", type=int, default=10, help="genes listed per factor")
     p.add_argument("--seed", type=int, default=None)
+    p.add_argument("--labels", default=None, help="FILE.npy: a group per cell (-1: none); adds the group means "
+                                                  "and the marker genes per group")
+    p.add_argument("--group-draws", type=int, default=32, help="posterior draws of the group means")
     return p
 
 
@@ -118,7 +125,30 @@ def main(argv=None):
         print(f"factor {p}: " + ", ".join(f"{gene_names[j]}({gene_score[p, j]:.3g})" for j in top))
     top = np.argsort(W[0, :])[::-1][:P * args.top]                                     # :174-175
     print("intercept: " + ", ".join(str(gene_names[j]) for j in top))
+    if args.labels is not None:
+        group_table(factor, X, np.load(args.labels), gene_names, f"{stem}_groupmean_{P}.npy", args)
     return losses
+
+
+def group_table(factor, X, labels, gene_names, path, args):
+    """The marker-gene table: group means over the posterior draws and the log fold change of every group
+    against the rest."""
+    from spmf_amd import groups
+    res = factor.group_means({factor.count_key: X}, labels, nsamples=args.group_draws)
+    np.save(path, res["mean"].cpu().numpy())
+    count = res["count"].cpu().numpy()
+    filled = [g for g in range(len(count)) if count[g] > 0]
+    for g in filled:
+        rest = tuple(h for h in filled if h != g)
+        if not rest:
+            print(f"group {g} ({count[g]} cells): no other group to compare with")
+            continue
+        c = groups.contrast(res, g, rest)
+        lfc, share = c["lfc"].cpu().numpy(), c["p_abs_gt"].cpu().numpy()
+        sd = c["sd"].cpu().numpy() if "sd" in c else np.zeros_like(lfc)
+        top = np.argsort(lfc)[::-1][:args.top]
+        print(f"group {g} ({count[g]} cells): " + ", ".join(
+            f"{gene_names[j]}({lfc[j]:+.2f}+-{sd[j]:.2f}, {share[j]:.2f})" for j in top))
 
 
 if __name__ == "__main__":

@@ -664,6 +664,43 @@ int spmf_predict_columns(spmf_ctx* ctx, const spmf_counts* counts, int S,
                          float* mean_out, float* sd_out, float* pnz_out,
                          void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- per-group sums of the predictions (added within ABI 6: two new entry points, no struct changed) ----
+ * The posterior predictive reduced over the rows of the batch `counts`, per draw: with r_s and m_s as for
+ * spmf_predict_columns, for every draw s < S, group g < n_groups and listed column j
+ *   sum_out[s][g][j]     += sum over the rows b with labels[b] == g of m_s(b, cols[j]);
+ *   nonzero_out[s][g][j] += the same sum of -expm1(-r_s) on a Poisson column (the expected number of rows
+ *                           with x > 0), of m_s on a Bernoulli one
+ * without a [n_rows][n_cols] block (csrc/groups.hip).  Both are [S][n_groups][n_cols] fp64, device, and are
+ * ADDED to: the caller zeroes them, and batches and row chunks accumulate (as sums6 of
+ * spmf_waic_accumulate); nonzero_out may be NULL.  All additions are fp64: every fp32 m_s is converted
+ * before its first addition, no fp32 partial sums and no floating-point atomics.  The order of the
+ * additions is a function of (n_rows, S, n_groups, n_cols) and the labels alone: rows in ascending order
+ * inside 64-row blocks of a group, blocks in ascending order; two calls return the same bits.
+ * labels: [n_rows] int32, device; a value outside [0, n_groups) is "no group": the row is in no sum.  A
+ * row with a NaN count makes the sums of ITS group NaN in every draw and column and touches no other
+ * group; in no group it changes nothing.  cols == NULL: all columns, n_cols must be D.  Otherwise cols
+ * lists 0 <= n_cols <= D columns as for spmf_predict_columns; a listed column outside [0, D) makes its
+ * output column NaN (of the groups that have rows).
+ * params: only u, v, w, s (slots 2, 0, 1, 7) are read, each with the leading axis S.
+ * scratch: 256-byte aligned, at least spmf_groups_scratch_bytes(ctx, counts->n_rows, S, n_groups, n_cols)
+ * bytes: the draw stage's scratch, the row order (about n_rows / 1024 * n_groups + n_rows + 80 * n_groups
+ * int32), the encoded rows once more in group order (S * (n_rows + 64 * n_groups) * KP floats), the
+ * compacted tables of the list and the partial sums of a column range, at most 16 MiB unless a single
+ * 64-column block needs more: the entry walks column ranges.  The size is 0 for bad arguments.
+ * SPMF_E_ARG for the draw stage's errors (S outside 1..65535, NULL params / eta / scratch, a misaligned
+ * scratch, a mixed context without column types, a struct_size mismatch), n_groups < 1, n_cols outside
+ * 0..D, cols == NULL with n_cols != D, NULL labels or sum_out with work to do; SPMF_E_UNSUPPORTED for
+ * n_groups > 2^24; then SPMF_E_WORKSPACE for a short scratch, naming the need; every error returns before
+ * any launch or write.  n_cols == 0 or n_rows == 0 returns SPMF_OK without work.  The context's workspace
+ * is not touched.  Stream-ordered, synchronises nowhere.  K as for spmf_waic_accumulate. */
+size_t spmf_groups_scratch_bytes(const spmf_ctx* ctx, int64_t n_rows, int S, int32_t n_groups,
+                                 int32_t n_cols);
+int spmf_group_sums(spmf_ctx* ctx, const spmf_counts* counts, int S,
+                    const float* const params[SPMF_NVARS], const float* eta,
+                    const int32_t* labels, int32_t n_groups, int32_t n_cols, const int32_t* cols,
+                    double* sum_out, double* nonzero_out,
+                    void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- posterior mean encoding (added within ABI 6: two new entry points, no struct changed) ----
  * The rows of the batch `counts` in the latent space: mean_out[b][k] = (1/S) sum_s z_sb[k], k < K,
  * where z_sb is the encode sweep of draw s (what spmf_encode computes from u_s, s_s), fp32, the sum in

@@ -1170,8 +1170,8 @@ int spmf_dense_ll(spmf_ctx* c, const spmf_counts* ct, const float* u, const floa
 }
 
 // ---- the draw stage of the streaming calls ---------------------------------------------------
-// spmf_waic_accumulate, spmf_topk_rows, spmf_score_cells, spmf_rank_cells, spmf_predict_columns and
-// spmf_embed_rows are one stage and a consumer each.
+// spmf_waic_accumulate, spmf_topk_rows, spmf_score_cells, spmf_rank_cells, spmf_predict_columns,
+// spmf_group_sums and spmf_embed_rows are one stage and a consumer each.
 // The stage: for S draws the per-draw tables (prep) and the encoded rows z[S,B,KP] go into the caller's scratch; the consumer
 // kernel then reads z, V' and phi of every draw (kernels.h DrawTables).  The context's workspace is not used, so
 // a step that is bound (or half way: spmf_step_begin .. spmf_step_end) keeps everything it has.
@@ -1451,6 +1451,80 @@ int spmf_predict_columns(spmf_ctx* c, const spmf_counts* ct, int S, const float*
   pa.Vc = (float*)(base + pc.Vc); pa.phic = (float*)(base + pc.phic); pa.ctc = (uint8_t*)(base + pc.ctc);
   pa.mean = mean_out; pa.sd = sd_out; pa.pnz = pnz_out;
   if (!launch_panel(pa, st)) return fail(c, SPMF_E_UNSUPPORTED, "predict_columns: no kernel for this K / likelihood");
+  HIPCHK(c, hipGetLastError());
+  return SPMF_OK;
+}
+
+// ---- per-group sums of the predictions over the rows (groups.hip) ------------------------------
+// Scratch of one call: the draw carve and, behind it, the ordering (chunk table, ranks, counts, offsets, block
+// records, the padded row order), the rows z in that order, the compacted tables of a listed panel sized for
+// n_cols, and the partial sums of one column range (kernels.h group_geom bounds them).
+constexpr int32_t kGroupMaxGroups = 1 << 24;
+struct GroupCarve {
+  size_t tbl, lrank, cnt, boff, fincl, rec, perm, zs, Vc, phic, ctc, part, total;
+  GroupGeom q;
+};
+static GroupCarve group_carve(const spmf_ctx* c, int64_t rows, int S, int G, int C) {
+  GroupCarve k;
+  k.q = group_geom(rows, S, G, C);
+  const size_t KP = c->KP, nS = S, nG = G, nC = C, NB = (size_t)k.q.NB;
+  size_t o = draw_carve(c, rows, S).total;
+  k.tbl = o;   o += al((size_t)k.q.chunks * nG * sizeof(int32_t));
+  k.lrank = o; o += al((size_t)rows * sizeof(int32_t));
+  k.cnt = o;   o += al(nG * sizeof(int32_t));
+  k.boff = o;  o += al((nG + 1) * sizeof(int32_t));
+  k.fincl = o; o += al(nG * sizeof(int32_t));
+  k.rec = o;   o += al(NB * sizeof(int4));
+  k.perm = o;  o += al(NB * 64 * sizeof(int32_t));
+  k.zs = o;    o += al(nS * NB * 64 * KP * sizeof(float));
+  k.Vc = o;    o += al(nS * nC * KP * sizeof(float));
+  k.phic = o;  o += al(nS * nC * sizeof(float));
+  k.ctc = o;   o += al(nC);
+  k.part = o;  o += al(k.q.part_bytes);
+  k.total = o;
+  return k;
+}
+
+size_t spmf_groups_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S, int32_t n_groups, int32_t n_cols) {
+  if (!c || n_rows < 0 || S < 1 || n_groups < 1 || n_groups > kGroupMaxGroups || n_cols < 0 || n_cols > c->D)
+    return 0;
+  return group_carve(c, n_rows, S, n_groups, n_cols).total;
+}
+
+int spmf_group_sums(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS],
+    const float* eta, const int32_t* labels, int32_t n_groups, int32_t n_cols, const int32_t* cols,
+    double* sum_out, double* nonzero_out, void* scratch, size_t scratch_bytes, void* stream) {
+  // (the scratch's size depends on n_groups and n_cols: it is checked below, behind the call's own arguments)
+  int rc = draw_check(c, "group_sums", ct, S, 1, params, eta, scratch, (size_t)-1, spmf_embed_scratch_bytes);
+  if (rc) return rc;
+  if (n_groups < 1) return fail(c, SPMF_E_ARG, "group_sums: n_groups must be at least 1");
+  if (n_cols < 0 || n_cols > c->D) return fail(c, SPMF_E_ARG, "group_sums: n_cols must be in 0..D");
+  if (!cols && n_cols != c->D) return fail(c, SPMF_E_ARG, "group_sums: cols == NULL is all columns: n_cols must "
+      "be D");
+  if (n_groups > kGroupMaxGroups) return fail(c, SPMF_E_UNSUPPORTED, "group_sums: n_groups above 2^24");
+  const GroupCarve k = group_carve(c, ct->n_rows, S, n_groups, n_cols);
+  if (k.total > scratch_bytes) {
+    char b[200];
+    snprintf(b, sizeof b, "group_sums: scratch too small: need %zu bytes for rows=%lld S=%d groups=%d cols=%d, "
+        "have %zu", k.total, (long long)ct->n_rows, S, (int)n_groups, (int)n_cols, scratch_bytes);
+    return fail(c, SPMF_E_WORKSPACE, b);
+  }
+  const bool work = n_cols > 0 && ct->n_rows > 0;
+  if (work && (!labels || !sum_out)) return fail(c, SPMF_E_ARG, "group_sums: labels and sum_out must be set");
+  if (!work) return SPMF_OK;
+  hipStream_t st = (hipStream_t)stream;
+  GroupArgs ga{};
+  rc = draw_stage(c, "group_sums", ct, S, params, eta, scratch, st, ga.t);
+  if (rc) return rc;
+  char* base = (char*)scratch;
+  ga.n_groups = n_groups; ga.n_cols = n_cols; ga.labels = labels; ga.cols = cols;
+  ga.sum = sum_out; ga.nonzero = nonzero_out;
+  ga.tbl = (int32_t*)(base + k.tbl); ga.lrank = (int32_t*)(base + k.lrank); ga.cnt = (int32_t*)(base + k.cnt);
+  ga.boff = (int32_t*)(base + k.boff); ga.fincl = (int32_t*)(base + k.fincl); ga.rec = (int4*)(base + k.rec);
+  ga.perm = (int32_t*)(base + k.perm); ga.zs = (float*)(base + k.zs);
+  ga.Vc = (float*)(base + k.Vc); ga.phic = (float*)(base + k.phic); ga.ctc = (uint8_t*)(base + k.ctc);
+  ga.part = (double*)(base + k.part);
+  if (!launch_groups(ga, st)) return fail(c, SPMF_E_UNSUPPORTED, "group_sums: no kernel for this K / likelihood");
   HIPCHK(c, hipGetLastError());
   return SPMF_OK;
 }

@@ -327,6 +327,42 @@ struct PanelArgs {
   float *mean, *sd, *pnz;          // [B][n_cols]; sd (S >= 2) and pnz may be null
 };
 bool launch_panel(const PanelArgs& a, hipStream_t st);
+// panel.hip: the gather of a listed panel alone, for all t.S draws: Vc[s][j] = t.Vp[s][cols[j]], phic likewise
+// (NaN for a column outside [0, t.D)), ctc[j] = t.ctype[cols[j]] (ctc may be null)
+void launch_panel_gather(const DrawTables& t, int C, const int32_t* cols, float* Vc, float* phic, uint8_t* ctc,
+                         hipStream_t st);
+// groups.hip: per draw, group and column the fp64 sum over the group's rows of the posterior predictive mean m_s
+// and, where asked for, of P(x > 0), added onto sum / nonzero [S][n_groups][n_cols].  labels [B]: a value outside
+// [0, n_groups) is no group.  cols as in PanelArgs.  The scratch pointers are api.hip's carve, sized from
+// group_geom, a pure function of (B, S, G, C): the order of every sum depends on the call's arguments alone.
+// false: KP / lik not built (nothing launched).
+constexpr int kGroupRowChunk = 1024;     // rows per workgroup of the ordering's rank kernel
+constexpr int kGroupDrawChunk = 8;       // draws per workgroup of group_kernel
+constexpr int kGroupTargetBlocks = 4096; // runs x column blocks aimed at (a constant: not the device's CU count)
+// bytes of the partial sums when not all columns fit: a range then has about budget / (16 * 8 * 64) = 2048
+// workgroups per 8 draws, enough for the device, and a test can reach the walk over ranges
+constexpr size_t kGroupPartBudget = (size_t)16 << 20;
+struct GroupGeom {
+  int64_t NB, chunks, nseg;        // row blocks (bound: ceil(B / 64) + G), rank chunks, segments (bound: min(run
+                                   // target, NB) + G >= runs + G, non-decreasing in B)
+  int runs, RB, CR;                // runs of RB row blocks; columns per range (a multiple of 64)
+  size_t part_bytes;
+};
+GroupGeom group_geom(int64_t B, int S, int G, int C);
+struct GroupArgs {
+  DrawTables t;
+  int n_groups, n_cols;
+  const int32_t* labels;           // [B]
+  const int32_t* cols;             // [n_cols] or null
+  double *sum, *nonzero;           // [S][n_groups][n_cols], accumulated; nonzero may be null
+  int32_t *tbl, *lrank, *cnt, *boff, *fincl, *perm;   // [chunks][G], [B], [G], [G + 1], [G], [64 NB]
+  int4* rec;                       // [NB]
+  float* zs;                       // [S][64 NB][KP]
+  float *Vc, *phic;                // as PanelArgs (cols set)
+  uint8_t* ctc;
+  double* part;                    // part_bytes
+};
+bool launch_groups(const GroupArgs& a, hipStream_t st);
 bool launch_col_pass(int KP, const ColArgs& a, hipStream_t st);   // true: launched, with the pack block if asked
 bool launch_col_widek(int KP, const ColArgs& a, hipStream_t st);  // KP = 128, 256 (widek.hip)
 

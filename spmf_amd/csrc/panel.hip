@@ -111,16 +111,21 @@ __global__ __launch_bounds__(256) void panel_kernel(int64_t B, int C, int KP, in
   }
 }
 
+void launch_panel_gather(const DrawTables& t, int C, const int32_t* cols, float* Vc, float* phic, uint8_t* ctc,
+                         hipStream_t st) {
+  const int64_t n4 = (int64_t)C * (t.KP / 4);
+  hipLaunchKernelGGL(panel_gather_kernel, dim3((unsigned)((n4 + 255) / 256), (unsigned)t.S), dim3(256), 0, st, t.D,
+                     C, t.KP, cols, t.Vp, t.phi, t.ctype, Vc, phic, ctc);
+}
+
 bool launch_panel(const PanelArgs& a, hipStream_t st) {
   DrawTables t = a.t;
   const int C = a.n_cols;
   if (!with_kc(t.KP, [](auto) {}) || !with_lik(t.lik, [](auto) {})) return false;
   if (t.B <= 0 || C <= 0) return true;
   if (a.cols) {
-    const int64_t n4 = (int64_t)C * (t.KP / 4);
     uint8_t* ctc = t.lik == 3 ? a.ctc : nullptr;
-    hipLaunchKernelGGL(panel_gather_kernel, dim3((unsigned)((n4 + 255) / 256), (unsigned)t.S), dim3(256), 0, st, t.D,
-                       C, t.KP, a.cols, t.Vp, t.phi, t.ctype, a.Vc, a.phic, ctc);
+    launch_panel_gather(t, C, a.cols, a.Vc, a.phic, ctc, st);
     t.Vp = a.Vc;
     t.phi = a.phic;
     t.ctype = ctc;

@@ -604,7 +604,7 @@ class PoissonFactorization:
                 "lppd": float(lppd_i.sum()), "pwaic": float(pwaic_i.sum())}
 
     def _draw_call(self, name, draws, nsamples, min_draws, dense_alternative):
-        """What the streaming calls (waic_streaming, top_k, score_cells, rank_cells, predict, embed) hand the library's draw stage:
+        """What the streaming calls (waic_streaming, top_k, score_cells, rank_cells, predict, group_means, embed) hand the library's draw stage:
         ``(S, pin, eta_ptr, stream, KP, lib, h)``.  ``draws``: dict with 's','u','v','w' of shape [S,...]
         (None: ``surrogate_distribution.sample(nsamples)``), at least ``min_draws`` of them; ``pin`` is the
         C-ABI's twelve parameter slots and keeps the packed tensors it points into alive."""
@@ -953,6 +953,115 @@ class PoissonFactorization:
                 return p[0]
             return torch.cat(p) if p else torch.empty(0, n_cols, dtype=torch.float32, device=self.device)
         res = {n: cat(parts[n]) for n in names}
+        if cols is not None:
+            res["columns"] = cols
+        return res
+
+    _GROUP_OUT_CAP = 1 << 30          # bytes of one [S, G, C] fp64 output of group_means
+
+    def _group_labels(self, name, data, labels, n_groups):
+        """The labels of ``group_means`` (``name``), checked before any library call: 1-D integers in
+        {-1, 0 .. n_groups - 1}, one per row of all batches.  The rows are counted off the batches' shapes: a
+        factory is called once for the count and once for the run, a list is walked twice, and no batch is kept
+        alive in between; a one-shot iterator cannot be walked twice, so its length is checked as its batches
+        arrive (``counted`` False).  -> (int32 labels on the device, n_groups, counted)."""
+        if not isinstance(labels, torch.Tensor):
+            labels = np.asarray(labels)
+            if labels.size == 0 and labels.ndim == 1:       # [] has no dtype of its own
+                labels = labels.astype(np.int64)
+            labels = torch.as_tensor(labels)
+        if labels.dim() != 1:
+            raise ValueError(f"{name}: labels must be 1-D, got shape {tuple(labels.shape)}")
+        if labels.dtype.is_floating_point or labels.dtype == torch.bool:
+            raise ValueError(f"{name}: labels must hold integers, got {labels.dtype}")
+        if callable(data):
+            batches = data()
+        elif isinstance(data, (dict, SparseCounts)) or hasattr(data, "shape"):
+            batches = (data,)
+        else:
+            batches = data
+        counted = callable(data) or iter(batches) is not batches
+        if counted:
+            n_rows = sum(self._batch_rows(b) for b in batches)
+            if int(labels.numel()) != n_rows:
+                raise ValueError(f"{name}: labels must have one entry per row, got {int(labels.numel())} for "
+                                 f"{n_rows} rows")
+        lo, hi = (int(labels.min()), int(labels.max())) if labels.numel() else (-1, -1)
+        if n_groups is None:
+            n_groups = hi + 1
+        n_groups = int(n_groups)
+        if n_groups < 1:
+            raise ValueError(f"{name}: n_groups must be at least 1, got {n_groups}")
+        if lo < -1 or hi >= n_groups:
+            raise ValueError(f"{name}: labels must lie in [-1, {n_groups}) (-1: no group), got {lo} .. {hi}")
+        return labels.to(device=self.device, dtype=torch.int32).contiguous(), n_groups, counted
+
+    def group_means(self, data, labels, n_groups=None, cols=None, nsamples=32, draws=None, p_nonzero=False,
+                    max_rows=None):
+        """The posterior predictive reduced over rows: per draw, the mean over the rows of every group of
+        m_s(b, d) -- the cell of ``predict`` for draw s, the rate on a Poisson column and sigmoid(logit) on a
+        Bernoulli one -- without a [rows, C] block per draw (csrc/groups.hip).  What a cluster, cell type or
+        segment expresses, with the draws kept apart so that a non-linear contrast between groups
+        (``spmf_amd.groups.contrast``: a log fold change) has a posterior of its own.
+
+        ``data``, ``draws``, ``cols`` and ``max_rows`` as in ``predict``; batches are streamed, never held
+        together (a factory is called twice, first for the row count alone; for a one-shot iterator the length
+        of ``labels`` is checked batch by batch instead of up front).  ``labels``: 1-D integers, numpy or torch on any device, one per row of all batches in
+        arrival order, in {-1, 0 .. n_groups - 1}; -1 is "no group".  ``n_groups`` defaults to
+        max(labels) + 1.  ``p_nonzero=True`` adds the expected fraction of the group with x > 0 (the sum of
+        ``predict``'s P(x > 0) terms per draw).
+
+        Returns device tensors: 'draws' fp64 [S, G, C] (sum / count), 'mean' [G, C] and, with two draws or
+        more, 'sd' [G, C] (unbiased) over the draws, 'count' int64 [G], 'sum' fp64 [S, G, C] (the raw sums:
+        shards add up), with ``p_nonzero`` 'p_nonzero_draws' [S, G, C] / 'p_nonzero' [G, C] and their raw
+        sums 'sum_nonzero', with a list 'columns'.  An empty group has NaN means and count 0.  A row with a NaN count makes its own group
+        NaN and no other.  Every sum is fp64 from the first addition on, in an order fixed by the arguments:
+        bit-reproducible; ``max_rows`` and the split into batches change the order of the fp64 additions
+        only.  Memory: each [S, G, C] array is S * G * C * 8 bytes and at most 1 GiB -- bound it with
+        ``cols``.  ``max_rows`` bounds the two copies of the encoded rows and the per-row part of the ordering;
+        the scratch also holds 64 pad rows per group (S * 64 * G * K floats), which no row limit bounds."""
+        labels, G, _ = self._group_labels("group_means", data, labels, n_groups)
+        cols = self._column_list("group_means", cols)
+        n_cols = self.feature_dim if cols is None else int(cols.numel())
+        if draws is not None and self._custom_codec is None:
+            n_draws = int(next(iter(draws.values())).shape[0])
+        else:
+            n_draws = int(nsamples)
+        if n_draws * G * n_cols * 8 > self._GROUP_OUT_CAP:
+            raise ValueError(f"group_means: an output of {n_draws} draws x {G} groups x {n_cols} columns is "
+                             f"{n_draws * G * n_cols * 8} bytes, above the cap of {self._GROUP_OUT_CAP}: pass "
+                             "fewer columns at a time with cols")
+        S, pin, eta, stream, KP, lib, h = self._draw_call("group_means", draws, nsamples, 1, "predict")
+        total = torch.zeros(S, G, n_cols, dtype=torch.float64, device=self.device)
+        nonzero = torch.zeros_like(total) if p_nonzero else None
+        scratch, off = _Scratch(self.device), 0
+        # per row: the encoded rows twice (arrival order, group order), rank and slot, its share of the chunk table
+        row_bytes = 2 * S * KP * 4 + 8 + (G + 1023) // 1024 * 4
+        for n_rows, chunks in self._row_chunks(data, row_bytes, max_rows):
+            if off + n_rows > int(labels.numel()):
+                raise ValueError(f"group_means: labels must have one entry per row, got {int(labels.numel())} "
+                                 f"for at least {off + n_rows} rows")
+            for r0, sub in chunks if n_cols else ():
+                _lib.check(h, lib.spmf_group_sums(
+                    h, C.byref(sub), S, pin, eta, labels[off + r0:].data_ptr(), G, n_cols,
+                    cols.data_ptr() if cols is not None else None, total.data_ptr(),
+                    nonzero.data_ptr() if nonzero is not None else None,
+                    *scratch.fit(lib.spmf_groups_scratch_bytes(h, int(sub.n_rows), S, G, n_cols)), stream),
+                    "spmf_group_sums")
+            off += n_rows
+        if off != int(labels.numel()):
+            raise ValueError(f"group_means: labels must have one entry per row, got {int(labels.numel())} for "
+                             f"{off} rows")
+        count = torch.bincount(labels[labels >= 0].to(torch.int64), minlength=G)
+        n = count.to(torch.float64).masked_fill(count == 0, float("nan"))[None, :, None]
+        res = {"draws": total / n, "count": count, "sum": total}
+        res["mean"] = res["draws"].mean(0)
+        if S >= 2:
+            res["sd"] = res["draws"].std(0, unbiased=True)
+        if nonzero is not None:
+            res["sum_nonzero"] = nonzero
+            res["p_nonzero_draws"] = nonzero / n
+            res["p_nonzero"] = res["p_nonzero_draws"].mean(0)
         if cols is not None:
             res["columns"] = cols
         return res
