@@ -1171,11 +1171,14 @@ int spmf_dense_ll(spmf_ctx* c, const spmf_counts* ct, const float* u, const floa
 
 // ---- the draw stage of the streaming calls ---------------------------------------------------
 // spmf_waic_accumulate, spmf_topk_rows, spmf_score_cells, spmf_rank_cells, spmf_predict_columns,
-// spmf_group_sums and spmf_embed_rows are one stage and a consumer each.
-// The stage: for S draws the per-draw tables (prep) and the encoded rows z[S,B,KP] go into the caller's scratch; the consumer
-// kernel then reads z, V' and phi of every draw (kernels.h DrawTables).  The context's workspace is not used, so
-// a step that is bound (or half way: spmf_step_begin .. spmf_step_end) keeps everything it has.
+// spmf_group_sums and spmf_embed_rows are one stage and a consumer each (spmf_knn, at the end of the section,
+// takes rows as given and shares the scratch and launch helpers only).
+// The stage: for S draws the per-draw tables (prep) and the encoded rows z[S,B,KP] go into the caller's scratch;
+// the consumer kernel then reads z, V' and phi of every draw (kernels.h DrawTables).  The context's workspace is
+// not used, so a step that is bound (or half way: spmf_step_begin .. spmf_step_end) keeps everything it has.
 // Scratch of a call = the draw carve + the consumer's own buffers behind it.
+// An entry is: draw_check, its own argument checks, its empty returns, draw_stage, its carve, `launched`.  What
+// two entries need alike is written once: scratch_too_small, check_column_list, panel_tables, stored_bits.
 struct DrawCarve {
   size_t Ap, Vp, phi, dprep, dacc, z, total;
 };
@@ -1191,6 +1194,22 @@ static DrawCarve draw_carve(const spmf_ctx* c, int64_t rows, int S) {
   k.z = o;     o += al(nS * (size_t)rows * KP * sizeof(float));
   k.total = o;
   return k;
+}
+
+// The SPMF_E_WORKSPACE failure of a call `fn` whose scratch holds `have` bytes of the `need` its size function
+// returns for the shape `detail` ("rows=70 S=2").
+static int scratch_too_small(spmf_ctx* c, const char* fn, size_t need, size_t have, const std::string& detail) {
+  return fail(c, SPMF_E_WORKSPACE, std::string(fn) + ": scratch too small: need " + std::to_string(need) +
+      " bytes for " + detail + ", have " + std::to_string(have));
+}
+static std::string rows_S(const spmf_counts* ct, int S) {
+  return "rows=" + std::to_string((long long)ct->n_rows) + " S=" + std::to_string(S);
+}
+// The end of every entry: `ok` is what its launcher returned, `no_kernel` the entry's text for false.
+static int launched(spmf_ctx* c, bool ok, const char* no_kernel) {
+  if (!ok) return fail(c, SPMF_E_UNSUPPORTED, no_kernel);
+  HIPCHK(c, hipGetLastError());
+  return SPMF_OK;
 }
 
 // What every streaming call `fn` checks before anything is launched: S in min_S..65535, the shared pointers, the
@@ -1215,12 +1234,7 @@ static int draw_check(spmf_ctx* c, const char* fn, const spmf_counts* ct, int S,
   // 31-bit grid extent, a listed cell's row an int32
   if (ct->n_rows > ((int64_t)1 << 31) - 64) return fail(c, SPMF_E_ARG, f + "too many rows in one call");
   const size_t total = need(c, ct->n_rows, S);
-  if (total > scratch_bytes) {
-    char b[160];
-    snprintf(b, sizeof b, "%s: scratch too small: need %zu bytes for rows=%lld S=%d, have %zu", fn, total,
-        (long long)ct->n_rows, S, scratch_bytes);
-    return fail(c, SPMF_E_WORKSPACE, b);
-  }
+  if (total > scratch_bytes) return scratch_too_small(c, fn, total, scratch_bytes, rows_S(ct, S));
   return SPMF_OK;
 }
 
@@ -1256,9 +1270,7 @@ int spmf_waic_accumulate(spmf_ctx* c, const spmf_counts* ct, int S, const float*
   rc = draw_stage(c, "waic_accumulate", ct, S, params, eta, scratch, st, dt);
   if (rc || ct->n_rows == 0) return rc;
   WaicArgs wa{dt, ct->nnz, ct->row_ptr, ct->col_idx, ct->val, sums6, row_out};
-  if (!launch_waic(wa, st)) return fail(c, SPMF_E_UNSUPPORTED, "waic_accumulate: no kernel for this K / likelihood");
-  HIPCHK(c, hipGetLastError());
-  return SPMF_OK;
+  return launched(c, launch_waic(wa, st), "waic_accumulate: no kernel for this K / likelihood");
 }
 
 // ---- streaming per-row top-k of the posterior predictive mean (topk.hip) ---------------------
@@ -1307,6 +1319,16 @@ static TopkCarve topk_carve(const spmf_ctx* c, int64_t rows, int S) {
   return k;
 }
 
+// The bitmap inside a checked call's scratch, zeroed on the stream, when flag bit 0 (exclude stored cells) is
+// set; `stored` stays NULL otherwise.
+static int stored_bits(spmf_ctx* c, unsigned flags, void* scratch, const TopkCarve& tc, int64_t rows,
+    hipStream_t st, uint32_t*& stored) {
+  if (!(flags & 1u)) return SPMF_OK;
+  stored = (uint32_t*)((char*)scratch + tc.bits);
+  HIPCHK(c, hipMemsetAsync(stored, 0, stored_bits_bytes(c, rows), st));
+  return SPMF_OK;
+}
+
 size_t spmf_topk_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S) {
   if (!c || n_rows < 0 || S < 1) return 0;
   return topk_carve(c, n_rows, S).total;
@@ -1327,15 +1349,11 @@ int spmf_topk_rows(spmf_ctx* c, const spmf_counts* ct, int S, const float* const
   char* base = (char*)scratch;
   ta.nnz = ct->nnz; ta.k = k; ta.slices = tc.slices;
   ta.row_ptr = ct->row_ptr; ta.col = ct->col_idx;
-  if (flags & 1u) {
-    ta.stored = (uint32_t*)(base + tc.bits);
-    HIPCHK(c, hipMemsetAsync(ta.stored, 0, stored_bits_bytes(c, ct->n_rows), st));
-  }
+  rc = stored_bits(c, flags, scratch, tc, ct->n_rows, st, ta.stored);
+  if (rc) return rc;
   ta.part_cols = (int32_t*)(base + tc.pcols); ta.part_scores = (float*)(base + tc.pscores);
   ta.cols = cols_out; ta.scores = score_out;
-  if (!launch_topk(ta, st)) return fail(c, SPMF_E_UNSUPPORTED, "topk_rows: no kernel for this K / likelihood");
-  HIPCHK(c, hipGetLastError());
-  return SPMF_OK;
+  return launched(c, launch_topk(ta, st), "topk_rows: no kernel for this K / likelihood");
 }
 
 // ---- posterior predictive mean / lppd of a list of cells (cells.hip) --------------------------
@@ -1363,9 +1381,7 @@ int spmf_score_cells(spmf_ctx* c, const spmf_counts* ct, int S, const float* con
   rc = draw_stage(c, "score_cells", ct, S, params, eta, scratch, st, dt);
   if (rc) return rc;
   CellsArgs ca{dt, n_cells, cell_row, cell_col, cell_val, mean_out, lppd_out};
-  if (!launch_cells(ca, st)) return fail(c, SPMF_E_UNSUPPORTED, "score_cells: no kernel for this K / likelihood");
-  HIPCHK(c, hipGetLastError());
-  return SPMF_OK;
+  return launched(c, launch_cells(ca, st), "score_cells: no kernel for this K / likelihood");
 }
 
 // ---- rank of listed cells among their row's candidates (rank.hip) ------------------------------
@@ -1393,32 +1409,39 @@ int spmf_rank_cells(spmf_ctx* c, const spmf_counts* ct, int S, const float* cons
   const TopkCarve tc = topk_carve(c, ct->n_rows, S);
   ra.nnz = ct->nnz; ra.slices = tc.slices;
   ra.row_ptr = ct->row_ptr; ra.col = ct->col_idx;
-  if (flags & 1u) {
-    ra.stored = (uint32_t*)((char*)scratch + tc.bits);
-    HIPCHK(c, hipMemsetAsync(ra.stored, 0, stored_bits_bytes(c, ct->n_rows), st));
-  }
+  rc = stored_bits(c, flags, scratch, tc, ct->n_rows, st, ra.stored);
+  if (rc) return rc;
   ra.n_cells = n_cells; ra.cell_row = cell_row; ra.cell_col = cell_col;
   ra.rank = rank_out; ra.cand = cand_out; ra.score = score_out;
-  if (!launch_rank(ra, st)) return fail(c, SPMF_E_UNSUPPORTED, "rank_cells: no kernel for this K / likelihood");
-  HIPCHK(c, hipGetLastError());
-  return SPMF_OK;
+  return launched(c, launch_rank(ra, st), "rank_cells: no kernel for this K / likelihood");
 }
 
 // ---- predictions of a panel of columns (panel.hip) ---------------------------------------------
-// Scratch of one call: the draw carve and, behind it, the compacted tables of a listed panel in a region of
-// their own (the carve's Ap is not reused), sized for n_cols = D: the size does not depend on the list.
+// The compacted tables of a panel of C listed columns for S draws (V' rows, phi, the column types), three
+// regions from offset `o` of a scratch on; `total` is where they end.  spmf_group_sums carves them too.
 struct PanelCarve {
   size_t Vc, phic, ctc, total;
 };
-static PanelCarve panel_carve(const spmf_ctx* c, int64_t rows, int S) {
+static PanelCarve panel_tables(const spmf_ctx* c, size_t o, int S, int C) {
   PanelCarve k;
-  const size_t KP = c->KP, D = c->D, nS = S;
-  size_t o = draw_carve(c, rows, S).total;
-  k.Vc = o;   o += al(nS * D * KP * sizeof(float));
-  k.phic = o; o += al(nS * D * sizeof(float));
-  k.ctc = o;  o += al(D);
+  const size_t KP = c->KP, nS = S, nC = C;
+  k.Vc = o;   o += al(nS * nC * KP * sizeof(float));
+  k.phic = o; o += al(nS * nC * sizeof(float));
+  k.ctc = o;  o += al(nC);
   k.total = o;
   return k;
+}
+// Scratch of one call: the draw carve and, behind it, the compacted tables in a region of their own (the carve's
+// Ap is not reused), sized for n_cols = D: the size does not depend on the list.
+static PanelCarve panel_carve(const spmf_ctx* c, int64_t rows, int S) {
+  return panel_tables(c, draw_carve(c, rows, S).total, S, c->D);
+}
+// The column list of a call `fn`: n_cols in 0..D, and no list is all D columns.
+static int check_column_list(spmf_ctx* c, const char* fn, int32_t n_cols, const int32_t* cols) {
+  const std::string f = std::string(fn) + ": ";
+  if (n_cols < 0 || n_cols > c->D) return fail(c, SPMF_E_ARG, f + "n_cols must be in 0..D");
+  if (!cols && n_cols != c->D) return fail(c, SPMF_E_ARG, f + "cols == NULL is all columns: n_cols must be D");
+  return SPMF_OK;
 }
 
 size_t spmf_predict_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S) {
@@ -1431,9 +1454,8 @@ int spmf_predict_columns(spmf_ctx* c, const spmf_counts* ct, int S, const float*
     void* scratch, size_t scratch_bytes, void* stream) {
   int rc = draw_check(c, "predict_columns", ct, S, 1, params, eta, scratch, scratch_bytes, spmf_predict_scratch_bytes);
   if (rc) return rc;
-  if (n_cols < 0 || n_cols > c->D) return fail(c, SPMF_E_ARG, "predict_columns: n_cols must be in 0..D");
-  if (!cols && n_cols != c->D) return fail(c, SPMF_E_ARG, "predict_columns: cols == NULL is all columns: n_cols "
-      "must be D");
+  rc = check_column_list(c, "predict_columns", n_cols, cols);
+  if (rc) return rc;
   if (sd_out && S < 2) return fail(c, SPMF_E_ARG, "predict_columns: sd_out needs S >= 2 (the deviation over the "
       "draws)");
   const bool work = n_cols > 0 && ct->n_rows > 0;
@@ -1450,24 +1472,23 @@ int spmf_predict_columns(spmf_ctx* c, const spmf_counts* ct, int S, const float*
   pa.n_cols = n_cols; pa.cols = cols;
   pa.Vc = (float*)(base + pc.Vc); pa.phic = (float*)(base + pc.phic); pa.ctc = (uint8_t*)(base + pc.ctc);
   pa.mean = mean_out; pa.sd = sd_out; pa.pnz = pnz_out;
-  if (!launch_panel(pa, st)) return fail(c, SPMF_E_UNSUPPORTED, "predict_columns: no kernel for this K / likelihood");
-  HIPCHK(c, hipGetLastError());
-  return SPMF_OK;
+  return launched(c, launch_panel(pa, st), "predict_columns: no kernel for this K / likelihood");
 }
 
 // ---- per-group sums of the predictions over the rows (groups.hip) ------------------------------
 // Scratch of one call: the draw carve and, behind it, the ordering (chunk table, ranks, counts, offsets, block
 // records, the padded row order), the rows z in that order, the compacted tables of a listed panel sized for
-// n_cols, and the partial sums of one column range (kernels.h group_geom bounds them).
+// n_cols (panel_tables), and the partial sums of one column range (kernels.h group_geom bounds them).
 constexpr int32_t kGroupMaxGroups = 1 << 24;
 struct GroupCarve {
-  size_t tbl, lrank, cnt, boff, fincl, rec, perm, zs, Vc, phic, ctc, part, total;
+  size_t tbl, lrank, cnt, boff, fincl, rec, perm, zs, part, total;
+  PanelCarve p;
   GroupGeom q;
 };
 static GroupCarve group_carve(const spmf_ctx* c, int64_t rows, int S, int G, int C) {
   GroupCarve k;
   k.q = group_geom(rows, S, G, C);
-  const size_t KP = c->KP, nS = S, nG = G, nC = C, NB = (size_t)k.q.NB;
+  const size_t KP = c->KP, nS = S, nG = G, NB = (size_t)k.q.NB;
   size_t o = draw_carve(c, rows, S).total;
   k.tbl = o;   o += al((size_t)k.q.chunks * nG * sizeof(int32_t));
   k.lrank = o; o += al((size_t)rows * sizeof(int32_t));
@@ -1477,9 +1498,8 @@ static GroupCarve group_carve(const spmf_ctx* c, int64_t rows, int S, int G, int
   k.rec = o;   o += al(NB * sizeof(int4));
   k.perm = o;  o += al(NB * 64 * sizeof(int32_t));
   k.zs = o;    o += al(nS * NB * 64 * KP * sizeof(float));
-  k.Vc = o;    o += al(nS * nC * KP * sizeof(float));
-  k.phic = o;  o += al(nS * nC * sizeof(float));
-  k.ctc = o;   o += al(nC);
+  k.p = panel_tables(c, o, S, C);
+  o = k.p.total;
   k.part = o;  o += al(k.q.part_bytes);
   k.total = o;
   return k;
@@ -1498,17 +1518,12 @@ int spmf_group_sums(spmf_ctx* c, const spmf_counts* ct, int S, const float* cons
   int rc = draw_check(c, "group_sums", ct, S, 1, params, eta, scratch, (size_t)-1, spmf_embed_scratch_bytes);
   if (rc) return rc;
   if (n_groups < 1) return fail(c, SPMF_E_ARG, "group_sums: n_groups must be at least 1");
-  if (n_cols < 0 || n_cols > c->D) return fail(c, SPMF_E_ARG, "group_sums: n_cols must be in 0..D");
-  if (!cols && n_cols != c->D) return fail(c, SPMF_E_ARG, "group_sums: cols == NULL is all columns: n_cols must "
-      "be D");
+  rc = check_column_list(c, "group_sums", n_cols, cols);
+  if (rc) return rc;
   if (n_groups > kGroupMaxGroups) return fail(c, SPMF_E_UNSUPPORTED, "group_sums: n_groups above 2^24");
   const GroupCarve k = group_carve(c, ct->n_rows, S, n_groups, n_cols);
-  if (k.total > scratch_bytes) {
-    char b[200];
-    snprintf(b, sizeof b, "group_sums: scratch too small: need %zu bytes for rows=%lld S=%d groups=%d cols=%d, "
-        "have %zu", k.total, (long long)ct->n_rows, S, (int)n_groups, (int)n_cols, scratch_bytes);
-    return fail(c, SPMF_E_WORKSPACE, b);
-  }
+  if (k.total > scratch_bytes) return scratch_too_small(c, "group_sums", k.total, scratch_bytes,
+      rows_S(ct, S) + " groups=" + std::to_string(n_groups) + " cols=" + std::to_string(n_cols));
   const bool work = n_cols > 0 && ct->n_rows > 0;
   if (work && (!labels || !sum_out)) return fail(c, SPMF_E_ARG, "group_sums: labels and sum_out must be set");
   if (!work) return SPMF_OK;
@@ -1522,11 +1537,9 @@ int spmf_group_sums(spmf_ctx* c, const spmf_counts* ct, int S, const float* cons
   ga.tbl = (int32_t*)(base + k.tbl); ga.lrank = (int32_t*)(base + k.lrank); ga.cnt = (int32_t*)(base + k.cnt);
   ga.boff = (int32_t*)(base + k.boff); ga.fincl = (int32_t*)(base + k.fincl); ga.rec = (int4*)(base + k.rec);
   ga.perm = (int32_t*)(base + k.perm); ga.zs = (float*)(base + k.zs);
-  ga.Vc = (float*)(base + k.Vc); ga.phic = (float*)(base + k.phic); ga.ctc = (uint8_t*)(base + k.ctc);
+  ga.Vc = (float*)(base + k.p.Vc); ga.phic = (float*)(base + k.p.phic); ga.ctc = (uint8_t*)(base + k.p.ctc);
   ga.part = (double*)(base + k.part);
-  if (!launch_groups(ga, st)) return fail(c, SPMF_E_UNSUPPORTED, "group_sums: no kernel for this K / likelihood");
-  HIPCHK(c, hipGetLastError());
-  return SPMF_OK;
+  return launched(c, launch_groups(ga, st), "group_sums: no kernel for this K / likelihood");
 }
 
 // ---- posterior mean encoding of a batch (knn.hip) ---------------------------------------------
@@ -1547,9 +1560,8 @@ int spmf_embed_rows(spmf_ctx* c, const spmf_counts* ct, int S, const float* cons
   DrawTables dt;
   rc = draw_stage(c, "embed_rows", ct, S, params, eta, scratch, st, dt);
   if (rc) return rc;
-  launch_embed(dt, c->K, mean_out, sd_out, st);
-  HIPCHK(c, hipGetLastError());
-  return SPMF_OK;
+  launch_embed(dt, c->K, mean_out, sd_out, st);   // (one kernel for every K)
+  return launched(c, true, "");
 }
 
 // ---- exact k nearest rows (knn.hip) -----------------------------------------------------------
@@ -1611,12 +1623,9 @@ int spmf_knn(spmf_ctx* c, const float* q, int64_t n_query, const float* r, int64
       "knn: null argument");
   if ((uintptr_t)scratch & 255) return fail(c, SPMF_E_ARG, "knn: scratch must be 256-byte aligned");
   const KnnCarve kc = knn_carve(c, n_query, n_ref, row_len);
-  if (kc.total > scratch_bytes) {
-    char b[200];
-    snprintf(b, sizeof b, "knn: scratch too small: need %zu bytes for n_query=%lld n_ref=%lld row_len=%d, have %zu",
-        kc.total, (long long)n_query, (long long)n_ref, row_len, scratch_bytes);
-    return fail(c, SPMF_E_WORKSPACE, b);
-  }
+  if (kc.total > scratch_bytes) return scratch_too_small(c, "knn", kc.total, scratch_bytes,
+      "n_query=" + std::to_string((long long)n_query) + " n_ref=" + std::to_string((long long)n_ref) + " row_len=" +
+      std::to_string(row_len));
   if (n_query == 0) return SPMF_OK;
   char* base = (char*)scratch;
   KnnArgs ka{};
@@ -1628,9 +1637,7 @@ int spmf_knn(spmf_ctx* c, const float* q, int64_t n_query, const float* r, int64
   ka.cpart = (float*)(base + kc.cpart); ka.ccnt = (int32_t*)(base + kc.ccnt); ka.centre = (float*)(base + kc.centre);
   ka.part_idx = (int32_t*)(base + kc.pidx); ka.part_score = (float*)(base + kc.pscore);
   ka.idx = idx_out; ka.dist = dist_out;
-  if (!launch_knn(ka, (hipStream_t)stream)) return fail(c, SPMF_E_UNSUPPORTED, "knn: no kernel for this row_len / k");
-  HIPCHK(c, hipGetLastError());
-  return SPMF_OK;
+  return launched(c, launch_knn(ka, (hipStream_t)stream), "knn: no kernel for this row_len / k");
 }
 
 int spmf_nonfinite_reduce(spmf_ctx* c, int64_t n, const float* ll, int pass, double* io, void* stream) {

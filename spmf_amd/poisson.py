@@ -20,6 +20,7 @@ import torch
 from . import _lib
 from ._lib import PART_ORDER, VAR_ORDER, SpmfError
 from .sparse import SparseCounts
+from .streaming import StreamingQueries
 
 
 def var_shapes(D: int, K: int) -> Dict[str, tuple]:
@@ -33,7 +34,7 @@ def var_shapes(D: int, K: int) -> Dict[str, tuple]:
     }
 
 
-class PoissonFactorization:
+class PoissonFactorization(StreamingQueries):
     """Sparse (horseshoe) poisson matrix factorization  (poisson.py:25-29).
 
     Constructor keywords are the reference's (poisson.py:56-64), including the
@@ -603,596 +604,6 @@ class PoissonFactorization:
                 "se": float(2.0 * torch.sqrt(n * elpd_i.var(unbiased=True))),
                 "lppd": float(lppd_i.sum()), "pwaic": float(pwaic_i.sum())}
 
-    def _draw_call(self, name, draws, nsamples, min_draws, dense_alternative):
-        """What the streaming calls (waic_streaming, top_k, score_cells, rank_cells, predict, group_means, embed) hand the library's draw stage:
-        ``(S, pin, eta_ptr, stream, KP, lib, h)``.  ``draws``: dict with 's','u','v','w' of shape [S,...]
-        (None: ``surrogate_distribution.sample(nsamples)``), at least ``min_draws`` of them; ``pin`` is the
-        C-ABI's twelve parameter slots and keeps the packed tensors it points into alive."""
-        if self._custom_codec is not None:
-            raise NotImplementedError(f"{name}: custom encoder/decoder callables have no kernel "
-                                      f"(use {dense_alternative}, which evaluates them densely)")
-        why = " (the variance over the draws)" if min_draws > 1 else ""
-        if draws is None:
-            if int(nsamples) < min_draws:
-                raise ValueError(f"{name} needs nsamples >= {min_draws}{why}")
-            draws = self.surrogate_distribution.sample(int(nsamples))
-        S, P = self._pack_params(draws, names=("s", "u", "v", "w"))
-        if S < min_draws:
-            raise ValueError(f"{name} needs at least {min_draws} draws{why}")
-        lib, h = _lib.load(), self._handle()
-        pin = _lib.PtrArray(*[P[n].data_ptr() if n in P else None for n in VAR_ORDER])
-        pin.tensors = P
-        return (S, pin, self._eta_device().data_ptr(), torch.cuda.current_stream(self.device).cuda_stream,
-                int(lib.spmf_padded_k(h)), lib, h)
-
-    def waic_streaming(self, data, nsamples=100, draws=None, row_scores=False, max_rows=None):
-        """``waic`` at any size: per-cell lppd_i / pwaic_i over the draws are formed in
-        registers (csrc/waic.hip) and only their sums over the cells leave the kernel, so
-        nothing of size S*B*D or B*D is written.
-
-        ``data``: one batch (dict / counts), an iterable of batches or a data-factory
-        callable; the sums are added across batches.  ``draws``: dict with 's','u','v','w' of
-        shape [S,...] (default: ``surrogate_distribution.sample(nsamples)``), the same for every
-        batch.  ``row_scores=True`` adds 'row_lppd' / 'row_pwaic', fp64 tensors concatenated
-        over the batches.  ``max_rows`` caps the rows of one kernel call (whole panels), which
-        bounds the scratch of the encoded rows (S * rows * K floats; default 1 GiB of them).
-
-        Returns {'waic','se','lppd','pwaic','n','n_excluded'} (spmf_amd.waic.combine): a cell
-        with a non-finite log-pmf in any draw (NaN count, rate 0 under a positive count) is
-        left out of the sums and counted in 'n_excluded', where ``waic`` returns NaN / -inf."""
-        from . import waic as _waic
-        S, pin, eta, stream, KP, lib, h = self._draw_call("waic_streaming", draws, nsamples, 2, "waic()")
-        sums = torch.zeros(_waic.NSUMS, dtype=torch.float64, device=self.device)
-        scratch, rows_out = _Scratch(self.device), []
-        for n_rows, chunks in self._row_chunks(data, S * KP * 4, max_rows):
-            rows = torch.zeros(n_rows, 2, dtype=torch.float64, device=self.device) if row_scores else None
-            for r0, sub in chunks:
-                _lib.check(h, lib.spmf_waic_accumulate(
-                    h, C.byref(sub), S, pin, eta, sums.data_ptr(),
-                    rows[r0:].data_ptr() if rows is not None else None,
-                    *scratch.fit(lib.spmf_waic_scratch_bytes(h, int(sub.n_rows), S)), stream),
-                    "spmf_waic_accumulate")
-            if rows is not None:
-                rows_out.append(rows)
-        out = _waic.combine(sums)
-        if row_scores:
-            allrows = torch.cat(rows_out) if rows_out else torch.zeros(0, 2, dtype=torch.float64, device=self.device)
-            out["row_lppd"], out["row_pwaic"] = allrows[:, 0].contiguous(), allrows[:, 1].contiguous()
-        return out
-
-    def _row_chunks(self, data, row_bytes, max_rows):
-        """The batch and row-chunk iteration of the streaming calls.
-        ``data``: one batch (dict / counts), an iterable of batches or a data-factory callable; a
-        ``{"counts": sc, "panels": (p0, p1)}`` batch is the rows of those panels.  Yields
-        ``(n_rows, chunks)`` per batch; ``chunks`` yields ``(r0, sub)``: the batch struct of the
-        next non-empty chunk of whole panels and its first row inside the batch.  A chunk has at
-        most ``max_rows`` rows (default: 1 GiB of scratch at ``row_bytes`` per row)."""
-        if callable(data):
-            batches = data()
-        elif isinstance(data, (dict, SparseCounts)) or hasattr(data, "shape"):
-            batches = (data,)
-        else:
-            batches = data
-        for batch in batches:
-            sc, cs = self._batch(batch)
-            p0, p1 = sc.panel_range(batch.get("panels") if isinstance(batch, dict) else None)
-            cap = int(max_rows) if max_rows else max(1, (1 << 30) // int(row_bytes))
-            step = max(1, cap // sc.panel_rows)
-
-            def chunks(sc=sc, p0=p0, p1=p1, step=step):
-                for q0 in range(p0, p1, step):
-                    sub = sc.struct(q0, min(q0 + step, p1))
-                    if sub.n_rows == 0:
-                        continue
-                    yield (q0 - p0) * sc.panel_rows, sub
-            yield int(cs.n_rows), chunks()
-
-    def top_k(self, data, k=10, nsamples=32, draws=None, exclude_stored=True, max_rows=None):
-        """Per row the ``k`` columns with the largest posterior predictive mean
-        score_bd = mean_s m_s(b, d), m_s = the rate of draw s on a Poisson column and
-        sigmoid(logit) on a Bernoulli one, without a [B,D] array: the scores are formed and
-        selected in csrc/topk.hip and only [B,k] leaves the kernel.
-
-        ``data``, ``draws`` and ``max_rows`` as in ``waic_streaming`` (``draws`` may hold a single
-        draw, e.g. a point estimate from ``calibrated_expectations``; ``max_rows`` also bounds the
-        bitmap of the stored cells, rows * D / 8 bytes).  ``exclude_stored``: cells the batch
-        stores are no candidates.  A cell with a non-finite score is none either (a NaN count
-        takes its whole row out).
-
-        Returns {'columns': int32 [B,k], 'scores': float32 [B,k]} on the device, the rows of all
-        batches concatenated: score descending, equal scores by ascending column, a row with
-        fewer than k candidates padded with column -1 / score -inf.  Bit-reproducible."""
-        k = int(k)
-        if not 1 <= k <= 64:
-            raise ValueError("top_k needs 1 <= k <= 64")
-        S, pin, eta, stream, KP, lib, h = self._draw_call("top_k", draws, nsamples, 1, "log_likelihood_components")
-        flags = 1 if exclude_stored else 0
-        scratch, cols_out, scores_out = _Scratch(self.device), [], []
-        for n_rows, chunks in self._row_chunks(data, S * KP * 4 + (self.feature_dim + 31) // 32 * 4, max_rows):
-            cols = torch.empty(n_rows, k, dtype=torch.int32, device=self.device)
-            scores = torch.empty(n_rows, k, dtype=torch.float32, device=self.device)
-            for r0, sub in chunks:
-                _lib.check(h, lib.spmf_topk_rows(
-                    h, C.byref(sub), S, pin, eta, k, flags, cols[r0:].data_ptr(), scores[r0:].data_ptr(),
-                    *scratch.fit(lib.spmf_topk_scratch_bytes(h, int(sub.n_rows), S)), stream),
-                    "spmf_topk_rows")
-            cols_out.append(cols)
-            scores_out.append(scores)
-        if len(cols_out) == 1:
-            return {"columns": cols_out[0], "scores": scores_out[0]}
-        if not cols_out:
-            return {"columns": torch.empty(0, k, dtype=torch.int32, device=self.device),
-                    "scores": torch.empty(0, k, dtype=torch.float32, device=self.device)}
-        return {"columns": torch.cat(cols_out), "scores": torch.cat(scores_out)}
-
-    def score_cells(self, data, rows, cols, values=None, nsamples=32, draws=None, max_rows=None):
-        """Held-out evaluation: the posterior predictive mean and, with ``values``, the log
-        pointwise predictive density lppd_i = log mean_s p(value_i | theta_s) of the listed cells
-        ``(rows[i], cols[i])``, without a [S,B,D] array (csrc/cells.hip).  'mean' is the score of
-        ``top_k``: the mean over the draws of the rate on a Poisson column and of sigmoid(logit) on
-        a Bernoulli one.
-
-        ``data`` is ONE batch (dict / counts; ``{"counts": sc, "panels": (p0, p1)}`` is the rows
-        of those panels).  The batch conditions the scores: its stored counts encode the rows, as
-        everywhere else, and the listed values are only scored.  A held-out cell should therefore
-        not also be stored in ``data`` with its true value, or it informs its own row's encoding;
-        that is the caller's split and is not checked.  ``rows`` are relative to the first row of
-        the batch (of the panel range); ``rows``, ``cols``, ``values`` are 1-D and of equal length,
-        numpy or torch on any device, in any order, duplicates and zeros allowed.  ``draws`` /
-        ``nsamples`` as in ``top_k`` (a single draw is allowed), ``max_rows`` as in
-        ``waic_streaming``.
-
-        Returns {'mean': float32 [N]} on the device in the caller's order and, with values,
-        'lppd': float32 [N] plus the summary of ``spmf_amd.heldout.summarize``: 'lppd_sum',
-        'lppd_mean', 'se', 'n', 'n_excluded'.  A cell with a non-finite log-pmf in any draw (NaN
-        value, rate 0 under a positive value) has lppd NaN and is counted in 'n_excluded'; a NaN
-        count in the batch makes every score of its row NaN.  A cell's scores do not depend on
-        the order of the list or on ``max_rows``.  Bit-reproducible."""
-        from . import heldout as _heldout
-        rows, cols, vals, n_rows = self._cell_list("score_cells", data, rows, cols, values)
-        N = int(rows.numel())
-        S, pin, eta, stream, KP, lib, h = self._draw_call("score_cells", draws, nsamples, 1,
-                                                          "log_likelihood_components")
-        rows, cols, vals, order, segments = self._cell_segments(data, rows, cols, vals, n_rows, S * KP * 4, max_rows)
-        nan = float("nan")
-        mean = torch.full((N,), nan, dtype=torch.float32, device=self.device)
-        lppd = torch.full((N,), nan, dtype=torch.float32, device=self.device) if vals is not None else None
-        scratch = _Scratch(self.device)
-        for sub, rel, lo, hi in segments:
-            _lib.check(h, lib.spmf_score_cells(
-                h, C.byref(sub), S, pin, eta, hi - lo, rel.data_ptr(), cols[lo:hi].data_ptr(),
-                vals[lo:hi].data_ptr() if vals is not None else None, mean[lo:hi].data_ptr(),
-                lppd[lo:hi].data_ptr() if lppd is not None else None,
-                *scratch.fit(lib.spmf_cells_scratch_bytes(h, int(sub.n_rows), S)), stream), "spmf_score_cells")
-        del rows, cols, vals, scratch, segments
-        out = {"mean": torch.empty_like(mean).index_copy_(0, order, mean)}
-        del mean
-        if lppd is not None:
-            out["lppd"] = torch.empty_like(lppd).index_copy_(0, order, lppd)
-            del lppd, order
-            out.update(_heldout.summarize(out["lppd"]))
-        return out
-
-    def _cell_list(self, name, data, rows, cols, values=None):
-        """The cell list of ``score_cells`` / ``rank_cells`` (``name``), checked before any library call:
-        ``data`` is one batch, ``rows`` / ``cols`` (/ ``values``) are 1-D and of equal length, the indices
-        integers inside the batch.  -> (rows, cols, values or None, rows of the batch), on the device."""
-        if callable(data) or not (isinstance(data, (dict, SparseCounts)) or hasattr(data, "shape")):
-            raise ValueError(f"{name} takes ONE batch (a dict or counts), not an iterable or a factory")
-
-        def vector(what, t, floating):
-            if not isinstance(t, torch.Tensor):
-                t = np.asarray(t)
-                if t.size == 0 and not floating:        # [] has no dtype of its own
-                    t = t.astype(np.int64)
-                t = torch.as_tensor(t)
-            if t.dim() != 1:
-                raise ValueError(f"{name}: {what} must be 1-D, got shape {tuple(t.shape)}")
-            if floating:
-                return t.to(device=self.device, dtype=torch.float32)
-            if t.dtype.is_floating_point or t.dtype == torch.bool:
-                raise ValueError(f"{name}: {what} must hold integers, got {t.dtype}")
-            return t.to(device=self.device)
-        rows, cols = vector("rows", rows, False), vector("cols", cols, False)
-        vals = vector("values", values, True) if values is not None else None
-        N = int(rows.numel())
-        if cols.numel() != N or (vals is not None and vals.numel() != N):
-            raise ValueError(f"{name}: rows, cols and values must have equal length, got {N}, "
-                             f"{int(cols.numel())}" + (f", {int(vals.numel())}" if vals is not None else ""))
-        # the index check: one device-side min / max and one read-back, before any library call
-        # (the batch's row count is read off its shape, not off the library's descriptor)
-        n_rows = self._batch_rows(data)
-        if n_rows > 2 ** 31 - 1:
-            raise ValueError(f"{name}: a batch of {n_rows} rows is beyond the int32 row index of the list; "
-                             "score it by panel ranges")
-        if N:
-            r_lo, r_hi, c_lo, c_hi = torch.stack(
-                [t.to(torch.int64) for t in (rows.min(), rows.max(), cols.min(), cols.max())]).tolist()
-            if r_lo < 0 or r_hi >= n_rows:
-                raise ValueError(f"{name}: rows must lie in [0, {n_rows}), got {r_lo} .. {r_hi}")
-            if c_lo < 0 or c_hi >= self.feature_dim:
-                raise ValueError(f"{name}: cols must lie in [0, {self.feature_dim}), got {c_lo} .. {c_hi}")
-        return rows, cols, vals, n_rows
-
-    def _cell_segments(self, data, rows, cols, vals, n_rows, row_bytes, max_rows):
-        """The checked list of ``_cell_list`` cut along the row chunks of ``_row_chunks``: the cells sorted by
-        row (stable), so that a chunk's cells are one contiguous segment.  -> (rows, cols, vals as int32 / int32 /
-        float32 in sorted order, order, segments); ``order[i]`` is the caller's position of sorted cell i and
-        ``segments`` lists ``(sub, rel, lo, hi)`` per chunk with cells: the chunk's batch struct, its cells' rows
-        relative to the chunk's first row, and its slice of the sorted list."""
-        (lib_rows, chunks), = self._row_chunks(data, row_bytes, max_rows)
-        assert lib_rows == n_rows, (lib_rows, n_rows)
-        N = int(rows.numel())
-        rows, order = torch.sort(rows.to(torch.int32), stable=True)
-        cols = cols.to(torch.int32)[order]
-        if vals is not None:
-            vals = vals[order]
-        chunks = list(chunks)
-        # a chunk's segment, from its first and its last row: both fit the int32 of the list
-        first = torch.tensor([r0 for r0, _ in chunks] or [0], dtype=torch.int32, device=self.device)
-        last = torch.tensor([r0 + int(sub.n_rows) - 1 for r0, sub in chunks] or [0], dtype=torch.int32,
-                            device=self.device)
-        edges = torch.stack([torch.searchsorted(rows, first), torch.searchsorted(rows, last, right=True)],
-                            1).tolist() if N else []
-        segments = [(sub, rows[lo:hi] - r0 if r0 else rows[lo:hi], lo, hi)
-                    for (r0, sub), (lo, hi) in zip(chunks, edges) if hi > lo]
-        return rows, cols, vals, order, segments
-
-    def rank_cells(self, data, rows, cols, k=(1, 5, 10, 20, 50), nsamples=32, draws=None, exclude_stored=True,
-                   max_rows=None):
-        """Held-out ranking: where the listed cells ``(rows[i], cols[i])`` land in the ranking of ``top_k``,
-        without a [B,D] array (csrc/rank.hip).  Score, order and candidates are ``top_k``'s: the mean over the
-        draws of the rate on a Poisson column and of sigmoid(logit) on a Bernoulli one; score descending, equal
-        scores by ascending column; the candidates of a row are its columns with a finite score that, with
-        ``exclude_stored``, the batch does not store.  A listed cell may or may not be a candidate itself.
-
-        ``data`` is ONE batch and ``rows`` / ``cols`` are as in ``score_cells`` (any order, duplicates allowed,
-        any number of cells per row); ``draws`` / ``nsamples`` as in ``top_k``, ``max_rows`` as in ``top_k``.
-        ``k``: the cut-offs of the summary's hit rates (an int or a sequence of ints).
-
-        Returns, on the device and in the caller's order, 'rank': int32 [N], the number of the row's other
-        candidates that precede the cell (0 is the best; -1 for a non-finite score, e.g. a row with a NaN
-        count), 'candidates': int32 [N], the number of the row's candidates beside the cell, and 'score':
-        float32 [N], bit for bit the score ``top_k`` reports for that cell -- so for a cell that is not stored,
-        ``rank < k`` exactly when ``top_k(k)["columns"][row, rank]`` is its column.  Plus the summary of
-        ``spmf_amd.heldout.rank_summary``: 'n', 'n_excluded', 'hit_rate' {k: share}, 'mrr', 'auc'.  A cell's
-        result does not depend on the order of the list, on its other cells or on ``max_rows``.
-        Bit-reproducible.  Cost: about two ``top_k`` sweeps while no row lists more than 32 cells; the kernel
-        serves 32 listed cells per row and round, so a row with n listed cells costs its block of 64 rows
-        ceil(n / 32) such double sweeps (listing every column of a row is correct but slow)."""
-        from . import heldout as _heldout
-        rows, cols, _, n_rows = self._cell_list("rank_cells", data, rows, cols)
-        ks = (int(k),) if isinstance(k, (int, np.integer)) else tuple(int(v) for v in k)
-        if any(v < 1 for v in ks):
-            raise ValueError(f"rank_cells: the cut-offs k must be >= 1, got {ks}")
-        N = int(rows.numel())
-        S, pin, eta, stream, KP, lib, h = self._draw_call("rank_cells", draws, nsamples, 1,
-                                                          "log_likelihood_components")
-        rows, cols, _, order, segments = self._cell_segments(
-            data, rows, cols, None, n_rows, S * KP * 4 + (self.feature_dim + 31) // 32 * 4, max_rows)
-        rank = torch.full((N,), -1, dtype=torch.int32, device=self.device)
-        cand = torch.zeros(N, dtype=torch.int32, device=self.device)
-        score = torch.full((N,), float("nan"), dtype=torch.float32, device=self.device)
-        scratch = _Scratch(self.device)
-        flags = 1 if exclude_stored else 0
-        for sub, rel, lo, hi in segments:
-            _lib.check(h, lib.spmf_rank_cells(
-                h, C.byref(sub), S, pin, eta, hi - lo, rel.data_ptr(), cols[lo:hi].data_ptr(), flags,
-                rank[lo:hi].data_ptr(), cand[lo:hi].data_ptr(), score[lo:hi].data_ptr(),
-                *scratch.fit(lib.spmf_rank_scratch_bytes(h, int(sub.n_rows), S)), stream), "spmf_rank_cells")
-        del rows, cols, scratch, segments
-        out = {"rank": torch.empty_like(rank).index_copy_(0, order, rank),
-               "candidates": torch.empty_like(cand).index_copy_(0, order, cand),
-               "score": torch.empty_like(score).index_copy_(0, order, score)}
-        del rank, cand, score, order
-        out.update(_heldout.rank_summary(out["rank"], out["candidates"], ks))
-        return out
-
-    def _column_list(self, name, cols):
-        """The column list of ``predict`` (``name``), checked before any library call: None (all columns) or
-        1-D integers inside [0, D), at most D of them, duplicates kept.  -> int32 on the device, or None."""
-        if cols is None:
-            return None
-        D = self.feature_dim
-        if not isinstance(cols, torch.Tensor):
-            cols = np.asarray(cols)
-            if cols.size == 0 and cols.ndim == 1:         # [] has no dtype of its own
-                cols = cols.astype(np.int64)
-            cols = torch.as_tensor(cols)
-        if cols.dim() != 1:
-            raise ValueError(f"{name}: cols must be 1-D, got shape {tuple(cols.shape)}")
-        if cols.dtype.is_floating_point or cols.dtype == torch.bool:
-            raise ValueError(f"{name}: cols must hold integers, got {cols.dtype}")
-        if cols.numel() > D:
-            raise ValueError(f"{name}: cols lists {int(cols.numel())} columns, more than the {D} there are")
-        if cols.numel():
-            lo, hi = int(cols.min()), int(cols.max())
-            if lo < 0 or hi >= D:
-                raise ValueError(f"{name}: cols must lie in [0, {D}), got {lo} .. {hi}")
-        return cols.to(device=self.device, dtype=torch.int32).contiguous()
-
-    def predict(self, data, cols=None, nsamples=32, draws=None, sd=False, p_nonzero=False, max_rows=None):
-        """The reconstruction: the posterior predictive mean of every cell of the rows of ``data`` and the
-        columns ``cols`` as a dense block, without a [S,B,D] array (csrc/panel.hip).  'mean' is the score of
-        ``top_k`` / ``rank_cells``, bit for bit: the mean over the draws of m_s, the rate on a Poisson column
-        and sigmoid(logit) on a Bernoulli one.
-
-        ``data``, ``draws`` and ``max_rows`` as in ``top_k`` (``draws`` may hold a single draw); the rows of
-        all batches are concatenated.  ``cols``: None (all D columns) or 1-D integers in [0, D), numpy or
-        torch on any device, at most D of them, in any order, duplicates kept: output column j is column
-        ``cols[j]``.  ``sd=True`` adds the unbiased standard deviation of m_s over the draws (at least two
-        draws; Welford in draw order).  ``p_nonzero=True`` adds P(x > 0) under the predictive mixture:
-        mean_s (1 - exp(-rate_s)) on a Poisson column, formed as -expm1(-rate_s) so that small rates keep
-        their digits, and the mean itself on a Bernoulli column.
-
-        Returns device tensors {'mean': float32 [B, C]} plus 'sd' and 'p_nonzero' when asked for and, with a
-        list, 'columns': the int32 list as used.  Memory: every output is B * C * 4 bytes and is allocated
-        whole -- bound it with the column list or, over the rows, with a ``{"counts": sc, "panels": (p0, p1)}``
-        range per call; the scratch is bounded by ``max_rows`` as in ``top_k``.  A row with a NaN count is NaN.
-        A value depends on its cell alone: not on the list, on the other outputs asked for or on
-        ``max_rows``.  Bit-reproducible."""
-        cols = self._column_list("predict", cols)
-        S, pin, eta, stream, KP, lib, h = self._draw_call("predict", draws, nsamples, 2 if sd else 1,
-                                                          "log_likelihood_components")
-        n_cols = self.feature_dim if cols is None else int(cols.numel())
-        names = ("mean",) + (("sd",) if sd else ()) + (("p_nonzero",) if p_nonzero else ())
-        scratch, parts = _Scratch(self.device), {n: [] for n in names}
-        for n_rows, chunks in self._row_chunks(data, S * KP * 4, max_rows):
-            out = {n: torch.empty(n_rows, n_cols, dtype=torch.float32, device=self.device) for n in names}
-            for r0, sub in chunks if n_cols else ():       # (an empty list has no pointer to pass)
-                _lib.check(h, lib.spmf_predict_columns(
-                    h, C.byref(sub), S, pin, eta, n_cols, cols.data_ptr() if cols is not None else None,
-                    *[out[n][r0:].data_ptr() if n in out else None for n in ("mean", "sd", "p_nonzero")],
-                    *scratch.fit(lib.spmf_predict_scratch_bytes(h, int(sub.n_rows), S)), stream),
-                    "spmf_predict_columns")
-            for n in names:
-                parts[n].append(out[n])
-
-        def cat(p):
-            if len(p) == 1:
-                return p[0]
-            return torch.cat(p) if p else torch.empty(0, n_cols, dtype=torch.float32, device=self.device)
-        res = {n: cat(parts[n]) for n in names}
-        if cols is not None:
-            res["columns"] = cols
-        return res
-
-    _GROUP_OUT_CAP = 1 << 30          # bytes of one [S, G, C] fp64 output of group_means
-
-    def _group_labels(self, name, data, labels, n_groups):
-        """The labels of ``group_means`` (``name``), checked before any library call: 1-D integers in
-        {-1, 0 .. n_groups - 1}, one per row of all batches.  The rows are counted off the batches' shapes: a
-        factory is called once for the count and once for the run, a list is walked twice, and no batch is kept
-        alive in between; a one-shot iterator cannot be walked twice, so its length is checked as its batches
-        arrive (``counted`` False).  -> (int32 labels on the device, n_groups, counted)."""
-        if not isinstance(labels, torch.Tensor):
-            labels = np.asarray(labels)
-            if labels.size == 0 and labels.ndim == 1:       # [] has no dtype of its own
-                labels = labels.astype(np.int64)
-            labels = torch.as_tensor(labels)
-        if labels.dim() != 1:
-            raise ValueError(f"{name}: labels must be 1-D, got shape {tuple(labels.shape)}")
-        if labels.dtype.is_floating_point or labels.dtype == torch.bool:
-            raise ValueError(f"{name}: labels must hold integers, got {labels.dtype}")
-        if callable(data):
-            batches = data()
-        elif isinstance(data, (dict, SparseCounts)) or hasattr(data, "shape"):
-            batches = (data,)
-        else:
-            batches = data
-        counted = callable(data) or iter(batches) is not batches
-        if counted:
-            n_rows = sum(self._batch_rows(b) for b in batches)
-            if int(labels.numel()) != n_rows:
-                raise ValueError(f"{name}: labels must have one entry per row, got {int(labels.numel())} for "
-                                 f"{n_rows} rows")
-        lo, hi = (int(labels.min()), int(labels.max())) if labels.numel() else (-1, -1)
-        if n_groups is None:
-            n_groups = hi + 1
-        n_groups = int(n_groups)
-        if n_groups < 1:
-            raise ValueError(f"{name}: n_groups must be at least 1, got {n_groups}")
-        if lo < -1 or hi >= n_groups:
-            raise ValueError(f"{name}: labels must lie in [-1, {n_groups}) (-1: no group), got {lo} .. {hi}")
-        return labels.to(device=self.device, dtype=torch.int32).contiguous(), n_groups, counted
-
-    def group_means(self, data, labels, n_groups=None, cols=None, nsamples=32, draws=None, p_nonzero=False,
-                    max_rows=None):
-        """The posterior predictive reduced over rows: per draw, the mean over the rows of every group of
-        m_s(b, d) -- the cell of ``predict`` for draw s, the rate on a Poisson column and sigmoid(logit) on a
-        Bernoulli one -- without a [rows, C] block per draw (csrc/groups.hip).  What a cluster, cell type or
-        segment expresses, with the draws kept apart so that a non-linear contrast between groups
-        (``spmf_amd.groups.contrast``: a log fold change) has a posterior of its own.
-
-        ``data``, ``draws``, ``cols`` and ``max_rows`` as in ``predict``; batches are streamed, never held
-        together (a factory is called twice, first for the row count alone; for a one-shot iterator the length
-        of ``labels`` is checked batch by batch instead of up front).  ``labels``: 1-D integers, numpy or torch on any device, one per row of all batches in
-        arrival order, in {-1, 0 .. n_groups - 1}; -1 is "no group".  ``n_groups`` defaults to
-        max(labels) + 1.  ``p_nonzero=True`` adds the expected fraction of the group with x > 0 (the sum of
-        ``predict``'s P(x > 0) terms per draw).
-
-        Returns device tensors: 'draws' fp64 [S, G, C] (sum / count), 'mean' [G, C] and, with two draws or
-        more, 'sd' [G, C] (unbiased) over the draws, 'count' int64 [G], 'sum' fp64 [S, G, C] (the raw sums:
-        shards add up), with ``p_nonzero`` 'p_nonzero_draws' [S, G, C] / 'p_nonzero' [G, C] and their raw
-        sums 'sum_nonzero', with a list 'columns'.  An empty group has NaN means and count 0.  A row with a NaN count makes its own group
-        NaN and no other.  Every sum is fp64 from the first addition on, in an order fixed by the arguments:
-        bit-reproducible; ``max_rows`` and the split into batches change the order of the fp64 additions
-        only.  Memory: each [S, G, C] array is S * G * C * 8 bytes and at most 1 GiB -- bound it with
-        ``cols``.  ``max_rows`` bounds the two copies of the encoded rows and the per-row part of the ordering;
-        the scratch also holds 64 pad rows per group (S * 64 * G * K floats), which no row limit bounds."""
-        labels, G, _ = self._group_labels("group_means", data, labels, n_groups)
-        cols = self._column_list("group_means", cols)
-        n_cols = self.feature_dim if cols is None else int(cols.numel())
-        if draws is not None and self._custom_codec is None:
-            n_draws = int(next(iter(draws.values())).shape[0])
-        else:
-            n_draws = int(nsamples)
-        if n_draws * G * n_cols * 8 > self._GROUP_OUT_CAP:
-            raise ValueError(f"group_means: an output of {n_draws} draws x {G} groups x {n_cols} columns is "
-                             f"{n_draws * G * n_cols * 8} bytes, above the cap of {self._GROUP_OUT_CAP}: pass "
-                             "fewer columns at a time with cols")
-        S, pin, eta, stream, KP, lib, h = self._draw_call("group_means", draws, nsamples, 1, "predict")
-        total = torch.zeros(S, G, n_cols, dtype=torch.float64, device=self.device)
-        nonzero = torch.zeros_like(total) if p_nonzero else None
-        scratch, off = _Scratch(self.device), 0
-        # per row: the encoded rows twice (arrival order, group order), rank and slot, its share of the chunk table
-        row_bytes = 2 * S * KP * 4 + 8 + (G + 1023) // 1024 * 4
-        for n_rows, chunks in self._row_chunks(data, row_bytes, max_rows):
-            if off + n_rows > int(labels.numel()):
-                raise ValueError(f"group_means: labels must have one entry per row, got {int(labels.numel())} "
-                                 f"for at least {off + n_rows} rows")
-            for r0, sub in chunks if n_cols else ():
-                _lib.check(h, lib.spmf_group_sums(
-                    h, C.byref(sub), S, pin, eta, labels[off + r0:].data_ptr(), G, n_cols,
-                    cols.data_ptr() if cols is not None else None, total.data_ptr(),
-                    nonzero.data_ptr() if nonzero is not None else None,
-                    *scratch.fit(lib.spmf_groups_scratch_bytes(h, int(sub.n_rows), S, G, n_cols)), stream),
-                    "spmf_group_sums")
-            off += n_rows
-        if off != int(labels.numel()):
-            raise ValueError(f"group_means: labels must have one entry per row, got {int(labels.numel())} for "
-                             f"{off} rows")
-        count = torch.bincount(labels[labels >= 0].to(torch.int64), minlength=G)
-        n = count.to(torch.float64).masked_fill(count == 0, float("nan"))[None, :, None]
-        res = {"draws": total / n, "count": count, "sum": total}
-        res["mean"] = res["draws"].mean(0)
-        if S >= 2:
-            res["sd"] = res["draws"].std(0, unbiased=True)
-        if nonzero is not None:
-            res["sum_nonzero"] = nonzero
-            res["p_nonzero_draws"] = nonzero / n
-            res["p_nonzero"] = res["p_nonzero_draws"].mean(0)
-        if cols is not None:
-            res["columns"] = cols
-        return res
-
-    def embed(self, data, nsamples=32, draws=None, sd=False, max_rows=None):
-        """The rows of ``data`` in the latent space, at any size: the posterior mean encoding
-        e_b = (1/S) sum_s z_sb, where z_sb is what ``encode(x, u_s, s_s)`` returns for draw s (the
-        draw stage's encode sweep; csrc/knn.hip reduces it over the draws, so [S,B,K] never leaves
-        the scratch).
-
-        ``data``, ``draws`` and ``max_rows`` as in ``waic_streaming`` (``draws`` may hold a single
-        draw); the rows of all batches are concatenated.  Returns {'mean': float32 [N, latent_dim]}
-        on the device and, with ``sd=True``, 'sd': the unbiased standard deviation over the draws
-        (at least two draws).  fp32: the sum in draw order times 1/S, Welford in draw order for the
-        deviation.  A row with a NaN count is NaN.  Bit-reproducible and independent of
-        ``max_rows``."""
-        S, pin, eta, stream, KP, lib, h = self._draw_call("embed", draws, nsamples, 2 if sd else 1, "encode")
-        K = self.latent_dim
-        scratch, means, sds = _Scratch(self.device), [], []
-        for n_rows, chunks in self._row_chunks(data, S * KP * 4, max_rows):
-            mean = torch.empty(n_rows, K, dtype=torch.float32, device=self.device)
-            dev = torch.empty(n_rows, K, dtype=torch.float32, device=self.device) if sd else None
-            for r0, sub in chunks:
-                _lib.check(h, lib.spmf_embed_rows(
-                    h, C.byref(sub), S, pin, eta, mean[r0:].data_ptr(),
-                    dev[r0:].data_ptr() if dev is not None else None,
-                    *scratch.fit(lib.spmf_embed_scratch_bytes(h, int(sub.n_rows), S)), stream),
-                    "spmf_embed_rows")
-            means.append(mean)
-            sds.append(dev)
-
-        def cat(parts):
-            if len(parts) == 1:
-                return parts[0]
-            return torch.cat(parts) if parts else torch.empty(0, K, dtype=torch.float32, device=self.device)
-        out = {"mean": cat(means)}
-        if sd:
-            out["sd"] = cat(sds)
-        return out
-
-    @staticmethod
-    def _knn_args(name, k, metric):
-        """k and the metric of ``knn`` / ``neighbors``, checked before any library call -> (k, flags)."""
-        from . import neighbors as _neighbors
-        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
-            raise ValueError(f"{name}: k must be an integer, got {k!r}")
-        if not 1 <= int(k) <= 64:
-            raise ValueError(f"{name} needs 1 <= k <= 64, got {k}")
-        if metric not in _neighbors.METRICS:
-            raise ValueError(f"{name}: metric must be one of {_neighbors.METRICS}, got {metric!r}")
-        return int(k), 1 if metric == "cosine" else 0
-
-    @staticmethod
-    def _knn_rows(name, what, t):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{name}: {what} must be a torch tensor, got {type(t).__name__}")
-        if t.dim() != 2:
-            raise ValueError(f"{name}: {what} must be 2-D [rows, width], got shape {tuple(t.shape)}")
-        if t.dtype != torch.float32:
-            raise ValueError(f"{name}: {what} must be float32, got {t.dtype}")
-        if not 1 <= t.shape[1] <= 256:
-            raise ValueError(f"{name}: the width of {what} must be in 1..256, got {t.shape[1]}")
-        return t
-
-    def knn(self, points, k=15, queries=None, metric="euclidean", include_self=False):
-        """The exact ``k`` nearest rows of ``points`` [Nr, Kx] for every row of ``queries`` [Nq, Kx]
-        (default: ``points`` itself), without an [Nq, Nr] array (csrc/knn.hip).  Both are float32
-        tensors on the model's device, 1 <= Kx <= 256 whatever the model's latent_dim, 1 <= k <= 64.
-        ``metric``: 'euclidean' or 'cosine' (the distance 1 - cos).  Without ``queries`` (or with
-        ``queries=points``) a row is no neighbour of its own unless ``include_self``.
-
-        Returns {'indices': int32 [Nq,k], 'distances': float32 [Nq,k]} on the device: distance
-        ascending, equal distances by ascending index, a query with fewer than k candidates padded
-        with -1 / +inf at the tail.  A non-finite row of ``points`` is nobody's neighbour; a non-finite
-        query (or a zero row under 'cosine') has none.  The selection runs on the matrix cores over
-        centred (or unit) rows; the reported distances are recomputed from the rows as given
-        (include/spmf_hip.h spmf_knn has the definition).  Bit-reproducible; a query's result does
-        not depend on the other queries.  ``spmf_amd.neighbors.to_csr`` turns the result into the
-        CSR arrays of a neighbour graph."""
-        k, flags = self._knn_args("knn", k, metric)
-        pts = self._knn_rows("knn", "points", points)
-        same = queries is None or queries is points or (
-            isinstance(queries, torch.Tensor) and queries.shape == points.shape and queries.dtype == points.dtype
-            and queries.device == points.device and queries.data_ptr() == points.data_ptr()
-            and queries.stride() == points.stride())
-        qry = pts if same else self._knn_rows("knn", "queries", queries)
-        if qry.shape[1] != pts.shape[1]:
-            raise ValueError(f"knn: queries have width {qry.shape[1]}, points {pts.shape[1]}")
-        if pts.shape[0] > 2 ** 31 - 1:
-            raise ValueError(f"knn: {pts.shape[0]} points are beyond the int32 index of the result")
-        dev = torch.device(self.device)
-        for what, t in (("points", pts), ("queries", qry)):
-            if t.device.type != "cuda" or (dev.index is not None and t.device != dev):
-                raise ValueError(f"knn: {what} must be on the model's device {self.device}, got {t.device}")
-        pts = pts.contiguous()
-        qry = pts if same else qry.contiguous()
-        nq, nr, width = int(qry.shape[0]), int(pts.shape[0]), int(pts.shape[1])
-        lib, h = _lib.load(), self._handle()
-        idx = torch.empty(nq, k, dtype=torch.int32, device=pts.device)
-        dist = torch.empty(nq, k, dtype=torch.float32, device=pts.device)
-        scratch = _Scratch(pts.device)
-        _lib.check(h, lib.spmf_knn(
-            h, qry.data_ptr(), nq, pts.data_ptr(), nr, width, k, flags, 0 if same and not include_self else -1,
-            idx.data_ptr(), dist.data_ptr(), *scratch.fit(lib.spmf_knn_scratch_bytes(h, nq, nr, width)),
-            torch.cuda.current_stream(pts.device).cuda_stream), "spmf_knn")
-        return {"indices": idx, "distances": dist}
-
-    def neighbors(self, data, k=15, query=None, metric="euclidean", include_self=False, nsamples=32, draws=None,
-                  max_rows=None):
-        """The neighbour graph of the rows of ``data`` in the model's latent space: ``embed`` on
-        ``data`` -- and on ``query``, when given, with the SAME draws -- then ``knn`` on the posterior
-        mean encodings.  Without ``query`` every row of ``data`` gets its k nearest other rows (itself
-        too with ``include_self``); with ``query`` every row of ``query`` gets its k nearest rows of
-        ``data``.  ``data`` / ``query``, ``nsamples`` / ``draws`` and ``max_rows`` as in ``embed``;
-        ``k`` and ``metric`` as in ``knn``.
-
-        Returns {'indices': int32 [Nq,k], 'distances': float32 [Nq,k]} on the device, bit for bit
-        ``knn(embed(data, draws=draws)["mean"], k, ...)``."""
-        self._knn_args("neighbors", k, metric)
-        if not 1 <= self.latent_dim <= 256:
-            raise ValueError(f"neighbors: latent_dim {self.latent_dim} is beyond the 256 columns of knn")
-        if draws is None and self._custom_codec is None:
-            if int(nsamples) < 1:
-                raise ValueError("neighbors needs nsamples >= 1")
-            draws = self.surrogate_distribution.sample(int(nsamples))      # once: data and query share them
-        ref = self.embed(data, nsamples=nsamples, draws=draws, max_rows=max_rows)["mean"]
-        if query is None:
-            return self.knn(ref, k=k, metric=metric, include_self=include_self)
-        qry = self.embed(query, nsamples=nsamples, draws=draws, max_rows=max_rows)["mean"]
-        return self.knn(ref, k=k, queries=qry, metric=metric, include_self=True)
-
     def _nonfinite_scan(self, sc, cs, data, S, P, max_cells=1 << 27):
         """Dense part of the replacement rule (poisson.py:606-616): the minimum
         of the per-cell log-pmf over ALL S*B*D cells (finite ones; the
@@ -1406,22 +817,6 @@ def _wrap_f32(ptr, n, device, owner):
     off = ptr - base
     assert off >= 0 and off % 4 == 0
     return owner[off:off + 4 * n].view(torch.float32)
-
-
-class _Scratch:
-    """The grow-only device scratch of one streaming call."""
-
-    def __init__(self, device):
-        self.device, self.buf = device, None
-
-    def fit(self, need_bytes):
-        """-> (256-byte aligned pointer, usable bytes >= need_bytes).  An outgrown buffer is dropped
-        before the larger one is allocated."""
-        if self.buf is None or self.buf.numel() < need_bytes + 256:
-            self.buf = None
-            self.buf = torch.empty(need_bytes + 256, dtype=torch.uint8, device=self.device)
-        off = (-self.buf.data_ptr()) % 256
-        return self.buf.data_ptr() + off, self.buf.numel() - off
 
 
 class PoissonMatrixFactorization(PoissonFactorization):

@@ -1,30 +1,73 @@
-"""What the tests of the three streaming calls share (waic_streaming / spmf_waic_accumulate, top_k /
-spmf_topk_rows, score_cells / spmf_score_cells): the cached problems of the GPU files and, for the
-C-ABI, each entry point as a raw ctypes call with a dict of good arguments plus the error contract
-of the draw stage they have in common (include/spmf_hip.h), asserted by one function on a device
-(test_gpu_stream_abi.py) and without one (test_stream_host.py).
+"""What the tests of the streaming calls share: the cached problems of the GPU files and, for the C-ABI, ONE
+contract table of the draw-stage entry points (waic_streaming / spmf_waic_accumulate, top_k / spmf_topk_rows,
+score_cells / spmf_score_cells, rank_cells / spmf_rank_cells, predict / spmf_predict_columns, group_means /
+spmf_group_sums, embed / spmf_embed_rows): each entry as a raw ctypes call with a dict of good arguments --
+dummy addresses without a device (host_good_call), real buffers with one (gpu_good_call) -- plus the error
+contract of the draw stage they have in common (include/spmf_hip.h), asserted by one function on a device
+(test_gpu_stream_abi.py) and without one (test_stream_host.py).  A new draw-stage call adds one row to ENTRIES
+and one branch to each of the two good calls.
 """
+import collections
 import ctypes as C
+import fnmatch
 import functools
+import os
+import re
 
 import numpy as np
 import torch
 
 T = torch.as_tensor
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 BERN_DAMP = {"bernoulli": 1.0 / 64.0, "bernoulli_log": 1.0 / 8.0}
 
-# entry point -> (the call, its scratch size, smallest S, the Python method, the arguments between `eta` and
-# `scratch` in the header's order with their ctypes)
+# the shape of the contract tests: a ragged 64-row block, K padded 3 -> 4, two draws so that sd is defined
+B, D, K, S = 70, 45, 3, 2
+# the list of predict / groups in the good calls: four columns, one of them twice
+PANEL_COLS = (7, 0, 7, 44)
+
+# One row per entry point: the call, its scratch size, the smallest S, the Python method, `own`: the arguments
+# between `eta` and `scratch` in the header's order with their ctypes, `size_args`: those of `own` the size
+# function takes behind (rows, S), `header_args`: the argument counts of (scratch size, call) in include/spmf_hip.h
+Entry = collections.namedtuple("Entry", "call size min_S method own size_args header_args")
+_P, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 ENTRIES = {
-    "waic": ("spmf_waic_accumulate", "spmf_waic_scratch_bytes", 2, "waic_streaming",
-             (("sums", C.c_void_p), ("rows", C.c_void_p))),
-    "topk": ("spmf_topk_rows", "spmf_topk_scratch_bytes", 1, "top_k",
-             (("k", C.c_int), ("flags", C.c_uint), ("cols", C.c_void_p), ("scores", C.c_void_p))),
-    "cells": ("spmf_score_cells", "spmf_cells_scratch_bytes", 1, "score_cells",
-              (("n", C.c_int64), ("row", C.c_void_p), ("col", C.c_void_p), ("val", C.c_void_p),
-               ("mean", C.c_void_p), ("lppd", C.c_void_p))),
+    "waic": Entry("spmf_waic_accumulate", "spmf_waic_scratch_bytes", 2, "waic_streaming",
+                  (("sums", _P), ("rows", _P)), (), (3, 10)),
+    "topk": Entry("spmf_topk_rows", "spmf_topk_scratch_bytes", 1, "top_k",
+                  (("k", C.c_int), ("flags", C.c_uint), ("cols", _P), ("scores", _P)), (), (3, 12)),
+    "cells": Entry("spmf_score_cells", "spmf_cells_scratch_bytes", 1, "score_cells",
+                   (("n", _I64), ("row", _P), ("col", _P), ("val", _P), ("mean", _P), ("lppd", _P)), (), (3, 14)),
+    "rank": Entry("spmf_rank_cells", "spmf_rank_scratch_bytes", 1, "rank_cells",
+                  (("n", _I64), ("row", _P), ("col", _P), ("flags", C.c_uint), ("rank", _P), ("cand", _P),
+                   ("score", _P)), (), (3, 15)),
+    "predict": Entry("spmf_predict_columns", "spmf_predict_scratch_bytes", 1, "predict",
+                     (("n", _I32), ("cols", _P), ("mean", _P), ("sd", _P), ("pnz", _P)), (), (3, 13)),
+    "groups": Entry("spmf_group_sums", "spmf_groups_scratch_bytes", 1, "group_means",
+                    (("labels", _P), ("G", _I32), ("n", _I32), ("cols", _P), ("sum", _P), ("nz", _P)), ("G", "n"),
+                    (5, 14)),
+    "embed": Entry("spmf_embed_rows", "spmf_embed_scratch_bytes", 1, "embed", (("mean", _P), ("sd", _P)), (),
+                   (3, 10)),
 }
+
+
+def assert_declared_exported_bound(name, nargs):
+    """``name`` is declared in include/spmf_hip.h with ``nargs`` arguments, matched by the export list and
+    bound in spmf_amd._lib with as many."""
+    from spmf_amd import _lib
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "spmf_hip.h")).read(), flags=re.S)
+    exports = open(os.path.join(ROOT, "spmf_amd", "csrc", "exports.map")).read()
+    exports = re.sub(r"/\*.*?\*/", "", exports, flags=re.S)
+    globs = re.search(r"global:\s*([^}]*?)local:", exports, re.S).group(1)
+    patterns = [p.strip() for p in globs.split(";") if p.strip()]
+    assert any(fnmatch.fnmatchcase(name, p) for p in patterns), (name, patterns)
+    assert name in _lib.SIGNATURES, name
+    m = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", hdr, re.S)
+    assert m, f"{name} is not declared in include/spmf_hip.h"
+    declared = len([a for a in m.group(1).split(",") if a.strip()])
+    assert len(_lib.SIGNATURES[name][1]) == declared == nargs, name
+    assert "define SPMF_ABI_VERSION 6" in hdr and _lib.ABI_VERSION == 6
 
 
 def _bern_cols(lik, mask, D):
@@ -62,8 +105,8 @@ def abi_call(entry, good):
     NULL can stand for `params` and `counts` too, with the arguments of ``good`` (keys h, ct, S, pin, eta,
     the entry's own of ENTRIES, ptr, nbytes, stream) unless overridden."""
     from spmf_amd import _lib
-    name, _, _, _, own = ENTRIES[entry]
-    fn = getattr(C.CDLL(_lib.LIB_PATH), name)
+    own = ENTRIES[entry].own
+    fn = getattr(C.CDLL(_lib.LIB_PATH), ENTRIES[entry].call)
     fn.restype = C.c_int
     fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [t for _, t in own] + [
         C.c_void_p, C.c_size_t, C.c_void_p]
@@ -75,63 +118,134 @@ def abi_call(entry, good):
     return call
 
 
+def scratch_need(lib, entry, h, rows, s, own):
+    """The entry's scratch size for ``rows`` rows and ``s`` draws, with its extra size arguments out of ``own``."""
+    e = ENTRIES[entry]
+    return int(getattr(lib, e.size)(h, rows, s, *[own[n] for n in e.size_args]))
+
+
+def host_good_call(lib, entry):
+    """A valid-looking call of ``entry`` that needs no device: a context of spmf_ctx_create (K = 3, D = 45), a
+    hand-filled descriptor of 70 empty rows and dummy aligned addresses -- nothing in it may be dereferenced, so
+    only refused and empty calls may be made with it.  -> (good, need, pin_without_u, mixed_ctx_without_types,
+    cleanup); ``cleanup()`` destroys the two contexts."""
+    from spmf_amd import _lib
+    from spmf_amd._lib import VAR_ORDER
+    h, raw = C.c_void_p(), C.c_void_p()
+    assert lib.spmf_ctx_create(0, K, D, 0, C.byref(h)) == 0
+    assert lib.spmf_ctx_create(0, K, D, _lib.FLAG_MIXED, C.byref(raw)) == 0
+
+    def cleanup():
+        lib.spmf_ctx_destroy(h)
+        lib.spmf_ctx_destroy(raw)
+    try:
+        cs = _lib.CountsStruct()
+        cs.struct_size = C.sizeof(_lib.CountsStruct)
+        cs.n_cols, cs.n_rows, cs.nnz, cs.row_ptr = D, B, 0, 0x10000
+        slots = {n: 0x100000 * (i + 1) for i, n in enumerate(VAR_ORDER) if n in ("s", "u", "v", "w")}
+        own = {"waic": dict(sums=0x2000000, rows=None),
+               "topk": dict(k=5, flags=1, cols=0x2000000, scores=0x3000000),
+               "cells": dict(n=4, row=0x2000000, col=0x3000000, val=0x4000000, mean=0x5000000, lppd=0x6000000),
+               "rank": dict(n=4, row=0x2000000, col=0x3000000, flags=1, rank=0x4000000, cand=0x5000000,
+                            score=0x6000000),
+               "predict": dict(n=4, cols=0x2000000, mean=0x3000000, sd=0x4000000, pnz=0x5000000),
+               "groups": dict(labels=0x6000000, G=4, n=4, cols=0x2000000, sum=0x3000000, nz=0x5000000),
+               "embed": dict(mean=0x2000000, sd=0x3000000)}[entry]
+        need = scratch_need(lib, entry, h, B, S, own)
+        assert need > 0 and need % 256 == 0
+        good = dict(h=h, ct=cs, S=S, pin=_lib.PtrArray(*[slots.get(n) for n in VAR_ORDER]), eta=0x7000000,
+                    ptr=0x8000000, nbytes=need, stream=None, **own)
+        no_u = _lib.PtrArray(*[slots.get(n) if n != "u" else None for n in VAR_ORDER])
+    except BaseException:
+        cleanup()
+        raise
+    return good, need, no_u, raw, cleanup
+
+
 def gpu_good_call(entry, m, x, params, k=5):
     """The arguments of a valid call of ``entry`` on model ``m`` for the batch ``x`` and the draws ``params``,
     with an exactly sized scratch of zeros and outputs filled with the sentinel -7: -> (good, need, outputs,
-    scratch, pin_without_u).  The cell list is every cell once, row by row, with values 0, 1, 2, 0, ...
-    ``outputs`` holds the device tensors by argument name; ``good["keep"]`` keeps the inputs alive."""
+    scratch, pin_without_u).  topk: ``k``.  cells and rank: every cell once, row by row (cells: with values
+    0, 1, 2, 0, ...).  predict and groups: the columns PANEL_COLS; groups: G = 3 and the labels -1, 0, 1, 2,
+    -1, ... .  ``outputs`` holds the device tensors by argument name; ``good["keep"]`` keeps the inputs alive
+    (the lists of an entry that has some come last, as a dict by argument name)."""
     from spmf_amd import _lib
     from spmf_amd._lib import VAR_ORDER
     lib, h = _lib.load(), m._handle()
     _, cs = m._batch({"counts": x})
-    S, P = m._pack_params(params, names=("s", "u", "v", "w"))
+    n_draws, P = m._pack_params(params, names=("s", "u", "v", "w"))
     pin = _lib.PtrArray(*[P[n].data_ptr() if n in P else None for n in VAR_ORDER])
     no_u = _lib.PtrArray(*[P[n].data_ptr() if n in P and n != "u" else None for n in VAR_ORDER])
     eta = m._eta_device()
-    B, D = x.shape
-    need = int(getattr(lib, ENTRIES[entry][1])(h, int(cs.n_rows), S))
-    assert need > 0 and need % 256 == 0
-    scratch = torch.zeros(need + 512, dtype=torch.uint8, device="cuda")
+    rows, width = x.shape
 
     def full(shape, dtype):
         return torch.full(shape, -7, dtype=dtype, device="cuda")
-    keep = [P, eta]
+
+    def ptrs(*dicts):
+        return {n: t.data_ptr() for d in dicts for n, t in d.items()}
+    f32, f64, i32 = torch.float32, torch.float64, torch.int32
+    lists = {}
     if entry == "waic":
-        out = {"sums": full((6,), torch.float64), "rows": full((B, 2), torch.float64)}
-        own = {n: t.data_ptr() for n, t in out.items()}
+        out = {"sums": full((6,), f64), "rows": full((rows, 2), f64)}
+        own = ptrs(out)
     elif entry == "topk":
-        out = {"cols": full((B, k), torch.int32), "scores": full((B, k), torch.float32)}
-        own = dict(k=k, flags=1, **{n: t.data_ptr() for n, t in out.items()})
-    else:
-        N = B * D
+        out = {"cols": full((rows, k), i32), "scores": full((rows, k), f32)}
+        own = dict(k=k, flags=1, **ptrs(out))
+    elif entry in ("cells", "rank"):
+        N = rows * width
         cell = torch.arange(N, device="cuda")
-        lists = {"row": (cell // D).to(torch.int32), "col": (cell % D).to(torch.int32),
-                 "val": (cell % 3).to(torch.float32)}
-        keep.append(lists)
-        out = {"mean": full((N,), torch.float32), "lppd": full((N,), torch.float32)}
-        own = dict(n=N, **{n: t.data_ptr() for n, t in {**lists, **out}.items()})
-    good = dict(h=h, ct=cs, S=S, pin=pin, eta=eta.data_ptr(), ptr=scratch.data_ptr() + (-scratch.data_ptr()) % 256,
-                nbytes=need, stream=torch.cuda.current_stream().cuda_stream, keep=keep, **own)
+        lists = {"row": (cell // width).to(i32), "col": (cell % width).to(i32)}
+        if entry == "cells":
+            lists["val"] = (cell % 3).to(f32)
+            out = {"mean": full((N,), f32), "lppd": full((N,), f32)}
+            own = dict(n=N, **ptrs(lists, out))
+        else:
+            out = {"rank": full((N,), i32), "cand": full((N,), i32), "score": full((N,), f32)}
+            own = dict(n=N, flags=1, **ptrs(lists, out))
+    elif entry == "predict":
+        lists = {"cols": torch.tensor(PANEL_COLS, dtype=i32, device="cuda")}
+        out = {n: full((rows, len(PANEL_COLS)), f32) for n in ("mean", "sd", "pnz")}
+        own = dict(n=len(PANEL_COLS), **ptrs(lists, out))
+    elif entry == "groups":
+        lists = {"labels": (torch.arange(rows, device="cuda") % 4 - 1).to(i32),
+                 "cols": torch.tensor(PANEL_COLS, dtype=i32, device="cuda")}
+        out = {n: full((n_draws, 3, len(PANEL_COLS)), f64) for n in ("sum", "nz")}
+        own = dict(G=3, n=len(PANEL_COLS), **ptrs(lists, out))
+    else:
+        out = {n: full((rows, m.latent_dim), f32) for n in ("mean", "sd")}
+        own = ptrs(out)
+    need = scratch_need(lib, entry, h, int(cs.n_rows), n_draws, own)
+    assert need > 0 and need % 256 == 0
+    scratch = torch.zeros(need + 512, dtype=torch.uint8, device="cuda")
+    good = dict(h=h, ct=cs, S=n_draws, pin=pin, eta=eta.data_ptr(),
+                ptr=scratch.data_ptr() + (-scratch.data_ptr()) % 256, nbytes=need,
+                stream=torch.cuda.current_stream().cuda_stream, keep=[P, eta, lists], **own)
     return good, need, out, scratch, no_u
 
 
-def assert_shared_errors(lib, entry, good, need, pin_without_u, mixed_ctx_without_types):
-    """The error contract of the draw stage for one entry point; every call here returns before a launch.
-    ``good``: arguments of a valid call whose scratch holds exactly ``need`` bytes."""
+def assert_shared_errors(lib, entry, good, need, pin_without_u, mixed_ctx_without_types, after=lambda: None):
+    """The error contract of the draw stage for one entry point; every call here returns before a launch, and
+    ``after`` is run behind each (the GPU files check their sentinels there).  ``good``: arguments of a valid
+    call whose scratch holds exactly ``need`` bytes.  -> the raw call."""
     call = abi_call(entry, good)
-    min_S = ENTRIES[entry][2]
     h = good["h"]
-    assert call(S=min_S - 1) == -1, "S below the minimum"
-    assert call(S=65536) == -1
-    assert call(pin=None) == -1 and call(eta=None) == -1 and call(ptr=None) == -1 and call(ct=None) == -1
-    assert call(pin=pin_without_u) == -1, "slot u missing"
-    assert call(ptr=good["ptr"] + 4) == -1, "scratch off by 4 bytes"
+
+    def refused(code, why=None, **kw):
+        assert call(**kw) == code, why or kw
+        after()
+    refused(-1, "S below the minimum", S=ENTRIES[entry].min_S - 1)
+    refused(-1, S=65536)
+    for name in ("pin", "eta", "ptr", "ct"):
+        refused(-1, **{name: None})
+    refused(-1, "slot u missing", pin=pin_without_u)
+    refused(-1, "scratch off by 4 bytes", ptr=good["ptr"] + 4)
     bad = type(good["ct"]).from_buffer_copy(good["ct"])
     bad.struct_size += 8
-    assert call(ct=bad) == -1, "struct_size + 8"
-    assert call(h=mixed_ctx_without_types) == -1
+    refused(-1, "struct_size + 8", ct=bad)
+    refused(-1, h=mixed_ctx_without_types)
     assert "column_types" in lib.spmf_last_error(mixed_ctx_without_types).decode()
-    assert call(nbytes=need - 256) == -3
+    refused(-3, nbytes=need - 256)
     msg = lib.spmf_last_error(h).decode()
     assert str(need) in msg, msg
     return call

@@ -29,9 +29,9 @@ import pytest
 import torch
 
 from oracle import spmf_oracle as O
-from _stream_cases import _problem
+from _stream_cases import _problem, assert_shared_errors, gpu_good_call
 from test_gpu_dense import _dense_model
-from test_knn_host import assert_embed_errors, assert_knn_errors, embed_raw_call, knn_raw_call
+from test_knn_host import assert_embed_own_errors, assert_knn_errors, knn_raw_call
 
 pytestmark = pytest.mark.gpu
 T = torch.as_tensor
@@ -404,33 +404,23 @@ def test_embed_nan_count_and_custom_codec():
 
 def test_embed_rows_shared_errors_launch_nothing():
     from spmf_amd import _lib
-    from spmf_amd._lib import VAR_ORDER
     lik, B, D, K, S = EMBED[0]
     cfg, x, params, mask, _ = _problem(*EMBED[0])
     m = _dense_model(lik, cfg, mask, 32)
-    lib, h = _lib.load(), m._handle()
-    _, cs = m._batch({"counts": x})
-    S_, P = m._pack_params(params, names=("s", "u", "v", "w"))
-    pin = _lib.PtrArray(*[P[n].data_ptr() if n in P else None for n in VAR_ORDER])
-    no_u = _lib.PtrArray(*[P[n].data_ptr() if n in P and n != "u" else None for n in VAR_ORDER])
-    eta = m._eta_device()
-    need = int(lib.spmf_embed_scratch_bytes(h, int(cs.n_rows), S_))
-    scratch = torch.zeros(need + 512, dtype=torch.uint8, device="cuda")
-    mean = torch.full((B, K), -7.0, dtype=torch.float32, device="cuda")
-    sd = torch.full((B, K), -7.0, dtype=torch.float32, device="cuda")
-    good = dict(h=h, ct=cs, S=S_, pin=pin, eta=eta.data_ptr(), mean=mean.data_ptr(), sd=sd.data_ptr(),
-                ptr=scratch.data_ptr() + (-scratch.data_ptr()) % 256, nbytes=need,
-                stream=torch.cuda.current_stream().cuda_stream)
+    lib = _lib.load()
+    good, need, out, scratch, no_u = gpu_good_call("embed", m, x, params)
+    mean, sd = out["mean"], out["sd"]
     raw = _dense_model("mixed", cfg, np.arange(D) % 3 == 1, 32)._new_ctx()
 
     def untouched():
         torch.cuda.synchronize()
         assert bool((mean == -7).all()) and bool((sd == -7).all()) and not bool(scratch.any())
     try:
-        assert_embed_errors(lib, good, need, no_u, raw, untouched)
+        call = assert_shared_errors(lib, "embed", good, need, no_u, raw, untouched)
+        assert_embed_own_errors(lib, call, good, untouched)
     finally:
         lib.spmf_ctx_destroy(raw)
-    assert embed_raw_call(good)() == 0
+    assert call() == 0
     torch.cuda.synchronize()
     want = m.embed({"counts": x}, draws=params, sd=True)
     assert torch.equal(_bits(mean), _bits(want["mean"])) and torch.equal(_bits(sd), _bits(want["sd"]))

@@ -15,7 +15,6 @@ _check asserts on the oracle alone what the case expects to be finite before the
 looked at, and prints the largest observed error of each output before asserting.
 
 Bernoulli damping as in test_gpu_topk (_stream_cases._problem is shared: same seeds, same cached inputs)."""
-import ctypes as C
 import functools
 import math
 
@@ -24,7 +23,7 @@ import pytest
 import torch
 
 from oracle import spmf_oracle as O
-from _stream_cases import _bern_cols, _problem
+from _stream_cases import _bern_cols, _problem, assert_shared_errors
 from test_gpu_dense import LIKELIHOODS, _dense_model, _dense_problem
 from test_gpu_parity import build_model, make_problem
 
@@ -357,40 +356,17 @@ def test_c_abi_errors_launch_nothing():
     lppd = torch.full((N,), -7.0, dtype=torch.float32, device="cuda")
     stream = torch.cuda.current_stream().cuda_stream
     good = dict(h=h, ct=cs, S=S, pin=pin, eta=eta.data_ptr(), n=N, row=r32.data_ptr(), col=c32.data_ptr(),
-                val=v32.data_ptr(), mean=mean.data_ptr(), lppd=lppd.data_ptr(), ptr=base, nbytes=need)
-
-    # a binding of its own with plain pointers, so that NULL can stand for `params` and `counts` too
-    fn = C.CDLL(_lib.LIB_PATH).spmf_score_cells
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 6 + [
-        C.c_size_t, C.c_void_p]
-
-    def call(**kw):
-        a = dict(good, **kw)
-        return fn(a["h"], C.byref(a["ct"]) if a["ct"] is not None else None, a["S"], a["pin"], a["eta"], a["n"],
-                  a["row"], a["col"], a["val"], a["mean"], a["lppd"], a["ptr"], a["nbytes"], stream)
-    assert call(S=0) == -1 and call(S=65536) == -1
-    assert call(pin=None) == -1 and call(eta=None) == -1 and call(ptr=None) == -1 and call(ct=None) == -1
-    assert call(row=None) == -1 and call(col=None) == -1 and call(mean=None) == -1
+                val=v32.data_ptr(), mean=mean.data_ptr(), lppd=lppd.data_ptr(), ptr=base, nbytes=need,
+                stream=stream)
     no_u = _lib.PtrArray(*[P[n].data_ptr() if n in P and n != "u" else None for n in VAR_ORDER])
-    assert call(pin=no_u) == -1
-    assert call(val=None) == -1 and call(lppd=None) == -1          # one of the pair without the other
-    assert call(ptr=base + 4) == -1
-    assert call(n=-1) == -1
-    bad = type(cs).from_buffer_copy(cs)
-    bad.struct_size += 8
-    assert call(ct=bad) == -1
-    mixed_mask = np.arange(45) % 3 == 1
-    mm = _dense_model("mixed", cfg, mixed_mask, 32)
-    raw = mm._new_ctx()                                            # a mixed context nobody gave column types
+    raw = _dense_model("mixed", cfg, np.arange(45) % 3 == 1, 32)._new_ctx()   # mixed, and no column types given
     try:
-        assert call(h=raw) == -1
-        assert "column_types" in lib.spmf_last_error(raw).decode()
+        call = assert_shared_errors(lib, "cells", good, need, no_u, raw)      # the draw stage's list
     finally:
         lib.spmf_ctx_destroy(raw)
-    assert call(nbytes=need - 256) == -3
-    msg = lib.spmf_last_error(h).decode()
-    assert str(need) in msg, msg
+    assert call(row=None) == -1 and call(col=None) == -1 and call(mean=None) == -1
+    assert call(val=None) == -1 and call(lppd=None) == -1          # one of the pair without the other
+    assert call(n=-1) == -1
     assert call(n=0, nbytes=need - 256) == -3                      # errors come before the empty-list return
     assert call(n=0) == 0 and call(n=0, row=None, col=None, mean=None) == 0
     torch.cuda.synchronize()

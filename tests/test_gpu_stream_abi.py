@@ -1,24 +1,29 @@
-"""GPU: the C-ABI error contract the three streaming entry points share (spmf_waic_accumulate,
-spmf_topk_rows, spmf_score_cells: include/spmf_hip.h), through ctypes at B = 70, D = 45, K = 3,
-S = 2, Poisson, panel_rows = 32.  Every error returns before a launch: outputs and scratch keep
-their sentinels.  Then the valid call returns what the Python method returns: the same bits for
-top-k and the cell list; the WAIC sums go through fp64 atomics, so they are held to the
-tolerances of test_gpu_waic_streaming.py (lppd and waic 1e-5 relative, pwaic 1e-3, row scores
-the same with an atol of that fraction of the largest row value).  The entry-specific cases (k,
-flags, the cell list's own arguments) stay with test_gpu_topk.py / test_gpu_score_cells.py."""
+"""GPU: the C-ABI error contract the draw-stage entry points share (the table of tests/_stream_cases.py:
+spmf_waic_accumulate, spmf_topk_rows, spmf_score_cells, spmf_rank_cells, spmf_predict_columns, spmf_group_sums,
+spmf_embed_rows: include/spmf_hip.h), through ctypes at B = 70, D = 45, K = 3, S = 2, Poisson, panel_rows = 32:
+a ragged 64-row block, K padded 3 -> 4, two draws so that sd is defined.  Every error returns before a launch:
+outputs and scratch keep their sentinels.  Then the valid call returns what the Python method returns: the same
+bits for every entry but the WAIC sums, which go through fp64 atomics and are held to the tolerances of
+test_gpu_waic_streaming.py (lppd and waic 1e-5 relative, pwaic 1e-3, row scores the same with an atol of that
+fraction of the largest row value).  The entry-specific cases (k, flags, the lists' own arguments) stay with
+each entry's own test file."""
 import numpy as np
 import pytest
 import torch
 
-from _stream_cases import ENTRIES, _problem, assert_shared_errors, gpu_good_call
+from _stream_cases import B, D, K, S, ENTRIES, PANEL_COLS, _problem, assert_shared_errors, gpu_good_call
 from test_gpu_dense import _dense_model
 
 pytestmark = pytest.mark.gpu
-B, D, K, S = 70, 45, 3, 2
+ACCUMULATED = ("waic", "groups")          # entries that add into their outputs
 
 
 def _bits(t):
-    return t.view(torch.int32)
+    return t.view({4: torch.int32, 8: torch.int64}[t.element_size()]) if t.dtype.is_floating_point else t
+
+
+def _same(got, want):
+    return got.dtype == want.dtype and got.shape == want.shape and torch.equal(_bits(got), _bits(want))
 
 
 @pytest.mark.parametrize("entry", list(ENTRIES))
@@ -30,28 +35,46 @@ def test_shared_errors_launch_nothing_and_the_valid_call_is_the_methods(entry):
     lib = _lib.load()
     good, need, out, scratch, no_u = gpu_good_call(entry, m, x, params)
     raw = _dense_model("mixed", cfg, np.arange(D) % 3 == 1, 32)._new_ctx()   # a mixed context nobody gave column types
+
+    def untouched():
+        torch.cuda.synchronize()
+        assert all(bool((t == -7).all()) for t in out.values()) and not bool(scratch.any())
     try:
         call = assert_shared_errors(lib, entry, good, need, no_u, raw)
     finally:
         lib.spmf_ctx_destroy(raw)
-    torch.cuda.synchronize()
-    assert all(bool((t == -7).all()) for t in out.values()) and not bool(scratch.any())
-    if entry == "waic":                                   # sums and row scores are accumulated
+    untouched()
+    if entry in ACCUMULATED:
         for t in out.values():
             t.zero_()
     assert call() == 0
     torch.cuda.synchronize()
+    batch, lists = {"counts": x}, good["keep"][-1]
     if entry == "topk":
-        want = m.top_k({"counts": x}, k=good["k"], draws=params)
-        assert torch.equal(out["cols"], want["columns"]) and torch.equal(_bits(out["scores"]), _bits(want["scores"]))
+        want = m.top_k(batch, k=good["k"], draws=params)
+        assert _same(out["cols"], want["columns"]) and _same(out["scores"], want["scores"])
     elif entry == "cells":
-        lists = good["keep"][-1]
-        want = m.score_cells({"counts": x}, lists["row"], lists["col"], values=lists["val"], draws=params)
-        assert torch.equal(_bits(out["mean"]), _bits(want["mean"]))
-        assert torch.equal(_bits(out["lppd"]), _bits(want["lppd"]))
+        want = m.score_cells(batch, lists["row"], lists["col"], values=lists["val"], draws=params)
+        assert _same(out["mean"], want["mean"]) and _same(out["lppd"], want["lppd"])
+    elif entry == "rank":
+        want = m.rank_cells(batch, lists["row"], lists["col"], draws=params)
+        assert _same(out["rank"], want["rank"]) and _same(out["cand"], want["candidates"])
+        assert _same(out["score"], want["score"])
+    elif entry == "predict":
+        want = m.predict(batch, cols=list(PANEL_COLS), draws=params, sd=True, p_nonzero=True)
+        assert _same(out["mean"], want["mean"]) and _same(out["sd"], want["sd"])
+        assert _same(out["pnz"], want["p_nonzero"])
+    elif entry == "groups":
+        want = m.group_means(batch, lists["labels"], n_groups=good["G"], cols=list(PANEL_COLS), draws=params,
+                             p_nonzero=True)
+        assert _same(out["sum"], want["sum"]) and _same(out["nz"], want["sum_nonzero"])
+        assert want["count"].tolist() == [18, 17, 17], "the labels -1, 0, 1, 2, -1, ... of 70 rows"
+    elif entry == "embed":
+        want = m.embed(batch, draws=params, sd=True)
+        assert _same(out["mean"], want["mean"]) and _same(out["sd"], want["sd"])
     else:
         got = _waic.combine(out["sums"])
-        want = m.waic_streaming({"counts": x}, draws=params, row_scores=True)
+        want = m.waic_streaming(batch, draws=params, row_scores=True)
         print("ctypes", got, "method", {k: v for k, v in want.items() if not k.startswith("row_")})
         assert got["n"] == want["n"] == B * D and got["n_excluded"] == want["n_excluded"] == 0
         assert abs(got["lppd"] - want["lppd"]) <= 1e-5 * abs(want["lppd"])

@@ -1,21 +1,21 @@
 """CPU-side tests of the neighbour calls (PoissonFactorization.embed / knn / neighbors, spmf_embed_rows,
-spmf_knn, csrc/knn.hip): the four entry points in the header, the export list and the binding, the methods on
-the class surface, the argument checks of the methods that need no device, the host helpers of
-spmf_amd.neighbors, and the argument errors of the two calls -- all refused before anything touches a device.
+spmf_knn, csrc/knn.hip): the two entry points of knn in the header, the export list and the binding (those of
+embed: the "embed" row of tests/test_stream_host.py), the methods' signatures on the class surface, the
+argument checks of the methods that need no device, the host helpers of spmf_amd.neighbors, and the argument errors of the two calls -- all refused before anything touches a device.
 (The valid calls: tests/test_gpu_knn.py.)"""
 import ctypes as C
-import fnmatch
 import inspect
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER_ARGS = {"spmf_embed_scratch_bytes": 3, "spmf_embed_rows": 10, "spmf_knn_scratch_bytes": 4, "spmf_knn": 14}
-B, D, K, S = 70, 45, 3, 2
+from _stream_cases import (B, D, K, S, ENTRIES, abi_call, assert_declared_exported_bound, assert_shared_errors,
+                           host_good_call)
+
+# spmf_knn is no draw-stage call: it is not in the contract table
+HEADER_ARGS = {"spmf_knn_scratch_bytes": 4, "spmf_knn": 14}
 
 
 @pytest.fixture(scope="module")
@@ -27,28 +27,13 @@ def lib():
     return _lib.load()
 
 
-def _header_args(hdr, name):
-    m = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", hdr, re.S)
-    assert m, f"{name} is not declared in include/spmf_hip.h"
-    return len([a for a in m.group(1).split(",") if a.strip()])
-
-
 def test_entry_points_are_declared_exported_and_bound():
-    from spmf_amd import _lib
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "spmf_hip.h")).read(), flags=re.S)
-    exports = open(os.path.join(ROOT, "spmf_amd", "csrc", "exports.map")).read()
-    exports = re.sub(r"/\*.*?\*/", "", exports, flags=re.S)
-    globs = re.search(r"global:\s*([^}]*?)local:", exports, re.S).group(1)
-    patterns = [p.strip() for p in globs.split(";") if p.strip()]
     for name, nargs in HEADER_ARGS.items():
-        assert any(fnmatch.fnmatchcase(name, p) for p in patterns), (name, patterns)
-        assert name in _lib.SIGNATURES, name
-        assert len(_lib.SIGNATURES[name][1]) == _header_args(hdr, name) == nargs, name
-    assert "define SPMF_ABI_VERSION 6" in hdr and _lib.ABI_VERSION == 6
+        assert_declared_exported_bound(name, nargs)
 
 
 def test_symbols_are_in_the_built_library(lib):
-    for name in HEADER_ARGS:
+    for name in (*HEADER_ARGS, ENTRIES["embed"].size, ENTRIES["embed"].call):
         assert callable(getattr(lib, name)), name
 
 
@@ -328,70 +313,27 @@ def test_knn_scratch_size(lib):
         lib.spmf_ctx_destroy(h)
 
 
-EMBED_OWN = (("mean", C.c_void_p), ("sd", C.c_void_p))
-
-
-def embed_raw_call(good):
-    from spmf_amd import _lib
-    fn = C.CDLL(_lib.LIB_PATH).spmf_embed_rows
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [t for _, t in EMBED_OWN] + [
-        C.c_void_p, C.c_size_t, C.c_void_p]
-
-    def call(**kw):
-        a = dict(good, **kw)
-        return fn(a["h"], C.byref(a["ct"]) if a["ct"] is not None else None, a["S"], a["pin"], a["eta"],
-                  *[a[n] for n, _ in EMBED_OWN], a["ptr"], a["nbytes"], a["stream"])
-    return call
-
-
-def assert_embed_errors(lib, good, need, no_u, mixed_ctx_without_types, after=lambda: None):
-    """The draw stage's contract (the list of _stream_cases.assert_shared_errors, min_S = 1) and the entry's
-    own; every call returns before a launch."""
-    call, h = embed_raw_call(good), good["h"]
-
-    def refused(code, **kw):
-        assert call(**kw) == code, kw
-        after()
-    refused(-1, S=0)
-    refused(-1, S=65536)
-    for name in ("pin", "eta", "ptr", "ct"):
-        refused(-1, **{name: None})
-    refused(-1, pin=no_u)
-    refused(-1, ptr=good["ptr"] + 4)
-    bad = type(good["ct"]).from_buffer_copy(good["ct"])
-    bad.struct_size += 8
-    refused(-1, ct=bad)
-    refused(-1, h=mixed_ctx_without_types)
-    assert "column_types" in lib.spmf_last_error(mixed_ctx_without_types).decode()
-    refused(-3, nbytes=need - 256)
-    assert str(need) in lib.spmf_last_error(h).decode()
-    refused(-1, mean=None)
+def assert_embed_own_errors(lib, call, good, after=lambda: None):
+    """The argument errors of spmf_embed_rows beyond the draw stage's; ``call`` is the raw call of ``good``
+    (_stream_cases.abi_call), every call returns before a launch and ``after`` is run behind each."""
+    assert call(mean=None) == -1
+    after()
     one = good["sd"] if good["sd"] is not None else 0x6000000
-    refused(-1, S=1, sd=one)
-    assert "sd_out" in lib.spmf_last_error(h).decode()
+    assert call(S=1, sd=one) == -1
+    assert "sd_out" in lib.spmf_last_error(good["h"]).decode()
+    after()
 
 
 def test_embed_errors_return_before_any_device_call(lib):
-    from spmf_amd import _lib
-    from spmf_amd._lib import VAR_ORDER
-    h, raw = _ctx(lib, K), _ctx(lib, K, _lib.FLAG_MIXED)
+    good, need, no_u, raw, cleanup = host_good_call(lib, "embed")
+    h, cs = good["h"], good["ct"]
     try:
-        cs = _lib.CountsStruct()
-        cs.struct_size = C.sizeof(_lib.CountsStruct)
-        cs.n_cols, cs.n_rows, cs.nnz, cs.row_ptr = D, B, 0, 0x10000
-        slots = {n: 0x100000 * (i + 1) for i, n in enumerate(VAR_ORDER) if n in ("s", "u", "v", "w")}
-        need = int(lib.spmf_embed_scratch_bytes(h, B, S))
-        assert need > 0 and need % 256 == 0 and need == int(lib.spmf_cells_scratch_bytes(h, B, S)), \
-            "the draw carve alone"
+        assert need == int(lib.spmf_cells_scratch_bytes(h, B, S)), "the draw carve alone"
         assert int(lib.spmf_embed_scratch_bytes(h, B, 0)) == 0 and int(lib.spmf_embed_scratch_bytes(h, B, 1)) > 0
-        good = dict(h=h, ct=cs, S=S, pin=_lib.PtrArray(*[slots.get(n) for n in VAR_ORDER]), eta=0x7000000,
-                    ptr=0x8000000, nbytes=need, stream=None, mean=0x2000000, sd=0x3000000)
-        no_u = _lib.PtrArray(*[slots.get(n) if n != "u" else None for n in VAR_ORDER])
-        assert_embed_errors(lib, good, need, no_u, raw)
+        call = assert_shared_errors(lib, "embed", good, need, no_u, raw)
+        assert_embed_own_errors(lib, call, good)
         empty = type(cs).from_buffer_copy(cs)
         empty.n_rows = 0
-        assert embed_raw_call(good)(ct=empty) == 0, "an empty batch launches nothing"
+        assert abi_call("embed", good)(ct=empty) == 0, "an empty batch launches nothing"
     finally:
-        lib.spmf_ctx_destroy(h)
-        lib.spmf_ctx_destroy(raw)
+        cleanup()

@@ -1,22 +1,17 @@
-"""CPU-side tests of predict (PoissonFactorization.predict, spmf_predict_columns, csrc/panel.hip): the two
-entry points in the header, the export list and the binding, the method on the class surface, the error
+"""CPU-side tests of predict (PoissonFactorization.predict, spmf_predict_columns, csrc/panel.hip): the error
 contract of the draw stage and the entry's own argument errors -- all refused before anything touches a
 device -- the empty cases, the scratch size, and the argument checks of the method that need no device.
-(The valid call: tests/test_gpu_predict.py.)"""
+(Declared / exported / bound and the method on the classes: the "predict" row of tests/test_stream_host.py; the
+valid call: tests/test_gpu_predict.py.)"""
 import ctypes as C
-import fnmatch
 import os
-import re
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CALL, SIZE = "spmf_predict_columns", "spmf_predict_scratch_bytes"
-HEADER_ARGS = {SIZE: 3, CALL: 13}
-# the arguments between `eta` and `scratch` in the header's order
-OWN = (("n", C.c_int32), ("cols", C.c_void_p), ("mean", C.c_void_p), ("sd", C.c_void_p), ("pnz", C.c_void_p))
-B, D, K, S = 70, 45, 3, 2
+from _stream_cases import B, D, ENTRIES, S, assert_shared_errors, host_good_call
+
+CALL, SIZE = ENTRIES["predict"].call, ENTRIES["predict"].size
 
 
 @pytest.fixture(scope="module")
@@ -28,35 +23,9 @@ def lib():
     return _lib.load()
 
 
-def _header_args(hdr, name):
-    m = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", hdr, re.S)
-    assert m, f"{name} is not declared in include/spmf_hip.h"
-    return len([a for a in m.group(1).split(",") if a.strip()])
-
-
-def test_entry_points_are_declared_exported_and_bound():
-    from spmf_amd import _lib
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "spmf_hip.h")).read(), flags=re.S)
-    exports = open(os.path.join(ROOT, "spmf_amd", "csrc", "exports.map")).read()
-    exports = re.sub(r"/\*.*?\*/", "", exports, flags=re.S)
-    globs = re.search(r"global:\s*([^}]*?)local:", exports, re.S).group(1)
-    patterns = [p.strip() for p in globs.split(";") if p.strip()]
-    for name, nargs in HEADER_ARGS.items():
-        assert any(fnmatch.fnmatchcase(name, p) for p in patterns), (name, patterns)
-        assert name in _lib.SIGNATURES, name
-        assert len(_lib.SIGNATURES[name][1]) == _header_args(hdr, name) == nargs, name
-    assert "define SPMF_ABI_VERSION 6" in hdr and _lib.ABI_VERSION == 6
-
-
 def test_symbols_are_in_the_built_library(lib):
     assert callable(getattr(lib, CALL)) and callable(getattr(lib, SIZE))
     assert lib.spmf_version() == 6
-
-
-def test_method_is_on_all_three_classes():
-    from spmf_amd import BernoulliFactorization, MixedFactorization, PoissonFactorization
-    for cls in (PoissonFactorization, BernoulliFactorization, MixedFactorization):
-        assert callable(getattr(cls, "predict", None)), cls.__name__
 
 
 def _ctx(lib, k, flags=0, d=D):
@@ -65,56 +34,14 @@ def _ctx(lib, k, flags=0, d=D):
     return h
 
 
-def _raw_call(good):
-    """-> call(**overrides): spmf_predict_columns through a binding of its own with plain pointers, so that
-    NULL can stand for `params` and `counts` too."""
-    from spmf_amd import _lib
-    fn = getattr(C.CDLL(_lib.LIB_PATH), CALL)
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [t for _, t in OWN] + [
-        C.c_void_p, C.c_size_t, C.c_void_p]
-
-    def call(**kw):
-        a = dict(good, **kw)
-        return fn(a["h"], C.byref(a["ct"]) if a["ct"] is not None else None, a["S"], a["pin"], a["eta"],
-                  *[a[n] for n, _ in OWN], a["ptr"], a["nbytes"], a["stream"])
-    return call
-
-
 def test_shared_and_own_errors_return_before_any_device_call(lib):
-    """A context of spmf_ctx_create (K = 3, D = 45), a hand-filled descriptor of 70 empty rows and dummy aligned
-    addresses: the error cases of the draw stage (the list of _stream_cases.assert_shared_errors) and the
-    entry's own are refused with their codes, before the empty returns; nothing here is a valid call with
-    work to do, so nothing may be launched or dereferenced."""
-    from spmf_amd import _lib
-    from spmf_amd._lib import VAR_ORDER
-    h, raw = _ctx(lib, K), _ctx(lib, K, _lib.FLAG_MIXED)
+    """The dummy-address call of _stream_cases.host_good_call (K = 3, D = 45, 70 empty rows): the error cases of
+    the draw stage (_stream_cases.assert_shared_errors) and the entry's own are refused with their codes, before
+    the empty returns; nothing here is a valid call with work to do, so nothing may be launched or dereferenced."""
+    good, need, no_u, raw, cleanup = host_good_call(lib, "predict")
+    h, cs = good["h"], good["ct"]
     try:
-        cs = _lib.CountsStruct()
-        cs.struct_size = C.sizeof(_lib.CountsStruct)
-        cs.n_cols, cs.n_rows, cs.nnz, cs.row_ptr = D, B, 0, 0x10000
-        slots = {n: 0x100000 * (i + 1) for i, n in enumerate(VAR_ORDER) if n in ("s", "u", "v", "w")}
-        need = int(lib.spmf_predict_scratch_bytes(h, B, S))
-        assert need > 0 and need % 256 == 0
-        good = dict(h=h, ct=cs, S=S, pin=_lib.PtrArray(*[slots.get(n) for n in VAR_ORDER]), eta=0x7000000,
-                    ptr=0x8000000, nbytes=need, stream=None, n=4, cols=0x2000000, mean=0x3000000,
-                    sd=0x4000000, pnz=0x5000000)
-        no_u = _lib.PtrArray(*[slots.get(n) if n != "u" else None for n in VAR_ORDER])
-        call = _raw_call(good)
-        # the draw stage's contract (min_S = 1)
-        assert call(S=0) == -1, "S below the minimum"
-        assert call(S=65536) == -1
-        assert call(pin=None) == -1 and call(eta=None) == -1 and call(ptr=None) == -1 and call(ct=None) == -1
-        assert call(pin=no_u) == -1, "slot u missing"
-        assert call(ptr=good["ptr"] + 4) == -1, "scratch off by 4 bytes"
-        bad = type(cs).from_buffer_copy(cs)
-        bad.struct_size += 8
-        assert call(ct=bad) == -1, "struct_size + 8"
-        assert call(h=raw) == -1
-        assert "column_types" in lib.spmf_last_error(raw).decode()
-        assert call(nbytes=need - 256) == -3
-        msg = lib.spmf_last_error(h).decode()
-        assert str(need) in msg, msg
+        call = assert_shared_errors(lib, "predict", good, need, no_u, raw)
         # the entry's own
         assert call(mean=None) == -1, "no mean_out with work to do"
         assert "mean_out" in lib.spmf_last_error(h).decode()
@@ -139,8 +66,7 @@ def test_shared_and_own_errors_return_before_any_device_call(lib):
             "an empty batch"
         assert call(n=0, S=1, sd=None, nbytes=need1) == 0
     finally:
-        lib.spmf_ctx_destroy(h)
-        lib.spmf_ctx_destroy(raw)
+        cleanup()
 
 
 @pytest.mark.parametrize("k", [3, 16, 64, 128])

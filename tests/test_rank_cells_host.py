@@ -1,25 +1,19 @@
-"""CPU-side tests of rank_cells (PoissonFactorization.rank_cells, spmf_rank_cells, csrc/rank.hip): the two
-entry points in the header, the export list and the binding, the method on the class surface, the error
+"""CPU-side tests of rank_cells (PoissonFactorization.rank_cells, spmf_rank_cells, csrc/rank.hip): the error
 contract of the draw stage and the entry's own argument errors -- all refused before anything touches a
-device -- the summary of spmf_amd.heldout.rank_summary on hand cases, and the argument checks of the method
-that need no device.  (The valid call: tests/test_gpu_rank_cells.py.)"""
+device -- the scratch size, the summary of spmf_amd.heldout.rank_summary on hand cases, and the argument checks
+of the method that need no device.  (Declared / exported / bound and the method on the classes: the "rank" row
+of tests/test_stream_host.py; the valid call: tests/test_gpu_rank_cells.py.)"""
 import ctypes as C
-import fnmatch
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CALL, SIZE = "spmf_rank_cells", "spmf_rank_scratch_bytes"
-HEADER_ARGS = {SIZE: 3, CALL: 15}
-# the arguments between `eta` and `scratch` in the header's order
-OWN = (("n", C.c_int64), ("row", C.c_void_p), ("col", C.c_void_p), ("flags", C.c_uint), ("rank", C.c_void_p),
-       ("cand", C.c_void_p), ("score", C.c_void_p))
-B, D, K, S = 70, 45, 3, 2
+from _stream_cases import B, D, ENTRIES, assert_shared_errors, host_good_call
+
+CALL, SIZE = ENTRIES["rank"].call, ENTRIES["rank"].size
 
 
 @pytest.fixture(scope="module")
@@ -31,34 +25,8 @@ def lib():
     return _lib.load()
 
 
-def _header_args(hdr, name):
-    m = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", hdr, re.S)
-    assert m, f"{name} is not declared in include/spmf_hip.h"
-    return len([a for a in m.group(1).split(",") if a.strip()])
-
-
-def test_entry_points_are_declared_exported_and_bound():
-    from spmf_amd import _lib
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "spmf_hip.h")).read(), flags=re.S)
-    exports = open(os.path.join(ROOT, "spmf_amd", "csrc", "exports.map")).read()
-    exports = re.sub(r"/\*.*?\*/", "", exports, flags=re.S)
-    globs = re.search(r"global:\s*([^}]*?)local:", exports, re.S).group(1)
-    patterns = [p.strip() for p in globs.split(";") if p.strip()]
-    for name, nargs in HEADER_ARGS.items():
-        assert any(fnmatch.fnmatchcase(name, p) for p in patterns), (name, patterns)
-        assert name in _lib.SIGNATURES, name
-        assert len(_lib.SIGNATURES[name][1]) == _header_args(hdr, name) == nargs, name
-    assert "define SPMF_ABI_VERSION 6" in hdr and _lib.ABI_VERSION == 6
-
-
 def test_symbols_are_in_the_built_library(lib):
     assert callable(getattr(lib, CALL)) and callable(getattr(lib, SIZE))
-
-
-def test_method_is_on_all_three_classes():
-    from spmf_amd import BernoulliFactorization, MixedFactorization, PoissonFactorization
-    for cls in (PoissonFactorization, BernoulliFactorization, MixedFactorization):
-        assert callable(getattr(cls, "rank_cells", None)), cls.__name__
 
 
 def _ctx(lib, k, flags=0):
@@ -67,55 +35,14 @@ def _ctx(lib, k, flags=0):
     return h
 
 
-def _raw_call(good):
-    """-> call(**overrides): spmf_rank_cells through a binding of its own with plain pointers, so that NULL can
-    stand for `params` and `counts` too (what _stream_cases.abi_call does for the entries of its table)."""
-    from spmf_amd import _lib
-    fn = getattr(C.CDLL(_lib.LIB_PATH), CALL)
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [t for _, t in OWN] + [
-        C.c_void_p, C.c_size_t, C.c_void_p]
-
-    def call(**kw):
-        a = dict(good, **kw)
-        return fn(a["h"], C.byref(a["ct"]) if a["ct"] is not None else None, a["S"], a["pin"], a["eta"],
-                  *[a[n] for n, _ in OWN], a["ptr"], a["nbytes"], a["stream"])
-    return call
-
-
 def test_shared_and_own_errors_return_before_any_device_call(lib):
-    """A context of spmf_ctx_create, a hand-filled descriptor of 70 empty rows and dummy aligned addresses: the
-    error cases of the draw stage (the list of _stream_cases.assert_shared_errors) and the entry's own are
-    refused with their codes; nothing here is a valid call, so nothing may be launched or dereferenced."""
-    from spmf_amd import _lib
-    from spmf_amd._lib import VAR_ORDER
-    h, raw = _ctx(lib, K), _ctx(lib, K, _lib.FLAG_MIXED)
+    """The dummy-address call of _stream_cases.host_good_call: the error cases of the draw stage
+    (_stream_cases.assert_shared_errors) and the entry's own are refused with their codes; nothing here is a
+    valid call, so nothing may be launched or dereferenced."""
+    good, need, no_u, raw, cleanup = host_good_call(lib, "rank")
+    h, cs = good["h"], good["ct"]
     try:
-        cs = _lib.CountsStruct()
-        cs.struct_size = C.sizeof(_lib.CountsStruct)
-        cs.n_cols, cs.n_rows, cs.nnz, cs.row_ptr = D, B, 0, 0x10000
-        slots = {n: 0x100000 * (i + 1) for i, n in enumerate(VAR_ORDER) if n in ("s", "u", "v", "w")}
-        need = int(lib.spmf_rank_scratch_bytes(h, B, S))
-        assert need > 0 and need % 256 == 0
-        good = dict(h=h, ct=cs, S=S, pin=_lib.PtrArray(*[slots.get(n) for n in VAR_ORDER]), eta=0x7000000,
-                    ptr=0x8000000, nbytes=need, stream=None, n=4, row=0x2000000, col=0x3000000, flags=1,
-                    rank=0x4000000, cand=0x5000000, score=0x6000000)
-        no_u = _lib.PtrArray(*[slots.get(n) if n != "u" else None for n in VAR_ORDER])
-        call = _raw_call(good)
-        # the draw stage's contract
-        assert call(S=0) == -1, "S below the minimum"
-        assert call(S=65536) == -1
-        assert call(pin=None) == -1 and call(eta=None) == -1 and call(ptr=None) == -1 and call(ct=None) == -1
-        assert call(pin=no_u) == -1, "slot u missing"
-        assert call(ptr=good["ptr"] + 4) == -1, "scratch off by 4 bytes"
-        bad = type(cs).from_buffer_copy(cs)
-        bad.struct_size += 8
-        assert call(ct=bad) == -1, "struct_size + 8"
-        assert call(h=raw) == -1
-        assert "column_types" in lib.spmf_last_error(raw).decode()
-        assert call(nbytes=need - 256) == -3
-        msg = lib.spmf_last_error(h).decode()
-        assert str(need) in msg, msg
+        call = assert_shared_errors(lib, "rank", good, need, no_u, raw)
         # the entry's own
         assert call(n=-1) == -1
         assert "n_cells" in lib.spmf_last_error(h).decode()
@@ -131,8 +58,7 @@ def test_shared_and_own_errors_return_before_any_device_call(lib):
         empty.n_rows = 0
         assert call(ct=empty) == 0, "an empty batch"
     finally:
-        lib.spmf_ctx_destroy(h)
-        lib.spmf_ctx_destroy(raw)
+        cleanup()
 
 
 @pytest.mark.parametrize("k", [3, 16, 64, 128])

@@ -1,8 +1,8 @@
 """Do two builds of the library return the same bits from the streaming calls?
 
-    stream_bits.py dump FILE          run top_k, score_cells, rank_cells, embed and waic_streaming at four small
-                                      cases, and knn at two shapes, with the library that SPMF_LIB_PATH names
-                                      (default: the tree's own) and save every output to FILE
+    stream_bits.py dump FILE          run top_k, score_cells, rank_cells, embed, predict, group_means and
+                                      waic_streaming at four small cases, and knn at two shapes, with the library
+                                      that SPMF_LIB_PATH names (default: the tree's own) and save every output to FILE
     stream_bits.py compare A B [OUT]  compare two dumps tensor by tensor with torch.equal -> one JSON line,
                                       also written to OUT
 
@@ -10,14 +10,16 @@ The cases are problems of tests/_stream_cases.py, (likelihood, B, D, K, S): pois
 (65, 130, 40, 3), bernoulli_log (70, 150, 3, 2) and poisson (40, 70, 128, 3), i.e. KP 16, 64, 4 and 128.
 top_k: k = 10 and 64, stored cells excluded and not, columns and scores.  score_cells: every cell listed in a
 seeded random order with values 0 .. 3: mean and lppd.  rank_cells: the same list, stored cells excluded: rank,
-candidates and score.  embed: mean and (S >= 2) deviation.  knn: two of tests/test_gpu_knn.py's SHAPES with its
+candidates and score.  embed: mean and (S >= 2) deviation.  predict: mean, (S >= 2) sd and p_nonzero for all
+columns and for the list (D - 1, 0, 3, 3, D // 2), which holds a duplicate.  group_means: sum and sum_nonzero for
+the labels -1, 0, 1, 2, -1, ... with four groups (group 3 is empty), all columns and the same list.  knn: two of tests/test_gpu_knn.py's SHAPES with its
 points, (nq, nr, K, k) = (131, 197, 16, 10) Euclidean under both SPMF_KNN_TILE values and (5, 333, 33, 64) cosine:
 indices and distances.  waic_streaming (row scores included) is called
 TWICE in each dump: its fp64 sums are atomics, so `compare` also reports whether the two calls of one build
 agree, which is the bar a comparison across builds has to be read against.
 
 A dump is made in a process of its own per build (a library is loaded once per process); a build from before
-embed / knn lacks their entry points and dumps no embed / knn tensor."""
+embed / knn (predict, group_means) lacks their entry points and dumps no tensor of theirs."""
 import ctypes as C
 import json
 import os
@@ -30,7 +32,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 CASES = [("poisson", 131, 197, 16, 7), ("mixed", 65, 130, 40, 3), ("bernoulli_log", 70, 150, 3, 2),
          ("poisson", 40, 70, 128, 3)]
 KNN_CASES = [(131, 197, 16, 10, "euclidean", ("0", "1")), (5, 333, 33, 64, "cosine", (None,))]
-CALLS = ("top_k", "score_cells", "rank_cells", "embed", "knn")
+CALLS = ("top_k", "score_cells", "rank_cells", "embed", "knn", "predict", "group_means")
 
 
 def dump(path):
@@ -44,7 +46,8 @@ def dump(path):
     from _stream_cases import _problem
     from test_gpu_dense import _dense_model
     with_knn = "spmf_knn" in _lib.SIGNATURES and "spmf_embed_rows" in _lib.SIGNATURES
-    out = {"lib": os.path.relpath(_lib.LIB_PATH, ROOT), "device": torch.cuda.get_device_name(0)}
+    out = {"lib": os.path.relpath(_lib.LIB_PATH, ROOT), "tree": os.path.basename(ROOT),
+           "device": torch.cuda.get_device_name(0)}
     for lik, B, D, K, S in CASES:
         cfg, x, params, mask, _ = _problem(lik, B, D, K, S)
         m = _dense_model(lik, cfg, mask, 32)
@@ -65,6 +68,17 @@ def dump(path):
         if with_knn:
             for name, v in m.embed(batch, draws=params, sd=S >= 2).items():
                 out[f"embed/{tag}/{name}"] = v.cpu()
+        listed = np.array([D - 1, 0, 3, 3, D // 2])
+        for cols, ctag in ((None, "all"), (listed, "listed")):
+            if "spmf_predict_columns" in _lib.SIGNATURES:
+                for name, v in m.predict(batch, cols=cols, draws=params, sd=S >= 2, p_nonzero=True).items():
+                    if name != "columns":
+                        out[f"predict/{tag}/{ctag}/{name}"] = v.cpu()
+            if "spmf_group_sums" in _lib.SIGNATURES:
+                grp = m.group_means(batch, np.arange(B) % 4 - 1, n_groups=4, cols=cols, draws=params, p_nonzero=True)
+                assert grp["count"].tolist()[3] == 0
+                for name in ("sum", "sum_nonzero"):
+                    out[f"group_means/{tag}/{ctag}/{name}"] = grp[name].cpu()
         for call in (0, 1):
             w = m.waic_streaming(batch, draws=params, row_scores=True)
             for name, v in w.items():
@@ -98,7 +112,7 @@ def compare(a_path, b_path, out_path=None):
     a, b = torch.load(a_path), torch.load(b_path)
     keys = sorted(k for k in a if torch.is_tensor(a[k]))
     assert keys == sorted(k for k in b if torch.is_tensor(b[k])), "the two dumps hold different outputs"
-    res = {"a": a["lib"], "b": b["lib"], "device": a["device"], "cases": ["%s %dx%d K=%d S=%d" % c for c in CASES],
+    res = {"a": a["lib"], "b": b["lib"], "a_tree": a.get("tree"), "b_tree": b.get("tree"), "device": a["device"], "cases": ["%s %dx%d K=%d S=%d" % c for c in CASES],
            "knn_cases": ["%dx%d K=%d k=%d %s, SPMF_KNN_TILE %s" % (*c[:5], " and ".join(t or "unset" for t in c[5]))
                          for c in KNN_CASES]}
     for call in CALLS:
