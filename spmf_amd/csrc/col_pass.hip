@@ -23,10 +23,13 @@
 // float4, so a wave holds NG=64/LPN lane groups; EACH GROUP OWNS ONE ITEM and
 // keeps that item's gV'/gA'/gphi slices in registers, so there is no
 // cross-lane reduction besides the DPP fold of the dot product.  A group
-// streams its item LPN entries per fetch (one per lane, a 4*LPN-B contiguous
-// read), two fetches ahead of use, and broadcasts an entry inside the group
-// with ds_bpermute; gathers are issued four entries (eight 16-B loads per
-// lane) at a time.
+// streams its item 4*LPN entries per fetch (four per lane, a 16*LPN-B
+// contiguous read; the narrow form LPN entries, one per lane) and broadcasts
+// an entry inside the group with ds_bpermute; gathers are issued four entries
+// (eight 16-B loads per lane) at a time.  The next fetch is loaded at the top
+// of a step, under each lane's own bound, and copied into place at its end
+// (the kernel's loop: the forms that load it unconditionally behind the step's
+// gathers, in a loop body that stands twice, measured slower).
 //
 // L2 residency is what makes the 2 x 4*KP-B-per-entry gathers affordable
 // (measured: served from Infinity Cache instead, the pass runs at ~8.6 TB/s
@@ -248,7 +251,14 @@ __global__ __launch_bounds__(256, EPL == 4 ? COL_WIDE_WAVES : 1) void col_pass_k
     }
   };
 
-  // the wide fetch runs one fetch (4*LPN entries) ahead of use, the narrow one two (2*LPN entries)
+  // The next fetch is loaded at the top of a step (the wide form's next 4*LPN entries; the narrow form runs two
+  // fetches, 2*LPN entries, ahead).  It stands in front of the step's gathers -- vector-memory operations return in
+  // issue order, so the first gather's wait is a wait for it too -- and the copy fa = fb at the step's end waits for it
+  // again.  Round 6 built the alternative: every lane loads, unconditionally (inside the lists' padding), behind the
+  // gathers of the step's first or last group or at the top, in a loop body that stands twice with fa and fb in
+  // swapped roles, so that every wait is counted.  All of those were SLOWER on C3 (1.21 -> 1.26 ... 1.30 ms,
+  // profiles/r06_stream_issue_ab.txt): the lanes behind a list's end then load too (one more 128-B line per list
+  // of ~57 entries, from HBM), and the later the fetch is issued, the less of a step it has to land in.
   Raw fa, fb, fc;
   fetch_raw(fa);
   if (EPL == 1) fetch_raw(fb);

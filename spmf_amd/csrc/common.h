@@ -218,6 +218,16 @@ __device__ __forceinline__ float4 gather4(const GTable& t, int row, int sub) {
   return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
 }
 
+// Pins the ISSUE point of the memory operations around it: no load or store is moved across it, by the
+// optimiser (which sinks a load whose result is first used much later down to that use) or by the instruction
+// scheduler.  It emits no instruction and no wait.  The row pass places its stream loads with it: vector
+// memory operations return in issue order, so where a load stands among the gathers decides who waits for it.
+// The (wave-uniform) base pointers of the arrays concerned are handed to it: what a __restrict__ kernel argument
+// points to is otherwise known not to be touched by it, and loads from it move across all the same.
+__device__ __forceinline__ void issue_fence(const void* a, const void* b = nullptr, const void* c = nullptr) {
+  asm volatile("" ::"s"(a), "s"(b), "s"(c) : "memory");
+}
+
 // ---- DPP cross-lane adds (no LDS traffic, fold into v_add_f32_dpp) --------
 // ctrl: quad_perm[1,0,3,2]=0xB1 (xor 1), quad_perm[2,3,0,1]=0x4E (xor 2),
 // row_half_mirror=0x141 (i <-> 7-i), row_mirror=0x140 (i <-> 15-i),

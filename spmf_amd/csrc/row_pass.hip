@@ -23,6 +23,11 @@
 // flight per wave; rows of <= 128 entries keep col/val in registers for both
 // sweeps.
 //
+// Stream loads: the entry words of the next row, the row pointers of the one
+// after it and the dynamic tail's counter are asked for at ONE point of a row,
+// behind its last gathers (issue_next in the row loop: why, and what it
+// measured, is written there and in profiles/r06_stream_issue_ab.txt).
+//
 // Roofline: HBM traffic is 8 B per stored entry (+ an L2-served re-read for
 // long rows) + 8*KP B per row written; the factor-row gathers (2 x 4*KP B per
 // entry) are served by L2/Infinity Cache because A' and V' (D*KP*4 B each)
@@ -47,10 +52,6 @@ static_assert(ROW_MAX_BLOCKS <= spmf::kDetMaxBlocks,
 #ifndef ROW_GRP
 #define ROW_GRP 4
 #endif
-// short rows: the V' gathers of a row's first chunk are issued before sweep 1 (RowCtx::s2_load)
-#ifndef ROW_V_AHEAD
-#define ROW_V_AHEAD 2
-#endif
 #ifndef ROW_WAVES_PER_SIMD
 #define ROW_WAVES_PER_SIMD 1
 #endif
@@ -68,30 +69,51 @@ __device__ __forceinline__ float* lds_dyn() {
 
 // One stored entry: from the packed stream (col << 16 | count: half the bytes) when the batch
 // carries one, from the canonical col / val arrays otherwise.  PACKED is a template parameter of the
-// kernel (the resident-set launches have both forms).  load_entry only LOADS (into the pipeline registers of the row prefetch);
+// kernel (the resident-set launches have both forms).  load_entry only LOADS (into the row loop's pipeline registers, at its issue point);
 // unpack_entry turns them into (column, count) where they are used, one row later -- arithmetic
-// on the loaded word right away would put the wait for the prefetch in front of it.
+// on the loaded word right away would put the wait for that load in front of it.
 // FMT 0: canonical (col, val).  FMT 1: packed word.
-template <int FMT, bool NT>
-__device__ __forceinline__ void load_entry(const int32_t* __restrict__ col, const float* __restrict__ val,
-                                           const uint32_t* __restrict__ ent, int i, bool ok, int& ra,
-                                           float& rb) {
+//
+// The entries of ONE row as a buffer (EntryRow: base = the row's first entry, size = its length; start and n are
+// wave-uniform), so that every lane loads on every path: a lane behind the row's end is dropped by the address
+// unit's range check (no memory operation; it returns 0), and unpack_entry, which is given the lane's `ok`,
+// puts the padding entry in its place.  A load under a lane predicate is a branch on the exec mask instead, and
+// behind the join of two paths that issued different numbers of loads the compiler waits for the longer count.
+template <int FMT>
+struct EntryRow {
+  __amdgpu_buffer_rsrc_t a, b;
+};
+template <int FMT>
+__device__ __forceinline__ EntryRow<FMT> entry_row(const int32_t* __restrict__ col, const float* __restrict__ val,
+                                                   const uint32_t* __restrict__ ent, int start, int n) {
+  EntryRow<FMT> r;
+  start = __builtin_amdgcn_readfirstlane(start);
+  n = __builtin_amdgcn_readfirstlane(n);
   if (FMT == 1) {
-    ra = ok ? (int)(NT ? __builtin_nontemporal_load(&ent[i]) : ent[i]) : (int)kPadWord;
-    rb = 0.f;
+    r.a = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(ent + start), 0, n * 4, 0x00020000);
+    r.b = r.a;
   } else {
-    ra = ok ? (NT ? __builtin_nontemporal_load(&col[i]) : col[i]) : kPadRow;
-    rb = ok ? (NT ? __builtin_nontemporal_load(&val[i]) : val[i]) : 0.f;
+    r.a = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(col + start), 0, n * 4, 0x00020000);
+    r.b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(val + start), 0, n * 4, 0x00020000);
   }
+  return r;
+}
+// entry i of the row (NT: read once, the non-temporal hint)
+template <int FMT, bool NT>
+__device__ __forceinline__ void load_entry(const EntryRow<FMT>& r, int i, int& ra, float& rb) {
+  constexpr int AUX = NT ? 2 : 0;
+  ra = (int)__builtin_amdgcn_raw_buffer_load_b32(r.a, i * 4, 0, AUX);
+  rb = FMT == 1 ? 0.f : __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r.b, i * 4, 0, AUX));
 }
 template <int FMT>
-__device__ __forceinline__ void unpack_entry(int ra, float rb, int& c, float& x) {
+__device__ __forceinline__ void unpack_entry(int ra, float rb, bool ok, int& c, float& x) {
   if (FMT == 1) {
-    c = (int)((uint32_t)ra >> 16);
-    x = (float)((uint32_t)ra & 0xffffu);
+    const uint32_t w = ok ? (uint32_t)ra : kPadWord;
+    c = (int)(w >> 16);
+    x = (float)(w & 0xffffu);
   } else {
-    c = ra;
-    x = rb;
+    c = ok ? ra : kPadRow;
+    x = ok ? rb : 0.f;
   }
 }
 
@@ -150,13 +172,15 @@ struct RowCtx {
 
   // sweep-2 pieces of one group of GRP gather instructions of which CNT carry entries
   template <int CNT>
-  __device__ __forceinline__ void s2_gather(int c, int g0, const float4& z, float4 (&vv)[LPN],
-                                            float& rmine) const {
+  __device__ __forceinline__ void s2_issue(int c, int g0, float4 (&vv)[LPN]) const {
 #pragma unroll
     for (int j = 0; j < CNT; ++j) {
       const int d = bperm_i<BPI>(bp_grp, (g0 + j) * NPI, c);
       vv[g0 + j] = gather4<LPN>(Vp, d, sub);
     }
+  }
+  template <int CNT>
+  __device__ __forceinline__ void s2_dots(int g0, const float4& z, float4 (&vv)[LPN], float& rmine) const {
 #pragma unroll
     for (int j = 0; j < CNT; ++j) {
       const float dot = group_sum<LPN>(dot4(z, vv[g0 + j]));
@@ -175,10 +199,9 @@ struct RowCtx {
     }
   }
 
-  // The V' gathers of one chunk, ISSUED and not waited for (short rows, ROW_V_AHEAD: a row's first chunk asks for
-  // its V' rows before sweep 1 starts -- they depend on the column indices only, not on z -- so they are in
-  // flight beside the A' gathers and sweep 2 of that chunk starts on loaded registers; a later chunk asks for all
-  // of its groups at once instead of group by group)
+  // The V' gathers of one chunk, ISSUED and not waited for (short rows at K <= 32: a chunk asks for all of its
+  // groups at once instead of group by group, and the row loop puts its issue point between this and the dot
+  // products)
   __device__ __forceinline__ void s2_load(int c, int nchunk, float4 (&vv)[LPN]) const {
 #pragma unroll
     for (int g0 = 0; g0 < LPN; g0 += GRP) {
@@ -213,15 +236,20 @@ struct RowCtx {
     s2_cells(c, x, nchunk, rmine, vv, gz, ll, nnf);
   }
 
-  // rates, log-likelihood and gz partial over one chunk
-  __device__ __forceinline__ void sweep2(int c, float x, int nchunk, const float4& z,
-                                         float4& gz, float& ll, double& nnf) const {
+  // rates, log-likelihood and gz partial over one chunk, group by group; `behind_last` runs behind the gathers of
+  // the chunk's last group, before they are waited for (the row loop's issue_next in a row's last chunk)
+  template <class Hook>
+  __device__ __forceinline__ void sweep2(int c, float x, int nchunk, const float4& z, float4& gz, float& ll,
+                                         double& nnf, Hook&& behind_last) const {
     float4 vv[LPN];
     float rmine = 0.f;
 #pragma unroll
     for (int g0 = 0; g0 < LPN; g0 += GRP) {
-      if (g0 * NPI < nchunk) s2_gather<GRP>(c, g0, z, vv, rmine);
-      else s2_gather<0>(c, g0, z, vv, rmine);
+      const bool occ = g0 * NPI < nchunk;                                     // wave-uniform
+      if (occ) s2_issue<GRP>(c, g0, vv);
+      if (g0 + GRP >= LPN) behind_last();
+      if (occ) s2_dots<GRP>(g0, z, vv, rmine);
+      else s2_dots<0>(g0, z, vv, rmine);
     }
     s2_cells(c, x, nchunk, rmine, vv, gz, ll, nnf);
   }
@@ -278,6 +306,8 @@ struct RowCtx {
 // BT: threads per workgroup.  256: phi from global memory.  512 / 1024: phi staged in LDS
 // (4*D bytes of dynamic LDS: two workgroups per CU up to D = 20 480, one up to 40 960),
 // four waves per SIMD either way.
+// Launch contract: blockDim.x == BT (the wave number is computed from BT), and B < 2^31 -- row numbers are 32-bit
+// scalars inside, although the argument is int64_t (the host admits B * KP * 4 < 4 GiB only: api.hip).
 template <int KP, int LIK, int BT = 256, int PACKED = 0>
 __global__ __launch_bounds__(BT, BT == 256 ? ROW_WAVES_PER_SIMD : 4) void row_pass_kernel(
     int64_t B, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
@@ -316,8 +346,12 @@ __global__ __launch_bounds__(BT, BT == 256 ? ROW_WAVES_PER_SIMD : 4) void row_pa
   cx.bp_grp = cx.grp * 4;
   cx.bp_row = cx.grp * LPN * 4;
   const int lane = cx.lane, sub = cx.sub, grp = cx.grp;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  // The wave's number as a scalar (blockDim.x is BT): the row numbers a wave derives from it, and with them the
+  // addresses of row_ptr[b], row_ptr[b + 1] and row_scale[b], are then wave-uniform for the compiler too, and a
+  // row's bookkeeping is read by scalar loads -- three vector loads per row less in the in-order queue.
+  const int wave = (int)blockIdx.x * (BT / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int nwaves = (int)gridDim.x * (BT / 64);
+  const int Bn = (int)B;   // row numbers fit 32 bits: B * KP * 4 < 4 GiB (checked by the host), and scalars are scarce here
 
   float4 veta4 = make_float4(0.f, 0.f, 0.f, 0.f);
   if (!encode_only && (mode != 2 || LIK == 3 || !gzd))
@@ -337,82 +371,108 @@ __global__ __launch_bounds__(BT, BT == 256 ? ROW_WAVES_PER_SIMD : 4) void row_pa
   // the slot, so its tail pair is always zero).
   // Off (B_static = B) in the deterministic mode -- which workgroup sums which rows must not depend on timing
   // there -- and for launches that share a step's scalar block with another row launch (dyn_tail = 0).
-  int64_t B_static = B;
-  int64_t dyn_lo = B, dyn_hi = B;
+  int B_static = Bn;
+  int dyn_lo = Bn, dyn_hi = Bn;
   unsigned int* dyn_ctr = nullptr;
   if (dyn_tail && !det_slots && !encode_only) {
-    const int64_t per_wave = B / nwaves;
+    const int per_wave = Bn / nwaves;
     if (per_wave >= 8) {
-      int64_t fixed = per_wave - (per_wave * ROW_DYN_NUM) / ROW_DYN_DEN;
+      int fixed = per_wave - (per_wave * ROW_DYN_NUM) / ROW_DYN_DEN;
       if (fixed < 2) fixed = 2;
       B_static = fixed * nwaves;
       const int r = (int)(wave & (kDaccRep - 1));
-      const int64_t each = (B - B_static + kDaccRep - 1) / kDaccRep;
+      const int each = (Bn - B_static + kDaccRep - 1) / kDaccRep;
       dyn_lo = B_static + r * each;
-      dyn_hi = dyn_lo + each < B ? dyn_lo + each : B;
-      if (dyn_lo > B) dyn_lo = B;
+      dyn_hi = dyn_lo + each < Bn ? dyn_lo + each : Bn;
+      if (dyn_lo > Bn) dyn_lo = Bn;
       dyn_ctr = reinterpret_cast<unsigned int*>(dacc + (size_t)r * (kDaccHead + KP) + kDaccDynSlot);
     }
   }
   // the row after `cur` in this wave's sequence when it is a fixed one, else -1 (ask the counter)
-  auto fixed_next = [&](int64_t cur) -> int64_t {
-    if (cur >= B) return B;
+  auto fixed_next = [&](int cur) -> int {
+    if (cur >= Bn) return Bn;
     if (cur + nwaves < B_static) return cur + nwaves;
-    return dyn_ctr ? (int64_t)-1 : B;
+    return dyn_ctr ? -1 : Bn;
   };
-  auto take_dynamic = [&]() -> int64_t {          // (wave-uniform; the wait for the atomic is here)
+  auto take_dynamic = [&]() -> int {          // (wave-uniform; the wait for the atomic is here)
     unsigned int k = 0;
     if (lane == 0) k = atomicAdd(dyn_ctr, 1u);
     k = (unsigned int)__builtin_amdgcn_readfirstlane((int)k);
-    const int64_t row = dyn_lo + (int64_t)k;
-    return row < dyn_hi ? row : B;
+    const int row = dyn_lo + (int)k;
+    return row < dyn_hi ? row : Bn;
   };
 
-  // Software pipeline across rows: the pointers of the row after next and the first
-  // two 64-entry chunks of the next row are in flight while a row is processed,
-  // so the row_ptr -> col/val dependent latency is off the per-row critical path.
+  // The counter as a one-word buffer, so that the ask can be issued by every row on every path: a lane that is
+  // not lane 0, and every lane of a row that has no ask to make, addresses the word BEHIND the counter, which the
+  // address unit's range check drops (no memory operation; it returns 0).  The number of vector-memory operations
+  // of a row's issue point then does not depend on the path (issue_next below).
+  const __amdgpu_buffer_rsrc_t dyn_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+      dyn_ctr ? dyn_ctr : reinterpret_cast<unsigned int*>(dacc), 0, dyn_ctr ? 4 : 0, 0x00020000);
+
+  // Software pipeline across rows: while a row is processed, the first two 64-entry chunks of the next row and
+  // the pointers of the row after next are in flight, so the row_ptr -> col/val dependent latency is off the
+  // per-row critical path.
+  // WHERE they are issued (issue_next): behind the row's LAST gathers, before those are waited for.  Vector-memory
+  // operations return in issue order -- a counted s_waitcnt vmcnt(N) relies on it -- so a load in front of a
+  // gather is waited for by the first wait on that gather: issued at the top of the row (as until round 5), the
+  // entry words (HBM) and the counter's atomic stood in front of the row's first A' group.  Behind the last
+  // gathers they are younger than every gather of the row and have its arithmetic tail (dot folds, log, rcp,
+  // back-substitution, cross-group sums, stores) to land; they are first needed by the next row.
+  // row_ptr and row_scale are read-only for the kernel's lifetime: read as constant memory, a load from a
+  // wave-uniform address is a scalar load whatever the kernel stores elsewhere
+  typedef const __attribute__((address_space(4))) int32_t* RowPtr;
+  typedef const __attribute__((address_space(4))) float* RowScale;
+  const RowPtr rptr = (RowPtr)row_ptr;
+  const RowScale rscale = (RowScale)row_scale;
   int start = 0, end = 0, pc0 = 0, pc1 = 0, nstart = 0, nend = 0;
   float xi = 1.f, px0 = 0.f, px1 = 0.f, nxi = 1.f;
-  int64_t b = wave < B_static ? wave : B;
-  int64_t bn = fixed_next(b);
+  int b = wave < B_static ? wave : Bn;
+  int bn = fixed_next(b);
   if (bn < 0) bn = take_dynamic();
-  int64_t bnn = fixed_next(bn);
+  int bnn = fixed_next(bn);
   if (bnn < 0) bnn = take_dynamic();
-  if (b < B) {
-    start = row_ptr[b];
-    end = row_ptr[b + 1];
-    xi = row_scale ? row_scale[b] : 1.f;
-    const int f0 = min(end - start, 64);
-    const int i0 = start + lane, i1 = start + f0 + lane;
-    load_entry<PACKED, true>(col, val, ent, i0, lane < f0, pc0, px0);
-    load_entry<PACKED, true>(col, val, ent, i1, i1 < end, pc1, px1);
+  if (b < Bn) {
+    start = rptr[b];
+    end = rptr[b + 1];
+    xi = row_scale ? rscale[b] : 1.f;
+    const EntryRow<PACKED> er = entry_row<PACKED>(col, val, ent, start, end - start);
+    load_entry<PACKED, true>(er, lane, pc0, px0);
+    load_entry<PACKED, true>(er, lane + 64, pc1, px1);
   }
-  if (bn < B) {
-    nstart = row_ptr[bn];
-    nend = row_ptr[bn + 1];
-    nxi = row_scale ? row_scale[bn] : 1.f;
+  if (bn < Bn) {
+    nstart = rptr[bn];
+    nend = rptr[bn + 1];
+    nxi = row_scale ? rscale[bn] : 1.f;
   }
-  while (b < B) {
+  while (b < Bn) {
     const int n = end - start;
-    // prefetch: chunks of the next row, pointers of the one after
     int qc0 = 0, qc1 = 0, nnstart = 0, nnend = 0;
     float qx0 = 0.f, qx1 = 0.f, nnxi = 1.f;
-    if (bn < B) {
-      const int f0 = min(nend - nstart, 64);
-      const int j0 = nstart + lane, j1 = nstart + f0 + lane;
-      load_entry<PACKED, true>(col, val, ent, j0, lane < f0, qc0, qx0);
-      load_entry<PACKED, true>(col, val, ent, j1, j1 < nend, qc1, qx1);
-    }
-    if (bnn < B) {
-      nnstart = row_ptr[bnn];
-      nnend = row_ptr[bnn + 1];
-      nnxi = row_scale ? row_scale[bnn] : 1.f;
-    }
-    // the row three ahead: a fixed one, or a counter's next (asked for now, looked at when this row is done)
-    int64_t bnnn = fixed_next(bnn);
-    unsigned int dyn_k = 0;
+    // the row three ahead: a fixed one, or a counter's next (asked for at the issue point, looked at when this
+    // row is done)
+    int bnnn = fixed_next(bnn);
     const bool dyn_ask = bnnn < 0;                  // wave-uniform
-    if (dyn_ask && lane == 0) dyn_k = atomicAdd(dyn_ctr, 1u);
+    unsigned int dyn_k = 0;
+    // The row's issue point, run ONCE on every path through the row: the counter's ask, the two chunks of the
+    // next row (whose pointers came a row ago; a wave's last rows load nothing) and the pointers of the
+    // row after next (scalar loads).  Nothing here stands under a lane predicate.
+    auto issue_next = [&]() {
+      issue_fence(PACKED ? (const void*)ent : (const void*)col, val, row_ptr);
+      dyn_k = (unsigned int)__builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(1, dyn_rsrc, (dyn_ask && lane == 0) ? 0 : 4,
+                                                                       0, 0);
+      const EntryRow<PACKED> er = entry_row<PACKED>(col, val, ent, nstart, nend - nstart);
+      load_entry<PACKED, true>(er, lane, qc0, qx0);
+      load_entry<PACKED, true>(er, lane + 64, qc1, qx1);
+      if (bnn < Bn) {
+        nnstart = rptr[bnn];
+        nnend = rptr[bnn + 1];
+        nnxi = row_scale ? rscale[bnn] : 1.f;
+      }
+      issue_fence(PACKED ? (const void*)ent : (const void*)col, val, row_ptr);
+    };
+    // K = 64 has no register for it (a chunk's V' rows alone are 64): its issue point stays at the top of the row
+    constexpr bool BEHIND = KP <= 32;
+    if constexpr (!BEHIND) issue_next();
     float4 zacc = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 gz = make_float4(0.f, 0.f, 0.f, 0.f);
     float llrow = 0.f;
@@ -420,50 +480,48 @@ __global__ __launch_bounds__(BT, BT == 256 ? ROW_WAVES_PER_SIMD : 4) void row_pa
       // ---- short row: col/val stay in registers for both sweeps ----------
       int c0, c1;
       float x0, x1;
-      unpack_entry<PACKED>(pc0, px0, c0, x0);
-      unpack_entry<PACKED>(pc1, px1, c1, x1);
-      const int n0 = min(n, 64), n1 = n - 64;
-      // ROW_V_AHEAD (K <= 32; at K = 64 a chunk's V' rows are 64 registers): 1 = the first chunk's V' gathers
-      // are issued before sweep 1, 3 = between sweep 1 and its cross-group sum, 2 = not ahead, but a chunk's
-      // sweep 2 issues all of its gathers before its first dot product; 0 = group by group (the round-3 form)
-      constexpr int VAHEAD = KP <= 32 ? ROW_V_AHEAD : 0;
-      float4 vv0[VAHEAD ? LPN : 1];
-      if constexpr (VAHEAD == 1) {
-        if (!encode_only) cx.s2_load(c0, n0, vv0);
-      }
+      unpack_entry<PACKED>(pc0, px0, lane < n, c0, x0);
+      unpack_entry<PACKED>(pc1, px1, lane + 64 < n, c1, x1);
+      int n0 = min(n, 64);
+      const int n1 = n - 64;
       if (mode != 2) {
         cx.sweep1(c0, x0, n0, zacc);
         if (n1 > 0) cx.sweep1(c1, x1, n1, zacc);
-        if constexpr (VAHEAD == 3) {
-          if (!encode_only) cx.s2_load(c0, n0, vv0);
-        }
         zacc = across_groups_sum4<LPN>(zacc);
         zacc.x *= xi; zacc.y *= xi; zacc.z *= xi; zacc.w *= xi;
+        // (stored here, not in the row epilogue: profiles/r06_stream_issue_ab.txt)
         if (grp == 0) reinterpret_cast<float4*>(z)[(size_t)b * LPN + sub] = zacc;
       } else {
         zacc = gather4<LPN>(z, (int)b, sub);
       }
-      if (!encode_only) {
-      if constexpr (VAHEAD != 0) {
-        if constexpr (VAHEAD == 2) cx.s2_load(c0, n0, vv0);
-        if constexpr (VAHEAD == 3) {
-          if (mode == 2) cx.s2_load(c0, n0, vv0);
-        }
-        cx.sweep2_loaded(c0, x0, n0, zacc, gz, llrow, nnf_acc, vv0);
-        if (n1 > 0) {
-          float4 vv1[LPN];
-          cx.s2_load(c1, n1, vv1);
-          cx.sweep2_loaded(c1, x1, n1, zacc, gz, llrow, nnf_acc, vv1);
-        }
+      if (encode_only) {
+        if constexpr (BEHIND) issue_next();        // behind the last sweep-1 group
       } else {
-        cx.sweep2(c0, x0, n0, zacc, gz, llrow, nnf_acc);
-        if (n1 > 0) cx.sweep2(c1, x1, n1, zacc, gz, llrow, nnf_acc);
-      }
+        // The first of two chunks, then the row's last chunk with the issue point behind its gathers.
+        // K <= 32: a chunk's sweep 2 asks for all of its V' rows before its first dot product (s2_load; asking for
+        // them ahead of sweep 1 or of its cross-group sum measured slower: profiles/r05_row_v_ahead_ab.txt); at
+        // K = 64 a chunk's V' rows are 64 registers, and it gathers group by group.
+        if constexpr (KP <= 32) {
+          float4 vv[LPN];
+          if (n1 > 0) {
+            cx.s2_load(c0, n0, vv);
+            cx.sweep2_loaded(c0, x0, n0, zacc, gz, llrow, nnf_acc, vv);
+            c0 = c1; x0 = x1; n0 = n1;
+          }
+          cx.s2_load(c0, n0, vv);
+          issue_next();
+          cx.sweep2_loaded(c0, x0, n0, zacc, gz, llrow, nnf_acc, vv);
+        } else {
+          // (K = 64: group by group, the issue point was at the top of the row)
+          cx.sweep2(c0, x0, n0, zacc, gz, llrow, nnf_acc, [] {});
+          if (n1 > 0) cx.sweep2(c1, x1, n1, zacc, gz, llrow, nnf_acc, [] {});
+        }
       }
     } else {
       // ---- long row: stream the row twice (second read is L2 served) -----
-      // Chunks 0 and 1 came with the row's prefetch; chunk i+2 is fetched while chunk i is
+      // Chunks 0 and 1 were loaded at the previous row's issue point; chunk i+2 is fetched while chunk i is
       // processed, so no chunk waits for its own col/val (14 chunks a row on C4).
+      const EntryRow<PACKED> er = entry_row<PACKED>(col, val, ent, start, n);
       if (mode != 2) {
         int ra = pc0, ra1 = pc1;
         float rb = px0, rb1 = px1;
@@ -471,10 +529,10 @@ __global__ __launch_bounds__(BT, BT == 256 ? ROW_WAVES_PER_SIMD : 4) void row_pa
           const int i2 = base + 128 + lane;
           int ra2;
           float rb2;
-          load_entry<PACKED, false>(col, val, ent, i2, i2 < end, ra2, rb2);
+          load_entry<PACKED, false>(er, i2 - start, ra2, rb2);
           int c;
           float x;
-          unpack_entry<PACKED>(ra, rb, c, x);
+          unpack_entry<PACKED>(ra, rb, base + lane < end, c, x);
           cx.sweep1(c, x, min(64, end - base), zacc);
           ra = ra1; rb = rb1; ra1 = ra2; rb1 = rb2;
         }
@@ -484,31 +542,36 @@ __global__ __launch_bounds__(BT, BT == 256 ? ROW_WAVES_PER_SIMD : 4) void row_pa
       } else {
         zacc = gather4<LPN>(z, (int)b, sub);
       }
-      if (!encode_only) {
+      if (encode_only) {
+        if constexpr (BEHIND) issue_next();        // behind the last sweep-1 group
+      } else {
         int ra = pc0, ra1 = pc1;
         float rb = px0, rb1 = px1;
         for (int base = start; base < end; base += 64) {
           const int i2 = base + 128 + lane;
           int ra2;
           float rb2;
-          load_entry<PACKED, false>(col, val, ent, i2, i2 < end, ra2, rb2);
+          load_entry<PACKED, false>(er, i2 - start, ra2, rb2);
           int c;
           float x;
-          unpack_entry<PACKED>(ra, rb, c, x);
-          cx.sweep2(c, x, min(64, end - base), zacc, gz, llrow, nnf_acc);
+          unpack_entry<PACKED>(ra, rb, base + lane < end, c, x);
+          // (the row's last chunk, K <= 32, carries the issue point behind its last group's gathers)
+          if (BEHIND && base + 64 >= end) cx.sweep2(c, x, end - base, zacc, gz, llrow, nnf_acc, issue_next);
+          else cx.sweep2(c, x, min(64, end - base), zacc, gz, llrow, nnf_acc, [] {});
           ra = ra1; rb = rb1; ra1 = ra2; rb1 = rb2;
         }
       }
     }
     // rotate the pipeline registers
     const float xi_cur = xi;
-    const int64_t b_cur = b;
+    const int b_cur = b;
     start = nstart; end = nend; xi = nxi;
     pc0 = qc0; px0 = qx0; pc1 = qc1; px1 = qx1;
     nstart = nnstart; nend = nnend; nxi = nnxi;
-    if (dyn_ask) {
-      const int64_t row = dyn_lo + (int64_t)(unsigned int)__builtin_amdgcn_readfirstlane((int)dyn_k);
-      bnnn = row < dyn_hi ? row : B;
+    {
+      // (read on every path: an answer left unread would stay "in flight" for the compiler's wait counting)
+      const int row = dyn_lo + (int)(unsigned int)__builtin_amdgcn_readfirstlane((int)dyn_k);
+      if (dyn_ask) bnnn = row < dyn_hi ? row : Bn;
     }
     b = bn; bn = bnn; bnn = bnnn;
     if (encode_only) continue;
