@@ -23,6 +23,15 @@
 // flight per wave; rows of <= 128 entries keep col/val in registers for both
 // sweeps.
 //
+// Short rows at K <= 32: only a row's LAST chunk can be partly filled, so the
+// chunk in front of it is straight-line code over all LPN gather instructions,
+// and the last chunk is dispatched ONCE per sweep, by a wave-uniform switch, to
+// the arm for the T = ceil(entries / NPI) instructions that carry entries: T
+// gathers, dot products and back-substitutions, no per-group guard and no padded
+// instruction (RowCtx::sweep1_last / sweep2_last; DESIGN.md section 4 and
+// profiles/r07_row_dispatch_ab.txt).  Long rows (> 128 entries) and K = 64 keep
+// the guarded groups of four (RowCtx::sweep1 / sweep2).
+//
 // Stream loads: the entry words of the next row, the row pointers of the one
 // after it and the dynamic tail's counter are asked for at ONE point of a row,
 // behind its last gathers (issue_next in the row loop: why, and what it
@@ -163,6 +172,7 @@ struct RowCtx {
 #pragma unroll
     for (int j = 0; j < CNT; ++j) zacc = fma4(xv[j], a[j], zacc);
   }
+  // (a chunk of nchunk entries under the per-group guard: long rows, and every row at K = 64)
   __device__ __forceinline__ void sweep1(int c, float x, int nchunk, float4& zacc) const {
 #pragma unroll
     for (int g0 = 0; g0 < LPN; g0 += GRP) {
@@ -170,7 +180,8 @@ struct RowCtx {
     }
   }
 
-  // sweep-2 pieces of one group of GRP gather instructions of which CNT carry entries
+  // sweep-2 pieces of one group of GRP gather instructions of which CNT carry entries (an arm, below, passes its
+  // whole count with g0 = 0)
   template <int CNT>
   __device__ __forceinline__ void s2_issue(int c, int g0, float4 (&vv)[LPN]) const {
 #pragma unroll
@@ -199,45 +210,79 @@ struct RowCtx {
     }
   }
 
-  // The V' gathers of one chunk, ISSUED and not waited for (short rows at K <= 32: a chunk asks for all of its
-  // groups at once instead of group by group, and the row loop puts its issue point between this and the dot
-  // products)
-  __device__ __forceinline__ void s2_load(int c, int nchunk, float4 (&vv)[LPN]) const {
+  // ---- short rows at K <= 32: a chunk by the number T of its gather instructions that carry entries --------------
+  // Only a row's LAST chunk can be partly filled; the chunk in front of it is T = LPN.  An arm is straight-line
+  // code for one T: exactly T gathers, dot products and back-substitutions, no guard and no padded instruction in
+  // it (the lanes behind the row's end in instruction T - 1 are still dropped by the range check).  The row loop
+  // picks the arm ONCE per sweep with a wave-uniform switch (sweep1_last / sweep2_last).
+
+  // sweep 1 of a chunk of T gather instructions, written in groups of GRP as everywhere.  (With no guard between
+  // the groups the compiler asks for a later group's rows ahead of the first group's fma where it has the registers:
+  // all eight of a full chunk at K = 32.  Holding it to four in flight with a scheduling barrier measured the same.)
+  template <int T>
+  __device__ __forceinline__ void s1_arm(int c, float x, float4& zacc) const {
+    constexpr int WHOLE = T / GRP * GRP;
 #pragma unroll
-    for (int g0 = 0; g0 < LPN; g0 += GRP) {
-      if (g0 * NPI < nchunk) {
-#pragma unroll
-        for (int j = 0; j < GRP; ++j) {
-          const int d = bperm_i<BPI>(bp_grp, (g0 + j) * NPI, c);
-          vv[g0 + j] = gather4<LPN>(Vp, d, sub);
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < GRP; ++j) vv[g0 + j] = make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    }
+    for (int g0 = 0; g0 < WHOLE; g0 += GRP) s1_group<GRP>(c, x, g0, zacc);
+    if constexpr (T > WHOLE) s1_group<T - WHOLE>(c, x, WHOLE, zacc);
   }
-  // sweep 2 of a chunk whose V' rows were asked for by s2_load
+  // sweep 2 of a chunk of T gather instructions: the chunk asks for all of its V' rows before its first dot
+  // product (asking for them ahead of sweep 1 or of its cross-group sum measured slower:
+  // profiles/r05_row_v_ahead_ab.txt); `behind` runs behind the gathers, before they are waited for (the row
+  // loop's issue_next in a row's last chunk).  Every arm consumes all of its gathers, so the arms of a switch meet
+  // with what `behind` issued in flight and nothing else, and the waits inside an arm count T - 1 ... 0 on top of it.
   // (one fold per dot product: a transpose-reduce of the chunk's eight at K = 32 and the packed multiply / fma
   //  forms both measured no faster, profiles/r05_row_valu_ab.txt)
-  __device__ __forceinline__ void sweep2_loaded(int c, float x, int nchunk, const float4& z, float4& gz, float& ll,
-                                                double& nnf, const float4 (&vv)[LPN]) const {
+  template <int T, class Hook>
+  __device__ __forceinline__ void s2_arm(int c, float x, int nchunk, const float4& z, float4& gz, float& ll,
+                                         double& nnf, Hook&& behind) const {
+    float4 vv[LPN];
     float rmine = 0.f;
+    s2_issue<T>(c, 0, vv);
+    behind();
+    if constexpr (T > 0) {
 #pragma unroll
-    for (int g0 = 0; g0 < LPN; g0 += GRP) {
-      if (g0 * NPI < nchunk) {
-#pragma unroll
-        for (int j = 0; j < GRP; ++j) {
-          const float dot = group_sum<LPN>(dot4(z, vv[g0 + j]));
-          if (sub == g0 + j) rmine = dot;
-        }
+      for (int j = 0; j < T; ++j) {
+        const float dot = group_sum<LPN>(dot4(z, vv[j]));
+        if (sub == j) rmine = dot;
       }
+      s2_cells<T>(c, x, nchunk, rmine, vv, gz, ll, nnf);
     }
-    s2_cells(c, x, nchunk, rmine, vv, gz, ll, nnf);
+  }
+  // f(integral constant T) for the wave-uniform t in 0 ... LPN
+  template <class F>
+  __device__ __forceinline__ static void by_count(int t, F&& f) {
+    static_assert(LPN <= 8, "the arms are written out up to eight gather instructions per chunk");
+#define SPMF_ROW_ARM(T_)                                            \
+  case T_:                                                          \
+    if constexpr (LPN >= T_) f(std::integral_constant<int, T_>{});  \
+    break;
+    switch (t) {
+      SPMF_ROW_ARM(1) SPMF_ROW_ARM(2) SPMF_ROW_ARM(3) SPMF_ROW_ARM(4)
+      SPMF_ROW_ARM(5) SPMF_ROW_ARM(6) SPMF_ROW_ARM(7) SPMF_ROW_ARM(8)
+      default: f(std::integral_constant<int, 0>{}); break;   // an empty row
+    }
+#undef SPMF_ROW_ARM
+  }
+  // the number of gather instructions that carry entries of a chunk of n (wave-uniform)
+  __device__ __forceinline__ static int count_of(int n) { return (int)((unsigned)(n + NPI - 1) / (unsigned)NPI); }
+  __device__ __forceinline__ void sweep1_last(int c, float x, int nlast, float4& zacc) const {
+    by_count(count_of(nlast), [&](auto t) __attribute__((always_inline)) {
+      constexpr int T = decltype(t)::value;
+      if constexpr (T > 0) s1_arm<T>(c, x, zacc);
+    });
+  }
+  template <class Hook>
+  __device__ __forceinline__ void sweep2_last(int c, float x, int nlast, const float4& z, float4& gz, float& ll,
+                                              double& nnf, Hook&& behind) const {
+    by_count(count_of(nlast), [&](auto t) __attribute__((always_inline)) {
+      s2_arm<decltype(t)::value>(c, x, nlast, z, gz, ll, nnf, behind);
+    });
   }
 
-  // rates, log-likelihood and gz partial over one chunk, group by group; `behind_last` runs behind the gathers of
-  // the chunk's last group, before they are waited for (the row loop's issue_next in a row's last chunk)
+  // rates, log-likelihood and gz partial over one chunk, group by group under the per-group guard (long rows, and
+  // every row at K = 64); `behind_last` runs behind the gathers of the chunk's last group, before they are waited
+  // for (the row loop's issue_next in a long row's last chunk)
   template <class Hook>
   __device__ __forceinline__ void sweep2(int c, float x, int nchunk, const float4& z, float4& gz, float& ll,
                                          double& nnf, Hook&& behind_last) const {
@@ -253,7 +298,9 @@ struct RowCtx {
     }
     s2_cells(c, x, nchunk, rmine, vv, gz, ll, nnf);
   }
-  // the per-cell part of sweep 2 (one entry per lane) and the gz partial
+  // the per-cell part of sweep 2 (one entry per lane) and the gz partial: over the CNT gather instructions of an
+  // arm, or (CNT < 0, K = 64) group by group under the per-group guard
+  template <int CNT = -1>
   __device__ __forceinline__ void s2_cells(int c, float x, int nchunk, float rmine, const float4 (&vv)[LPN],
                                            float4& gz, float& ll, double& nnf) const {
     // one entry per lane: lane (grp,sub) owns slot sub*NPI+grp
@@ -294,9 +341,13 @@ struct RowCtx {
         }
       }
     }
+    if constexpr (CNT >= 0) {
+      s2_back<CNT>(cc, 0, vv, gz);
+    } else {
 #pragma unroll
-    for (int g0 = 0; g0 < LPN; g0 += GRP) {
-      if (g0 * NPI < nchunk) s2_back<GRP>(cc, g0, vv, gz);
+      for (int g0 = 0; g0 < LPN; g0 += GRP) {
+        if (g0 * NPI < nchunk) s2_back<GRP>(cc, g0, vv, gz);
+      }
     }
   }
 };
@@ -305,11 +356,13 @@ struct RowCtx {
 
 // BT: threads per workgroup.  256: phi from global memory.  512 / 1024: phi staged in LDS
 // (4*D bytes of dynamic LDS: two workgroups per CU up to D = 20 480, one up to 40 960),
-// four waves per SIMD either way.
+// four waves per SIMD either way.  The 256-thread form is left to the compiler, except at K = 32, where it is held
+// to four waves too: those five kernels sit at 128 - 134 registers unbounded, three waves for a handful of registers
+// (all five fit 128 without scratch).
 // Launch contract: blockDim.x == BT (the wave number is computed from BT), and B < 2^31 -- row numbers are 32-bit
 // scalars inside, although the argument is int64_t (the host admits B * KP * 4 < 4 GiB only: api.hip).
 template <int KP, int LIK, int BT = 256, int PACKED = 0>
-__global__ __launch_bounds__(BT, BT == 256 ? ROW_WAVES_PER_SIMD : 4) void row_pass_kernel(
+__global__ __launch_bounds__(BT, BT == 256 && KP != 32 ? ROW_WAVES_PER_SIMD : 4) void row_pass_kernel(
     int64_t B, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
     const float* __restrict__ val, const float* __restrict__ row_scale,
     const float* __restrict__ Ap, const float* __restrict__ Vp, const float* __restrict__ phi,
@@ -456,7 +509,8 @@ __global__ __launch_bounds__(BT, BT == 256 ? ROW_WAVES_PER_SIMD : 4) void row_pa
     // The row's issue point, run ONCE on every path through the row: the counter's ask, the two chunks of the
     // next row (whose pointers came a row ago; a wave's last rows load nothing) and the pointers of the
     // row after next (scalar loads).  Nothing here stands under a lane predicate.
-    auto issue_next = [&]() {
+    // (always_inline: at K <= 32 every arm of the last chunk's switch carries a copy)
+    auto issue_next = [&]() __attribute__((always_inline)) {
       issue_fence(PACKED ? (const void*)ent : (const void*)col, val, row_ptr);
       dyn_k = (unsigned int)__builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(1, dyn_rsrc, (dyn_ask && lane == 0) ? 0 : 4,
                                                                        0, 0);
@@ -482,11 +536,22 @@ __global__ __launch_bounds__(BT, BT == 256 ? ROW_WAVES_PER_SIMD : 4) void row_pa
       float x0, x1;
       unpack_entry<PACKED>(pc0, px0, lane < n, c0, x0);
       unpack_entry<PACKED>(pc1, px1, lane + 64 < n, c1, x1);
-      int n0 = min(n, 64);
+      const int n0 = min(n, 64);
       const int n1 = n - 64;
+      // K <= 32: the row is one full chunk (n1 > 0: 64 entries, straight-line code) and its LAST chunk (cl, xl,
+      // nl), the only one that can be partly filled, which each sweep dispatches once on its number of gather
+      // instructions (RowCtx::sweep1_last / sweep2_last)
+      const bool two = n1 > 0;                            // wave-uniform
+      const int cl = two ? c1 : c0, nl = two ? n1 : n0;
+      const float xl = two ? x1 : x0;
       if (mode != 2) {
-        cx.sweep1(c0, x0, n0, zacc);
-        if (n1 > 0) cx.sweep1(c1, x1, n1, zacc);
+        if constexpr (KP <= 32) {
+          if (two) cx.template s1_arm<LPN>(c0, x0, zacc);
+          cx.sweep1_last(cl, xl, nl, zacc);
+        } else {
+          cx.sweep1(c0, x0, n0, zacc);
+          if (two) cx.sweep1(c1, x1, n1, zacc);
+        }
         zacc = across_groups_sum4<LPN>(zacc);
         zacc.x *= xi; zacc.y *= xi; zacc.z *= xi; zacc.w *= xi;
         // (stored here, not in the row epilogue: profiles/r06_stream_issue_ab.txt)
@@ -498,19 +563,11 @@ __global__ __launch_bounds__(BT, BT == 256 ? ROW_WAVES_PER_SIMD : 4) void row_pa
         if constexpr (BEHIND) issue_next();        // behind the last sweep-1 group
       } else {
         // The first of two chunks, then the row's last chunk with the issue point behind its gathers.
-        // K <= 32: a chunk's sweep 2 asks for all of its V' rows before its first dot product (s2_load; asking for
-        // them ahead of sweep 1 or of its cross-group sum measured slower: profiles/r05_row_v_ahead_ab.txt); at
+        // K <= 32: a chunk's sweep 2 asks for all of its V' rows before its first dot product (s2_arm); at
         // K = 64 a chunk's V' rows are 64 registers, and it gathers group by group.
         if constexpr (KP <= 32) {
-          float4 vv[LPN];
-          if (n1 > 0) {
-            cx.s2_load(c0, n0, vv);
-            cx.sweep2_loaded(c0, x0, n0, zacc, gz, llrow, nnf_acc, vv);
-            c0 = c1; x0 = x1; n0 = n1;
-          }
-          cx.s2_load(c0, n0, vv);
-          issue_next();
-          cx.sweep2_loaded(c0, x0, n0, zacc, gz, llrow, nnf_acc, vv);
+          if (two) cx.template s2_arm<LPN>(c0, x0, 64, zacc, gz, llrow, nnf_acc, [] {});
+          cx.sweep2_last(cl, xl, nl, zacc, gz, llrow, nnf_acc, issue_next);
         } else {
           // (K = 64: group by group, the issue point was at the top of the row)
           cx.sweep2(c0, x0, n0, zacc, gz, llrow, nnf_acc, [] {});
