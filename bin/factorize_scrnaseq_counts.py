@@ -25,6 +25,10 @@ With --labels FILE.npy (one integer per cell, -1 = no group; e.g. a clustering o
   <stem>_groupmean_<P>.npy       [groups, genes] posterior predictive mean expression per group
 and, per group, the --top genes by log2 fold change against the rest (mean over the draws, with its sd and the
 share of draws beyond one doubling).  Without the flag nothing changes.
+With --gene-sets FILE.gmt (tab-separated: set name, description, member gene names, looked up in --genes):
+  <stem>_setscore_<P>.npy        [cells, sets] posterior predictive expression summed over each gene set
+  <stem>_setscore_sd_<P>.npy     [cells, sets] its standard deviation over the --set-draws posterior draws
+Without the flag nothing changes.
 """
 import argparse
 import os
@@ -53,6 +57,9 @@ def build_parser():
     p.add_argument("--labels", default=None, help="FILE.npy: a group per cell (-1: none); adds the group means "
                                                   "and the marker genes per group")
     p.add_argument("--group-draws", type=int, default=32, help="posterior draws of the group means")
+    p.add_argument("--gene-sets", default=None, help="FILE.gmt: gene sets (name, description, members per line); "
+                                                     "adds a score per cell and set with its posterior sd")
+    p.add_argument("--set-draws", type=int, default=32, help="posterior draws of the gene-set scores (>= 2)")
     return p
 
 
@@ -127,7 +134,20 @@ def main(argv=None):
     print("intercept: " + ", ".join(str(gene_names[j]) for j in top))
     if args.labels is not None:
         group_table(factor, X, np.load(args.labels), gene_names, f"{stem}_groupmean_{P}.npy", args)
+    if args.gene_sets is not None:
+        gene_set_scores(factor, X, gene_names, f"{stem}_setscore_{P}.npy", f"{stem}_setscore_sd_{P}.npy", args)
     return losses
+
+
+def gene_set_scores(factor, X, gene_names, path, sd_path, args):
+    """The gene-set scores: per cell and set the posterior predictive expression summed over the set's genes
+    and its standard deviation over the draws."""
+    from spmf_amd import sets as gene_sets
+    set_names, sets, dropped = gene_sets.read_gmt(args.gene_sets, gene_names)
+    print(f"gene sets: {len(sets)} sets, {sum(len(s) for s in sets)} members, {dropped} unknown members dropped")
+    res = factor.set_scores({factor.count_key: X}, sets, nsamples=args.set_draws, sd=True)
+    np.save(path, res["mean"].cpu().numpy())
+    np.save(sd_path, res["sd"].cpu().numpy())
 
 
 def group_table(factor, X, labels, gene_names, path, args):

@@ -701,6 +701,47 @@ int spmf_group_sums(spmf_ctx* ctx, const spmf_counts* counts, int S,
                     double* sum_out, double* nonzero_out,
                     void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- per-row sums of the predictions over column sets (added within ABI 6: two new entry points, no struct changed) ----
+ * The posterior predictive reduced over columns: a gene-set or signature score per row, with its posterior
+ * standard deviation, without a [n_rows][columns] block (csrc/sets.hip).  With m_s as for spmf_predict_columns,
+ * for every row b of the batch `counts` and every set g < n_sets, whose list is set_cols[set_ptr[g] ..
+ * set_ptr[g+1]) with the weights set_weights[..] beside it (j runs over the list: a column listed twice counts
+ * twice):
+ *   score_s(b, g)   = sum_j (double)w_j * (double)m_s(b, c_j)            per draw s
+ *   mean[b*ld + g]  = (1/S) sum_s score_s(b, g), fp64, added in draw order;
+ *   sd[b*ld + g]    = the unbiased standard deviation of score_s over the draws (fp64 Welford in draw order),
+ *                     which needs S >= 2; sd may be NULL.
+ * Both are fp64, device, row stride ld >= n_sets; columns n_sets .. ld-1 of a row are not written, so several
+ * calls may fill column ranges of one array.  All additions are fp64: w_j * m_s is formed from the two converted
+ * operands (exact), no fp32 partial sums and no atomics.  The order of the additions of a set is a function of
+ * that set's own list, S and K alone: a set's output has the same bits whatever the other sets of the call, its
+ * position among them, or how the rows are cut into calls; two calls return the same bits.  Sets may overlap;
+ * signed weights give a contrast of two signatures its own posterior sd.
+ * set_ptr: HOST array of n_sets + 1 offsets, set_ptr[0] == 0, non-decreasing; it is read during the call only.
+ * set_cols: int32, device; set_weights: fp32, device, or NULL for weight 1.  An empty set scores 0 (sd 0) in
+ * every row.  A listed column outside [0, D) reads nothing and makes its set NaN in every row.  A row with a NaN
+ * count is NaN in every non-empty set; a non-finite cell makes its set NaN for that row.
+ * params: only u, v, w, s (slots 2, 0, 1, 7) are read, each with the leading axis S.
+ * scratch: 256-byte aligned, at least spmf_sets_scratch_bytes(ctx, counts->n_rows, S, n_sets, set_ptr) bytes:
+ * the draw stage's scratch and the compacted tables of the padded list (every set in whole 64-column blocks:
+ * P = 64 * sum_g ceil(n_g / 64) columns, S * P * (KP + 1) floats and 9 P bytes) -- bound it by calling over
+ * runs of sets.  The size is 0 for bad arguments (a bad set_ptr included).
+ * SPMF_E_ARG for the draw stage's errors (S outside 1..65535, NULL params / eta / scratch, a misaligned
+ * scratch, a mixed context without column types, a struct_size mismatch), n_sets < 0, a set_ptr that is NULL
+ * (n_sets > 0), does not start at 0 or decreases, ld < n_sets, sd with S < 2; SPMF_E_UNSUPPORTED for P >= 2^31;
+ * then SPMF_E_WORKSPACE for a short scratch, naming the need; then SPMF_E_ARG for a NULL mean with work to do
+ * or a NULL set_cols with listed columns; every error returns before any launch or write.  n_sets == 0 or
+ * n_rows == 0 returns SPMF_OK without work; when every set is empty the outputs are zero-filled and the draw
+ * stage does not run.  The context's workspace is not touched.  Stream-ordered, synchronises nowhere.  K as for
+ * spmf_waic_accumulate. */
+size_t spmf_sets_scratch_bytes(const spmf_ctx* ctx, int64_t n_rows, int S, int32_t n_sets,
+                               const int64_t* set_ptr);
+int spmf_set_scores(spmf_ctx* ctx, const spmf_counts* counts, int S,
+                    const float* const params[SPMF_NVARS], const float* eta,
+                    int32_t n_sets, const int64_t* set_ptr, const int32_t* set_cols,
+                    const float* set_weights, int64_t ld, double* mean, double* sd,
+                    void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- posterior mean encoding (added within ABI 6: two new entry points, no struct changed) ----
  * The rows of the batch `counts` in the latent space: mean_out[b][k] = (1/S) sum_s z_sb[k], k < K,
  * where z_sb is the encode sweep of draw s (what spmf_encode computes from u_s, s_s), fp32, the sum in

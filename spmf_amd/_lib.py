@@ -160,6 +160,10 @@ SIGNATURES = {
     "spmf_group_sums": (C.c_int, [C.c_void_p, C.POINTER(CountsStruct), C.c_int, PtrArray, C.c_void_p,
                                   C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spmf_sets_scratch_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int, C.c_int32, C.c_void_p]),
+    "spmf_set_scores": (C.c_int, [C.c_void_p, C.POINTER(CountsStruct), C.c_int, PtrArray, C.c_void_p,
+                                  C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "spmf_embed_scratch_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int]),
     "spmf_embed_rows": (C.c_int, [C.c_void_p, C.POINTER(CountsStruct), C.c_int, PtrArray, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -1171,7 +1171,7 @@ int spmf_dense_ll(spmf_ctx* c, const spmf_counts* ct, const float* u, const floa
 
 // ---- the draw stage of the streaming calls ---------------------------------------------------
 // spmf_waic_accumulate, spmf_topk_rows, spmf_score_cells, spmf_rank_cells, spmf_predict_columns,
-// spmf_group_sums and spmf_embed_rows are one stage and a consumer each (spmf_knn, at the end of the section,
+// spmf_group_sums, spmf_set_scores and spmf_embed_rows are one stage and a consumer each (spmf_knn, at the end of the section,
 // takes rows as given and shares the scratch and launch helpers only).
 // The stage: for S draws the per-draw tables (prep) and the encoded rows z[S,B,KP] go into the caller's scratch;
 // the consumer kernel then reads z, V' and phi of every draw (kernels.h DrawTables).  The context's workspace is
@@ -1540,6 +1540,81 @@ int spmf_group_sums(spmf_ctx* c, const spmf_counts* ct, int S, const float* cons
   ga.Vc = (float*)(base + k.p.Vc); ga.phic = (float*)(base + k.p.phic); ga.ctc = (uint8_t*)(base + k.p.ctc);
   ga.part = (double*)(base + k.part);
   return launched(c, launch_groups(ga, st), "group_sums: no kernel for this K / likelihood");
+}
+
+// ---- per-row sums of the predictions over column sets (sets.hip) -------------------------------
+// Scratch of one call: the draw carve and, behind it, the compacted tables of the padded list (panel_tables), the
+// padded list itself, its weights and the sets' records.
+struct SetCarve {
+  size_t colsp, wp, srec, total;
+  PanelCarve p;
+};
+// The padded columns of the host array set_ptr[0 .. n_sets]: every set in whole 64-column blocks.  -1: set_ptr is
+// not 0 = set_ptr[0] <= set_ptr[1] <= ..; -2: the padded total is beyond the int32 column blocks of a launch.
+static int64_t set_padded_cols(int32_t n_sets, const int64_t* set_ptr) {
+  if (n_sets == 0) return 0;
+  if (!set_ptr || set_ptr[0] != 0) return -1;
+  int64_t blocks = 0;
+  for (int32_t g = 0; g < n_sets; ++g) {
+    const int64_t n = set_ptr[g + 1] - set_ptr[g];
+    if (n < 0) return -1;
+    if (n > ((int64_t)1 << 31)) return -2;
+    blocks += (n + 63) / 64;
+    if (blocks > (((int64_t)1 << 31) - 64) / 64) return -2;
+  }
+  return blocks * 64;
+}
+static SetCarve set_carve(const spmf_ctx* c, int64_t rows, int S, int32_t n_sets, int64_t padded) {
+  SetCarve k;
+  k.p = panel_tables(c, draw_carve(c, rows, S).total, S, (int)padded);
+  size_t o = k.p.total;
+  k.colsp = o; o += al((size_t)padded * sizeof(int32_t));
+  k.wp = o;    o += al((size_t)padded * sizeof(float));
+  k.srec = o;  o += al((size_t)n_sets * sizeof(int2));
+  k.total = o;
+  return k;
+}
+
+size_t spmf_sets_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S, int32_t n_sets, const int64_t* set_ptr) {
+  if (!c || n_rows < 0 || S < 1 || n_sets < 0) return 0;
+  const int64_t padded = set_padded_cols(n_sets, set_ptr);
+  if (padded < 0) return 0;
+  return set_carve(c, n_rows, S, n_sets, padded).total;
+}
+
+int spmf_set_scores(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS],
+    const float* eta, int32_t n_sets, const int64_t* set_ptr, const int32_t* set_cols, const float* set_weights,
+    int64_t ld, double* mean_out, double* sd_out, void* scratch, size_t scratch_bytes, void* stream) {
+  // (the scratch's size depends on the sets: it is checked below, behind the call's own arguments)
+  int rc = draw_check(c, "set_scores", ct, S, 1, params, eta, scratch, (size_t)-1, spmf_embed_scratch_bytes);
+  if (rc) return rc;
+  if (n_sets < 0) return fail(c, SPMF_E_ARG, "set_scores: n_sets must be >= 0");
+  if (n_sets > 0 && !set_ptr) return fail(c, SPMF_E_ARG, "set_scores: set_ptr (host, n_sets + 1) must be set");
+  const int64_t padded = set_padded_cols(n_sets, set_ptr);
+  if (padded == -1) return fail(c, SPMF_E_ARG, "set_scores: set_ptr must start at 0 and be non-decreasing");
+  if (padded < 0) return fail(c, SPMF_E_UNSUPPORTED, "set_scores: the padded list is beyond 2^31 columns");
+  if (ld < n_sets) return fail(c, SPMF_E_ARG, "set_scores: ld must be at least n_sets");
+  if (sd_out && S < 2) return fail(c, SPMF_E_ARG, "set_scores: sd_out needs S >= 2 (the deviation over the draws)");
+  const SetCarve k = set_carve(c, ct->n_rows, S, n_sets, padded);
+  if (k.total > scratch_bytes) return scratch_too_small(c, "set_scores", k.total, scratch_bytes,
+      rows_S(ct, S) + " sets=" + std::to_string(n_sets) + " padded columns=" + std::to_string((long long)padded));
+  const bool work = n_sets > 0 && ct->n_rows > 0;
+  if (work && !mean_out) return fail(c, SPMF_E_ARG, "set_scores: mean_out must be set");
+  if (work && padded > 0 && !set_cols) return fail(c, SPMF_E_ARG, "set_scores: set_cols must be set");
+  if (!work) return SPMF_OK;
+  hipStream_t st = (hipStream_t)stream;
+  SetArgs sa{};
+  sa.t = DrawTables{ct->n_rows, c->D, c->KP, S, likelihood_code(c), nullptr, nullptr, nullptr, c->ctype};
+  if (padded > 0) {   // (all sets empty: the zero fill alone)
+    rc = draw_stage(c, "set_scores", ct, S, params, eta, scratch, st, sa.t);
+    if (rc) return rc;
+  }
+  char* base = (char*)scratch;
+  sa.n_sets = n_sets; sa.set_ptr = set_ptr; sa.cols = set_cols; sa.weights = set_weights;
+  sa.padded_cols = padded; sa.ld = ld; sa.mean = mean_out; sa.sd = sd_out;
+  sa.colsp = (int32_t*)(base + k.colsp); sa.wp = (float*)(base + k.wp); sa.srec = (int2*)(base + k.srec);
+  sa.Vc = (float*)(base + k.p.Vc); sa.phic = (float*)(base + k.p.phic); sa.ctc = (uint8_t*)(base + k.p.ctc);
+  return launched(c, launch_sets(sa, st), "set_scores: no kernel for this K / likelihood");
 }
 
 // ---- posterior mean encoding of a batch (knn.hip) ---------------------------------------------

@@ -363,6 +363,34 @@ struct GroupArgs {
   double* part;                    // part_bytes
 };
 bool launch_groups(const GroupArgs& a, hipStream_t st);
+// sets.hip: per row and column set the fp64 weighted sum over the set's listed columns of the posterior
+// predictive mean m_s, reduced over the draws: mean [B][ld] (column g = set g) and, where asked for, the unbiased
+// standard deviation over the draws (S >= 2).  set_ptr: HOST, [n_sets + 1], set g lists cols[set_ptr[g] ..
+// set_ptr[g + 1]) (device; any order, repeats allowed, one outside [0, t.D) makes its set NaN) with the weights
+// beside them (device, null = 1).  The scratch pointers are api.hip's carve for padded_cols = 64 * sum_g
+// ceil(n_g / 64) columns.  false: KP / lik not built (nothing launched).
+constexpr int kSetDrawChunk = 8;         // draws per pass of set_kernel over the set's column blocks
+constexpr int kSetFillChunk = 128;       // sets whose offsets one launch of the fill kernel takes as arguments
+struct SetFill {
+  int64_t ptr[kSetFillChunk + 1];        // set_ptr of the chunk's sets
+  int32_t boff[kSetFillChunk + 1];       // their first 64-column blocks in the padded list
+};
+struct SetArgs {
+  DrawTables t;
+  int n_sets;
+  const int64_t* set_ptr;          // host
+  const int32_t* cols;             // [set_ptr[n_sets]]
+  const float* weights;            // [set_ptr[n_sets]] or null
+  int64_t padded_cols;             // 0: every set is empty (the outputs are zero-filled)
+  int32_t* colsp;                  // [padded_cols]: the padded list, -1 in a pad slot
+  float* wp;                       // [padded_cols]: the padded weights
+  int2* srec;                      // [n_sets]: (first block, columns)
+  float *Vc, *phic;                // as PanelArgs, for padded_cols columns
+  uint8_t* ctc;
+  int64_t ld;                      // row stride of mean / sd, >= n_sets
+  double *mean, *sd;               // sd may be null
+};
+bool launch_sets(const SetArgs& a, hipStream_t st);
 bool launch_col_pass(int KP, const ColArgs& a, hipStream_t st);   // true: launched, with the pack block if asked
 bool launch_col_widek(int KP, const ColArgs& a, hipStream_t st);  // KP = 128, 256 (widek.hip)
 

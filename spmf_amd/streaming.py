@@ -1,6 +1,6 @@
 """The streaming posterior queries of the model classes: ``StreamingQueries`` is the mixin that gives
 PoissonFactorization (and through it the Bernoulli and mixed classes) waic_streaming, top_k, score_cells,
-rank_cells, predict, group_means, embed, knn and neighbors.
+rank_cells, predict, group_means, set_scores, embed, knn and neighbors.
 
 Every draw-stage query is the same three pieces around its own kernel (include/spmf_hip.h, csrc/api.hip "the
 draw stage"): ``_Draws``, the checked draws and the one place a library call is spelled; a driver that walks
@@ -494,6 +494,64 @@ class StreamingQueries:
             res["p_nonzero"] = res["p_nonzero_draws"].mean(0)
         if cols is not None:
             res["columns"] = cols
+        return res
+
+    def set_scores(self, data, sets, weights=None, nsamples=32, draws=None, sd=False, max_rows=None,
+                   max_listed=None):
+        """The posterior predictive reduced over columns: per row the weighted sum over each column set of
+        m_s(b, d) -- the cell of ``predict`` for draw s, the rate on a Poisson column and sigmoid(logit) on a
+        Bernoulli one -- averaged over the draws, without a [rows, columns] block (csrc/sets.hip).  A gene-set
+        or signature score per cell, a category affinity per user, the expected row total (the set of all
+        columns); with ``sd=True`` its posterior standard deviation, which a sum of ``predict``'s per-cell
+        deviations cannot give.
+
+        ``data``, ``draws`` and ``max_rows`` as in ``predict``; the rows of all batches are concatenated.
+        ``sets``: a sequence of 1-D integer arrays (numpy / torch / lists) of columns in [0, D), in any order; a
+        column listed twice counts twice, sets may overlap, a set may be empty.  ``weights``: None (all 1) or a
+        sequence of as many float arrays, each as long as its set, finite; signed weights make a contrast of two
+        signatures one set with a posterior sd of its own.  ``sd=True`` needs two draws.
+
+        Returns device tensors {'mean': fp64 [B, G]} plus 'sd': fp64 [B, G] (unbiased, over the per-draw
+        scores) when asked for, and 'sizes': int64 [G], the length of every list.  Every sum is fp64 from the
+        first addition on (each fp32 cell and weight is converted first) and runs in an order fixed by the
+        set's own list and the number of draws: a set's column has the same bits whatever the other sets, its
+        position, ``max_rows`` or ``max_listed``.  An empty set scores 0 (sd 0); a row with a NaN count is NaN
+        in every non-empty set.  Bit-reproducible.
+
+        Memory and cost: the sets are served in runs of whole sets whose lists, each padded to whole 64-column
+        blocks, stay within ``max_listed`` columns (default: 256 MiB of compacted decoding rows at S draws; a
+        single larger set is a run of its own), and the rows in chunks of ``max_rows``.  The draw stage --
+        the tables of the S draws and the encoding of the chunk's rows -- runs once per (row chunk, run): with
+        many runs prefer a larger ``max_listed``."""
+        from . import sets as _sets
+        set_ptr, cols, wts = _sets.pack(sets, weights, self.feature_dim)
+        dr = _Draws(self, "set_scores", draws, nsamples, 2 if sd else 1, "predict")
+        G = len(set_ptr) - 1
+        sizes = np.diff(set_ptr)
+        padded = (sizes + 63) // 64 * 64
+        cap = int(max_listed) if max_listed else max(64, (256 << 20) // (dr.S * dr.KP * 4) // 64 * 64)
+        runs, g0, load = [], 0, 0           # (first set, end set, the run's own set_ptr on the host)
+        for g in range(G + 1):
+            if g == G or (g > g0 and load + int(padded[g]) > cap):
+                if g > g0:
+                    runs.append((g0, g, np.ascontiguousarray(set_ptr[g0:g + 1] - set_ptr[g0])))
+                g0, load = g, 0
+            if g < G:
+                load += int(padded[g])
+        cols = cols.to(self.device)
+        wts = wts.to(self.device) if wts is not None else None
+        names = ("mean", "sd") if sd else ("mean",)
+
+        def call(sub, ptr):
+            for a, b, run_ptr in runs:
+                first = int(set_ptr[a])
+                dr.call("spmf_set_scores", "spmf_sets_scratch_bytes", sub, b - a, run_ptr.ctypes.data,
+                        cols.data_ptr() + 4 * first, wts.data_ptr() + 4 * first if wts is not None else None, G,
+                        ptr["mean"] + 8 * a, ptr["sd"] + 8 * a if sd else None,
+                        size_args=(b - a, run_ptr.ctypes.data))
+        res = self._stream_rows(data, dr.S * dr.KP * 4, max_rows, {n: (G, torch.float64, False) for n in names},
+                                call if G else None)
+        res["sizes"] = torch.as_tensor(sizes, dtype=torch.int64, device=self.device)
         return res
 
     def embed(self, data, nsamples=32, draws=None, sd=False, max_rows=None):
