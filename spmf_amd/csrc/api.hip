@@ -12,34 +12,46 @@
 #include <string>
 
 #include "../../include/spmf_hip.h"
+#include "arena.h"
 #include "common.h"
 #include "kernels.h"
 
 using namespace spmf;
 
-struct spmf_ctx {
+// What a data pass binds inside the caller's workspace (ws_layout), in the order of the memory
+struct WsBuffers {
+  float* acc = nullptr;
+  double* dacc = nullptr;
+  double* dprep = nullptr;
+  double* fpart = nullptr;   // finish kernel: per-block prior-part sums
+  float* futau = nullptr;    //                per-block u_tau gradient sums
+  float *Ap = nullptr, *Vp = nullptr, *phi = nullptr, *dbias = nullptr;
+  float *Vb = nullptr, *bb = nullptr;   // mixed likelihood only: compacted V' rows / logit biases of the Bernoulli columns
+  float *z = nullptr, *gzs = nullptr;
+  float* gzd = nullptr;      // contexts with a dense term only
+  // log_transform: E = exp(<z_b, W_d>) is computed once and kept for the second contraction
+  // (dense.hip, estdot_kernel), in row chunks of at most est_cap_bytes; kDenseEKept only
+  float* est = nullptr;
+  int64_t est_rows = 0;      // rows per chunk of E
+  int batched = 0;           // the tables and row outputs exist per draw (S draws per launch)
+};
+
+struct spmf_ctx : WsBuffers {
   int device = 0, K = 0, D = 0, KP = 0;
   unsigned flags = 0;
   double u_tau_scale = 0.01, s_tau_scale = 1.0, decay = 0.99;  // poisson.py:59
-  // workspace carve
+  // the workspace and the batch it is bound for
   char* ws = nullptr;
   size_t ws_bytes = 0;
   int64_t ws_rows = 0;
   int ws_S = 0;
-  float* acc = nullptr;
-  double* dacc = nullptr;
-  double* dprep = nullptr;
   // deterministic mode (spmf_ctx_set_deterministic): caller-owned scratch for the row pass's per-workgroup
   // scalar slots and the column pass's per-item partial sums; null = off
   char* det_buf = nullptr;
   size_t det_bytes = 0;
-  double* fpart = nullptr;   // finish kernel: per-block prior-part sums
-  float* futau = nullptr;    //                per-block u_tau gradient sums
-  float *Ap = nullptr, *Vp = nullptr, *phi = nullptr, *z = nullptr, *gzs = nullptr, *gzd = nullptr, *dbias = nullptr;
   const uint8_t* ctype = nullptr;   // mixed likelihood: 1 = Bernoulli column (device, caller-owned)
   const int32_t* bcols = nullptr;   // mixed likelihood: ascending indices of the Bernoulli columns (optional)
   int n_bcols = 0;
-  float *Vb = nullptr, *bb = nullptr;   // compacted V' rows / logit biases of those columns
   // timing taps
   int timing = 0;
   static constexpr int kSets = 64;  // ring of event sets: no sync inside a timed loop
@@ -52,15 +64,10 @@ struct spmf_ctx {
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int Dh = 0;                     // column split of the accumulator layout (0 = none)
-  int batched = 0;                // the bound workspace holds per-draw tables (S draws per launch)
   int prior_pending = 0;          // S of the launched prior half, 0 = none
   const double* prior_parts = nullptr;
   // the library's only device allocation: a small scratch for per-block partial sums of the
   // O(D*K) surrogate kernels (fixed-order reductions instead of same-address atomics)
-  // log_transform: E = exp(<z_b, W_d>) is computed once and kept for the second contraction
-  // (dense.hip, estdot_kernel), in row chunks of at most kEstCapBytes
-  float* est = nullptr;
-  int64_t est_rows = 0;           // rows per chunk of the bound workspace
   int e_once = 1;                 // SPMF_DENSE_E_ONCE=0: recompute E in a second launch instead
   int dense3 = 1;                 // exp sums on the bf16 matrix cores with three-way split operands
                                   // (dense3.hip; Poisson log_transform at KP = 64 only);
@@ -152,8 +159,6 @@ static int padded_k(int K) {
   while (kp < K) kp <<= 1;
   return kp;
 }
-static size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static size_t var_size(const spmf_ctx* c, int i) {
   const size_t D = c->D, K = c->K;
   switch (i) {
@@ -164,9 +169,6 @@ static size_t var_size(const spmf_ctx* c, int i) {
   }
 }
 
-struct Carve {
-  size_t acc, dacc, dprep, ppart, putau, Ap, Vp, phi, dbias, Vb, bb, z, gzs, gzd, est, total;
-};
 // Small batches run all S draws in ONE launch per kernel (gridDim.y = S): the per-draw tables and
 // row outputs then exist S times.  Only for the linear Poisson decoder.  Two cases:
 //   * the S table pairs stay L2 sized (<= 3 MB): any batch up to 256 MB of row outputs -- beyond that size a
@@ -209,7 +211,7 @@ static int64_t est_chunk_rows(const spmf_ctx* c, int64_t rows) {
   return rows < cap ? rows : cap;
 }
 
-// Which dense form a context runs: the workspace carve (the E buffer) and the launch sequence of the row stage
+// Which dense form a context runs: the workspace layout (the E buffer) and the launch sequence of the row stage
 // (data_pass_impl, dense_rows) both follow this one answer.
 enum DenseForm {
   kDenseNone,       // Poisson / linear decoder: closed-form dense term, one row pass
@@ -259,31 +261,37 @@ static int pick_chunks(int nbx, int ntiles, int slots, int max_chunks) {
   return best;
 }
 
-static Carve carve(const spmf_ctx* c, int64_t rows, int S) {
-  Carve k;
-  size_t o = 0;
-  const size_t KP = c->KP, D = c->D;
-  const size_t nd = batched_draws(c, rows, S) ? (size_t)S : 1;   // per-draw copies
-  k.acc = o;   o += al((size_t)S * acc_len(c->D, c->KP) * sizeof(float));
-  k.dacc = o;  o += al((size_t)S * kDaccRep * (kDaccHead + KP) * sizeof(double));
-  k.dprep = o; o += al((size_t)S * kPrepSeg * (KP + 1) * sizeof(double));
-  const size_t fnb = (D + kFinishCols - 1) / kFinishCols;                     // workgroups of the finish kernel
-  k.ppart = o; o += al((size_t)S * fnb * 12 * sizeof(double));
-  k.putau = o; o += al((size_t)S * fnb * KP * sizeof(float));
-  k.Ap = o;    o += al(nd * D * KP * sizeof(float));
-  k.Vp = o;    o += al(nd * D * KP * sizeof(float));
-  k.phi = o;   o += al(nd * D * sizeof(float));
-  k.dbias = o; o += al(D * sizeof(float));
-  k.Vb = o;    if (c->flags & SPMF_FLAG_MIXED) o += al(D * KP * sizeof(float));
-  k.bb = o;    if (c->flags & SPMF_FLAG_MIXED) o += al(D * sizeof(float));
-  k.z = o;     o += al(nd * (size_t)rows * KP * sizeof(float));
-  k.gzs = o;   o += al(nd * (size_t)rows * KP * sizeof(float));
-  k.gzd = o;   if (c->flags & (SPMF_FLAG_LOG_TRANSFORM | SPMF_FLAG_BERNOULLI | SPMF_FLAG_MIXED)) o += al((size_t)rows * KP * sizeof(float));
-  k.est = o;
-  if (dense_form(c) == kDenseEKept)
-    o += al((size_t)((D + 31) / 32) * 32 * (size_t)est_chunk_rows(c, rows) * sizeof(float));
-  k.total = o;
-  return k;
+// The workspace of a batch of `rows` rows under S draws.  acc | dacc are contiguous: the step's first prep launch
+// zeroes them as one range.
+static void ws_layout(Arena& a, const spmf_ctx* c, int64_t rows, int S, WsBuffers& w) {
+  const size_t KP = c->KP, D = c->D, nS = S, B = rows;
+  const unsigned dense_flags = SPMF_FLAG_LOG_TRANSFORM | SPMF_FLAG_BERNOULLI | SPMF_FLAG_MIXED;
+  w.batched = batched_draws(c, rows, S) ? 1 : 0;
+  const size_t nd = w.batched ? nS : 1;   // per-draw copies
+  w.acc = a.take<float>(nS * acc_len(c->D, c->KP));
+  w.dacc = a.take<double>(nS * kDaccRep * (kDaccHead + KP));
+  w.dprep = a.take<double>(nS * kPrepSeg * (KP + 1));
+  const size_t fnb = (D + kFinishCols - 1) / kFinishCols;   // workgroups of the finish kernel
+  w.fpart = a.take<double>(nS * fnb * 12);
+  w.futau = a.take<float>(nS * fnb * KP);
+  w.Ap = a.take<float>(nd * D * KP);
+  w.Vp = a.take<float>(nd * D * KP);
+  w.phi = a.take<float>(nd * D);
+  w.dbias = a.take<float>(D);
+  const bool mixed = (c->flags & SPMF_FLAG_MIXED) != 0;
+  w.Vb = mixed ? a.take<float>(D * KP) : nullptr;
+  w.bb = mixed ? a.take<float>(D) : nullptr;
+  w.z = a.take<float>(nd * B * KP);
+  w.gzs = a.take<float>(nd * B * KP);
+  w.gzd = (c->flags & dense_flags) ? a.take<float>(B * KP) : nullptr;
+  w.est_rows = est_chunk_rows(c, rows);
+  w.est = dense_form(c) == kDenseEKept ? a.take<float>((D + 31) / 32 * 32 * (size_t)w.est_rows) : nullptr;
+}
+static size_t ws_bytes_for(const spmf_ctx* c, int64_t rows, int S) {
+  Arena a;
+  WsBuffers w;
+  ws_layout(a, c, rows, S, w);
+  return a.used;
 }
 
 extern "C" {
@@ -366,7 +374,7 @@ int spmf_ctx_set_bernoulli_columns(spmf_ctx* c, const int32_t* cols, int n) {
   return SPMF_OK;
 }
 
-// Forget the carve of the previous workspace: until the next data pass binds the new one the
+// Forget the buffers bound in the previous workspace: until the next data pass binds the new one the
 // entry points that only READ a bound workspace (spmf_prior_async, spmf_finish,
 // spmf_nonfinite_patch, spmf_acc_ptr) fail with SPMF_E_WORKSPACE / return NULL instead of
 // touching memory the caller may have freed.
@@ -389,17 +397,17 @@ static void unbind_ws(spmf_ctx* c) {
 int spmf_ctx_set_e_cap(spmf_ctx* c, size_t bytes) {
   if (!c || bytes < ((size_t)1 << 20)) return fail(c, SPMF_E_ARG, "set_e_cap: at least 1 MiB");
   c->est_cap_bytes = bytes;
-  unbind_ws(c);               // the carve changes: the next data pass re-binds (and re-checks) the workspace
+  unbind_ws(c);               // the layout changes: the next data pass re-binds (and re-checks) the workspace
   return SPMF_OK;
 }
 
 size_t spmf_workspace_bytes(const spmf_ctx* c, int64_t max_rows, int S) {
   if (!c || max_rows < 0 || S < 1) return 0;
-  size_t need = carve(c, max_rows, S).total;
+  size_t need = ws_bytes_for(c, max_rows, S);
   // (a batch of at most kSmallBatchRows rows keeps S table pairs: cover it too, so that every batch of up
   //  to max_rows rows fits the workspace this sizes)
   if (max_rows > kSmallBatchRows) {
-    const size_t small = carve(c, kSmallBatchRows, S).total;
+    const size_t small = ws_bytes_for(c, kSmallBatchRows, S);
     if (small > need) need = small;
   }
   return need;
@@ -417,32 +425,18 @@ int spmf_ctx_set_workspace(spmf_ctx* c, void* workspace, size_t bytes) {
 
 static int bind_ws(spmf_ctx* c, int64_t rows, int S) {
   if (!c->ws) return fail(c, SPMF_E_WORKSPACE, "no workspace set (spmf_ctx_set_workspace)");
-  Carve k = carve(c, rows, S);
-  if (k.total > c->ws_bytes) {
+  Arena a(c->ws, c->ws_bytes);
+  WsBuffers w;
+  ws_layout(a, c, rows, S, w);
+  if (!a.fits()) {   // (what is bound stays bound)
     char b[160];
-    snprintf(b, sizeof b, "workspace too small: need %zu bytes for rows=%lld S=%d, have %zu", k.total,
+    snprintf(b, sizeof b, "workspace too small: need %zu bytes for rows=%lld S=%d, have %zu", a.used,
         (long long)rows, S, c->ws_bytes);
     return fail(c, SPMF_E_WORKSPACE, b);
   }
-  c->acc = (float*)(c->ws + k.acc);
-  c->dacc = (double*)(c->ws + k.dacc);
-  c->dprep = (double*)(c->ws + k.dprep);
-  c->fpart = (double*)(c->ws + k.ppart);
-  c->futau = (float*)(c->ws + k.putau);
-  c->Ap = (float*)(c->ws + k.Ap);
-  c->Vp = (float*)(c->ws + k.Vp);
-  c->phi = (float*)(c->ws + k.phi);
-  c->dbias = (float*)(c->ws + k.dbias);
-  c->Vb = (float*)(c->ws + k.Vb);
-  c->bb = (float*)(c->ws + k.bb);
-  c->z = (float*)(c->ws + k.z);
-  c->gzs = (float*)(c->ws + k.gzs);
-  c->gzd = (float*)(c->ws + k.gzd);
-  c->est = dense_form(c) == kDenseEKept ? (float*)(c->ws + k.est) : nullptr;
-  c->est_rows = est_chunk_rows(c, rows);
+  static_cast<WsBuffers&>(*c) = w;
   c->ws_rows = rows;
   c->ws_S = S;
-  c->batched = batched_draws(c, rows, S) ? 1 : 0;
   return SPMF_OK;
 }
 
@@ -564,15 +558,28 @@ int spmf_counts_gvals(spmf_ctx* c, const spmf_counts* ct, const float* eta, floa
   return SPMF_OK;
 }
 
-// deterministic-mode scratch, per draw: [kDetMeta + kDetMaxBlocks * (kDaccHead + KP) doubles | n_items * det_part_len floats]
-static size_t det_slot_doubles(int KP) { return (size_t)kDetMeta + (size_t)kDetMaxBlocks * (kDaccHead + KP); }
-static size_t det_slots_bytes(int KP) { return (det_slot_doubles(KP) * sizeof(double) + 255) & ~size_t(255); }
-static size_t det_part_bytes(int KP, int64_t n_items) {
-  return ((size_t)(n_items > 0 ? n_items : 0) * det_part_len(KP) * sizeof(float) + 255) & ~size_t(255);
+// deterministic-mode scratch: per draw the row pass's slots, then the column pass's per-item partial sums.
+// Draw 0's two buffers inside the `bytes` of `buf` (null: sizes only); draw s lies s * dstride doubles = s * fstride
+// floats behind (the data pass checks all S draws against spmf_det_scratch_bytes first).
+struct DetDraw {
+  double* slots;                // [kDetMeta + kDetMaxBlocks * (kDaccHead + KP)]
+  float* part;                  // [n_items][det_part_len]
+  int64_t dstride, fstride;
+  size_t bytes;                 // of one draw
+};
+static DetDraw det_layout(void* buf, size_t bytes, int KP, int64_t n_items) {
+  Arena a(buf, bytes);
+  DetDraw d;
+  d.slots = a.take<double>((size_t)kDetMeta + (size_t)kDetMaxBlocks * (kDaccHead + KP));
+  d.part = a.take<float>((size_t)(n_items > 0 ? n_items : 0) * det_part_len(KP));
+  d.bytes = a.used;
+  d.dstride = (int64_t)(a.used / sizeof(double));
+  d.fstride = (int64_t)(a.used / sizeof(float));
+  return d;
 }
 size_t spmf_det_scratch_bytes(const spmf_ctx* c, int64_t n_items, int S) {
   if (!c || S < 1) return 0;
-  return (size_t)S * (det_slots_bytes(c->KP) + det_part_bytes(c->KP, n_items));
+  return (size_t)S * det_layout(nullptr, 0, c->KP, n_items).bytes;
 }
 int spmf_ctx_set_deterministic(spmf_ctx* c, void* scratch, size_t bytes) {
   if (!c) return SPMF_E_ARG;
@@ -587,7 +594,7 @@ int spmf_ctx_set_deterministic(spmf_ctx* c, void* scratch, size_t bytes) {
   if (c->Dh > 0) return fail(c, SPMF_E_UNSUPPORTED, "set_deterministic: not together with the column split");
   if (c->KP > 64) return fail(c, SPMF_E_UNSUPPORTED, "set_deterministic: latent dimensions up to 64 only");
   if ((uintptr_t)scratch & 255) return fail(c, SPMF_E_ARG, "set_deterministic: scratch must be 256-byte aligned");
-  if (bytes < spmf_det_scratch_bytes(c, 0, 1)) return fail(c, SPMF_E_WORKSPACE, "set_deterministic: scratch too small");
+  if (bytes < det_layout(nullptr, 0, c->KP, 0).bytes) return fail(c, SPMF_E_WORKSPACE, "set_deterministic: scratch too small");
   c->det_buf = (char*)scratch;
   c->det_bytes = bytes;
   return SPMF_OK;
@@ -839,8 +846,8 @@ static int data_pass_impl(spmf_ctx* c, const spmf_counts* ct, int S, const float
   if (!split && parts_mask != 3) return fail(c, SPMF_E_ARG, "data_pass_split needs spmf_ctx_set_column_split");
   if (parts_mask != 3 && S != 1) return fail(c, SPMF_E_UNSUPPORTED, "data_pass_split: one draw per step only");
   const bool first = parts_mask & 1, second = parts_mask & 2;
-  const size_t det_draw = det ? det_slots_bytes(KP) + det_part_bytes(KP, ct->n_items) : 0;
-  // acc | dacc (contiguous in the carve) are zeroed by the first prep launch of the step,
+  const DetDraw dd = det ? det_layout(c->det_buf, c->det_bytes, KP, ct->n_items) : DetDraw{};
+  // acc | dacc (contiguous in the workspace) are zeroed by the first prep launch of the step,
   // slice by slice in its tile blocks; dprep is written, not accumulated (prep.hip)
   if (c->timing && first) {
     c->ev_set = (c->ev_set + 1) % spmf_ctx::kSets;
@@ -856,7 +863,8 @@ static int data_pass_impl(spmf_ctx* c, const spmf_counts* ct, int S, const float
     Tables T = ws_tables(c);   // (the scalar blocks are draw s's)
     T.dacc += (size_t)s * dacc_stride;
     T.dprep += (size_t)s * kPrepSeg * (KP + 1);
-    char* det_draw_buf = det ? c->det_buf + (size_t)s * det_draw : nullptr;
+    double* det_slots = det ? dd.slots + s * dd.dstride : nullptr;
+    float* det_part = det ? dd.part + s * dd.fstride : nullptr;
     bool packed = false;
     if (first) {
       if (tm) HIPCHK(c, hipEventRecord(c->ev[0], st));
@@ -887,8 +895,8 @@ static int data_pass_impl(spmf_ctx* c, const spmf_counts* ct, int S, const float
           if (rc) return rc;
         } else {
           if (det) {
-            ra.det_slots = (double*)det_draw_buf;
-            ra.det_stride = (int64_t)(det_draw / sizeof(double));
+            ra.det_slots = det_slots;
+            ra.det_stride = dd.dstride;
           }
           launch_row_pass(KP, ra, st);
         }
@@ -904,10 +912,10 @@ static int data_pass_impl(spmf_ctx* c, const spmf_counts* ct, int S, const float
         if (!split && hf == 1) continue;
         ColArgs ca = col_args(c, ct, nbat, T, acc, L, hf);
         if (det) {
-          ca.det_slots = (const double*)det_draw_buf;
-          ca.det_stride = (int64_t)(det_draw / sizeof(double));
-          ca.det_part = (float*)(det_draw_buf + det_slots_bytes(KP));
-          ca.det_part_stride = (int64_t)(det_draw / sizeof(float));
+          ca.det_slots = det_slots;
+          ca.det_stride = dd.dstride;
+          ca.det_part = det_part;
+          ca.det_part_stride = dd.fstride;
         }
         if (hf == (split ? 1 : 0)) {
           // the fp64 scalars of the row pass are complete before this launch starts: its
@@ -924,7 +932,7 @@ static int data_pass_impl(spmf_ctx* c, const spmf_counts* ct, int S, const float
     if (det && ct->n_rows > 0 && ct->nnz > 0) {
       // the per-item partial sums, column by column in (panel, segment) order, into the zeroed accumulators
       DetReduceArgs dr{D, KP, ct->n_panels, nbat, ct->list_first, ct->item_pos, ct->item_ptr,
-          (const float*)(det_draw_buf + det_slots_bytes(KP)), (int64_t)(det_draw / sizeof(float)),
+          det_part, dd.fstride,
           acc + L.gA_off(0), acc + L.gV_off(0), acc + L.gphi_off(0), (int64_t)al_};
       launch_det_reduce(dr, st);
     }
@@ -1176,28 +1184,31 @@ int spmf_dense_ll(spmf_ctx* c, const spmf_counts* ct, const float* u, const floa
 // The stage: for S draws the per-draw tables (prep) and the encoded rows z[S,B,KP] go into the caller's scratch;
 // the consumer kernel then reads z, V' and phi of every draw (kernels.h DrawTables).  The context's workspace is
 // not used, so a step that is bound (or half way: spmf_step_begin .. spmf_step_end) keeps everything it has.
-// Scratch of a call = the draw carve + the consumer's own buffers behind it.
-// An entry is: draw_check, its own argument checks, its empty returns, draw_stage, its carve, `launched`.  What
-// two entries need alike is written once: scratch_too_small, check_column_list, panel_tables, stored_bits.
-struct DrawCarve {
-  size_t Ap, Vp, phi, dprep, dacc, z, total;
-};
-static DrawCarve draw_carve(const spmf_ctx* c, int64_t rows, int S) {
-  DrawCarve k;
-  size_t o = 0;
+// Scratch of a call = one arena (arena.h): the draw tables first, the consumer's own buffers behind them.  Each
+// call has one layout function, which takes the arena and the call's argument struct and names every buffer
+// once; its spmf_*_scratch_bytes is that function on an arena without memory.
+// An entry is: draw_check, its layout on the caller's scratch and byte count with the SPMF_E_WORKSPACE failure
+// where that does not fit (scratch_too_small), its own argument checks -- in front of the layout where it depends
+// on them --, its empty returns, draw_stage, `launched`.  What two entries need alike is written once:
+// draw_tables, stored_layout, panel_tables, check_column_list.
+static void draw_tables(Arena& a, const spmf_ctx* c, int64_t rows, int S, Tables& T) {
   const size_t KP = c->KP, D = c->D, nS = S;
-  k.Ap = o;    o += al(nS * D * KP * sizeof(float));
-  k.Vp = o;    o += al(nS * D * KP * sizeof(float));
-  k.phi = o;   o += al(nS * D * sizeof(float));
-  k.dprep = o; o += al(nS * kPrepSeg * (KP + 1) * sizeof(double));
-  k.dacc = o;  o += al((size_t)kDaccRep * (kDaccHead + KP) * sizeof(double));
-  k.z = o;     o += al(nS * (size_t)rows * KP * sizeof(float));
-  k.total = o;
-  return k;
+  T.Ap = a.take<float>(nS * D * KP);
+  T.Vp = a.take<float>(nS * D * KP);
+  T.phi = a.take<float>(nS * D);
+  T.dprep = a.take<double>(nS * kPrepSeg * (KP + 1));
+  T.dacc = a.take<double>((size_t)kDaccRep * (kDaccHead + KP));
+  T.z = T.gzs = a.take<float>(nS * (size_t)rows * KP);
+}
+static size_t draw_tables_bytes(const spmf_ctx* c, int64_t rows, int S) {
+  Arena a;
+  Tables T;
+  draw_tables(a, c, rows, S, T);
+  return a.used;
 }
 
-// The SPMF_E_WORKSPACE failure of a call `fn` whose scratch holds `have` bytes of the `need` its size function
-// returns for the shape `detail` ("rows=70 S=2").
+// The SPMF_E_WORKSPACE failure of a call `fn` whose scratch holds `have` bytes where its layout takes `need` for
+// the shape `detail` ("rows=70 S=2").
 static int scratch_too_small(spmf_ctx* c, const char* fn, size_t need, size_t have, const std::string& detail) {
   return fail(c, SPMF_E_WORKSPACE, std::string(fn) + ": scratch too small: need " + std::to_string(need) +
       " bytes for " + detail + ", have " + std::to_string(have));
@@ -1213,11 +1224,11 @@ static int launched(spmf_ctx* c, bool ok, const char* no_kernel) {
 }
 
 // What every streaming call `fn` checks before anything is launched: S in min_S..65535, the shared pointers, the
-// scratch's alignment, the column types of a mixed context, the counts, and the scratch size against
-// need(c, rows, S), the call's own spmf_*_scratch_bytes.
+// scratch's alignment, the column types of a mixed context and the counts.  Behind it the context, the counts and
+// S are fit to run the call's layout on: the scratch's size is the entry's next check, or, where the layout
+// depends on further arguments, the one behind their checks.
 static int draw_check(spmf_ctx* c, const char* fn, const spmf_counts* ct, int S, int min_S,
-    const float* const params[SPMF_NVARS], const float* eta, const void* scratch, size_t scratch_bytes,
-    size_t (*need)(const spmf_ctx*, int64_t, int)) {
+    const float* const params[SPMF_NVARS], const float* eta, const void* scratch) {
   if (!c) return SPMF_E_ARG;
   const std::string f = std::string(fn) + ": ";
   if (S < min_S || S > 65535) return fail(c, SPMF_E_ARG, f + (min_S == 2 ? "S must be in 2..65535 (the variance "
@@ -1233,41 +1244,44 @@ static int draw_check(spmf_ctx* c, const char* fn, const spmf_counts* ct, int S,
   // the encode sweep of S draws gathers z with 32-bit byte offsets per draw; the consumers' row blocks are a
   // 31-bit grid extent, a listed cell's row an int32
   if (ct->n_rows > ((int64_t)1 << 31) - 64) return fail(c, SPMF_E_ARG, f + "too many rows in one call");
-  const size_t total = need(c, ct->n_rows, S);
-  if (total > scratch_bytes) return scratch_too_small(c, fn, total, scratch_bytes, rows_S(ct, S));
   return SPMF_OK;
 }
 
-// The stage of a checked call: the tables inside its scratch (draw_carve), filled by the prep launch (S draws)
+// The stage of a checked call: the tables T inside its scratch (draw_tables), filled by the prep launch (S draws)
 // and the encode sweep, which writes z and nothing else: gzs and the scalar block are never touched.  `dt` is
 // what the consumer reads.  Nothing is launched for an empty batch.
 static int draw_stage(spmf_ctx* c, const char* fn, const spmf_counts* ct, int S,
-    const float* const params[SPMF_NVARS], const float* eta, void* scratch, hipStream_t st, DrawTables& dt) {
-  const DrawCarve k = draw_carve(c, ct->n_rows, S);
-  char* base = (char*)scratch;
-  Tables T{};
-  T.Ap = (float*)(base + k.Ap); T.Vp = (float*)(base + k.Vp); T.phi = (float*)(base + k.phi);
-  T.dprep = (double*)(base + k.dprep); T.dacc = (double*)(base + k.dacc);
-  T.z = T.gzs = (float*)(base + k.z);
+    const float* const params[SPMF_NVARS], const float* eta, const Tables& T, hipStream_t st, DrawTables& dt) {
   dt = DrawTables{ct->n_rows, c->D, c->KP, S, likelihood_code(c), T.z, T.Vp, T.phi, c->ctype};
   return encode_rows(c, fn, ct, S, &T, params[2], params[0], params[1], params[7], eta, st);
+}
+// waic_accumulate, score_cells and embed_rows, whose scratch is the draw tables alone: draw_check, and the tables
+// T laid out in the scratch with the size check
+static int draw_only_check(spmf_ctx* c, const char* fn, const spmf_counts* ct, int S, int min_S,
+    const float* const params[SPMF_NVARS], const float* eta, void* scratch, size_t scratch_bytes, Tables& T) {
+  const int rc = draw_check(c, fn, ct, S, min_S, params, eta, scratch);
+  if (rc) return rc;
+  Arena a(scratch, scratch_bytes);
+  draw_tables(a, c, ct->n_rows, S, T);
+  return a.fits() ? SPMF_OK : scratch_too_small(c, fn, a.used, scratch_bytes, rows_S(ct, S));
 }
 
 // ---- streaming WAIC (waic.hip) ------------------------------------------------------------
 size_t spmf_waic_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S) {
   if (!c || n_rows < 0 || S < 2) return 0;
-  return draw_carve(c, n_rows, S).total;
+  return draw_tables_bytes(c, n_rows, S);
 }
 
 int spmf_waic_accumulate(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS],
     const float* eta, double* sums6, double* row_out, void* scratch, size_t scratch_bytes, void* stream) {
-  int rc = draw_check(c, "waic_accumulate", ct, S, 2, params, eta, scratch, scratch_bytes, spmf_waic_scratch_bytes);
+  Tables T;
+  int rc = draw_only_check(c, "waic_accumulate", ct, S, 2, params, eta, scratch, scratch_bytes, T);
   if (rc) return rc;
   if (!sums6) return fail(c, SPMF_E_ARG, "waic_accumulate: null argument");
   if ((int64_t)(c->D + 63) / 64 > 65535) return fail(c, SPMF_E_UNSUPPORTED, "waic_accumulate: D above 65535 * 64");
   hipStream_t st = (hipStream_t)stream;
   DrawTables dt;
-  rc = draw_stage(c, "waic_accumulate", ct, S, params, eta, scratch, st, dt);
+  rc = draw_stage(c, "waic_accumulate", ct, S, params, eta, T, st, dt);
   if (rc || ct->n_rows == 0) return rc;
   WaicArgs wa{dt, ct->nnz, ct->row_ptr, ct->col_idx, ct->val, sums6, row_out};
   return launched(c, launch_waic(wa, st), "waic_accumulate: no kernel for this K / likelihood");
@@ -1296,77 +1310,74 @@ static int topk_slices(int64_t n_rows, int D, int cus) {
   const int64_t per = (cb + nsl - 1) / nsl;
   return (int)((cb + per - 1) / per);
 }
-// the bitmap of the stored cells of `rows` rows, a bit per column in 32-bit words (topk_mark_kernel)
-static size_t stored_bits_bytes(const spmf_ctx* c, int64_t rows) {
-  return (size_t)rows * ((c->D + 31) / 32) * sizeof(uint32_t);
+// Scratch of rank_cells, and the head of top-k's: the draw tables and the bitmap of the stored cells of `rows` rows,
+// a bit per column in 32-bit words (topk_mark_kernel), whatever the call's flags; `slices` of the select launch
+static size_t stored_words(const spmf_ctx* c, int64_t rows) { return (size_t)rows * ((c->D + 31) / 32); }
+static void stored_layout(Arena& a, const spmf_ctx* c, int64_t rows, int S, Tables& T, uint32_t*& stored, int& slices) {
+  draw_tables(a, c, rows, S, T);
+  stored = a.take<uint32_t>(stored_words(c, rows));
+  slices = topk_slices(rows, c->D, device_cus(c));
 }
-// Scratch of one call: the draw carve, the bitmap of the stored cells and the slices' results
-// (sized for k = kTopkMaxK: the size does not depend on the call's k or flags)
-struct TopkCarve {
-  size_t bits, bits_end, pcols, pscores, total;   // bits_end: the carve without the slices' results (rank_cells)
-  int slices;
-};
-static TopkCarve topk_carve(const spmf_ctx* c, int64_t rows, int S) {
-  TopkCarve k;
-  k.slices = topk_slices(rows, c->D, device_cus(c));
-  size_t o = draw_carve(c, rows, S).total;
-  k.bits = o;    o += al(stored_bits_bytes(c, rows));
-  k.bits_end = o;
-  const size_t part = k.slices > 1 ? (size_t)k.slices * rows * kTopkMaxK : 0;
-  k.pcols = o;   o += al(part * sizeof(int32_t));
-  k.pscores = o; o += al(part * sizeof(float));
-  k.total = o;
-  return k;
+// The bitmap of a laid-out call: zeroed on the stream when flag bit 0 (exclude stored cells) is set, else NULL.
+static int stored_bits(spmf_ctx* c, unsigned flags, int64_t rows, hipStream_t st, uint32_t*& stored) {
+  if (!(flags & 1u)) stored = nullptr;
+  else HIPCHK(c, hipMemsetAsync(stored, 0, stored_words(c, rows) * sizeof(uint32_t), st));
+  return SPMF_OK;
 }
 
-// The bitmap inside a checked call's scratch, zeroed on the stream, when flag bit 0 (exclude stored cells) is
-// set; `stored` stays NULL otherwise.
-static int stored_bits(spmf_ctx* c, unsigned flags, void* scratch, const TopkCarve& tc, int64_t rows,
-    hipStream_t st, uint32_t*& stored) {
-  if (!(flags & 1u)) return SPMF_OK;
-  stored = (uint32_t*)((char*)scratch + tc.bits);
-  HIPCHK(c, hipMemsetAsync(stored, 0, stored_bits_bytes(c, rows), st));
-  return SPMF_OK;
+// Scratch of one top-k call: the draw tables, the bitmap and the slices' results (sized for k = kTopkMaxK: the size
+// does not depend on the call's k or flags)
+static void topk_layout(Arena& a, const spmf_ctx* c, int64_t rows, int S, Tables& T, TopkArgs& ta) {
+  stored_layout(a, c, rows, S, T, ta.stored, ta.slices);
+  const size_t part = ta.slices > 1 ? (size_t)ta.slices * rows * kTopkMaxK : 0;
+  ta.part_cols = a.take<int32_t>(part);
+  ta.part_scores = a.take<float>(part);
 }
 
 size_t spmf_topk_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S) {
   if (!c || n_rows < 0 || S < 1) return 0;
-  return topk_carve(c, n_rows, S).total;
+  Arena a;
+  Tables T;
+  TopkArgs ta{};
+  topk_layout(a, c, n_rows, S, T, ta);
+  return a.used;
 }
 
 int spmf_topk_rows(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS], const float* eta,
     int k, unsigned flags, int32_t* cols_out, float* score_out, void* scratch, size_t scratch_bytes, void* stream) {
-  int rc = draw_check(c, "topk_rows", ct, S, 1, params, eta, scratch, scratch_bytes, spmf_topk_scratch_bytes);
+  int rc = draw_check(c, "topk_rows", ct, S, 1, params, eta, scratch);
   if (rc) return rc;
+  Tables T;
+  TopkArgs ta{};
+  Arena a(scratch, scratch_bytes);
+  topk_layout(a, c, ct->n_rows, S, T, ta);
+  if (!a.fits()) return scratch_too_small(c, "topk_rows", a.used, scratch_bytes, rows_S(ct, S));
   if (k < 1 || k > kTopkMaxK) return fail(c, SPMF_E_ARG, "topk_rows: k must be in 1..64");
   if (flags & ~1u) return fail(c, SPMF_E_ARG, "topk_rows: unknown flag (bit 0: exclude stored cells)");
   if (!cols_out || !score_out) return fail(c, SPMF_E_ARG, "topk_rows: null argument");
   hipStream_t st = (hipStream_t)stream;
-  TopkArgs ta{};
-  rc = draw_stage(c, "topk_rows", ct, S, params, eta, scratch, st, ta.t);
+  rc = draw_stage(c, "topk_rows", ct, S, params, eta, T, st, ta.t);
   if (rc || ct->n_rows == 0) return rc;
-  const TopkCarve tc = topk_carve(c, ct->n_rows, S);
-  char* base = (char*)scratch;
-  ta.nnz = ct->nnz; ta.k = k; ta.slices = tc.slices;
+  ta.nnz = ct->nnz; ta.k = k;
   ta.row_ptr = ct->row_ptr; ta.col = ct->col_idx;
-  rc = stored_bits(c, flags, scratch, tc, ct->n_rows, st, ta.stored);
+  rc = stored_bits(c, flags, ct->n_rows, st, ta.stored);
   if (rc) return rc;
-  ta.part_cols = (int32_t*)(base + tc.pcols); ta.part_scores = (float*)(base + tc.pscores);
   ta.cols = cols_out; ta.scores = score_out;
   return launched(c, launch_topk(ta, st), "topk_rows: no kernel for this K / likelihood");
 }
 
 // ---- posterior predictive mean / lppd of a list of cells (cells.hip) --------------------------
-// Scratch of one call: the draw carve alone.
+// Scratch of one call: the draw tables alone.
 size_t spmf_cells_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S) {
   if (!c || n_rows < 0 || S < 1) return 0;
-  return draw_carve(c, n_rows, S).total;
+  return draw_tables_bytes(c, n_rows, S);
 }
 
 int spmf_score_cells(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS], const float* eta,
     int64_t n_cells, const int32_t* cell_row, const int32_t* cell_col, const float* cell_val, float* mean_out,
     float* lppd_out, void* scratch, size_t scratch_bytes, void* stream) {
-  int rc = draw_check(c, "score_cells", ct, S, 1, params, eta, scratch, scratch_bytes, spmf_cells_scratch_bytes);
+  Tables T;
+  int rc = draw_only_check(c, "score_cells", ct, S, 1, params, eta, scratch, scratch_bytes, T);
   if (rc) return rc;
   if (n_cells < 0) return fail(c, SPMF_E_ARG, "score_cells: n_cells is negative");
   if (n_cells > 0 && (!cell_row || !cell_col || !mean_out)) return fail(c, SPMF_E_ARG, "score_cells: cell_row, "
@@ -1378,38 +1389,45 @@ int spmf_score_cells(spmf_ctx* c, const spmf_counts* ct, int S, const float* con
   if (n_cells == 0 || ct->n_rows == 0) return SPMF_OK;   // (no row: no valid cell; the Python surface lists none)
   hipStream_t st = (hipStream_t)stream;
   DrawTables dt;
-  rc = draw_stage(c, "score_cells", ct, S, params, eta, scratch, st, dt);
+  rc = draw_stage(c, "score_cells", ct, S, params, eta, T, st, dt);
   if (rc) return rc;
   CellsArgs ca{dt, n_cells, cell_row, cell_col, cell_val, mean_out, lppd_out};
   return launched(c, launch_cells(ca, st), "score_cells: no kernel for this K / likelihood");
 }
 
 // ---- rank of listed cells among their row's candidates (rank.hip) ------------------------------
-// Scratch of one call: the draw carve and the bitmap of the stored cells (the size does not depend on the flags);
-// the kernel keeps everything else in LDS and in the caller's outputs.  That is topk_carve up to the slices' results.
+// Scratch of one call: stored_layout (the size does not depend on the flags); the kernel keeps everything else in
+// LDS and in the caller's outputs.
 size_t spmf_rank_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S) {
   if (!c || n_rows < 0 || S < 1) return 0;
-  return topk_carve(c, n_rows, S).bits_end;
+  Arena a;
+  Tables T;
+  RankArgs ra{};
+  stored_layout(a, c, n_rows, S, T, ra.stored, ra.slices);
+  return a.used;
 }
 
 int spmf_rank_cells(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS], const float* eta,
     int64_t n_cells, const int32_t* cell_row, const int32_t* cell_col, unsigned flags, int32_t* rank_out,
     int32_t* cand_out, float* score_out, void* scratch, size_t scratch_bytes, void* stream) {
-  int rc = draw_check(c, "rank_cells", ct, S, 1, params, eta, scratch, scratch_bytes, spmf_rank_scratch_bytes);
+  int rc = draw_check(c, "rank_cells", ct, S, 1, params, eta, scratch);
   if (rc) return rc;
+  Tables T;
+  RankArgs ra{};
+  Arena a(scratch, scratch_bytes);
+  stored_layout(a, c, ct->n_rows, S, T, ra.stored, ra.slices);
+  if (!a.fits()) return scratch_too_small(c, "rank_cells", a.used, scratch_bytes, rows_S(ct, S));
   if (n_cells < 0) return fail(c, SPMF_E_ARG, "rank_cells: n_cells is negative");
   if (n_cells > 0 && (!cell_row || !cell_col || !rank_out || !cand_out || !score_out)) return fail(c, SPMF_E_ARG,
       "rank_cells: cell_row, cell_col, rank_out, cand_out and score_out must be set for a non-empty list");
   if (flags & ~1u) return fail(c, SPMF_E_ARG, "rank_cells: unknown flag (bit 0: exclude stored cells)");
   if (n_cells == 0 || ct->n_rows == 0) return SPMF_OK;   // (no row: no valid cell; the Python surface lists none)
   hipStream_t st = (hipStream_t)stream;
-  RankArgs ra{};
-  rc = draw_stage(c, "rank_cells", ct, S, params, eta, scratch, st, ra.t);
+  rc = draw_stage(c, "rank_cells", ct, S, params, eta, T, st, ra.t);
   if (rc) return rc;
-  const TopkCarve tc = topk_carve(c, ct->n_rows, S);
-  ra.nnz = ct->nnz; ra.slices = tc.slices;
+  ra.nnz = ct->nnz;
   ra.row_ptr = ct->row_ptr; ra.col = ct->col_idx;
-  rc = stored_bits(c, flags, scratch, tc, ct->n_rows, st, ra.stored);
+  rc = stored_bits(c, flags, ct->n_rows, st, ra.stored);
   if (rc) return rc;
   ra.n_cells = n_cells; ra.cell_row = cell_row; ra.cell_col = cell_col;
   ra.rank = rank_out; ra.cand = cand_out; ra.score = score_out;
@@ -1418,23 +1436,18 @@ int spmf_rank_cells(spmf_ctx* c, const spmf_counts* ct, int S, const float* cons
 
 // ---- predictions of a panel of columns (panel.hip) ---------------------------------------------
 // The compacted tables of a panel of C listed columns for S draws (V' rows, phi, the column types), three
-// regions from offset `o` of a scratch on; `total` is where they end.  spmf_group_sums carves them too.
-struct PanelCarve {
-  size_t Vc, phic, ctc, total;
-};
-static PanelCarve panel_tables(const spmf_ctx* c, size_t o, int S, int C) {
-  PanelCarve k;
-  const size_t KP = c->KP, nS = S, nC = C;
-  k.Vc = o;   o += al(nS * nC * KP * sizeof(float));
-  k.phic = o; o += al(nS * nC * sizeof(float));
-  k.ctc = o;  o += al(nC);
-  k.total = o;
-  return k;
+// regions, into the Vc / phic / ctc of PanelArgs, GroupArgs or SetArgs.
+static void panel_tables(Arena& a, const spmf_ctx* c, int S, size_t C, float*& Vc, float*& phic, uint8_t*& ctc) {
+  const size_t KP = c->KP, nS = S;
+  Vc = a.take<float>(nS * C * KP);
+  phic = a.take<float>(nS * C);
+  ctc = a.take<uint8_t>(C);
 }
-// Scratch of one call: the draw carve and, behind it, the compacted tables in a region of their own (the carve's
-// Ap is not reused), sized for n_cols = D: the size does not depend on the list.
-static PanelCarve panel_carve(const spmf_ctx* c, int64_t rows, int S) {
-  return panel_tables(c, draw_carve(c, rows, S).total, S, c->D);
+// Scratch of one call: the draw tables and, behind them, the compacted tables in a region of their own (the draw
+// tables' Ap is not reused), sized for n_cols = D: the size does not depend on the list.
+static void predict_layout(Arena& a, const spmf_ctx* c, int64_t rows, int S, Tables& T, PanelArgs& pa) {
+  draw_tables(a, c, rows, S, T);
+  panel_tables(a, c, S, c->D, pa.Vc, pa.phic, pa.ctc);
 }
 // The column list of a call `fn`: n_cols in 0..D, and no list is all D columns.
 static int check_column_list(spmf_ctx* c, const char* fn, int32_t n_cols, const int32_t* cols) {
@@ -1446,14 +1459,23 @@ static int check_column_list(spmf_ctx* c, const char* fn, int32_t n_cols, const 
 
 size_t spmf_predict_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S) {
   if (!c || n_rows < 0 || S < 1) return 0;
-  return panel_carve(c, n_rows, S).total;
+  Arena a;
+  Tables T;
+  PanelArgs pa{};
+  predict_layout(a, c, n_rows, S, T, pa);
+  return a.used;
 }
 
 int spmf_predict_columns(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS],
     const float* eta, int32_t n_cols, const int32_t* cols, float* mean_out, float* sd_out, float* pnz_out,
     void* scratch, size_t scratch_bytes, void* stream) {
-  int rc = draw_check(c, "predict_columns", ct, S, 1, params, eta, scratch, scratch_bytes, spmf_predict_scratch_bytes);
+  int rc = draw_check(c, "predict_columns", ct, S, 1, params, eta, scratch);
   if (rc) return rc;
+  Tables T;
+  PanelArgs pa{};
+  Arena a(scratch, scratch_bytes);
+  predict_layout(a, c, ct->n_rows, S, T, pa);
+  if (!a.fits()) return scratch_too_small(c, "predict_columns", a.used, scratch_bytes, rows_S(ct, S));
   rc = check_column_list(c, "predict_columns", n_cols, cols);
   if (rc) return rc;
   if (sd_out && S < 2) return fail(c, SPMF_E_ARG, "predict_columns: sd_out needs S >= 2 (the deviation over the "
@@ -1464,91 +1486,72 @@ int spmf_predict_columns(spmf_ctx* c, const spmf_counts* ct, int S, const float*
       "65535 * 64");
   if (!work) return SPMF_OK;
   hipStream_t st = (hipStream_t)stream;
-  PanelArgs pa{};
-  rc = draw_stage(c, "predict_columns", ct, S, params, eta, scratch, st, pa.t);
+  rc = draw_stage(c, "predict_columns", ct, S, params, eta, T, st, pa.t);
   if (rc) return rc;
-  const PanelCarve pc = panel_carve(c, ct->n_rows, S);
-  char* base = (char*)scratch;
   pa.n_cols = n_cols; pa.cols = cols;
-  pa.Vc = (float*)(base + pc.Vc); pa.phic = (float*)(base + pc.phic); pa.ctc = (uint8_t*)(base + pc.ctc);
   pa.mean = mean_out; pa.sd = sd_out; pa.pnz = pnz_out;
   return launched(c, launch_panel(pa, st), "predict_columns: no kernel for this K / likelihood");
 }
 
 // ---- per-group sums of the predictions over the rows (groups.hip) ------------------------------
-// Scratch of one call: the draw carve and, behind it, the ordering (chunk table, ranks, counts, offsets, block
+// Scratch of one call: the draw tables and, behind them, the ordering (chunk table, ranks, counts, offsets, block
 // records, the padded row order), the rows z in that order, the compacted tables of a listed panel sized for
 // n_cols (panel_tables), and the partial sums of one column range (kernels.h group_geom bounds them).
 constexpr int32_t kGroupMaxGroups = 1 << 24;
-struct GroupCarve {
-  size_t tbl, lrank, cnt, boff, fincl, rec, perm, zs, part, total;
-  PanelCarve p;
-  GroupGeom q;
-};
-static GroupCarve group_carve(const spmf_ctx* c, int64_t rows, int S, int G, int C) {
-  GroupCarve k;
-  k.q = group_geom(rows, S, G, C);
-  const size_t KP = c->KP, nS = S, nG = G, NB = (size_t)k.q.NB;
-  size_t o = draw_carve(c, rows, S).total;
-  k.tbl = o;   o += al((size_t)k.q.chunks * nG * sizeof(int32_t));
-  k.lrank = o; o += al((size_t)rows * sizeof(int32_t));
-  k.cnt = o;   o += al(nG * sizeof(int32_t));
-  k.boff = o;  o += al((nG + 1) * sizeof(int32_t));
-  k.fincl = o; o += al(nG * sizeof(int32_t));
-  k.rec = o;   o += al(NB * sizeof(int4));
-  k.perm = o;  o += al(NB * 64 * sizeof(int32_t));
-  k.zs = o;    o += al(nS * NB * 64 * KP * sizeof(float));
-  k.p = panel_tables(c, o, S, C);
-  o = k.p.total;
-  k.part = o;  o += al(k.q.part_bytes);
-  k.total = o;
-  return k;
+static void groups_layout(Arena& a, const spmf_ctx* c, int64_t rows, int S, int G, int C, Tables& T, GroupArgs& ga) {
+  const GroupGeom q = group_geom(rows, S, G, C);
+  const size_t KP = c->KP, nS = S, nG = G, NB = (size_t)q.NB;
+  draw_tables(a, c, rows, S, T);
+  ga.tbl = a.take<int32_t>((size_t)q.chunks * nG);
+  ga.lrank = a.take<int32_t>((size_t)rows);
+  ga.cnt = a.take<int32_t>(nG);
+  ga.boff = a.take<int32_t>(nG + 1);
+  ga.fincl = a.take<int32_t>(nG);
+  ga.rec = a.take<int4>(NB);
+  ga.perm = a.take<int32_t>(NB * 64);
+  ga.zs = a.take<float>(nS * NB * 64 * KP);
+  panel_tables(a, c, S, C, ga.Vc, ga.phic, ga.ctc);
+  ga.part = a.take<double>(q.part_bytes / sizeof(double));   // (whole doubles: group_geom)
 }
 
 size_t spmf_groups_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S, int32_t n_groups, int32_t n_cols) {
   if (!c || n_rows < 0 || S < 1 || n_groups < 1 || n_groups > kGroupMaxGroups || n_cols < 0 || n_cols > c->D)
     return 0;
-  return group_carve(c, n_rows, S, n_groups, n_cols).total;
+  Arena a;
+  Tables T;
+  GroupArgs ga{};
+  groups_layout(a, c, n_rows, S, n_groups, n_cols, T, ga);
+  return a.used;
 }
 
 int spmf_group_sums(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS],
     const float* eta, const int32_t* labels, int32_t n_groups, int32_t n_cols, const int32_t* cols,
     double* sum_out, double* nonzero_out, void* scratch, size_t scratch_bytes, void* stream) {
-  // (the scratch's size depends on n_groups and n_cols: it is checked below, behind the call's own arguments)
-  int rc = draw_check(c, "group_sums", ct, S, 1, params, eta, scratch, (size_t)-1, spmf_embed_scratch_bytes);
+  int rc = draw_check(c, "group_sums", ct, S, 1, params, eta, scratch);
   if (rc) return rc;
+  // (the scratch's size depends on n_groups and n_cols: it is checked behind them)
   if (n_groups < 1) return fail(c, SPMF_E_ARG, "group_sums: n_groups must be at least 1");
   rc = check_column_list(c, "group_sums", n_cols, cols);
   if (rc) return rc;
   if (n_groups > kGroupMaxGroups) return fail(c, SPMF_E_UNSUPPORTED, "group_sums: n_groups above 2^24");
-  const GroupCarve k = group_carve(c, ct->n_rows, S, n_groups, n_cols);
-  if (k.total > scratch_bytes) return scratch_too_small(c, "group_sums", k.total, scratch_bytes,
+  Tables T;
+  GroupArgs ga{};
+  Arena a(scratch, scratch_bytes);
+  groups_layout(a, c, ct->n_rows, S, n_groups, n_cols, T, ga);
+  if (!a.fits()) return scratch_too_small(c, "group_sums", a.used, scratch_bytes,
       rows_S(ct, S) + " groups=" + std::to_string(n_groups) + " cols=" + std::to_string(n_cols));
   const bool work = n_cols > 0 && ct->n_rows > 0;
   if (work && (!labels || !sum_out)) return fail(c, SPMF_E_ARG, "group_sums: labels and sum_out must be set");
   if (!work) return SPMF_OK;
   hipStream_t st = (hipStream_t)stream;
-  GroupArgs ga{};
-  rc = draw_stage(c, "group_sums", ct, S, params, eta, scratch, st, ga.t);
+  rc = draw_stage(c, "group_sums", ct, S, params, eta, T, st, ga.t);
   if (rc) return rc;
-  char* base = (char*)scratch;
   ga.n_groups = n_groups; ga.n_cols = n_cols; ga.labels = labels; ga.cols = cols;
   ga.sum = sum_out; ga.nonzero = nonzero_out;
-  ga.tbl = (int32_t*)(base + k.tbl); ga.lrank = (int32_t*)(base + k.lrank); ga.cnt = (int32_t*)(base + k.cnt);
-  ga.boff = (int32_t*)(base + k.boff); ga.fincl = (int32_t*)(base + k.fincl); ga.rec = (int4*)(base + k.rec);
-  ga.perm = (int32_t*)(base + k.perm); ga.zs = (float*)(base + k.zs);
-  ga.Vc = (float*)(base + k.p.Vc); ga.phic = (float*)(base + k.p.phic); ga.ctc = (uint8_t*)(base + k.p.ctc);
-  ga.part = (double*)(base + k.part);
   return launched(c, launch_groups(ga, st), "group_sums: no kernel for this K / likelihood");
 }
 
 // ---- per-row sums of the predictions over column sets (sets.hip) -------------------------------
-// Scratch of one call: the draw carve and, behind it, the compacted tables of the padded list (panel_tables), the
-// padded list itself, its weights and the sets' records.
-struct SetCarve {
-  size_t colsp, wp, srec, total;
-  PanelCarve p;
-};
 // The padded columns of the host array set_ptr[0 .. n_sets]: every set in whole 64-column blocks.  -1: set_ptr is
 // not 0 = set_ptr[0] <= set_ptr[1] <= ..; -2: the padded total is beyond the int32 column blocks of a launch.
 static int64_t set_padded_cols(int32_t n_sets, const int64_t* set_ptr) {
@@ -1564,30 +1567,34 @@ static int64_t set_padded_cols(int32_t n_sets, const int64_t* set_ptr) {
   }
   return blocks * 64;
 }
-static SetCarve set_carve(const spmf_ctx* c, int64_t rows, int S, int32_t n_sets, int64_t padded) {
-  SetCarve k;
-  k.p = panel_tables(c, draw_carve(c, rows, S).total, S, (int)padded);
-  size_t o = k.p.total;
-  k.colsp = o; o += al((size_t)padded * sizeof(int32_t));
-  k.wp = o;    o += al((size_t)padded * sizeof(float));
-  k.srec = o;  o += al((size_t)n_sets * sizeof(int2));
-  k.total = o;
-  return k;
+// Scratch of one call: the draw tables and, behind them, the compacted tables of the padded list (panel_tables),
+// the padded list itself, its weights and the sets' records.
+static void sets_layout(Arena& a, const spmf_ctx* c, int64_t rows, int S, int32_t n_sets, int64_t padded, Tables& T,
+    SetArgs& sa) {
+  draw_tables(a, c, rows, S, T);
+  panel_tables(a, c, S, (size_t)padded, sa.Vc, sa.phic, sa.ctc);
+  sa.colsp = a.take<int32_t>((size_t)padded);
+  sa.wp = a.take<float>((size_t)padded);
+  sa.srec = a.take<int2>((size_t)n_sets);
 }
 
 size_t spmf_sets_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S, int32_t n_sets, const int64_t* set_ptr) {
   if (!c || n_rows < 0 || S < 1 || n_sets < 0) return 0;
   const int64_t padded = set_padded_cols(n_sets, set_ptr);
   if (padded < 0) return 0;
-  return set_carve(c, n_rows, S, n_sets, padded).total;
+  Arena a;
+  Tables T;
+  SetArgs sa{};
+  sets_layout(a, c, n_rows, S, n_sets, padded, T, sa);
+  return a.used;
 }
 
 int spmf_set_scores(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS],
     const float* eta, int32_t n_sets, const int64_t* set_ptr, const int32_t* set_cols, const float* set_weights,
     int64_t ld, double* mean_out, double* sd_out, void* scratch, size_t scratch_bytes, void* stream) {
-  // (the scratch's size depends on the sets: it is checked below, behind the call's own arguments)
-  int rc = draw_check(c, "set_scores", ct, S, 1, params, eta, scratch, (size_t)-1, spmf_embed_scratch_bytes);
+  int rc = draw_check(c, "set_scores", ct, S, 1, params, eta, scratch);
   if (rc) return rc;
+  // (the scratch's size depends on the sets: it is checked behind them)
   if (n_sets < 0) return fail(c, SPMF_E_ARG, "set_scores: n_sets must be >= 0");
   if (n_sets > 0 && !set_ptr) return fail(c, SPMF_E_ARG, "set_scores: set_ptr (host, n_sets + 1) must be set");
   const int64_t padded = set_padded_cols(n_sets, set_ptr);
@@ -1595,45 +1602,45 @@ int spmf_set_scores(spmf_ctx* c, const spmf_counts* ct, int S, const float* cons
   if (padded < 0) return fail(c, SPMF_E_UNSUPPORTED, "set_scores: the padded list is beyond 2^31 columns");
   if (ld < n_sets) return fail(c, SPMF_E_ARG, "set_scores: ld must be at least n_sets");
   if (sd_out && S < 2) return fail(c, SPMF_E_ARG, "set_scores: sd_out needs S >= 2 (the deviation over the draws)");
-  const SetCarve k = set_carve(c, ct->n_rows, S, n_sets, padded);
-  if (k.total > scratch_bytes) return scratch_too_small(c, "set_scores", k.total, scratch_bytes,
+  Tables T;
+  SetArgs sa{};
+  Arena a(scratch, scratch_bytes);
+  sets_layout(a, c, ct->n_rows, S, n_sets, padded, T, sa);
+  if (!a.fits()) return scratch_too_small(c, "set_scores", a.used, scratch_bytes,
       rows_S(ct, S) + " sets=" + std::to_string(n_sets) + " padded columns=" + std::to_string((long long)padded));
   const bool work = n_sets > 0 && ct->n_rows > 0;
   if (work && !mean_out) return fail(c, SPMF_E_ARG, "set_scores: mean_out must be set");
   if (work && padded > 0 && !set_cols) return fail(c, SPMF_E_ARG, "set_scores: set_cols must be set");
   if (!work) return SPMF_OK;
   hipStream_t st = (hipStream_t)stream;
-  SetArgs sa{};
   sa.t = DrawTables{ct->n_rows, c->D, c->KP, S, likelihood_code(c), nullptr, nullptr, nullptr, c->ctype};
   if (padded > 0) {   // (all sets empty: the zero fill alone)
-    rc = draw_stage(c, "set_scores", ct, S, params, eta, scratch, st, sa.t);
+    rc = draw_stage(c, "set_scores", ct, S, params, eta, T, st, sa.t);
     if (rc) return rc;
   }
-  char* base = (char*)scratch;
   sa.n_sets = n_sets; sa.set_ptr = set_ptr; sa.cols = set_cols; sa.weights = set_weights;
   sa.padded_cols = padded; sa.ld = ld; sa.mean = mean_out; sa.sd = sd_out;
-  sa.colsp = (int32_t*)(base + k.colsp); sa.wp = (float*)(base + k.wp); sa.srec = (int2*)(base + k.srec);
-  sa.Vc = (float*)(base + k.p.Vc); sa.phic = (float*)(base + k.p.phic); sa.ctc = (uint8_t*)(base + k.p.ctc);
   return launched(c, launch_sets(sa, st), "set_scores: no kernel for this K / likelihood");
 }
 
 // ---- posterior mean encoding of a batch (knn.hip) ---------------------------------------------
-// Scratch of one call: the draw carve alone.
+// Scratch of one call: the draw tables alone.
 size_t spmf_embed_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S) {
   if (!c || n_rows < 0 || S < 1) return 0;
-  return draw_carve(c, n_rows, S).total;
+  return draw_tables_bytes(c, n_rows, S);
 }
 
 int spmf_embed_rows(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS], const float* eta,
     float* mean_out, float* sd_out, void* scratch, size_t scratch_bytes, void* stream) {
-  int rc = draw_check(c, "embed_rows", ct, S, 1, params, eta, scratch, scratch_bytes, spmf_embed_scratch_bytes);
+  Tables T;
+  int rc = draw_only_check(c, "embed_rows", ct, S, 1, params, eta, scratch, scratch_bytes, T);
   if (rc) return rc;
   if (!mean_out) return fail(c, SPMF_E_ARG, "embed_rows: null argument");
   if (sd_out && S < 2) return fail(c, SPMF_E_ARG, "embed_rows: sd_out needs S >= 2 (the deviation over the draws)");
   if (ct->n_rows == 0) return SPMF_OK;
   hipStream_t st = (hipStream_t)stream;
   DrawTables dt;
-  rc = draw_stage(c, "embed_rows", ct, S, params, eta, scratch, st, dt);
+  rc = draw_stage(c, "embed_rows", ct, S, params, eta, T, st, dt);
   if (rc) return rc;
   launch_embed(dt, c->K, mean_out, sd_out, st);   // (one kernel for every K)
   return launched(c, true, "");
@@ -1648,31 +1655,30 @@ static int knn_padded(int row_len) {
   while (kp < row_len) kp *= 2;
   return kp;
 }
-struct KnnCarve {
-  size_t rw, bias, qw, cpart, ccnt, centre, pidx, pscore, total;
-  int KP, slices;
-};
-static KnnCarve knn_carve(const spmf_ctx* c, int64_t nq, int64_t nr, int row_len) {
-  KnnCarve k;
-  k.KP = knn_padded(row_len);
-  k.slices = nr > 0 ? topk_slices(nq, (int)nr, device_cus(c)) : 1;
-  size_t o = 0;
-  k.rw = o;     o += al((size_t)nr * k.KP * sizeof(float));
-  k.bias = o;   o += al((size_t)nr * sizeof(float));
-  k.qw = o;     o += al((size_t)nq * k.KP * sizeof(float));
-  k.cpart = o;  o += al((size_t)kKnnCentreBlocks * k.KP * sizeof(float));
-  k.ccnt = o;   o += al((size_t)kKnnCentreBlocks * sizeof(int32_t));
-  k.centre = o; o += al((size_t)k.KP * sizeof(float));
-  const size_t part = k.slices > 1 ? (size_t)k.slices * nq * kTopkMaxK : 0;
-  k.pidx = o;   o += al(part * sizeof(int32_t));
-  k.pscore = o; o += al(part * sizeof(float));
-  k.total = o;
-  return k;
+// The shape (the padded row length; the reference slices of the select launch, where the queries take the place
+// of top-k's rows and the reference rows that of its columns) and the scratch of a call, all into ka
+static void knn_layout(Arena& a, const spmf_ctx* c, int64_t n_query, int64_t n_ref, int row_len, KnnArgs& ka) {
+  ka.n_query = n_query; ka.n_ref = n_ref; ka.row_len = row_len;
+  ka.KP = knn_padded(row_len);
+  ka.slices = n_ref > 0 ? topk_slices(n_query, (int)n_ref, device_cus(c)) : 1;
+  const size_t nq = n_query, nr = n_ref, KP = ka.KP;
+  ka.rw = a.take<float>(nr * KP);
+  ka.bias = a.take<float>(nr);
+  ka.qw = a.take<float>(nq * KP);
+  ka.cpart = a.take<float>(kKnnCentreBlocks * KP);
+  ka.ccnt = a.take<int32_t>(kKnnCentreBlocks);
+  ka.centre = a.take<float>(KP);
+  const size_t part = ka.slices > 1 ? (size_t)ka.slices * nq * kTopkMaxK : 0;
+  ka.part_idx = a.take<int32_t>(part);
+  ka.part_score = a.take<float>(part);
 }
 
 size_t spmf_knn_scratch_bytes(const spmf_ctx* c, int64_t n_query, int64_t n_ref, int row_len) {
   if (!c || n_query < 0 || n_ref < 0 || n_ref > 0x7fffffffLL || row_len < 1 || row_len > 256) return 0;
-  return knn_carve(c, n_query, n_ref, row_len).total;
+  Arena a;
+  KnnArgs ka{};
+  knn_layout(a, c, n_query, n_ref, row_len, ka);
+  return a.used;
 }
 
 // SPMF_KNN_TILE = 0 | 1 picks the tile function of the select kernel (knn.hip); both give the same bits
@@ -1697,20 +1703,17 @@ int spmf_knn(spmf_ctx* c, const float* q, int64_t n_query, const float* r, int64
   if ((n_query > 0 && (!q || !idx_out || !dist_out)) || (n_ref > 0 && !r)) return fail(c, SPMF_E_ARG,
       "knn: null argument");
   if ((uintptr_t)scratch & 255) return fail(c, SPMF_E_ARG, "knn: scratch must be 256-byte aligned");
-  const KnnCarve kc = knn_carve(c, n_query, n_ref, row_len);
-  if (kc.total > scratch_bytes) return scratch_too_small(c, "knn", kc.total, scratch_bytes,
+  KnnArgs ka{};
+  Arena a(scratch, scratch_bytes);
+  knn_layout(a, c, n_query, n_ref, row_len, ka);
+  if (!a.fits()) return scratch_too_small(c, "knn", a.used, scratch_bytes,
       "n_query=" + std::to_string((long long)n_query) + " n_ref=" + std::to_string((long long)n_ref) + " row_len=" +
       std::to_string(row_len));
   if (n_query == 0) return SPMF_OK;
-  char* base = (char*)scratch;
-  KnnArgs ka{};
-  ka.n_query = n_query; ka.n_ref = n_ref; ka.row_len = row_len; ka.KP = kc.KP; ka.k = k; ka.slices = kc.slices;
+  ka.k = k;
   ka.cosine = (flags & 1u) != 0; ka.tile = knn_tile(); ka.self_offset = self_offset;
   ka.q = q; ka.r = r;
-  ka.rw = (float*)(base + kc.rw); ka.bias = (float*)(base + kc.bias);
-  ka.qw = (q == r && n_query == n_ref) ? ka.rw : (float*)(base + kc.qw);
-  ka.cpart = (float*)(base + kc.cpart); ka.ccnt = (int32_t*)(base + kc.ccnt); ka.centre = (float*)(base + kc.centre);
-  ka.part_idx = (int32_t*)(base + kc.pidx); ka.part_score = (float*)(base + kc.pscore);
+  if (q == r && n_query == n_ref) ka.qw = ka.rw;
   ka.idx = idx_out; ka.dist = dist_out;
   return launched(c, launch_knn(ka, (hipStream_t)stream), "knn: no kernel for this row_len / k");
 }

@@ -5,7 +5,7 @@
 # paths; GPU sanitizer runs are not available on the pool.
 ASAN_RT ?= $(shell $(HIPCC) -print-file-name=libclang_rt.asan-x86_64.so 2>/dev/null)
 ASAN_LIB = ../libspmf_hip_asan.so
-%_asan.o: %.hip common.h kernels.h ../../include/spmf_hip.h
+%_asan.o: %.hip arena.h common.h kernels.h ../../include/spmf_hip.h
 	$(HIPCC) $(CXXFLAGS) -O1 -g -Xarch_host -fsanitize=address -Xarch_host -fno-omit-frame-pointer -c $< -o $@
 # instrumented: the two files with host-side logic behind the C-ABI (api.hip, layout.hip)
 ASAN_OBJS = api_asan.o layout_asan.o $(filter-out api.o layout.o,$(OBJS))

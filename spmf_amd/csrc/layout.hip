@@ -27,6 +27,7 @@
 #include <string>
 
 #include "spmf_hip.h"
+#include "arena.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -49,8 +50,6 @@ int lfail(int code, const std::string& m) {
     if (e_ != hipSuccess)                                                              \
       return lfail(SPMF_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_));    \
   } while (0)
-
-inline size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
 
 // The entry points below take a device ordinal: they make it current for their own launches and put
 // the caller's current device back on every return path (a process that drives several GPUs keeps its own).
@@ -115,34 +114,43 @@ int make_geo(int64_t B, int64_t nnz, int D, int P, int khint, Geo* g) {
   return SPMF_OK;
 }
 
-struct LayoutCarve {
-  size_t pc_ptr, pc_row, pc_val, pc_ent, ent, item_ptr, item_mid, per_panel, lower, items, list_first, item_pos, total;
+// The caller's layout buffer: what spmf_counts and spmf_layout_info point into
+struct LayoutBufs {
+  int32_t *pc_ptr, *pc_row;
+  float* pc_val;
+  uint32_t *pc_ent, *ent;
+  int32_t *item_ptr, *item_mid, *per_panel, *lower;
+  int4* items;
+  int32_t* list_first;     // raw index of each list's first work item
+  int32_t* item_pos;       // raw item -> position in `items`
 };
-LayoutCarve carve_layout(const Geo& g) {
-  LayoutCarve c{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o += up256(bytes); return at; };
-  c.pc_ptr = take(((size_t)g.nkeys + g.nP) * 4);
-  c.pc_row = take(((size_t)g.nnz + kPcPad) * 4);
-  c.pc_val = take(((size_t)g.nnz + kPcPad) * 4);
-  c.pc_ent = take(((size_t)g.nnz + kPcPad) * 4);
-  c.ent = take(((size_t)g.nnz + 1) * 4);
-  c.item_ptr = take(((size_t)g.nP + 1) * 4);
-  c.item_mid = take((size_t)g.nP * 4);
-  c.per_panel = take((size_t)g.nP * 4);
-  c.lower = take((size_t)g.nP * 4);
-  c.items = take((size_t)g.max_items * 16);
-  c.list_first = take(((size_t)g.nkeys + 1) * 4);     // raw index of each list's first work item
-  c.item_pos = take((size_t)g.max_items * 4);          // raw item -> position in `items`
-  c.total = o;
-  return c;
+void layout_buffers(Arena& a, const Geo& g, LayoutBufs& L) {
+  const size_t nnz = g.nnz, nkeys = g.nkeys, nP = g.nP, items = g.max_items;
+  L.pc_ptr = a.take<int32_t>(nkeys + nP);
+  L.pc_row = a.take<int32_t>(nnz + kPcPad);
+  L.pc_val = a.take<float>(nnz + kPcPad);
+  L.pc_ent = a.take<uint32_t>(nnz + kPcPad);
+  L.ent = a.take<uint32_t>(nnz + 1);
+  L.item_ptr = a.take<int32_t>(nP + 1);
+  L.item_mid = a.take<int32_t>(nP);
+  L.per_panel = a.take<int32_t>(nP);
+  L.lower = a.take<int32_t>(nP);
+  L.items = a.take<int4>(items);
+  L.list_first = a.take<int32_t>(nkeys + 1);
+  L.item_pos = a.take<int32_t>(items);
 }
 
-struct ScratchCarve {
-  size_t key_in, key_out, word_in, excl, nseg, raw, ikey_in, ikey_out, ival_in, ival_out, info, temp,
-      temp_bytes, total;
+// The build's scratch: sort keys and values of the entries and of the work items, the list bounds, the info
+// block and rocPRIM's temporary storage
+struct ScratchBufs {
+  uint32_t *key_in, *key_out, *word_in;
+  int32_t *excl, *nseg;
+  int4* raw;
+  uint32_t *ikey_in, *ikey_out, *ival_in, *ival_out;
+  int* info;
+  char* temp;
+  size_t temp_bytes;
 };
-
 template <typename KeyT>
 hipError_t sort_temp_bytes(size_t n, int bits, hipStream_t st, size_t* bytes) {
   *bytes = 0;
@@ -150,22 +158,19 @@ hipError_t sort_temp_bytes(size_t n, int bits, hipStream_t st, size_t* bytes) {
                                    (uint32_t*)nullptr, n, 0u, (unsigned)bits, st);
 }
 
-int carve_scratch(const Geo& g, hipStream_t st, ScratchCarve* out) {
-  ScratchCarve c{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o += up256(bytes); return at; };
-  const size_t ks = 4;
-  c.key_in = take(((size_t)g.nnz + 1) * ks);
-  c.key_out = take(((size_t)g.nnz + 1) * ks);
-  c.word_in = take(((size_t)g.nnz + 1) * 4);
-  c.excl = take(((size_t)g.nkeys + 1) * 4);
-  c.nseg = take(((size_t)g.nkeys + 1) * 4);
-  c.raw = take((size_t)g.max_items * 16);
-  c.ikey_in = take((size_t)g.max_items * 4);
-  c.ikey_out = take((size_t)g.max_items * 4);
-  c.ival_in = take((size_t)g.max_items * 4);
-  c.ival_out = take((size_t)g.max_items * 4);
-  c.info = take(I_LEN * 4);
+int scratch_buffers(Arena& a, const Geo& g, hipStream_t st, ScratchBufs& S) {
+  const size_t nnz = g.nnz, nkeys = g.nkeys, items = g.max_items;
+  S.key_in = a.take<uint32_t>(nnz + 1);
+  S.key_out = a.take<uint32_t>(nnz + 1);
+  S.word_in = a.take<uint32_t>(nnz + 1);
+  S.excl = a.take<int32_t>(nkeys + 1);
+  S.nseg = a.take<int32_t>(nkeys + 1);
+  S.raw = a.take<int4>(items);
+  S.ikey_in = a.take<uint32_t>(items);
+  S.ikey_out = a.take<uint32_t>(items);
+  S.ival_in = a.take<uint32_t>(items);
+  S.ival_out = a.take<uint32_t>(items);
+  S.info = a.take<int>(I_LEN);
   size_t t1 = 0, t2 = 0, t3 = 0;
   hipError_t e = sort_temp_bytes<uint32_t>((size_t)g.nnz, g.key_bits, st, &t1);
   if (e == hipSuccess) e = sort_temp_bytes<uint32_t>((size_t)g.max_items, g.item_bits, st, &t2);
@@ -173,10 +178,8 @@ int carve_scratch(const Geo& g, hipStream_t st, ScratchCarve* out) {
     e = rocprim::exclusive_scan(nullptr, t3, (int32_t*)nullptr, (int32_t*)nullptr, 0, (size_t)g.nkeys + 1,
                                 rocprim::plus<int32_t>(), st);
   if (e != hipSuccess) return lfail(SPMF_E_HIP, std::string("layout: rocprim size query: ") + hipGetErrorString(e));
-  c.temp_bytes = t1 > t2 ? (t1 > t3 ? t1 : t3) : (t2 > t3 ? t2 : t3);
-  c.temp = take(c.temp_bytes + 256);
-  c.total = o;
-  *out = c;
+  S.temp_bytes = t1 > t2 ? (t1 > t3 ? t1 : t3) : (t2 > t3 ? t2 : t3);
+  S.temp = a.take<char>(S.temp_bytes + 256);
   return SPMF_OK;
 }
 
@@ -505,19 +508,11 @@ __global__ __launch_bounds__(256) void dense_fill_kernel(int64_t B, int D, const
 
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
 
-template <typename KeyT>
 int run_build(const Geo& g, const int32_t* row_ptr, const int32_t* col, const float* val, int col_split,
-              char* layout, const LayoutCarve& L, char* scratch, const ScratchCarve& S, bool* packed_words,
-              int host_info[I_LEN], hipStream_t st) {
-  KeyT* key_in = (KeyT*)(scratch + S.key_in);
-  KeyT* key_out = (KeyT*)(scratch + S.key_out);
-  uint32_t* word_in = (uint32_t*)(scratch + S.word_in);
-  uint32_t* pc_ent = (uint32_t*)(layout + L.pc_ent);
-  uint32_t* ent = g.D <= 65536 ? (uint32_t*)(layout + L.ent) : nullptr;
-  int* info = (int*)(scratch + S.info);
-  int32_t* excl = (int32_t*)(scratch + S.excl);
-  int32_t* first = (int32_t*)(layout + L.list_first);
-  void* temp = scratch + S.temp;
+              const LayoutBufs& L, const ScratchBufs& S, bool* packed_words, int host_info[I_LEN], hipStream_t st) {
+  using KeyT = uint32_t;   // panel * D + column stays below 2^32 (make_geo)
+  uint32_t* ent = g.D <= 65536 ? L.ent : nullptr;
+  int* info = S.info;
   size_t tb = S.temp_bytes;
   const int64_t want = (g.B + 3) / 4;
   const unsigned nb = (unsigned)(want < 1 ? 1 : (want > 8192 ? 8192 : want));
@@ -527,48 +522,39 @@ int run_build(const Geo& g, const int32_t* row_ptr, const int32_t* col, const fl
     if (g.nnz > 0) {
       if (by_index)
         hipLaunchKernelGGL((layout_keys_kernel<KeyT, true>), dim3(nb), dim3(256), 0, st, g.B, g.nnz, g.D, g.P,
-                           row_ptr, col, val, key_in, word_in, ent, info);
+                           row_ptr, col, val, S.key_in, S.word_in, ent, info);
       else
         hipLaunchKernelGGL((layout_keys_kernel<KeyT, false>), dim3(nb), dim3(256), 0, st, g.B, g.nnz, g.D, g.P,
-                           row_ptr, col, val, key_in, word_in, ent, info);
-      LCHK(rocprim::radix_sort_pairs(temp, tb, key_in, key_out, word_in, pc_ent, (size_t)g.nnz, 0u,
+                           row_ptr, col, val, S.key_in, S.word_in, ent, info);
+      LCHK(rocprim::radix_sort_pairs(S.temp, tb, S.key_in, S.key_out, S.word_in, L.pc_ent, (size_t)g.nnz, 0u,
                                      (unsigned)g.key_bits, st));
     }
     hipLaunchKernelGGL((layout_bounds_kernel<KeyT>), dim3(blocks_for(g.nkeys + 1)), dim3(256), 0, st, g.nkeys, g.D,
-                       g.P, g.B, g.nnz, row_ptr, key_out, excl, (int32_t*)(layout + L.pc_ptr));
+                       g.P, g.B, g.nnz, row_ptr, S.key_out, S.excl, L.pc_ptr);
     if (by_index)
       hipLaunchKernelGGL((layout_unpack_kernel<KeyT, true>), dim3(blocks_for(g.nnz + kPcPad)), dim3(256), 0, st,
-                         g.nnz, g.D, g.P, g.B, row_ptr, val, key_out, pc_ent, (int32_t*)(layout + L.pc_row),
-                         (float*)(layout + L.pc_val));
+                         g.nnz, g.D, g.P, g.B, row_ptr, val, S.key_out, L.pc_ent, L.pc_row, L.pc_val);
     else
       hipLaunchKernelGGL((layout_unpack_kernel<KeyT, false>), dim3(blocks_for(g.nnz + kPcPad)), dim3(256), 0, st,
-                         g.nnz, g.D, g.P, g.B, row_ptr, val, key_out, pc_ent, (int32_t*)(layout + L.pc_row),
-                         (float*)(layout + L.pc_val));
+                         g.nnz, g.D, g.P, g.B, row_ptr, val, S.key_out, L.pc_ent, L.pc_row, L.pc_val);
     if (attempt == 0) {
       // work items: they depend on the list lengths only
-      int32_t* nseg = (int32_t*)(scratch + S.nseg);
-      hipLaunchKernelGGL(layout_nseg_kernel, dim3(blocks_for(g.nkeys + 1)), dim3(256), 0, st, g.nkeys, g.seg, excl,
-                         nseg, info);
-      LCHK(rocprim::exclusive_scan(temp, tb, nseg, first, 0, (size_t)g.nkeys + 1, rocprim::plus<int32_t>(), st));
-      uint32_t* ikey_in = (uint32_t*)(scratch + S.ikey_in);
-      uint32_t* ikey_out = (uint32_t*)(scratch + S.ikey_out);
-      uint32_t* ival_in = (uint32_t*)(scratch + S.ival_in);
-      uint32_t* ival_out = (uint32_t*)(scratch + S.ival_out);
+      hipLaunchKernelGGL(layout_nseg_kernel, dim3(blocks_for(g.nkeys + 1)), dim3(256), 0, st, g.nkeys, g.seg,
+                         S.excl, S.nseg, info);
+      LCHK(rocprim::exclusive_scan(S.temp, tb, S.nseg, L.list_first, 0, (size_t)g.nkeys + 1,
+                                   rocprim::plus<int32_t>(), st));
       hipLaunchKernelGGL(layout_fill_kernel, dim3(blocks_for(g.max_items)), dim3(256), 0, st, g.max_items, kPadKey,
-                         ikey_in);
+                         S.ikey_in);
       hipLaunchKernelGGL(layout_fill_kernel, dim3(blocks_for(g.max_items)), dim3(256), 0, st, g.max_items, 0u,
-                         ival_in);
+                         S.ival_in);
       hipLaunchKernelGGL(layout_items_kernel, dim3(blocks_for(g.nkeys + 1)), dim3(256), 0, st, g.nkeys, g.D, g.seg,
-                         col_split, excl, first, (int4*)(scratch + S.raw), ikey_in, ival_in, info,
-                         (int64_t)g.max_items);
-      LCHK(rocprim::radix_sort_pairs(temp, tb, ikey_in, ikey_out, ival_in, ival_out, (size_t)g.max_items, 0u,
+                         col_split, S.excl, L.list_first, S.raw, S.ikey_in, S.ival_in, info, (int64_t)g.max_items);
+      LCHK(rocprim::radix_sort_pairs(S.temp, tb, S.ikey_in, S.ikey_out, S.ival_in, S.ival_out, (size_t)g.max_items, 0u,
                                      (unsigned)g.item_bits, st));
       hipLaunchKernelGGL(layout_gather_items_kernel, dim3(blocks_for(g.max_items)), dim3(256), 0, st, info,
-                         (const int4*)(scratch + S.raw), ival_out, (int4*)(layout + L.items),
-                         (int32_t*)(layout + L.item_pos));
-      hipLaunchKernelGGL(layout_panel_items_kernel, dim3(blocks_for(g.nP)), dim3(256), 0, st, g.nP, g.seg, ikey_out,
-                         (int32_t*)(layout + L.item_ptr), (int32_t*)(layout + L.item_mid),
-                         (int32_t*)(layout + L.per_panel), (int32_t*)(layout + L.lower), info);
+                         S.raw, S.ival_out, L.items, L.item_pos);
+      hipLaunchKernelGGL(layout_panel_items_kernel, dim3(blocks_for(g.nP)), dim3(256), 0, st, g.nP, g.seg,
+                         S.ikey_out, L.item_ptr, L.item_mid, L.per_panel, L.lower, info);
     }
     LCHK(hipGetLastError());
     int hi[I_LEN];
@@ -656,13 +642,17 @@ int spmf_layout_sizes_k(int device, int64_t n_rows, int64_t nnz, int32_t n_cols,
   Geo g;
   int rc = make_geo(n_rows, nnz, n_cols, panel_rows, latent_dim, &g);
   if (rc) return rc;
-  *layout_bytes = carve_layout(g).total;
+  LayoutBufs L;
+  Arena la;
+  layout_buffers(la, g, L);
+  *layout_bytes = la.used;
   DeviceScope dev_scope(device);
   LCHK(dev_scope.err);
-  ScratchCarve s;
-  rc = carve_scratch(g, nullptr, &s);
+  ScratchBufs S;
+  Arena sa;
+  rc = scratch_buffers(sa, g, nullptr, S);
   if (rc) return rc;
-  *scratch_bytes = s.total;
+  *scratch_bytes = sa.used;
   return SPMF_OK;
 }
 
@@ -692,23 +682,23 @@ int spmf_layout_build_k(int device, int64_t n_rows, int64_t nnz, int32_t n_cols,
   DeviceScope dev_scope(device);
   LCHK(dev_scope.err);
   hipStream_t st = (hipStream_t)stream;
-  const LayoutCarve L = carve_layout(g);
-  ScratchCarve S;
-  rc = carve_scratch(g, st, &S);
+  LayoutBufs L;
+  ScratchBufs S;
+  Arena la(layout, layout_bytes), sa(scratch, scratch_bytes);
+  layout_buffers(la, g, L);
+  rc = scratch_buffers(sa, g, st, S);
   if (rc) return rc;
-  if (layout_bytes < L.total || scratch_bytes < S.total)
+  if (!la.fits() || !sa.fits())
     return lfail(SPMF_E_WORKSPACE, "layout_build: buffers smaller than spmf_layout_sizes reports");
   bool packed_words = false;
   int hi[I_LEN] = {0};
-  rc = run_build<uint32_t>(g, row_ptr, col_idx, val, col_split, (char*)layout, L, (char*)scratch, S,
-                           &packed_words, hi, st);
+  rc = run_build(g, row_ptr, col_idx, val, col_split, L, S, &packed_words, hi, st);
   if (rc) return rc;
   if (hi[I_FLAGS] & F_ROWPTR)
     return lfail(SPMF_E_ARG, "layout_build: row_ptr is not a CSR offset array of this shard (row_ptr[0] == 0, "
                              "non-decreasing, row_ptr[n_rows] == nnz)");
   if (hi[I_FLAGS] & F_COLUMN) return lfail(SPMF_E_ARG, "layout_build: a column index lies outside [0, n_cols)");
   const bool values_pack = !(hi[I_FLAGS] & F_VALUE) && g.nnz > 0;
-  char* lb = (char*)layout;
   spmf_counts c{};
   c.struct_size = (int32_t)sizeof(spmf_counts);
   c.n_rows = g.B;
@@ -720,22 +710,22 @@ int spmf_layout_build_k(int device, int64_t n_rows, int64_t nnz, int32_t n_cols,
   c.row_ptr = row_ptr;
   c.col_idx = col_idx;
   c.val = val;
-  c.pc_ptr = (const int32_t*)(lb + L.pc_ptr);
-  c.pc_row = (const int32_t*)(lb + L.pc_row);
-  c.pc_val = (const float*)(lb + L.pc_val);
-  c.item_ptr = (const int32_t*)(lb + L.item_ptr);
-  c.items = (const int32_t*)(lb + L.items);
-  c.item_mid = (const int32_t*)(lb + L.item_mid);
+  c.pc_ptr = L.pc_ptr;
+  c.pc_row = L.pc_row;
+  c.pc_val = L.pc_val;
+  c.item_ptr = L.item_ptr;
+  c.items = (const int32_t*)L.items;
+  c.item_mid = L.item_mid;
   c.max_items_per_panel = hi[I_MAXPANEL];
   c.max_items_half[0] = hi[I_MAXLO];
   c.max_items_half[1] = hi[I_MAXHI];
   c.col_split = col_split;
   c.pc_pad = kPcPad;
-  c.list_first = (const int32_t*)(lb + L.list_first);
-  c.item_pos = (const int32_t*)(lb + L.item_pos);
+  c.list_first = L.list_first;
+  c.item_pos = L.item_pos;
   c.n_items = hi[I_NITEMS];
-  c.ent = values_pack && g.D <= 65536 ? (const uint32_t*)(lb + L.ent) : nullptr;
-  c.pc_ent = values_pack && packed_words ? (const uint32_t*)(lb + L.pc_ent) : nullptr;
+  c.ent = values_pack && g.D <= 65536 ? L.ent : nullptr;
+  c.pc_ent = values_pack && packed_words ? L.pc_ent : nullptr;
   *out = c;
   info->n_panels = g.nP;
   info->panel_rows = g.P;
@@ -743,8 +733,8 @@ int spmf_layout_build_k(int device, int64_t n_rows, int64_t nnz, int32_t n_cols,
   info->n_items = hi[I_NITEMS];
   info->packed_ent = c.ent != nullptr;
   info->packed_pc_ent = c.pc_ent != nullptr;
-  info->items_per_panel = (const int32_t*)(lb + L.per_panel);
-  info->items_lower = (const int32_t*)(lb + L.lower);
+  info->items_per_panel = L.per_panel;
+  info->items_lower = L.lower;
   return SPMF_OK;
 }
 

@@ -1,7 +1,7 @@
 """Do two builds of the library return the same bits from the streaming calls?
 
-    stream_bits.py dump FILE          run top_k, score_cells, rank_cells, embed, predict, group_means and
-                                      waic_streaming at four small cases, and knn at two shapes, with the library
+    stream_bits.py dump FILE          run top_k, score_cells, rank_cells, embed, predict, group_means, set_scores
+                                      and waic_streaming at four small cases, and knn at two shapes, with the library
                                       that SPMF_LIB_PATH names (default: the tree's own) and save every output to FILE
     stream_bits.py compare A B [OUT]  compare two dumps tensor by tensor with torch.equal -> one JSON line,
                                       also written to OUT
@@ -12,14 +12,16 @@ top_k: k = 10 and 64, stored cells excluded and not, columns and scores.  score_
 seeded random order with values 0 .. 3: mean and lppd.  rank_cells: the same list, stored cells excluded: rank,
 candidates and score.  embed: mean and (S >= 2) deviation.  predict: mean, (S >= 2) sd and p_nonzero for all
 columns and for the list (D - 1, 0, 3, 3, D // 2), which holds a duplicate.  group_means: sum and sum_nonzero for
-the labels -1, 0, 1, 2, -1, ... with four groups (group 3 is empty), all columns and the same list.  knn: two of tests/test_gpu_knn.py's SHAPES with its
+the labels -1, 0, 1, 2, -1, ... with four groups (group 3 is empty), all columns and the same list.  set_scores:
+mean and sd of three sets -- that list (its repeated column counts twice), an empty set and every second column --
+with seeded normal weights.  knn: two of tests/test_gpu_knn.py's SHAPES with its
 points, (nq, nr, K, k) = (131, 197, 16, 10) Euclidean under both SPMF_KNN_TILE values and (5, 333, 33, 64) cosine:
 indices and distances.  waic_streaming (row scores included) is called
 TWICE in each dump: its fp64 sums are atomics, so `compare` also reports whether the two calls of one build
 agree, which is the bar a comparison across builds has to be read against.
 
 A dump is made in a process of its own per build (a library is loaded once per process); a build from before
-embed / knn (predict, group_means) lacks their entry points and dumps no tensor of theirs."""
+embed / knn (predict, group_means, set_scores) lacks their entry points and dumps no tensor of theirs."""
 import ctypes as C
 import json
 import os
@@ -32,7 +34,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 CASES = [("poisson", 131, 197, 16, 7), ("mixed", 65, 130, 40, 3), ("bernoulli_log", 70, 150, 3, 2),
          ("poisson", 40, 70, 128, 3)]
 KNN_CASES = [(131, 197, 16, 10, "euclidean", ("0", "1")), (5, 333, 33, 64, "cosine", (None,))]
-CALLS = ("top_k", "score_cells", "rank_cells", "embed", "knn", "predict", "group_means")
+CALLS = ("top_k", "score_cells", "rank_cells", "embed", "knn", "predict", "group_means", "set_scores")
 
 
 def dump(path):
@@ -79,6 +81,12 @@ def dump(path):
                 assert grp["count"].tolist()[3] == 0
                 for name in ("sum", "sum_nonzero"):
                     out[f"group_means/{tag}/{ctag}/{name}"] = grp[name].cpu()
+        if "spmf_set_scores" in _lib.SIGNATURES:
+            sets = [listed, np.array([], dtype=np.int64), np.arange(0, D, 2)]
+            wts = [np.random.default_rng(7 + i).normal(size=len(s)).astype(np.float32) for i, s in enumerate(sets)]
+            sc = m.set_scores(batch, sets, weights=wts, draws=params, sd=True)
+            for name in ("mean", "sd"):
+                out[f"set_scores/{tag}/{name}"] = sc[name].cpu()
         for call in (0, 1):
             w = m.waic_streaming(batch, draws=params, row_scores=True)
             for name, v in w.items():
