@@ -117,8 +117,8 @@ typedef struct spmf_counts {
   /* Readable int32/float entries behind the END of the last list in pc_row, pc_val, pc_ent
    * AND pc_gval (every list array the context's decoder reads must carry the same padding:
    * with log_transform that includes pc_gval).  With pc_pad >= 4*ceil(K/4) - 1 (K padded to 4,
-   * 8, 16, 32, 64) the column pass fetches list entries four at a time (16-B loads that may run
-   * past a list's end); 0 selects the entry-at-a-time fetch, which never reads behind a list.
+   * 8, 16, 32, 64) the column pass fetches list entries four or eight at a time (16-B loads that
+   * may run past a list's end); 0 selects the entry-at-a-time fetch, which never reads behind a list.
    * Negative values are rejected.  (Until version 2 this slot was a reserved field: a caller
    * that left it uninitialised is caught by struct_size below.) */
   int32_t pc_pad;

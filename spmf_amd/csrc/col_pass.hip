@@ -23,13 +23,26 @@
 // float4, so a wave holds NG=64/LPN lane groups; EACH GROUP OWNS ONE ITEM and
 // keeps that item's gV'/gA'/gphi slices in registers, so there is no
 // cross-lane reduction besides the DPP fold of the dot product.  A group
-// streams its item 4*LPN entries per fetch (four per lane, a 16*LPN-B
-// contiguous read; the narrow form LPN entries, one per lane) and broadcasts
-// an entry inside the group with ds_bpermute; gathers are issued four entries
-// (eight 16-B loads per lane) at a time.  The next fetch is loaded at the top
-// of a step, under each lane's own bound, and copied into place at its end
-// (the kernel's loop: the forms that load it unconditionally behind the step's
-// gathers, in a loop body that stands twice, measured slower).
+// streams its item FE = EPL*LPN entries per fetch -- EPL = 8 per lane for the
+// packed lists at K <= 32 (two 16-B loads, a 32*LPN-B contiguous read: 64
+// entries at K = 32), 4 for the packed lists at K = 64 and for the canonical
+// arrays, 1 in the narrow form -- and broadcasts an entry inside the group
+// with ds_bpermute; gathers are issued four entries (eight 16-B loads per
+// lane) at a time.  The first fetch is issued right behind the item
+// descriptor, beside the V' row and phi.  A wave whose lists all end inside it
+// (five C3 lists in six have <= 64 entries) runs the loop body ONCE: no second
+// fetch, no copy.  Otherwise the next fetch is loaded at the top of a step,
+// under each lane's own bound, and copied into place at its end (the kernel's
+// loop: behind the step's first gather group it measured slower, as did the
+// forms that load it unconditionally, in a loop body that stands twice).
+//
+// Padding.  A lane loads its EPL words only if the FIRST of them belongs to
+// the list (EPL*sub < cnt), so a fetch reads at most EPL - 1 entries behind a
+// list's end: 7 (EPL = 8), 3 (EPL = 4), 0 (EPL = 1).  The documented rule is
+// coarser -- spmf_counts.pc_pad >= 4*ceil(K/4) - 1 selects a wide fetch
+// (include/spmf_hip.h) -- and stays: it grants 3 entries at every K and 7 at
+// every K >= 5, so only KP = 4 with pc_pad 3 ... 6 takes the four-word form
+// for want of padding (launch_col_t).
 //
 // L2 residency is what makes the 2 x 4*KP-B-per-entry gathers affordable
 // (measured: served from Infinity Cache instead, the pass runs at ~8.6 TB/s
@@ -56,6 +69,10 @@ namespace spmf {
 #ifndef COL_GRP
 #define COL_GRP 4
 #endif
+// Largest KP whose packed lists are fetched eight words per lane.  K = 64 stays at four: with eight,
+// col_pass_kernel<64, 1, 8, true> (log_transform: pc_gval at the same width) needs 12 bytes of scratch per lane
+// under the four-wave bound, and <64, 4, 8, true> all 128 registers (profiles/r08_col_fetch_ab.txt)
+constexpr int kCol8MaxKP = 32;
 
 // The extra first block of a launch (pack_dacc != null): fold the kDaccRep replicas of the row
 // pass's fp64 scalars into the accumulator tail as (hi, lo) float pairs, so that ONE fp32
@@ -98,19 +115,24 @@ __device__ __forceinline__ void pack_block(const double* __restrict__ dacc, floa
   if (i < kDaccHead + KP) fold_dacc(i, dacc, tail, KP);
 }
 
-// ONE kernel body for both fetch shapes (the round-3 file carried it twice):
-//   EPL = 4 ("wide", the default): every lane reads FOUR consecutive entries of its group's list (one
-//     16-B load per array; list starts are only 4-B aligned), so a fetch covers 4*LPN entries = one 128-B
-//     line per group and array at K = 32, against one 32-B piece of a line per 8 entries with EPL = 1
-//     (four times the vector-cache line slots for the same bytes).  Reads up to 4*LPN - 1 entries past the
-//     end of a list: the caller guarantees that much readable padding behind the panel-CSC arrays
-//     (spmf_counts.pc_pad).  PACKED: one word per entry, row inside the panel << 16 | count
-//     (spmf_counts.pc_ent).
+// ONE kernel body for all fetch shapes (the round-3 file carried it twice):
+//   EPL = 4 ("wide"): every lane reads FOUR consecutive entries of its group's list (one 16-B load per
+//     array; list starts are only 4-B aligned), so a fetch covers 4*LPN entries = one 128-B stretch per
+//     group and array at K = 32, against one 32-B piece of a line per 8 entries with EPL = 1 (four times
+//     the vector-cache line slots for the same bytes).  A lane loads under its own bound, so a fetch reads
+//     at most EPL - 1 = 3 entries past the end of a list; the caller guarantees readable padding behind the
+//     panel-CSC arrays (spmf_counts.pc_pad; the rule and what it grants: the header comment).  PACKED: one
+//     word per entry, row inside the panel << 16 | count (spmf_counts.pc_ent).
+//   EPL = 8 (the packed lists at K <= 32, the default there): EIGHT consecutive words per lane, two 16-B
+//     loads under the one bound -- 8*LPN entries per fetch, 64 at K = 32, so that a typical list (C3: 57 +- 7.5
+//     entries) is fetched whole ahead of its first gather, in three lines where two fetches of four words
+//     touch four.  Reads at most 7 entries past the end of a list.  With log_transform pc_gval is fetched at
+//     the same width.
 //   EPL = 1 ("narrow"): one entry per lane and fetch, never reads behind a list (pc_pad = 0: a C-ABI
 //     caller whose arrays carry no padding).
 // LIK: 0 Poisson / linear, 1 Poisson / log_transform, 2 Bernoulli(logits) / linear, 3 mixed, 4 Bernoulli / exp
 template <int KP, int LIK, int EPL, bool PACKED>
-__global__ __launch_bounds__(256, EPL == 4 ? COL_WIDE_WAVES : 1) void col_pass_kernel(
+__global__ __launch_bounds__(256, EPL >= 4 ? COL_WIDE_WAVES : 1) void col_pass_kernel(
     int D, int n_panels, int row_base, int blocks_per_panel,
     const int32_t* __restrict__ item_ptr, const int4* __restrict__ items,
     const int32_t* __restrict__ pc_row, const float* __restrict__ pc_val,
@@ -122,8 +144,9 @@ __global__ __launch_bounds__(256, EPL == 4 ? COL_WIDE_WAVES : 1) void col_pass_k
     float* __restrict__ pack_tail, int64_t dacc_stride, const uint32_t* __restrict__ pc_ent,
     int panel_rows, float* __restrict__ det_part, int64_t det_part_stride,
     const double* __restrict__ det_slots, int64_t det_stride) {
-  static_assert(EPL == 1 || EPL == 4, "entries per lane and fetch: 1 or 4");
-  static_assert(!PACKED || EPL == 4, "the packed lists are read by the wide fetch only");
+  static_assert(EPL == 1 || EPL == 4 || EPL == 8, "entries per lane and fetch: 1, 4 or 8");
+  static_assert(!PACKED || EPL >= 4, "the packed lists are read by the wide fetches only");
+  static_assert(EPL != 8 || PACKED, "eight entries per lane: the packed lists only");
   if (pack_dacc && blockIdx.x == 0) {
     pack_block<KP>(pack_dacc + (size_t)blockIdx.y * dacc_stride, pack_tail + (size_t)blockIdx.y * acc_stride,
                    det_slots ? det_slots + (size_t)blockIdx.y * det_stride : nullptr);
@@ -144,9 +167,9 @@ __global__ __launch_bounds__(256, EPL == 4 ? COL_WIDE_WAVES : 1) void col_pass_k
   // z and xi*gz as range-checked tables: the slots behind a list's end (and the lane groups without an item)
   // ask for row kPadRow, which the address unit drops (common.h GTable)
   const GTable zt = gtable(z, Brows, KP), gt = gtable(gzs, Brows, KP);
-  // entries gathered back to back: COL_GRP of the 4 * LPN a wide fetch holds (also at K <= 8, where a lane group
+  // entries gathered back to back: COL_GRP of the EPL * LPN a wide fetch holds (also at K <= 8, where a lane group
   // is one or two lanes and used to keep ONE or two entries in flight); the narrow fetch holds LPN
-  constexpr int GRP = EPL == 4 ? COL_GRP : (LPN < COL_GRP ? LPN : COL_GRP);
+  constexpr int GRP = EPL >= 4 ? COL_GRP : (LPN < COL_GRP ? LPN : COL_GRP);
   static_assert((EPL * LPN) % GRP == 0, "a fetch is a whole number of gather groups");
   __shared__ __attribute__((aligned(16))) float stage[4][NG][2 * KP];
   const int lane = threadIdx.x & 63;
@@ -211,19 +234,22 @@ __global__ __launch_bounds__(256, EPL == 4 ? COL_WIDE_WAVES : 1) void col_pass_k
       f.g[t] = 0.f;
     }
     if (EPL * sub < f.cnt) {
-      if constexpr (EPL == 4) {
-        if (PACKED) {
-          const I4 w = *reinterpret_cast<const I4*>(reinterpret_cast<const int32_t*>(pc_ent) + e);
-          f.r[0] = w.x; f.r[1] = w.y; f.r[2] = w.z; f.r[3] = w.w;
-        } else {
-          const I4 w = *reinterpret_cast<const I4*>(pc_row + e);
-          const F4 v = *reinterpret_cast<const F4*>(pc_val + e);
-          f.r[0] = w.x; f.r[1] = w.y; f.r[2] = w.z; f.r[3] = w.w;
-          f.x[0] = v.x; f.x[1] = v.y; f.x[2] = v.z; f.x[3] = v.w;
-        }
-        if (LIK == 1 || LIK == 4) {                   // g(x) = log(x/eta+1), data side
-          const F4 v = *reinterpret_cast<const F4*>(pc_gval + e);
-          f.g[0] = v.x; f.g[1] = v.y; f.g[2] = v.z; f.g[3] = v.w;
+      if constexpr (EPL >= 4) {
+#pragma unroll
+        for (int h = 0; h < EPL; h += 4) {            // one 16-B load per array and four entries
+          if (PACKED) {
+            const I4 w = *reinterpret_cast<const I4*>(reinterpret_cast<const int32_t*>(pc_ent) + e + h);
+            f.r[h] = w.x; f.r[h + 1] = w.y; f.r[h + 2] = w.z; f.r[h + 3] = w.w;
+          } else {
+            const I4 w = *reinterpret_cast<const I4*>(pc_row + e + h);
+            const F4 v = *reinterpret_cast<const F4*>(pc_val + e + h);
+            f.r[h] = w.x; f.r[h + 1] = w.y; f.r[h + 2] = w.z; f.r[h + 3] = w.w;
+            f.x[h] = v.x; f.x[h + 1] = v.y; f.x[h + 2] = v.z; f.x[h + 3] = v.w;
+          }
+          if (LIK == 1 || LIK == 4) {                 // g(x) = log(x/eta+1), data side
+            const F4 v = *reinterpret_cast<const F4*>(pc_gval + e + h);
+            f.g[h] = v.x; f.g[h + 1] = v.y; f.g[h + 2] = v.z; f.g[h + 3] = v.w;
+          }
         }
       } else {
         f.r[0] = pc_row[e];
@@ -251,20 +277,29 @@ __global__ __launch_bounds__(256, EPL == 4 ? COL_WIDE_WAVES : 1) void col_pass_k
     }
   };
 
-  // The next fetch is loaded at the top of a step (the wide form's next 4*LPN entries; the narrow form runs two
-  // fetches, 2*LPN entries, ahead).  It stands in front of the step's gathers -- vector-memory operations return in
-  // issue order, so the first gather's wait is a wait for it too -- and the copy fa = fb at the step's end waits for it
-  // again.  Round 6 built the alternative: every lane loads, unconditionally (inside the lists' padding), behind the
-  // gathers of the step's first or last group or at the top, in a loop body that stands twice with fa and fb in
-  // swapped roles, so that every wait is counted.  All of those were SLOWER on C3 (1.21 -> 1.26 ... 1.30 ms,
-  // profiles/r06_stream_issue_ab.txt): the lanes behind a list's end then load too (one more 128-B line per list
-  // of ~57 entries, from HBM), and the later the fetch is issued, the less of a step it has to land in.
+  // The first fetch (fa) was asked for with the item's V' row and phi.  A step works on fa; a further fetch is
+  // loaded only while some group of the wave has entries behind fa (`more`, wave-uniform), so the wave of short
+  // lists -- with EPL = 8 five C3 lists in six -- runs ONE step: nothing stands in front of its first gathers but
+  // what they need, and there is no copy and no second round of bound arithmetic.  When there is a next fetch
+  // (the wide forms' next FE entries; the narrow form runs two fetches, 2*LPN entries, ahead) it is loaded at the
+  // top of the step.  It then stands in front of the step's gathers -- vector-memory operations return in issue
+  // order, so the first gather's wait is a wait for it too -- and the copy fa = fb at the step's end waits for it
+  // again.  Two other placements were built and were SLOWER on C3.  Round 6 (profiles/r06_stream_issue_ab.txt,
+  // 1.21 -> 1.26 ... 1.30 ms): every lane loads, unconditionally (inside the lists' padding), behind the gathers
+  // of the step's first or last group or at the top, in a loop body that stands twice with fa and fb in swapped
+  // roles -- the lanes behind a list's end then load too (one more 128-B line per list of ~57 entries, from HBM),
+  // and the later the fetch is issued, the less of a step it has to land in.  Round 8
+  // (profiles/r08_col_fetch_ab.txt): this loop with the next fetch, still under the lane bound, behind the first
+  // gather group of a step instead of at its top -- +0.006 ms on the column tap against the top-of-step form.
   Raw fa, fb, fc;
   fetch_raw(fa);
   if (EPL == 1) fetch_raw(fb);
-  while (__any(fa.cnt > 0)) {
-    if (EPL == 1) fetch_raw(fc);
-    else fetch_raw(fb);
+  bool more;                                          // wave-uniform: another step follows this one
+  do {
+    // (wide forms) entries left behind the fetch in fa, in some group of the wave?  If not, this is the last
+    // step and nothing more is fetched or copied: a wave of short lists runs the body once on its first fetch
+    more = EPL == 1 || __any(cur < end);
+    if (more) fetch_raw(EPL == 1 ? fc : fb);
     int rr0[EPL];
     float xx0[EPL], gx0[EPL];
     decode(fa, rr0, xx0, gx0);
@@ -317,10 +352,11 @@ __global__ __launch_bounds__(256, EPL == 4 ? COL_WIDE_WAVES : 1) void col_pass_k
     if (EPL == 1) {
       fa = fb;
       fb = fc;
-    } else {
+      more = __any(fa.cnt > 0);
+    } else if (more) {
       fa = fb;
     }
-  }
+  } while (more);
   // ---- transpose through LDS so each atomic instruction covers whole rows --
   // (a wave leaves through 8 float-atomic wave instructions, each covering two whole 128-B gradient
   //  rows: the shape MI355X runs atomics at full rate; n_items * (2KP+1)*4 B, 0.49 GB on C3.  The
@@ -372,14 +408,30 @@ static bool launch_col_t(const ColArgs& a, hipStream_t st) {
       a.item_ptr, items, a.pc_row, a.pc_val, a.pc_gval, a.Vp, a.phi, a.z, a.gzs, a.gAp, a.gVp, \
       a.gphi, a.ctype, a.item_mid, a.half_sel, a.B, a.acc_stride, a.pack_dacc, a.pack_tail,     \
       a.dacc_stride, a.pc_ent, a.panel_rows, a.det_part, a.det_part_stride, a.det_slots, a.det_stride
-  const bool wide = a.pc_pad >= KP - 1;   // 4*LPN - 1 entries of readable padding
+  // the documented rule (include/spmf_hip.h): pc_pad >= 4*ceil(K/4) - 1 selects a wide fetch.  What the wide
+  // forms need is EPL - 1 entries (a lane loads under its own bound, the header comment): 3 and 7, so the rule
+  // covers four words at every KP and eight words at every KP >= 8
+  const bool wide = a.pc_pad >= KP - 1;
   // packed lists (spmf_counts.pc_ent: row in panel << 16 | count) when the batch carries them
   const bool packed = wide && a.pc_ent && a.panel_rows > 0 && a.panel_rows <= 65536;
+  // ... eight words per lane at KP <= kCol8MaxKP.  Only KP = 4 can be `wide` with less than seven entries of
+  // padding (pc_pad 3 ... 6): it alone keeps a packed four-word instance beside the eight-word one
+  constexpr bool has8 = KP <= kCol8MaxKP, has4 = !has8 || KP - 1 < 7;
 #define SPMF_COL_LAUNCH(L_)                                                                        \
   do {                                                                                             \
-    if (packed)                                                                                    \
-      hipLaunchKernelGGL((col_pass_kernel<KP, L_, 4, true>), SPMF_COL_ARGS);                       \
-    else if (wide)                                                                                 \
+    if constexpr (has8) {                                                                          \
+      if (packed && a.pc_pad >= 7) {                                                               \
+        hipLaunchKernelGGL((col_pass_kernel<KP, L_, 8, true>), SPMF_COL_ARGS);                     \
+        break;                                                                                     \
+      }                                                                                            \
+    }                                                                                              \
+    if constexpr (has4) {                                                                          \
+      if (packed) {                                                                                \
+        hipLaunchKernelGGL((col_pass_kernel<KP, L_, 4, true>), SPMF_COL_ARGS);                     \
+        break;                                                                                     \
+      }                                                                                            \
+    }                                                                                              \
+    if (wide)                                                                                      \
       hipLaunchKernelGGL((col_pass_kernel<KP, L_, 4, false>), SPMF_COL_ARGS);                      \
     else                                                                                           \
       hipLaunchKernelGGL((col_pass_kernel<KP, L_, 1, false>), SPMF_COL_ARGS);                      \
