@@ -45,6 +45,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "row_prefetch.h"
 
 namespace spmf {
 
@@ -64,6 +65,12 @@ static_assert(ROW_MAX_BLOCKS <= spmf::kDetMaxBlocks,
 #ifndef ROW_WAVES_PER_SIMD
 #define ROW_WAVES_PER_SIMD 1
 #endif
+// The warm-up of a coming row's entry lines by scalar loads (issue_next in the row loop, K <= 32): 0 = none,
+// L = 1 or 2 = the row whose vector load is L rows away.  (ROW_PREFETCH_WORDS, row_prefetch.h: words between two loads.)
+#ifndef ROW_PREFETCH
+#define ROW_PREFETCH 1
+#endif
+static_assert(ROW_PREFETCH >= 0 && ROW_PREFETCH <= 2, "ROW_PREFETCH: 0, or a lead of 1 or 2 rows");
 
 namespace {
 
@@ -124,6 +131,42 @@ __device__ __forceinline__ void unpack_entry(int ra, float rb, bool ok, int& c, 
     c = ok ? ra : kPadRow;
     x = ok ? rb : 0.f;
   }
+}
+
+// The warm-up of a coming row's entry lines: one word of every 64-byte half line that the first 128 entry words of the
+// row span (which words: row_warm_word, row_prefetch.h), read through the constant address space from a wave-uniform
+// address -- scalar loads, whose path into this XCD's L2 holds no miss slot of the vector cache.  The entry arrays
+// are read-only for the kernel's lifetime.  The values are dead: warm_retire keeps them until a point where the scalar
+// loads of the issue point have been waited for anyway, so that no wait is added.  A row without entries reads nothing.
+template <int FMT>
+struct RowWarm {
+  static constexpr int N = (FMT == 1 ? 1 : 2) * kRowWarmLoads;
+  uint32_t w[N] = {};
+};
+template <int FMT>
+__device__ __forceinline__ void warm_issue(RowWarm<FMT>& r, const int32_t* __restrict__ col,
+                                           const float* __restrict__ val, const uint32_t* __restrict__ ent, int start,
+                                           int n) {
+  typedef const __attribute__((address_space(4))) uint32_t* Words;
+  if (n > 0) {   // wave-uniform
+#pragma unroll
+    for (int i = 0; i < kRowWarmLoads; ++i) {
+      const int at = start + row_warm_word(i, n);
+      if (FMT == 1) {
+        r.w[i] = ((Words)ent)[at];
+      } else {
+        r.w[i] = ((Words)col)[at];
+        r.w[kRowWarmLoads + i] = ((Words)val)[at];
+      }
+    }
+  }
+}
+// (`behind`: a value that is there only behind the wait that covers them -- the consumer takes it as an operand too,
+//  or the optimiser moves it, and with it the wait for the scalar loads, up to the loads)
+template <int FMT>
+__device__ __forceinline__ void warm_retire(const RowWarm<FMT>& r, int behind) {
+#pragma unroll
+  for (int i = 0; i < RowWarm<FMT>::N; ++i) asm volatile("" ::"s"(r.w[i]), "v"(behind));
 }
 
 // Lane `base/4 + IMM` 's value: ds_bpermute with the compile-time part of the source lane in the instruction's
@@ -233,9 +276,9 @@ struct RowCtx {
   // with what `behind` issued in flight and nothing else, and the waits inside an arm count T - 1 ... 0 on top of it.
   // (one fold per dot product: a transpose-reduce of the chunk's eight at K = 32 and the packed multiply / fma
   //  forms both measured no faster, profiles/r05_row_valu_ab.txt)
-  template <int T, class Hook>
+  template <int T, class Hook, class Landed>
   __device__ __forceinline__ void s2_arm(int c, float x, int nchunk, const float4& z, float4& gz, float& ll,
-                                         double& nnf, Hook&& behind) const {
+                                         double& nnf, Hook&& behind, Landed&& landed) const {
     float4 vv[LPN];
     float rmine = 0.f;
     s2_issue<T>(c, 0, vv);
@@ -246,7 +289,9 @@ struct RowCtx {
         const float dot = group_sum<LPN>(dot4(z, vv[j]));
         if (sub == j) rmine = dot;
       }
-      s2_cells<T>(c, x, nchunk, rmine, vv, gz, ll, nnf);
+      s2_cells<T>(c, x, nchunk, rmine, vv, gz, ll, nnf, landed);
+    } else {
+      landed(0);
     }
   }
   // f(integral constant T) for the wave-uniform t in 0 ... LPN
@@ -272,20 +317,20 @@ struct RowCtx {
       if constexpr (T > 0) s1_arm<T>(c, x, zacc);
     });
   }
-  template <class Hook>
+  template <class Hook, class Landed>
   __device__ __forceinline__ void sweep2_last(int c, float x, int nlast, const float4& z, float4& gz, float& ll,
-                                              double& nnf, Hook&& behind) const {
+                                              double& nnf, Hook&& behind, Landed&& landed) const {
     by_count(count_of(nlast), [&](auto t) __attribute__((always_inline)) {
-      s2_arm<decltype(t)::value>(c, x, nlast, z, gz, ll, nnf, behind);
+      s2_arm<decltype(t)::value>(c, x, nlast, z, gz, ll, nnf, behind, landed);
     });
   }
 
   // rates, log-likelihood and gz partial over one chunk, group by group under the per-group guard (long rows, and
   // every row at K = 64); `behind_last` runs behind the gathers of the chunk's last group, before they are waited
-  // for (the row loop's issue_next in a long row's last chunk)
-  template <class Hook>
+  // for (the row loop's issue_next in a long row's last chunk); `landed`: s2_cells
+  template <class Hook, class Landed>
   __device__ __forceinline__ void sweep2(int c, float x, int nchunk, const float4& z, float4& gz, float& ll,
-                                         double& nnf, Hook&& behind_last) const {
+                                         double& nnf, Hook&& behind_last, Landed&& landed) const {
     float4 vv[LPN];
     float rmine = 0.f;
 #pragma unroll
@@ -296,17 +341,20 @@ struct RowCtx {
       if (occ) s2_dots<GRP>(g0, z, vv, rmine);
       else s2_dots<0>(g0, z, vv, rmine);
     }
-    s2_cells(c, x, nchunk, rmine, vv, gz, ll, nnf);
+    s2_cells(c, x, nchunk, rmine, vv, gz, ll, nnf, landed);
   }
   // the per-cell part of sweep 2 (one entry per lane) and the gz partial: over the CNT gather instructions of an
-  // arm, or (CNT < 0, K = 64) group by group under the per-group guard
-  template <int CNT = -1>
+  // arm, or (CNT < 0, K = 64) group by group under the per-group guard.  `landed` is given a value of the chunk's last
+  // dot product and of the broadcasts below: what waits for them has waited for every scalar load of the issue
+  // point as well (the row loop retires its warm-up words there)
+  template <int CNT = -1, class Landed>
   __device__ __forceinline__ void s2_cells(int c, float x, int nchunk, float rmine, const float4 (&vv)[LPN],
-                                           float4& gz, float& ll, double& nnf) const {
+                                           float4& gz, float& ll, double& nnf, Landed&& landed) const {
     // one entry per lane: lane (grp,sub) owns slot sub*NPI+grp
     const int slot = sub * NPI + grp;
     const float xs = __shfl(x, slot);
     const int cs = __shfl(c, slot);
+    landed(__float_as_int(rmine) ^ cs);
     float cc = 0.f;
     if (slot < nchunk && xs > 0.f) {
       if (LIK == 2 || LIK == 4 || (LIK == 3 && ctype[cs])) {
@@ -479,6 +527,17 @@ __global__ __launch_bounds__(BT, BT == 256 && KP != 32 ? ROW_WAVES_PER_SIMD : 4)
   const RowScale rscale = (RowScale)row_scale;
   int start = 0, end = 0, pc0 = 0, pc1 = 0, nstart = 0, nend = 0;
   float xi = 1.f, px0 = 0.f, px1 = 0.f, nxi = 1.f;
+  // One more stage of lookahead for the warm-up (K <= 32, where the issue point stands behind the gathers): a row's
+  // pointers are asked for one issue point before its lines are touched, and those are touched ROW_PREFETCH rows
+  // ahead of the row's vector load.  (wstart, wend) is that pair; it feeds dead loads only, the rows themselves
+  // still take their pointers from (nstart, nend) as before.  A row that a counter hands out has no number that
+  // early and goes without (the pair stays 0, 0: nothing is read); so does each wave's first fixed row behind the
+  // two of the prologue.  The entry loads of the issue point drop their non-temporal hint with it (issue_next).
+  // Not the canonical format at K = 32: it retires two words per rung (two arrays), and with five rungs four of its
+  // instances -- LIK 0 and 3 in both LDS forms -- already needed 12 bytes of scratch under the four-wave bound.  One
+  // rule for the format at that K: the parent's loop.
+  constexpr bool WARM = ROW_PREFETCH > 0 && KP <= 32 && (PACKED || KP < 32);
+  int wstart = 0, wend = 0;
   int b = wave < B_static ? wave : Bn;
   int bn = fixed_next(b);
   if (bn < 0) bn = take_dynamic();
@@ -506,6 +565,12 @@ __global__ __launch_bounds__(BT, BT == 256 && KP != 32 ? ROW_WAVES_PER_SIMD : 4)
     int bnnn = fixed_next(bnn);
     const bool dyn_ask = bnnn < 0;                  // wave-uniform
     unsigned int dyn_k = 0;
+    // the row whose pointers the warm-up asks for now and uses at the next issue point: bnnn, which is bnn there
+    // (a lead of one row), or the row behind it (a lead of two); -1 or Bn: none
+    int wrow = bnnn;
+    if (ROW_PREFETCH == 2 && wrow >= 0) wrow = fixed_next(wrow);
+    int nwstart = 0, nwend = 0;
+    RowWarm<PACKED> warm;
     // The row's issue point, run ONCE on every path through the row: the counter's ask, the two chunks of the
     // next row (whose pointers came a row ago; a wave's last rows load nothing) and the pointers of the
     // row after next (scalar loads).  Nothing here stands under a lane predicate.
@@ -515,14 +580,33 @@ __global__ __launch_bounds__(BT, BT == 256 && KP != 32 ? ROW_WAVES_PER_SIMD : 4)
       dyn_k = (unsigned int)__builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(1, dyn_rsrc, (dyn_ask && lane == 0) ? 0 : 4,
                                                                        0, 0);
       const EntryRow<PACKED> er = entry_row<PACKED>(col, val, ent, nstart, nend - nstart);
-      load_entry<PACKED, true>(er, lane, qc0, qx0);
-      load_entry<PACKED, true>(er, lane + 64, qc1, qx1);
+      // (no non-temporal hint on lines that the warm-up has brought in: with the hint the warm-up gains less than
+      //  half as much, profiles/r09_row_prefetch_ab.txt; without the warm-up the hint makes no difference)
+      load_entry<PACKED, !WARM>(er, lane, qc0, qx0);
+      load_entry<PACKED, !WARM>(er, lane + 64, qc1, qx1);
       if (bnn < Bn) {
         nnstart = rptr[bnn];
         nnend = rptr[bnn + 1];
         nnxi = row_scale ? rscale[bnn] : 1.f;
       }
+      // The warm-up rides in this batch of scalar loads and nowhere else: a scalar load in flight turns the next wait
+      // on a ds_bpermute into a full lgkmcnt(0) (one counter, and scalar loads return out of order), which the row
+      // pointers cause here in any case; at the top of a row it would park the wave in front of sweep 1.
+      if constexpr (WARM) {
+        warm_issue<PACKED>(warm, col, val, ent, wstart, wend - wstart);
+        if (wrow >= 0 && wrow < Bn) {
+          nwstart = rptr[wrow];
+          nwend = rptr[wrow + 1];
+        }
+      }
       issue_fence(PACKED ? (const void*)ent : (const void*)col, val, row_ptr);
+    };
+    // Where the warm-up's dead words are let go: behind the first broadcasts that follow the issue point (s2_cells),
+    // whose wait covers the scalar loads in any case -- no wait is added, and the words hold their registers for the
+    // dot products only.  (The encode-only sweep has nothing behind its issue point: the next row's first broadcast
+    // is that wait.)
+    auto landed = [&](int behind) __attribute__((always_inline)) {
+      if constexpr (WARM) warm_retire<PACKED>(warm, behind);
     };
     // K = 64 has no register for it (a chunk's V' rows alone are 64): its issue point stays at the top of the row
     constexpr bool BEHIND = KP <= 32;
@@ -560,18 +644,18 @@ __global__ __launch_bounds__(BT, BT == 256 && KP != 32 ? ROW_WAVES_PER_SIMD : 4)
         zacc = gather4<LPN>(z, (int)b, sub);
       }
       if (encode_only) {
-        if constexpr (BEHIND) issue_next();        // behind the last sweep-1 group
+        if constexpr (BEHIND) { issue_next(); landed(0); }   // behind the last sweep-1 group
       } else {
         // The first of two chunks, then the row's last chunk with the issue point behind its gathers.
         // K <= 32: a chunk's sweep 2 asks for all of its V' rows before its first dot product (s2_arm); at
         // K = 64 a chunk's V' rows are 64 registers, and it gathers group by group.
         if constexpr (KP <= 32) {
-          if (two) cx.template s2_arm<LPN>(c0, x0, 64, zacc, gz, llrow, nnf_acc, [] {});
-          cx.sweep2_last(cl, xl, nl, zacc, gz, llrow, nnf_acc, issue_next);
+          if (two) cx.template s2_arm<LPN>(c0, x0, 64, zacc, gz, llrow, nnf_acc, [] {}, [](int) {});
+          cx.sweep2_last(cl, xl, nl, zacc, gz, llrow, nnf_acc, issue_next, landed);
         } else {
           // (K = 64: group by group, the issue point was at the top of the row)
-          cx.sweep2(c0, x0, n0, zacc, gz, llrow, nnf_acc, [] {});
-          if (n1 > 0) cx.sweep2(c1, x1, n1, zacc, gz, llrow, nnf_acc, [] {});
+          cx.sweep2(c0, x0, n0, zacc, gz, llrow, nnf_acc, [] {}, [](int) {});
+          if (n1 > 0) cx.sweep2(c1, x1, n1, zacc, gz, llrow, nnf_acc, [] {}, [](int) {});
         }
       }
     } else {
@@ -600,7 +684,7 @@ __global__ __launch_bounds__(BT, BT == 256 && KP != 32 ? ROW_WAVES_PER_SIMD : 4)
         zacc = gather4<LPN>(z, (int)b, sub);
       }
       if (encode_only) {
-        if constexpr (BEHIND) issue_next();        // behind the last sweep-1 group
+        if constexpr (BEHIND) { issue_next(); landed(0); }   // behind the last sweep-1 group
       } else {
         int ra = pc0, ra1 = pc1;
         float rb = px0, rb1 = px1;
@@ -613,8 +697,8 @@ __global__ __launch_bounds__(BT, BT == 256 && KP != 32 ? ROW_WAVES_PER_SIMD : 4)
           float x;
           unpack_entry<PACKED>(ra, rb, base + lane < end, c, x);
           // (the row's last chunk, K <= 32, carries the issue point behind its last group's gathers)
-          if (BEHIND && base + 64 >= end) cx.sweep2(c, x, end - base, zacc, gz, llrow, nnf_acc, issue_next);
-          else cx.sweep2(c, x, min(64, end - base), zacc, gz, llrow, nnf_acc, [] {});
+          if (BEHIND && base + 64 >= end) cx.sweep2(c, x, end - base, zacc, gz, llrow, nnf_acc, issue_next, landed);
+          else cx.sweep2(c, x, min(64, end - base), zacc, gz, llrow, nnf_acc, [] {}, [](int) {});
           ra = ra1; rb = rb1; ra1 = ra2; rb1 = rb2;
         }
       }
@@ -625,6 +709,7 @@ __global__ __launch_bounds__(BT, BT == 256 && KP != 32 ? ROW_WAVES_PER_SIMD : 4)
     start = nstart; end = nend; xi = nxi;
     pc0 = qc0; px0 = qx0; pc1 = qc1; px1 = qx1;
     nstart = nnstart; nend = nnend; nxi = nnxi;
+    if constexpr (WARM) { wstart = nwstart; wend = nwend; }
     {
       // (read on every path: an answer left unread would stay "in flight" for the compiler's wait counting)
       const int row = dyn_lo + (int)(unsigned int)__builtin_amdgcn_readfirstlane((int)dyn_k);
