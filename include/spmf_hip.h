@@ -872,7 +872,11 @@ typedef struct spmf_sur_var {
  * variable index, draw, element), so replicas on different ranks that pass the
  * same seed draw the same noise, and a step replayed from a hipGraph gets fresh
  * noise through the device-resident step counter state[13] (spmf_vi_gate advances
- * it; pass state = NULL to use `counter` alone). */
+ * it; pass state = NULL to use `counter` alone).
+ * Domain of dgda: its series runs to the first term past g and stops after 4000 terms, so the
+ * derivative is valid for draws g < 3998, which a concentration softplus(t0) <= 3500 keeps
+ * (g <= a + 8 sqrt(a)); above that the series is cut short and dgda is wrong.  g itself is
+ * clamped below at 1e-30. */
 int spmf_sample_noise(spmf_ctx* ctx, const spmf_sur_var* vars, int nvars, int S, uint64_t seed,
                       uint64_t counter, const double* state, void* stream);
 

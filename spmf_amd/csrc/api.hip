@@ -2150,8 +2150,7 @@ int spmf_adam_step(spmf_ctx* c, const spmf_adam_var* tensors, int ntensors, doub
   const int rc = adam_table(c, "adam_step", tensors, ntensors, T, max_n);
   if (rc) return rc;
   const double c1 = 1.0 - pow(beta1, step), c2 = 1.0 - pow(beta2, step);
-  launch_adam(T, ntensors, max_n, (float)lr, (float)beta1, (float)beta2, (float)eps, (float)c1, (float)c2,
-      (float)clip, (hipStream_t)stream);
+  launch_adam(T, ntensors, max_n, lr, beta1, beta2, eps, c1, c2, clip, (hipStream_t)stream);
   HIPCHK(c, hipGetLastError());
   return SPMF_OK;
 }

@@ -472,7 +472,7 @@ void launch_surrogate_bwd_adam(const SurTable& T, const AdamTable& A, int nvars,
                                float c, const double* state, hipStream_t st);
 void launch_vi_gate(const double* parts, const double* logq, const double* nnf, int S, double c, double rows, double* state, hipStream_t st);
 void launch_adam_dev(const AdamTable& T, int ntensors, int max_n, const double* state, hipStream_t st);
-void launch_adam(const AdamTable& T, int ntensors, int max_n, float lr, float b1, float b2, float eps, float c1, float c2, float clip, hipStream_t st);
+void launch_adam(const AdamTable& T, int ntensors, int max_n, double lr, double b1, double b2, double eps, double c1, double c2, double clip, hipStream_t st);
 
 // ---- the step's collective over peer pointers (p2p.hip) ---------------------------------
 constexpr int kP2PMaxWorld = 16;    // ranks of one node

@@ -34,6 +34,14 @@ __device__ __forceinline__ float sigmoidf_(float x) {
   const float inv = 1.f / (1.f + e);
   return x >= 0.f ? inv : e * inv;
 }
+// sigmoid(x), and om = 1 - sigmoid(x) = sigmoid(-x) without the cancellation of 1.f - sigmoid
+// (d/dy of -log sigmoid(y) is -(1 - sigmoid(y)) = -e^-y for large y, where 1.f - sig is 0 or one ulp of 1)
+__device__ __forceinline__ float sigmoid_pair_(float x, float& om) {
+  const float e = expf(-fabsf(x));
+  const float inv = 1.f / (1.f + e), lo = e * inv;
+  om = x >= 0.f ? lo : inv;
+  return x >= 0.f ? inv : lo;
+}
 // log sigmoid(y) = -softplus(-y)
 __device__ __forceinline__ float logsigmoidf_(float y) { return -softplusf(-y); }
 __device__ __forceinline__ float digammaf_(float x) {
@@ -178,18 +186,23 @@ __device__ __forceinline__ void sur_bwd_elem(const SurVar& v, int i, int S, floa
   if (v.kind == 2) {
     const float a = softplusf(t0), b = softplusf(t1);
     const float lb = logf(b), dga = digammaf_(a);
+    // d a / d t0 and d b / d t1 go into the per-draw factors, not onto the finished sums: with a = 1e-3 the sum
+    // over a is 1000 x the gradient of t0 and leaves the fp32 range where the gradient itself does not
+    const float s0 = sigmoidf_(t0), s1 = sigmoidf_(t1);
+    const float k0 = inv_sb * c * s0, k1 = inv_sb * c * s1;
     for (int s = 0; s < S; ++s) {
       const size_t o = (size_t)s * v.n + i, on = (size_t)s * v.ld + i;
       const float g = v.noise[on], dgda = v.dgda[on], ge = v.gtheta[o];
-      const float y = b / g, sig = sigmoidf_(y);
-      const float dlq_dy = -(a + 1.f) / y + b / (y * y) - (1.f - sig);
+      float oms;
+      const float y = b / g, sig = sigmoid_pair_(y, oms);
+      const float dlq_dy = -(a + 1.f) / y + b / (y * y) - oms;
       const float dL_dy = inv_sb * (-ge * sig + c * dlq_dy);
-      const float dy_da = -b / (g * g) * dgda, dy_db = 1.f / g;
-      g0 += dL_dy * dy_da + inv_sb * c * (lb - dga - logf(y));
-      g1 += dL_dy * dy_db + inv_sb * c * (a / b - 1.f / y);
+      // dy/da = -b/g^2 * dg/da without the square: g reaches the sampler's clamp 1e-30, and g*g is
+      // zero in fp32 below 3.7e-23 (a denormal below 1e-19) where the exact value is finite
+      const float dy_dt0 = -(y * (dgda * s0)) / g, dy_dt1 = s1 / g;
+      g0 += dL_dy * dy_dt0 + k0 * (lb - dga - logf(y));
+      g1 += dL_dy * dy_dt1 + k1 * (a / b - 1.f / y);
     }
-    g0 *= sigmoidf_(t0);
-    g1 *= sigmoidf_(t1);
   } else {
     const float sg = softplusf(t1);
     const bool ident = v.kind != 0 || (v.ident && v.ident[i]);
@@ -199,8 +212,9 @@ __device__ __forceinline__ void sur_bwd_elem(const SurVar& v, int i, int S, floa
       const float y = t0 + sg * eps;
       float dth = 1.f, dlq_dy = 0.f;
       if (!ident) {
-        dth = sigmoidf_(y);
-        dlq_dy = -(1.f - dth);
+        float oms;
+        dth = sigmoid_pair_(y, oms);
+        dlq_dy = -oms;
       }
       const float dL_dy = inv_sb * (-ge * dth + c * dlq_dy);
       g0 += dL_dy;
@@ -235,16 +249,24 @@ __global__ __launch_bounds__(256) void surrogate_bwd_kernel(SurTable T, int S, f
 }
 
 // Adam over 256*kEPT consecutive elements per block.
-__device__ __forceinline__ float adam_elem(float& m, float& v, float p, float g, float lr, float b1,
-                                           float b2, float eps, float c1, float c2, float clip) {
-  if (clip > 0.f) g = fminf(fmaxf(g, -clip), clip);
-  m = b1 * m + (1.f - b1) * g;
-  v = b2 * v + (1.f - b2) * g * g;
-  return p - lr * (m / c1) / (sqrtf(v / c2) + eps);
+// AdamCoef: the step's scalars.  omb1 / omb2 are 1 - beta rounded from fp64: formed in fp32,
+// 1.f - 0.999f is 0.99998713e-3, 1.3e-5 off the weight of g*g in v.
+struct AdamCoef {
+  float lr, b1, b2, omb1, omb2, eps, c1, c2, clip;
+};
+__device__ __forceinline__ AdamCoef adam_coef_dev(const double* __restrict__ state) {
+  return AdamCoef{(float)state[0], (float)state[1], (float)state[2], (float)(1.0 - state[1]),
+                  (float)(1.0 - state[2]), (float)state[3], (float)(1.0 - state[5]),
+                  (float)(1.0 - state[6]), (float)state[4]};
+}
+__device__ __forceinline__ float adam_elem(float& m, float& v, float p, float g, const AdamCoef& k) {
+  if (k.clip > 0.f) g = fminf(fmaxf(g, -k.clip), k.clip);
+  m = k.b1 * m + k.omb1 * g;
+  v = k.b2 * v + k.omb2 * g * g;
+  return p - k.lr * (m / k.c1) / (sqrtf(v / k.c2) + k.eps);
 }
 
-__device__ __forceinline__ void adam_block(const AdamVar& a, float lr, float b1, float b2, float eps,
-                                           float c1, float c2, float clip) {
+__device__ __forceinline__ void adam_block(const AdamVar& a, const AdamCoef& k) {
   const int base = blockIdx.x * (256 * kEPT);
   if (base >= a.n) return;
   // 16-B lanes when the four arrays allow it (dword streams run at about half the
@@ -270,10 +292,10 @@ __device__ __forceinline__ void adam_block(const AdamVar& a, float lr, float b1,
       const int i = base4 + e * 256 + threadIdx.x;
       if (i < n4) {
         float4 o;
-        o.x = adam_elem(m[e].x, vv[e].x, p[e].x, g[e].x, lr, b1, b2, eps, c1, c2, clip);
-        o.y = adam_elem(m[e].y, vv[e].y, p[e].y, g[e].y, lr, b1, b2, eps, c1, c2, clip);
-        o.z = adam_elem(m[e].z, vv[e].z, p[e].z, g[e].z, lr, b1, b2, eps, c1, c2, clip);
-        o.w = adam_elem(m[e].w, vv[e].w, p[e].w, g[e].w, lr, b1, b2, eps, c1, c2, clip);
+        o.x = adam_elem(m[e].x, vv[e].x, p[e].x, g[e].x, k);
+        o.y = adam_elem(m[e].y, vv[e].y, p[e].y, g[e].y, k);
+        o.z = adam_elem(m[e].z, vv[e].z, p[e].z, g[e].z, k);
+        o.w = adam_elem(m[e].w, vv[e].w, p[e].w, g[e].w, k);
         reinterpret_cast<float4*>(a.m)[i] = m[e];
         reinterpret_cast<float4*>(a.v)[i] = vv[e];
         reinterpret_cast<float4*>(a.p)[i] = o;
@@ -296,7 +318,7 @@ __device__ __forceinline__ void adam_block(const AdamVar& a, float lr, float b1,
   for (int e = 0; e < kEPT; ++e) {
     const int i = base + e * 256 + threadIdx.x;
     if (i < a.n) {
-      const float o = adam_elem(m[e], vv[e], p[e], g[e], lr, b1, b2, eps, c1, c2, clip);
+      const float o = adam_elem(m[e], vv[e], p[e], g[e], k);
       a.m[i] = m[e];
       a.v[i] = vv[e];
       a.p[i] = o;
@@ -304,9 +326,8 @@ __device__ __forceinline__ void adam_block(const AdamVar& a, float lr, float b1,
   }
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(AdamTable T, float lr, float b1, float b2,
-                                                   float eps, float c1, float c2, float clip) {
-  adam_block(T.v[blockIdx.y], lr, b1, b2, eps, c1, c2, clip);
+__global__ __launch_bounds__(256) void adam_kernel(AdamTable T, AdamCoef k) {
+  adam_block(T.v[blockIdx.y], k);
 }
 
 // ---- device-resident optimiser state (graph-capturable VI step) -------------
@@ -366,6 +387,9 @@ __device__ __forceinline__ float gamma_dgda(double a, double x) {
   // the density cancels analytically, so no exp / lgamma is needed.  fp64 throughout
   // (in the right tail the terms reach ~e^x before they cancel); the reciprocal is a
   // v_rcp_f32 seed + two Newton steps instead of an fp64 division; ~x + 40 terms.
+  // Domain: the loop ends at the first small term past n > x and at 4000 terms at the latest, so
+  // x < 3998 is needed; draws of a <= 3500 stay below (x <= a + 8 sqrt(a)).  Past that the series
+  // is cut short and the result is wrong (include/spmf_hip.h states the same domain).
   const double lx = log(x);
   double R = x / a;                                     // R_0
   double psi = digammad_(a + 1.0);
@@ -556,8 +580,7 @@ __global__ void vi_gate_kernel(const double* __restrict__ parts, const double* _
 
 __global__ __launch_bounds__(256) void adam_dev_kernel(AdamTable T, const double* __restrict__ state) {
   if (state[9] == 0.0) return;                              // step skipped (poisson.py fit: NaN batch)
-  adam_block(T.v[blockIdx.y], (float)state[0], (float)state[1], (float)state[2], (float)state[3],
-             (float)(1.0 - state[5]), (float)(1.0 - state[6]), (float)state[4]);
+  adam_block(T.v[blockIdx.y], adam_coef_dev(state));
 }
 
 // Chain rule and gated Adam in one pass: the gradient of a trainable pair never goes
@@ -572,13 +595,12 @@ __global__ __launch_bounds__(256) void surrogate_bwd_adam_kernel(SurTable T, Ada
   if (i >= v.n) return;
   float g0, g1;
   sur_bwd_elem(v, i, S, inv_sb, c, g0, g1);
-  const float lr = (float)state[0], b1 = (float)state[1], b2 = (float)state[2], eps = (float)state[3];
-  const float c1 = (float)(1.0 - state[5]), c2 = (float)(1.0 - state[6]), clip = (float)state[4];
+  const AdamCoef k = adam_coef_dev(state);
   const AdamVar& a0 = A.v[2 * blockIdx.y];
   const AdamVar& a1 = A.v[2 * blockIdx.y + 1];
   float m0 = a0.m[i], v0 = a0.v[i], m1 = a1.m[i], v1 = a1.v[i];
-  const float p0 = adam_elem(m0, v0, a0.p[i], g0, lr, b1, b2, eps, c1, c2, clip);
-  const float p1 = adam_elem(m1, v1, a1.p[i], g1, lr, b1, b2, eps, c1, c2, clip);
+  const float p0 = adam_elem(m0, v0, a0.p[i], g0, k);
+  const float p1 = adam_elem(m1, v1, a1.p[i], g1, k);
   a0.m[i] = m0; a0.v[i] = v0; a0.p[i] = p0;
   a1.m[i] = m1; a1.v[i] = v1; a1.p[i] = p1;
 }
@@ -615,10 +637,12 @@ void launch_surrogate_bwd(const SurTable& T, int nvars, int max_n, int S, float 
   dim3 grid((max_n + 256 * kEPTB - 1) / (256 * kEPTB), nvars);
   hipLaunchKernelGGL(surrogate_bwd_kernel, grid, dim3(256), 0, st, T, S, inv_sb, c);
 }
-void launch_adam(const AdamTable& T, int ntensors, int max_n, float lr, float b1, float b2,
-                 float eps, float c1, float c2, float clip, hipStream_t st) {
+void launch_adam(const AdamTable& T, int ntensors, int max_n, double lr, double b1, double b2,
+                 double eps, double c1, double c2, double clip, hipStream_t st) {
+  const AdamCoef k{(float)lr, (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), (float)eps,
+                   (float)c1, (float)c2, (float)clip};
   dim3 grid((max_n + 256 * kEPT - 1) / (256 * kEPT), ntensors);
-  hipLaunchKernelGGL(adam_kernel, grid, dim3(256), 0, st, T, lr, b1, b2, eps, c1, c2, clip);
+  hipLaunchKernelGGL(adam_kernel, grid, dim3(256), 0, st, T, k);
 }
 
 }  // namespace spmf

@@ -653,10 +653,10 @@ def test_vi_step_with_the_hierarchy_beside_the_column_pass_equals_the_single_str
 @pytest.mark.parametrize("D,K,S", [(24, 2, 3), (700, 32, 2), (5000, 16, 1)])
 def test_sample_transform_in_one_launch_equals_the_two_calls(D, K, S):
     """spmf_sample_transform (the VI step's path since round 5): base noise, theta and log q in ONE launch --
-    the per-workgroup log-q sums folded by the last workgroup to arrive -- give the same draws and the same theta
-    BITS as spmf_sample_noise + spmf_surrogate_fwd, and the same log q to fp64 rounding (its partial sums group 256
-    elements, the two-call form 1024); repeated (the arrival ticket resets), with the device step counter, and
-    for a subset of the variables."""
+    every workgroup stores its log-q sum in its own slot and logq_reduce_kernel adds the slots in block order --
+    give the same draws and the same theta BITS as spmf_sample_noise + spmf_surrogate_fwd, and the same log q to
+    fp64 rounding (its partial sums group 256 elements, the two-call form 1024); repeated (every slot is
+    rewritten by every call), with the device step counter, and for a subset of the variables."""
     from spmf_amd import PoissonFactorization
     from spmf_amd import vi
     torch.manual_seed(4)
