@@ -455,7 +455,15 @@ int spmf_p2p_destroy(spmf_ctx* ctx);
  *   workgroups of the dense exp kernel (128 rows x all columns each) in which a
  *   log_transform exponent exceeded 70 and was saturated there: fp32 cannot
  *   hold exp(y) beyond y ~ 88 where the fp64 reference still can, so the decoder
- *   is evaluated as exp(min(y,70)) - 1; 0 means the decoder was exact. */
+ *   is evaluated as exp(min(y,70)) - 1; 0 means the decoder was exact.
+ * Input domain (also of spmf_prior_async / spmf_step_begin): positive, finite fp32 parameters (v, w of
+ *   Bernoulli columns: any sign).  Every gradient entry whose yardstick -- the sum of the absolute additive
+ *   pieces of that entry, |d piece / d entry| over the prior's terms and the data term -- is below 1e37 is
+ *   returned finite and to 1e-5 of that yardstick: no intermediate of the prior's gradients exceeds the result
+ *   it goes into.  An entry whose yardstick is above has left fp32 (+-inf / NaN; d/d u_tau[k] sums over d, so
+ *   one such (d, k) takes the entry).  The twelve prior parts are accurate to 1e-12 of the sum of their
+ *   absolute terms (fp64 throughout, u_tau_scale / s_tau_scale / 0.1 as doubles); 'z' and 'x' likewise given
+ *   the accumulators.  Tested at the edge: tests/test_gpu_finish_edges.py, DESIGN.md 7a. */
 int spmf_finish(spmf_ctx* ctx, int S, int64_t n_rows_global,
                 double lgamma_sum_global, double prior_weight,
                 const float* const params[SPMF_NVARS], const float* eta,

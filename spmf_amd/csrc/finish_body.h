@@ -105,14 +105,31 @@ __device__ __forceinline__ double ipow(double b, int t) {
 // The log-densities (the energy PARTS) are evaluated in fp64: a part is a sum
 // of O(D*K) terms of either sign, so fp32 term error would be amplified by the
 // cancellation (seen: 2.6e-5 relative on a 4307-term part).  Gradients stay fp32.
-// HalfNormal(sig) at y: log-prob, d/dy, d/dsig
-__device__ __forceinline__ void halfnormal(float y, float sig, double& lp, float& gy, float& gs) {
-  const float is = frcp(sig);
+// HalfNormal(sig) at y with a CONSTANT scale (v: 0.1, w: 1): log-prob and d/dy.  The log-prob takes the
+// scale as a double: (double)0.1f is 1.5e-8 off 0.1, a systematic 3e-8 of the quadratic term of part 'v'.
+__device__ __forceinline__ void halfnormal(float y, double sigd, double& lp, float& gy) {
+  const float is = frcp((float)sigd);
+  const double qd = (double)y * fast_rcp(sigd);
+  lp = kHalfLog2OverPi - fast_log(sigd) - 0.5 * qd * qd;
+  gy = -(y * is) * is;
+}
+// (q^2 - 1) / x from q = y / sig and ix = 1 / x, x one factor of sig: d/dx of HalfNormal(sig)(y).  Formed as
+// q * (q * ix) - ix: no intermediate is larger than the result.  (q^2 - 1) / sig first and the other factors of
+// sig multiplied back on leaves the fp32 range where the gradient itself is far inside it (sig = 1e-12,
+// q = 1e15: 1e42 on the way to 1e36).
+__device__ __forceinline__ float hn_dscale(float q, float ix) { return fmaf(q, q * ix, -ix); }
+// HalfNormal(s1 * s2) at y: log-prob, d/dy, d/ds1, d/ds2.  The log-prob forms the scale in fp64 (an fp32
+// product is 6e-8 off, per term and of either sign).
+__device__ __forceinline__ void halfnormal2(float y, float s1, float s2, double& lp, float& gy, float& g1,
+                                            float& g2) {
+  const float is = frcp(s1 * s2);
   const float q = y * is;
-  const double qd = (double)y * fast_rcp((double)sig);
-  lp = kHalfLog2OverPi - fast_log((double)sig) - 0.5 * qd * qd;
+  const double sigd = (double)s1 * (double)s2;
+  const double qd = (double)y * fast_rcp(sigd);
+  lp = kHalfLog2OverPi - fast_log(sigd) - 0.5 * qd * qd;
   gy = -q * is;
-  gs = (q * q - 1.f) * is;
+  g1 = hn_dscale(q, frcp(s1));
+  g2 = hn_dscale(q, frcp(s2));
 }
 // SqrtInvGamma(1/2, scale=1/a) at y: log-prob, d/dy, d/da
 __device__ __forceinline__ void sqrt_ig(float y, float a, double& lp, float& gy, float& ga) {
@@ -123,13 +140,13 @@ __device__ __forceinline__ void sqrt_ig(float y, float a, double& lp, float& gy,
   gy = -2.f * iy + 2.f * t * iy;
   ga = -0.5f * ia + t * ia;
 }
-// InvGamma(1/2, beta) at a: log-prob, d/da
-__device__ __forceinline__ void ig_half(float a, float beta, float half_log_beta, double& lp,
-                                        float& ga) {
+// InvGamma(1/2, beta) at a: log-prob, d/da (beta = 1 / scale^2 comes from the host as a double: formed in fp32
+// it is 1e-7 off, and the log-prob carries it twice)
+__device__ __forceinline__ void ig_half(float a, double beta, double& lp, float& ga) {
   const float ia = frcp(a);
   const double ad = (double)a;
-  lp = 0.5 * fast_log((double)beta) - kLgammaHalf - 1.5 * fast_log(ad) - (double)beta * fast_rcp(ad);
-  ga = -1.5f * ia + beta * ia * ia;
+  lp = 0.5 * fast_log(beta) - kLgammaHalf - 1.5 * fast_log(ad) - beta * fast_rcp(ad);
+  ga = -1.5f * ia + (float)beta * ia * ia;
 }
 
 // tfd.Horseshoe(scale).log_prob (TFP's closed-form approximation of the HalfCauchy-Normal
@@ -194,7 +211,8 @@ __device__ __forceinline__ void parts_wave_sums(const double (&part)[12], int la
 struct FinishK {
   int D, K;
   double Bglob, lgamma_sum;
-  float u_tau_scale, s_tau_scale;
+  double u_tau_scale, s_tau_scale;   // doubles: they enter the fp64 parts (hs: the scales themselves)
+  double beta_u, beta_s;             // 1 / u_tau_scale^2, 1 / s_tau_scale^2: InvGamma scales of u_tau_a, s_tau_a
   double decay;
   float pw;
   const float* acc;
@@ -226,7 +244,8 @@ __device__ __forceinline__ void finish_body(const FinishK& a_, const int bx, con
                                             const int nby) {
   const int D = a_.D, K = a_.K;
   const double Bglob = a_.Bglob, lgamma_sum = a_.lgamma_sum;
-  const float u_tau_scale = a_.u_tau_scale, s_tau_scale = a_.s_tau_scale;
+  const double u_tau_scale = a_.u_tau_scale, s_tau_scale = a_.s_tau_scale;
+  const double beta_u = a_.beta_u, beta_s = a_.beta_s;
   const double decay = a_.decay;
   const float pw = a_.pw;
   const float* __restrict__ acc = a_.acc;
@@ -267,7 +286,7 @@ __device__ __forceinline__ void finish_body(const FinishK& a_, const int bx, con
   if (putau) putau += ((size_t)by * nbx + bx) * KP;
   __shared__ float tile[KP][FTD + 1];
   __shared__ float w1s[FTD], ietas[FTD], etas_[FTD], GAs[FTD];
-  __shared__ float zsum_s[KP], utau_s[KP], dec_s[KP], gutau_s[KP];
+  __shared__ float zsum_s[KP], sc_s[KP], iutau_s[KP], gutau_s[KP];   // sc: u_tau_k * decay^k, iutau: 1 / u_tau_k
   __shared__ double lsc_s[KP];     // log(u_tau_k * decay^k)
   __shared__ double scd_s[KP];     // u_tau_k * decay^k in fp64 (an fp32 product is a per-k systematic
                                    // error of the quadratic term: 8e-6 of part 'u' at K ~ 60)
@@ -365,12 +384,15 @@ __device__ __forceinline__ void finish_body(const FinishK& a_, const int bx, con
     // log_transform: the dense kernel already subtracted sum_b E_bd z_b from gV'
     // (mixed, code 3: still needed for the Poisson columns)
     zsum_s[t] = (!DATA || lik_exp(logt) || lik_bern(logt)) ? 0.f : (float)unpack(tail, kDaccHead + t);
-    utau_s[t] = hs ? u_tau_scale : c_ut;   // hs: scale = u_tau_scale * decay^k (c_ut is 1 for k >= K)
-    dec_s[t] = (float)ipow(decay, t);   // powf is ~1e-6 off at t~60: a systematic part error
+    // hs: scale = u_tau_scale * decay^k (c_ut is 1 for k >= K)
+    const double dec = ipow(decay, t);   // powf is ~1e-6 off at t~60: a systematic part error
+    sc_s[t] = c_ut * (float)dec;
+    iutau_s[t] = frcp(c_ut);
     gutau_s[t] = 0.f;
     if (PRIOR) {
-      lsc_s[t] = fast_log((double)utau_s[t]) + (double)t * fast_log(decay);
-      scd_s[t] = (double)utau_s[t] * ipow(decay, t);
+      const double utd = hs ? u_tau_scale : (double)c_ut;
+      lsc_s[t] = fast_log(utd) + (double)t * fast_log(decay);
+      scd_s[t] = utd * dec;
     }
   }
   if (t < FTD) {
@@ -412,22 +434,23 @@ __device__ __forceinline__ void finish_body(const FinishK& a_, const int bx, con
         G.p[U_][i] = du + pw * (float)dlp;
       } else if (PRIOR) {
         const float ue = in_ue[it], ua = in_ua[it];
-        const float sc = utau_s[k] * dec_s[k];
+        const float sc = sc_s[k], iut = iutau_s[k];
         // the three log-densities share their fp64 logs (software fp64 log is what
         // this kernel's time goes to): log sig = log ue + log(utau_k dec_k)
         const double Lue = fast_log((double)ue), Lua = fast_log((double)ua);
         const float sig = ue * sc, is = frcp(sig), q = u * is;
         const double qd = (double)u * fast_rcp((double)ue * scd_s[k]);
         part[U_] += kHalfLog2OverPi - (Lue + lsc_s[k]) - 0.5 * qd * qd;
-        const float gy = -q * is, gs = (q * q - 1.f) * is;
-        G.p[U_][i] = du + pw * gy;
-        gut = pw * gs * ue * dec_s[k];
         const float iy = frcp(ue), ia = frcp(ua);
+        // d/d u_eta and d/d u_tau of HalfNormal(sig)(u) are (q^2 - 1) / u_eta and (q^2 - 1) / u_tau (hn_dscale)
+        const float gy = -q * is, gs_e = hn_dscale(q, iy);
+        G.p[U_][i] = du + pw * gy;
+        gut = pw * hn_dscale(q, iut);
         const float tt = ia * iy * iy;                       // 1/(ua ue^2)
         part[UETA_] += -0.5 * Lua - kLgammaHalf - 2.0 * Lue
                        - fast_rcp((double)ua * (double)ue * (double)ue) + kLog2;
         const float gy2 = -2.f * iy + 2.f * tt * iy, ga2 = -0.5f * ia + tt * ia;
-        G.p[UETA_][i] = pw * (gs * sc + gy2);
+        G.p[UETA_][i] = pw * (gs_e + gy2);
         part[UETAA_] += -kLgammaHalf - 1.5 * Lua - fast_rcp((double)ua);   // InvGamma(1/2, 1)
         const float ga3 = -1.5f * ia + ia * ia;
         G.p[UETAA_][i] = pw * (ga2 + ga3);
@@ -489,8 +512,8 @@ __device__ __forceinline__ void finish_body(const FinishK& a_, const int bx, con
       if (PRIOR) {
         const float v = in_v[it];
         double lp;
-        float gy, gs;
-        halfnormal(v, 0.1f, lp, gy, gs);
+        float gy;
+        halfnormal(v, 0.1, lp, gy);
         if (bern_s[dl]) lp -= kLog2;   // Bernoulli column: v ~ Normal(0,.1) (bernoulli.py:187-200)
         part[V_] += (double)lp;
         G.p[V_][i] = dv + pw * gy;
@@ -504,24 +527,23 @@ __device__ __forceinline__ void finish_body(const FinishK& a_, const int bx, con
   if (VSPREAD) {
     if (von) {
       double lp, a_lp, c_lp;
-      float gy, gs, a_gy, a_ga, c_ga;
+      float gy, gs_e, gs_t, a_gy, a_ga, c_ga;
       if (vg < 2) {                    // row vg of s, s_eta, s_eta_a
-        halfnormal(v_a, v_b * v_st, lp, gy, gs);
+        halfnormal2(v_a, v_b, v_st, lp, gy, gs_e, gs_t);
         sqrt_ig(v_b, v_c, a_lp, a_gy, a_ga);
-        ig_half(v_c, 1.f, 0.f, c_lp, c_ga);
+        ig_half(v_c, 1.0, c_lp, c_ga);
         part[S_] += lp;
         part[SETA_] += a_lp;
         part[SETAA_] += c_lp;
         G.p[S_][vrow + vd] = pw * gy;
-        G.p[SETA_][vrow + vd] = pw * (gs * v_st + a_gy);
+        G.p[SETA_][vrow + vd] = pw * (gs_e + a_gy);
         G.p[SETAA_][vrow + vd] = pw * (a_ga + c_ga);
-        xs_s[vg][vdl] = gs * v_b;      // d/d s_tau through this row's scale
+        xs_s[vg][vdl] = gs_t;          // d/d s_tau through this row's scale
       } else {                         // w, s_tau, s_tau_a
-        halfnormal(v_a, 1.f, lp, gy, gs);
+        halfnormal(v_a, 1.0, lp, gy);
         if (bern_s[vdl]) lp -= kLog2;   // Bernoulli column: w ~ Normal(0,1) (bernoulli.py:201-216)
         sqrt_ig(v_b, v_c, a_lp, a_gy, a_ga);
-        const float beta = 1.f / (s_tau_scale * s_tau_scale);
-        ig_half(v_c, beta, 0.5f * logf(beta), c_lp, c_ga);
+        ig_half(v_c, beta_s, c_lp, c_ga);
         part[W_] += lp;
         part[STAU_] += a_lp;
         part[STAUA_] += c_lp;
@@ -548,23 +570,23 @@ __device__ __forceinline__ void finish_body(const FinishK& a_, const int bx, con
     }
     if (PRIOR) {
       double lp;
-      float gy, gs;
-      halfnormal(w, 1.f, lp, gy, gs);
+      float gy;
+      halfnormal(w, 1.0, lp, gy);
       if (bern_s[t]) lp -= kLog2;     // Bernoulli column: w ~ Normal(0,1) (bernoulli.py:201-216)
       part[W_] += (double)lp;
       G.p[W_][d] = dw + pw * gy;
       if (hs) {
         double l0, g0, l1, g1;
-        abs_horseshoe((double)s0, (double)s_tau_scale, l0, g0);
-        abs_horseshoe((double)s1, (double)s_tau_scale, l1, g1);
+        abs_horseshoe((double)s0, s_tau_scale, l0, g0);
+        abs_horseshoe((double)s1, s_tau_scale, l1, g1);
         part[S_] += l0 + l1;
         G.p[S_][d] = ds0 + pw * (float)g0;
         G.p[S_][D + d] = ds1 + pw * (float)g1;
       } else {
       double lp0, lp1;
-      float gy0, gs0, gy1, gs1;
-      halfnormal(s0, se0 * stau, lp0, gy0, gs0);
-      halfnormal(s1, se1 * stau, lp1, gy1, gs1);
+      float gy0, ge0, gt0, gy1, ge1, gt1;
+      halfnormal2(s0, se0, stau, lp0, gy0, ge0, gt0);
+      halfnormal2(s1, se1, stau, lp1, gy1, ge1, gt1);
       part[S_] += (double)lp0 + (double)lp1;
       G.p[S_][d] = ds0 + pw * gy0;
       G.p[S_][D + d] = ds1 + pw * gy1;
@@ -573,19 +595,18 @@ __device__ __forceinline__ void finish_body(const FinishK& a_, const int bx, con
       sqrt_ig(se0, sa0, a_lp, a_gy, a_ga);
       sqrt_ig(se1, sa1, b_lp, b_gy, b_ga);
       part[SETA_] += (double)a_lp + (double)b_lp;
-      G.p[SETA_][d] = pw * (gs0 * stau + a_gy);
-      G.p[SETA_][D + d] = pw * (gs1 * stau + b_gy);
-      ig_half(sa0, 1.f, 0.f, c_lp, c_ga);
+      G.p[SETA_][d] = pw * (ge0 + a_gy);
+      G.p[SETA_][D + d] = pw * (ge1 + b_gy);
+      ig_half(sa0, 1.0, c_lp, c_ga);
       part[SETAA_] += (double)c_lp;
       G.p[SETAA_][d] = pw * (a_ga + c_ga);
-      ig_half(sa1, 1.f, 0.f, c_lp, c_ga);
+      ig_half(sa1, 1.0, c_lp, c_ga);
       part[SETAA_] += (double)c_lp;
       G.p[SETAA_][D + d] = pw * (b_ga + c_ga);
       sqrt_ig(stau, sta, a_lp, a_gy, a_ga);
       part[STAU_] += (double)a_lp;
-      G.p[STAU_][d] = pw * (gs0 * se0 + gs1 * se1 + a_gy);
-      const float beta = 1.f / (s_tau_scale * s_tau_scale);
-      ig_half(sta, beta, 0.5f * logf(beta), c_lp, c_ga);
+      G.p[STAU_][d] = pw * (gt0 + gt1 + a_gy);
+      ig_half(sta, beta_s, c_lp, c_ga);
       part[STAUA_] += (double)c_lp;
       G.p[STAUA_][d] = pw * (a_ga + c_ga);
       }
@@ -608,8 +629,7 @@ __device__ __forceinline__ void finish_body(const FinishK& a_, const int bx, con
         sqrt_ig(ut, uta, lp, gy, ga);
         part[UTAU_] += (double)lp;
         g += pw * gy;
-        const float beta = 1.f / (u_tau_scale * u_tau_scale);
-        ig_half(uta, beta, 0.5f * logf(beta), lp2, ga2);
+        ig_half(uta, beta_u, lp2, ga2);
         part[UTAUA_] += (double)lp2;
         G.p[UTAUA_][t] = pw * (ga + ga2);
       }
@@ -664,8 +684,10 @@ inline FinishK make_finish_k(const FinishArgs& a) {
   k.K = a.K;
   k.Bglob = (double)a.B_global;
   k.lgamma_sum = a.lgamma_sum;
-  k.u_tau_scale = (float)a.u_tau_scale;
-  k.s_tau_scale = (float)a.s_tau_scale;
+  k.u_tau_scale = a.u_tau_scale;
+  k.s_tau_scale = a.s_tau_scale;
+  k.beta_u = 1.0 / (a.u_tau_scale * a.u_tau_scale);
+  k.beta_s = 1.0 / (a.s_tau_scale * a.s_tau_scale);
   k.decay = a.decay;
   k.pw = (float)a.prior_weight;
   k.acc = a.acc;

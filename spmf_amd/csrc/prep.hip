@@ -29,7 +29,7 @@ constexpr int prep_td() { return KP > 128 ? 32 : 64; }
 // Grid: tile blocks [0, nt) form A', V', phi for TD columns each and zero a slice of the
 // step's accumulators (the zero fill used to be a launch of its own); the (KP+1)*kPrepSeg
 // blocks behind them are the SUM blocks: block (j, seg) owns the partial sum of
-// veta[j] = sum_d fl(eta_d v[j,d]) (row j of v is contiguous; j = KP: phisum) over column
+// veta[j] = sum_d eta_d v[j,d] (row j of v is contiguous; j = KP: phisum) over column
 // segment seg.  One writer per slot, fp64, fixed order: no atomics (313 blocks adding into
 // the same 33 doubles made this kernel 16 of its 22 us on C3), nothing to zero first,
 // bit-identical from run to run; the readers fold the segments (common.h prep_sum).
@@ -84,8 +84,8 @@ __device__ __forceinline__ void prep_body(const PrepK& a_, const int bx, const i
     if (dbias) dbias += sd * (size_t)D;
   }
   if (bx >= nt) {
-    // ---- sum block: one segment of one closed-form column sum, the same fp32 products the
-    // tiles store ----
+    // ---- sum block: one segment of one closed-form column sum, products and sum in fp64 (they go into the
+    // fp64 part 'x'; the fp32 products the tiles store are 6e-8 off each) ----
     const int j = (bx - nt) / kPrepSeg, seg = (bx - nt) % kPrepSeg;
     const int per = (D + kPrepSeg - 1) / kPrepSeg;
     const int d_lo = seg * per, d_hi = min(D, d_lo + per);
@@ -93,16 +93,12 @@ __device__ __forceinline__ void prep_body(const PrepK& a_, const int bx, const i
     if (j < K && v) {
       const float* vr = v + (size_t)j * D;
       for (int d = d_lo + t; d < d_hi; d += 256)
-        if (!(ctype && ctype[d])) {
-          const float p = vr[d] * eta[d];
-          acc += (double)p;
-        }
+        if (!(ctype && ctype[d])) acc += (double)vr[d] * (double)eta[d];
     } else if (j == KP && w) {
       for (int d = d_lo + t; d < d_hi; d += 256)
         if (!(ctype && ctype[d])) {
-          const float s0 = s[d], s1 = s[D + d];
-          const float p = eta[d] * (s1 / (s0 + s1)) * w[d];
-          acc += (double)p;
+          const double s0 = s[d], s1 = s[D + d];
+          acc += (double)eta[d] * (s1 / (s0 + s1)) * (double)w[d];
         }
     }
     const double tot = block_sum(acc, red);
