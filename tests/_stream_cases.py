@@ -17,6 +17,9 @@ import re
 import numpy as np
 import torch
 
+from oracle import spmf_oracle as O
+from _problems import _dense_model, _dense_problem
+
 T = torch.as_tensor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -78,7 +81,6 @@ def _bern_cols(lik, mask, D):
 
 def _oracle_scores(cfg, x, params, bern):
     """fp64 [B,D]: mean over the draws of the rate (Poisson column) / sigmoid(logit) (Bernoulli)."""
-    from oracle import spmf_oracle as O
     rate = O.log_likelihood_components(cfg, T(x), T(params["s"]), T(params["u"]), T(params["v"]),
                                        T(params["w"]))["rate"]
     if rate.dim() == 2:
@@ -90,7 +92,6 @@ def _oracle_scores(cfg, x, params, bern):
 @functools.lru_cache(maxsize=None)
 def _problem(lik, B, D, K, S, seed=None, density=0.3):
     """The problem of a case and its oracle scores, computed once and shared (read-only)."""
-    from test_gpu_dense import _dense_problem
     cfg, x, params, mask = _dense_problem(lik, B, D, K, S, 9100 + B + K if seed is None else seed,
                                           density=density)
     if lik in BERN_DAMP:
@@ -98,6 +99,76 @@ def _problem(lik, B, D, K, S, seed=None, density=0.3):
         params["w"] = params["w"] * BERN_DAMP[lik]
     score = _oracle_scores(cfg, x, params, _bern_cols(lik, mask, D))
     return cfg, x, params, mask, score
+
+
+# ---- predict's cases, which group_means and set_scores are held against too ------------------------------------
+# (B, D, K, S): the three shapes of test_gpu_topk.SHAPES -- ragged 64 x 64 blocks and 32 x 32 tiles, K padded
+# 3 -> 4, K = 16, K = 33 -> 64 (two K chunks)
+SHAPES = [(70, 45, 3, 2), (131, 197, 16, 7), (5, 333, 33, 3)]
+PNZ_DAMP = {70: 2.0 ** -8, 131: 2.0 ** -14, 5: 2.0 ** -16}      # by B of SHAPES
+OUTS = ("mean", "sd", "p_nonzero")
+
+
+def _bar(v, smax):
+    return 1e-5 * np.abs(v) + 1e-5 * smax
+
+
+def _lists(D):
+    """The column lists of a shape: all columns, one column, a seeded permutation, and min(D, 65) columns that
+    start D-1, 0, 0: a duplicate, a 64-block edge crossed, both ends touched."""
+    rng = np.random.default_rng(77 + D)
+    n = min(D, 65)
+    mixed = np.concatenate([[D - 1, 0, 0], rng.integers(0, D, size=n - 3)]).astype(np.int64)
+    return {"all": None, "one": np.array([D - 1]), "perm": rng.permutation(D), "dup": mixed}
+
+
+def _per_draw(cfg, x, params, bern):
+    """fp64 [S,B,D]: the oracle's rate and m_s of every draw."""
+    rate = O.log_likelihood_components(cfg, T(x), T(params["s"]), T(params["u"]), T(params["v"]),
+                                       T(params["w"]))["rate"]
+    if rate.dim() == 2:
+        rate = rate.unsqueeze(0)
+    m = torch.where(T(bern), torch.sigmoid(rate), rate)
+    return rate.numpy(), m.numpy()
+
+
+@functools.lru_cache(maxsize=None)
+def _case(lik, B, D, K, S):
+    """The problem of test_gpu_topk at this shape, its per-draw oracle values, the model and the full
+    prediction with all outputs; computed once and shared (read-only)."""
+    cfg, x, params, mask, score = _problem(lik, B, D, K, S)
+    bern = _bern_cols(lik, mask, D)
+    rate, ms = _per_draw(cfg, x, params, bern)
+    np.testing.assert_allclose(ms.mean(0), score, rtol=1e-12, atol=0)
+    m = _dense_model(lik, cfg, mask, 32)
+    full = m.predict({"counts": x}, draws=params, sd=True, p_nonzero=True)
+    assert set(full) == set(OUTS)
+    for n in OUTS:
+        assert full[n].dtype == torch.float32 and tuple(full[n].shape) == (B, D) and full[n].is_cuda, n
+    return dict(cfg=cfg, x=x, params=params, mask=mask, bern=bern, score=score, rate=rate, ms=ms, m=m, full=full)
+
+
+@functools.lru_cache(maxsize=None)
+def _damped_case(lik, B, D, K, S):
+    """poisson / mixed with u and w scaled by PNZ_DAMP[B]: rates small enough for P(x > 0) to say something."""
+    cfg, x, params, mask = _dense_problem(lik, B, D, K, S, 9100 + B + K)
+    params = dict(params)
+    params["u"] = params["u"] * PNZ_DAMP[B]
+    params["w"] = params["w"] * PNZ_DAMP[B]
+    bern = _bern_cols(lik, mask, D)
+    rate, ms = _per_draw(cfg, x, params, bern)
+    return dict(cfg=cfg, x=x, params=params, mask=mask, bern=bern, rate=rate, ms=ms)
+
+
+@functools.lru_cache(maxsize=None)
+def _points(nq, nr, K, self_case, shift=0.0):
+    """The seeded query and reference rows of the knn tests (fp32; self_case: one set)."""
+    rng = np.random.default_rng(7300 + nq + K)
+    R = rng.standard_normal((nr, K))
+    Q = R if self_case else rng.standard_normal((nq, K))
+    R32 = (R + shift).astype(np.float32)
+    Q32 = R32 if self_case else (Q + shift).astype(np.float32)
+    return Q32, R32
 
 
 def abi_call(entry, good):
@@ -249,3 +320,64 @@ def assert_shared_errors(lib, entry, good, need, pin_without_u, mixed_ctx_withou
     msg = lib.spmf_last_error(h).decode()
     assert str(need) in msg, msg
     return call
+
+
+# ---- spmf_knn and spmf_embed_rows: their own argument errors, asserted with and without a device ----------------
+KNN_ARGS = (("q", C.c_void_p), ("nq", C.c_int64), ("r", C.c_void_p), ("nr", C.c_int64), ("row_len", C.c_int),
+            ("k", C.c_int), ("flags", C.c_uint), ("self_offset", C.c_int64), ("idx", C.c_void_p),
+            ("dist", C.c_void_p), ("ptr", C.c_void_p), ("nbytes", C.c_size_t), ("stream", C.c_void_p))
+
+
+def knn_raw_call(good):
+    """-> call(**overrides): spmf_knn through a binding of its own with the arguments of ``good``."""
+    from spmf_amd import _lib
+    fn = C.CDLL(_lib.LIB_PATH).spmf_knn
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p] + [t for _, t in KNN_ARGS]
+
+    def call(**kw):
+        a = dict(good, **kw)
+        return fn(a["h"], *[a[n] for n, _ in KNN_ARGS])
+    return call
+
+
+def assert_knn_errors(lib, good, need, after=lambda: None):
+    """The error contract of spmf_knn; every call here returns before a launch or a memset, and ``after`` is
+    run behind each (the GPU file checks its sentinels there)."""
+    call, h = knn_raw_call(good), good["h"]
+
+    def refused(code, **kw):
+        assert call(**kw) == code, kw
+        assert lib.spmf_last_error(h).decode().startswith("knn: "), lib.spmf_last_error(h).decode()
+        after()
+    for k in (0, 65, -3):
+        refused(-1, k=k)
+    for row_len in (0, 257, -1):
+        refused(-1, row_len=row_len)
+    refused(-1, flags=2)
+    refused(-1, flags=3)
+    assert "flag" in lib.spmf_last_error(h).decode()
+    refused(-1, nr=2 ** 31)
+    assert "int32" in lib.spmf_last_error(h).decode()
+    refused(-1, nq=-1)
+    refused(-1, nr=-1)
+    refused(-1, self_offset=-2)
+    for name in ("q", "r", "idx", "dist", "ptr"):
+        refused(-1, **{name: None})
+    refused(-1, ptr=good["ptr"] + 4)
+    assert "aligned" in lib.spmf_last_error(h).decode()
+    refused(-3, nbytes=need - 256)
+    assert str(need) in lib.spmf_last_error(h).decode()
+    refused(-3, nq=0, nbytes=0)             # errors come before the empty return
+    assert call(h=None) == -1
+
+
+def assert_embed_own_errors(lib, call, good, after=lambda: None):
+    """The argument errors of spmf_embed_rows beyond the draw stage's; ``call`` is the raw call of ``good``
+    (abi_call), every call returns before a launch and ``after`` is run behind each."""
+    assert call(mean=None) == -1
+    after()
+    one = good["sd"] if good["sd"] is not None else 0x6000000
+    assert call(S=1, sd=one) == -1
+    assert "sd_out" in lib.spmf_last_error(good["h"]).decode()
+    after()

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from oracle import spmf_oracle as O
-from test_gpu_parity import build_model, make_problem
+from _problems import LIKELIHOODS, _dense_model, _dense_problem, build_model, make_problem
 
 pytestmark = pytest.mark.gpu
 T = torch.as_tensor
@@ -42,65 +42,6 @@ def test_log_likelihood_components_dense(K, logt):
     g1 = m.log_likelihood_components(s=one["s"], u=one["u"], v=one["v"], w=one["w"],
                                      data={"counts": x})
     assert tuple(g1["rate"].shape) == (70, 45)
-
-
-LIKELIHOODS = ("poisson", "poisson_log", "bernoulli", "bernoulli_log", "mixed")
-
-
-def _dense_problem(lik, B, D, K, S, seed, density=0.3, xmax=2.0, x=None):
-    """One batch, its oracle configuration and fp32-exact parameters for a likelihood code of
-    dense_ll.hip: 0 Poisson/linear, 1 Poisson + log_transform, 2 Bernoulli, 4 Bernoulli +
-    log_transform, 3 mixed (every third column Bernoulli, so both 64-column blocks of a
-    D > 64 batch hold some).  With log_transform v is scaled so that the largest exponent is 8."""
-    rng = np.random.default_rng(seed)
-    if x is None:
-        x = ((rng.random((B, D)) < density) * (1 + rng.poisson(xmax, size=(B, D)))).astype(np.float64)
-    logt = lik.endswith("_log")
-    mask = None
-    if lik.startswith("bernoulli"):
-        x = (x > 0).astype(np.float64)
-        cfg = O.OracleConfig(latent_dim=K, feature_dim=D, likelihood="bernoulli", scale_rows=False,
-                             log_transform=logt)
-    elif lik == "mixed":
-        mask = np.arange(D) % 3 == 1
-        x[:, mask] = x[:, mask] > 0
-        cfg = O.OracleConfig(latent_dim=K, feature_dim=D, likelihood="mixed",
-                             extra={"bernoulli_columns": mask})
-    else:
-        cfg = O.OracleConfig(latent_dim=K, feature_dim=D, log_transform=logt,
-                             u_tau_scale=1.0 / math.sqrt(B * D))
-    cfg.eta_i = T(rng.uniform(0.5, 3.0, size=(1, D)))
-    cfg.xi_u_global = float(rng.uniform(2.0, 6.0))
-    params = O.random_params(cfg, S, seed + 1, fp32_exact=True)
-    if mask is not None or lik.startswith("bernoulli"):
-        # logits of both signs; the Poisson columns of a mixed model keep their positive intercept
-        cols = mask if mask is not None else np.ones(D, dtype=bool)
-        params["w"][..., cols] -= 1.0
-    if logt:
-        z = O.encode(cfg, T(x), T(params["u"]), T(params["s"]))
-        top = float((torch.matmul(z, T(params["v"])) * cfg.eta_i).max())
-        if top > 0:
-            params["v"] = params["v"] * (7.99 / top)
-    for k in ("v", "w"):
-        params[k] = params[k].astype(np.float32).astype(np.float64)
-    return cfg, x, params, mask
-
-
-def _dense_model(lik, cfg, mask, panel_rows):
-    from spmf_amd import BernoulliFactorization, MixedFactorization, PoissonFactorization
-    K, D = cfg.latent_dim, cfg.feature_dim
-    if lik.startswith("bernoulli"):
-        m = BernoulliFactorization(latent_dim=K, feature_dim=D, log_transform=cfg.log_transform,
-                                   column_norms=cfg.eta_i, device="cuda", panel_rows=panel_rows)
-    elif lik == "mixed":
-        m = MixedFactorization(mask, latent_dim=K, column_norms=cfg.eta_i, initialize_distributions=False,
-                               device="cuda", panel_rows=panel_rows)
-    else:
-        m = PoissonFactorization(latent_dim=K, feature_dim=D, u_tau_scale=cfg.u_tau_scale,
-                                 log_transform=cfg.log_transform, column_norms=cfg.eta_i,
-                                 initialize_distributions=False, device="cuda", panel_rows=panel_rows)
-    m.xi_u_global = cfg.xi_u_global
-    return m
 
 
 def _assert_cells(got, ref, shape, tag=""):

@@ -140,13 +140,9 @@ def test_deterministic_minibatch_training_under_graph_replay_repeats_exactly():
 def test_deterministic_mode_against_the_oracle(B, D, K, S, density, scale_rows, panel_rows):
     """The same entry-wise bar as the default path (tests/test_gpu_parity.py): 14 parts to 1e-5, every gradient
     entry to 1e-5 of the sum of the absolute contributions to it, against the fp64 oracle."""
-    from oracle import spmf_oracle as O
-    from test_gpu_parity import assert_close_grads, assert_close_parts, build_model, make_problem
+    from _energy_check import check_dense_oracle
+    from _problems import build_model, make_problem
     cfg, x, params = make_problem(B, D, K, S, 4000 + B + D + K, density, scale_rows)
-    parts_ref, grads_ref, _ = O.energy_and_grads(cfg, x, params)
     m = build_model(cfg, panel_rows)
     m.deterministic = True
-    parts, grads, nnf = m.energy_and_grads({"counts": x}, params)
-    assert float(nnf.sum()) == 0
-    assert_close_parts(parts, parts_ref)
-    assert_close_grads(grads, grads_ref, O.energy_grad_scales(cfg, x, params), tag="deterministic")
+    check_dense_oracle(m, cfg, x, params, tag="deterministic")

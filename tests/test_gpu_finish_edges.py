@@ -29,6 +29,7 @@ import torch
 import _finish_table as F
 from _gradcheck import assert_grads_entrywise, worst_entry
 from oracle import spmf_oracle as O
+from _problems import bernoulli_problem, mixed_problem, poisson_log_problem
 
 pytestmark = pytest.mark.gpu
 
@@ -256,20 +257,17 @@ def test_other_likelihood_codes(kind):
     from spmf_amd import BernoulliFactorization, MixedFactorization, PoissonFactorization
     B, D, K, S = 40, 33, 5, 2
     if kind == "log_transform":
-        import test_gpu_logtransform as TL
-        cfg, x, params = TL.problem(B, D, K, S, 71, 0.3)
+        cfg, x, params = poisson_log_problem((B, D, 0.3), K, S, 71)
         params["v"] = F.f32(params["v"])
         m = PoissonFactorization(latent_dim=K, feature_dim=D, u_tau_scale=cfg.u_tau_scale, log_transform=True,
                                  column_norms=cfg.eta_i, initialize_distributions=False, device="cuda", panel_rows=32)
     elif kind == "bernoulli":
-        import test_gpu_bernoulli as TB
-        cfg, x, params = TB.problem(B, D, K, S, 72, 0.3)
+        cfg, x, params = bernoulli_problem((B, D, 0.3), K, S, 72)
         assert (params["v"] < 0).any() and (params["w"] < 0).all()
         m = BernoulliFactorization(latent_dim=K, feature_dim=D, u_tau_scale=cfg.u_tau_scale, column_norms=cfg.eta_i,
                                    device="cuda", panel_rows=32)
     else:
-        import test_gpu_mixed as TM
-        cfg, x, params, mask = TM.problem(B, D, K, S, 73, 0.3)
+        cfg, x, params, mask = mixed_problem((B, D, 0.3), K, S, 73)
         assert (mask == (np.arange(D) % 2 == 1)).all() and (params["w"][..., mask] < 0).all()
         assert (params["v"][..., mask] < 0).any()
         m = MixedFactorization(mask, latent_dim=K, u_tau_scale=cfg.u_tau_scale, column_norms=cfg.eta_i,

@@ -21,9 +21,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_dense import LIKELIHOODS, _dense_model, _dense_problem
-from test_gpu_parity import build_model, make_problem
-from test_gpu_predict import SHAPES, _bar, _case, _damped_case, _lists
+from _problems import LIKELIHOODS, _dense_model, _dense_problem, build_model, make_problem
+from _stream_cases import SHAPES, _bar, _case, _damped_case, _lists
 
 pytestmark = pytest.mark.gpu
 T = torch.as_tensor

@@ -29,9 +29,9 @@ import pytest
 import torch
 
 from oracle import spmf_oracle as O
-from _stream_cases import _problem, assert_shared_errors, gpu_good_call
-from test_gpu_dense import _dense_model
-from test_knn_host import assert_embed_own_errors, assert_knn_errors, knn_raw_call
+from _problems import _dense_model
+from _stream_cases import (_points, _problem, assert_embed_own_errors, assert_knn_errors, assert_shared_errors,
+                           gpu_good_call, knn_raw_call)
 
 pytestmark = pytest.mark.gpu
 T = torch.as_tensor
@@ -53,16 +53,6 @@ def _bits(t):
 def _model():
     from spmf_amd import PoissonFactorization
     return PoissonFactorization(latent_dim=3, feature_dim=8, initialize_distributions=False, device="cuda")
-
-
-@functools.lru_cache(maxsize=None)
-def _points(nq, nr, K, self_case, shift=0.0):
-    rng = np.random.default_rng(7300 + nq + K)
-    R = rng.standard_normal((nr, K))
-    Q = R if self_case else rng.standard_normal((nq, K))
-    R32 = (R + shift).astype(np.float32)
-    Q32 = R32 if self_case else (Q + shift).astype(np.float32)
-    return Q32, R32
 
 
 def _oracle_view(Q, R, k, metric, self_off):

@@ -7,28 +7,11 @@ import pytest
 import torch
 
 from oracle import spmf_oracle as O
+from _energy_check import check_dense_oracle
 from _gradcheck import assert_grads_entrywise
+from _problems import build_model, poisson_log_problem
 
 pytestmark = pytest.mark.gpu
-
-
-def problem(B, D, K, S, seed, density, scale_rows=True):
-    rng = np.random.default_rng(seed)
-    x = ((rng.random((B, D)) < density) * (1 + rng.poisson(2.0, size=(B, D)))).astype(np.float64)
-    if B > 4 and D > 4:
-        x[1, :] = 0
-        x[:, 2] = 0
-    cfg = O.OracleConfig(latent_dim=K, feature_dim=D, scale_rows=scale_rows, log_transform=True,
-                         u_tau_scale=1.0 / math.sqrt(B * D))
-    cfg.eta_i = torch.as_tensor(rng.uniform(0.5, 3.0, size=(1, D)))
-    cfg.xi_u_global = float(rng.uniform(4.0, 8.0))
-    params = O.random_params(cfg, S, seed + 1, fp32_exact=True)
-    # keep exp(<z, eta v>) in a sane range: rescale v so the largest exponent is 8
-    T = torch.as_tensor
-    z = O.encode(cfg, T(x), T(params["u"]), T(params["s"]))
-    ymax = float((torch.matmul(z, T(params["v"])) * cfg.eta_i).max())
-    params["v"] *= 8.0 / ymax
-    return cfg, x, params
 
 
 CASES = [(37, 23, 3, 2, 0.3, True), (150, 90, 8, 1, 0.1, True), (260, 200, 32, 1, 0.05, True),
@@ -41,20 +24,10 @@ def test_log_transform_energy_and_grads(monkeypatch, B, D, K, S, density, scale_
     """Both dense paths (read at spmf_ctx_create): the bf16x3 kernels (csrc/dense3.hip: expdot3 at K padded
     to 64, the sigdot3 family's exp form at K padded to 32) and the exact-f32 MFMA kernels; the last case
     spans several Q tiles and chunks."""
-    from spmf_amd import PoissonFactorization
     monkeypatch.setenv("SPMF_DENSE_BF16X3", bf16x3)
-    cfg, x, params = problem(B, D, K, S, 500 + B + K, density, scale_rows)
-    pref, gref, _ = O.energy_and_grads(cfg, x, params)
-    m = PoissonFactorization(latent_dim=K, feature_dim=D, u_tau_scale=cfg.u_tau_scale,
-                             scale_rows=scale_rows, log_transform=True, column_norms=cfg.eta_i,
-                             initialize_distributions=False, device="cuda", panel_rows=64)
-    m.xi_u_global = cfg.xi_u_global
-    parts, grads, nnf = m.energy_and_grads({"counts": x}, params)
-    assert float(nnf.sum()) == 0
-    for k, r in pref.items():
-        np.testing.assert_allclose(parts[k].cpu().numpy(), r.numpy(), rtol=1e-5, atol=1e-5,
-                                   err_msg=k)
-    assert_grads_entrywise(grads, gref, O.energy_grad_scales(cfg, x, params), 1e-5, "")
+    cfg, x, params = poisson_log_problem((B, D, density), K, S, 500 + B + K, scale_rows)
+    m = build_model(cfg, 64)
+    check_dense_oracle(m, cfg, x, params)
     T = torch.as_tensor
     z = m.encode(x, u=T(params["u"]), s=T(params["s"])).cpu().numpy()
     zr = O.encode(cfg, T(x), T(params["u"]), T(params["s"])).numpy()
@@ -65,15 +38,11 @@ def test_log_transform_energy_and_grads(monkeypatch, B, D, K, S, density, scale_
 def test_two_launch_form_still_matches_oracle(monkeypatch, B, D, K, S):
     """SPMF_DENSE_E_ONCE=0 (read at spmf_ctx_create): the form that recomputes E in a second
     exp launch instead of keeping it in HBM -- same oracle, same contract."""
-    from spmf_amd import PoissonFactorization
     monkeypatch.setenv("SPMF_DENSE_E_ONCE", "0")
     monkeypatch.setenv("SPMF_DENSE_BF16X3", "0")        # (a switch of the exact-f32 kernels)
-    cfg, x, params = problem(B, D, K, S, 900 + B + K, 0.05)
+    cfg, x, params = poisson_log_problem((B, D, 0.05), K, S, 900 + B + K)
     pref, gref, _ = O.energy_and_grads(cfg, x, params)
-    m = PoissonFactorization(latent_dim=K, feature_dim=D, u_tau_scale=cfg.u_tau_scale,
-                             log_transform=True, column_norms=cfg.eta_i,
-                             initialize_distributions=False, device="cuda", panel_rows=64)
-    m.xi_u_global = cfg.xi_u_global
+    m = build_model(cfg, 64)
     parts, grads, nnf = m.energy_and_grads({"counts": x}, params)
     for k, r in pref.items():
         np.testing.assert_allclose(parts[k].cpu().numpy(), r.numpy(), rtol=1e-5, atol=1e-5, err_msg=k)
@@ -85,15 +54,12 @@ def test_e_buffer_in_several_row_chunks(monkeypatch):
     that keep E: SPMF_DENSE_BF16X3=0) in several chunks (at C4 scale the Python class sizes the buffer for
     ONE chunk, so the chunk loop is exercised here): 4000 rows with a 1 MiB cap = 3 chunks of
     1408 / 1408 / 1184 rows."""
-    from spmf_amd import PoissonFactorization, _lib
+    from spmf_amd import _lib
     monkeypatch.setenv("SPMF_DENSE_BF16X3", "0")
     B, D, K, S = 4000, 129, 64, 1
-    cfg, x, params = problem(B, D, K, S, 4321, 0.03)
+    cfg, x, params = poisson_log_problem((B, D, 0.03), K, S, 4321)
     pref, gref, _ = O.energy_and_grads(cfg, x, params)
-    m = PoissonFactorization(latent_dim=K, feature_dim=D, u_tau_scale=cfg.u_tau_scale,
-                             log_transform=True, column_norms=cfg.eta_i,
-                             initialize_distributions=False, device="cuda", panel_rows=512)
-    m.xi_u_global = cfg.xi_u_global
+    m = build_model(cfg, 512)
     lib, h = _lib.load(), m._handle()
     _lib.check(h, lib.spmf_ctx_set_e_cap(h, 1 << 20), "spmf_ctx_set_e_cap")
     assert (1 << 20) // (160 * 4) < B          # the cap really is below one chunk of all rows
@@ -104,27 +70,16 @@ def test_e_buffer_in_several_row_chunks(monkeypatch):
 
 
 def test_log_transform_randomised_sweep():
-    from spmf_amd import PoissonFactorization
     rng = np.random.default_rng(77)
     for case in range(12):
         B, D = int(rng.integers(2, 300)), int(rng.integers(2, 300))
         K, S = int(rng.integers(1, 65)), int(rng.integers(1, 3))
         density = float(rng.choice([0.03, 0.2, 0.8]))
         sr = bool(rng.integers(0, 2))
-        cfg, x, params = problem(B, D, K, S, 9000 + case, density, sr)
-        pref, gref, _ = O.energy_and_grads(cfg, x, params)
-        m = PoissonFactorization(latent_dim=K, feature_dim=D, u_tau_scale=cfg.u_tau_scale,
-                                 scale_rows=sr, log_transform=True, column_norms=cfg.eta_i,
-                                 initialize_distributions=False, device="cuda",
-                                 panel_rows=int(rng.choice([5, 64, 4096])))
-        m.xi_u_global = cfg.xi_u_global
-        parts, grads, nnf = m.energy_and_grads({"counts": x}, params)
+        cfg, x, params = poisson_log_problem((B, D, density), K, S, 9000 + case, sr)
+        m = build_model(cfg, int(rng.choice([5, 64, 4096])))
         tag = f"case {case}: B={B} D={D} K={K} S={S} dens={density} sr={sr}"
-        assert float(nnf.sum()) == 0, tag
-        for k, r in pref.items():
-            np.testing.assert_allclose(parts[k].cpu().numpy(), r.numpy(), rtol=1e-5, atol=1e-5,
-                                       err_msg=f"{tag} {k}")
-        assert_grads_entrywise(grads, gref, O.energy_grad_scales(cfg, x, params), 1e-5, tag)
+        check_dense_oracle(m, cfg, x, params, tag=tag)
 
 
 def test_log_transform_fit_smoke():
@@ -192,15 +147,11 @@ def test_bf16x3_dense_path_matches_oracle(monkeypatch, B, D, S, ymax, K):
     the yardstick (tools/b3_err.py) while this path, which keeps a1 b1 and
     the small partial products in separate accumulators, measured 6 - 8.5e-6; B, D off the
     32 / 64 / 256 tile edges; several Q chunks in the W-stationary launch (D = 1000)."""
-    from spmf_amd import PoissonFactorization
     monkeypatch.setenv("SPMF_DENSE_BF16X3", "1")
-    cfg, x, params = problem(B, D, K, S, 2900 + B + D, 0.05)
-    params["v"] *= ymax / 8.0                  # problem() scaled the largest exponent to 8
+    cfg, x, params = poisson_log_problem((B, D, 0.05), K, S, 2900 + B + D)
+    params["v"] *= ymax / 8.0                  # the recipe scaled the largest exponent to 8
     pref, gref, _ = O.energy_and_grads(cfg, x, params)
-    m = PoissonFactorization(latent_dim=K, feature_dim=D, u_tau_scale=cfg.u_tau_scale,
-                             log_transform=True, column_norms=cfg.eta_i,
-                             initialize_distributions=False, device="cuda", panel_rows=64)
-    m.xi_u_global = cfg.xi_u_global
+    m = build_model(cfg, 64)
     parts, grads, nnf = m.energy_and_grads({"counts": x}, params)
     assert float(nnf.sum()) == 0 and float(m.last_saturated.sum()) == 0
     for k, r in pref.items():
@@ -216,10 +167,7 @@ def test_bf16x3_dense_path_matches_oracle(monkeypatch, B, D, S, ymax, K):
                            1e-5 if ymax <= 45.0 else 1.5e-5, f"bf16x3 {B}x{D}")
     # and it agrees with the exact-f32 MFMA form of the same library far inside the contract
     monkeypatch.setenv("SPMF_DENSE_BF16X3", "0")
-    m2 = PoissonFactorization(latent_dim=K, feature_dim=D, u_tau_scale=cfg.u_tau_scale,
-                              log_transform=True, column_norms=cfg.eta_i,
-                              initialize_distributions=False, device="cuda", panel_rows=64)
-    m2.xi_u_global = cfg.xi_u_global
+    m2 = build_model(cfg, 64)
     parts2, grads2, _ = m2.energy_and_grads({"counts": x}, params)
     # (the two kernels are each within the contract of the oracle; at exponents of 45 - 60 both
     #  are a few 1e-6 from it, on either side)
@@ -238,15 +186,7 @@ def test_log_transform_on_the_lds_phi_row_launches_matches_oracle(B, D, S):
     stored-cell sweep 2 (the exp decoder keeps its two row launches: the fused row pass was slower on C4,
     profiles/r04_fused_rows_c4.txt) -- on >= 4096 rows, where the row launches take the 512-thread LDS-phi
     shapes that the small batches above do not reach.  Against the oracle at the contract."""
-    from spmf_amd import PoissonFactorization
     K = 64
-    cfg, x, params = problem(B, D, K, S, 4100 + D, 0.03)
-    pref, gref, _ = O.energy_and_grads(cfg, x, params)
-    m = PoissonFactorization(latent_dim=K, feature_dim=D, u_tau_scale=cfg.u_tau_scale, log_transform=True,
-                             column_norms=cfg.eta_i, initialize_distributions=False, device="cuda")
-    m.xi_u_global = cfg.xi_u_global
-    parts, grads, nnf = m.energy_and_grads({"counts": x}, params)
-    assert float(nnf.sum()) == 0
-    for k, r in pref.items():
-        np.testing.assert_allclose(parts[k].cpu().numpy(), r.numpy(), rtol=1e-5, atol=1e-5, err_msg=k)
-    assert_grads_entrywise(grads, gref, O.energy_grad_scales(cfg, x, params), 1e-5, "exp decoder, LDS-phi rows")
+    cfg, x, params = poisson_log_problem((B, D, 0.03), K, S, 4100 + D)
+    m = build_model(cfg, None)
+    check_dense_oracle(m, cfg, x, params, tag="exp decoder, LDS-phi rows")

@@ -8,25 +8,11 @@ import pytest
 import torch
 
 from oracle import spmf_oracle as O
+from _energy_check import check_dense_oracle
 from _gradcheck import assert_grads_entrywise
+from _problems import bernoulli_problem, likelihood_model, mixed_problem
 
 pytestmark = pytest.mark.gpu
-
-
-def problem(B, D, K, S, seed, density, scale_rows=True):
-    rng = np.random.default_rng(seed)
-    mask = (np.arange(D) % 2 == 1)                       # 50/50 columns, as config 5
-    x = ((rng.random((B, D)) < density) * (1 + rng.poisson(2.0, size=(B, D)))).astype(np.float64)
-    x[:, mask] = (x[:, mask] > 0)
-    cfg = O.OracleConfig(latent_dim=K, feature_dim=D, scale_rows=scale_rows, likelihood="mixed",
-                         u_tau_scale=1.0 / math.sqrt(B * D), extra={"bernoulli_columns": mask})
-    cfg.eta_i = torch.as_tensor(rng.uniform(0.5, 2.0, size=(1, D)))
-    cfg.xi_u_global = float(rng.uniform(2.0, 6.0))
-    params = O.random_params(cfg, S, seed + 1, fp32_exact=True)
-    sign = np.where(mask, rng.choice([-1.0, 1.0], size=D), 1.0)
-    params["v"] = params["v"] * sign[None, None, :]
-    params["w"] = params["w"] * np.where(mask, -3.0, 1.0)[None, None, :]
-    return cfg, x, params, mask
 
 
 @pytest.mark.parametrize("bf16x3", ["1", "0"])
@@ -35,19 +21,10 @@ def problem(B, D, K, S, seed, density, scale_rows=True):
 def test_mixed_energy_and_grads(monkeypatch, B, D, K, S, density, sr, bf16x3):
     """Both dense paths of the sigmoid sums (read at spmf_ctx_create): the bf16x3 kernels with the fused
     row pass (csrc/dense3.hip sigdot3, default at K <= 32) and the exact-f32 MFMA kernels."""
-    from spmf_amd import MixedFactorization
     monkeypatch.setenv("SPMF_DENSE_BF16X3", bf16x3)
-    cfg, x, params, mask = problem(B, D, K, S, 800 + B + K, density, sr)
-    pref, gref, _ = O.energy_and_grads(cfg, x, params)
-    m = MixedFactorization(mask, latent_dim=K, u_tau_scale=cfg.u_tau_scale, scale_rows=sr,
-                           column_norms=cfg.eta_i, device="cuda", panel_rows=64)
-    m.xi_u_global = cfg.xi_u_global
-    parts, grads, nnf = m.energy_and_grads({"counts": x}, params)
-    assert float(nnf.sum()) == 0
-    for k, r in pref.items():
-        np.testing.assert_allclose(parts[k].cpu().numpy(), r.numpy(), rtol=1e-5, atol=1e-5,
-                                   err_msg=k)
-    assert_grads_entrywise(grads, gref, O.energy_grad_scales(cfg, x, params), 1e-5, "")
+    cfg, x, params, mask = mixed_problem((B, D, density), K, S, 800 + B + K, sr)
+    m = likelihood_model(cfg, 64)
+    check_dense_oracle(m, cfg, x, params)
 
 
 @pytest.mark.parametrize("bf16x3", ["0", "1"])
@@ -58,19 +35,15 @@ def test_sigmoid_e_buffer_in_several_row_chunks(monkeypatch, kind, bf16x3):
     masked there), and -- mixed -- the scatter through the compacted Bernoulli column list.
     bf16x3 = 1: the same problem on the sigdot3 kernels (no E buffer): row and column counts off the
     128 / 256 tile edges, several Q chunks with float-atomic epilogues, the compacted column list."""
-    from spmf_amd import BernoulliFactorization, MixedFactorization, _lib
+    from spmf_amd import _lib
     monkeypatch.setenv("SPMF_DENSE_BF16X3", bf16x3)
     B, D, K, S = 3001, 90, 32, 1
     if kind == "mixed":
-        cfg, x, params, mask = problem(B, D, K, S, 5150, 0.04, True)
-        m = MixedFactorization(mask, latent_dim=K, u_tau_scale=cfg.u_tau_scale, scale_rows=True,
-                               column_norms=cfg.eta_i, device="cuda", panel_rows=512)
-        m.xi_u_global = cfg.xi_u_global
+        cfg, x, params, mask = mixed_problem((B, D, 0.04), K, S, 5150, True)
+        m = likelihood_model(cfg, 512)
     else:
-        import test_gpu_bernoulli as TB
-        cfg, x, params = TB.problem(B, D, K, S, 5151, 0.04)
-        m = BernoulliFactorization(latent_dim=K, feature_dim=D, u_tau_scale=cfg.u_tau_scale,
-                                   column_norms=cfg.eta_i, device="cuda", panel_rows=512)
+        cfg, x, params = bernoulli_problem((B, D, 0.04), K, S, 5151)
+        m = likelihood_model(cfg, 512)
     pref, gref, _ = O.energy_and_grads(cfg, x, params)
     lib, h = _lib.load(), m._handle()
     _lib.check(h, lib.spmf_ctx_set_e_cap(h, 1 << 20), "spmf_ctx_set_e_cap")   # 2 chunks of 1536 / 1465 rows

@@ -3,59 +3,15 @@ same seeded inputs.  Tolerance (north_star): 1e-5 relative, fp32 kernels.
 Gradients are compared ENTRY by entry against 1e-5 of the sum of the absolute
 contributions to that entry (tests/_gradcheck.py, oracle.energy_grad_scales):
 entries of a sparse gradient cancel to ~0, so the yardstick is what was added up."""
-import math
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import spmf_oracle as O
-from _gradcheck import assert_grads_entrywise
+from _energy_check import RTOL, assert_close_grads, assert_close_parts, check_dense_oracle
+from _problems import _config, build_model, cap_exponents, make_problem
 
 pytestmark = pytest.mark.gpu
-
-RTOL = 1e-5
-
-
-def make_problem(B, D, K, S, seed, density, scale_rows=True, empty=True, xmax=2.0):
-    rng = np.random.default_rng(seed)
-    mask = rng.random((B, D)) < density
-    x = (mask * (1 + rng.poisson(xmax, size=(B, D)))).astype(np.float64)
-    if empty and B > 4 and D > 4:
-        x[1, :] = 0.0
-        x[:, 2] = 0.0
-        x[B - 1, :] = 0.0
-    cfg = O.OracleConfig(latent_dim=K, feature_dim=D, scale_rows=scale_rows,
-                         u_tau_scale=1.0 / math.sqrt(B * D))
-    cfg.eta_i = torch.as_tensor(rng.uniform(0.5, 3.0, size=(1, D)))
-    cfg.xi_u_global = float(rng.uniform(2.0, 6.0))
-    params = O.random_params(cfg, S, seed + 1, fp32_exact=True)
-    return cfg, x, params
-
-
-def build_model(cfg, panel_rows=64):
-    from spmf_amd import PoissonFactorization
-    m = PoissonFactorization(
-        latent_dim=cfg.latent_dim, feature_dim=cfg.feature_dim,
-        u_tau_scale=cfg.u_tau_scale, s_tau_scale=cfg.s_tau_scale,
-        symmetry_breaking_decay=cfg.symmetry_breaking_decay,
-        scale_rows=cfg.scale_rows, log_transform=cfg.log_transform, column_norms=cfg.eta_i,
-        initialize_distributions=False, device="cuda", panel_rows=panel_rows)
-    m.xi_u_global = cfg.xi_u_global
-    return m
-
-
-def assert_close_parts(got, ref, rtol=RTOL):
-    for k in ref:
-        g = got[k].detach().cpu().numpy()
-        r = ref[k].numpy()
-        np.testing.assert_allclose(g, r, rtol=rtol, atol=rtol, err_msg=f"part {k}")
-
-
-def assert_close_grads(got, ref, scales, rtol=RTOL, tag=""):
-    """Entry-wise: |hip - oracle| <= rtol * sum of |contributions| to that entry."""
-    assert_grads_entrywise(got, ref, scales, rtol, tag)
-
 
 CASES = [
     # B,   D,   K,  S, density, scale_rows, panel_rows
@@ -74,12 +30,7 @@ CASES = [
 @pytest.mark.parametrize("B,D,K,S,density,scale_rows,panel_rows", CASES)
 def test_energy_parts_and_grads_match_oracle(B, D, K, S, density, scale_rows, panel_rows):
     cfg, x, params = make_problem(B, D, K, S, 1000 + B + D + K, density, scale_rows)
-    parts_ref, grads_ref, _ = O.energy_and_grads(cfg, x, params)
-    m = build_model(cfg, panel_rows)
-    parts, grads, nnf = m.energy_and_grads({"counts": x}, params)
-    assert float(nnf.sum()) == 0
-    assert_close_parts(parts, parts_ref)
-    assert_close_grads(grads, grads_ref, O.energy_grad_scales(cfg, x, params))
+    check_dense_oracle(build_model(cfg, panel_rows), cfg, x, params)
 
 
 @pytest.mark.parametrize("K,log_transform", [(32, False), (16, False), (64, False), (64, True)])
@@ -95,21 +46,10 @@ def test_row_lengths_around_the_chunk_boundaries(K, log_transform):
         n = lengths[b % len(lengths)]
         cols = rng.choice(D, size=n, replace=False)
         x[b, cols] = 1 + rng.poisson(1.5, size=n)
-    cfg = O.OracleConfig(latent_dim=K, feature_dim=D, scale_rows=True, log_transform=log_transform,
-                         u_tau_scale=1.0 / math.sqrt(B * D))
-    cfg.eta_i = torch.as_tensor(rng.uniform(0.5, 3.0, size=(1, D)))
-    cfg.xi_u_global = float(rng.uniform(2.0, 6.0))
-    params = O.random_params(cfg, S, 78 + K, fp32_exact=True)
+    cfg, params = _config(x, K, 77 + K, S, log_transform=log_transform, rng=rng)
     if log_transform:   # keep exp(<z, eta v>) in range: the largest exponent is 8
-        T = torch.as_tensor
-        z = O.encode(cfg, T(x), T(params["u"]), T(params["s"]))
-        params["v"] *= 8.0 / float((torch.matmul(z, T(params["v"])) * cfg.eta_i).max())
-    parts_ref, grads_ref, _ = O.energy_and_grads(cfg, x, params)
-    m = build_model(cfg, 1024)
-    parts, grads, nnf = m.energy_and_grads({"counts": x}, params)
-    assert float(nnf.sum()) == 0
-    assert_close_parts(parts, parts_ref)
-    assert_close_grads(grads, grads_ref, O.energy_grad_scales(cfg, x, params))
+        cap_exponents(cfg, x, params, 8.0)
+    check_dense_oracle(build_model(cfg, 1024), cfg, x, params)
 
 
 @pytest.mark.parametrize("kind", ["fractional", "large"])
@@ -130,12 +70,7 @@ def test_counts_outside_the_packed_format_take_the_canonical_streams(kind, monke
     assert sc.ent is None and sc.pc_ent is None
     ok = SparseCounts.from_any(np.round(np.minimum(x, 100.0)), "cuda", 1024)
     assert ok.ent is not None and ok.pc_ent is not None
-    parts_ref, grads_ref, _ = O.energy_and_grads(cfg, x, params)
-    m = build_model(cfg, 1024)
-    parts, grads, nnf = m.energy_and_grads({"counts": sc}, params)
-    assert float(nnf.sum()) == 0
-    assert_close_parts(parts, parts_ref)
-    assert_close_grads(grads, grads_ref, O.energy_grad_scales(cfg, x, params))
+    check_dense_oracle(build_model(cfg, 1024), cfg, x, params, batch={"counts": sc})
 
 
 @pytest.mark.parametrize("K,log_transform", [(32, False), (64, True)])
@@ -148,9 +83,7 @@ def test_packed_and_canonical_entry_streams_agree_bit_for_bit(K, log_transform, 
     cfg, x, params = make_problem(B, D, K, S, 99 + K, 0.25)
     cfg.log_transform = log_transform
     if log_transform:
-        T = torch.as_tensor
-        z = O.encode(cfg, T(x), T(params["u"]), T(params["s"]))
-        params["v"] *= 8.0 / float((torch.matmul(z, T(params["v"])) * cfg.eta_i).max())
+        cap_exponents(cfg, x, params, 8.0)
     monkeypatch.delenv("SPMF_PACKED_ENTRIES", raising=False)
     packed = SparseCounts.from_any(x, "cuda", 512)
     monkeypatch.setenv("SPMF_PACKED_ENTRIES", "0")
@@ -292,15 +225,8 @@ def test_randomised_shapes_sweep():
         scale_rows = bool(rng.integers(0, 2))
         panel_rows = int(rng.choice([1, 7, 64, 10_000]))
         cfg, x, params = make_problem(B, D, K, S, 5000 + case, density, scale_rows, empty=False)
-        pref, gref, _ = O.energy_and_grads(cfg, x, params)
-        m = build_model(cfg, panel_rows)
-        parts, grads, nnf = m.energy_and_grads({"counts": x}, params)
         tag = f"case {case}: B={B} D={D} K={K} S={S} dens={density} sr={scale_rows} P={panel_rows}"
-        assert float(nnf.sum()) == 0, tag
-        for k in pref:
-            np.testing.assert_allclose(parts[k].cpu().numpy(), pref[k].numpy(), rtol=RTOL,
-                                       atol=RTOL, err_msg=f"{tag} part {k}")
-        assert_close_grads(grads, gref, O.energy_grad_scales(cfg, x, params), tag=tag)
+        check_dense_oracle(build_model(cfg, panel_rows), cfg, x, params, tag=tag)
 
 
 def test_c_abi_argument_errors():

@@ -18,32 +18,20 @@ a Poisson column.  Bars (bar(v) = 1e-5 |v| + 1e-5 max|score|, the bar of test_gp
 Everything else is bit for bit: against rank_cells, between column lists, between the outputs asked for,
 between row chunkings, and beside a NaN row."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
 import torch
 
-from oracle import spmf_oracle as O
-from _stream_cases import _bern_cols, _problem
-from test_gpu_dense import LIKELIHOODS, _dense_model, _dense_problem
-from test_gpu_parity import build_model, make_problem
+from _problems import LIKELIHOODS, _dense_model, _dense_problem, build_model, make_problem
+from _stream_cases import OUTS, SHAPES, _bar, _case, _damped_case, _lists
 
 pytestmark = pytest.mark.gpu
 T = torch.as_tensor
 
-# (B, D, K, S): the three shapes of test_gpu_topk.SHAPES -- ragged 64 x 64 blocks and 32 x 32 tiles, K padded
-# 3 -> 4, K = 16, K = 33 -> 64 (two K chunks)
-SHAPES = [(70, 45, 3, 2), (131, 197, 16, 7), (5, 333, 33, 3)]
 # share of cells whose oracle sd exceeds ten times the sd bound; measured minimum over SHAPES on the CPU oracle:
 # poisson 0.993, mixed 0.662, poisson_log 0.484, bernoulli 0.892, bernoulli_log 0.984
 SD_FLOOR = {"poisson": 0.99, "mixed": 0.65, "poisson_log": 0.45, "bernoulli": 0.85, "bernoulli_log": 0.95}
-PNZ_DAMP = {70: 2.0 ** -8, 131: 2.0 ** -14, 5: 2.0 ** -16}      # by B of SHAPES
-OUTS = ("mean", "sd", "p_nonzero")
-
-
-def _bar(v, smax):
-    return 1e-5 * np.abs(v) + 1e-5 * smax
 
 
 def _bits(t):
@@ -52,53 +40,6 @@ def _bits(t):
 
 def _same(a, b):
     return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
-
-
-def _lists(D):
-    """The column lists of a shape: all columns, one column, a seeded permutation, and min(D, 65) columns that
-    start D-1, 0, 0: a duplicate, a 64-block edge crossed, both ends touched."""
-    rng = np.random.default_rng(77 + D)
-    n = min(D, 65)
-    mixed = np.concatenate([[D - 1, 0, 0], rng.integers(0, D, size=n - 3)]).astype(np.int64)
-    return {"all": None, "one": np.array([D - 1]), "perm": rng.permutation(D), "dup": mixed}
-
-
-def _per_draw(cfg, x, params, bern):
-    """fp64 [S,B,D]: the oracle's rate and m_s of every draw."""
-    rate = O.log_likelihood_components(cfg, T(x), T(params["s"]), T(params["u"]), T(params["v"]),
-                                       T(params["w"]))["rate"]
-    if rate.dim() == 2:
-        rate = rate.unsqueeze(0)
-    m = torch.where(T(bern), torch.sigmoid(rate), rate)
-    return rate.numpy(), m.numpy()
-
-
-@functools.lru_cache(maxsize=None)
-def _case(lik, B, D, K, S):
-    """The problem of test_gpu_topk at this shape, its per-draw oracle values, the model and the full
-    prediction with all outputs; computed once and shared (read-only)."""
-    cfg, x, params, mask, score = _problem(lik, B, D, K, S)
-    bern = _bern_cols(lik, mask, D)
-    rate, ms = _per_draw(cfg, x, params, bern)
-    np.testing.assert_allclose(ms.mean(0), score, rtol=1e-12, atol=0)
-    m = _dense_model(lik, cfg, mask, 32)
-    full = m.predict({"counts": x}, draws=params, sd=True, p_nonzero=True)
-    assert set(full) == set(OUTS)
-    for n in OUTS:
-        assert full[n].dtype == torch.float32 and tuple(full[n].shape) == (B, D) and full[n].is_cuda, n
-    return dict(cfg=cfg, x=x, params=params, mask=mask, bern=bern, score=score, rate=rate, ms=ms, m=m, full=full)
-
-
-@functools.lru_cache(maxsize=None)
-def _damped_case(lik, B, D, K, S):
-    """poisson / mixed with u and w scaled by PNZ_DAMP[B]: rates small enough for P(x > 0) to say something."""
-    cfg, x, params, mask = _dense_problem(lik, B, D, K, S, 9100 + B + K)
-    params = dict(params)
-    params["u"] = params["u"] * PNZ_DAMP[B]
-    params["w"] = params["w"] * PNZ_DAMP[B]
-    bern = _bern_cols(lik, mask, D)
-    rate, ms = _per_draw(cfg, x, params, bern)
-    return dict(cfg=cfg, x=x, params=params, mask=mask, bern=bern, rate=rate, ms=ms)
 
 
 def _sd_view(c):

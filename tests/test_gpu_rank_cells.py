@@ -24,8 +24,7 @@ import pytest
 import torch
 
 from _stream_cases import _oracle_scores, _problem
-from test_gpu_dense import _dense_model
-from test_gpu_parity import build_model, make_problem
+from _problems import _dense_model, build_model, make_problem
 
 pytestmark = pytest.mark.gpu
 T = torch.as_tensor

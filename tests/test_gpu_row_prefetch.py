@@ -10,45 +10,26 @@ between rows that have the warm-up and rows that a counter hands out (they have 
 entries) next to short ones.  Those shapes are below, in both entry formats (the canonical one carries the warm-up
 at K <= 16) and at K = 64, which keeps the parent's loop.
 
-Reference and bars are those of tests/test_gpu_row_dispatch.py (its helpers are used): the fp64 sparse-exact port
+Reference and bars are those of tests/_energy_check.py (check_sparse): the fp64 sparse-exact port
 (oracle/sparse_exact.py) for 'x', 'z' and the gradients, parts at 1e-5 (rtol and atol), gradients entry by entry
 through tests/_gradcheck.assert_grads_entrywise at 1e-5 of the summed absolute contributions; the encode-only call
 against the port's z rows as in tests/test_gpu_stream_issue.py."""
-import functools
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import sparse_exact as SE
-from test_gpu_parity import build_model
-from test_gpu_row_dispatch import _check, _config, _reference
-from test_gpu_stream_issue import _csr, _counts
+from _energy_check import assert_same_bits, check_sparse, sparse_reference
+from _pass_cases import _fractional, _mixed_lengths
+from _problems import _config, _counts, _csr, build_model
 
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-5
-D = 320
-# empty rows first, last and in runs; every window boundary (31 ... 33, 63 ... 65, 127 ... 129); a 129- and a 300-entry
-# row directly before and after short ones, and next to each other
-LENGTHS = [0, 0, 1, 31, 32, 33, 0, 63, 64, 65, 129, 127, 300, 128, 1, 129, 300, 0, 0, 0, 33, 300, 129, 64, 0, 31, 128,
-           65, 127, 63, 32, 1, 0]
-
-
-def _fractional(X):
-    X = X.copy()
-    X.data[5] = 2.5                         # one non-integer value: the canonical col / val arrays
-    return X
-
-
-@functools.lru_cache(maxsize=None)
-def _mixed(B=len(LENGTHS)):
-    """The lengths above, tiled to B rows (the last row is empty whenever B is a multiple of their number)."""
-    return _csr([LENGTHS[b % len(LENGTHS)] for b in range(B)], D, np.random.default_rng(9001))
 
 
 def test_the_lengths_cover_the_issue():
-    n = np.diff(_mixed().indptr).tolist()
+    n = np.diff(_mixed_lengths().indptr).tolist()
     assert set(n) == {0, 1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 300}
     assert n[0] == 0 and n[1] == 0 and n[-1] == 0 and n[17:20] == [0, 0, 0]
     pairs = set(zip(n, n[1:]))
@@ -60,11 +41,11 @@ def test_the_lengths_cover_the_issue():
 @pytest.mark.parametrize("K", [4, 16, 32, 64])
 def test_mixed_row_lengths(K, fmt):
     """33 rows, one per wave of the 256-thread form: the issue point of every length with nothing to warm."""
-    X = _mixed() if fmt == "packed" else _fractional(_mixed())
+    X = _mixed_lengths() if fmt == "packed" else _fractional(_mixed_lengths())
     sc = _counts(X, 16)
     assert (sc.ent is not None) == (fmt == "packed")
     cfg, params = _config(X, K, 9010 + K)
-    _check(cfg, X, params, {"counts": sc}, build_model(cfg, 16), f"lengths K={K} {fmt}")
+    check_sparse(cfg, X, params, {"counts": sc}, build_model(cfg, 16), f"lengths K={K} {fmt}")
 
 
 @pytest.mark.parametrize("K,fmt", [(32, "packed"), (16, "canonical"), (16, "packed")])
@@ -74,11 +55,11 @@ def test_mixed_row_lengths_several_rows_per_wave(K, fmt):
     lengths -- a wave's consecutive rows run through different ones, the long ones and the empty ones included, as
     the row that warms, the row that is warmed and the row whose pointers are asked for."""
     B = 6 * 4096 + 33
-    X = _mixed(B) if fmt == "packed" else _fractional(_mixed(B))
+    X = _mixed_lengths(B) if fmt == "packed" else _fractional(_mixed_lengths(B))
     sc = _counts(X, 4096)
     assert (sc.ent is not None) == (fmt == "packed")
     cfg, params = _config(X, K, 9020 + K)
-    _check(cfg, X, params, {"counts": sc}, build_model(cfg, 4096), f"tiled lengths K={K} {fmt}")
+    check_sparse(cfg, X, params, {"counts": sc}, build_model(cfg, 4096), f"tiled lengths K={K} {fmt}")
 
 
 # ---- pipeline fill and drain ----------------------------------------------------------------------------------------
@@ -87,7 +68,7 @@ def test_fewer_rows_than_a_workgroup_has_waves(B):
     rng = np.random.default_rng(9030 + B)
     X = _csr(rng.integers(1, 40, size=B), 64, rng)
     cfg, params = _config(X, 32, 9035 + B)
-    _check(cfg, X, params, {"counts": _counts(X, 16)}, build_model(cfg, 16), f"B={B}")
+    check_sparse(cfg, X, params, {"counts": _counts(X, 16)}, build_model(cfg, 16), f"B={B}")
 
 
 @pytest.mark.parametrize("B,rows", [(16384, (1, 1)), (16384 + 8192, (1, 2)), (2 * 16384 + 8192, (2, 3)),
@@ -100,7 +81,7 @@ def test_the_256_thread_form_with_one_to_four_rows_per_wave(B, rows):
     rng = np.random.default_rng(9040 + B % 97)
     X = _csr(np.minimum(rng.poisson(5, size=B), 40), 40, rng)
     cfg, params = _config(X, 8, 9045)
-    _check(cfg, X, params, {"counts": _counts(X, 4096)}, build_model(cfg, 4096), f"256-thread form B={B}")
+    check_sparse(cfg, X, params, {"counts": _counts(X, 4096)}, build_model(cfg, 4096), f"256-thread form B={B}")
 
 
 def test_the_smallest_resident_set_launch():
@@ -108,7 +89,7 @@ def test_the_smallest_resident_set_launch():
     rng = np.random.default_rng(9050)
     X = _csr(rng.integers(0, 40, size=4096), 96, rng)
     cfg, params = _config(X, 32, 9051)
-    _check(cfg, X, params, {"counts": _counts(X, 1024)}, build_model(cfg, 1024), "B=4096")
+    check_sparse(cfg, X, params, {"counts": _counts(X, 1024)}, build_model(cfg, 1024), "B=4096")
 
 
 def test_rows_with_the_warm_up_meet_rows_dealt_out_by_the_counters():
@@ -117,23 +98,23 @@ def test_rows_with_the_warm_up_meet_rows_dealt_out_by_the_counters():
     rng = np.random.default_rng(9060)
     X = _csr(np.minimum(rng.poisson(10, size=40_000), 256), 256, rng)
     cfg, params = _config(X, 32, 9061)
-    _check(cfg, X, params, {"counts": _counts(X, 4096)}, build_model(cfg, 4096), "dynamic tail")
+    check_sparse(cfg, X, params, {"counts": _counts(X, 4096)}, build_model(cfg, 4096), "dynamic tail")
 
 
 # ---- draws, modes ---------------------------------------------------------------------------------------------------
 def test_two_draws_in_one_launch():
     """S = 2 on 3 x 4096 + 33 rows: gridDim.y = 2, each draw with its own tables; the entry arrays are shared."""
     B = 3 * 4096 + 33
-    X = _mixed(B)
+    X = _mixed_lengths(B)
     cfg, params = _config(X, 32, 9070, S=2)
-    _check(cfg, X, params, {"counts": _counts(X, 4096)}, build_model(cfg, 4096), "S=2")
+    check_sparse(cfg, X, params, {"counts": _counts(X, 4096)}, build_model(cfg, 4096), "S=2")
 
 
 @pytest.mark.parametrize("B", [33, 5 * 4096 + 33])
 def test_encode_alone_gives_the_oracles_z(B):
     """The encode-only call: its issue point, warm-up included, stands behind the last sweep-1 group.  The 256-thread
     grid and the resident-set launch (five or six rows per wave)."""
-    X = _mixed(B)
+    X = _mixed_lengths(B)
     cfg, params = _config(X, 32, 9080)
     one = {k: np.asarray(v[0], dtype=np.float64) for k, v in params.items()}
     ref = SE.data_term(X, cfg.eta_i.numpy().reshape(-1), float(cfg.xi_u_global), True, one["u"], one["v"], one["w"],
@@ -147,7 +128,7 @@ def test_encode_alone_gives_the_oracles_z(B):
 def test_deterministic_mode_repeats_bit_for_bit():
     """Five or six rows per wave of the LDS form, all dealt out with the fixed stride (the mode has no dynamic tail)."""
     B = 5 * 4096 + 33
-    X = _mixed(B)
+    X = _mixed_lengths(B)
     cfg, params = _config(X, 32, 9090)
     m = build_model(cfg, 4096)
     m.deterministic = True
@@ -157,12 +138,9 @@ def test_deterministic_mode_repeats_bit_for_bit():
         parts, grads, nnf = m.energy_and_grads({"counts": sc}, params)
         assert float(nnf.sum()) == 0
         steps.append(({k: v.clone() for k, v in parts.items()}, {k: v.clone() for k, v in grads.items()}))
-    data, grads_ref, scales = _reference(cfg, X, params)
+    data, grads_ref, scales = sparse_reference(cfg, X, params)
     from _gradcheck import assert_grads_entrywise
     for k in ("x", "z"):
         np.testing.assert_allclose(float(steps[0][0][k][0]), data[k], rtol=RTOL, atol=RTOL, err_msg=k)
     assert_grads_entrywise({k: v[0] for k, v in steps[0][1].items()}, grads_ref, scales, RTOL, "deterministic")
-    for k in steps[0][0]:
-        assert torch.equal(steps[0][0][k], steps[1][0][k]), k
-    for k in steps[0][1]:
-        assert torch.equal(steps[0][1][k], steps[1][1][k]), k
+    assert_same_bits(steps[0], steps[1])

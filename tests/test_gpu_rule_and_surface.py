@@ -10,50 +10,10 @@ import pytest
 import torch
 
 from oracle import spmf_oracle as O
-from test_gpu_parity import build_model, make_problem
+from _problems import _bad_cell_problem, _rule_energy, build_model, make_problem
 
 pytestmark = pytest.mark.gpu
 T = torch.as_tensor
-
-
-def _rule_energy(cfg, x, params):
-    """The energy of poisson.py:582-621 with the replacement rule written so that
-    autograd carries what the rule MEANS: finite cells pass through clip with
-    gradient one, replaced cells are worth min_val = (min over finite cells) - 10,
-    whose derivative is that of the minimum's cell.  (Differentiating the
-    reference's own graph literally -- TF or torch alike -- multiplies the zero
-    cotangent of the unselected where() branch by d log(r)/dr = inf at a rate-0
-    cell and yields NaN; see test_literal_autograd_through_the_rule_is_nan.)"""
-    p = {k: T(np.asarray(v, dtype=np.float64)).clone().requires_grad_(True) for k, v in params.items()}
-    xt = T(np.asarray(x, dtype=np.float64))
-    parts = O.prior_log_prob_parts(cfg, p)
-    theta = O.encode(cfg, xt, p["u"], p["s"])
-    rate = O.decoder_function(cfg, torch.matmul(theta, p["v"])) + O.intercept_matrix(cfg, p["w"], p["s"])
-    bad = (xt > 0) & ~(rate > 0)
-    safe = torch.where(bad, torch.ones_like(rate), rate)
-    ll = O.poisson_log_prob(xt, safe)
-    good = ~bad
-    mval = torch.minimum(ll[good.expand_as(ll)].min(), torch.zeros((), dtype=ll.dtype)) - 10.0
-    parts["x"] = torch.where(good, ll, torch.zeros_like(ll)).sum((-1, -2)) + bad.sum((-1, -2)) * mval
-    parts["z"] = (O.HALF_LOG_2_OVER_PI - 0.5 * theta ** 2).sum((-1, -2))
-    tot = sum(v.sum() for v in parts.values())
-    g = torch.autograd.grad(tot, [p[k] for k in O.VAR_ORDER])
-    return ({k: v.detach() for k, v in parts.items()},
-            {k: gk.numpy() for k, gk in zip(O.VAR_ORDER, g)})
-
-
-def _bad_cell_problem(logt=False):
-    cfg, x, params = make_problem(24, 15, 2, 2, 3, 0.3, empty=False)
-    cfg.log_transform = logt
-    if logt:
-        params["v"] *= 0.3
-    params["w"][0, 0, 0] = 0.0          # phi = 0 for draw 0, column 0
-    params["u"][0, 0, :] = 0.0          # column 0 feeds nothing into z
-    x[:, 0] = 0
-    x[0, :] = 0
-    x[0, 0] = 3.0                       # row 0: only column 0 -> z_0 = 0 -> rate 0 under x = 3
-    x[5, 0] = 2.0                       # a second stored cell in column 0 (finite: z_5 > 0)
-    return cfg, x, params
 
 
 @pytest.mark.parametrize("logt", [False, True])

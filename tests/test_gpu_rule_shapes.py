@@ -1,6 +1,6 @@
 """The non-finite replacement rule (poisson.py:606-616) at real shapes: values against the literal
 oracle (oracle.unormalized_log_prob_parts), gradients against fp64 autograd through _rule_energy
-(tests/test_gpu_rule_and_surface.py), on batches with a known set of rate-0 stored cells per draw
+(tests/_problems.py), on batches with a known set of rate-0 stored cells per draw
 (tests/_rule_cases.py).
 
 What the cases reach that the 24 x 15 problem of test_gpu_rule_and_surface.py cannot: the minimum
@@ -22,12 +22,11 @@ import torch
 
 import _rule_cases as RC
 from oracle import spmf_oracle as O
-from test_gpu_parity import build_model
-from test_gpu_rule_and_surface import _rule_energy
+from _energy_check import MIN_GAP, assert_same_bits, check_rule
+from _problems import _rule_energy, build_model
 
 gpu = pytest.mark.gpu
 T = torch.as_tensor
-MIN_GAP = 1e-3          # fp32 cells must pick the fp64 argmin: relative gap to the runner-up
 
 
 @functools.lru_cache(maxsize=4)
@@ -96,23 +95,6 @@ def _batch(c, x, model=None):
     return {"counts": sc, "panels": c.panels}
 
 
-def _check(c, m, batch, params, ref_v, rgrads, tag=""):
-    """The assertions of test_rule_value_and_gradient_match_oracle on one evaluation."""
-    parts, grads, nnf = m.energy_and_grads(batch, params, nonfinite="rule")
-    assert nnf.cpu().tolist() == RC.planted_counts(c), tag
-    for k, r in ref_v.items():
-        np.testing.assert_allclose(parts[k].cpu().numpy(), r.numpy(), rtol=1e-5, err_msg=f"{tag} {k}")
-    for k, r in rgrads.items():
-        g = grads[k].cpu().double().numpy().reshape(r.shape)
-        assert np.isfinite(g).all(), (tag, k)
-        err = np.abs(g - r).max()
-        print(f"{c.name} {tag} grad {k}: max err {err:.3e}, bar {1e-5 * np.abs(r).max():.3e}")
-        assert err <= 1e-5 * np.abs(r).max(), (tag, k, err, np.abs(r).max())
-    got = m.unormalized_log_prob_parts(batch, **params)
-    np.testing.assert_allclose(got["x"].cpu().numpy(), ref_v["x"].numpy(), rtol=1e-5, err_msg=tag)
-    return parts, grads
-
-
 def _run(case, **model_kw):
     c, cfg, x, xb, params, ref_v, rgrads = _reference(case.name)
     m = build_model(cfg, c.panel_rows)
@@ -124,7 +106,7 @@ def _run(case, **model_kw):
 @gpu
 @pytest.mark.parametrize("case", RC.CASES + [RC.MANY_CELLS, RC.TALL, RC.BACK_TO_BACK], ids=lambda c: c.name)
 def test_rule_value_and_gradient_at_shape(case):
-    _check(*_run(case))
+    check_rule(*_run(case))
 
 
 @gpu
@@ -134,7 +116,7 @@ def test_rule_on_a_panel_range_minibatch(case):
     range do not count."""
     c, m, batch, params, ref_v, rgrads = _run(case)
     assert sum(RC.planted_counts(c)) < sum(len(r) * len(k) for r, k in c.plants.values())
-    _check(c, m, batch, params, ref_v, rgrads)
+    check_rule(c, m, batch, params, ref_v, rgrads)
 
 
 @gpu
@@ -144,7 +126,7 @@ def test_rule_with_the_scan_cut_into_row_chunks(case, monkeypatch):
     chunk is neither the first nor one with bad cells) == the unchunked scan to 1e-12 on 'x', and
     each == the oracle."""
     c, m, batch, params, ref_v, rgrads = _run(case)
-    whole, gwhole = _check(c, m, batch, params, ref_v, rgrads, "unchunked")
+    whole, gwhole = check_rule(c, m, batch, params, ref_v, rgrads, "unchunked")
     scan = m._nonfinite_scan
     for panels_per_chunk in (1, 2):
         calls = []
@@ -153,7 +135,7 @@ def test_rule_with_the_scan_cut_into_row_chunks(case, monkeypatch):
             calls.append(_n)
             return scan(*a, max_cells=_n * c.panel_rows * c.D, **kw)
         monkeypatch.setattr(m, "_nonfinite_scan", counted)
-        parts, grads = _check(c, m, batch, params, ref_v, rgrads, f"{panels_per_chunk} panel(s) per chunk")
+        parts, grads = check_rule(c, m, batch, params, ref_v, rgrads, f"{panels_per_chunk} panel(s) per chunk")
         assert calls, "the scan did not run"
         np.testing.assert_allclose(parts["x"].cpu().numpy(), whole["x"].cpu().numpy(), rtol=1e-12)
         for k in gwhole:
@@ -170,7 +152,7 @@ def test_rule_with_column_split_accumulators(case):
     c, cfg, x, xb, params, ref_v, rgrads = _reference(case.name)
     m = build_model(cfg, c.panel_rows)
     assert m.enable_column_split(64) == 64
-    _check(c, m, {"counts": x}, params, ref_v, rgrads)
+    check_rule(c, m, {"counts": x}, params, ref_v, rgrads)
 
 
 @gpu
@@ -179,10 +161,7 @@ def test_rule_in_deterministic_mode_is_bit_reproducible(case):
     c, m, batch, params, ref_v, rgrads = _run(case, deterministic=True)
     runs = []
     for rep in range(2):
-        parts, grads = _check(c, m, batch, params, ref_v, rgrads, f"run {rep}")
+        parts, grads = check_rule(c, m, batch, params, ref_v, rgrads, f"run {rep}")
         torch.cuda.synchronize()
         runs.append(({k: v.clone() for k, v in parts.items()}, {k: v.clone() for k, v in grads.items()}))
-    for k in runs[0][0]:
-        assert torch.equal(runs[0][0][k], runs[1][0][k]), ("part", k)
-    for k in runs[0][1]:
-        assert torch.equal(runs[0][1][k], runs[1][1][k]), ("grad", k)
+    assert_same_bits(runs[0], runs[1])

@@ -24,8 +24,7 @@ import torch
 
 from oracle import spmf_oracle as O
 from _stream_cases import _bern_cols, _problem, assert_shared_errors
-from test_gpu_dense import LIKELIHOODS, _dense_model, _dense_problem
-from test_gpu_parity import build_model, make_problem
+from _problems import LIKELIHOODS, _dense_model, _dense_problem, build_model, make_problem
 
 pytestmark = pytest.mark.gpu
 T = torch.as_tensor

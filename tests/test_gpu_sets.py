@@ -23,9 +23,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_dense import LIKELIHOODS, _dense_model, _dense_problem
-from test_gpu_parity import build_model, make_problem
-from test_gpu_predict import SHAPES, _bar, _case
+from _problems import LIKELIHOODS, _dense_model, _dense_problem, build_model, make_problem
+from _stream_cases import SHAPES, _bar, _case
 
 pytestmark = pytest.mark.gpu
 T = torch.as_tensor

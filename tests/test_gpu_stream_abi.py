@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from _stream_cases import B, D, K, S, ENTRIES, PANEL_COLS, _problem, assert_shared_errors, gpu_good_call
-from test_gpu_dense import _dense_model
+from _problems import _dense_model
 
 pytestmark = pytest.mark.gpu
 ACCUMULATED = ("waic", "groups")          # entries that add into their outputs

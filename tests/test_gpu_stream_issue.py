@@ -12,7 +12,6 @@ gradients, held to the bars of tests/test_gpu_parity.py: parts 1e-5 (rtol and at
 through tests/_gradcheck.assert_grads_entrywise at 1e-5 of the summed absolute contributions (yardstick: the dense
 oracle in row chunks, tests/_chunked_oracle.py).  The log_transform case has no sparse-exact form (the port is the
 linear decoder's) and uses the dense fp64 oracle it is pinned to."""
-import math
 
 import numpy as np
 import pytest
@@ -21,68 +20,13 @@ import torch
 
 from oracle import spmf_oracle as O
 from oracle import sparse_exact as SE
-from _chunked_oracle import data_term as dense_data_term, prior_scales
+from _energy_check import RTOL, assert_same_bits, check_sparse, sparse_reference
 from _gradcheck import assert_grads_entrywise
-from test_gpu_parity import build_model
+from _problems import _config, _counts, _csr, build_model, cap_exponents
 
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-5
 ROW_LENGTHS = [0, 1, 7, 8, 9, 63, 64, 65, 127, 128, 129, 191, 192, 193, 300]
-
-
-def _csr(lengths, D, rng):
-    """Rows of the given numbers of stored entries (integer counts 1 + Poisson(1.5)), columns drawn without
-    replacement."""
-    lengths = np.asarray(lengths, dtype=np.int64)
-    indptr = np.concatenate([[0], np.cumsum(lengths)])
-    idx = [np.sort(rng.choice(D, size=int(n), replace=False)) for n in lengths]
-    indices = np.concatenate(idx) if len(idx) else np.zeros(0, dtype=np.int64)
-    data = (1 + rng.poisson(1.5, size=int(indptr[-1]))).astype(np.float64)
-    return sp.csr_matrix((data, indices, indptr), shape=(len(lengths), D))
-
-
-def _config(X, K, seed, scale_rows=True):
-    B, D = X.shape
-    rng = np.random.default_rng(seed)
-    cfg = O.OracleConfig(latent_dim=K, feature_dim=D, scale_rows=scale_rows, u_tau_scale=1.0 / math.sqrt(B * D))
-    cfg.eta_i = torch.as_tensor(rng.uniform(0.5, 3.0, size=(1, D)))
-    cfg.xi_u_global = float(rng.uniform(2.0, 6.0))
-    return cfg, O.random_params(cfg, 1, seed + 1, fp32_exact=True)
-
-
-def _reference(cfg, X, params):
-    """(sparse-exact data term, total gradients of the 12 variables, their entry-wise yardsticks), one draw."""
-    one = {k: np.asarray(v[0], dtype=np.float64) for k, v in params.items()}
-    eta = cfg.eta_i.numpy().reshape(-1)
-    ref = SE.data_term(X, eta, float(cfg.xi_u_global), cfg.scale_rows, one["u"], one["v"], one["w"], one["s"])
-    assert ref["n_nonfinite"] == 0
-    _, pg = SE.prior_term(one, cfg.u_tau_scale, cfg.s_tau_scale,
-                          cfg.symmetry_breaking_decay ** np.arange(cfg.latent_dim))
-    grads = {k: pg[k] + ref["grads"].get(k, 0.0) for k in pg}
-    p64 = {k: np.asarray(v, dtype=np.float64) for k, v in params.items()}
-    dense = dense_data_term(cfg, X, p64, chunk=8192, scales=True)
-    psc = prior_scales(cfg, p64)
-    scales = {k: psc[k][0] + (dense["scales"][k][0] if k in dense["scales"] else 0.0) for k in pg}
-    return ref, grads, scales
-
-
-def _check(cfg, X, params, batch, model, tag, ref=None):
-    ref = _reference(cfg, X, params) if ref is None else ref
-    data, grads_ref, scales = ref
-    parts, grads, nnf = model.energy_and_grads(batch, params)
-    assert float(nnf.sum()) == 0, tag
-    for k in ("x", "z"):
-        got = float(parts[k][0])
-        print(tag, k, got, data[k])
-        np.testing.assert_allclose(got, data[k], rtol=RTOL, atol=RTOL, err_msg=f"{tag} part {k}")
-    assert_grads_entrywise({k: v[0] for k, v in grads.items()}, grads_ref, scales, RTOL, tag)
-    return parts, grads
-
-
-def _counts(X, panel_rows):
-    from spmf_amd import SparseCounts
-    return SparseCounts.from_any(X, "cuda", panel_rows)
 
 
 # ---- row lengths ------------------------------------------------------------------------------------------------
@@ -96,7 +40,7 @@ def test_row_lengths_around_the_chunks_and_empty_rows_at_both_ends(shape, K):
     lengths = ROW_LENGTHS + [0] if shape == "boundaries" else [0, 0, 0, 0, 0, 70]
     X = _csr(lengths, 512, rng)
     cfg, params = _config(X, K, 610 + K)
-    _check(cfg, X, params, {"counts": _counts(X, 64)}, build_model(cfg, 64), f"{shape} K={K}")
+    check_sparse(cfg, X, params, {"counts": _counts(X, 64)}, build_model(cfg, 64), f"{shape} K={K}")
 
 
 # ---- row counts and launch shapes -------------------------------------------------------------------------------
@@ -106,7 +50,7 @@ def test_fewer_rows_than_waves(B):
     rng = np.random.default_rng(620 + B)
     X = _csr(rng.integers(0, 30, size=B), 40, rng)
     cfg, params = _config(X, 32, 630 + B)
-    _check(cfg, X, params, {"counts": _counts(X, 16)}, build_model(cfg, 16), f"B={B}")
+    check_sparse(cfg, X, params, {"counts": _counts(X, 16)}, build_model(cfg, 16), f"B={B}")
 
 
 @pytest.mark.parametrize("B,fmt", [(4096, "packed"), (4097, "packed"), (4097, "large_count"), (4097, "fractional")])
@@ -123,7 +67,7 @@ def test_the_switch_to_the_resident_set_launch_in_both_entry_formats(B, fmt):
     sc = _counts(X, 512)
     assert (sc.ent is not None and sc.pc_ent is not None) == (fmt == "packed")
     cfg, params = _config(X, 32, 650 + B)
-    _check(cfg, X, params, {"counts": sc}, build_model(cfg, 512), f"B={B} {fmt}")
+    check_sparse(cfg, X, params, {"counts": sc}, build_model(cfg, 512), f"B={B} {fmt}")
 
 
 @pytest.mark.parametrize("B,D,K,mean", [(40_000, 64, 32, 10), (140_000, 48, 8, 6)])
@@ -134,7 +78,7 @@ def test_rows_dealt_out_by_the_counters(B, D, K, mean):
     rng = np.random.default_rng(660 + K)
     X = _csr(np.minimum(rng.poisson(mean, size=B), D), D, rng)
     cfg, params = _config(X, K, 670 + K)
-    _check(cfg, X, params, {"counts": _counts(X, 4096)}, build_model(cfg, 4096), f"B={B} K={K}")
+    check_sparse(cfg, X, params, {"counts": _counts(X, 4096)}, build_model(cfg, 4096), f"B={B} K={K}")
 
 
 # ---- modes ------------------------------------------------------------------------------------------------------
@@ -148,7 +92,7 @@ def _mode_problem(K=32, B=4200, D=300, seed=680, scale_rows=True):
 @pytest.mark.parametrize("scale_rows", [True, False])
 def test_row_scaling_on_and_off(scale_rows):
     cfg, X, params = _mode_problem(scale_rows=scale_rows)
-    _check(cfg, X, params, {"counts": _counts(X, 1024)}, build_model(cfg, 1024), f"scale_rows={scale_rows}")
+    check_sparse(cfg, X, params, {"counts": _counts(X, 1024)}, build_model(cfg, 1024), f"scale_rows={scale_rows}")
 
 
 @pytest.mark.parametrize("B", [37, 4200])
@@ -172,14 +116,8 @@ def test_log_transform_launches_at_K64():
     x = ((rng.random((64, 48)) < 0.3) * (1 + rng.poisson(2.0, size=(64, 48)))).astype(np.float64)
     x[0, :] = 0.0
     x[63, :] = 0.0
-    cfg = O.OracleConfig(latent_dim=64, feature_dim=48, scale_rows=True, log_transform=True,
-                         u_tau_scale=1.0 / math.sqrt(64 * 48))
-    cfg.eta_i = torch.as_tensor(rng.uniform(0.5, 3.0, size=(1, 48)))
-    cfg.xi_u_global = float(rng.uniform(2.0, 6.0))
-    params = O.random_params(cfg, 1, 691, fp32_exact=True)
-    T = torch.as_tensor
-    z = O.encode(cfg, T(x), T(params["u"]), T(params["s"]))
-    params["v"] *= 8.0 / float((torch.matmul(z, T(params["v"])) * cfg.eta_i).max())   # largest exponent: 8
+    cfg, params = _config(x, 64, 690, log_transform=True, rng=rng)
+    cap_exponents(cfg, x, params, 8.0)                                                 # largest exponent: 8
     pref, gref, _ = O.energy_and_grads(cfg, x, params)
     parts, grads, nnf = build_model(cfg, 32).energy_and_grads({"counts": x}, params)
     assert float(nnf.sum()) == 0
@@ -193,7 +131,7 @@ def test_panel_range_minibatch():
     sc = _counts(X, 256)
     m = build_model(cfg, 256)
     for p0, p1 in [(0, 1), (1, 4), (3, 4)]:
-        _check(cfg, X[p0 * 256:p1 * 256], params, {"counts": sc, "panels": (p0, p1)}, m, f"panels {p0}:{p1}")
+        check_sparse(cfg, X[p0 * 256:p1 * 256], params, {"counts": sc, "panels": (p0, p1)}, m, f"panels {p0}:{p1}")
 
 
 def test_deterministic_mode_repeats_bit_for_bit():
@@ -201,13 +139,10 @@ def test_deterministic_mode_repeats_bit_for_bit():
     m = build_model(cfg, 1024)
     m.deterministic = True
     sc = _counts(X, 1024)
-    ref = _reference(cfg, X, params)
-    pa, ga = _check(cfg, X, params, {"counts": sc}, m, "deterministic step 1", ref)
-    pb, gb = _check(cfg, X, params, {"counts": sc}, m, "deterministic step 2", ref)
-    for k in pa:
-        assert torch.equal(pa[k], pb[k]), k
-    for k in ga:
-        assert torch.equal(ga[k], gb[k]), k
+    ref = sparse_reference(cfg, X, params)
+    pa, ga = check_sparse(cfg, X, params, {"counts": sc}, m, "deterministic step 1", ref)
+    pb, gb = check_sparse(cfg, X, params, {"counts": sc}, m, "deterministic step 2", ref)
+    assert_same_bits((pa, ga), (pb, gb))
 
 
 # ---- column lists -----------------------------------------------------------------------------------------------
@@ -233,7 +168,7 @@ def _list_problem(K):
 @pytest.fixture(scope="module", params=[8, 32])
 def list_case(request):
     cfg, X, params = _list_problem(request.param)
-    return cfg, X, params, _reference(cfg, X, params)
+    return cfg, X, params, sparse_reference(cfg, X, params)
 
 
 @pytest.mark.parametrize("fetch", ["wide", "narrow"])
@@ -246,4 +181,4 @@ def test_column_lists_around_the_fetch_and_segment_boundaries(list_case, fetch):
     assert sc.n_panels == 2
     if fetch == "narrow":
         sc.pc_pad = 0
-    _check(cfg, X, params, {"counts": sc}, build_model(cfg, 640), f"lists K={cfg.latent_dim} {fetch}", ref)
+    check_sparse(cfg, X, params, {"counts": sc}, build_model(cfg, 640), f"lists K={cfg.latent_dim} {fetch}", ref)

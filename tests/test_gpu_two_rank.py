@@ -140,8 +140,7 @@ def _rule_worker(rank, world, port, q, flip):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     torch.cuda.set_device(0)
     from spmf_amd.dist import ShardReducer, shard_bounds
-    from test_gpu_parity import build_model
-    from test_gpu_rule_and_surface import _bad_cell_problem
+    from _problems import _bad_cell_problem, build_model
     cfg, x, params = _bad_cell_problem()
     if flip:
         x = x[::-1].copy()          # the rate-0 cell (and the minimum's cell) move to the other shard
@@ -174,8 +173,7 @@ def test_two_rank_nonfinite_rule_equals_single_process(flip):
         p.join(120)
         assert p.exitcode == 0
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from test_gpu_parity import build_model
-    from test_gpu_rule_and_surface import _bad_cell_problem
+    from _problems import _bad_cell_problem, build_model
     cfg, x, params = _bad_cell_problem()
     if flip:
         x = x[::-1].copy()
@@ -207,7 +205,7 @@ def _custom_worker(rank, world, port, q):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     torch.cuda.set_device(0)
     from spmf_amd.dist import ShardReducer, shard_bounds
-    from test_gpu_parity import make_problem
+    from _problems import make_problem
     cfg, x, params = make_problem(48, 20, 3, 2, 41, 0.3)
     r0, r1 = shard_bounds(x.shape[0], world, rank, granule=8)
     m = _custom_model(cfg)
@@ -234,7 +232,7 @@ def test_two_rank_custom_callables_equal_single_process():
         p.join(120)
         assert p.exitcode == 0
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from test_gpu_parity import make_problem
+    from _problems import make_problem
     cfg, x, params = make_problem(48, 20, 3, 2, 41, 0.3)
     parts, grads, nnf = _custom_model(cfg).energy_and_grads({"counts": x}, params)
     assert res["nnf"].tolist() == nnf.cpu().tolist() == [0.0, 0.0]

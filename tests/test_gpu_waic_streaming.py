@@ -13,8 +13,7 @@ import pytest
 import torch
 
 from oracle import spmf_oracle as O
-from test_gpu_dense import LIKELIHOODS, _dense_model, _dense_problem
-from test_gpu_parity import build_model, make_problem
+from _problems import LIKELIHOODS, _dense_model, _dense_problem, build_model, make_problem
 
 pytestmark = pytest.mark.gpu
 T = torch.as_tensor

@@ -9,7 +9,8 @@ import pytest
 import torch
 
 from oracle import spmf_oracle as O
-from test_gpu_parity import make_problem, build_model, assert_close_parts, assert_close_grads
+from _energy_check import assert_close_grads, assert_close_parts, check_dense_oracle
+from _problems import build_model, make_problem
 
 pytestmark = pytest.mark.gpu
 
@@ -26,12 +27,7 @@ CASES = [
 @pytest.mark.parametrize("B,D,K,S,density,scale_rows,panel_rows", CASES)
 def test_energy_parts_and_grads_match_oracle_above_k64(B, D, K, S, density, scale_rows, panel_rows):
     cfg, x, params = make_problem(B, D, K, S, 4000 + B + D + K, density, scale_rows)
-    parts_ref, grads_ref, _ = O.energy_and_grads(cfg, x, params)
-    m = build_model(cfg, panel_rows)
-    parts, grads, nnf = m.energy_and_grads({"counts": x}, params)
-    assert float(nnf.sum()) == 0
-    assert_close_parts(parts, parts_ref)
-    assert_close_grads(grads, grads_ref, O.energy_grad_scales(cfg, x, params))
+    check_dense_oracle(build_model(cfg, panel_rows), cfg, x, params)
 
 
 def test_feature_dim_default_latent_dim_and_encode():
@@ -62,11 +58,7 @@ def test_minibatch_of_panels_and_nonfinite_cells_above_k64():
     cfg, x, params = make_problem(B, D, K, 1, 4343, 0.2, empty=False)
     m = build_model(cfg, 32)
     xs = x[32:96]
-    parts_ref, grads_ref, _ = O.energy_and_grads(cfg, xs, params)
-    parts, grads, nnf = m.energy_and_grads({"counts": x, "panels": (1, 3)}, params)
-    assert float(nnf.sum()) == 0
-    assert_close_parts(parts, parts_ref)
-    assert_close_grads(grads, grads_ref, O.energy_grad_scales(cfg, xs, params))
+    check_dense_oracle(m, cfg, xs, params, batch={"counts": x, "panels": (1, 3)})
     # negative intercepts on a few columns: stored cells with r <= 0 are counted, not propagated
     p2 = {k: np.array(v, copy=True) for k, v in params.items()}
     p2["w"][..., :5] = -1e7
@@ -122,9 +114,4 @@ def test_draws_in_turn_on_a_batch_too_big_for_one_launch_per_kernel():
     each through the K > 64 kernels with its own tables, row outputs and accumulators."""
     B, D, K, S = 2100, 1700, 128, 2
     cfg, x, params = make_problem(B, D, K, S, 4545, 0.01, empty=False)
-    parts_ref, grads_ref, _ = O.energy_and_grads(cfg, x, params)
-    m = build_model(cfg, 1024)
-    parts, grads, nnf = m.energy_and_grads({"counts": x}, params)
-    assert float(nnf.sum()) == 0
-    assert_close_parts(parts, parts_ref)
-    assert_close_grads(grads, grads_ref, O.energy_grad_scales(cfg, x, params))
+    check_dense_oracle(build_model(cfg, 1024), cfg, x, params)

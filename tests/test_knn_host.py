@@ -11,8 +11,8 @@ import numpy as np
 import pytest
 import torch
 
-from _stream_cases import (B, D, K, S, ENTRIES, abi_call, assert_declared_exported_bound, assert_shared_errors,
-                           host_good_call)
+from _stream_cases import (B, D, K, S, ENTRIES, abi_call, assert_declared_exported_bound, assert_embed_own_errors,
+                           assert_knn_errors, assert_shared_errors, host_good_call, knn_raw_call)
 
 # spmf_knn is no draw-stage call: it is not in the contract table
 HEADER_ARGS = {"spmf_knn_scratch_bytes": 4, "spmf_knn": 14}
@@ -229,55 +229,6 @@ def _ctx(lib, k, flags=0):
     return h
 
 
-KNN_ARGS = (("q", C.c_void_p), ("nq", C.c_int64), ("r", C.c_void_p), ("nr", C.c_int64), ("row_len", C.c_int),
-            ("k", C.c_int), ("flags", C.c_uint), ("self_offset", C.c_int64), ("idx", C.c_void_p),
-            ("dist", C.c_void_p), ("ptr", C.c_void_p), ("nbytes", C.c_size_t), ("stream", C.c_void_p))
-
-
-def knn_raw_call(good):
-    """-> call(**overrides): spmf_knn through a binding of its own with the arguments of ``good``."""
-    from spmf_amd import _lib
-    fn = C.CDLL(_lib.LIB_PATH).spmf_knn
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p] + [t for _, t in KNN_ARGS]
-
-    def call(**kw):
-        a = dict(good, **kw)
-        return fn(a["h"], *[a[n] for n, _ in KNN_ARGS])
-    return call
-
-
-def assert_knn_errors(lib, good, need, after=lambda: None):
-    """The error contract of spmf_knn; every call here returns before a launch or a memset, and ``after`` is
-    run behind each (the GPU file checks its sentinels there)."""
-    call, h = knn_raw_call(good), good["h"]
-
-    def refused(code, **kw):
-        assert call(**kw) == code, kw
-        assert lib.spmf_last_error(h).decode().startswith("knn: "), lib.spmf_last_error(h).decode()
-        after()
-    for k in (0, 65, -3):
-        refused(-1, k=k)
-    for row_len in (0, 257, -1):
-        refused(-1, row_len=row_len)
-    refused(-1, flags=2)
-    refused(-1, flags=3)
-    assert "flag" in lib.spmf_last_error(h).decode()
-    refused(-1, nr=2 ** 31)
-    assert "int32" in lib.spmf_last_error(h).decode()
-    refused(-1, nq=-1)
-    refused(-1, nr=-1)
-    refused(-1, self_offset=-2)
-    for name in ("q", "r", "idx", "dist", "ptr"):
-        refused(-1, **{name: None})
-    refused(-1, ptr=good["ptr"] + 4)
-    assert "aligned" in lib.spmf_last_error(h).decode()
-    refused(-3, nbytes=need - 256)
-    assert str(need) in lib.spmf_last_error(h).decode()
-    refused(-3, nq=0, nbytes=0)             # errors come before the empty return
-    assert call(h=None) == -1
-
-
 def test_knn_errors_return_before_any_device_call(lib):
     """A context of spmf_ctx_create and dummy aligned addresses: nothing here is a valid call with queries, so
     nothing may be launched or dereferenced."""
@@ -311,17 +262,6 @@ def test_knn_scratch_size(lib):
         assert int(lib.spmf_knn_scratch_bytes(None, 5, 5, 8)) == 0
     finally:
         lib.spmf_ctx_destroy(h)
-
-
-def assert_embed_own_errors(lib, call, good, after=lambda: None):
-    """The argument errors of spmf_embed_rows beyond the draw stage's; ``call`` is the raw call of ``good``
-    (_stream_cases.abi_call), every call returns before a launch and ``after`` is run behind each."""
-    assert call(mean=None) == -1
-    after()
-    one = good["sd"] if good["sd"] is not None else 0x6000000
-    assert call(S=1, sd=one) == -1
-    assert "sd_out" in lib.spmf_last_error(good["h"]).decode()
-    after()
 
 
 def test_embed_errors_return_before_any_device_call(lib):

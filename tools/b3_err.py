@@ -6,12 +6,12 @@ import numpy as np, torch
 sys.path.insert(0, "."); sys.path.insert(0, "tests")
 from oracle import spmf_oracle as O
 from _gradcheck import worst_entry
-from test_gpu_logtransform import problem
+from _problems import poisson_log_problem
 from spmf_amd import PoissonFactorization
 out = {}
 for (B, D, ymax) in [(300, 129, 8.0), (513, 64, 30.0), (90, 1000, 45.0), (90, 1000, 60.0), (700, 333, 60.0)]:
     K = 64
-    cfg, x, params = problem(B, D, K, 1, 2900 + B + D, 0.05)
+    cfg, x, params = poisson_log_problem((B, D, 0.05), K, 1, 2900 + B + D)
     params["v"] *= ymax / 8.0
     pref, gref, _ = O.energy_and_grads(cfg, x, params)
     sc = O.energy_grad_scales(cfg, x, params)

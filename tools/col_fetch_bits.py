@@ -53,8 +53,8 @@ def dump(path, rows=250_000):
     out["shard_segment"] = int(getattr(sc, "segment", 0))
     del sc, m
 
-    import test_gpu_col_fetch as T
-    from test_gpu_parity import build_model
+    import _pass_cases as T
+    from _problems import build_model
     for K in (2, 4, 8, 16, 32, 64):
         cfg, X, params, _ = T._list_case(K)
         m = build_model(cfg, T.R)

@@ -55,15 +55,15 @@ def dump(path, rows=250_000):
     out[f"encode_{rows}x{D}_K{K}/z"] = m.encode(sc, u=params["u"], s=params["s"]).cpu().clone()
     del sc, m
 
-    import test_gpu_row_prefetch as T
-    from test_gpu_parity import build_model
+    import _pass_cases as T
+    from _problems import _config, _counts, build_model
     B = 6 * 4096 + 33
     for K, fmt in ((32, "packed"), (16, "canonical")):
-        X = T._mixed(B) if fmt == "packed" else T._fractional(T._mixed(B))
-        cfg, params = T._config(X, K, 9020 + K)
+        X = T._mixed_lengths(B) if fmt == "packed" else T._fractional(T._mixed_lengths(B))
+        cfg, params = _config(X, K, 9020 + K)
         m = build_model(cfg, 4096)
         m.deterministic = True
-        sc = T._counts(X, 4096)
+        sc = _counts(X, 4096)
         assert (sc.ent is not None) == (fmt == "packed")
         keep(f"lengths_K{K}_{fmt}", m.energy_and_grads({"counts": sc}, params))
         t = torch.as_tensor

@@ -46,7 +46,7 @@ def dump(path):
         print(f"{_lib.LIB_PATH} has no {name}: not bound", file=sys.stderr)
         del _lib.SIGNATURES[name]
     from _stream_cases import _problem
-    from test_gpu_dense import _dense_model
+    from _problems import _dense_model
     with_knn = "spmf_knn" in _lib.SIGNATURES and "spmf_embed_rows" in _lib.SIGNATURES
     out = {"lib": os.path.relpath(_lib.LIB_PATH, ROOT), "tree": os.path.basename(ROOT),
            "device": torch.cuda.get_device_name(0)}
@@ -93,7 +93,7 @@ def dump(path):
                 v = v.cpu() if torch.is_tensor(v) else torch.tensor(float(v), dtype=torch.float64)
                 out[f"waic_streaming/{tag}/{name}/call{call}"] = v
     if with_knn:
-        from test_gpu_knn import _points
+        from _stream_cases import _points
         for nq, nr, K, k, metric, tiles in KNN_CASES:
             Q, R = _points(nq, nr, K, False)
             for tile in tiles:

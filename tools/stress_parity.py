@@ -3,7 +3,7 @@ fresh seeds, bigger shapes than the tests use, against the fp64 oracle.  Prints 
 import sys, contextlib, io
 import numpy as np, torch
 sys.path.insert(0, "."); sys.path.insert(0, "tests")
-import test_gpu_parity as T
+import _problems as T
 from oracle import spmf_oracle as O
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 200

@@ -4,7 +4,7 @@ import sys, contextlib, io, math
 import numpy as np, torch
 sys.path.insert(0, "."); sys.path.insert(0, "tests")
 from oracle import spmf_oracle as O
-import test_gpu_logtransform as TL, test_gpu_bernoulli as TB, test_gpu_mixed as TM
+from _problems import bernoulli_problem, mixed_problem, poisson_log_problem
 from spmf_amd import PoissonFactorization, BernoulliFactorization, MixedFactorization
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 60
@@ -33,18 +33,18 @@ for mode in ("logt", "bern", "bernlogt", "mixed"):
         tag = f"{mode} case {case}: B={B} D={D} K={K} S={S} dens={density} sr={sr} P={P}"
         with contextlib.redirect_stdout(io.StringIO()):
             if mode == "logt":
-                cfg, x, params = TL.problem(B, D, K, S, seed, density, sr)
+                cfg, x, params = poisson_log_problem((B, D, density), K, S, seed, sr)
                 m = PoissonFactorization(latent_dim=K, feature_dim=D, u_tau_scale=cfg.u_tau_scale, scale_rows=sr,
                                          log_transform=True, column_norms=cfg.eta_i,
                                          initialize_distributions=False, device="cuda", panel_rows=P)
                 m.xi_u_global = cfg.xi_u_global
             elif mode in ("bern", "bernlogt"):
                 lt = mode == "bernlogt"
-                cfg, x, params = (TB.problem_logt if lt else TB.problem)(B, D, K, S, seed, density)
+                cfg, x, params = bernoulli_problem((B, D, density), K, S, seed, lt)
                 m = BernoulliFactorization(latent_dim=K, feature_dim=D, u_tau_scale=cfg.u_tau_scale,
                                            column_norms=cfg.eta_i, log_transform=lt, device="cuda", panel_rows=P)
             else:
-                cfg, x, params, mask = TM.problem(B, D, K, S, seed, density, sr)
+                cfg, x, params, mask = mixed_problem((B, D, density), K, S, seed, sr)
                 m = MixedFactorization(mask, latent_dim=K, u_tau_scale=cfg.u_tau_scale, scale_rows=sr,
                                        column_norms=cfg.eta_i, device="cuda", panel_rows=P)
                 m.xi_u_global = cfg.xi_u_global
