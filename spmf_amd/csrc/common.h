@@ -25,7 +25,7 @@ constexpr int kDaccDynSlot = 5;
 // so a batch with a few runaway cells still trains -- its gradient pushes their
 // exponents down -- instead of being skipped.  Saturation events are counted
 // (dacc[4], workgroup granularity); while that count is 0 the decoder is exact.
-// Likelihood code of a context (api.hip likelihood_code): 0 Poisson / linear decoder, 1 Poisson /
+// Likelihood code of a context (ctx.h likelihood_code): 0 Poisson / linear decoder, 1 Poisson /
 // exp decoder (log_transform), 2 Bernoulli(logits) / linear, 3 mixed per column / linear,
 // 4 Bernoulli(logits) / exp decoder (bernoulli.py:60-61: logit = exp(<z, eta v>) - 1 + phi).
 __host__ __device__ constexpr bool lik_exp(int l) { return l == 1 || l == 4; }
@@ -196,7 +196,7 @@ __device__ __forceinline__ float4 gather4(const float* __restrict__ base, int ro
 // vector cache's 64-B tag cycles per four lanes, and the sparse passes run that pipe at 98 % of its cycles:
 // DESIGN.md section 4, round 5 (e)) cost an issue slot and nothing else, with no branch and no exec mask in
 // the straight-line groups of loads.  A padded slot asks for row kPadRow: -1 wraps to the last KP*4 bytes
-// below 4 GiB, behind every table the host admits (api.hip checks rows*KP*4 < 4 GiB - KP*4).
+// below 4 GiB, behind every table the host admits (api_ctx.hip checks rows*KP*4 < 4 GiB - KP*4).
 // (measured against padded slots that read row 0: profiles/r05_oob_pad_ab.txt)
 constexpr int kPadRow = -1;
 constexpr uint32_t kPadWord = 0xffff0000u;     // packed entry (column or panel row 65 535, count 0)

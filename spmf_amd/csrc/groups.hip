@@ -30,7 +30,7 @@
 // order onto the caller's output.  One summation order, a pure function of (B, G, S, C) and the labels.
 //
 // launch_groups walks column ranges of CR columns (group_kernel + group_combine_kernel per range) so that part
-// stays inside its budget; api.hip carves the scratch from the same group_geom.
+// stays inside its budget; api_stream.hip carves the scratch from the same group_geom.
 #include "common.h"
 #include "kernels.h"
 #include "score_block.h"

@@ -211,7 +211,7 @@ struct NfPatchArgs {
 };
 void launch_nonfinite_patch(int KP, const NfPatchArgs& a, hipStream_t st);
 void launch_nonfinite_lgamma(const DenseLLArgs& a, double* out, hipStream_t st);   // uses B, D, logt, ctype, CSR, rate
-// What the consumer kernel of a streaming call reads: the draw stage's output for S draws over B rows (api.hip
+// What the consumer kernel of a streaming call reads: the draw stage's output for S draws over B rows (api_stream.hip
 // draw_stage).
 struct DrawTables {
   int64_t B;
@@ -261,7 +261,7 @@ void launch_topk_merge(int64_t B, int k, int nsl, const int32_t* pc, const float
 // t.z[S,B,KP], unpadded: mean / sd [B][K].  Nothing is launched for B == 0.
 void launch_embed(const DrawTables& t, int K, float* mean, float* sd, hipStream_t st);
 // knn.hip: exact k nearest rows of r [n_ref][row_len] for every row of q [n_query][row_len] (include/spmf_hip.h
-// spmf_knn has the definition).  The scratch pointers are api.hip's carve; qw == rw when q == r.  false: KP / k /
+// spmf_knn has the definition).  The scratch pointers are api_stream.hip's carve; qw == rw when q == r.  false: KP / k /
 // slices not built (nothing launched).
 constexpr int kKnnCentreBlocks = 512;   // most per-block partial sums of the centre
 constexpr int kKnnDefaultTile = 1;      // the tile function without SPMF_KNN_TILE: the faster one
@@ -333,7 +333,7 @@ void launch_panel_gather(const DrawTables& t, int C, const int32_t* cols, float*
                          hipStream_t st);
 // groups.hip: per draw, group and column the fp64 sum over the group's rows of the posterior predictive mean m_s
 // and, where asked for, of P(x > 0), added onto sum / nonzero [S][n_groups][n_cols].  labels [B]: a value outside
-// [0, n_groups) is no group.  cols as in PanelArgs.  The scratch pointers are api.hip's carve, sized from
+// [0, n_groups) is no group.  cols as in PanelArgs.  The scratch pointers are api_stream.hip's carve, sized from
 // group_geom, a pure function of (B, S, G, C): the order of every sum depends on the call's arguments alone.
 // false: KP / lik not built (nothing launched).
 constexpr int kGroupRowChunk = 1024;     // rows per workgroup of the ordering's rank kernel
@@ -367,7 +367,7 @@ bool launch_groups(const GroupArgs& a, hipStream_t st);
 // predictive mean m_s, reduced over the draws: mean [B][ld] (column g = set g) and, where asked for, the unbiased
 // standard deviation over the draws (S >= 2).  set_ptr: HOST, [n_sets + 1], set g lists cols[set_ptr[g] ..
 // set_ptr[g + 1]) (device; any order, repeats allowed, one outside [0, t.D) makes its set NaN) with the weights
-// beside them (device, null = 1).  The scratch pointers are api.hip's carve for padded_cols = 64 * sum_g
+// beside them (device, null = 1).  The scratch pointers are api_stream.hip's carve for padded_cols = 64 * sum_g
 // ceil(n_g / 64) columns.  false: KP / lik not built (nothing launched).
 constexpr int kSetDrawChunk = 8;         // draws per pass of set_kernel over the set's column blocks
 constexpr int kSetFillChunk = 128;       // sets whose offsets one launch of the fill kernel takes as arguments

@@ -15,7 +15,7 @@
 //   rank_init_kernel : rank 0 / candidates 0 of every listed cell; a cell outside [0,B) x [0,D), which no
 //     workgroup serves, gets its final rank -1 / 0 candidates / score NaN here.
 //   rank_kernel      : a workgroup owns 64 rows and a slice of the 64-column blocks (grid: row blocks x column
-//     slices, api.hip topk_slices).  The list is sorted by row: 65 binary searches over cell_row, bounded to
+//     slices, api_stream.hip topk_slices).  The list is sorted by row: 65 binary searches over cell_row, bounded to
 //     [0, n_cells), give the segment of each of the 64 rows.  A round takes the next T = kRankMaxPerRow listed
 //     cells of every row into an LDS table (column, score); a row with more is served by further rounds of the
 //     same workgroup, each round complete in itself, so the result does not depend on the rounds.

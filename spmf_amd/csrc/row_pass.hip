@@ -408,7 +408,7 @@ struct RowCtx {
 // to four waves too: those five kernels sit at 128 - 134 registers unbounded, three waves for a handful of registers
 // (all five fit 128 without scratch).
 // Launch contract: blockDim.x == BT (the wave number is computed from BT), and B < 2^31 -- row numbers are 32-bit
-// scalars inside, although the argument is int64_t (the host admits B * KP * 4 < 4 GiB only: api.hip).
+// scalars inside, although the argument is int64_t (the host admits B * KP * 4 < 4 GiB only: api_ctx.hip).
 template <int KP, int LIK, int BT = 256, int PACKED = 0>
 __global__ __launch_bounds__(BT, BT == 256 && KP != 32 ? ROW_WAVES_PER_SIMD : 4) void row_pass_kernel(
     int64_t B, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,

@@ -19,7 +19,7 @@
 //     that beats its row's threshold -- and only such a cell looks up its bit -- is appended, a full row is
 //     compacted to its best k by rank: the exact top k whatever the order of the appends, bit-reproducible.
 //     After the first blocks a cell beats the threshold with probability ~ k / (columns seen).
-//   topk_merge_kernel  : with few row blocks the columns are split over gridDim.y slices (api.hip
+//   topk_merge_kernel  : with few row blocks the columns are split over gridDim.y slices (api_stream.hip
 //     topk_slices), each writing its k per row; one wave per row ranks the slices' candidates.
 //
 // LDS and occupancy (160 KiB per CU): operand tiles 2 x 2 x 64 x (KC+4) floats = 36 864 B at KC = 32,

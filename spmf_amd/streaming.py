@@ -2,7 +2,7 @@
 PoissonFactorization (and through it the Bernoulli and mixed classes) waic_streaming, top_k, score_cells,
 rank_cells, predict, group_means, set_scores, embed, knn and neighbors.
 
-Every draw-stage query is the same three pieces around its own kernel (include/spmf_hip.h, csrc/api.hip "the
+Every draw-stage query is the same three pieces around its own kernel (include/spmf_hip.h, csrc/api_stream.hip "the
 draw stage"): ``_Draws``, the checked draws and the one place a library call is spelled; a driver that walks
 the batches and row chunks (``_stream_rows`` for [rows, width] outputs, ``_stream_cells`` for a cell list);
 and the check of the query's own arguments, which comes first.  A new query is one method here, one row in

@@ -176,7 +176,7 @@ def test_per_cell_outputs_of_a_batch_taller_than_a_grid_extent():
     """B = 270 000 rows of 5 columns: four rows per block put 67 500 blocks on the grid's y extent
     (dense_ll.hip launch_dense_t), past the 65 535 of a CUDA launch.  The HIP runtime bounds
     grid * block per dimension by 2^32 instead and takes the launch; a refusal would surface as an
-    SpmfError (api.hip checks hipGetLastError), a wrong row mapping as a value mismatch here."""
+    SpmfError (api_step.hip checks hipGetLastError), a wrong row mapping as a value mismatch here."""
     B, D, K = 270000, 5, 2
     cfg, x, params, mask = _dense_problem("poisson", B, D, K, 1, 8600, density=0.5)
     _check_dense("poisson", cfg, x, params, mask, panel_rows=None)

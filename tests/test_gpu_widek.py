@@ -110,7 +110,7 @@ def test_fit_trains_a_model_with_latent_dim_above_64():
 
 
 def test_draws_in_turn_on_a_batch_too_big_for_one_launch_per_kernel():
-    """More than 2048 rows and S table pairs above 3 MB: the draws run back to back (api.hip batched_draws),
+    """More than 2048 rows and S table pairs above 3 MB: the draws run back to back (api_step.hip batched_draws),
     each through the K > 64 kernels with its own tables, row outputs and accumulators."""
     B, D, K, S = 2100, 1700, 128, 2
     cfg, x, params = make_problem(B, D, K, S, 4545, 0.01, empty=False)
