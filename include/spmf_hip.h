@@ -672,6 +672,40 @@ int spmf_predict_columns(spmf_ctx* ctx, const spmf_counts* counts, int S,
                          float* mean_out, float* sd_out, float* pnz_out,
                          void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- streaming per-column top-k rows (added within ABI 6: two new entry points, no struct changed) ----
+ * The selection of spmf_topk_rows along the other axis: for every column of a panel the k rows of the batch
+ * `counts` with the largest posterior predictive mean over S >= 1 draws, without a [n_rows][n_cols] array
+ * (csrc/toprows.hip).  The score of a cell is mean_out of spmf_predict_columns, bit for bit (and so the score of
+ * spmf_topk_rows and spmf_rank_cells).  A row is a candidate of a column when the cell's score is finite (a NaN
+ * count makes its whole row's z NaN: that row is a candidate of no column) and, with bit 0 of `flags` (exclude
+ * stored cells), when `counts` holds no entry for the cell.  The panel is that of spmf_predict_columns: cols ==
+ * NULL is all columns and n_cols must be D; otherwise cols lists 0 <= n_cols <= D columns (int32, device) in any
+ * order, repeats allowed, and output row j belongs to column cols[j]; a listed column outside [0, D) reads nothing
+ * and has no candidates.  rows_out / scores_out = [n_cols][k] int32 / fp32: the column's best k candidates, score
+ * descending, equal scores by ascending row, the rows relative to the first row of `counts`; a column with fewer
+ * candidates is padded with row -1 / score -inf.  The result is the exact top k under that order of the fp32
+ * scores: it does not depend on the other listed columns or on the row slices of the launch, and two calls on the
+ * same inputs return the same bits.  Row chunks are combined by the caller: concatenate the chunks' results per
+ * column in ascending row order and keep the best k under a stable sort by score.
+ * params: only u, v, w, s (slots 2, 0, 1, 7) are read, each with the leading axis S.
+ * scratch: 256-byte aligned, at least spmf_toprows_scratch_bytes(ctx, counts->n_rows, S, n_cols) bytes: the
+ * scratch of spmf_rank_cells (the WAIC call's and the bitmap of the stored cells, n_rows * ceil(D/32) words), the
+ * compacted tables of the panel, S * n_cols * (KP + 1) floats and n_cols bytes, and, for a panel too narrow to
+ * fill the device with its column blocks, the partial results of its row slices; SPMF_E_WORKSPACE when short
+ * (the size function returns 0 for n_cols outside 0..D).  SPMF_E_ARG for S outside 1..65535, NULL params / eta /
+ * scratch, a misaligned scratch, a mixed context without column types, a struct_size mismatch, n_cols outside
+ * 0..D, cols == NULL with n_cols != D, k outside 1..64, unknown flag bits, a NULL output with n_cols > 0; every
+ * error returns before any launch.  n_cols == 0 returns SPMF_OK: nothing is launched or written.  n_rows == 0
+ * returns SPMF_OK: nothing is launched but the fill of both outputs with the padding, on the stream.  The
+ * context's workspace is not touched: the call may sit between other calls on the context, a spmf_step_begin ..
+ * spmf_step_end pair included.  Stream-ordered, synchronises nowhere.  K as for spmf_waic_accumulate. */
+size_t spmf_toprows_scratch_bytes(const spmf_ctx* ctx, int64_t n_rows, int S, int32_t n_cols);
+int spmf_toprows_columns(spmf_ctx* ctx, const spmf_counts* counts, int S,
+                         const float* const params[SPMF_NVARS], const float* eta,
+                         int32_t n_cols, const int32_t* cols, int k, unsigned flags,
+                         int32_t* rows_out, float* scores_out,
+                         void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- per-group sums of the predictions (added within ABI 6: two new entry points, no struct changed) ----
  * The posterior predictive reduced over the rows of the batch `counts`, per draw: with r_s and m_s as for
  * spmf_predict_columns, for every draw s < S, group g < n_groups and listed column j

@@ -156,6 +156,10 @@ SIGNATURES = {
     "spmf_predict_columns": (C.c_int, [C.c_void_p, C.POINTER(CountsStruct), C.c_int, PtrArray, C.c_void_p,
                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spmf_toprows_scratch_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int, C.c_int32]),
+    "spmf_toprows_columns": (C.c_int, [C.c_void_p, C.POINTER(CountsStruct), C.c_int, PtrArray, C.c_void_p,
+                                       C.c_int32, C.c_void_p, C.c_int, C.c_uint, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_size_t, C.c_void_p]),
     "spmf_groups_scratch_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int, C.c_int32, C.c_int32]),
     "spmf_group_sums": (C.c_int, [C.c_void_p, C.POINTER(CountsStruct), C.c_int, PtrArray, C.c_void_p,
                                   C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -10,7 +10,7 @@ extern "C" {
 
 // ---- the draw stage of the streaming calls ---------------------------------------------------
 // spmf_waic_accumulate, spmf_topk_rows, spmf_score_cells, spmf_rank_cells, spmf_predict_columns,
-// spmf_group_sums, spmf_set_scores and spmf_embed_rows are one stage and a consumer each (spmf_knn, at the end of the section,
+// spmf_toprows_columns, spmf_group_sums, spmf_set_scores and spmf_embed_rows are one stage and a consumer each (spmf_knn, at the end of the section,
 // takes rows as given and shares the scratch and launch helpers only).
 // The stage: for S draws the per-draw tables (prep) and the encoded rows z[S,B,KP] go into the caller's scratch;
 // the consumer kernel then reads z, V' and phi of every draw (kernels.h DrawTables).  The context's workspace is
@@ -322,6 +322,67 @@ int spmf_predict_columns(spmf_ctx* c, const spmf_counts* ct, int S, const float*
   pa.n_cols = n_cols; pa.cols = cols;
   pa.mean = mean_out; pa.sd = sd_out; pa.pnz = pnz_out;
   return launched(c, launch_panel(pa, st), "predict_columns: no kernel for this K / likelihood");
+}
+
+// ---- streaming per-column top-k rows of the posterior predictive mean (toprows.hip) -------------
+// Scratch of one call: stored_layout (the draw tables and the bitmap, whatever the flags), the compacted tables of
+// a listed panel sized for n_cols (panel_tables), and the row slices' results (sized for k = kTopkMaxK: the size
+// does not depend on the call's k or flags).  The slices are topk_slices with the roles swapped, as in knn_layout:
+// the keys are the column blocks of the panel, the candidates the row blocks.
+static void toprows_layout(Arena& a, const spmf_ctx* c, int64_t rows, int S, int n_cols, Tables& T, TopRowsArgs& ra) {
+  int topk_own;   // (the column slices of a top-k launch over these rows: not this call's)
+  stored_layout(a, c, rows, S, T, ra.stored, topk_own);
+  panel_tables(a, c, S, (size_t)n_cols, ra.Vc, ra.phic, ra.ctc);
+  const int64_t cand_rows = rows < 0x7fffffffLL - 63 ? rows : 0x7fffffffLL - 63;   // (draw_check's bound)
+  ra.slices = rows > 0 && n_cols > 0 ? topk_slices(n_cols, (int)cand_rows, device_cus(c)) : 1;
+  const size_t part = ra.slices > 1 ? (size_t)ra.slices * n_cols * kTopkMaxK : 0;
+  ra.part_rows = a.take<int32_t>(part);
+  ra.part_scores = a.take<float>(part);
+}
+
+size_t spmf_toprows_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S, int32_t n_cols) {
+  if (!c || n_rows < 0 || S < 1 || n_cols < 0 || n_cols > c->D) return 0;
+  Arena a;
+  Tables T;
+  TopRowsArgs ra{};
+  toprows_layout(a, c, n_rows, S, n_cols, T, ra);
+  return a.used;
+}
+
+int spmf_toprows_columns(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS],
+    const float* eta, int32_t n_cols, const int32_t* cols, int k, unsigned flags, int32_t* rows_out,
+    float* scores_out, void* scratch, size_t scratch_bytes, void* stream) {
+  int rc = draw_check(c, "toprows_columns", ct, S, 1, params, eta, scratch);
+  if (rc) return rc;
+  // (the scratch's size depends on n_cols: it is checked behind the list)
+  rc = check_column_list(c, "toprows_columns", n_cols, cols);
+  if (rc) return rc;
+  Tables T;
+  TopRowsArgs ra{};
+  Arena a(scratch, scratch_bytes);
+  toprows_layout(a, c, ct->n_rows, S, n_cols, T, ra);
+  if (!a.fits()) return scratch_too_small(c, "toprows_columns", a.used, scratch_bytes,
+      rows_S(ct, S) + " cols=" + std::to_string(n_cols));
+  if (k < 1 || k > kTopkMaxK) return fail(c, SPMF_E_ARG, "toprows_columns: k must be in 1..64");
+  if (flags & ~1u) return fail(c, SPMF_E_ARG, "toprows_columns: unknown flag (bit 0: exclude stored cells)");
+  if (n_cols > 0 && (!rows_out || !scores_out)) return fail(c, SPMF_E_ARG, "toprows_columns: rows_out and "
+      "scores_out must be set for a non-empty list");
+  if (n_cols == 0) return SPMF_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (ct->n_rows == 0) {   // no row: every column is padding (-1 is all bits set, -inf is 0xff800000)
+    const size_t n = (size_t)n_cols * k;
+    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)rows_out, -1, n, st));
+    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)scores_out, (int)0xff800000u, n, st));
+    return SPMF_OK;
+  }
+  rc = draw_stage(c, "toprows_columns", ct, S, params, eta, T, st, ra.t);
+  if (rc) return rc;
+  ra.nnz = ct->nnz; ra.n_cols = n_cols; ra.k = k; ra.cols = cols;
+  ra.row_ptr = ct->row_ptr; ra.col = ct->col_idx;
+  rc = stored_bits(c, flags, ct->n_rows, st, ra.stored);
+  if (rc) return rc;
+  ra.rows = rows_out; ra.scores = scores_out;
+  return launched(c, launch_toprows(ra, st), "toprows_columns: no kernel for this K / likelihood");
 }
 
 // ---- per-group sums of the predictions over the rows (groups.hip) ------------------------------

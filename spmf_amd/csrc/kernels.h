@@ -257,6 +257,27 @@ void launch_topk_mark(int64_t B, int D, const int32_t* row_ptr, const int32_t* c
 // cols / scores [B][k] (launch_topk runs it itself; knn.hip merges its reference slices with it)
 void launch_topk_merge(int64_t B, int k, int nsl, const int32_t* pc, const float* ps, int32_t* cols, float* scores,
                        hipStream_t st);
+// toprows.hip: per listed column the k rows with the largest posterior predictive mean over S draws (the score of
+// launch_topk and launch_panel, the same bits), ordered by (score descending, row ascending) and padded with row
+// -1 / score -inf.  cols as in PanelArgs (null: the tables' own columns, n_cols == t.D); the bitmap is indexed by
+// the columns of the draw tables, not of the list.  false: KP / lik / k / slices not built (nothing launched).
+struct TopRowsArgs {
+  DrawTables t;
+  int64_t nnz;
+  int n_cols, k;
+  int slices;                      // gridDim.y of the select launch: row slices, 1 .. min(kTopkMaxSlices, row blocks)
+  const int32_t* cols;             // [n_cols] or null
+  const int32_t* row_ptr;
+  const int32_t* col;
+  uint32_t* stored;                // as TopkArgs.stored
+  float *Vc, *phic;                // as PanelArgs (cols set)
+  uint8_t* ctc;
+  int32_t* part_rows;              // slices > 1: [slices][n_cols][k] each
+  float* part_scores;
+  int32_t* rows;                   // [n_cols][k], relative to the first row of t.z
+  float* scores;                   // [n_cols][k]
+};
+bool launch_toprows(const TopRowsArgs& a, hipStream_t st);
 // knn.hip: the mean (and, with sd, the unbiased standard deviation) over the S draws of the encoded rows
 // t.z[S,B,KP], unpadded: mean / sd [B][K].  Nothing is launched for B == 0.
 void launch_embed(const DrawTables& t, int K, float* mean, float* sd, hipStream_t st);

@@ -8,7 +8,9 @@
 // distinct) and the threshold moves up.  Cells that found the buffer full try again behind the compaction if
 // they still beat the new threshold.  What is dropped is never among the best k of what was seen, so the result
 // is the exact best k under that order whatever the order of the appends: bit-reproducible.  Both consumers
-// include these functions, so the selection of one is the selection of the other.
+// include these functions, so the selection of one is the selection of the other.  toprows.hip selects along the
+// other axis of the block -- 64 columns as the keys, rows as the candidates -- with select_block_cols below and
+// the same buffers, compaction, select_begin and select_end.
 #pragma once
 #include "common.h"
 #include "score_block.h"
@@ -128,6 +130,61 @@ __device__ __forceinline__ void select_block(const SelectRows<CAP> L, const floa
     for (int r = 0; r < 16; ++r) {
       const int rl = score_tile_row(wr, r, h);
       if ((pend >> r & 1u) && !score_precedes(sc[r], d, L.thr_s[rl], L.thr_c[rl])) pend &= ~(1u << r);
+    }
+  }
+}
+
+// select_block with the axes exchanged (toprows.hip): the 64 keys of the workgroup are the COLUMNS d0 .. d0 + 63
+// and the blocks it feeds are row blocks; the candidate id kept beside a score is the row, so the order is (score
+// descending, row ascending), strict since the rows of a column are distinct.  The key of a lane's 16 cells is one
+// column: its threshold is read once.  A cell inside [0,B) x [0,C) with a finite score that beats its column's
+// threshold is a candidate iff cand(b, d).  Buffers, counters, compaction and select_begin / select_end are those
+// of select_block, with "row" read as "key".  Every thread of the workgroup calls it (barriers inside).
+template <int CAP, class Cand>
+__device__ __forceinline__ void select_block_cols(const SelectRows<CAP> L, const float (&sc)[16], int64_t B, int C,
+                                                  int64_t b0, int d0, int k, Cand cand) {
+  const int t = threadIdx.x;
+  const int lane = t & 63, wv = t >> 6;
+  const int i32 = lane & 31, h = lane >> 5;
+  const int wr = wv >> 1, wc = wv & 1;
+  const int cl = wc * 32 + i32;           // the lane's key
+  const int d = d0 + cl;
+  float ts = L.thr_s[cl];
+  int tc = L.thr_c[cl];
+  unsigned pend = 0;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int64_t b = b0 + score_tile_row(wr, r, h);
+    const float v = sc[r];
+    bool in = b < B && d < C && isfinite(v) && score_precedes(v, (int)b, ts, tc);
+    if (in) in = cand(b, d);
+    pend |= in ? 1u << r : 0u;
+  }
+  while (true) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      if (pend >> r & 1u) {
+        const int slot = atomicAdd(&L.cnt[cl], 1);
+        if (slot < CAP) {
+          L.cand_s[cl][slot] = sc[r];
+          L.cand_c[cl][slot] = (int)(b0 + score_tile_row(wr, r, h));
+          pend &= ~(1u << r);
+        }
+      }
+    }
+    __syncthreads();
+    for (int i = 0; i < 16; ++i) {        // wave wv keeps keys 16 wv .. 16 wv + 15
+      const int kl = wv * 16 + i;
+      const int n = L.cnt[kl];            // (wave-uniform)
+      if (n >= CAP) compact_row<CAP>(L.cand_s[kl], L.cand_c[kl], CAP, k, lane, &L.cnt[kl], &L.thr_s[kl], &L.thr_c[kl]);
+    }
+    // a cell is still pending only where its column was full, and that column now has CAP - k free slots
+    if (!__syncthreads_or(pend != 0)) break;
+    ts = L.thr_s[cl];
+    tc = L.thr_c[cl];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      if ((pend >> r & 1u) && !score_precedes(sc[r], (int)(b0 + score_tile_row(wr, r, h)), ts, tc)) pend &= ~(1u << r);
     }
   }
 }

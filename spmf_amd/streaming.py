@@ -1,6 +1,6 @@
 """The streaming posterior queries of the model classes: ``StreamingQueries`` is the mixin that gives
 PoissonFactorization (and through it the Bernoulli and mixed classes) waic_streaming, top_k, score_cells,
-rank_cells, predict, group_means, set_scores, embed, knn and neighbors.
+rank_cells, predict, top_rows, group_means, set_scores, embed, knn and neighbors.
 
 Every draw-stage query is the same three pieces around its own kernel (include/spmf_hip.h, csrc/api_stream.hip "the
 draw stage"): ``_Draws``, the checked draws and the one place a library call is spelled; a driver that walks
@@ -45,6 +45,20 @@ def _vector(name, what, t, integer=True):
     if integer and (t.dtype.is_floating_point or t.dtype == torch.bool):
         raise ValueError(f"{name}: {what} must hold integers, got {t.dtype}")
     return t
+
+
+def fold_top_rows(rows, scores, new_rows, new_scores, offset):
+    """The running best k of ``top_rows`` with one more row chunk: ``rows`` int64 / ``scores`` float32 [C, k] are
+    the best so far (padding: row -1 / score -inf at the tail), ``new_rows`` int32 / ``new_scores`` [C, k] the
+    chunk's result with rows relative to the chunk's first row, global row ``offset``.  Chunks arrive in ascending
+    row order and each is ordered by (score descending, row ascending), so a stable sort of [running | new] by
+    score keeps equal scores in ascending row order and the padding at the tail.  -> (rows, scores)."""
+    k = scores.shape[1]
+    new_rows = new_rows.to(torch.int64)
+    both_r = torch.cat([rows, torch.where(new_rows >= 0, new_rows + int(offset), new_rows)], 1)
+    both_s = torch.cat([scores, new_scores], 1)
+    both_s, order = torch.sort(both_s, dim=1, descending=True, stable=True)
+    return both_r.gather(1, order)[:, :k].contiguous(), both_s[:, :k].contiguous()
 
 
 class _Scratch:
@@ -424,6 +438,51 @@ class StreamingQueries:
                     ptr.get("sd"), ptr.get("p_nonzero"))
         res = self._stream_rows(data, dr.S * dr.KP * 4, max_rows, {n: (n_cols, torch.float32, False) for n in names},
                                 call if n_cols else None)       # (an empty list has no pointer to pass)
+        if cols is not None:
+            res["columns"] = cols
+        return res
+
+    def top_rows(self, data, cols=None, k=10, nsamples=32, draws=None, exclude_stored=True, max_rows=None):
+        """Per column the ``k`` rows with the largest posterior predictive mean -- the cells that most express a
+        marker gene, the audience of an item -- without a [B, C] block (csrc/toprows.hip): ``top_k`` along the
+        other axis.  The score of a cell is ``predict``'s 'mean', bit for bit: the mean over the draws of the rate
+        on a Poisson column and of sigmoid(logit) on a Bernoulli one.
+
+        ``data``, ``draws`` / ``nsamples`` and ``max_rows`` as in ``top_k`` (one batch, an iterable or a factory;
+        ``draws`` may hold a single draw); the rows are numbered across all batches in arrival order, as
+        ``predict`` concatenates them.  ``cols`` as in ``predict``: None (all D columns) or 1-D integers in
+        [0, D), in any order, duplicates kept; output row j belongs to column ``cols[j]``.  ``exclude_stored``:
+        a row that stores the column in its batch is no candidate for that column.  A row with a non-finite
+        score is no candidate for any column (a NaN count takes its row out everywhere).
+
+        Returns device tensors {'rows': int64 [C, k], 'scores': float32 [C, k]} and, with a list, 'columns': the
+        int32 list as used.  Within a column: score descending, equal scores by ascending row; a column with
+        fewer than k candidates is padded at the tail with row -1 / score -inf.  Every row chunk is selected in
+        the kernel and folded into the running best k (``fold_top_rows``), so at most 2 * C * k candidates are
+        alive.  The result does not depend on ``max_rows``, on how the rows are split into batches or on the other
+        listed columns.  Bit-reproducible."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise ValueError(f"top_rows: k must be an integer, got {k!r}")
+        k = int(k)
+        if not 1 <= k <= 64:
+            raise ValueError(f"top_rows needs 1 <= k <= 64, got {k}")
+        cols = self._column_list("top_rows", cols)
+        dr = _Draws(self, "top_rows", draws, nsamples, 1, "predict")
+        n_cols = self.feature_dim if cols is None else int(cols.numel())
+        cols_ptr = cols.data_ptr() if cols is not None else None
+        flags = 1 if exclude_stored else 0
+        rows = torch.full((n_cols, k), -1, dtype=torch.int64, device=self.device)
+        scores = torch.full((n_cols, k), float("-inf"), dtype=torch.float32, device=self.device)
+        new_rows = torch.empty(n_cols, k, dtype=torch.int32, device=self.device)
+        new_scores = torch.empty(n_cols, k, dtype=torch.float32, device=self.device)
+        off = 0
+        for n_rows, chunks in self._row_chunks(data, dr.S * dr.KP * 4 + (self.feature_dim + 31) // 32 * 4, max_rows):
+            for r0, sub in chunks if n_cols else ():
+                dr.call("spmf_toprows_columns", "spmf_toprows_scratch_bytes", sub, n_cols, cols_ptr, k, flags,
+                        new_rows.data_ptr(), new_scores.data_ptr(), size_args=(n_cols,))
+                rows, scores = fold_top_rows(rows, scores, new_rows, new_scores, off + r0)
+            off += n_rows
+        res = {"rows": rows, "scores": scores}
         if cols is not None:
             res["columns"] = cols
         return res

@@ -13,14 +13,15 @@ The grid.  Contexts (K, D, flags): (3, 17, 0), (16, 197, 0), (32, 20000, SCALE_R
 refuses, a split being a multiple of 32: that context has none -- and after spmf_ctx_set_column_split(2496); a
 setting's return code is part of its context's name.  Rows 0, 1, 63, 64, 65, 2048, 2049, 4096, 100000, 2^20;
 S 1, 2, 7, 20.  spmf_workspace_bytes and the waic / topk / cells / rank /
-predict / embed sizes: every context x rows x S.  Groups: G 1, 4, 1025, 2^24 x n_cols 0, 5, D on top of that.  Sets:
+predict / embed sizes: every context x rows x S.  Groups: G 1, 4, 1025, 2^24 x n_cols 0, 5, D on top of that.  Top
+rows: n_cols 0, 5, 64, 65, D on top of that (64 / 65 where D allows).  Sets:
 set_ptr (0), (0, 0), (0, 4), (0, 64, 65, 65, 200) on top of that.  knn (context-free but for the device):
 (n_query, n_ref, row_len) (0, 0, 8), (131, 197, 16), (5, 333, 33), (100000, 100000, 256).  Deterministic-mode
 scratch: n_items 0, 1, 1000 x S 1, 2 per context.  One call with an invalid argument per function: it returns 0.
 
 No GPU is needed, except for spmf_layout_sizes_k (it asks rocPRIM for its temporary storage on the device): its
 sizes, for LAYOUTS below, are dumped only where a device is present, and "layout_sizes_dumped" says whether.
-The top-k and knn sizes depend on the device's CU count (256 is assumed without a device): compare dumps made on
+The top-k, top-rows and knn sizes depend on the device's CU count (256 is assumed without a device): compare dumps made on
 the same machine."""
 import ctypes as C
 import json
@@ -75,6 +76,8 @@ def dump(path):
                     for n_cols in (0, 5, D):
                         out[f"spmf_groups_scratch_bytes/{at}/G{G}/C{n_cols}"] = \
                             lib.spmf_groups_scratch_bytes(h, rows, S, G, n_cols)
+                for n_cols in sorted({n for n in (0, 5, 64, 65, D) if n <= D}):
+                    out[f"spmf_toprows_scratch_bytes/{at}/C{n_cols}"] = lib.spmf_toprows_scratch_bytes(h, rows, S, n_cols)
                 for ptr in SETS:
                     arr = (C.c_int64 * len(ptr))(*ptr)
                     out[f"spmf_sets_scratch_bytes/{at}/ptr{'_'.join(map(str, ptr))}"] = \
@@ -86,6 +89,7 @@ def dump(path):
         # one invalid argument each: every one of these is 0
         for fn in ROW_S_CALLS:
             out[f"{fn}/{tag}/invalid_rows-1"] = getattr(lib, fn)(h, -1, 2)
+        out[f"spmf_toprows_scratch_bytes/{tag}/invalid_C-1"] = lib.spmf_toprows_scratch_bytes(h, 64, 2, -1)
         out[f"spmf_groups_scratch_bytes/{tag}/invalid_G0"] = lib.spmf_groups_scratch_bytes(h, 64, 2, 0, 5)
         bad = (C.c_int64 * 3)(0, 9, 4)
         out[f"spmf_sets_scratch_bytes/{tag}/invalid_ptr_decreasing"] = lib.spmf_sets_scratch_bytes(h, 64, 2, 2, bad)

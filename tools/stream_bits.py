@@ -1,7 +1,7 @@
 """Do two builds of the library return the same bits from the streaming calls?
 
-    stream_bits.py dump FILE          run top_k, score_cells, rank_cells, embed, predict, group_means, set_scores
-                                      and waic_streaming at four small cases, and knn at two shapes, with the library
+    stream_bits.py dump FILE          run top_k, score_cells, rank_cells, embed, predict, top_rows, group_means,
+                                      set_scores and waic_streaming at four small cases, and knn at two shapes, with the library
                                       that SPMF_LIB_PATH names (default: the tree's own) and save every output to FILE
     stream_bits.py compare A B [OUT]  compare two dumps tensor by tensor with torch.equal -> one JSON line,
                                       also written to OUT
@@ -11,7 +11,8 @@ The cases are problems of tests/_stream_cases.py, (likelihood, B, D, K, S): pois
 top_k: k = 10 and 64, stored cells excluded and not, columns and scores.  score_cells: every cell listed in a
 seeded random order with values 0 .. 3: mean and lppd.  rank_cells: the same list, stored cells excluded: rank,
 candidates and score.  embed: mean and (S >= 2) deviation.  predict: mean, (S >= 2) sd and p_nonzero for all
-columns and for the list (D - 1, 0, 3, 3, D // 2), which holds a duplicate.  group_means: sum and sum_nonzero for
+columns and for the list (D - 1, 0, 3, 3, D // 2), which holds a duplicate.  top_rows: k = 10 and 64, stored cells
+excluded and not, for all columns and for the same list: rows and scores.  group_means: sum and sum_nonzero for
 the labels -1, 0, 1, 2, -1, ... with four groups (group 3 is empty), all columns and the same list.  set_scores:
 mean and sd of three sets -- that list (its repeated column counts twice), an empty set and every second column --
 with seeded normal weights.  knn: two of tests/test_gpu_knn.py's SHAPES with its
@@ -21,7 +22,7 @@ TWICE in each dump: its fp64 sums are atomics, so `compare` also reports whether
 agree, which is the bar a comparison across builds has to be read against.
 
 A dump is made in a process of its own per build (a library is loaded once per process); a build from before
-embed / knn (predict, group_means, set_scores) lacks their entry points and dumps no tensor of theirs."""
+embed / knn (predict, top_rows, group_means, set_scores) lacks their entry points and dumps no tensor of theirs."""
 import ctypes as C
 import json
 import os
@@ -34,7 +35,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 CASES = [("poisson", 131, 197, 16, 7), ("mixed", 65, 130, 40, 3), ("bernoulli_log", 70, 150, 3, 2),
          ("poisson", 40, 70, 128, 3)]
 KNN_CASES = [(131, 197, 16, 10, "euclidean", ("0", "1")), (5, 333, 33, 64, "cosine", (None,))]
-CALLS = ("top_k", "score_cells", "rank_cells", "embed", "knn", "predict", "group_means", "set_scores")
+CALLS = ("top_k", "score_cells", "rank_cells", "embed", "knn", "predict", "top_rows", "group_means", "set_scores")
 
 
 def dump(path):
@@ -76,6 +77,12 @@ def dump(path):
                 for name, v in m.predict(batch, cols=cols, draws=params, sd=S >= 2, p_nonzero=True).items():
                     if name != "columns":
                         out[f"predict/{tag}/{ctag}/{name}"] = v.cpu()
+            if "spmf_toprows_columns" in _lib.SIGNATURES:
+                for k in (10, 64):
+                    for ex in (True, False):
+                        top = m.top_rows(batch, cols=cols, k=k, draws=params, exclude_stored=ex)
+                        for name in ("rows", "scores"):
+                            out[f"top_rows/{tag}/{ctag}/k{k}/exclude{int(ex)}/{name}"] = top[name].cpu()
             if "spmf_group_sums" in _lib.SIGNATURES:
                 grp = m.group_means(batch, np.arange(B) % 4 - 1, n_groups=4, cols=cols, draws=params, p_nonzero=True)
                 assert grp["count"].tolist()[3] == 0
