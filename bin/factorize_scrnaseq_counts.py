@@ -29,6 +29,10 @@ With --gene-sets FILE.gmt (tab-separated: set name, description, member gene nam
   <stem>_setscore_<P>.npy        [cells, sets] posterior predictive expression summed over each gene set
   <stem>_setscore_sd_<P>.npy     [cells, sets] its standard deviation over the --set-draws posterior draws
 Without the flag nothing changes.
+With --gene-waic (model criticism per gene: which genes the model fits badly):
+  <stem>_genewaic_<P>.npy        [genes, 6] float64: n, n_excluded, lppd, pwaic, waic, se of every gene's
+                                 cells over the --waic-draws posterior draws, in gene order
+and the --top genes with the largest waic per counted cell.  Without the flag nothing changes.
 """
 import argparse
 import os
@@ -60,7 +64,18 @@ def build_parser():
     p.add_argument("--gene-sets", default=None, help="FILE.gmt: gene sets (name, description, members per line); "
                                                      "adds a score per cell and set with its posterior sd")
     p.add_argument("--set-draws", type=int, default=32, help="posterior draws of the gene-set scores (>= 2)")
+    p.add_argument("--gene-waic", action="store_true", help="adds the WAIC of every gene's cells (lppd, pwaic, "
+                                                            "waic, se) and lists the worst-fitted genes")
+    p.add_argument("--waic-draws", type=_at_least_two, default=32, help="posterior draws of the per-gene WAIC "
+                                                                        "(>= 2)")
     return p
+
+
+def _at_least_two(text):
+    n = int(text)
+    if n < 2:
+        raise argparse.ArgumentTypeError("at least 2 draws (the variance over the draws needs two)")
+    return n
 
 
 def load_counts(path):
@@ -136,7 +151,22 @@ def main(argv=None):
         group_table(factor, X, np.load(args.labels), gene_names, f"{stem}_groupmean_{P}.npy", args)
     if args.gene_sets is not None:
         gene_set_scores(factor, X, gene_names, f"{stem}_setscore_{P}.npy", f"{stem}_setscore_sd_{P}.npy", args)
+    if args.gene_waic:
+        gene_waic(factor, X, gene_names, f"{stem}_genewaic_{P}.npy", args)
     return losses
+
+
+def gene_waic(factor, X, gene_names, path, args):
+    """The per-gene WAIC: n, n_excluded, lppd, pwaic, waic and se of every gene's cells, and the genes with the
+    largest waic per counted cell."""
+    res = factor.waic_streaming({factor.count_key: X}, nsamples=args.waic_draws, col_scores=True)
+    table = np.stack([res[k].cpu().numpy().astype(np.float64) for k in
+                      ("col_n", "col_n_excluded", "col_lppd", "col_pwaic", "col_waic", "col_se")], axis=1)
+    np.save(path, table)
+    per_cell = np.where(table[:, 0] > 0, table[:, 4] / np.maximum(table[:, 0], 1.0), -np.inf)
+    top = np.argsort(per_cell, kind="stable")[::-1][:args.top]
+    print(f"gene waic: {res['waic']:.6g} over {res['n']} cells ({res['n_excluded']} excluded); worst per cell: "
+          + ", ".join(f"{gene_names[j]}({per_cell[j]:.3g})" for j in top))
 
 
 def gene_set_scores(factor, X, gene_names, path, sd_path, args):

@@ -532,12 +532,28 @@ int spmf_dense_ll(spmf_ctx* ctx, const spmf_counts* counts, const float* u,
  * over row chunks to bound it); SPMF_E_WORKSPACE when short.  SPMF_E_ARG for S < 2, NULL pointers
  * or a struct_size mismatch.  The context's workspace is not touched: the call may sit between
  * other calls on the context, a spmf_step_begin .. spmf_step_end pair included.  Stream-ordered,
- * synchronises nowhere; the fp64 sums are atomics (not bit-reproducible). */
+ * synchronises nowhere; the fp64 sums, the row and the column sums (spmf_waic_accumulate_cols)
+ * included, are atomics (not bit-reproducible). */
 size_t spmf_waic_scratch_bytes(const spmf_ctx* ctx, int64_t n_rows, int S);
 int spmf_waic_accumulate(spmf_ctx* ctx, const spmf_counts* counts, int S,
                          const float* const params[SPMF_NVARS], const float* eta,
                          double* sums6, double* row_out, void* scratch,
                          size_t scratch_bytes, void* stream);
+/* The same call with the column reduction (added within ABI 6: one new entry point, no struct
+ * changed).  col_out (NULL = skip: then exactly spmf_waic_accumulate) = double [D][5], ADDED to
+ * (zero it before the first call; batches and row chunks add up): slot j of column d is sums6[j]
+ * restricted to the cells of that column --
+ *   [0] cells counted  [1] sum lppd_i  [2] sum pwaic_i  [3] sum elpd_i^2  [4] cells excluded --
+ * so that  sum_d col_out[d][j] = the call's contribution to sums6[j].  A column nothing is stored
+ * in is scored like any other (all x = 0); a NaN count excludes its whole row, one cell of every
+ * column.  Arguments, scratch (spmf_waic_scratch_bytes), checks and their order, and the empty
+ * batch are those of spmf_waic_accumulate; this entry's name stands in front of its messages.
+ * The fp64 column sums are atomics too (not bit-reproducible): one per (column, slot) and
+ * 64 x 64 block of cells, and three to five per stored entry. */
+int spmf_waic_accumulate_cols(spmf_ctx* ctx, const spmf_counts* counts, int S,
+                              const float* const params[SPMF_NVARS], const float* eta,
+                              double* sums6, double* row_out, double* col_out, void* scratch,
+                              size_t scratch_bytes, void* stream);
 
 /* ---- streaming per-row top-k (added within ABI 6: two new entry points, no struct changed) ----
  * For every row of `counts` the k cells with the largest posterior predictive mean over S >= 1

@@ -140,6 +140,9 @@ SIGNATURES = {
     "spmf_waic_accumulate": (C.c_int, [C.c_void_p, C.POINTER(CountsStruct), C.c_int, PtrArray,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                        C.c_void_p]),
+    "spmf_waic_accumulate_cols": (C.c_int, [C.c_void_p, C.POINTER(CountsStruct), C.c_int, PtrArray,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_size_t, C.c_void_p]),
     "spmf_topk_scratch_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int]),
     "spmf_topk_rows": (C.c_int, [C.c_void_p, C.POINTER(CountsStruct), C.c_int, PtrArray, C.c_void_p,
                                  C.c_int, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,

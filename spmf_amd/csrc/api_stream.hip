@@ -9,7 +9,7 @@ using namespace spmf;
 extern "C" {
 
 // ---- the draw stage of the streaming calls ---------------------------------------------------
-// spmf_waic_accumulate, spmf_topk_rows, spmf_score_cells, spmf_rank_cells, spmf_predict_columns,
+// spmf_waic_accumulate (and its _cols form), spmf_topk_rows, spmf_score_cells, spmf_rank_cells, spmf_predict_columns,
 // spmf_toprows_columns, spmf_group_sums, spmf_set_scores and spmf_embed_rows are one stage and a consumer each (spmf_knn, at the end of the section,
 // takes rows as given and shares the scratch and launch helpers only).
 // The stage: for S draws the per-draw tables (prep) and the encoded rows z[S,B,KP] go into the caller's scratch;
@@ -103,19 +103,35 @@ size_t spmf_waic_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int S) {
   return draw_tables_bytes(c, n_rows, S);
 }
 
-int spmf_waic_accumulate(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS],
-    const float* eta, double* sums6, double* row_out, void* scratch, size_t scratch_bytes, void* stream) {
+// The body of the two entries; `fn` stands in front of every message, col_out may be NULL.
+static int waic_accumulate(spmf_ctx* c, const char* fn, const spmf_counts* ct, int S,
+    const float* const params[SPMF_NVARS], const float* eta, double* sums6, double* row_out, double* col_out,
+    void* scratch, size_t scratch_bytes, void* stream) {
   Tables T;
-  int rc = draw_only_check(c, "waic_accumulate", ct, S, 2, params, eta, scratch, scratch_bytes, T);
+  int rc = draw_only_check(c, fn, ct, S, 2, params, eta, scratch, scratch_bytes, T);
   if (rc) return rc;
-  if (!sums6) return fail(c, SPMF_E_ARG, "waic_accumulate: null argument");
-  if ((int64_t)(c->D + 63) / 64 > 65535) return fail(c, SPMF_E_UNSUPPORTED, "waic_accumulate: D above 65535 * 64");
+  const std::string f = std::string(fn) + ": ";
+  if (!sums6) return fail(c, SPMF_E_ARG, f + "null argument");
+  if ((int64_t)(c->D + 63) / 64 > 65535) return fail(c, SPMF_E_UNSUPPORTED, f + "D above 65535 * 64");
   hipStream_t st = (hipStream_t)stream;
   DrawTables dt;
-  rc = draw_stage(c, "waic_accumulate", ct, S, params, eta, T, st, dt);
+  rc = draw_stage(c, fn, ct, S, params, eta, T, st, dt);
   if (rc || ct->n_rows == 0) return rc;
-  WaicArgs wa{dt, ct->nnz, ct->row_ptr, ct->col_idx, ct->val, sums6, row_out};
-  return launched(c, launch_waic(wa, st), "waic_accumulate: no kernel for this K / likelihood");
+  WaicArgs wa{dt, ct->nnz, ct->row_ptr, ct->col_idx, ct->val, sums6, row_out, col_out};
+  return launched(c, launch_waic(wa, st), (f + "no kernel for this K / likelihood").c_str());
+}
+
+int spmf_waic_accumulate(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS],
+    const float* eta, double* sums6, double* row_out, void* scratch, size_t scratch_bytes, void* stream) {
+  return waic_accumulate(c, "waic_accumulate", ct, S, params, eta, sums6, row_out, nullptr, scratch, scratch_bytes,
+      stream);
+}
+
+int spmf_waic_accumulate_cols(spmf_ctx* c, const spmf_counts* ct, int S, const float* const params[SPMF_NVARS],
+    const float* eta, double* sums6, double* row_out, double* col_out, void* scratch, size_t scratch_bytes,
+    void* stream) {
+  return waic_accumulate(c, "waic_accumulate_cols", ct, S, params, eta, sums6, row_out, col_out, scratch,
+      scratch_bytes, stream);
 }
 
 // ---- streaming per-row top-k of the posterior predictive mean (topk.hip) ---------------------

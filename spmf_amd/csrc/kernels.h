@@ -229,6 +229,7 @@ struct WaicArgs {
   const float* val;
   double* sums;                    // [6]
   double* row_out;                 // [B][2] (sum_d lppd, sum_d pwaic), accumulated; may be null
+  double* col_out;                 // [D][5] (slots 0..4 of sums over the column's cells), accumulated; may be null
 };
 bool launch_waic(const WaicArgs& a, hipStream_t st);
 // topk.hip: per row the k cells with the largest posterior predictive mean over S draws (mean of the rate on a

@@ -7,6 +7,8 @@
 //   elpd_i  = lppd_i - pwaic_i
 // and the call adds  #cells, sum lppd_i, sum pwaic_i, sum elpd_i^2, #excluded cells  to a
 // caller-owned double[6] (a cell with a non-finite ll_s in any draw is excluded and counted).
+// Optionally the sums of each row's cells (lppd, pwaic: row_out[B][2]) and the five sums of each
+// column's cells (col_out[D][5], the slots of the double[6]) are added to caller-owned arrays.
 //
 // Two launches over the per-draw tables z[S,B,KP] (encode sweep), V'[S,D,KP], phi[S,D] (prep):
 //   waic_dense_kernel : EVERY cell as if x = 0.  A workgroup owns a 64 x 64 block of cells, a
@@ -20,6 +22,10 @@
 //     tables; the x = 0 contribution is taken out of the sums and the true one put in (the
 //     sums are additive over cells).  lgamma(x+1) does not depend on the draw: it cancels in
 //     the variance and is subtracted from lppd_i once, behind the loop.
+// Column sums: a lane's 16 cells lie in one column, so the dense kernel's share of a column is the
+// lane's own five sums, joined across the lane halves by a shuffle and across the two waves of a
+// block column through LDS: one fp64 atomic per (column, slot) and workgroup.  The fix kernel adds
+// an entry's net change to its column: three atomics, five where a count changes.
 // The log-mean-exp carries a running maximum, so a cell whose every ll_s is below -1000 is as
 // exact as any other.
 #include "common.h"
@@ -54,8 +60,9 @@ __global__ __launch_bounds__(256) void waic_dense_kernel(int64_t B, int D, int K
                                                          const float* __restrict__ phi,
                                                          const uint8_t* __restrict__ ctype,
                                                          double* __restrict__ sums,
-                                                         double* __restrict__ row_out) {
-  __shared__ float tiles[2][2][64][KC + 4];
+                                                         double* __restrict__ row_out,
+                                                         double* __restrict__ col_out) {
+  __shared__ __align__(16) float tiles[2][2][64][KC + 4];
   __shared__ double red[16];
   const int t = threadIdx.x;
   const int lane = t & 63, wv = t >> 6;
@@ -123,6 +130,28 @@ __global__ __launch_bounds__(256) void waic_dense_kernel(int64_t B, int D, int K
     atomicAdd(&sums[3], tE);
     if (tx != 0.0) atomicAdd(&sums[4], tx);
   }
+  if (col_out) {                                          // block-uniform
+    // the lane's five sums are those of its column over 16 of the wave's 32 rows: the other lane half holds
+    // the other 16, wave row 1 the block's other 32 rows (through the tile buffers, which the loop's last
+    // barrier released: [5][64] doubles of their 12 KB and more)
+    double* cs = reinterpret_cast<double*>(&tiles[0][0][0][0]);
+    double c[5] = {an, aL, aP, aE, ax};
+#pragma unroll
+    for (int j = 0; j < 5; ++j) c[j] += __shfl_xor(c[j], 32);
+    const int cl = (wv & 1) * 32 + i32;                   // the column inside the block
+    if (wr == 1 && h == 0) {
+#pragma unroll
+      for (int j = 0; j < 5; ++j) cs[j * 64 + cl] = c[j];
+    }
+    __syncthreads();
+    if (wr == 0 && h == 0 && d < D) {
+      double* co = col_out + (size_t)d * 5;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) atomicAdd(&co[j], c[j] + cs[j * 64 + cl]);
+      const double cx = c[4] + cs[4 * 64 + cl];
+      if (cx != 0.0) atomicAdd(&co[4], cx);
+    }
+  }
 }
 
 // stored cells: x = 0 statistics out, true statistics in.  One wave per row, one lane per entry.
@@ -135,7 +164,8 @@ __global__ __launch_bounds__(256) void waic_fix_kernel(int64_t B, int D, int KP,
                                                        const float* __restrict__ phi,
                                                        const uint8_t* __restrict__ ctype,
                                                        double* __restrict__ sums,
-                                                       double* __restrict__ row_out) {
+                                                       double* __restrict__ row_out,
+                                                       double* __restrict__ col_out) {
   __shared__ double red[16];
   const int lane = threadIdx.x & 63;
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -182,19 +212,32 @@ __global__ __launch_bounds__(256) void waic_fix_kernel(int64_t B, int D, int KP,
       const double lg = bern ? 0.0 : (double)lgammaf(x + 1.f);
       const double lp0 = (double)m0 + (double)logf(e0) - logS, pw0 = (double)q0 * inv_sm1;
       const double lp1 = (double)m1 + (double)logf(e1) - logS - lg, pw1 = (double)q1 * inv_sm1;
-      if (isfinite(lp0) && isfinite(pw0)) {
+      const bool fin0 = isfinite(lp0) && isfinite(pw0), fin1 = isfinite(lp1) && isfinite(pw1);
+      if (fin0) {
         const double e = lp0 - pw0;
         an -= 1.0; aL -= lp0; aP -= pw0; aE -= e * e;
         rl -= lp0; rp -= pw0;
       } else {
         ax -= 1.0;
       }
-      if (isfinite(lp1) && isfinite(pw1)) {
+      if (fin1) {
         const double e = lp1 - pw1;
         an += 1.0; aL += lp1; aP += pw1; aE += e * e;
         rl += lp1; rp += pw1;
       } else {
         ax += 1.0;
+      }
+      if (col_out) {                                       // grid-uniform: the entry's net change to its column
+        const double e0 = lp0 - pw0, e1 = lp1 - pw1;
+        const double dn = (fin1 ? 1.0 : 0.0) - (fin0 ? 1.0 : 0.0);
+        double* co = col_out + (size_t)d * 5;
+        if (dn != 0.0) {                                   // counted <-> excluded
+          atomicAdd(&co[0], dn);
+          atomicAdd(&co[4], -dn);
+        }
+        atomicAdd(&co[1], (fin1 ? lp1 : 0.0) - (fin0 ? lp0 : 0.0));
+        atomicAdd(&co[2], (fin1 ? pw1 : 0.0) - (fin0 ? pw0 : 0.0));
+        atomicAdd(&co[3], (fin1 ? e1 * e1 : 0.0) - (fin0 ? e0 * e0 : 0.0));
       }
     }
     if (row_out && end > start) {                          // wave-uniform
@@ -227,7 +270,7 @@ bool launch_waic(const WaicArgs& a, hipStream_t st) {
   with_kc(t.KP, [&](auto kc) {
     ok = with_lik(t.lik, [&](auto lik) {
       hipLaunchKernelGGL((waic_dense_kernel<decltype(kc)::value, decltype(lik)::value>), grid, dim3(256), 0, st, t.B,
-                         t.D, t.KP, t.S, t.z, t.Vp, t.phi, t.ctype, a.sums, a.row_out);
+                         t.D, t.KP, t.S, t.z, t.Vp, t.phi, t.ctype, a.sums, a.row_out, a.col_out);
     });
   });
   if (!ok) return false;
@@ -235,7 +278,7 @@ bool launch_waic(const WaicArgs& a, hipStream_t st) {
     const int64_t want = (t.B + 3) / 4;
     const int nb = (int)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
     hipLaunchKernelGGL(waic_fix_kernel, dim3(nb), dim3(256), 0, st, t.B, t.D, t.KP, t.S, t.lik, a.row_ptr, a.col,
-                       a.val, t.z, t.Vp, t.phi, t.ctype, a.sums, a.row_out);
+                       a.val, t.z, t.Vp, t.phi, t.ctype, a.sums, a.row_out, a.col_out);
   }
   return true;
 }

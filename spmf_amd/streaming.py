@@ -281,7 +281,7 @@ class StreamingQueries:
     # ------------------------------------------------------------------
     # the queries
     # ------------------------------------------------------------------
-    def waic_streaming(self, data, nsamples=100, draws=None, row_scores=False, max_rows=None):
+    def waic_streaming(self, data, nsamples=100, draws=None, row_scores=False, max_rows=None, col_scores=False):
         """``waic`` at any size: per-cell lppd_i / pwaic_i over the draws are formed in
         registers (csrc/waic.hip) and only their sums over the cells leave the kernel, so
         nothing of size S*B*D or B*D is written.
@@ -295,17 +295,37 @@ class StreamingQueries:
 
         Returns {'waic','se','lppd','pwaic','n','n_excluded'} (spmf_amd.waic.combine): a cell
         with a non-finite log-pmf in any draw (NaN count, rate 0 under a positive count) is
-        left out of the sums and counted in 'n_excluded', where ``waic`` returns NaN / -inf."""
+        left out of the sums and counted in 'n_excluded', where ``waic`` returns NaN / -inf.
+
+        ``col_scores=True`` adds the same criterion per column -- which genes or items the model
+        fits badly -- as device tensors of length D (spmf_amd.waic.combine_columns): 'col_n' and
+        'col_n_excluded' (int64), 'col_lppd', 'col_pwaic', 'col_waic' = -2 (lppd - pwaic) and
+        'col_se' (fp64; NaN where a column has at most one counted cell).  Columns ADD across
+        batches and row chunks, where the row scores concatenate.  The exclusion rule holds per
+        column: an excluded cell is left out of its column's sums and counted in its
+        'col_n_excluded'; a NaN count makes every cell of its row non-finite, so it takes one
+        cell out of EVERY column.  A column in which nothing is stored is scored like any other
+        (all its counts are 0).  The column sums are fp64 atomics, as the totals are: equal to
+        rounding from call to call, not bit-reproducible."""
         from . import waic as _waic
         dr = _Draws(self, "waic_streaming", draws, nsamples, 2, "waic()")
         sums = torch.zeros(_waic.NSUMS, dtype=torch.float64, device=self.device)
+        if col_scores:
+            cols = torch.zeros(self.feature_dim, _waic.NCOLSUMS, dtype=torch.float64, device=self.device)
+
+            def call(sub, ptr):
+                dr.call("spmf_waic_accumulate_cols", "spmf_waic_scratch_bytes", sub, sums.data_ptr(),
+                        ptr.get("rows"), cols.data_ptr())
+        else:
+            def call(sub, ptr):
+                dr.call("spmf_waic_accumulate", "spmf_waic_scratch_bytes", sub, sums.data_ptr(), ptr.get("rows"))
         rows = self._stream_rows(
-            data, dr.S * dr.KP * 4, max_rows, {"rows": (2, torch.float64, True)} if row_scores else {},
-            lambda sub, ptr: dr.call("spmf_waic_accumulate", "spmf_waic_scratch_bytes", sub, sums.data_ptr(),
-                                     ptr.get("rows")))
+            data, dr.S * dr.KP * 4, max_rows, {"rows": (2, torch.float64, True)} if row_scores else {}, call)
         out = _waic.combine(sums)
         if row_scores:
             out["row_lppd"], out["row_pwaic"] = rows["rows"][:, 0].contiguous(), rows["rows"][:, 1].contiguous()
+        if col_scores:
+            out.update(_waic.combine_columns(cols))
         return out
 
     def top_k(self, data, k=10, nsamples=32, draws=None, exclude_stored=True, max_rows=None):

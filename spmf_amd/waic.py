@@ -6,6 +6,8 @@ fp64 sums a batch leaves behind, and what they mean.
 
 with elpd_i = lppd_i - pwaic_i.  Every slot is a sum over cells: the sums of
 several batches, row chunks or row shards are ADDED, then combined once.
+spmf_waic_accumulate_cols leaves the first five slots per column as well
+([D, 5], ``combine_columns``): they add across batches in the same way.
 """
 from __future__ import annotations
 
@@ -14,6 +16,7 @@ import math
 import numpy as np
 
 NSUMS = 6
+NCOLSUMS = 5
 
 
 def combine(sums):
@@ -28,3 +31,22 @@ def combine(sums):
     var = (e2 - e * e / n) / (n - 1.0) if n > 1 else float("nan")
     return {"waic": -2.0 * e, "se": 2.0 * math.sqrt(n * max(var, 0.0)) if var == var else float("nan"),
             "lppd": lppd, "pwaic": pwaic, "n": int(round(n)), "n_excluded": int(round(float(s[4])))}
+
+
+def combine_columns(col_sums):
+    """[D, 5] fp64 column sums (slots 0..4 of the sums, per column) -> {'col_n', 'col_n_excluded'} int64 and
+    {'col_lppd', 'col_pwaic', 'col_waic', 'col_se'} fp64, each [D], on the device of the input:
+    col_waic = -2 (lppd - pwaic) and col_se = ``combine``'s formula over the column's own counted cells, NaN
+    where the column has at most one."""
+    import torch
+    s = torch.as_tensor(col_sums).to(torch.float64)
+    if s.dim() != 2 or s.shape[1] != NCOLSUMS:
+        raise ValueError(f"expected [D, {NCOLSUMS}] column sums, got shape {tuple(s.shape)}")
+    n, lppd, pwaic, e2 = s[:, 0], s[:, 1], s[:, 2], s[:, 3]
+    e = lppd - pwaic
+    many = n > 1
+    safe_n = torch.where(many, n, torch.full_like(n, 2.0))
+    var = (e2 - e * e / safe_n) / (safe_n - 1.0)
+    se = torch.where(many, 2.0 * torch.sqrt(safe_n * var.clamp_min(0.0)), torch.full_like(n, float("nan")))
+    return {"col_n": n.round().to(torch.int64), "col_n_excluded": s[:, 4].round().to(torch.int64),
+            "col_lppd": lppd.contiguous(), "col_pwaic": pwaic.contiguous(), "col_waic": -2.0 * e, "col_se": se}

@@ -8,7 +8,8 @@
 Median of 10 timed calls after 3 warm-ups, device synchronised around every timed call, draws
 fixed across the calls.  The materialising path is timed as waic() runs it with the draws
 passed in (log_likelihood_components -> fp64 -> logsumexp / var).  --once runs a single
-streaming call (for a kernel trace).  One JSON line per step."""
+streaming call (for a kernel trace).  --cols times waic_streaming(col_scores=True), the call with
+the per-column sums.  One JSON line per step."""
 import argparse
 import json
 import math
@@ -60,20 +61,22 @@ def _median_ms(fn, warmup=3, reps=10):
     return statistics.median(ts), min(ts), max(ts)
 
 
-def run_step(name, once=False):
+def run_step(name, once=False, cols=False):
     import torch
     B, D, K, S, both, _ = STEPS[name]
     m, batch, draws = _problem(B, D, K, S)
+    kw = {"col_scores": True} if cols else {}
     if once:
-        out = m.waic_streaming(batch, draws=draws)
+        out = m.waic_streaming(batch, draws=draws, **kw)
         torch.cuda.synchronize()
-        print(json.dumps({"step": name, "once": True, **{k: out[k] for k in ("lppd", "pwaic", "n", "n_excluded")}}))
+        print(json.dumps({"step": name, "once": True, "cols": cols,
+                          **{k: out[k] for k in ("lppd", "pwaic", "n", "n_excluded")}}))
         return
-    res = {"step": name, "B": B, "D": D, "K": K, "S": S}
+    res = {"step": name, "B": B, "D": D, "K": K, "S": S, "cols": cols}
     out = {}
 
     def streaming():
-        out["s"] = m.waic_streaming(batch, draws=draws)
+        out["s"] = m.waic_streaming(batch, draws=draws, **kw)
     med, lo, hi = _median_ms(streaming)
     res.update(streaming_ms=round(med, 3), streaming_min_ms=round(lo, 3), streaming_max_ms=round(hi, 3),
                lppd=out["s"]["lppd"], pwaic=out["s"]["pwaic"], n_excluded=out["s"]["n_excluded"])
@@ -96,13 +99,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--step", choices=sorted(STEPS))
     ap.add_argument("--once", action="store_true")
+    ap.add_argument("--cols", action="store_true", help="waic_streaming(col_scores=True)")
     a = ap.parse_args()
     if a.step:
-        run_step(a.step, a.once)
+        run_step(a.step, a.once, a.cols)
         return 0
     for name in ("shared", "c2"):       # a fresh child per step, each under its own time limit
         rc = subprocess.run(["timeout", "-k", "10", str(STEPS[name][5]), sys.executable, os.path.abspath(__file__),
-                             "--step", name]).returncode
+                             "--step", name] + (["--cols"] if a.cols else [])).returncode
         if rc != 0:
             print(f"step {name} ended with status {rc}: stopping", file=sys.stderr)
             return rc
