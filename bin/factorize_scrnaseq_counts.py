@@ -25,6 +25,12 @@ With --labels FILE.npy (one integer per cell, -1 = no group; e.g. a clustering o
   <stem>_groupmean_<P>.npy       [groups, genes] posterior predictive mean expression per group
 and, per group, the --top genes by log2 fold change against the rest (mean over the draws, with its sd and the
 share of draws beyond one doubling).  Without the flag nothing changes.
+With --clusters G (deterministic k-means of the cells in the latent space, on the device):
+  <stem>_cluster_<P>.npy         [cells] int32: the cluster of every cell (-1: a cell without a finite encoding)
+  <stem>_centroid_<P>.npy        [G, P] float32: the centroids in the latent space
+over the mean encoding of --cluster-draws posterior draws, started by k-means++ with --cluster-seed (which also
+seeds the draws).  Without --labels these labels feed the group table above; with --labels the file wins for
+the table.  Without the flag nothing changes.
 With --gene-sets FILE.gmt (tab-separated: set name, description, member gene names, looked up in --genes):
   <stem>_setscore_<P>.npy        [cells, sets] posterior predictive expression summed over each gene set
   <stem>_setscore_sd_<P>.npy     [cells, sets] its standard deviation over the --set-draws posterior draws
@@ -61,6 +67,10 @@ def build_parser():
     p.add_argument("--labels", default=None, help="FILE.npy: a group per cell (-1: none); adds the group means "
                                                   "and the marker genes per group")
     p.add_argument("--group-draws", type=int, default=32, help="posterior draws of the group means")
+    p.add_argument("--clusters", type=int, default=None, help="G: k-means of the cells in the latent space into G "
+                                                              "clusters; writes the labels and the centroids")
+    p.add_argument("--cluster-seed", type=int, default=0, help="seed of the k-means++ start and of the draws")
+    p.add_argument("--cluster-draws", type=int, default=32, help="posterior draws of the clustered encoding")
     p.add_argument("--gene-sets", default=None, help="FILE.gmt: gene sets (name, description, members per line); "
                                                      "adds a score per cell and set with its posterior sd")
     p.add_argument("--set-draws", type=int, default=32, help="posterior draws of the gene-set scores (>= 2)")
@@ -147,8 +157,13 @@ def main(argv=None):
         print(f"factor {p}: " + ", ".join(f"{gene_names[j]}({gene_score[p, j]:.3g})" for j in top))
     top = np.argsort(W[0, :])[::-1][:P * args.top]                                     # :174-175
     print("intercept: " + ", ".join(str(gene_names[j]) for j in top))
+    clusters = None
+    if args.clusters is not None:
+        clusters = cluster_cells(factor, X, f"{stem}_cluster_{P}.npy", f"{stem}_centroid_{P}.npy", args)
     if args.labels is not None:
         group_table(factor, X, np.load(args.labels), gene_names, f"{stem}_groupmean_{P}.npy", args)
+    elif clusters is not None:
+        group_table(factor, X, clusters, gene_names, f"{stem}_groupmean_{P}.npy", args, n_groups=args.clusters)
     if args.gene_sets is not None:
         gene_set_scores(factor, X, gene_names, f"{stem}_setscore_{P}.npy", f"{stem}_setscore_sd_{P}.npy", args)
     if args.gene_waic:
@@ -180,11 +195,28 @@ def gene_set_scores(factor, X, gene_names, path, sd_path, args):
     np.save(sd_path, res["sd"].cpu().numpy())
 
 
-def group_table(factor, X, labels, gene_names, path, args):
+def cluster_cells(factor, X, labels_path, centroid_path, args):
+    """k-means of the cells in the latent space (``cluster``): the labels and the centroids as files; -> the
+    labels on the device, as ``group_means`` takes them (only the files' copies leave it)."""
+    import torch
+    torch.manual_seed(args.cluster_seed)                  # the posterior draws of the encoding
+    res = factor.cluster({factor.count_key: X}, args.clusters, nsamples=args.cluster_draws,
+                         seed=args.cluster_seed)
+    labels = res["labels"]
+    np.save(labels_path, labels.cpu().numpy())
+    np.save(centroid_path, res["centroids"].cpu().numpy())
+    sizes = ", ".join(str(n) for n in res["counts"].tolist())
+    print(f"clusters: {args.clusters} after {res['n_iter']} iterations"
+          f"{'' if res['converged'] else ' (not converged)'}, inertia {res['inertia']:.6g}, cells {sizes}"
+          + (f", {res['n_unassigned']} without a cluster" if res["n_unassigned"] else ""))
+    return labels
+
+
+def group_table(factor, X, labels, gene_names, path, args, n_groups=None):
     """The marker-gene table: group means over the posterior draws and the log fold change of every group
     against the rest."""
     from spmf_amd import groups
-    res = factor.group_means({factor.count_key: X}, labels, nsamples=args.group_draws)
+    res = factor.group_means({factor.count_key: X}, labels, n_groups=n_groups, nsamples=args.group_draws)
     np.save(path, res["mean"].cpu().numpy())
     count = res["count"].cpu().numpy()
     filled = [g for g in range(len(count)) if count[g] > 0]

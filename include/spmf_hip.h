@@ -850,6 +850,51 @@ int spmf_knn(spmf_ctx* ctx, const float* q, int64_t n_query, const float* r, int
              int row_len, int k, unsigned flags, int64_t self_offset, int32_t* idx_out,
              float* dist_out, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- one Lloyd step of k-means (added within ABI 6: two new entry points, no struct changed) ----
+ * For the rows x [n_rows][row_len] and the centroids [n_clusters][row_len] (fp32, device,
+ * 1 <= row_len <= 256 whatever the context's K, 1 <= n_clusters <= 65536): every row's nearest
+ * centroid, and per cluster the fp64 sums of its rows from which the caller forms the next
+ * centroids (csrc/kmeans.hip behind csrc/knn.hip).  Like spmf_knn the call takes rows as given: the
+ * context serves the error message and the device only.
+ *   Assignment: labels_out[i] and dist_out[i] are, bit for bit, idx_out[i][0] and dist_out[i][0]
+ * of spmf_knn(q = x, r = centroids, k = min(4, n_clusters), flags = 0, self_offset = -1) -- the
+ * same launches: the centre is the mean of the finite centroids, the score <x', c'> - 1/2 |c'|^2 on
+ * the exact-f32 matrix cores, and the best min(4, G) candidates are refined by the fmaf chain of
+ * squared differences in ascending k and ordered by (distance, index).  Four candidates, not one:
+ * the expansion decides membership only at near-ties, the label is the exact-distance minimum among
+ * them.  A non-finite row of x gets label -1 and distance +inf; a non-finite centroid is nobody's
+ * label; of equal centroids the smaller index wins.  labels_out int32 [n_rows]; dist_out fp32
+ * [n_rows], may be NULL.  A row's label and distance do not depend on the other rows or on its
+ * position.
+ *   Accumulation: sums_out[g][k], fp64 [n_clusters][row_len], = the sum of (double)x[i][k] over the
+ * rows labelled g; counts_out[g], int64, their number; stats_out[0] = the sum of (double)dist_i^2
+ * over the labelled rows, stats_out[1] = the rows with labels_out[i] != prev_labels[i] (n_rows when
+ * prev_labels is NULL), stats_out[2] = the rows with label -1 (fp64 [3]).  All outputs are
+ * overwritten, not added to.  Every addition is fp64 from the first one on: no fp32 partial sums, no
+ * floating-point atomics.
+ *   Orders: the rows are put in label order, stable in the row index, every cluster in whole 64-row
+ * blocks (the ordering of spmf_group_sums).  With KP = row_len rounded up to 4, 8, .., 256, the rows
+ * at positions rr, rr + 256 / KP, .. of a cluster's blocks are added in ascending order, blocks
+ * ascending, per run of blocks; the 256 / KP partial sums are added in ascending rr, and a cluster's
+ * runs in ascending order.  The statistics add 256 rows by a fixed tree and those sums in a fixed
+ * order.  All of it is a function of (n_rows, n_clusters, row_len, the labels) alone: two calls
+ * return the same bits.
+ * scratch: 256-byte aligned, at least spmf_kmeans_scratch_bytes(ctx, n_rows, n_clusters, row_len)
+ * bytes, non-decreasing in n_rows; the size is 0 for bad arguments.
+ * SPMF_E_ARG for n_clusters outside 1..65536, row_len outside 1..256, n_rows outside 0..2^31 - 64,
+ * prev_labels == labels_out, NULL sums_out / counts_out / stats_out, NULL x / centroids /
+ * labels_out with n_rows > 0, a NULL or misaligned scratch; then SPMF_E_WORKSPACE for a short
+ * scratch, naming the need; every error returns before any launch or write with "kmeans_step: " in
+ * front of the message.  n_rows == 0 returns SPMF_OK after zero fills of sums_out, counts_out and
+ * stats_out on the stream.  The context's workspace is not touched: the call may sit between
+ * spmf_step_begin and spmf_step_end.  Stream-ordered, synchronises nowhere. */
+size_t spmf_kmeans_scratch_bytes(const spmf_ctx* ctx, int64_t n_rows, int32_t n_clusters,
+                                 int row_len);
+int spmf_kmeans_step(spmf_ctx* ctx, const float* x, int64_t n_rows, int row_len,
+                     const float* centroids, int32_t n_clusters, const int32_t* prev_labels,
+                     int32_t* labels_out, float* dist_out, double* sums_out, int64_t* counts_out,
+                     double* stats_out, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Reductions of the non-finite rule (poisson.py:606-616) over a dense ll
  * buffer of n cells; io = double[3] on the device.
  *   pass 0: io[0] = min(io[0], min over finite cells)  (initialise io[0]=0:

@@ -1,5 +1,5 @@
 // api_stream.hip -- the streaming calls behind the C-ABI (include/spmf_hip.h): the draw stage, its consumers'
-// entries, and spmf_knn.  Host-side orchestration only (ctx.h).
+// entries, spmf_knn and spmf_kmeans_step.  Host-side orchestration only (ctx.h).
 #include <stdlib.h>
 
 #include "ctx.h"
@@ -565,7 +565,9 @@ static int knn_padded(int row_len) {
 }
 // The shape (the padded row length; the reference slices of the select launch, where the queries take the place
 // of top-k's rows and the reference rows that of its columns) and the scratch of a call, all into ka
-static void knn_layout(Arena& a, const spmf_ctx* c, int64_t n_query, int64_t n_ref, int row_len, KnnArgs& ka) {
+// (part_slots >= 0: the slots of the slices' results to carve instead of knn's own count -- kmeans_layout)
+static void knn_layout(Arena& a, const spmf_ctx* c, int64_t n_query, int64_t n_ref, int row_len, KnnArgs& ka,
+    int64_t part_slots = -1) {
   ka.n_query = n_query; ka.n_ref = n_ref; ka.row_len = row_len;
   ka.KP = knn_padded(row_len);
   ka.slices = n_ref > 0 ? topk_slices(n_query, (int)n_ref, device_cus(c)) : 1;
@@ -576,7 +578,7 @@ static void knn_layout(Arena& a, const spmf_ctx* c, int64_t n_query, int64_t n_r
   ka.cpart = a.take<float>(kKnnCentreBlocks * KP);
   ka.ccnt = a.take<int32_t>(kKnnCentreBlocks);
   ka.centre = a.take<float>(KP);
-  const size_t part = ka.slices > 1 ? (size_t)ka.slices * nq * kTopkMaxK : 0;
+  const size_t part = part_slots >= 0 ? (size_t)part_slots : ka.slices > 1 ? (size_t)ka.slices * nq * kTopkMaxK : 0;
   ka.part_idx = a.take<int32_t>(part);
   ka.part_score = a.take<float>(part);
 }
@@ -624,6 +626,85 @@ int spmf_knn(spmf_ctx* c, const float* q, int64_t n_query, const float* r, int64
   if (q == r && n_query == n_ref) ka.qw = ka.rw;
   ka.idx = idx_out; ka.dist = dist_out;
   return launched(c, launch_knn(ka, (hipStream_t)stream), "knn: no kernel for this row_len / k");
+}
+
+// ---- one Lloyd step of k-means (kmeans.hip behind knn.hip and groups.hip's ordering) -----------
+// Scratch of one call: knn's carve for the rows as queries and the centroids as reference set, the refined
+// candidates [rows][4], the ordering of the rows by label (launch_group_order), the segments' partial sums and the
+// statistics' partial sums (kernels.h kmeans_geom bounds them).  knn's slices drop to one as the rows grow, and
+// their results with them; here they are carved at their bound over all row counts, slices * rows <= 64 * (2 CUs +
+// row blocks) with at most 4 candidates each, so that the size is non-decreasing in the rows.
+constexpr int32_t kKmeansMaxClusters = 65536;
+constexpr int kKmeansCand = 4;
+static void kmeans_layout(Arena& a, const spmf_ctx* c, int64_t rows, int G, int row_len, KnnArgs& ka, KmeansArgs& ma) {
+  const KmeansGeom q = kmeans_geom(rows, G);
+  const size_t nr = rows, nG = G, NB = (size_t)q.NB;
+  knn_layout(a, c, rows, G, row_len, ka, 64 * (2 * (int64_t)device_cus(c) + (rows + 63) / 64) * kKmeansCand);
+  ka.k = ma.kc = G < kKmeansCand ? G : kKmeansCand;
+  ka.idx = a.take<int32_t>(nr * kKmeansCand);
+  ka.dist = a.take<float>(nr * kKmeansCand);
+  ma.tbl = a.take<int32_t>((size_t)q.chunks * nG);
+  ma.lrank = a.take<int32_t>(nr);
+  ma.cnt = a.take<int32_t>(nG);
+  ma.boff = a.take<int32_t>(nG + 1);
+  ma.fincl = a.take<int32_t>(nG);
+  ma.rec = a.take<int4>(NB);
+  ma.perm = a.take<int32_t>(NB * 64);
+  ma.part = a.take<double>((size_t)q.nseg * row_len);
+  ma.spart = a.take<double>((size_t)q.sblocks * 3);
+}
+static bool kmeans_shape_ok(int64_t n_rows, int32_t G, int row_len) {
+  return n_rows >= 0 && n_rows <= ((int64_t)1 << 31) - 64 && G >= 1 && G <= kKmeansMaxClusters && row_len >= 1 &&
+      row_len <= 256;
+}
+
+size_t spmf_kmeans_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int32_t n_clusters, int row_len) {
+  if (!c || !kmeans_shape_ok(n_rows, n_clusters, row_len)) return 0;
+  Arena a;
+  KnnArgs ka{};
+  KmeansArgs ma{};
+  kmeans_layout(a, c, n_rows, n_clusters, row_len, ka, ma);
+  return a.used;
+}
+
+int spmf_kmeans_step(spmf_ctx* c, const float* x, int64_t n_rows, int row_len, const float* centroids,
+    int32_t n_clusters, const int32_t* prev_labels, int32_t* labels_out, float* dist_out, double* sums_out,
+    int64_t* counts_out, double* stats_out, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!c) return SPMF_E_ARG;
+  const std::string f = "kmeans_step: ";
+  if (n_clusters < 1 || n_clusters > kKmeansMaxClusters) return fail(c, SPMF_E_ARG, f + "n_clusters must be in "
+      "1..65536");
+  if (row_len < 1 || row_len > 256) return fail(c, SPMF_E_ARG, f + "row_len must be in 1..256");
+  if (n_rows < 0 || n_rows > ((int64_t)1 << 31) - 64) return fail(c, SPMF_E_ARG, f + "n_rows must be in "
+      "0..2^31 - 64");
+  if (prev_labels && prev_labels == labels_out) return fail(c, SPMF_E_ARG, f + "prev_labels must not be labels_out");
+  if (!scratch) return fail(c, SPMF_E_ARG, f + "null argument");
+  if (!sums_out || !counts_out || !stats_out || (n_rows > 0 && (!x || !centroids || !labels_out))) return fail(c,
+      SPMF_E_ARG, f + "null argument");
+  if ((uintptr_t)scratch & 255) return fail(c, SPMF_E_ARG, f + "scratch must be 256-byte aligned");
+  KnnArgs ka{};
+  KmeansArgs ma{};
+  Arena a(scratch, scratch_bytes);
+  kmeans_layout(a, c, n_rows, n_clusters, row_len, ka, ma);
+  if (!a.fits()) return scratch_too_small(c, "kmeans_step", a.used, scratch_bytes,
+      "n_rows=" + std::to_string((long long)n_rows) + " n_clusters=" + std::to_string(n_clusters) + " row_len=" +
+      std::to_string(row_len));
+  hipStream_t st = (hipStream_t)stream;
+  if (n_rows == 0) {
+    HIPCHK(c, hipMemsetAsync(sums_out, 0, (size_t)n_clusters * row_len * sizeof(double), st));
+    HIPCHK(c, hipMemsetAsync(counts_out, 0, (size_t)n_clusters * sizeof(int64_t), st));
+    HIPCHK(c, hipMemsetAsync(stats_out, 0, 3 * sizeof(double), st));
+    return SPMF_OK;
+  }
+  // the assignment: spmf_knn's launches with q = x, r = centroids, k = min(4, G), Euclidean, no self
+  ka.cosine = false; ka.tile = knn_tile(); ka.self_offset = -1;
+  ka.q = x; ka.r = centroids;
+  if (!launch_knn(ka, st)) return fail(c, SPMF_E_UNSUPPORTED, f + "no kernel for this row_len");
+  ma.n_rows = n_rows; ma.row_len = row_len; ma.n_clusters = n_clusters;
+  ma.x = x; ma.cand_idx = ka.idx; ma.cand_dist = ka.dist; ma.prev = prev_labels;
+  ma.labels = labels_out; ma.dist = dist_out; ma.sums = sums_out; ma.counts = counts_out; ma.stats = stats_out;
+  launch_kmeans(ma, st);
+  return launched(c, true, "");
 }
 
 }  // extern "C"

@@ -311,6 +311,22 @@ __global__ __launch_bounds__(256) void group_combine_kernel(int S, int G, int C,
   }
 }
 
+// The ordering alone (kmeans.hip orders its rows by label with it): tbl [ceil(B / kGroupRowChunk)][G], lrank [B],
+// cnt [G], boff [G + 1], fincl [G], perm [64 NB], rec [NB] with NB = ceil(B / 64) + G; RB numbers the segments.
+void launch_group_order(int64_t B, int G, int RB, const int32_t* labels, int32_t* tbl, int32_t* lrank, int32_t* cnt,
+                        int32_t* boff, int32_t* fincl, int32_t* perm, int4* rec, hipStream_t st) {
+  const int64_t chunks = (B + kGroupRowChunk - 1) / kGroupRowChunk;
+  const int64_t NB = (B + 63) / 64 + G, NP = NB * 64;
+  launch_zero(tbl, (size_t)chunks * G * sizeof(int32_t), st);
+  hipLaunchKernelGGL(group_rank_kernel, dim3((unsigned)chunks), dim3(kGroupRowChunk), 0, st, B, G, labels, lrank, tbl);
+  hipLaunchKernelGGL(group_scan_kernel, dim3((unsigned)G), dim3(64), 0, st, chunks, G, tbl, cnt);
+  hipLaunchKernelGGL(group_offsets_kernel, dim3(1), dim3(256), 0, st, G, RB, cnt, boff, fincl);
+  hipLaunchKernelGGL(group_fill_kernel, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, st, NB, G, RB, cnt, boff,
+                     fincl, perm, rec);
+  hipLaunchKernelGGL(group_scatter_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, B, G, labels, lrank,
+                     tbl, boff, perm);
+}
+
 bool launch_groups(const GroupArgs& a, hipStream_t st) {
   DrawTables t = a.t;
   const int C = a.n_cols, G = a.n_groups;
@@ -319,15 +335,7 @@ bool launch_groups(const GroupArgs& a, hipStream_t st) {
   const GroupGeom q = group_geom(t.B, t.S, G, C);
   const int64_t NP = q.NB * 64;
 
-  launch_zero(a.tbl, (size_t)q.chunks * G * sizeof(int32_t), st);
-  hipLaunchKernelGGL(group_rank_kernel, dim3((unsigned)q.chunks), dim3(kGroupRowChunk), 0, st, t.B, G, a.labels,
-                     a.lrank, a.tbl);
-  hipLaunchKernelGGL(group_scan_kernel, dim3((unsigned)G), dim3(64), 0, st, q.chunks, G, a.tbl, a.cnt);
-  hipLaunchKernelGGL(group_offsets_kernel, dim3(1), dim3(256), 0, st, G, q.RB, a.cnt, a.boff, a.fincl);
-  hipLaunchKernelGGL(group_fill_kernel, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, st, q.NB, G, q.RB, a.cnt,
-                     a.boff, a.fincl, a.perm, a.rec);
-  hipLaunchKernelGGL(group_scatter_kernel, dim3((unsigned)((t.B + 255) / 256)), dim3(256), 0, st, t.B, G, a.labels,
-                     a.lrank, a.tbl, a.boff, a.perm);
+  launch_group_order(t.B, G, q.RB, a.labels, a.tbl, a.lrank, a.cnt, a.boff, a.fincl, a.perm, a.rec, st);
   const int64_t n4 = NP * (t.KP / 4);
   hipLaunchKernelGGL(group_gather_kernel, dim3((unsigned)((n4 + 255) / 256), (unsigned)t.S), dim3(256), 0, st, t.B,
                      NP, t.KP, a.perm, t.z, a.zs);

@@ -385,6 +385,42 @@ struct GroupArgs {
   double* part;                    // part_bytes
 };
 bool launch_groups(const GroupArgs& a, hipStream_t st);
+// groups.hip: the ordering of launch_groups alone (group_rank .. group_scatter): the B rows in label order,
+// stable in the row index, every group padded to whole 64-row blocks.  perm [64 NB] (row, -1 in a pad slot), rec
+// [NB] (group, valid rows, segment, 0; group -1 for a surplus block), cnt [G], boff [G + 1] (first block of a
+// group, boff[G] = blocks in use), with NB = ceil(B / 64) + G; tbl [ceil(B / kGroupRowChunk)][G], lrank [B] and
+// fincl [G] are its working arrays.  A segment is the blocks of one group inside one run of RB blocks.  B > 0.
+void launch_group_order(int64_t B, int G, int RB, const int32_t* labels, int32_t* tbl, int32_t* lrank, int32_t* cnt,
+                        int32_t* boff, int32_t* fincl, int32_t* perm, int4* rec, hipStream_t st);
+// kmeans.hip: one Lloyd step behind launch_knn (include/spmf_hip.h spmf_kmeans_step has the definition).  cand_idx /
+// cand_dist [n_rows][kc] are launch_knn's refined result for q = x, r = centroids, k = kc = min(4, G).  The
+// scratch pointers are api_stream.hip's carve, sized from kmeans_geom, a pure function of (n_rows, G): the order
+// of every sum depends on (n_rows, the labels) alone.  n_rows > 0.
+constexpr int kKmeansTargetRuns = 2048;  // runs of row blocks aimed at (a constant: not the device's CU count)
+constexpr int kKmeansStatRows = 256;     // rows per partial sum of the statistics
+struct KmeansGeom {
+  int64_t NB, chunks, nseg, sblocks;   // as GroupGeom; sblocks = ceil(n_rows / kKmeansStatRows)
+  int runs, RB;
+};
+KmeansGeom kmeans_geom(int64_t n_rows, int G);
+struct KmeansArgs {
+  int64_t n_rows;
+  int row_len, n_clusters, kc;
+  const float* x;                  // [n_rows][row_len]
+  const int32_t* cand_idx;         // [n_rows][kc]
+  const float* cand_dist;
+  const int32_t* prev;             // [n_rows] or null
+  int32_t* labels;                 // [n_rows]
+  float* dist;                     // [n_rows] or null
+  double* sums;                    // [G][row_len]
+  int64_t* counts;                 // [G]
+  double* stats;                   // [3]
+  int32_t *tbl, *lrank, *cnt, *boff, *fincl, *perm;   // as launch_group_order
+  int4* rec;
+  double* part;                    // [nseg][row_len]
+  double* spart;                   // [sblocks][3]
+};
+void launch_kmeans(const KmeansArgs& a, hipStream_t st);
 // sets.hip: per row and column set the fp64 weighted sum over the set's listed columns of the posterior
 // predictive mean m_s, reduced over the draws: mean [B][ld] (column g = set g) and, where asked for, the unbiased
 // standard deviation over the draws (S >= 2).  set_ptr: HOST, [n_sets + 1], set g lists cols[set_ptr[g] ..

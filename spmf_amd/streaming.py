@@ -1,6 +1,6 @@
 """The streaming posterior queries of the model classes: ``StreamingQueries`` is the mixin that gives
 PoissonFactorization (and through it the Bernoulli and mixed classes) waic_streaming, top_k, score_cells,
-rank_cells, predict, top_rows, group_means, set_scores, embed, knn and neighbors.
+rank_cells, predict, top_rows, group_means, set_scores, embed, knn, neighbors, kmeans and cluster.
 
 Every draw-stage query is the same three pieces around its own kernel (include/spmf_hip.h, csrc/api_stream.hip "the
 draw stage"): ``_Draws``, the checked draws and the one place a library call is spelled; a driver that walks
@@ -741,3 +741,65 @@ class StreamingQueries:
             return self.knn(ref, k=k, metric=metric, include_self=include_self)
         qry = self.embed(query, nsamples=nsamples, draws=draws, max_rows=max_rows)["mean"]
         return self.knn(ref, k=k, queries=qry, metric=metric, include_self=True)
+
+    def kmeans(self, points, n_clusters, init="k-means++", max_iter=100, seed=0):
+        """Deterministic k-means (Lloyd's iteration) of the rows of ``points`` [N, Kx], a float32 tensor on the
+        model's device with 1 <= Kx <= 256 whatever the model's latent_dim, into 1 <= ``n_clusters`` <= 65536
+        clusters.  One library call per iteration (include/spmf_hip.h spmf_kmeans_step, csrc/kmeans.hip): the
+        assignment is ``knn``'s -- the label of a row is, bit for bit,
+        ``knn(centroids, k=min(4, G), queries=points)["indices"][:, 0]`` -- and the clusters' sums are fp64 in
+        a fixed order, so two runs of an iteration give the same centroids.
+
+        ``init``: 'k-means++' (``spmf_amd.cluster.init_plus_plus`` with ``seed``), 'first' (the first
+        ``n_clusters`` finite rows) or a float32 [n_clusters, Kx] tensor on the device.  The loop: a step on
+        the current centroids; stop when no label changed; else centroids = sums / counts in fp64 rounded to
+        float32, an empty cluster keeping its centroid; at most ``max_iter`` steps.  One read-back of three
+        numbers per iteration.
+
+        Returns {'labels': int32 [N] (-1: a non-finite row), 'distances': float32 [N] (+inf beside -1),
+        'centroids': float32 [G, Kx], 'counts': int64 [G]} on the device and 'inertia' (the sum of the squared
+        distances), 'n_iter', 'converged', 'n_unassigned'.  Every output refers to the returned centroids, at
+        ``max_iter`` too.  Bit-reproducible for a tensor or 'first' init; for 'k-means++' the same seed gives
+        the same result on the same machine."""
+        from . import cluster as _cluster
+        G, max_iter = _cluster.check_args("kmeans", n_clusters, max_iter, init)
+        pts = self._knn_rows("kmeans", "points", points)
+        if isinstance(init, torch.Tensor):
+            _cluster.check_init_tensor("kmeans", init, G, pts)
+        if pts.shape[0] > 2 ** 31 - 64:
+            raise ValueError(f"kmeans: {pts.shape[0]} points are beyond one call of the library")
+        dev = torch.device(self.device)
+        if pts.device.type != "cuda" or (dev.index is not None and pts.device != dev):
+            raise ValueError(f"kmeans: points must be on the model's device {self.device}, got {pts.device}")
+        pts = pts.contiguous()
+        if isinstance(init, torch.Tensor):
+            start = init
+        elif init == "first":
+            start = _cluster.init_first(pts, G)
+        else:
+            start = _cluster.init_plus_plus(pts, G, seed)
+        return _cluster.lloyd(self._handle(), pts, start, max_iter)
+
+    def cluster(self, data, n_clusters, nsamples=32, draws=None, max_rows=None, init="k-means++", max_iter=100,
+                seed=0):
+        """k-means of the rows of ``data`` in the model's latent space: ``embed`` on ``data``, then ``kmeans``
+        on the posterior mean encodings, with no labelling leaving the device in between.  ``data``,
+        ``nsamples`` / ``draws`` and ``max_rows`` as in ``embed`` (the rows of all batches are concatenated);
+        ``n_clusters``, ``init``, ``max_iter`` and ``seed`` as in ``kmeans``.
+
+        Returns what ``kmeans`` returns, bit for bit ``kmeans(embed(data, draws=draws)["mean"], ...)``, and
+        'embedding': float32 [N, latent_dim].  The labels are those ``group_means`` takes."""
+        from . import cluster as _cluster
+        G, max_iter = _cluster.check_args("cluster", n_clusters, max_iter, init)
+        if not 1 <= self.latent_dim <= 256:
+            raise ValueError(f"cluster: latent_dim {self.latent_dim} is beyond the 256 columns of kmeans")
+        if isinstance(init, torch.Tensor):        # (its device is checked against the embedding's, in kmeans)
+            if init.dim() != 2 or tuple(init.shape) != (G, self.latent_dim):
+                raise ValueError(f"cluster: an init tensor must have shape {(G, self.latent_dim)}, got "
+                                 f"{tuple(init.shape)}")
+            if init.dtype != torch.float32:
+                raise ValueError(f"cluster: an init tensor must be float32, got {init.dtype}")
+        emb = self.embed(data, nsamples=nsamples, draws=draws, max_rows=max_rows)["mean"]
+        res = self.kmeans(emb, G, init=init, max_iter=max_iter, seed=seed)
+        res["embedding"] = emb
+        return res
