@@ -1,11 +1,14 @@
-"""What the tests of the streaming calls share: the cached problems of the GPU files and, for the C-ABI, ONE
-contract table of the draw-stage entry points (waic_streaming / spmf_waic_accumulate, top_k / spmf_topk_rows,
-score_cells / spmf_score_cells, rank_cells / spmf_rank_cells, predict / spmf_predict_columns, group_means /
-spmf_group_sums, embed / spmf_embed_rows): each entry as a raw ctypes call with a dict of good arguments --
-dummy addresses without a device (host_good_call), real buffers with one (gpu_good_call) -- plus the error
-contract of the draw stage they have in common (include/spmf_hip.h), asserted by one function on a device
+"""What the tests of the streaming calls share: the cached problems of the GPU files, the host helpers of the
+*_host.py files (library, cpu_model, no_library, host_ctx) and, for the C-ABI, ONE contract table of the
+draw-stage entry points, every one that include/spmf_hip.h declares (waic_streaming / spmf_waic_accumulate and
+spmf_waic_accumulate_cols, top_k / spmf_topk_rows, score_cells / spmf_score_cells, rank_cells / spmf_rank_cells,
+predict / spmf_predict_columns, group_means / spmf_group_sums, embed / spmf_embed_rows, top_rows /
+spmf_toprows_columns, set_scores / spmf_set_scores): each entry as a raw ctypes call with a dict of good
+arguments -- dummy addresses without a device (host_good_call), real buffers with one (gpu_good_call) -- plus the
+error contract of the draw stage they have in common (include/spmf_hip.h), asserted by one function on a device
 (test_gpu_stream_abi.py) and without one (test_stream_host.py).  A new draw-stage call adds one row to ENTRIES
-and one branch to each of the two good calls.
+and one branch to each of the two good calls.  spmf_knn and spmf_kmeans_step are no draw-stage calls: each has
+its argument list, raw call and error contract here once, behind the table's.
 """
 import collections
 import ctypes as C
@@ -27,8 +30,11 @@ BERN_DAMP = {"bernoulli": 1.0 / 64.0, "bernoulli_log": 1.0 / 8.0}
 
 # the shape of the contract tests: a ragged 64-row block, K padded 3 -> 4, two draws so that sd is defined
 B, D, K, S = 70, 45, 3, 2
-# the list of predict / groups in the good calls: four columns, one of them twice
+# the list of predict / groups / toprows in the good calls: four columns, one of them twice
 PANEL_COLS = (7, 0, 7, 44)
+# the sets of the GPU good call over those columns, one of them empty, and their weights (one set has some)
+PANEL_SETS = ((7, 0), (), (44, 7, 7))
+PANEL_WEIGHTS = ((0.5, -1.25), (), (1.0, 1.0, 1.0))
 
 # One row per entry point: the call, its scratch size, the smallest S, the Python method, `own`: the arguments
 # between `eta` and `scratch` in the header's order with their ctypes, `size_args`: those of `own` the size
@@ -52,7 +58,53 @@ ENTRIES = {
                     (5, 14)),
     "embed": Entry("spmf_embed_rows", "spmf_embed_scratch_bytes", 1, "embed", (("mean", _P), ("sd", _P)), (),
                    (3, 10)),
+    "waic_cols": Entry("spmf_waic_accumulate_cols", "spmf_waic_scratch_bytes", 2, "waic_streaming",
+                       (("sums", _P), ("rows", _P), ("colsum", _P)), (), (3, 11)),
+    "toprows": Entry("spmf_toprows_columns", "spmf_toprows_scratch_bytes", 1, "top_rows",
+                     (("n", _I32), ("cols", _P), ("k", C.c_int), ("flags", C.c_uint), ("rows", _P), ("scores", _P)),
+                     ("n",), (4, 14)),
+    # set_ptr is a HOST array the entry reads before anything else: a real int64 array in both good calls
+    "sets": Entry("spmf_set_scores", "spmf_sets_scratch_bytes", 1, "set_scores",
+                  (("n_sets", _I32), ("set_ptr", _P), ("cols", _P), ("weights", _P), ("ld", _I64), ("mean", _P),
+                   ("sd", _P)), ("n_sets", "set_ptr"), (5, 15)),
 }
+
+
+# ---- what the *_host.py files share ------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def library():
+    """The loaded library, built first where the shared object is missing."""
+    import __graft_entry__ as ge
+    from spmf_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        ge.build()
+    return _lib.load()
+
+
+def cpu_model(**kw):
+    """-> (a CPU-only Poisson model of 6 columns and K = 2, seeded counts [8, 6], two seeded draws)."""
+    from spmf_amd import PoissonFactorization
+    m = PoissonFactorization(latent_dim=2, feature_dim=6, initialize_distributions=False, device="cpu", **kw)
+    rng = np.random.default_rng(0)
+    x = rng.poisson(1.0, size=(8, 6)).astype(np.float64)
+    draws = {"u": rng.random((2, 6, 2)), "v": rng.random((2, 2, 6)), "w": rng.random((2, 1, 6)),
+             "s": rng.random((2, 2, 6))}
+    return m, x, draws
+
+
+def no_library(monkeypatch):
+    """Any load of the library from here on fails the test."""
+    from spmf_amd import _lib
+
+    def refuse():
+        raise AssertionError("the library was loaded before the arguments were checked")
+    monkeypatch.setattr(_lib, "load", refuse)
+
+
+def host_ctx(lib, k, flags=0, d=D):
+    h = C.c_void_p()
+    assert lib.spmf_ctx_create(0, k, d, flags, C.byref(h)) == 0
+    return h
 
 
 def assert_declared_exported_bound(name, nargs):
@@ -202,9 +254,7 @@ def host_good_call(lib, entry):
     cleanup); ``cleanup()`` destroys the two contexts."""
     from spmf_amd import _lib
     from spmf_amd._lib import VAR_ORDER
-    h, raw = C.c_void_p(), C.c_void_p()
-    assert lib.spmf_ctx_create(0, K, D, 0, C.byref(h)) == 0
-    assert lib.spmf_ctx_create(0, K, D, _lib.FLAG_MIXED, C.byref(raw)) == 0
+    h, raw = host_ctx(lib, K), host_ctx(lib, K, _lib.FLAG_MIXED)
 
     def cleanup():
         lib.spmf_ctx_destroy(h)
@@ -221,7 +271,11 @@ def host_good_call(lib, entry):
                             score=0x6000000),
                "predict": dict(n=4, cols=0x2000000, mean=0x3000000, sd=0x4000000, pnz=0x5000000),
                "groups": dict(labels=0x6000000, G=4, n=4, cols=0x2000000, sum=0x3000000, nz=0x5000000),
-               "embed": dict(mean=0x2000000, sd=0x3000000)}[entry]
+               "embed": dict(mean=0x2000000, sd=0x3000000),
+               "waic_cols": dict(sums=0x2000000, rows=None, colsum=0x3000000),
+               "toprows": dict(n=4, cols=0x2000000, k=5, flags=1, rows=0x3000000, scores=0x4000000),
+               "sets": dict(n_sets=2, set_ptr=(C.c_int64 * 3)(0, 4, 9), cols=0x2000000, weights=0x3000000, ld=2,
+                            mean=0x4000000, sd=0x5000000)}[entry]
         need = scratch_need(lib, entry, h, B, S, own)
         assert need > 0 and need % 256 == 0
         good = dict(h=h, ct=cs, S=S, pin=_lib.PtrArray(*[slots.get(n) for n in VAR_ORDER]), eta=0x7000000,
@@ -233,12 +287,13 @@ def host_good_call(lib, entry):
     return good, need, no_u, raw, cleanup
 
 
-def gpu_good_call(entry, m, x, params, k=5):
+def gpu_good_call(entry, m, x, params, k=5, sets=None):
     """The arguments of a valid call of ``entry`` on model ``m`` for the batch ``x`` and the draws ``params``,
     with an exactly sized scratch of zeros and outputs filled with the sentinel -7: -> (good, need, outputs,
-    scratch, pin_without_u).  topk: ``k``.  cells and rank: every cell once, row by row (cells: with values
-    0, 1, 2, 0, ...).  predict and groups: the columns PANEL_COLS; groups: G = 3 and the labels -1, 0, 1, 2,
-    -1, ... .  ``outputs`` holds the device tensors by argument name; ``good["keep"]`` keeps the inputs alive
+    scratch, pin_without_u).  topk and toprows: ``k``.  cells and rank: every cell once, row by row (cells: with
+    values 0, 1, 2, 0, ...).  predict, groups and toprows: the columns PANEL_COLS; groups: G = 3 and the labels
+    -1, 0, 1, 2, -1, ... .  sets: ``sets`` = (lists, weights, ld), else PANEL_SETS with PANEL_WEIGHTS and
+    ld = n_sets.  ``outputs`` holds the device tensors by argument name; ``good["keep"]`` keeps the inputs alive
     (the lists of an entry that has some come last, as a dict by argument name)."""
     from spmf_amd import _lib
     from spmf_amd._lib import VAR_ORDER
@@ -257,8 +312,10 @@ def gpu_good_call(entry, m, x, params, k=5):
         return {n: t.data_ptr() for d in dicts for n, t in d.items()}
     f32, f64, i32 = torch.float32, torch.float64, torch.int32
     lists = {}
-    if entry == "waic":
+    if entry in ("waic", "waic_cols"):
         out = {"sums": full((6,), f64), "rows": full((rows, 2), f64)}
+        if entry == "waic_cols":
+            out["colsum"] = full((width, 5), f64)
         own = ptrs(out)
     elif entry == "topk":
         out = {"cols": full((rows, k), i32), "scores": full((rows, k), f32)}
@@ -283,6 +340,18 @@ def gpu_good_call(entry, m, x, params, k=5):
                  "cols": torch.tensor(PANEL_COLS, dtype=i32, device="cuda")}
         out = {n: full((n_draws, 3, len(PANEL_COLS)), f64) for n in ("sum", "nz")}
         own = dict(G=3, n=len(PANEL_COLS), **ptrs(lists, out))
+    elif entry == "toprows":
+        lists = {"cols": torch.tensor(PANEL_COLS, dtype=i32, device="cuda")}
+        out = {"rows": full((len(PANEL_COLS), k), i32), "scores": full((len(PANEL_COLS), k), f32)}
+        own = dict(n=len(PANEL_COLS), k=k, flags=1, **ptrs(lists, out))
+    elif entry == "sets":
+        members, weights, ld = sets or (PANEL_SETS, PANEL_WEIGHTS, len(PANEL_SETS))
+        set_ptr = np.concatenate([[0], np.cumsum([len(s) for s in members])]).astype(np.int64)
+        lists = {"cols": torch.tensor([j for s in members for j in s], dtype=i32, device="cuda"),
+                 "weights": torch.tensor([w for s in weights for w in s], dtype=f32, device="cuda")}
+        out = {n: full((rows, ld), f64) for n in ("mean", "sd")}
+        own = dict(n_sets=len(members), set_ptr=set_ptr.ctypes.data, ld=ld, **ptrs(lists, out))
+        lists["set_ptr"] = set_ptr
     else:
         out = {n: full((rows, m.latent_dim), f32) for n in ("mean", "sd")}
         own = ptrs(out)
@@ -298,31 +367,34 @@ def gpu_good_call(entry, m, x, params, k=5):
 def assert_shared_errors(lib, entry, good, need, pin_without_u, mixed_ctx_without_types, after=lambda: None):
     """The error contract of the draw stage for one entry point; every call here returns before a launch, and
     ``after`` is run behind each (the GPU files check their sentinels there).  ``good``: arguments of a valid
-    call whose scratch holds exactly ``need`` bytes.  -> the raw call."""
+    call whose scratch holds exactly ``need`` bytes.  Every refusal's message, read from the context the call was
+    made on, starts with the entry's name; the descriptor's own two are check_counts', worded for every call
+    alike.  -> the raw call."""
     call = abi_call(entry, good)
-    h = good["h"]
+    own_prefix = ENTRIES[entry].call[len("spmf_"):] + ": "
 
-    def refused(code, why=None, **kw):
+    def refused(code, why=None, prefix=own_prefix, **kw):
         assert call(**kw) == code, why or kw
+        msg = lib.spmf_last_error(kw.get("h", good["h"])).decode()
+        assert msg.startswith(prefix), (why or kw, msg)
         after()
+        return msg
     refused(-1, "S below the minimum", S=ENTRIES[entry].min_S - 1)
     refused(-1, S=65536)
-    for name in ("pin", "eta", "ptr", "ct"):
+    for name in ("pin", "eta", "ptr"):
         refused(-1, **{name: None})
+    refused(-1, prefix="counts is null", ct=None)
     refused(-1, "slot u missing", pin=pin_without_u)
-    refused(-1, "scratch off by 4 bytes", ptr=good["ptr"] + 4)
+    assert "aligned" in refused(-1, "scratch off by 4 bytes", ptr=good["ptr"] + 4)
     bad = type(good["ct"]).from_buffer_copy(good["ct"])
     bad.struct_size += 8
-    refused(-1, "struct_size + 8", ct=bad)
-    refused(-1, h=mixed_ctx_without_types)
-    assert "column_types" in lib.spmf_last_error(mixed_ctx_without_types).decode()
-    refused(-3, nbytes=need - 256)
-    msg = lib.spmf_last_error(h).decode()
-    assert str(need) in msg, msg
+    refused(-1, "struct_size + 8", prefix="counts.struct_size is ", ct=bad)
+    assert "column_types" in refused(-1, h=mixed_ctx_without_types)
+    assert str(need) in refused(-3, nbytes=need - 256)
     return call
 
 
-# ---- spmf_knn and spmf_embed_rows: their own argument errors, asserted with and without a device ----------------
+# ---- spmf_knn, spmf_kmeans_step and spmf_embed_rows: their own argument errors, with and without a device ----------
 KNN_ARGS = (("q", C.c_void_p), ("nq", C.c_int64), ("r", C.c_void_p), ("nr", C.c_int64), ("row_len", C.c_int),
             ("k", C.c_int), ("flags", C.c_uint), ("self_offset", C.c_int64), ("idx", C.c_void_p),
             ("dist", C.c_void_p), ("ptr", C.c_void_p), ("nbytes", C.c_size_t), ("stream", C.c_void_p))
@@ -369,6 +441,53 @@ def assert_knn_errors(lib, good, need, after=lambda: None):
     refused(-3, nbytes=need - 256)
     assert str(need) in lib.spmf_last_error(h).decode()
     refused(-3, nq=0, nbytes=0)             # errors come before the empty return
+    assert call(h=None) == -1
+
+
+KMEANS_ARGS = (("x", C.c_void_p), ("n", C.c_int64), ("row_len", C.c_int), ("cent", C.c_void_p), ("G", C.c_int32),
+               ("prev", C.c_void_p), ("labels", C.c_void_p), ("dist", C.c_void_p), ("sums", C.c_void_p),
+               ("counts", C.c_void_p), ("stats", C.c_void_p), ("ptr", C.c_void_p), ("nbytes", C.c_size_t),
+               ("stream", C.c_void_p))
+
+
+def kmeans_raw_call(good):
+    """-> call(**overrides): spmf_kmeans_step through a binding of its own with the arguments of ``good``."""
+    from spmf_amd import _lib
+    fn = C.CDLL(_lib.LIB_PATH).spmf_kmeans_step
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p] + [t for _, t in KMEANS_ARGS]
+
+    def call(**kw):
+        a = dict(good, **kw)
+        return fn(a["h"], *[a[n] for n, _ in KMEANS_ARGS])
+    return call
+
+
+def assert_kmeans_errors(lib, good, need, after=lambda: None):
+    """The error contract of spmf_kmeans_step; every call here returns before a launch or a memset, and ``after``
+    is run behind each (the GPU file checks its sentinels there)."""
+    call, h = kmeans_raw_call(good), good["h"]
+
+    def refused(code, **kw):
+        assert call(**kw) == code, kw
+        msg = lib.spmf_last_error(h).decode()
+        assert msg.startswith("kmeans_step: "), msg
+        after()
+        return msg
+    for g in (0, -1, 65537):
+        assert "n_clusters" in refused(-1, G=g)
+    for w in (0, 257, -1):
+        assert "row_len" in refused(-1, row_len=w)
+    for rows in (-1, 2 ** 31 - 63, 2 ** 40):
+        assert "n_rows" in refused(-1, n=rows)
+    assert "prev_labels" in refused(-1, prev=good["labels"])
+    for name in ("x", "cent", "labels", "sums", "counts", "stats", "ptr"):
+        assert "null" in refused(-1, **{name: None})
+    for name in ("sums", "counts", "stats", "ptr"):
+        refused(-1, n=0, **{name: None})
+    assert "aligned" in refused(-1, ptr=good["ptr"] + 4)
+    assert str(need) in refused(-3, nbytes=need - 256)
+    refused(-3, n=0, nbytes=0)               # errors come before the empty return
     assert call(h=None) == -1
 
 

@@ -17,7 +17,6 @@ Shapes: the smallest at which the kernels can go wrong -- N in {1, 63, 65, 130, 
 130}, widths {1, 3, 8, 16, 33, 100, 256} (every padded width), each value once; 64 rows against 2 600 centroids
 (reference slices and the merge); 300 rows against 10 centroids shifted by 50 (the centring).
 """
-import ctypes as C
 import functools
 
 import numpy as np
@@ -25,7 +24,7 @@ import pytest
 import torch
 
 from _problems import _dense_model
-from _stream_cases import _problem
+from _stream_cases import _problem, assert_kmeans_errors, kmeans_raw_call
 
 pytestmark = pytest.mark.gpu
 T = torch.as_tensor
@@ -276,32 +275,15 @@ def test_raw_errors_leave_the_outputs_untouched_and_no_rows_zero_fill():
             "counts": torch.full((G,), -7, dtype=torch.int64, device="cuda"),
             "stats": torch.full((3,), -7.0, dtype=torch.float64, device="cuda")}
     prev = torch.zeros(N, dtype=torch.int32, device="cuda")
-    good = dict(x=x.data_ptr(), n=N, row_len=W, cent=c.data_ptr(), G=G, prev=prev.data_ptr(),
+    good = dict(h=h, x=x.data_ptr(), n=N, row_len=W, cent=c.data_ptr(), G=G, prev=prev.data_ptr(),
                 ptr=scratch.data_ptr() + (-scratch.data_ptr()) % 256, nbytes=need,
                 stream=torch.cuda.current_stream().cuda_stream, **{k: v.data_ptr() for k, v in outs.items()})
-    order = ("x", "n", "row_len", "cent", "G", "prev", "labels", "dist", "sums", "counts", "stats", "ptr", "nbytes",
-             "stream")
-    fn = C.CDLL(_lib.LIB_PATH).spmf_kmeans_step
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int32] + [C.c_void_p] * 7 + [
-        C.c_size_t, C.c_void_p]
+    call = kmeans_raw_call(good)
 
-    def call(**kw):
-        a = dict(good, **kw)
-        return fn(h, *[a[n] for n in order])
-
-    def refused(code, **kw):
-        assert call(**kw) == code, kw
-        assert lib.spmf_last_error(h).decode().startswith("kmeans_step: ")
+    def untouched():
         torch.cuda.synchronize()
-        assert all(bool((t == -7).all()) for t in outs.values()) and not bool(scratch.any()), kw
-    for kw in (dict(G=0), dict(G=65537), dict(row_len=0), dict(row_len=257), dict(n=-1), dict(n=2 ** 31 - 63),
-               dict(prev=good["labels"]), dict(x=None), dict(cent=None), dict(labels=None), dict(sums=None),
-               dict(counts=None), dict(stats=None), dict(ptr=None), dict(ptr=good["ptr"] + 4)):
-        refused(-1, **kw)
-    refused(-3, nbytes=need - 256)
-    assert str(need) in lib.spmf_last_error(h).decode()
-    refused(-3, n=0, nbytes=0)
+        assert all(bool((t == -7).all()) for t in outs.values()) and not bool(scratch.any())
+    assert_kmeans_errors(lib, good, need, after=untouched)
     # no rows: the zero fills, and nothing else
     assert call(n=0) == 0
     torch.cuda.synchronize()

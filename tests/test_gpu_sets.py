@@ -16,7 +16,6 @@ accumulation shows at 1e-7 -- and sd within 1e-9 max_s sum_j |w_j m_s|: the fp64
 Everything else is bit for bit: a repeat, a set alone, a set at another position, row chunks, runs of sets.
 The weights are drawn as fp64 and rounded to fp32 once, so that the references use the numbers the kernel
 sees."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -24,7 +23,7 @@ import pytest
 import torch
 
 from _problems import LIKELIHOODS, _dense_model, _dense_problem, build_model, make_problem
-from _stream_cases import SHAPES, _bar, _case
+from _stream_cases import SHAPES, _bar, _case, assert_shared_errors, gpu_good_call, host_ctx
 
 pytestmark = pytest.mark.gpu
 T = torch.as_tensor
@@ -239,71 +238,31 @@ def test_a_nan_row_is_nan_in_every_set_and_touches_no_other_row():
 
 def test_c_abi_errors_an_outside_column_the_row_stride_and_the_empty_calls():
     """Through ctypes with an exactly sized scratch of zeros and outputs filled with the sentinel -7: every
-    refused call (the draw stage's shared cases, then the entry's own) and every empty call leaves both
-    untouched; a listed column D makes its set NaN and no other; ld = n_sets + 2 leaves the two gap columns of
-    every row untouched; the valid sets have the bits of the Python call."""
+    refused call (the draw stage's shared cases, _stream_cases.assert_shared_errors, then the entry's own) and
+    every empty call leaves both untouched; a listed column D makes its set NaN and no other; ld = n_sets + 2
+    leaves the two gap columns of every row untouched; the valid sets have the bits of the Python call."""
     from spmf_amd import _lib
-    from spmf_amd._lib import VAR_ORDER
     B, D, K, S = 70, 45, 3, 2
     c = _scase("mixed", B, D, K, S)
     m, x, params = c["m"], c["x"], c["params"]
     lib, h = _lib.load(), m._handle()
-    _, cs = m._batch({"counts": x})
-    S_, P = m._pack_params(params, names=("s", "u", "v", "w"))
-    assert S_ == S
-    pin = _lib.PtrArray(*[P[n].data_ptr() if n in P else None for n in VAR_ORDER])
-    no_u = _lib.PtrArray(*[P[n].data_ptr() if n in P and n != "u" else None for n in VAR_ORDER])
-    eta = m._eta_device()
     lists = [[3, D, 7], [0, 44], [], [4, 4], list(range(D)) + [9]]
     wlists = [[1.0, 1.0, 1.0], [0.5, -1.25], [], [2.0, 1.0], [1.0] * (D + 1)]
-    G, ld = len(lists), len(lists) + 2
-    set_ptr = np.concatenate([[0], np.cumsum([len(s) for s in lists])]).astype(np.int64)
-    cols = torch.tensor(sum(lists, []), dtype=torch.int32, device="cuda")
-    wts = torch.tensor(sum(wlists, []), dtype=torch.float32, device="cuda")
-    need = int(lib.spmf_sets_scratch_bytes(h, int(cs.n_rows), S, G, set_ptr.ctypes.data))
-    assert need > 0 and need % 256 == 0
-    scratch = torch.zeros(need + 512, dtype=torch.uint8, device="cuda")
-    off = (-scratch.data_ptr()) % 256
-    outs = {n: torch.full((B, ld), -7.0, dtype=torch.float64, device="cuda") for n in ("mean", "sd")}
-    raw = C.c_void_p()
-    assert lib.spmf_ctx_create(0, K, D, _lib.FLAG_MIXED, C.byref(raw)) == 0
-    fn = C.CDLL(_lib.LIB_PATH).spmf_set_scores
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
-                   C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    good = dict(h=h, ct=cs, S=S, pin=pin, eta=eta.data_ptr(), n_sets=G, set_ptr=set_ptr.ctypes.data,
-                cols=cols.data_ptr(), weights=wts.data_ptr(), ld=ld, mean=outs["mean"].data_ptr(),
-                sd=outs["sd"].data_ptr(), ptr=scratch.data_ptr() + off, nbytes=need,
-                stream=torch.cuda.current_stream().cuda_stream)
-
-    def call(**kw):
-        a = dict(good, **kw)
-        return fn(a["h"], C.byref(a["ct"]) if a["ct"] is not None else None, a["S"], a["pin"], a["eta"],
-                  a["n_sets"], a["set_ptr"], a["cols"], a["weights"], a["ld"], a["mean"], a["sd"], a["ptr"],
-                  a["nbytes"], a["stream"])
+    G = len(lists)
+    good, need, outs, scratch, no_u = gpu_good_call("sets", m, x, params, sets=(lists, wlists, G + 2))
+    cs, set_ptr, off = good["ct"], good["keep"][-1]["set_ptr"], good["ptr"] - scratch.data_ptr()
+    assert good["S"] == S and good["ld"] == G + 2
+    raw = host_ctx(lib, K, _lib.FLAG_MIXED)        # a mixed context nobody gave column types
 
     def untouched():
         torch.cuda.synchronize()
         assert all(bool((t == -7.0).all()) for t in outs.values()) and not bool(scratch.any())
-
-    def refused(code, **kw):
-        assert call(**kw) == code, kw
-        untouched()
     try:
-        # the draw stage's shared cases (tests/_stream_cases.assert_shared_errors, spelled for this entry)
-        refused(-1, S=0)
-        refused(-1, S=65536)
-        for name in ("pin", "eta", "ptr", "ct"):
-            refused(-1, **{name: None})
-        refused(-1, pin=no_u)
-        refused(-1, ptr=good["ptr"] + 4)
-        bad = type(cs).from_buffer_copy(cs)
-        bad.struct_size += 8
-        refused(-1, ct=bad)
-        refused(-1, h=raw)
-        assert "column_types" in lib.spmf_last_error(raw).decode()
-        refused(-3, nbytes=need - 256)
-        assert str(need) in lib.spmf_last_error(h).decode()
+        call = assert_shared_errors(lib, "sets", good, need, no_u, raw, after=untouched)
+
+        def refused(code, **kw):
+            assert call(**kw) == code, kw
+            untouched()
         # the entry's own
         down = set_ptr.copy()
         down[2] = 1

@@ -1,7 +1,8 @@
 """GPU: the C-ABI error contract the draw-stage entry points share (the table of tests/_stream_cases.py:
 spmf_waic_accumulate, spmf_topk_rows, spmf_score_cells, spmf_rank_cells, spmf_predict_columns, spmf_group_sums,
-spmf_embed_rows: include/spmf_hip.h), through ctypes at B = 70, D = 45, K = 3, S = 2, Poisson, panel_rows = 32:
-a ragged 64-row block, K padded 3 -> 4, two draws so that sd is defined.  Every error returns before a launch:
+spmf_embed_rows, spmf_waic_accumulate_cols, spmf_toprows_columns, spmf_set_scores: include/spmf_hip.h), through
+ctypes at B = 70, D = 45, K = 3, S = 2, Poisson, panel_rows = 32: a ragged 64-row block, K padded 3 -> 4, two
+draws so that sd and the WAIC variance are defined.  Every error returns before a launch:
 outputs and scratch keep their sentinels.  Then the valid call returns what the Python method returns: the same
 bits for every entry but the WAIC sums, which go through fp64 atomics and are held to the tolerances of
 test_gpu_waic_streaming.py (lppd and waic 1e-5 relative, pwaic 1e-3, row scores the same with an atol of that
@@ -11,11 +12,12 @@ import numpy as np
 import pytest
 import torch
 
-from _stream_cases import B, D, K, S, ENTRIES, PANEL_COLS, _problem, assert_shared_errors, gpu_good_call
+from _stream_cases import (B, D, K, S, ENTRIES, PANEL_COLS, PANEL_SETS, PANEL_WEIGHTS, _problem,
+                           assert_shared_errors, gpu_good_call)
 from _problems import _dense_model
 
 pytestmark = pytest.mark.gpu
-ACCUMULATED = ("waic", "groups")          # entries that add into their outputs
+ACCUMULATED = ("waic", "groups", "waic_cols")          # entries that add into their outputs
 
 
 def _bits(t):
@@ -72,7 +74,13 @@ def test_shared_errors_launch_nothing_and_the_valid_call_is_the_methods(entry):
     elif entry == "embed":
         want = m.embed(batch, draws=params, sd=True)
         assert _same(out["mean"], want["mean"]) and _same(out["sd"], want["sd"])
-    else:
+    elif entry == "toprows":
+        want = m.top_rows(batch, cols=list(PANEL_COLS), k=good["k"], draws=params)
+        assert torch.equal(out["rows"].long(), want["rows"]) and _same(out["scores"], want["scores"])
+    elif entry == "sets":
+        want = m.set_scores(batch, PANEL_SETS, PANEL_WEIGHTS, draws=params, sd=True)
+        assert _same(out["mean"], want["mean"]) and _same(out["sd"], want["sd"])
+    else:       # waic and waic_cols (the column sums against the method's: tests/test_gpu_waic_cols.py)
         got = _waic.combine(out["sums"])
         want = m.waic_streaming(batch, draws=params, row_scores=True)
         print("ctypes", got, "method", {k: v for k, v in want.items() if not k.startswith("row_")})

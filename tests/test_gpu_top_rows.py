@@ -24,14 +24,13 @@ CASES (B, D, K, S, k): ragged 64-blocks and 32-tiles, K padded 3 -> 4, K = 16, K
 candidate-buffer sizes with real competition ((131, 197) at k = 10 and k = 64), columns with no candidate and with
 fewer than k (B = 5 at k = 64; stored cells at B = 70), and one to four column blocks with one to three row blocks:
 the rows of (70, 45) and (131, 197) are split into 2 and 3 row slices on a 256-CU device, so the merge runs."""
-import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 import torch
 
-from _stream_cases import _case, _problem
+from _stream_cases import _case, _problem, assert_shared_errors, gpu_good_call, host_ctx
 from _problems import LIKELIHOODS, _dense_model, _dense_problem
 
 pytestmark = pytest.mark.gpu
@@ -264,57 +263,33 @@ def test_wide_k_runs_four_chunks_per_draw():
 
 
 def test_c_abi_valid_call_refused_calls_and_empty_calls():
-    """A raw valid call on an exactly sized scratch returns 0 and equals the method; every refused call leaves the
-    sentinel-filled outputs and the scratch untouched; n_cols = 0 returns 0 and writes nothing; a batch without rows
-    returns 0 and fills both outputs with the padding."""
+    """A raw valid call on an exactly sized scratch returns 0 and equals the method; every refused call (the draw
+    stage's shared cases, _stream_cases.assert_shared_errors, then the entry's own) leaves the sentinel-filled
+    outputs and the scratch untouched; n_cols = 0 returns 0 and writes nothing; a batch without rows returns 0 and
+    fills both outputs with the padding."""
     from spmf_amd import _lib
-    from spmf_amd._lib import VAR_ORDER
     c = _case("poisson", 70, 45, 3, 2)
     m, x, params = c["m"], c["x"], c["params"]
-    lib, h = _lib.load(), m._handle()
-    _, cs = m._batch({"counts": x})
-    S, P = m._pack_params(params, names=("s", "u", "v", "w"))
-    pin = _lib.PtrArray(*[P[n].data_ptr() if n in P else None for n in VAR_ORDER])
-    no_u = _lib.PtrArray(*[P[n].data_ptr() if n in P and n != "u" else None for n in VAR_ORDER])
-    eta = m._eta_device()
-    k, D = 5, 45
-    listed = torch.tensor([7, 0, 7, 44], dtype=torch.int32, device="cuda")
-    n = int(listed.numel())
-    need = int(lib.spmf_toprows_scratch_bytes(h, int(cs.n_rows), S, n))
-    assert need > 0 and need % 256 == 0
-    scratch = torch.zeros(need + 512, dtype=torch.uint8, device="cuda")
-    base = scratch.data_ptr() + (-scratch.data_ptr()) % 256
-    rows = torch.full((n, k), -7, dtype=torch.int32, device="cuda")
-    scores = torch.full((n, k), -7.0, dtype=torch.float32, device="cuda")
-    stream = torch.cuda.current_stream().cuda_stream
-    fn = C.CDLL(_lib.LIB_PATH).spmf_toprows_columns
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int, C.c_uint,
-                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    good = dict(ct=cs, S=S, pin=pin, eta=eta.data_ptr(), n=n, cols=listed.data_ptr(), k=k, flags=1,
-                rows=rows.data_ptr(), scores=scores.data_ptr(), ptr=base, nbytes=need)
-
-    def call(**kw):
-        a = dict(good, **kw)
-        return fn(h, C.byref(a["ct"]) if a["ct"] is not None else None, a["S"], a["pin"], a["eta"], a["n"], a["cols"],
-                  a["k"], a["flags"], a["rows"], a["scores"], a["ptr"], a["nbytes"], stream)
+    lib, h, k, D = _lib.load(), m._handle(), 5, 45
+    good, need, out, scratch, no_u = gpu_good_call("toprows", m, x, params, k=k)
+    rows, scores, cs, listed = out["rows"], out["scores"], good["ct"], good["keep"][-1]["cols"]
+    raw = host_ctx(lib, 3, _lib.FLAG_MIXED)        # a mixed context nobody gave column types
 
     def untouched():
         torch.cuda.synchronize()
         return bool((rows == -7).all()) and bool((scores == -7.0).all()) and not bool(scratch.any())
-    bad = type(cs).from_buffer_copy(cs)
-    bad.struct_size += 8
-    refused = [dict(S=0), dict(S=65536), dict(pin=None), dict(eta=None), dict(ptr=None), dict(ct=None),
-               dict(pin=no_u), dict(ptr=base + 4), dict(ct=bad), dict(k=0), dict(k=65), dict(flags=2), dict(n=-1),
-               dict(n=D + 1), dict(cols=None), dict(rows=None), dict(scores=None)]
-    for kw in refused:
+
+    def after():
+        assert untouched()
+    try:
+        call = assert_shared_errors(lib, "toprows", good, need, no_u, raw, after=after)
+    finally:
+        lib.spmf_ctx_destroy(raw)
+    for kw in (dict(k=0), dict(k=65), dict(flags=2), dict(n=-1), dict(n=D + 1), dict(cols=None), dict(rows=None),
+               dict(scores=None)):
         assert call(**kw) == -1, kw
-        if "ct" not in kw:      # (the descriptor's own errors are check_counts', worded for every call alike)
-            assert lib.spmf_last_error(h).decode().startswith("toprows_columns: "), kw
+        assert lib.spmf_last_error(h).decode().startswith("toprows_columns: "), kw
         assert untouched(), kw
-    assert call(nbytes=need - 256) == -3
-    assert str(need) in lib.spmf_last_error(h).decode()
-    assert untouched()
     # the empty calls
     assert call(n=0) == 0 and untouched(), "n_cols = 0: nothing launched, nothing written"
     assert call(n=0, k=0) == -1 and untouched(), "errors come before the empty return"

@@ -9,7 +9,6 @@ square: |d(e^2)| <= 2 |e| |de|, |de| <= 1e-5 |lppd_i| + 1e-3 |pwaic_i|, summed o
 
 The method returns six derived keys per column; the five raw sums of a call (and the six totals) are read where the
 method hands them to spmf_amd.waic.combine_columns / combine, which the helper here watches."""
-import ctypes as C
 import functools
 import importlib.util
 import math
@@ -22,6 +21,7 @@ import torch
 
 from oracle import spmf_oracle as O
 from _problems import LIKELIHOODS, _dense_model, _dense_problem, build_model, make_problem
+from _stream_cases import assert_shared_errors, gpu_good_call, host_ctx
 
 pytestmark = pytest.mark.gpu
 T = torch.as_tensor
@@ -232,39 +232,44 @@ def test_row_chunks_and_several_batches_add_up():
 
 
 def test_raw_call_equals_the_method_and_keeps_the_error_contract():
-    """spmf_waic_accumulate_cols through the binding: with row_out and col_out set the method's numbers; with
-    col_out NULL the plain entry, a poisoned [D,5] buffer untouched; refused calls write nothing."""
+    """spmf_waic_accumulate_cols through ctypes: refused calls (the draw stage's shared cases,
+    _stream_cases.assert_shared_errors, then the entry's own) write nothing; with row_out and col_out set the
+    method's numbers; with col_out NULL the plain entry, a poisoned [D,5] buffer untouched."""
     from spmf_amd import _lib
-    from spmf_amd._lib import VAR_ORDER
     B, D = 70, 45
     cfg, x, params, mask, _ = _dense_case("poisson", B, D, 3, 2, 4100 + 70 + 3)
     m = _dense_model("poisson", cfg, mask, 32)
     out, s_method, t_method = _stream_cols(m, {"counts": x}, draws=params, row_scores=True)
     lib, h = _lib.load(), m._handle()
-    _, cs = m._batch({"counts": x})
-    S, P = m._pack_params(params, names=("s", "u", "v", "w"))
-    pin = _lib.PtrArray(*[P[n].data_ptr() if n in P else None for n in VAR_ORDER])
-    eta = m._eta_device()
-    need = int(lib.spmf_waic_scratch_bytes(h, int(cs.n_rows), S))
-    assert need > 0 and need % 256 == 0
-    scratch = torch.zeros(need + 512, dtype=torch.uint8, device="cuda")
-    ptr = scratch.data_ptr() + (-scratch.data_ptr()) % 256
-    stream = torch.cuda.current_stream().cuda_stream
+    good, need, outs, scratch, no_u = gpu_good_call("waic_cols", m, x, params)
+    sums, rows, cols = outs["sums"], outs["rows"], outs["colsum"]
+    assert tuple(cols.shape) == (D, 5) and tuple(rows.shape) == (B, 2)
+    raw = host_ctx(lib, 3, _lib.FLAG_MIXED)        # a mixed context nobody gave column types
 
-    def call(sums, rows, cols, S=S, nbytes=need):
-        return lib.spmf_waic_accumulate_cols(h, C.byref(cs), S, pin, eta.data_ptr(),
-                                             sums.data_ptr() if sums is not None else None,
-                                             rows.data_ptr() if rows is not None else None,
-                                             cols.data_ptr() if cols is not None else None, ptr, nbytes, stream)
-
-    def zeros(*shape):
-        return torch.zeros(*shape, dtype=torch.float64, device="cuda")
+    def untouched():
+        torch.cuda.synchronize()
+        assert all(bool((t == -7.0).all()) for t in outs.values()) and not bool(scratch.any())
+    try:
+        call = assert_shared_errors(lib, "waic_cols", good, need, no_u, raw, after=untouched)
+    finally:
+        lib.spmf_ctx_destroy(raw)
+    assert call(sums=None) == -1                                # SPMF_E_ARG
+    assert lib.spmf_last_error(h).decode() == "waic_accumulate_cols: null argument"
+    untouched()
+    assert call(S=1) == -1                                      # SPMF_E_ARG
+    assert lib.spmf_last_error(h).decode().startswith("waic_accumulate_cols: S must be in 2..65535")
+    untouched()
+    assert call(nbytes=need - 1) == -3                          # SPMF_E_WORKSPACE
+    msg = lib.spmf_last_error(h).decode()
+    assert msg.startswith("waic_accumulate_cols: scratch too small") and str(need) in msg, msg
+    untouched()
 
     def close(a, b, tag):
         a, b = a.cpu().numpy(), np.asarray(b)
         np.testing.assert_allclose(a, b, rtol=1e-12, atol=1e-12 * np.abs(b).max(), err_msg=tag)
-    sums, rows, cols = zeros(6), zeros(B, 2), zeros(D, 5)
-    assert call(sums, rows, cols) == 0
+    for t in outs.values():         # the call adds into its outputs
+        t.zero_()
+    assert call() == 0
     torch.cuda.synchronize()
     close(sums, t_method, "sums6")
     close(cols, s_method, "col_out")
@@ -272,29 +277,15 @@ def test_raw_call_equals_the_method_and_keeps_the_error_contract():
     close(rows[:, 1], out["row_pwaic"].cpu().numpy(), "row pwaic")
     np.testing.assert_array_equal(cols[:, [0, 4]].cpu().numpy(), s_method[:, [0, 4]])
 
-    poison = torch.full((D, 5), -7.0, dtype=torch.float64, device="cuda")
-    sums2, rows2 = zeros(6), zeros(B, 2)
-    assert call(sums2, rows2, None) == 0
+    first = rows.cpu().numpy()
+    poison = cols.fill_(-7.0)
+    sums.zero_()
+    rows.zero_()
+    assert call(colsum=None) == 0
     torch.cuda.synchronize()
-    close(sums2, t_method, "sums6 without col_out")
-    close(rows2, rows.cpu().numpy(), "row_out without col_out")
+    close(sums, t_method, "sums6 without col_out")
+    close(rows, first, "row_out without col_out")
     assert bool((poison == -7.0).all())
-
-    before, rows_before = sums2.clone(), rows2.clone()
-
-    def untouched():
-        torch.cuda.synchronize()
-        assert bool((poison == -7.0).all()) and torch.equal(sums2, before) and torch.equal(rows2, rows_before)
-    assert call(None, rows2, poison) == -1                      # SPMF_E_ARG
-    assert lib.spmf_last_error(h).decode() == "waic_accumulate_cols: null argument"
-    untouched()
-    assert call(sums2, rows2, poison, S=1) == -1                # SPMF_E_ARG
-    assert lib.spmf_last_error(h).decode().startswith("waic_accumulate_cols: S must be in 2..65535")
-    untouched()
-    assert call(sums2, rows2, poison, nbytes=need - 1) == -3    # SPMF_E_WORKSPACE
-    msg = lib.spmf_last_error(h).decode()
-    assert msg.startswith("waic_accumulate_cols: scratch too small") and str(need) in msg, msg
-    untouched()
 
 
 def test_cli_writes_the_gene_table(tmp_path, capsys):

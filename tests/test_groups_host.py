@@ -3,45 +3,31 @@ spmf_amd.groups: the method's argument checks on a CPU-only model, the error con
 all refused before anything touches a device -- the scratch size, and contrast / observed against numpy
 restatements written here.  (Declared / exported / bound and the method on the classes: the "groups" row of
 tests/test_stream_host.py; the valid call: tests/test_gpu_groups.py.)"""
-import ctypes as C
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from _stream_cases import B, D, ENTRIES, S, assert_shared_errors, host_good_call
+from _stream_cases import B, D, ENTRIES, S, assert_shared_errors, cpu_model, host_ctx, host_good_call, library
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CALL, SIZE = ENTRIES["groups"].call, ENTRIES["groups"].size
 G = 4
 
 
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    from spmf_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
-
-
-def test_symbols_are_in_the_built_library(lib):
+def test_symbols_are_in_the_built_library():
+    lib = library()
     assert callable(getattr(lib, CALL)) and callable(getattr(lib, SIZE))
     assert lib.spmf_version() == 6
 
 
-def _ctx(lib, k, flags=0, d=D):
-    h = C.c_void_p()
-    assert lib.spmf_ctx_create(0, k, d, flags, C.byref(h)) == 0
-    return h
-
-
-def test_shared_and_own_errors_return_before_any_device_call(lib):
+def test_shared_and_own_errors_return_before_any_device_call():
     """The dummy-address call of _stream_cases.host_good_call (K = 3, D = 45, 70 empty rows, G = 4, four
     columns): the draw stage's error cases (_stream_cases.assert_shared_errors) and the entry's own are refused
     with their codes before the empty returns; nothing here is a valid call with work to do, so nothing may be
     launched or dereferenced."""
+    lib = library()
     good, need, no_u, raw, cleanup = host_good_call(lib, "groups")
     h, cs = good["h"], good["ct"]
     assert good["G"] == G and need == int(lib.spmf_groups_scratch_bytes(h, B, S, G, 4))
@@ -75,10 +61,11 @@ def test_shared_and_own_errors_return_before_any_device_call(lib):
 
 
 @pytest.mark.parametrize("k", [3, 16, 64, 128])
-def test_scratch_size(lib, k):
+def test_scratch_size(k):
     """0 for bad arguments; a multiple of 256; non-decreasing in the rows and in S; at least the draw carve
     (spmf_embed_scratch_bytes); the same on a second context."""
-    h, h2 = _ctx(lib, k), _ctx(lib, k)
+    lib = library()
+    h, h2 = host_ctx(lib, k), host_ctx(lib, k)
     try:
         size = lambda hh, rows, s, g=G, n=D: int(lib.spmf_groups_scratch_bytes(hh, rows, s, g, n))   # noqa: E731
         for g, n in ((1, D), (G, D), (G, 7), (300, 1), (G, 0)):
@@ -114,10 +101,11 @@ def test_scratch_size(lib, k):
     (64, 4096, 12, 64, 8, 261_000, 263_000),     # a listed panel of 64 columns of D = 4096
     (3, 45, 300, 45, 3, 0, 2_000),               # more groups than row blocks
 ])
-def test_scratch_size_never_drops_as_the_rows_grow(lib, k, d, g, n, s, lo, hi):
+def test_scratch_size_never_drops_as_the_rows_grow(k, d, g, n, s, lo, hi):
     """Every row count of a range that crosses a step of the run length RB (where the number of runs, ceil(NB /
     RB), falls to about half): the size must not fall with it; and every row count up to three run lengths."""
-    h = _ctx(lib, k, d=d)
+    lib = library()
+    h = host_ctx(lib, k, d=d)
     try:
         for a, b in ((lo, hi), (0, 300)):
             prev = 0
@@ -131,18 +119,8 @@ def test_scratch_size_never_drops_as_the_rows_grow(lib, k, d, g, n, s, lo, hi):
 
 # ---- the method's argument checks ---------------------------------------------------------------
 
-def _cpu_model(**kw):
-    from spmf_amd import PoissonFactorization
-    m = PoissonFactorization(latent_dim=2, feature_dim=6, initialize_distributions=False, device="cpu", **kw)
-    rng = np.random.default_rng(0)
-    x = rng.poisson(1.0, size=(8, 6)).astype(np.float64)
-    draws = {"u": rng.random((2, 6, 2)), "v": rng.random((2, 2, 6)), "w": rng.random((2, 1, 6)),
-             "s": rng.random((2, 2, 6))}
-    return m, x, draws
-
-
 def test_bad_labels_raise_value_error_without_a_device():
-    m, x, draws = _cpu_model()
+    m, x, draws = cpu_model()
     data = {"counts": x}
     lab = np.array([0, 1, 2, -1, 0, 1, 2, 2])
     with pytest.raises(ValueError, match="one entry per row, got 7 for 8"):
@@ -172,7 +150,7 @@ def test_bad_labels_raise_value_error_without_a_device():
 
 
 def test_output_cap_points_at_cols():
-    m, x, draws = _cpu_model()
+    m, x, draws = cpu_model()
     lab = np.zeros(8, dtype=np.int64)
     cap = m._GROUP_OUT_CAP
     g = cap // (2 * 6 * 8) + 1                 # S * G * C * 8 just above the cap
@@ -183,7 +161,7 @@ def test_output_cap_points_at_cols():
 
 
 def test_custom_codec_raises_after_the_argument_checks():
-    m, x, draws = _cpu_model(encoder_function=lambda t: t, decoder_function=lambda t: t)
+    m, x, draws = cpu_model(encoder_function=lambda t: t, decoder_function=lambda t: t)
     lab = np.zeros(8, dtype=np.int64)
     with pytest.raises(ValueError, match="one entry per row"):
         m.group_means({"counts": x}, lab[:3], draws=draws)
@@ -192,7 +170,7 @@ def test_custom_codec_raises_after_the_argument_checks():
 
 
 def test_a_valid_call_on_a_cpu_model_fails_like_top_k():
-    m, x, draws = _cpu_model()
+    m, x, draws = cpu_model()
     with pytest.raises(Exception) as e_topk:
         m.top_k({"counts": x}, k=3, draws=draws)
     with pytest.raises(Exception) as e_grp:

@@ -10,19 +10,13 @@ import pytest
 import scipy.sparse as sp
 import torch
 
+from _stream_cases import library
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    from spmf_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
-
-
-def test_library_exports_every_declared_symbol(lib):
+def test_library_exports_every_declared_symbol():
+    lib = library()
     from spmf_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "spmf_hip.h")).read()
     declared = set(re.findall(r"\b(spmf_[a-z0-9_]+)\s*\(", hdr))
@@ -33,9 +27,10 @@ def test_library_exports_every_declared_symbol(lib):
     assert lib.spmf_version() == 6 and 'define SPMF_ABI_VERSION 6' in hdr
 
 
-def test_library_exports_only_the_c_abi(lib):
+def test_library_exports_only_the_c_abi():
     """-fvisibility=hidden + the linker export map: the dynamic symbol table holds
     the header's functions and nothing else (no launch wrappers, no kernel handles)."""
+    lib = library()
     import subprocess
     from spmf_amd import _lib
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True,
@@ -44,9 +39,10 @@ def test_library_exports_only_the_c_abi(lib):
     assert names == set(_lib.SIGNATURES), names ^ set(_lib.SIGNATURES)
 
 
-def test_struct_sizes_agree_between_library_ctypes_and_integration_stub(lib):
+def test_struct_sizes_agree_between_library_ctypes_and_integration_stub():
     """spmf_sizeof_*: the library's own struct sizes == the ctypes mirrors in
     spmf_amd/_lib.py == the stub INTEGRATION.md tells a maintainer to copy."""
+    lib = library()
     from spmf_amd import _lib
     assert lib.spmf_sizeof_counts() == C.sizeof(_lib.CountsStruct) == 200
     assert lib.spmf_sizeof_sur_var() == C.sizeof(_lib.SurVar)
@@ -62,8 +58,9 @@ def test_struct_sizes_agree_between_library_ctypes_and_integration_stub(lib):
         [(n, getattr(_lib.CountsStruct, n).offset) for n, *_ in _lib.CountsStruct._fields_]
 
 
-def test_layout_builder_argument_errors_without_gpu(lib):
+def test_layout_builder_argument_errors_without_gpu():
     """spmf_layout_*: what is checked before the first device call."""
+    lib = library()
     from spmf_amd import _lib
     assert lib.spmf_sizeof_layout_info() == C.sizeof(_lib.LayoutInfo) == 48
     lb, sb = C.c_size_t(), C.c_size_t()
@@ -82,7 +79,8 @@ def test_layout_builder_argument_errors_without_gpu(lib):
     assert b"null" in lib.spmf_layout_last_error()
 
 
-def test_ctx_lifecycle_and_argument_errors_without_gpu(lib):
+def test_ctx_lifecycle_and_argument_errors_without_gpu():
+    lib = library()
     h = C.c_void_p()
     assert lib.spmf_ctx_create(0, 300, 10, 0, C.byref(h)) == -1      # K > 256
     assert lib.spmf_ctx_create(0, 100, 10, 2, C.byref(h)) == -4   # dense-term contexts: K <= 64
@@ -105,12 +103,13 @@ def test_ctx_lifecycle_and_argument_errors_without_gpu(lib):
     lib.spmf_ctx_destroy(h3)
 
 
-def test_counts_struct_abi_guard_rejects_foreign_layouts(lib):
+def test_counts_struct_abi_guard_rejects_foreign_layouts():
     """spmf_counts grew fields without a version signal.  Since ABI version 3
     every entry point that takes the struct refuses one whose struct_size is not the library's own
     sizeof (a caller compiled against the shorter layout, or one that never initialised the former
     reserved slot), a negative pc_pad, and a packed list stream with panels too tall for 16 bits
     -- all on the host, before anything touches the device."""
+    lib = library()
     from spmf_amd import _lib
     h = C.c_void_p()
     assert lib.spmf_ctx_create(0, 8, 100, 1, C.byref(h)) == 0

@@ -3,34 +3,20 @@ spmf_amd/cluster.py): the two entry points in the header, the export list and th
 class surface, every argument check of the methods before a library call, the raw entry's refusals through a
 ctypes call with dummy aligned addresses, the scratch size, and the centroid update against numpy.
 (The valid calls: tests/test_gpu_kmeans.py.)"""
-import ctypes as C
 import inspect
-import os
 
 import numpy as np
 import pytest
 import torch
 
-from _stream_cases import D, K, assert_declared_exported_bound
+from _stream_cases import (K, assert_declared_exported_bound, assert_kmeans_errors, cpu_model, host_ctx, library,
+                           no_library)
 
 HEADER_ARGS = {"spmf_kmeans_scratch_bytes": 4, "spmf_kmeans_step": 15}
 
-STEP_ARGS = (("x", C.c_void_p), ("n", C.c_int64), ("row_len", C.c_int), ("cent", C.c_void_p), ("G", C.c_int32),
-             ("prev", C.c_void_p), ("labels", C.c_void_p), ("dist", C.c_void_p), ("sums", C.c_void_p),
-             ("counts", C.c_void_p), ("stats", C.c_void_p), ("ptr", C.c_void_p), ("nbytes", C.c_size_t),
-             ("stream", C.c_void_p))
 
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    from spmf_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
-
-
-def test_entry_points_are_declared_exported_and_bound(lib):
+def test_entry_points_are_declared_exported_and_bound():
+    lib = library()
     for name, nargs in HEADER_ARGS.items():
         assert_declared_exported_bound(name, nargs)
         assert callable(getattr(lib, name)), name
@@ -53,28 +39,9 @@ def test_methods_and_signatures_on_all_three_classes():
 
 # ---- the methods' argument checks ----------------------------------------------------------------
 
-def _cpu_model(**kw):
-    from spmf_amd import PoissonFactorization
-    m = PoissonFactorization(latent_dim=2, feature_dim=6, initialize_distributions=False, device="cpu", **kw)
-    rng = np.random.default_rng(0)
-    x = rng.poisson(1.0, size=(8, 6)).astype(np.float64)
-    draws = {"u": rng.random((2, 6, 2)), "v": rng.random((2, 2, 6)), "w": rng.random((2, 1, 6)),
-             "s": rng.random((2, 2, 6))}
-    return m, x, draws
-
-
-def _no_library(monkeypatch):
-    """Any load of the library from here on fails the test."""
-    from spmf_amd import _lib
-
-    def refuse():
-        raise AssertionError("the library was loaded before the arguments were checked")
-    monkeypatch.setattr(_lib, "load", refuse)
-
-
 def test_every_argument_check_raises_before_a_library_call(monkeypatch):
-    m, x, draws = _cpu_model()
-    _no_library(monkeypatch)
+    m, x, draws = cpu_model()
+    no_library(monkeypatch)
     pts = torch.zeros(9, 3)
     data = {"counts": x}
     for g in (True, 0, -1, 65537, 2.0, None, "3"):
@@ -123,8 +90,8 @@ def test_every_argument_check_raises_before_a_library_call(monkeypatch):
 
 
 def test_custom_codec_raises_in_cluster_as_in_embed(monkeypatch):
-    m, x, draws = _cpu_model(encoder_function=lambda t: t, decoder_function=lambda t: t)
-    _no_library(monkeypatch)
+    m, x, draws = cpu_model(encoder_function=lambda t: t, decoder_function=lambda t: t)
+    no_library(monkeypatch)
     with pytest.raises(ValueError, match="n_clusters"):
         m.cluster({"counts": x}, 0, draws=draws)
     with pytest.raises(NotImplementedError) as e_embed:
@@ -175,28 +142,11 @@ def test_named_inits_on_the_cpu():
 
 # ---- the C-ABI's argument errors -----------------------------------------------------------------
 
-def _ctx(lib):
-    h = C.c_void_p()
-    assert lib.spmf_ctx_create(0, K, D, 0, C.byref(h)) == 0
-    return h
-
-
-def _raw_call(good):
-    from spmf_amd import _lib
-    fn = C.CDLL(_lib.LIB_PATH).spmf_kmeans_step
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p] + [t for _, t in STEP_ARGS]
-
-    def call(**kw):
-        a = dict(good, **kw)
-        return fn(a["h"], *[a[n] for n, _ in STEP_ARGS])
-    return call
-
-
-def test_step_errors_return_before_any_device_call(lib):
+def test_step_errors_return_before_any_device_call():
     """A context of spmf_ctx_create and dummy aligned addresses: no call here is valid, so nothing may be
     launched or dereferenced."""
-    h = _ctx(lib)
+    lib = library()
+    h = host_ctx(lib, K)
     try:
         n, G, row_len = 70, 5, 33
         need = int(lib.spmf_kmeans_scratch_bytes(h, n, G, row_len))
@@ -204,36 +154,16 @@ def test_step_errors_return_before_any_device_call(lib):
         good = dict(h=h, x=0x1000000, n=n, row_len=row_len, cent=0x2000000, G=G, prev=0x3000000, labels=0x4000000,
                     dist=0x5000000, sums=0x6000000, counts=0x7000000, stats=0x9000000, ptr=0x8000000, nbytes=need,
                     stream=None)
-        call = _raw_call(good)
-
-        def refused(code, **kw):
-            assert call(**kw) == code, kw
-            msg = lib.spmf_last_error(h).decode()
-            assert msg.startswith("kmeans_step: "), msg
-            return msg
-        for g in (0, -1, 65537):
-            assert "n_clusters" in refused(-1, G=g)
-        for w in (0, 257, -1):
-            assert "row_len" in refused(-1, row_len=w)
-        for rows in (-1, 2 ** 31 - 63, 2 ** 40):
-            assert "n_rows" in refused(-1, n=rows)
-        assert "prev_labels" in refused(-1, prev=good["labels"])
-        for name in ("x", "cent", "labels", "sums", "counts", "stats", "ptr"):
-            assert "null" in refused(-1, **{name: None})
-        for name in ("sums", "counts", "stats", "ptr"):
-            refused(-1, n=0, **{name: None})
-        assert "aligned" in refused(-1, ptr=good["ptr"] + 4)
-        assert str(need) in refused(-3, nbytes=need - 256)
-        refused(-3, n=0, nbytes=0)               # errors come before the empty return
-        assert call(h=None) == -1
+        assert_kmeans_errors(lib, good, need)
     finally:
         lib.spmf_ctx_destroy(h)
 
 
-def test_scratch_size(lib):
+def test_scratch_size():
     """0 for arguments the call refuses, else a positive multiple of 256 that holds the working rows and the
     ordering, and does not shrink as the rows grow (knn's own scratch does, where its slices drop to one)."""
-    h = _ctx(lib)
+    lib = library()
+    h = host_ctx(lib, K)
     try:
         for bad in ((-1, 5, 8), (2 ** 31 - 63, 5, 8), (5, 0, 8), (5, 65537, 8), (5, 5, 0), (5, 5, 257)):
             assert int(lib.spmf_kmeans_scratch_bytes(h, *bad)) == 0, bad

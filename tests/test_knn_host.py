@@ -3,28 +3,18 @@ spmf_knn, csrc/knn.hip): the two entry points of knn in the header, the export l
 embed: the "embed" row of tests/test_stream_host.py), the methods' signatures on the class surface, the
 argument checks of the methods that need no device, the host helpers of spmf_amd.neighbors, and the argument errors of the two calls -- all refused before anything touches a device.
 (The valid calls: tests/test_gpu_knn.py.)"""
-import ctypes as C
 import inspect
-import os
 
 import numpy as np
 import pytest
 import torch
 
-from _stream_cases import (B, D, K, S, ENTRIES, abi_call, assert_declared_exported_bound, assert_embed_own_errors,
-                           assert_knn_errors, assert_shared_errors, host_good_call, knn_raw_call)
+from _stream_cases import (B, K, S, ENTRIES, abi_call, assert_declared_exported_bound, assert_embed_own_errors,
+                           assert_knn_errors, assert_shared_errors, cpu_model, host_ctx, host_good_call, knn_raw_call,
+                           library)
 
 # spmf_knn is no draw-stage call: it is not in the contract table
 HEADER_ARGS = {"spmf_knn_scratch_bytes": 4, "spmf_knn": 14}
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    from spmf_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
 
 
 def test_entry_points_are_declared_exported_and_bound():
@@ -32,7 +22,8 @@ def test_entry_points_are_declared_exported_and_bound():
         assert_declared_exported_bound(name, nargs)
 
 
-def test_symbols_are_in_the_built_library(lib):
+def test_symbols_are_in_the_built_library():
+    lib = library()
     for name in (*HEADER_ARGS, ENTRIES["embed"].size, ENTRIES["embed"].call):
         assert callable(getattr(lib, name)), name
 
@@ -55,19 +46,9 @@ def test_methods_and_signatures_on_all_three_classes():
 
 # ---- the methods' argument checks ----------------------------------------------------------------
 
-def _cpu_model():
-    from spmf_amd import PoissonFactorization
-    m = PoissonFactorization(latent_dim=2, feature_dim=6, initialize_distributions=False, device="cpu")
-    rng = np.random.default_rng(0)
-    x = rng.poisson(1.0, size=(8, 6)).astype(np.float64)
-    draws = {"u": rng.random((2, 6, 2)), "v": rng.random((2, 2, 6)), "w": rng.random((2, 1, 6)),
-             "s": rng.random((2, 2, 6))}
-    return m, x, draws
-
-
 @pytest.mark.parametrize("k", [0, 65, -1, 2.5, True])
 def test_bad_k_raises_value_error(k):
-    m, x, draws = _cpu_model()
+    m, x, draws = cpu_model()
     pts = torch.zeros(9, 3)
     with pytest.raises(ValueError, match="k"):
         m.knn(pts, k=k)
@@ -76,7 +57,7 @@ def test_bad_k_raises_value_error(k):
 
 
 def test_bad_metric_and_inputs_raise_value_error():
-    m, x, draws = _cpu_model()
+    m, x, draws = cpu_model()
     pts = torch.zeros(9, 3)
     with pytest.raises(ValueError, match="metric"):
         m.knn(pts, k=3, metric="manhattan")
@@ -101,7 +82,7 @@ def test_bad_metric_and_inputs_raise_value_error():
 
 
 def test_sd_needs_two_draws():
-    m, x, draws = _cpu_model()
+    m, x, draws = cpu_model()
     one = {n: v[:1] for n, v in draws.items()}
     with pytest.raises(ValueError, match="at least 2 draws"):
         m.embed({"counts": x}, draws=one, sd=True)
@@ -110,7 +91,7 @@ def test_sd_needs_two_draws():
 
 
 def test_a_valid_embed_on_a_cpu_model_fails_like_top_k():
-    m, x, draws = _cpu_model()
+    m, x, draws = cpu_model()
     with pytest.raises(Exception) as e_topk:
         m.top_k({"counts": x}, k=3, draws=draws)
     with pytest.raises(Exception) as e_embed:
@@ -223,16 +204,11 @@ def test_recall():
 
 # ---- the C-ABI's argument errors -----------------------------------------------------------------
 
-def _ctx(lib, k, flags=0):
-    h = C.c_void_p()
-    assert lib.spmf_ctx_create(0, k, D, flags, C.byref(h)) == 0
-    return h
-
-
-def test_knn_errors_return_before_any_device_call(lib):
+def test_knn_errors_return_before_any_device_call():
     """A context of spmf_ctx_create and dummy aligned addresses: nothing here is a valid call with queries, so
     nothing may be launched or dereferenced."""
-    h = _ctx(lib, K)
+    lib = library()
+    h = host_ctx(lib, K)
     try:
         nq, nr, row_len = 70, 333, 33
         need = int(lib.spmf_knn_scratch_bytes(h, nq, nr, row_len))
@@ -248,10 +224,11 @@ def test_knn_errors_return_before_any_device_call(lib):
         lib.spmf_ctx_destroy(h)
 
 
-def test_knn_scratch_size(lib):
+def test_knn_scratch_size():
     """A multiple of 256 that holds the padded working rows of both sets and the biases; it does not depend on
     k (the call has no k) and is 0 for arguments the call refuses."""
-    h = _ctx(lib, K)
+    lib = library()
+    h = host_ctx(lib, K)
     try:
         for nq, nr, row_len, kp in ((70, 70, 3, 4), (5, 333, 33, 64), (197, 197, 70, 128), (1000, 20000, 256, 256)):
             need = int(lib.spmf_knn_scratch_bytes(h, nq, nr, row_len))
@@ -264,7 +241,8 @@ def test_knn_scratch_size(lib):
         lib.spmf_ctx_destroy(h)
 
 
-def test_embed_errors_return_before_any_device_call(lib):
+def test_embed_errors_return_before_any_device_call():
+    lib = library()
     good, need, no_u, raw, cleanup = host_good_call(lib, "embed")
     h, cs = good["h"], good["ct"]
     try:

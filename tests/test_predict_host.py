@@ -3,41 +3,25 @@ contract of the draw stage and the entry's own argument errors -- all refused be
 device -- the empty cases, the scratch size, and the argument checks of the method that need no device.
 (Declared / exported / bound and the method on the classes: the "predict" row of tests/test_stream_host.py; the
 valid call: tests/test_gpu_predict.py.)"""
-import ctypes as C
-import os
-
 import numpy as np
 import pytest
 
-from _stream_cases import B, D, ENTRIES, S, assert_shared_errors, host_good_call
+from _stream_cases import B, D, ENTRIES, S, assert_shared_errors, cpu_model, host_ctx, host_good_call, library
 
 CALL, SIZE = ENTRIES["predict"].call, ENTRIES["predict"].size
 
 
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    from spmf_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
-
-
-def test_symbols_are_in_the_built_library(lib):
+def test_symbols_are_in_the_built_library():
+    lib = library()
     assert callable(getattr(lib, CALL)) and callable(getattr(lib, SIZE))
     assert lib.spmf_version() == 6
 
 
-def _ctx(lib, k, flags=0, d=D):
-    h = C.c_void_p()
-    assert lib.spmf_ctx_create(0, k, d, flags, C.byref(h)) == 0
-    return h
-
-
-def test_shared_and_own_errors_return_before_any_device_call(lib):
+def test_shared_and_own_errors_return_before_any_device_call():
     """The dummy-address call of _stream_cases.host_good_call (K = 3, D = 45, 70 empty rows): the error cases of
     the draw stage (_stream_cases.assert_shared_errors) and the entry's own are refused with their codes, before
     the empty returns; nothing here is a valid call with work to do, so nothing may be launched or dereferenced."""
+    lib = library()
     good, need, no_u, raw, cleanup = host_good_call(lib, "predict")
     h, cs = good["h"], good["ct"]
     try:
@@ -70,11 +54,12 @@ def test_shared_and_own_errors_return_before_any_device_call(lib):
 
 
 @pytest.mark.parametrize("k", [3, 16, 64, 128])
-def test_scratch_size(lib, k):
+def test_scratch_size(k):
     """A multiple of 256: the draw stage's scratch plus the compacted tables of a listed panel sized for
     n_cols = D (V' rows, phi and the column types, three regions of their own); 0 for S < 1, for negative
     rows and without a context; a function of (rows, S) alone."""
-    h, h2 = _ctx(lib, k), _ctx(lib, k)
+    lib = library()
+    h, h2 = host_ctx(lib, k), host_ctx(lib, k)
     try:
         kp = int(lib.spmf_padded_k(h))
         for rows in (0, 1, B, 1000):
@@ -94,19 +79,9 @@ def test_scratch_size(lib, k):
 
 # ---- the method's argument checks ---------------------------------------------------------------
 
-def _cpu_model(**kw):
-    from spmf_amd import PoissonFactorization
-    m = PoissonFactorization(latent_dim=2, feature_dim=6, initialize_distributions=False, device="cpu", **kw)
-    rng = np.random.default_rng(0)
-    x = rng.poisson(1.0, size=(8, 6)).astype(np.float64)
-    draws = {"u": rng.random((2, 6, 2)), "v": rng.random((2, 2, 6)), "w": rng.random((2, 1, 6)),
-             "s": rng.random((2, 2, 6))}
-    return m, x, draws
-
-
 def test_bad_column_lists_raise_value_error_without_a_device():
     import torch
-    m, x, draws = _cpu_model()
+    m, x, draws = cpu_model()
     data = {"counts": x}
     with pytest.raises(ValueError, match=r"^predict: cols must be 1-D, got shape \(2, 1\)$"):
         m.predict(data, np.zeros((2, 1), dtype=np.int64), draws=draws)
@@ -122,7 +97,7 @@ def test_bad_column_lists_raise_value_error_without_a_device():
 
 
 def test_sd_needs_two_draws():
-    m, x, draws = _cpu_model()
+    m, x, draws = cpu_model()
     one = {n: v[:1] for n, v in draws.items()}
     with pytest.raises(ValueError, match="at least 2 draws"):
         m.predict({"counts": x}, [0, 1], draws=one, sd=True)
@@ -131,7 +106,7 @@ def test_sd_needs_two_draws():
 
 
 def test_custom_codec_raises_after_the_argument_checks():
-    m, x, draws = _cpu_model(encoder_function=lambda t: t, decoder_function=lambda t: t)
+    m, x, draws = cpu_model(encoder_function=lambda t: t, decoder_function=lambda t: t)
     with pytest.raises(ValueError, match="must lie in"):
         m.predict({"counts": x}, [0, 6], draws=draws)
     with pytest.raises(NotImplementedError, match="predict"):
@@ -141,7 +116,7 @@ def test_custom_codec_raises_after_the_argument_checks():
 def test_a_valid_list_on_a_cpu_model_fails_like_top_k():
     """Past the argument checks the call needs the library's context, as top_k does: the same failure, and not a
     ValueError."""
-    m, x, draws = _cpu_model()
+    m, x, draws = cpu_model()
     with pytest.raises(Exception) as e_topk:
         m.top_k({"counts": x}, k=3, draws=draws)
     for cols in (None, [5, 0, 0]):

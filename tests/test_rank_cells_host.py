@@ -3,42 +3,27 @@ contract of the draw stage and the entry's own argument errors -- all refused be
 device -- the scratch size, the summary of spmf_amd.heldout.rank_summary on hand cases, and the argument checks
 of the method that need no device.  (Declared / exported / bound and the method on the classes: the "rank" row
 of tests/test_stream_host.py; the valid call: tests/test_gpu_rank_cells.py.)"""
-import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
-from _stream_cases import B, D, ENTRIES, assert_shared_errors, host_good_call
+from _stream_cases import B, D, ENTRIES, assert_shared_errors, cpu_model, host_ctx, host_good_call, library
 
 CALL, SIZE = ENTRIES["rank"].call, ENTRIES["rank"].size
 
 
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    from spmf_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
-
-
-def test_symbols_are_in_the_built_library(lib):
+def test_symbols_are_in_the_built_library():
+    lib = library()
     assert callable(getattr(lib, CALL)) and callable(getattr(lib, SIZE))
 
 
-def _ctx(lib, k, flags=0):
-    h = C.c_void_p()
-    assert lib.spmf_ctx_create(0, k, D, flags, C.byref(h)) == 0
-    return h
-
-
-def test_shared_and_own_errors_return_before_any_device_call(lib):
+def test_shared_and_own_errors_return_before_any_device_call():
     """The dummy-address call of _stream_cases.host_good_call: the error cases of the draw stage
     (_stream_cases.assert_shared_errors) and the entry's own are refused with their codes; nothing here is a
     valid call, so nothing may be launched or dereferenced."""
+    lib = library()
     good, need, no_u, raw, cleanup = host_good_call(lib, "rank")
     h, cs = good["h"], good["ct"]
     try:
@@ -62,10 +47,11 @@ def test_shared_and_own_errors_return_before_any_device_call(lib):
 
 
 @pytest.mark.parametrize("k", [3, 16, 64, 128])
-def test_scratch_size(lib, k):
+def test_scratch_size(k):
     """A multiple of 256: the draw stage's scratch and the bitmap of the stored cells (at most the top-k call's,
     which adds its slices' partial results); 0 for S < 1, for negative rows and without a context."""
-    h = _ctx(lib, k)
+    lib = library()
+    h = host_ctx(lib, k)
     try:
         for s in (1, 2, 7):
             rank, cells, topk = (int(getattr(lib, f)(h, B, s)) for f in
@@ -131,18 +117,8 @@ def test_rank_summary_of_an_empty_list_and_of_unranked_cells():
 
 # ---- the method's argument checks ---------------------------------------------------------------
 
-def _cpu_model():
-    from spmf_amd import PoissonFactorization
-    m = PoissonFactorization(latent_dim=2, feature_dim=6, initialize_distributions=False, device="cpu")
-    rng = np.random.default_rng(0)
-    x = rng.poisson(1.0, size=(8, 6)).astype(np.float64)
-    draws = {"u": rng.random((2, 6, 2)), "v": rng.random((2, 2, 6)), "w": rng.random((2, 1, 6)),
-             "s": rng.random((2, 2, 6))}
-    return m, x, draws
-
-
 def test_bad_lists_raise_value_error_without_a_device():
-    m, x, draws = _cpu_model()
+    m, x, draws = cpu_model()
     data = {"counts": x}
     with pytest.raises(ValueError, match="1-D"):
         m.rank_cells(data, np.zeros((2, 1), dtype=np.int64), [1, 5], draws=draws)
@@ -164,7 +140,7 @@ def test_bad_lists_raise_value_error_without_a_device():
 def test_a_valid_list_on_a_cpu_model_fails_like_top_k():
     """Past the argument checks the call needs the library's context, as top_k does: the same failure, and not a
     ValueError."""
-    m, x, draws = _cpu_model()
+    m, x, draws = cpu_model()
     with pytest.raises(Exception) as e_topk:
         m.top_k({"counts": x}, k=3, draws=draws)
     with pytest.raises(Exception) as e_rank:
@@ -175,7 +151,7 @@ def test_a_valid_list_on_a_cpu_model_fails_like_top_k():
 
 def test_score_cells_keeps_its_error_messages():
     """The two methods share their list handling; each names itself."""
-    m, x, draws = _cpu_model()
+    m, x, draws = cpu_model()
     with pytest.raises(ValueError, match=r"^score_cells: rows must be 1-D, got shape \(2, 1\)$"):
         m.score_cells({"counts": x}, np.zeros((2, 1), dtype=np.int64), [1, 5], draws=draws)
     with pytest.raises(ValueError, match=r"^score_cells: rows, cols and values must have equal length, got 2, 2, 1$"):

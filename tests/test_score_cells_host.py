@@ -6,19 +6,11 @@ import numpy as np
 import pytest
 import torch
 
-
-def _cpu_model():
-    from spmf_amd import PoissonFactorization
-    m = PoissonFactorization(latent_dim=2, feature_dim=6, initialize_distributions=False, device="cpu")
-    rng = np.random.default_rng(0)
-    x = rng.poisson(1.0, size=(8, 6)).astype(np.float64)
-    draws = {"u": rng.random((2, 6, 2)), "v": rng.random((2, 2, 6)), "w": rng.random((2, 1, 6)),
-             "s": rng.random((2, 2, 6))}
-    return m, x, draws
+from _stream_cases import cpu_model
 
 
 def test_score_cells_on_a_cpu_model_fails_like_top_k():
-    m, x, draws = _cpu_model()
+    m, x, draws = cpu_model()
     with pytest.raises(Exception) as e_topk:
         m.top_k({"counts": x}, k=3, draws=draws)
     with pytest.raises(Exception) as e_cells:
@@ -28,7 +20,7 @@ def test_score_cells_on_a_cpu_model_fails_like_top_k():
 
 
 def test_unequal_lengths_and_an_iterable_raise_value_error():
-    m, x, draws = _cpu_model()
+    m, x, draws = cpu_model()
     with pytest.raises(ValueError):
         m.score_cells({"counts": x}, [0, 3], [1], draws=draws)
     with pytest.raises(ValueError):

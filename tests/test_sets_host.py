@@ -1,13 +1,8 @@
 """CPU-side tests of set_scores (PoissonFactorization.set_scores, spmf_set_scores, csrc/sets.hip) and of
-spmf_amd.sets: the entry points in the header, the export list and the binding, the method on the classes, the
-method's argument checks on a CPU-only model, pack / read_gmt, and the error contract of the entry through a raw
-ctypes call of this file's own (the draw stage's shared cases as tests/_stream_cases.assert_shared_errors lists
-them, then the entry's own) -- all refused before anything touches a device -- and the scratch size.  The valid
-call is tests/test_gpu_sets.py's.
-
-The call takes 15 arguments: ctx, counts, S, params, eta | n_sets, set_ptr, set_cols, set_weights, ld, mean, sd |
-scratch, scratch_bytes, stream -- the declaration of include/spmf_hip.h counted the way
-tests/test_stream_host.py counts the other entries (five in front, the entry's own, three behind)."""
+spmf_amd.sets: the method's argument checks on a CPU-only model, pack / read_gmt, the error contract of the entry
+through raw ctypes (the draw stage's shared cases, _stream_cases.assert_shared_errors, then the entry's own) -- all
+refused before anything touches a device -- and the scratch size.  (The method on the classes: the "sets" row of
+tests/test_stream_host.py; the valid call: tests/test_gpu_sets.py.)"""
 import ctypes as C
 import os
 
@@ -15,95 +10,32 @@ import numpy as np
 import pytest
 import torch
 
-from _stream_cases import B, D, K, S, assert_declared_exported_bound
+from _stream_cases import (B, ENTRIES, S, assert_declared_exported_bound, assert_shared_errors, cpu_model, host_ctx,
+                           host_good_call, library)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OWN = (("n_sets", C.c_int32), ("set_ptr", C.c_void_p), ("cols", C.c_void_p), ("weights", C.c_void_p),
-       ("ld", C.c_int64), ("mean", C.c_void_p), ("sd", C.c_void_p))
 
 
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    from spmf_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
-
-
-def test_entry_points_are_declared_exported_and_bound(lib):
+def test_entry_points_are_declared_exported_and_bound():
+    lib = library()
     assert_declared_exported_bound("spmf_sets_scratch_bytes", 5)
-    assert_declared_exported_bound("spmf_set_scores", len(OWN) + 8)
+    assert_declared_exported_bound("spmf_set_scores", len(ENTRIES["sets"].own) + 8)
     assert callable(lib.spmf_set_scores) and callable(lib.spmf_sets_scratch_bytes)
     assert lib.spmf_version() == 6
-
-
-def test_method_is_on_all_three_classes():
-    from spmf_amd import BernoulliFactorization, MixedFactorization, PoissonFactorization
-    for cls in (PoissonFactorization, BernoulliFactorization, MixedFactorization):
-        assert callable(getattr(cls, "set_scores", None)), cls.__name__
 
 
 def _i64(*v):
     return (C.c_int64 * len(v))(*v)
 
 
-def _host_good_call(lib):
-    """A valid-looking call that needs no device, as _stream_cases.host_good_call builds them: K = 3, D = 45, a
-    hand-filled descriptor of 70 empty rows, dummy aligned addresses, two sets of 4 and 5 listed columns (a real
-    host set_ptr).  Only refused and empty calls may be made with it."""
-    from spmf_amd import _lib
-    from spmf_amd._lib import VAR_ORDER
-    h, raw = C.c_void_p(), C.c_void_p()
-    assert lib.spmf_ctx_create(0, K, D, 0, C.byref(h)) == 0
-    assert lib.spmf_ctx_create(0, K, D, _lib.FLAG_MIXED, C.byref(raw)) == 0
-    cs = _lib.CountsStruct()
-    cs.struct_size = C.sizeof(_lib.CountsStruct)
-    cs.n_cols, cs.n_rows, cs.nnz, cs.row_ptr = D, B, 0, 0x10000
-    slots = {n: 0x100000 * (i + 1) for i, n in enumerate(VAR_ORDER) if n in ("s", "u", "v", "w")}
-    set_ptr = _i64(0, 4, 9)
-    need = int(lib.spmf_sets_scratch_bytes(h, B, S, 2, set_ptr))
-    assert need > 0 and need % 256 == 0
-    good = dict(h=h, ct=cs, S=S, pin=_lib.PtrArray(*[slots.get(n) for n in VAR_ORDER]), eta=0x7000000,
-                n_sets=2, set_ptr=set_ptr, cols=0x2000000, weights=0x3000000, ld=2, mean=0x4000000, sd=0x5000000,
-                ptr=0x8000000, nbytes=need, stream=None)
-    no_u = _lib.PtrArray(*[slots.get(n) if n != "u" else None for n in VAR_ORDER])
-    fn = C.CDLL(_lib.LIB_PATH).spmf_set_scores
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [t for _, t in OWN] + [
-        C.c_void_p, C.c_size_t, C.c_void_p]
-
-    def call(**kw):
-        a = dict(good, **kw)
-        sp = a["set_ptr"]
-        return fn(a["h"], C.byref(a["ct"]) if a["ct"] is not None else None, a["S"], a["pin"], a["eta"],
-                  a["n_sets"], C.cast(sp, C.c_void_p) if sp is not None else None, a["cols"], a["weights"],
-                  a["ld"], a["mean"], a["sd"], a["ptr"], a["nbytes"], a["stream"])
-
-    def cleanup():
-        lib.spmf_ctx_destroy(h)
-        lib.spmf_ctx_destroy(raw)
-    return good, need, no_u, raw, call, cleanup
-
-
-def test_shared_and_own_errors_return_before_any_device_call(lib):
-    good, need, no_u, raw, call, cleanup = _host_good_call(lib)
+def test_shared_and_own_errors_return_before_any_device_call():
+    """The dummy-address call of _stream_cases.host_good_call (K = 3, D = 45, 70 empty rows, two sets of 4 and 5
+    listed columns behind a real host set_ptr): only refused and empty calls may be made with it."""
+    lib = library()
+    good, need, no_u, raw, cleanup = host_good_call(lib, "sets")
     h, cs = good["h"], good["ct"]
     try:
-        # the draw stage's (tests/_stream_cases.assert_shared_errors, spelled for this entry)
-        assert call(S=0) == -1 and call(S=65536) == -1
-        for name in ("pin", "eta", "ptr", "ct"):
-            assert call(**{name: None}) == -1, name
-        assert call(pin=no_u) == -1, "slot u missing"
-        assert call(ptr=good["ptr"] + 4) == -1, "scratch off by 4 bytes"
-        bad = type(cs).from_buffer_copy(cs)
-        bad.struct_size += 8
-        assert call(ct=bad) == -1
-        assert call(h=raw) == -1
-        assert "column_types" in lib.spmf_last_error(raw).decode()
-        assert call(nbytes=need - 256) == -3
-        msg = lib.spmf_last_error(h).decode()
-        assert str(need) in msg and "set_scores" in msg, msg
+        call = assert_shared_errors(lib, "sets", good, need, no_u, raw)
         # the entry's own
         assert call(set_ptr=_i64(0, 5, 4)) == -1, "decreasing"
         assert "set_ptr" in lib.spmf_last_error(h).decode()
@@ -138,11 +70,11 @@ def test_shared_and_own_errors_return_before_any_device_call(lib):
 
 
 @pytest.mark.parametrize("k", [3, 16, 64, 128])
-def test_scratch_size(lib, k):
+def test_scratch_size(k):
     """0 for bad arguments; a multiple of 256; non-decreasing in the rows, in S and in the listed columns of a
     set; at least the draw carve (spmf_embed_scratch_bytes); a pure function of the padded sizes."""
-    h = C.c_void_p()
-    assert lib.spmf_ctx_create(0, k, D, 0, C.byref(h)) == 0
+    lib = library()
+    h = host_ctx(lib, k)
     try:
         def size(rows, s, ptr):
             return int(lib.spmf_sets_scratch_bytes(h, rows, s, len(ptr) - 1, _i64(*ptr)))
@@ -179,18 +111,8 @@ def test_scratch_size(lib, k):
 
 # ---- the method's argument checks ---------------------------------------------------------------
 
-def _cpu_model(**kw):
-    from spmf_amd import PoissonFactorization
-    m = PoissonFactorization(latent_dim=2, feature_dim=6, initialize_distributions=False, device="cpu", **kw)
-    rng = np.random.default_rng(0)
-    x = rng.poisson(1.0, size=(8, 6)).astype(np.float64)
-    draws = {"u": rng.random((2, 6, 2)), "v": rng.random((2, 2, 6)), "w": rng.random((2, 1, 6)),
-             "s": rng.random((2, 2, 6))}
-    return m, x, draws
-
-
 def test_bad_sets_and_weights_raise_value_error_without_a_device():
-    m, x, draws = _cpu_model()
+    m, x, draws = cpu_model()
     data = {"counts": x}
     with pytest.raises(ValueError, match="1-D"):
         m.set_scores(data, [np.arange(4).reshape(2, 2)], draws=draws)
@@ -217,7 +139,7 @@ def test_bad_sets_and_weights_raise_value_error_without_a_device():
 
 
 def test_sd_needs_two_draws():
-    m, x, draws = _cpu_model()
+    m, x, draws = cpu_model()
     one = {n: v[:1] for n, v in draws.items()}
     with pytest.raises(ValueError, match="at least 2 draws"):
         m.set_scores({"counts": x}, [[0, 1]], draws=one, sd=True)
@@ -226,7 +148,7 @@ def test_sd_needs_two_draws():
 
 
 def test_custom_codec_raises_after_the_argument_checks():
-    m, x, draws = _cpu_model(encoder_function=lambda t: t, decoder_function=lambda t: t)
+    m, x, draws = cpu_model(encoder_function=lambda t: t, decoder_function=lambda t: t)
     with pytest.raises(ValueError, match="must lie in"):
         m.set_scores({"counts": x}, [[0, 6]], draws=draws)
     with pytest.raises(NotImplementedError, match="set_scores"):
@@ -234,7 +156,7 @@ def test_custom_codec_raises_after_the_argument_checks():
 
 
 def test_a_valid_call_on_a_cpu_model_fails_like_top_k():
-    m, x, draws = _cpu_model()
+    m, x, draws = cpu_model()
     with pytest.raises(Exception) as e_topk:
         m.top_k({"counts": x}, k=3, draws=draws)
     with pytest.raises(Exception) as e_set:

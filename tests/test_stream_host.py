@@ -1,23 +1,13 @@
-"""CPU-side tests of the streaming calls of tests/_stream_cases.py's contract table (waic_streaming, top_k,
-score_cells, rank_cells, predict, group_means, embed): their entry points in the header, the export list and
+"""CPU-side tests of the streaming calls of tests/_stream_cases.py's contract table (waic_streaming with and
+without column sums, top_k, score_cells, rank_cells, predict, group_means, embed, top_rows, set_scores): their
+entry points in the header, the export list and
 the binding, the methods on the class surface, and the part of the C-ABI error contract they share, which is
 checked before anything touches a device -- every library call made here fails by contract (the valid call
 is tests/test_gpu_stream_abi.py's).  An entry's own argument errors are with its own *_host.py file."""
-import ctypes as C
-import os
-
 import pytest
 
-from _stream_cases import B, D, ENTRIES, assert_declared_exported_bound, assert_shared_errors, host_good_call
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    from spmf_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
+from _stream_cases import (B, ENTRIES, assert_declared_exported_bound, assert_shared_errors, host_ctx, host_good_call,
+                           library)
 
 
 @pytest.mark.parametrize("entry", list(ENTRIES))
@@ -37,9 +27,10 @@ def test_method_is_on_all_three_classes(entry):
 
 
 @pytest.mark.parametrize("entry", list(ENTRIES))
-def test_shared_errors_return_before_any_device_call(lib, entry):
+def test_shared_errors_return_before_any_device_call(entry):
     """The dummy-address call of _stream_cases.host_good_call: every shared error case is refused with its
     code; nothing here is a valid call."""
+    lib = library()
     good, need, no_u, raw, cleanup = host_good_call(lib, entry)
     try:
         assert_shared_errors(lib, entry, good, need, no_u, raw)
@@ -48,12 +39,12 @@ def test_shared_errors_return_before_any_device_call(lib, entry):
 
 
 @pytest.mark.parametrize("k", [3, 16, 64, 128])
-def test_scratch_sizes_of_the_three_calls(lib, k):
+def test_scratch_sizes_of_the_three_calls(k):
     """waic, topk and cells (the size of every later entry is with its own *_host.py file).  Multiples of 256; the
     cell call's scratch is the draw stage's alone (= the WAIC call's from two draws on), the top-k call adds its
     own buffers; 0 below the smallest S of each."""
-    h = C.c_void_p()
-    assert lib.spmf_ctx_create(0, k, D, 0, C.byref(h)) == 0
+    lib = library()
+    h = host_ctx(lib, k)
     try:
         for s in (2, 7):
             waic, topk, cells = (int(getattr(lib, ENTRIES[e].size)(h, B, s)) for e in ("waic", "topk", "cells"))

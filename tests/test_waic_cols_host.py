@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from _stream_cases import assert_declared_exported_bound
+from _stream_cases import assert_declared_exported_bound, library
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -90,11 +90,8 @@ def test_entry_point_is_declared_exported_and_bound():
 
 
 def test_library_exports_the_entry():
-    import __graft_entry__ as ge
     from spmf_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    lib = _lib.load()
+    lib = library()
     assert callable(lib.spmf_waic_accumulate_cols) and callable(lib.spmf_waic_accumulate)
     assert lib.spmf_version() == 6
     assert lib.spmf_waic_accumulate_cols(None, None, 2, _lib.PtrArray(), None, None, None, None, None, 0, None) == -1
