@@ -31,6 +31,11 @@ With --clusters G (deterministic k-means of the cells in the latent space, on th
 over the mean encoding of --cluster-draws posterior draws, started by k-means++ with --cluster-seed (which also
 seeds the draws).  Without --labels these labels feed the group table above; with --labels the file wins for
 the table.  Without the flag nothing changes.
+With --silhouette (beside --clusters or --labels; the clusters when both are given):
+  <stem>_silhouette_<P>.npy      [cells] float32: the silhouette of every cell in the latent space under those
+                                 labels (NaN: a cell without a label or a finite encoding)
+over the mean encoding of --cluster-draws posterior draws seeded by --cluster-seed (the encoding --clusters
+works on), and the overall score with the mean per cluster: all pairs of cells, exactly.
 With --gene-sets FILE.gmt (tab-separated: set name, description, member gene names, looked up in --genes):
   <stem>_setscore_<P>.npy        [cells, sets] posterior predictive expression summed over each gene set
   <stem>_setscore_sd_<P>.npy     [cells, sets] its standard deviation over the --set-draws posterior draws
@@ -71,6 +76,8 @@ def build_parser():
                                                               "clusters; writes the labels and the centroids")
     p.add_argument("--cluster-seed", type=int, default=0, help="seed of the k-means++ start and of the draws")
     p.add_argument("--cluster-draws", type=int, default=32, help="posterior draws of the clustered encoding")
+    p.add_argument("--silhouette", action="store_true", help="with --clusters or --labels: the silhouette of "
+                                                             "every cell under those labels, and the score")
     p.add_argument("--gene-sets", default=None, help="FILE.gmt: gene sets (name, description, members per line); "
                                                      "adds a score per cell and set with its posterior sd")
     p.add_argument("--set-draws", type=int, default=32, help="posterior draws of the gene-set scores (>= 2)")
@@ -96,7 +103,10 @@ def load_counts(path):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(sys.argv[1:] if argv is None else argv)
+    parser = build_parser()
+    args = parser.parse_args(sys.argv[1:] if argv is None else argv)
+    if args.silhouette and args.clusters is None and args.labels is None:
+        parser.error("--silhouette needs --clusters or --labels")
     if not os.path.exists(args.counts):
         sys.exit("File doesn't exist")
     import torch
@@ -164,6 +174,11 @@ def main(argv=None):
         group_table(factor, X, np.load(args.labels), gene_names, f"{stem}_groupmean_{P}.npy", args)
     elif clusters is not None:
         group_table(factor, X, clusters, gene_names, f"{stem}_groupmean_{P}.npy", args, n_groups=args.clusters)
+    if args.silhouette:
+        if clusters is not None:
+            silhouette_cells(factor, X, clusters, args.clusters, f"{stem}_silhouette_{P}.npy", args)
+        else:
+            silhouette_cells(factor, X, np.load(args.labels), None, f"{stem}_silhouette_{P}.npy", args)
     if args.gene_sets is not None:
         gene_set_scores(factor, X, gene_names, f"{stem}_setscore_{P}.npy", f"{stem}_setscore_sd_{P}.npy", args)
     if args.gene_waic:
@@ -210,6 +225,19 @@ def cluster_cells(factor, X, labels_path, centroid_path, args):
           f"{'' if res['converged'] else ' (not converged)'}, inertia {res['inertia']:.6g}, cells {sizes}"
           + (f", {res['n_unassigned']} without a cluster" if res["n_unassigned"] else ""))
     return labels
+
+
+def silhouette_cells(factor, X, labels, n_clusters, path, args):
+    """The silhouette of the cells under ``labels`` in the latent space (``silhouette`` on the encoding that
+    ``cluster_cells`` works on: the same seed, the same draws): the per-cell file, the score and the mean per
+    cluster."""
+    import torch
+    torch.manual_seed(args.cluster_seed)                  # the posterior draws of the encoding
+    emb = factor.embed({factor.count_key: X}, nsamples=args.cluster_draws)["mean"]
+    res = factor.silhouette(emb, labels, n_clusters)
+    np.save(path, res["silhouette"].cpu().numpy())
+    means = ", ".join(f"{v:.3f}" for v in res["cluster_mean"].tolist())
+    print(f"silhouette: {res['score']:.4f} over {res['n_scored']} cells; per cluster {means}")
 
 
 def group_table(factor, X, labels, gene_names, path, args, n_groups=None):

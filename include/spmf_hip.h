@@ -895,6 +895,57 @@ int spmf_kmeans_step(spmf_ctx* ctx, const float* x, int64_t n_rows, int row_len,
                      int32_t* labels_out, float* dist_out, double* sums_out, int64_t* counts_out,
                      double* stats_out, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- silhouette of labelled rows (added within ABI 6: two new entry points, no struct changed) ----
+ * For the rows x [n_rows][row_len] (fp32, device, 1 <= row_len <= 256 whatever the context's K) with
+ * labels int32 [n_rows] into 1 <= n_clusters <= 65536 clusters: every member's mean distance to its
+ * own cluster and to the nearest other one over ALL pairs, and the silhouette from the two, without an
+ * array of size n_rows * n_rows or n_rows * n_clusters (csrc/silhouette.hip).  The cost is n_rows^2
+ * distances.  The context serves the error message and the device only.  flags bit 0: cosine distance
+ * 1 - cos instead of the Euclidean distance.
+ *   Members: row i is a member of cluster g = labels[i] when 0 <= g < n_clusters and all its values
+ * are finite (under cosine its norm, the fp32 fmaf chain of knn's working rows, must also be positive
+ * and finite).  Every other row -- label -1 or any label outside [0, n_clusters), a non-finite row --
+ * is a non-member: it belongs to no cluster, gets sil = a = b = NaN and nearest = -1, and has no
+ * influence on any member's result, bit for bit.  n_g is the number of members of g.
+ *   Distances: working rows as spmf_knn's, Euclidean x' = x - c with c the mean of the member rows
+ * (fp64 sums in a fixed order, no float atomics, rounded to fp32), cosine x' = x/|x|; zero-padded to
+ * KP = 4 .. 256 and laid out in label order, stable in the row index, every cluster in whole 64-row
+ * blocks (the ordering of spmf_group_sums); bias_j = -1/2 |x'_j|^2 (fmaf chain, fp32).  The tile value
+ * t_ij = <x'_i, x'_j> + bias_j comes from the exact-f32 matrix cores (the tile loop of spmf_knn's
+ * selection), u_ij = -(bias_i + t_ij) = 1/2 |x'_i - x'_j|^2 in fp32, and
+ *   Euclidean d_ij = sqrtf(max(0, 2 u_ij)),   cosine d_ij = max(0, u_ij)   (= 1 - cos for unit rows).
+ * d_ii is not added; pad positions of a block are not added.  The absolute error of one d^2 is about
+ * 2^-24 KP (|x'_i|^2 + |x'_j|^2): distances far below the rows' norms are coarse.
+ *   Per member i of cluster g, all in fp64 (each fp32 d_ij is converted before its first addition):
+ * a_i = sum_{j in g, j != i} d_ij / (n_g - 1), 0 when n_g = 1;  b_i = the smallest over the clusters
+ * h != g with n_h > 0 of sum_{j in h} d_ij / n_h, nearest_i that h, equal means going to the smaller
+ * index;  s_i = 0 when n_g = 1 or max(a_i, b_i) = 0, else (b_i - a_i) / max(a_i, b_i), in [-1, 1].
+ * With fewer than two non-empty clusters b = +inf, nearest = -1 and s = NaN for every member.
+ * sil_out, a_out, b_out: fp32 [n_rows] in the caller's row order (the fp64 values rounded); a_out and
+ * b_out may be NULL.  nearest_out: int32 [n_rows], may be NULL.
+ *   Per cluster: cluster_sum_out[g], fp64 [n_clusters], = the sum of the fp64 s_i over the members of
+ * g (per 64-row block by a fixed tree, the blocks in ascending order; 0 for an empty cluster);
+ * counts_out[g], int64, = n_g.  Both are overwritten, not added to.  The caller forms the clusters'
+ * means and the overall score sum_g cluster_sum[g] / sum_g n_g.
+ *   Orders: a row's sum over a cluster adds, per position of a 64-row block, the blocks in ascending
+ * order, then the 64 positions by a fixed tree.  Everything is a function of (G, row_len, the
+ * members and their labels) alone: two calls return the same bits, and dropping the non-members from
+ * the input changes no bit of a member's results.
+ * scratch: 256-byte aligned, at least spmf_silhouette_scratch_bytes(ctx, n_rows, n_clusters, row_len)
+ * bytes, a multiple of 256, non-decreasing in n_rows; the size is 0 for bad arguments.
+ * SPMF_E_ARG for n_clusters outside 1..65536, row_len outside 1..256, n_rows outside 0..2^31 - 64,
+ * unknown flag bits, NULL cluster_sum_out / counts_out, NULL x / labels / sil_out with n_rows > 0, a
+ * NULL or misaligned scratch; then SPMF_E_WORKSPACE for a short scratch, naming the need; every error
+ * returns before any launch or write with "silhouette: " in front of the message.  n_rows == 0
+ * returns SPMF_OK after zero fills of cluster_sum_out and counts_out on the stream.  The context's
+ * workspace is not touched.  Stream-ordered, synchronises nowhere. */
+size_t spmf_silhouette_scratch_bytes(const spmf_ctx* ctx, int64_t n_rows, int32_t n_clusters,
+                                     int row_len);
+int spmf_silhouette(spmf_ctx* ctx, const float* x, int64_t n_rows, int row_len,
+                    const int32_t* labels, int32_t n_clusters, unsigned flags, float* sil_out,
+                    float* a_out, float* b_out, int32_t* nearest_out, double* cluster_sum_out,
+                    int64_t* counts_out, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Reductions of the non-finite rule (poisson.py:606-616) over a dense ll
  * buffer of n cells; io = double[3] on the device.
  *   pass 0: io[0] = min(io[0], min over finite cells)  (initialise io[0]=0:

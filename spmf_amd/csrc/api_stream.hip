@@ -1,5 +1,5 @@
 // api_stream.hip -- the streaming calls behind the C-ABI (include/spmf_hip.h): the draw stage, its consumers'
-// entries, spmf_knn and spmf_kmeans_step.  Host-side orchestration only (ctx.h).
+// entries, spmf_knn, spmf_kmeans_step and spmf_silhouette.  Host-side orchestration only (ctx.h).
 #include <stdlib.h>
 
 #include "ctx.h"
@@ -705,6 +705,73 @@ int spmf_kmeans_step(spmf_ctx* c, const float* x, int64_t n_rows, int row_len, c
   ma.labels = labels_out; ma.dist = dist_out; ma.sums = sums_out; ma.counts = counts_out; ma.stats = stats_out;
   launch_kmeans(ma, st);
   return launched(c, true, "");
+}
+
+// ---- the silhouette of labelled rows (silhouette.hip behind groups.hip's ordering) -------------
+// Scratch of one call: the effective labels, the ordering of the members by label (launch_group_order), the
+// working rows and biases in that order, the centre with its partial sums, and the blocks' sums of s (kernels.h
+// silhouette_geom bounds the blocks).  Every region grows with the rows.
+static void silhouette_layout(Arena& a, int64_t rows, int G, int row_len, SilhouetteArgs& sa) {
+  const SilhouetteGeom q = silhouette_geom(rows, G);
+  sa.n_rows = rows; sa.row_len = row_len; sa.n_clusters = G;
+  sa.KP = knn_padded(row_len);
+  const size_t nr = rows, nG = G, NB = (size_t)q.NB, KP = sa.KP;
+  sa.eff = a.take<int32_t>(nr);
+  sa.tbl = a.take<int32_t>((size_t)q.chunks * nG);
+  sa.lrank = a.take<int32_t>(nr);
+  sa.cnt = a.take<int32_t>(nG);
+  sa.boff = a.take<int32_t>(nG + 1);
+  sa.fincl = a.take<int32_t>(nG);
+  sa.rec = a.take<int4>(NB);
+  sa.perm = a.take<int32_t>(NB * 64);
+  sa.w = a.take<float>(NB * 64 * KP);
+  sa.bias = a.take<float>(NB * 64);
+  sa.cpart = a.take<double>((size_t)kSilCentreBlocks * KP);
+  sa.ccnt = a.take<int32_t>(kSilCentreBlocks);
+  sa.centre = a.take<float>(KP);
+  sa.spart = a.take<double>(NB);
+}
+
+size_t spmf_silhouette_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int32_t n_clusters, int row_len) {
+  if (!c || !kmeans_shape_ok(n_rows, n_clusters, row_len)) return 0;
+  Arena a;
+  SilhouetteArgs sa{};
+  silhouette_layout(a, n_rows, n_clusters, row_len, sa);
+  return a.used;
+}
+
+int spmf_silhouette(spmf_ctx* c, const float* x, int64_t n_rows, int row_len, const int32_t* labels,
+    int32_t n_clusters, unsigned flags, float* sil_out, float* a_out, float* b_out, int32_t* nearest_out,
+    double* cluster_sum_out, int64_t* counts_out, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!c) return SPMF_E_ARG;
+  const std::string f = "silhouette: ";
+  if (n_clusters < 1 || n_clusters > kKmeansMaxClusters) return fail(c, SPMF_E_ARG, f + "n_clusters must be in "
+      "1..65536");
+  if (row_len < 1 || row_len > 256) return fail(c, SPMF_E_ARG, f + "row_len must be in 1..256");
+  if (n_rows < 0 || n_rows > ((int64_t)1 << 31) - 64) return fail(c, SPMF_E_ARG, f + "n_rows must be in "
+      "0..2^31 - 64");
+  if (flags & ~1u) return fail(c, SPMF_E_ARG, f + "unknown flag (bit 0: cosine)");
+  if (!scratch) return fail(c, SPMF_E_ARG, f + "null argument");
+  if (!cluster_sum_out || !counts_out || (n_rows > 0 && (!x || !labels || !sil_out))) return fail(c, SPMF_E_ARG,
+      f + "null argument");
+  if ((uintptr_t)scratch & 255) return fail(c, SPMF_E_ARG, f + "scratch must be 256-byte aligned");
+  SilhouetteArgs sa{};
+  Arena a(scratch, scratch_bytes);
+  silhouette_layout(a, n_rows, n_clusters, row_len, sa);
+  if (!a.fits()) return scratch_too_small(c, "silhouette", a.used, scratch_bytes,
+      "n_rows=" + std::to_string((long long)n_rows) + " n_clusters=" + std::to_string(n_clusters) + " row_len=" +
+      std::to_string(row_len));
+  hipStream_t st = (hipStream_t)stream;
+  if (n_rows == 0) {
+    HIPCHK(c, hipMemsetAsync(cluster_sum_out, 0, (size_t)n_clusters * sizeof(double), st));
+    HIPCHK(c, hipMemsetAsync(counts_out, 0, (size_t)n_clusters * sizeof(int64_t), st));
+    return SPMF_OK;
+  }
+  sa.cosine = (flags & 1u) != 0;
+  sa.x = x; sa.labels = labels;
+  sa.sil = sil_out; sa.a = a_out; sa.b = b_out; sa.nearest = nearest_out;
+  sa.cluster_sum = cluster_sum_out; sa.counts = counts_out;
+  return launched(c, launch_silhouette(sa, st), "silhouette: no kernel for this row_len");
 }
 
 }  // extern "C"

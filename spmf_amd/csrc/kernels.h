@@ -421,6 +421,34 @@ struct KmeansArgs {
   double* spart;                   // [sblocks][3]
 };
 void launch_kmeans(const KmeansArgs& a, hipStream_t st);
+// silhouette.hip: the silhouette of labelled rows over all pairs (include/spmf_hip.h spmf_silhouette has the
+// definition).  The scratch pointers are api_stream.hip's carve, sized from silhouette_geom; every order of
+// additions depends on the members' labels alone.  false: KP not built or no row (nothing launched).
+constexpr int kSilCentreBlocks = 512;    // runs of blocks whose partial sums make the centre
+struct SilhouetteGeom {
+  int64_t NB, chunks;              // row blocks (bound: ceil(n_rows / 64) + G), rank chunks
+};
+SilhouetteGeom silhouette_geom(int64_t n_rows, int G);
+struct SilhouetteArgs {
+  int64_t n_rows;
+  int row_len, KP, n_clusters;
+  bool cosine;
+  const float* x;                  // [n_rows][row_len]
+  const int32_t* labels;           // [n_rows]
+  float *sil, *a, *b;              // [n_rows]; a and b may be null
+  int32_t* nearest;                // [n_rows] or null
+  double* cluster_sum;             // [G]
+  int64_t* counts;                 // [G]
+  int32_t* eff;                    // [n_rows]: the effective labels
+  int32_t *tbl, *lrank, *cnt, *boff, *fincl, *perm;   // as launch_group_order
+  int4* rec;
+  float *w, *bias;                 // working rows [64 NB][KP] in group order, bias [64 NB]
+  double* cpart;                   // [kSilCentreBlocks][KP]
+  int32_t* ccnt;                   // [kSilCentreBlocks]
+  float* centre;                   // [KP]
+  double* spart;                   // [NB]: the blocks' sums of s
+};
+bool launch_silhouette(const SilhouetteArgs& a, hipStream_t st);
 // sets.hip: per row and column set the fp64 weighted sum over the set's listed columns of the posterior
 // predictive mean m_s, reduced over the draws: mean [B][ld] (column g = set g) and, where asked for, the unbiased
 // standard deviation over the draws (S >= 2).  set_ptr: HOST, [n_sets + 1], set g lists cols[set_ptr[g] ..

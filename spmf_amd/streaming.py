@@ -1,6 +1,6 @@
 """The streaming posterior queries of the model classes: ``StreamingQueries`` is the mixin that gives
 PoissonFactorization (and through it the Bernoulli and mixed classes) waic_streaming, top_k, score_cells,
-rank_cells, predict, top_rows, group_means, set_scores, embed, knn, neighbors, kmeans and cluster.
+rank_cells, predict, top_rows, group_means, set_scores, embed, knn, neighbors, kmeans, cluster and silhouette.
 
 Every draw-stage query is the same three pieces around its own kernel (include/spmf_hip.h, csrc/api_stream.hip "the
 draw stage"): ``_Draws``, the checked draws and the one place a library call is spelled; a driver that walks
@@ -268,15 +268,22 @@ class StreamingQueries:
             if int(labels.numel()) != n_rows:
                 raise ValueError(f"{name}: labels must have one entry per row, got {int(labels.numel())} for "
                                  f"{n_rows} rows")
+        n_groups = self._label_range(name, labels, n_groups, "n_groups")
+        return labels.to(device=self.device, dtype=torch.int32).contiguous(), n_groups, counted
+
+    @staticmethod
+    def _label_range(name, labels, n_groups, what):
+        """``n_groups`` (None: max(labels) + 1) with the 1-D integer ``labels`` checked to lie in
+        {-1, 0 .. n_groups - 1} -> n_groups."""
         lo, hi = (int(labels.min()), int(labels.max())) if labels.numel() else (-1, -1)
         if n_groups is None:
             n_groups = hi + 1
         n_groups = int(n_groups)
         if n_groups < 1:
-            raise ValueError(f"{name}: n_groups must be at least 1, got {n_groups}")
+            raise ValueError(f"{name}: {what} must be at least 1, got {n_groups}")
         if lo < -1 or hi >= n_groups:
             raise ValueError(f"{name}: labels must lie in [-1, {n_groups}) (-1: no group), got {lo} .. {hi}")
-        return labels.to(device=self.device, dtype=torch.int32).contiguous(), n_groups, counted
+        return n_groups
 
     # ------------------------------------------------------------------
     # the queries
@@ -780,6 +787,72 @@ class StreamingQueries:
             start = _cluster.init_plus_plus(pts, G, seed)
         return _cluster.lloyd(self._handle(), pts, start, max_iter)
 
+    def silhouette(self, points, labels, n_clusters=None, metric="euclidean"):
+        """The exact silhouette of the rows of ``points`` [N, Kx] under ``labels``: per row its mean distance to
+        the other rows of its cluster (a), the smallest mean distance to the rows of another cluster (b, that
+        cluster in 'nearest') and s = (b - a) / max(a, b); per cluster the mean of s; and their overall mean, the
+        score that answers "how many clusters?" where ``kmeans``' inertia only falls.  One library call
+        (include/spmf_hip.h spmf_silhouette has the definition, csrc/silhouette.hip): every pair of rows on the
+        matrix cores, fp64 sums in a fixed order, no [N, N] or [N, G] array.
+
+        ``points``: a float32 tensor on the model's device with 1 <= Kx <= 256 whatever the model's latent_dim.
+        ``labels``: 1-D integers (numpy or torch on any device), one per row, in {-1, 0 .. n_clusters - 1}; -1 is
+        "no cluster" (what ``kmeans`` gives a non-finite row).  ``n_clusters`` (at most 65536) defaults to
+        max(labels) + 1.  ``metric``: 'euclidean' or 'cosine' (the distance 1 - cos).  A row with label -1 or a
+        non-finite value (under 'cosine' a zero row too) is no member of any cluster: its outputs are NaN /
+        nearest -1 and it changes no bit of any other row's result.
+
+        Returns device tensors 'silhouette', 'a', 'b' (float32 [N]), 'nearest' (int32 [N]), 'cluster_mean'
+        (fp64 [G], NaN for an empty cluster) and 'counts' (int64 [G], the members), and the host values 'score'
+        (the sum of the clusters' fp64 sums of s over the number of members; NaN with fewer than two non-empty
+        clusters) and 'n_scored' (the members).  A singleton cluster's row has s = 0.  Bit-reproducible.
+
+        Cost and accuracy: N^2 pairs -- sample rows (``points[idx]``, ``labels[idx]``) where that is too many.
+        Distances come from the fp32 expansion |x_i|^2 + |x_j|^2 - 2 <x_i, x_j> of centred (or unit) rows: the
+        absolute error of one squared distance is about 2^-24 * KP * (|x'_i|^2 + |x'_j|^2), with KP the width
+        rounded up to 4, 8, .., 256, so distances far below the rows' norms are coarse.  Separated clusters are
+        scored to fp32 accuracy; a near-collinear cloud with large norms (an untrained model's embedding) is
+        scored coarsely."""
+        from . import neighbors as _neighbors
+        pts = self._knn_rows("silhouette", "points", points)
+        if metric not in _neighbors.METRICS:
+            raise ValueError(f"silhouette: metric must be one of {_neighbors.METRICS}, got {metric!r}")
+        if n_clusters is not None:
+            if isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer)):
+                raise ValueError(f"silhouette: n_clusters must be an integer, got {n_clusters!r}")
+        labels = _vector("silhouette", "labels", labels)
+        N, width = int(pts.shape[0]), int(pts.shape[1])
+        if int(labels.numel()) != N:
+            raise ValueError(f"silhouette: labels must have one entry per row, got {int(labels.numel())} for "
+                             f"{N} rows")
+        G = self._label_range("silhouette", labels, n_clusters, "n_clusters")
+        if G > 65536:
+            raise ValueError(f"silhouette: n_clusters must be at most 65536, got {G}")
+        if N > 2 ** 31 - 64:
+            raise ValueError(f"silhouette: {N} points are beyond one call of the library")
+        dev = torch.device(self.device)
+        if pts.device.type != "cuda" or (dev.index is not None and pts.device != dev):
+            raise ValueError(f"silhouette: points must be on the model's device {self.device}, got {pts.device}")
+        pts = pts.contiguous()
+        labels = labels.to(device=pts.device, dtype=torch.int32).contiguous()
+        lib, h = _lib.load(), self._handle()
+        sil, a, b = (torch.empty(N, dtype=torch.float32, device=pts.device) for _ in range(3))
+        nearest = torch.empty(N, dtype=torch.int32, device=pts.device)
+        sums = torch.empty(G, dtype=torch.float64, device=pts.device)
+        counts = torch.empty(G, dtype=torch.int64, device=pts.device)
+        scratch = _Scratch(pts.device)
+        _lib.check(h, lib.spmf_silhouette(
+            h, pts.data_ptr(), N, width, labels.data_ptr(), G, 1 if metric == "cosine" else 0, sil.data_ptr(),
+            a.data_ptr(), b.data_ptr(), nearest.data_ptr(), sums.data_ptr(), counts.data_ptr(),
+            *scratch.fit(lib.spmf_silhouette_scratch_bytes(h, N, G, width)),
+            torch.cuda.current_stream(pts.device).cuda_stream), "spmf_silhouette")
+        n = counts.to(torch.float64)
+        mean = sums / n.masked_fill(counts == 0, float("nan"))
+        total, members, nonempty = torch.stack([sums.sum(), n.sum(), (counts > 0).sum().to(torch.float64)]).tolist()
+        score = total / members if nonempty >= 2 else float("nan")
+        return {"silhouette": sil, "a": a, "b": b, "nearest": nearest, "cluster_mean": mean, "counts": counts,
+                "score": score, "n_scored": int(members)}
+
     def cluster(self, data, n_clusters, nsamples=32, draws=None, max_rows=None, init="k-means++", max_iter=100,
                 seed=0):
         """k-means of the rows of ``data`` in the model's latent space: ``embed`` on ``data``, then ``kmeans``
@@ -788,7 +861,8 @@ class StreamingQueries:
         ``n_clusters``, ``init``, ``max_iter`` and ``seed`` as in ``kmeans``.
 
         Returns what ``kmeans`` returns, bit for bit ``kmeans(embed(data, draws=draws)["mean"], ...)``, and
-        'embedding': float32 [N, latent_dim].  The labels are those ``group_means`` takes."""
+        'embedding': float32 [N, latent_dim].  The labels are those ``group_means`` takes, and
+        ``silhouette(res["embedding"], res["labels"], n_clusters)`` scores the clustering."""
         from . import cluster as _cluster
         G, max_iter = _cluster.check_args("cluster", n_clusters, max_iter, init)
         if not 1 <= self.latent_dim <= 256:
