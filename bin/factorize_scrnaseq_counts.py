@@ -36,6 +36,13 @@ With --silhouette (beside --clusters or --labels; the clusters when both are giv
                                  labels (NaN: a cell without a label or a finite encoding)
 over the mean encoding of --cluster-draws posterior draws seeded by --cluster-seed (the encoding --clusters
 works on), and the overall score with the mean per cluster: all pairs of cells, exactly.
+With --umap (the 2-D map on which cells, clusters and factor scores are looked at):
+  <stem>_UMAP_<P>.npy            [cells, 2] float32: the layout of the cells' fuzzy neighbour graph in the latent
+                                 space (NaN: a cell without a finite encoding) -- the file the reference's
+                                 plotting script loads as <dataset>_UMAP_scanpy.npy
+from --umap-neighbors neighbours per cell, --umap-min-dist and --umap-epochs (default: 500 up to 10 000 cells,
+200 above), over the mean encoding of --cluster-draws posterior draws seeded by --cluster-seed (the encoding
+--clusters labels; the seed also draws the layout's negatives).  Without the flag nothing changes.
 With --gene-sets FILE.gmt (tab-separated: set name, description, member gene names, looked up in --genes):
   <stem>_setscore_<P>.npy        [cells, sets] posterior predictive expression summed over each gene set
   <stem>_setscore_sd_<P>.npy     [cells, sets] its standard deviation over the --set-draws posterior draws
@@ -78,6 +85,11 @@ def build_parser():
     p.add_argument("--cluster-draws", type=int, default=32, help="posterior draws of the clustered encoding")
     p.add_argument("--silhouette", action="store_true", help="with --clusters or --labels: the silhouette of "
                                                              "every cell under those labels, and the score")
+    p.add_argument("--umap", action="store_true", help="writes the 2-D layout of the cells' neighbour graph in the "
+                                                       "latent space")
+    p.add_argument("--umap-neighbors", type=int, default=15, help="neighbours per cell of the layout's graph")
+    p.add_argument("--umap-min-dist", type=float, default=0.1, help="min_dist of the layout's curve")
+    p.add_argument("--umap-epochs", type=int, default=None, help="epochs of the layout (default: by size)")
     p.add_argument("--gene-sets", default=None, help="FILE.gmt: gene sets (name, description, members per line); "
                                                      "adds a score per cell and set with its posterior sd")
     p.add_argument("--set-draws", type=int, default=32, help="posterior draws of the gene-set scores (>= 2)")
@@ -179,6 +191,8 @@ def main(argv=None):
             silhouette_cells(factor, X, clusters, args.clusters, f"{stem}_silhouette_{P}.npy", args)
         else:
             silhouette_cells(factor, X, np.load(args.labels), None, f"{stem}_silhouette_{P}.npy", args)
+    if args.umap:
+        umap_cells(factor, X, f"{stem}_UMAP_{P}.npy", args)
     if args.gene_sets is not None:
         gene_set_scores(factor, X, gene_names, f"{stem}_setscore_{P}.npy", f"{stem}_setscore_sd_{P}.npy", args)
     if args.gene_waic:
@@ -238,6 +252,22 @@ def silhouette_cells(factor, X, labels, n_clusters, path, args):
     np.save(path, res["silhouette"].cpu().numpy())
     means = ", ".join(f"{v:.3f}" for v in res["cluster_mean"].tolist())
     print(f"silhouette: {res['score']:.4f} over {res['n_scored']} cells; per cluster {means}")
+
+
+def umap_cells(factor, X, path, args):
+    """The 2-D map of the cells (``umap`` on the encoding that ``cluster_cells`` works on: the same seed, the same
+    draws): the coordinates as a file."""
+    import torch
+    torch.manual_seed(args.cluster_seed)                  # the posterior draws of the encoding
+    res = factor.umap({factor.count_key: X}, k=args.umap_neighbors, nsamples=args.cluster_draws,
+                      n_epochs=args.umap_epochs, min_dist=args.umap_min_dist, seed=args.cluster_seed)
+    y = res["embedding"].cpu().numpy()
+    np.save(path, y)
+    ok = np.isfinite(y).all(1)
+    span = np.abs(y[ok]).max() if ok.any() else float("nan")
+    print(f"umap: {y.shape[0]} cells, {int(res['graph']['indices'].numel())} graph entries, {res['n_epochs']} "
+          f"epochs, a = {res['a']:.4f}, b = {res['b']:.4f}, extent {span:.3g}"
+          + (f", {int((~ok).sum())} cells without a position" if not ok.all() else ""))
 
 
 def group_table(factor, X, labels, gene_names, path, args, n_groups=None):

@@ -946,6 +946,55 @@ int spmf_silhouette(spmf_ctx* ctx, const float* x, int64_t n_rows, int row_len,
                     float* a_out, float* b_out, int32_t* nearest_out, double* cluster_sum_out,
                     int64_t* counts_out, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- epochs of a 2-D graph layout (added within ABI 6: two new entry points, no struct changed) ----
+ * The full-batch form of UMAP's layout objective on a weighted graph in CSR form (csrc/graph_layout.hip):
+ * indptr int64 [n_rows + 1], indices int32 [nnz], weights fp32 [nnz], positions y_in / y_out fp32
+ * [n_rows][2], all on the device; y_out may be y_in (they may not overlap otherwise).  The call runs the
+ * epochs e = epoch0 .. epoch0 + n_epochs - 1 of a schedule of total_epochs, one launch per epoch behind a
+ * copy of y_in into the scratch.  The context serves the error message and the device only.
+ *   One epoch reads the positions y of the epoch before it and writes every row's new position into
+ * the other buffer (Jacobi, alternating between the two halves of the scratch, the last epoch into
+ * y_out): no row writes another row's position, so there are no atomics and no races.  For row i with
+ * its valid entries (j, w_ij), W_i = sum_j w_ij, D = y_i - y_j, d2 = |D|^2, clip4 = the clamp of each
+ * component to [-4, 4], q = a d2^b (through exp2f(b log2f(d2))):
+ *   attraction  F_i  = sum_j w_ij clip4(c_a D),  c_a = -2ab d2^(b-1) / (1 + q) = -2b q / (d2 (1 + q));
+ *               the term is 0 when d2 = 0;
+ *   repulsion   F_i += (negative_rate W_i / M) sum_{m < M} clip4(c_r (y_i - y_r)),
+ *               c_r = 2 repulsion b / ((0.001 + d2)(1 + q)),  r = r(i, e, m),  M = n_negatives;
+ *               the term is 0 when r = i, when d2 = 0 or when y_r is not finite; the scale keeps M;
+ *   update      y_i <- y_i + alpha_e F_i / max(1, W_i),  alpha_e = lr (1 - e / total_epochs), formed in
+ *               fp64 on the host and passed as fp32.
+ * An entry of weight w is what UMAP's sampler visits w times an epoch, each visit with negative_rate
+ * negatives, and both endpoints pull themselves.  The division by max(1, W_i) makes the simultaneous
+ * step a convex combination of clipped per-entry steps.  a, b, -2b, 2 repulsion b and
+ * negative_rate / M are rounded to fp32 once; all arithmetic of an epoch is fp32.
+ *   Negatives: Philox4x32-10 with key = (seed's low word, seed's high word) and counter =
+ * (i, m >> 2, e, 0x554D4150); word m & 3 of the block in x, y, z, w order; r = the high 32 bits of
+ * word * n_rows.  A draw is a function of (seed, i, e, m, n_rows): epochs split over several calls
+ * give the bits of one call.
+ *   Robustness: an entry whose index lies outside [0, n_rows), whose weight is not finite and
+ * positive or whose neighbour's position is not finite is skipped (it is no part of W_i); indptr
+ * values are clamped to [0, nnz]; no argument values make a kernel read outside its arrays.  A row
+ * with a non-finite position keeps its bits, and so does a row with W_i = 0, which is still a
+ * possible negative of others.
+ *   Order: a row's additions run in an order fixed by its own list length and M alone (16 lanes
+ * striding the list, then a fixed tree); two calls return the same bits.
+ * scratch: 256-byte aligned, at least spmf_graph_layout_scratch_bytes(ctx, n_rows) bytes, a multiple
+ * of 256, non-decreasing in n_rows; the size is 0 for bad arguments.
+ * SPMF_E_ARG for n_rows outside 0..2^31 - 64 or nnz < 0, n_negatives outside 1..64, epoch0 < 0,
+ * n_epochs < 0 or epoch0 + n_epochs > total_epochs, a <= 0, b <= 0, a non-finite or negative lr /
+ * repulsion / negative_rate, NULL indptr / y_in / y_out with n_rows > 0 (indices / weights with
+ * nnz > 0 too), a NULL or misaligned scratch; then SPMF_E_WORKSPACE for a short scratch, naming the
+ * need; every error returns before any launch or write with "graph_layout: " in front of the
+ * message.  n_rows == 0 or n_epochs == 0 returns SPMF_OK; with n_epochs == 0 and y_out != y_in, y_in
+ * is copied.  The context's workspace is not touched.  Stream-ordered, synchronises nowhere. */
+size_t spmf_graph_layout_scratch_bytes(const spmf_ctx* ctx, int64_t n_rows);
+int spmf_graph_layout(spmf_ctx* ctx, int64_t n_rows, int64_t nnz, const int64_t* indptr,
+                      const int32_t* indices, const float* weights, const float* y_in, float* y_out,
+                      int epoch0, int n_epochs, int total_epochs, double lr, double a, double b,
+                      double repulsion, double negative_rate, int n_negatives, uint64_t seed,
+                      void* scratch, size_t scratch_bytes, void* stream);
+
 /* Reductions of the non-finite rule (poisson.py:606-616) over a dense ll
  * buffer of n cells; io = double[3] on the device.
  *   pass 0: io[0] = min(io[0], min over finite cells)  (initialise io[0]=0:

@@ -186,6 +186,11 @@ SIGNATURES = {
     "spmf_silhouette": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int32, C.c_uint,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spmf_graph_layout_scratch_bytes": (C.c_size_t, [C.c_void_p, C.c_int64]),
+    "spmf_graph_layout": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                    C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint64, C.c_void_p,
+                                    C.c_size_t, C.c_void_p]),
     "spmf_nonfinite_reduce": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
                                         C.c_void_p, C.c_void_p]),
     "spmf_comm_unique_id": (C.c_int, [C.c_void_p]),

@@ -1,5 +1,5 @@
 // api_stream.hip -- the streaming calls behind the C-ABI (include/spmf_hip.h): the draw stage, its consumers'
-// entries, spmf_knn, spmf_kmeans_step and spmf_silhouette.  Host-side orchestration only (ctx.h).
+// entries, spmf_knn, spmf_kmeans_step, spmf_silhouette and spmf_graph_layout.  Host-side orchestration only (ctx.h).
 #include <stdlib.h>
 
 #include "ctx.h"
@@ -772,6 +772,71 @@ int spmf_silhouette(spmf_ctx* c, const float* x, int64_t n_rows, int row_len, co
   sa.sil = sil_out; sa.a = a_out; sa.b = b_out; sa.nearest = nearest_out;
   sa.cluster_sum = cluster_sum_out; sa.counts = counts_out;
   return launched(c, launch_silhouette(sa, st), "silhouette: no kernel for this row_len");
+}
+
+// ---- the epochs of a 2-D graph layout (graph_layout.hip) ---------------------------------------
+// Scratch of one call: the two position buffers the epochs alternate between; the first takes the start.
+static bool graph_layout_rows_ok(int64_t n_rows) { return n_rows >= 0 && n_rows <= ((int64_t)1 << 31) - 64; }
+static void graph_layout_carve(Arena& a, int64_t rows, GraphLayoutArgs& ga) {
+  const size_t n = rows > 0 ? (size_t)rows : 1;
+  ga.buf[0] = a.take<float2>(n);
+  ga.buf[1] = a.take<float2>(n);
+}
+
+size_t spmf_graph_layout_scratch_bytes(const spmf_ctx* c, int64_t n_rows) {
+  if (!c || !graph_layout_rows_ok(n_rows)) return 0;
+  Arena a;
+  GraphLayoutArgs ga{};
+  graph_layout_carve(a, n_rows, ga);
+  return a.used;
+}
+
+int spmf_graph_layout(spmf_ctx* c, int64_t n_rows, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+    const float* weights, const float* y_in, float* y_out, int epoch0, int n_epochs, int total_epochs, double lr,
+    double a, double b, double repulsion, double negative_rate, int n_negatives, uint64_t seed, void* scratch,
+    size_t scratch_bytes, void* stream) {
+  if (!c) return SPMF_E_ARG;
+  const std::string f = "graph_layout: ";
+  auto weight_ok = [](double v) { return v >= 0.0 && v <= 3.0e38; };          // finite, not negative, an fp32
+  if (!graph_layout_rows_ok(n_rows)) return fail(c, SPMF_E_ARG, f + "n_rows must be in 0..2^31 - 64");
+  if (nnz < 0) return fail(c, SPMF_E_ARG, f + "nnz is negative");
+  if (n_negatives < 1 || n_negatives > 64) return fail(c, SPMF_E_ARG, f + "n_negatives must be in 1..64");
+  if (epoch0 < 0 || n_epochs < 0 || (int64_t)epoch0 + n_epochs > (int64_t)total_epochs) return fail(c, SPMF_E_ARG,
+      f + "epochs: epoch0 >= 0, n_epochs >= 0 and epoch0 + n_epochs <= total_epochs must hold");
+  if (!(a > 0.0) || !(b > 0.0) || !(a <= 3.0e38) || !(b <= 3.0e38)) return fail(c, SPMF_E_ARG, f + "a and b must be "
+      "positive and finite");
+  if (!weight_ok(lr) || !weight_ok(repulsion) || !weight_ok(negative_rate)) return fail(c, SPMF_E_ARG, f + "lr, "
+      "repulsion and negative_rate must be finite and not negative");
+  if (n_rows > 0 && (!indptr || !y_in || !y_out || (nnz > 0 && (!indices || !weights)))) return fail(c, SPMF_E_ARG,
+      f + "null argument");
+  if (!scratch) return fail(c, SPMF_E_ARG, f + "null argument");
+  if ((uintptr_t)scratch & 255) return fail(c, SPMF_E_ARG, f + "scratch must be 256-byte aligned");
+  GraphLayoutArgs ga{};
+  Arena ar(scratch, scratch_bytes);
+  graph_layout_carve(ar, n_rows, ga);
+  if (!ar.fits()) return scratch_too_small(c, "graph_layout", ar.used, scratch_bytes,
+      "n_rows=" + std::to_string((long long)n_rows));
+  if (n_rows == 0) return SPMF_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t bytes = (size_t)n_rows * sizeof(float2);
+  if (n_epochs == 0) {
+    if (y_out != y_in) HIPCHK(c, hipMemcpyAsync(y_out, y_in, bytes, hipMemcpyDeviceToDevice, st));
+    return SPMF_OK;
+  }
+  // the prologue: the start goes into the first buffer, so no epoch reads y_in or y_out (they may be one)
+  HIPCHK(c, hipMemcpyAsync(ga.buf[0], y_in, bytes, hipMemcpyDeviceToDevice, st));
+  ga.n_rows = n_rows; ga.nnz = nnz;
+  ga.indptr = indptr; ga.indices = indices; ga.weights = weights;
+  ga.y_out = (float2*)y_out;
+  ga.epoch0 = epoch0; ga.n_epochs = n_epochs; ga.total_epochs = total_epochs; ga.n_negatives = n_negatives;
+  ga.lr = lr;
+  ga.a = (float)a; ga.b = (float)b;
+  ga.neg2b = (float)(-2.0 * b);
+  ga.two_gamma_b = (float)(2.0 * repulsion * b);
+  ga.rate_over_m = (float)(negative_rate / (double)n_negatives);
+  ga.seed_lo = (uint32_t)seed; ga.seed_hi = (uint32_t)(seed >> 32);
+  launch_graph_layout(ga, st);
+  return launched(c, true, "");
 }
 
 }  // extern "C"

@@ -449,6 +449,24 @@ struct SilhouetteArgs {
   double* spart;                   // [NB]: the blocks' sums of s
 };
 bool launch_silhouette(const SilhouetteArgs& a, hipStream_t st);
+// graph_layout.hip: the epochs of a 2-D layout of a CSR graph (include/spmf_hip.h spmf_graph_layout has the
+// definition).  One launch per epoch: epoch k reads every position of `from` and writes every row's position to
+// `to`, the last epoch into y_out; buf[0] / buf[1] are the api's two scratch buffers and buf[0] holds the start.
+// The step of epoch e is lr * (1 - e / total_epochs), formed in fp64 here and passed as fp32.  The graph is read as it stands: every index, weight
+// and indptr value is checked in the kernel.
+struct GraphLayoutArgs {
+  int64_t n_rows, nnz;
+  const int64_t* indptr;           // [n_rows + 1]
+  const int32_t* indices;          // [nnz]
+  const float* weights;            // [nnz]
+  float2* buf[2];                  // [n_rows] each
+  float2* y_out;                   // [n_rows]
+  int epoch0, n_epochs, total_epochs, n_negatives;
+  double lr;
+  float a, b, neg2b, two_gamma_b, rate_over_m;    // fp64 on the host, each rounded once
+  uint32_t seed_lo, seed_hi;
+};
+void launch_graph_layout(const GraphLayoutArgs& a, hipStream_t st);
 // sets.hip: per row and column set the fp64 weighted sum over the set's listed columns of the posterior
 // predictive mean m_s, reduced over the draws: mean [B][ld] (column g = set g) and, where asked for, the unbiased
 // standard deviation over the draws (S >= 2).  set_ptr: HOST, [n_sets + 1], set g lists cols[set_ptr[g] ..

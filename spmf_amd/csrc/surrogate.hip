@@ -23,6 +23,7 @@
 // All O(D*K) elementwise: HBM bound, microseconds.
 #include "common.h"
 #include "kernels.h"
+#include "philox.h"
 
 namespace spmf {
 
@@ -347,17 +348,7 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamTable T, AdamCoef k) {
 //             with P the regularised lower incomplete gamma function, from its series
 //             P(a,x) = sum_n T_n,  T_n = x^(a+n) e^-x / Gamma(a+n+1),
 //             dT_n/da = T_n (log x - psi(a+n+1)),  in fp64.
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-    c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
-    k.x += 0x9E3779B9u;
-    k.y += 0xBB67AE85u;
-  }
-  return c;
-}
+//   philox4x32_10: philox.h (graph_layout.hip draws from it too).
 __device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }  // (0,1)
 __device__ __forceinline__ float normal_bm(uint32_t a, uint32_t b) {
   return sqrtf(-2.f * logf(u01(a))) * cospif(2.f * u01(b));

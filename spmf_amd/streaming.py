@@ -1,6 +1,7 @@
 """The streaming posterior queries of the model classes: ``StreamingQueries`` is the mixin that gives
 PoissonFactorization (and through it the Bernoulli and mixed classes) waic_streaming, top_k, score_cells,
-rank_cells, predict, top_rows, group_means, set_scores, embed, knn, neighbors, kmeans, cluster and silhouette.
+rank_cells, predict, top_rows, group_means, set_scores, embed, knn, neighbors, kmeans, cluster, silhouette,
+fuzzy_graph, graph_layout and umap.
 
 Every draw-stage query is the same three pieces around its own kernel (include/spmf_hip.h, csrc/api_stream.hip "the
 draw stage"): ``_Draws``, the checked draws and the one place a library call is spelled; a driver that walks
@@ -852,6 +853,167 @@ class StreamingQueries:
         score = total / members if nonempty >= 2 else float("nan")
         return {"silhouette": sil, "a": a, "b": b, "nearest": nearest, "cluster_mean": mean, "counts": counts,
                 "score": score, "n_scored": int(members)}
+
+    def fuzzy_graph(self, indices, distances):
+        """The symmetric fuzzy neighbour graph of a ``knn`` result (``knn(points)`` on one set of rows): UMAP's
+        graph, scanpy's ``obsp["connectivities"]``.  ``spmf_amd.graph.fuzzy_graph`` has the definition; plain
+        torch in fp64 on the tensors' device, one stable sort and no scatter-add, so reproducible.  Returns
+        {'indptr': int64 [N+1], 'indices': int32, 'weights': float32, 'sigma', 'rho': fp64 [N]}: what
+        ``graph_layout`` takes, and ``spmf_amd.graph.to_csr`` turns it into the numpy CSR arrays."""
+        from . import graph as _graph
+        return _graph.fuzzy_graph(indices, distances)
+
+    @staticmethod
+    def _layout_args(name, n_epochs, min_dist, spread, a, b, n_negatives, negative_rate, repulsion, learning_rate,
+                     seed, init):
+        """The layout arguments of ``graph_layout`` / ``umap`` that need no graph, checked before any library
+        call -> namespace(n_epochs (or None), a, b, M, rate, gamma, lr, seed)."""
+        from . import graph as _graph
+
+        def integer(what, v, lo, hi):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+                raise ValueError(f"{name}: {what} must be an integer in {lo}..{hi}, got {v!r}")
+            return int(v)
+
+        def weight(what, v, positive=False):
+            ok = isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
+            if not ok or not np.isfinite(v) or v < 0 or v > 3.0e38 or (positive and v <= 0):
+                raise ValueError(f"{name}: {what} must be a finite number {'> 0' if positive else '>= 0'}, got {v!r}")
+            return float(v)
+        if n_epochs is not None:
+            n_epochs = integer("n_epochs", n_epochs, 0, 2 ** 31 - 1)
+        M = integer("n_negatives", n_negatives, 1, _graph.MAX_NEGATIVES)
+        seed = integer("seed", seed, 0, 2 ** 64 - 1)
+        rate, gamma = weight("negative_rate", negative_rate), weight("repulsion", repulsion)
+        lr = weight("learning_rate", learning_rate)
+        if (a is None) != (b is None):
+            raise ValueError(f"{name}: a and b go together (both, or neither for the fit to min_dist and spread)")
+        if a is None:
+            try:
+                a, b = _graph.find_ab(min_dist, spread)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"{name}: {e}") from None
+        else:
+            a, b = weight("a", a, positive=True), weight("b", b, positive=True)
+        if not isinstance(init, torch.Tensor) and not (isinstance(init, str) and init in _graph.INITS):
+            raise ValueError(f"{name}: init must be one of {_graph.INITS} or a float32 [N, 2] tensor, got {init!r}")
+        return SimpleNamespace(n_epochs=n_epochs, a=a, b=b, M=M, rate=rate, gamma=gamma, lr=lr, seed=seed)
+
+    def graph_layout(self, graph, init="pca", points=None, n_epochs=None, min_dist=0.1, spread=1.0, a=None, b=None,
+                     n_negatives=8, negative_rate=5.0, repulsion=1.0, learning_rate=1.0, seed=0):
+        """A deterministic 2-D layout of a weighted graph: the full-batch form of UMAP's objective, one kernel
+        launch per epoch (include/spmf_hip.h spmf_graph_layout has the definition, csrc/graph_layout.hip).  Every
+        epoch moves every row at once from the positions of the epoch before: along its edges towards its
+        neighbours, weighted by the edge, and away from ``n_negatives`` rows drawn by a counter-based generator
+        from (``seed``, row, epoch); the step is divided by max(1, the row's summed weight), which keeps the
+        simultaneous update from overshooting.  No atomics: two runs give the same bits.
+
+        ``graph``: what ``fuzzy_graph`` returns -- 'indptr' int64 [N+1] (monotone from 0 to nnz), 'indices' int32
+        in [0, N), 'weights' float32, on the model's device.  ``init``: a float32 [N, 2] tensor on the device;
+        'pca': the two leading principal axes of ``points`` [N, Kx] (``spmf_amd.graph.init_pca``: fp64 covariance
+        of the finite rows, max |coordinate| = 10, a non-finite row starts NaN and stays); 'random': uniform
+        [-10, 10] from a CPU generator seeded with ``seed``.  ``n_epochs``: None is 500 for N <= 10 000, else 200.
+        (``a``, ``b``): the curve 1 / (1 + a d^(2b)); None fits them to (``min_dist``, ``spread``) as umap-learn
+        does.  ``negative_rate``: negatives per visit of an edge (umap-learn's negative_sample_rate), spread over
+        the ``n_negatives`` (1..64) draws of a row; ``repulsion``: their strength; ``learning_rate``: the first
+        epoch's step, falling linearly to 0.
+
+        Returns {'embedding': float32 [N, 2] on the device, 'a', 'b', 'n_epochs'}.  Bit-reproducible for a tensor or
+        'pca' init on one machine; for 'random' the same seed gives the same result."""
+        from . import graph as _graph
+        name = "graph_layout"
+        la = self._layout_args(name, n_epochs, min_dist, spread, a, b, n_negatives, negative_rate, repulsion,
+                               learning_rate, seed, init)
+        if not isinstance(graph, dict) or any(n not in graph for n in ("indptr", "indices", "weights")):
+            raise ValueError(f"{name}: graph must be a dict with 'indptr', 'indices' and 'weights' (fuzzy_graph)")
+        want = {"indptr": torch.int64, "indices": torch.int32, "weights": torch.float32}
+        for n, dt in want.items():
+            t = graph[n]
+            if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != dt:
+                raise ValueError(f"{name}: graph['{n}'] must be a 1-D {dt} tensor")
+        indptr, indices, weights = (graph[n] for n in want)
+        if indptr.numel() < 1:
+            raise ValueError(f"{name}: graph['indptr'] must have N + 1 entries")
+        N, nnz = int(indptr.numel()) - 1, int(indices.numel())
+        if int(weights.numel()) != nnz:
+            raise ValueError(f"{name}: graph['weights'] has {int(weights.numel())} entries, graph['indices'] {nnz}")
+        if N > 2 ** 31 - 64:
+            raise ValueError(f"{name}: {N} rows are beyond one call of the library")
+        if indices.device != indptr.device or weights.device != indptr.device:
+            raise ValueError(f"{name}: the graph's tensors must be on one device")
+        if isinstance(init, torch.Tensor):
+            if init.dim() != 2 or tuple(init.shape) != (N, 2) or init.dtype != torch.float32:
+                raise ValueError(f"{name}: an init tensor must be float32 of shape {(N, 2)}, got {init.dtype} "
+                                 f"{tuple(init.shape)}")
+            if init.device != indptr.device:
+                raise ValueError(f"{name}: an init tensor must be on the device of the graph {indptr.device}, got "
+                                 f"{init.device}")
+        elif init == "pca":
+            if not isinstance(points, torch.Tensor) or points.dim() != 2 or not points.dtype.is_floating_point \
+                    or int(points.shape[0]) != N or int(points.shape[1]) < 1:
+                raise ValueError(f"{name}: init='pca' needs points, a floating-point [N, Kx] tensor with N = {N} rows")
+            if points.device != indptr.device:
+                raise ValueError(f"{name}: points must be on the device of the graph {indptr.device}, got "
+                                 f"{points.device}")
+        # the graph's numbers: one device-side reduction and one read-back, before any library call
+        ends = torch.stack([indptr[0], indptr[-1]])
+        step = torch.diff(indptr).amin().reshape(1) if N else torch.zeros(1, dtype=torch.int64, device=indptr.device)
+        span = torch.stack(list(torch.aminmax(indices))).to(torch.int64) if nnz else \
+            torch.zeros(2, dtype=torch.int64, device=indptr.device)
+        first, last, step, lo, hi = torch.cat([ends, step, span]).tolist()
+        if first != 0 or last != nnz or step < 0:
+            raise ValueError(f"{name}: graph['indptr'] must rise from 0 to the {nnz} entries, got {first} .. {last}"
+                             + (" with a falling step" if step < 0 else ""))
+        if nnz and (lo < 0 or hi >= N):
+            raise ValueError(f"{name}: graph['indices'] must lie in [0, {N}), got {lo} .. {hi}")
+        dev = torch.device(self.device)
+        if indptr.device.type != "cuda" or (dev.index is not None and indptr.device != dev):
+            raise ValueError(f"{name}: the graph must be on the model's device {self.device}, got {indptr.device}")
+        total = _graph.default_epochs(N) if la.n_epochs is None else la.n_epochs
+        if isinstance(init, torch.Tensor):
+            start = init.contiguous()
+        elif init == "pca":
+            start = _graph.init_pca(points)
+        else:
+            start = _graph.init_random(N, la.seed, indptr.device)
+        indptr, indices, weights = indptr.contiguous(), indices.contiguous(), weights.contiguous()
+        lib, h = _lib.load(), self._handle()
+        out = torch.empty(N, 2, dtype=torch.float32, device=indptr.device)
+        scratch = _Scratch(indptr.device)
+        _lib.check(h, lib.spmf_graph_layout(
+            h, N, nnz, indptr.data_ptr(), indices.data_ptr(), weights.data_ptr(), start.data_ptr(), out.data_ptr(),
+            0, total, total, la.lr, la.a, la.b, la.gamma, la.rate, la.M, la.seed,
+            *scratch.fit(lib.spmf_graph_layout_scratch_bytes(h, N)),
+            torch.cuda.current_stream(indptr.device).cuda_stream), "spmf_graph_layout")
+        return {"embedding": out, "a": la.a, "b": la.b, "n_epochs": total}
+
+    def umap(self, data, k=15, metric="euclidean", nsamples=32, draws=None, max_rows=None, init="pca", n_epochs=None,
+             min_dist=0.1, spread=1.0, a=None, b=None, n_negatives=8, negative_rate=5.0, repulsion=1.0,
+             learning_rate=1.0, seed=0):
+        """The 2-D map of the rows of ``data``: ``embed`` on ``data``, ``knn`` on the posterior mean encodings,
+        ``fuzzy_graph`` on their result and ``graph_layout`` on the graph ('pca' starts from the encodings) --
+        the coordinates scanpy keeps in ``obsm["X_umap"]``, on which clusters, factor scores and genes are looked
+        at.  ``data``, ``nsamples`` / ``draws`` and ``max_rows`` as in ``embed`` (the rows of all batches are
+        concatenated); ``k`` and ``metric`` as in ``knn``; the layout arguments as in ``graph_layout`` (``init``: a
+        tensor, 'pca' or 'random').
+
+        Returns what ``graph_layout`` returns, bit for bit the four calls made by hand, and 'graph' (the fuzzy
+        graph), 'latent' (the encoding, float32 [N, latent_dim]) and the 'indices' / 'distances' of ``knn``.
+        Bit-reproducible for given draws with a tensor or 'pca' init on one machine; for 'random' the same seed
+        gives the same result."""
+        self._knn_args("umap", k, metric)
+        self._layout_args("umap", n_epochs, min_dist, spread, a, b, n_negatives, negative_rate, repulsion,
+                          learning_rate, seed, init)
+        if not 1 <= self.latent_dim <= 256:
+            raise ValueError(f"umap: latent_dim {self.latent_dim} is beyond the 256 columns of knn")
+        emb = self.embed(data, nsamples=nsamples, draws=draws, max_rows=max_rows)["mean"]
+        nn = self.knn(emb, k=k, metric=metric)
+        g = self.fuzzy_graph(nn["indices"], nn["distances"])
+        res = self.graph_layout(g, init=init, points=emb, n_epochs=n_epochs, min_dist=min_dist, spread=spread, a=a,
+                                b=b, n_negatives=n_negatives, negative_rate=negative_rate, repulsion=repulsion,
+                                learning_rate=learning_rate, seed=seed)
+        res.update(graph=g, latent=emb, indices=nn["indices"], distances=nn["distances"])
+        return res
 
     def cluster(self, data, n_clusters, nsamples=32, draws=None, max_rows=None, init="k-means++", max_iter=100,
                 seed=0):
