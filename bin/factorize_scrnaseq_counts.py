@@ -43,6 +43,13 @@ With --umap (the 2-D map on which cells, clusters and factor scores are looked a
 from --umap-neighbors neighbours per cell, --umap-min-dist and --umap-epochs (default: 500 up to 10 000 cells,
 200 above), over the mean encoding of --cluster-draws posterior draws seeded by --cluster-seed (the encoding
 --clusters labels; the seed also draws the layout's negatives).  Without the flag nothing changes.
+With --map-counts FILE beside --umap (new cells over the same genes, e.g. a second sample; .npy dense or .npz CSR):
+  <stem>_UMAP_map_<P>.npy        [new cells, 2] float32: the new cells on the map above, which does not move (NaN:
+                                 a cell without a finite encoding)
+  <stem>_label_map_<P>.npy       [new cells] int64, with --clusters or --labels: the label with the largest summed
+                                 membership among a new cell's --umap-neighbors nearest cells of --counts (-1: none;
+                                 the clusters when both are given)
+over the same draws and seed.  Without the flag nothing changes.
 With --gene-sets FILE.gmt (tab-separated: set name, description, member gene names, looked up in --genes):
   <stem>_setscore_<P>.npy        [cells, sets] posterior predictive expression summed over each gene set
   <stem>_setscore_sd_<P>.npy     [cells, sets] its standard deviation over the --set-draws posterior draws
@@ -90,6 +97,8 @@ def build_parser():
     p.add_argument("--umap-neighbors", type=int, default=15, help="neighbours per cell of the layout's graph")
     p.add_argument("--umap-min-dist", type=float, default=0.1, help="min_dist of the layout's curve")
     p.add_argument("--umap-epochs", type=int, default=None, help="epochs of the layout (default: by size)")
+    p.add_argument("--map-counts", default=None, help="FILE: new cells over the same genes; with --umap they are "
+                                                      "placed on the map (and labelled with --clusters / --labels)")
     p.add_argument("--gene-sets", default=None, help="FILE.gmt: gene sets (name, description, members per line); "
                                                      "adds a score per cell and set with its posterior sd")
     p.add_argument("--set-draws", type=int, default=32, help="posterior draws of the gene-set scores (>= 2)")
@@ -119,6 +128,10 @@ def main(argv=None):
     args = parser.parse_args(sys.argv[1:] if argv is None else argv)
     if args.silhouette and args.clusters is None and args.labels is None:
         parser.error("--silhouette needs --clusters or --labels")
+    if args.map_counts is not None and not args.umap:
+        parser.error("--map-counts needs --umap")
+    if args.map_counts is not None and not os.path.exists(args.map_counts):
+        sys.exit("File doesn't exist")
     if not os.path.exists(args.counts):
         sys.exit("File doesn't exist")
     import torch
@@ -192,7 +205,15 @@ def main(argv=None):
         else:
             silhouette_cells(factor, X, np.load(args.labels), None, f"{stem}_silhouette_{P}.npy", args)
     if args.umap:
-        umap_cells(factor, X, f"{stem}_UMAP_{P}.npy", args)
+        reference = umap_cells(factor, X, f"{stem}_UMAP_{P}.npy", args)
+        if args.map_counts is not None:
+            known = clusters if clusters is not None else (np.load(args.labels) if args.labels is not None else None)
+            X_new = load_counts(args.map_counts)
+            if X_new.ndim != 2 or X_new.shape[1] != D:
+                sys.exit(f"--map-counts must hold [cells, {D}] counts over the genes of --counts, got {X_new.shape}")
+            map_cells(factor, X_new, reference, known,
+                      args.clusters if clusters is not None else None, f"{stem}_UMAP_map_{P}.npy",
+                      f"{stem}_label_map_{P}.npy", args)
     if args.gene_sets is not None:
         gene_set_scores(factor, X, gene_names, f"{stem}_setscore_{P}.npy", f"{stem}_setscore_sd_{P}.npy", args)
     if args.gene_waic:
@@ -268,6 +289,30 @@ def umap_cells(factor, X, path, args):
     print(f"umap: {y.shape[0]} cells, {int(res['graph']['indices'].numel())} graph entries, {res['n_epochs']} "
           f"epochs, a = {res['a']:.4f}, b = {res['b']:.4f}, extent {span:.3g}"
           + (f", {int((~ok).sum())} cells without a position" if not ok.all() else ""))
+    return res
+
+
+def map_cells(factor, X_new, reference, labels, n_classes, path, label_path, args):
+    """New cells on the map of ``umap_cells`` (``umap_transform`` with the same seed and draws: the map itself
+    stays as written): their coordinates as a file and, with ``labels`` of the mapped-on cells, the voted labels."""
+    import torch
+    torch.manual_seed(args.cluster_seed)                  # the posterior draws of the encoding
+    res = factor.umap_transform({factor.count_key: X_new}, reference, k=args.umap_neighbors,
+                                nsamples=args.cluster_draws, labels=labels, n_classes=n_classes,
+                                seed=args.cluster_seed)
+    y = res["embedding"].cpu().numpy()
+    np.save(path, y)
+    ok = np.isfinite(y).all(1)
+    line = f"umap map: {y.shape[0]} new cells on {reference['embedding'].shape[0]}, {res['n_epochs']} epochs"
+    if not ok.all():
+        line += f", {int((~ok).sum())} cells without a position"
+    if labels is not None:
+        voted = res["labels"].cpu().numpy()
+        np.save(label_path, voted)
+        share = res["label_share"].cpu().numpy()
+        line += (f", {int((voted >= 0).sum())} labelled, mean share of the winning label "
+                 f"{float(np.nanmean(share)) if (voted >= 0).any() else float('nan'):.3f}")
+    print(line)
 
 
 def group_table(factor, X, labels, gene_names, path, args, n_groups=None):

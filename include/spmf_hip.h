@@ -995,6 +995,51 @@ int spmf_graph_layout(spmf_ctx* ctx, int64_t n_rows, int64_t nnz, const int64_t*
                       double repulsion, double negative_rate, int n_negatives, uint64_t seed,
                       void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- new rows on a fitted 2-D layout (added within ABI 6: one new entry point, no scratch) ----
+ * umap-learn's transform (csrc/graph_transform.hip): n_query new rows are laid out among n_ref reference
+ * rows whose positions y_ref fp32 [n_ref][2] stay fixed.  idx int32 and w fp32 [n_query][k] hold every
+ * query row's k neighbours among the reference rows and their memberships (a bipartite graph in dense
+ * form); y_in / y_out fp32 [n_query][2]; all on the device.  y_out may be y_in (they may not overlap
+ * otherwise); y_in may be NULL.  The call runs the epochs e = epoch0 .. epoch0 + n_epochs - 1 of a
+ * schedule of total_epochs in ONE launch: no query row reads another query row, so a row's 16 lanes load
+ * its neighbours once, keep them in registers and write y_out once.  The context serves the error message
+ * and the device only.
+ *   Query row i has the global number g = row0 + i.  Its valid entries are the (j, w_ij) with
+ * 0 <= j < n_ref, w_ij finite and > 0 and y_ref[j] finite; W_i = the sum of the valid weights.
+ *   Start: with y_in == NULL, y_i = sum_j w_ij y_j / W_i, (NaN, NaN) when W_i = 0; else y_in[i].
+ *   One epoch e, with D = y_i - y_j, d2 = |D|^2, clip4 and q = a d2^b as in spmf_graph_layout:
+ *   attraction  F_i  = sum_j w_ij clip4(c_a D),  c_a = -2b q / (d2 (1 + q)); the term is 0 when d2 = 0;
+ *   repulsion   F_i += (negative_rate W_i / M) sum_{m < M} clip4(c_r (y_i - y_ref[r])),
+ *               c_r = 2 repulsion b / ((0.001 + d2)(1 + q)),  r = r(g, e, m),  M = n_negatives;
+ *               the term is 0 when d2 = 0 or when y_ref[r] is not finite (there is no r = i rule: the
+ *               two row sets differ); the scale keeps M;
+ *   update      y_i <- y_i + alpha_e F_i / max(1, W_i),  alpha_e = (float)(lr (1 - e / total_epochs)),
+ *               formed in fp64 in the kernel: the bits spmf_graph_layout forms on the host.
+ * a, b, -2b, 2 repulsion b and negative_rate / M are rounded to fp32 once; all other arithmetic of an
+ * epoch is fp32.
+ *   Negatives: Philox4x32-10 with key = (seed's low word, seed's high word) and counter =
+ * ((uint32)g, m >> 2, e, 0x554D5854); word m & 3 of the block in x, y, z, w order; r = the high 32 bits
+ * of word * n_ref.  With n_ref == 0 no negative is drawn and nothing of y_ref is read.
+ *   Rows that keep their bits: a row whose position is not finite (from y_in, or after an epoch), and a
+ * row with W_i = 0 -- from a NULL y_in it is NaN.
+ *   Order: a row's additions run in an order fixed by k and M alone (lane l of 16 takes the entries
+ * l, l + 16, .. and the negatives l, l + 16, .., then a fixed tree).  A row's result is a function of
+ * its own entries, y_ref, g and the arguments: rows may be mapped in chunks of any size, with row0 the
+ * chunk's first global number, and epochs split over several calls (through epoch0 and y_in) give the
+ * bits of one call.  No argument values make the kernel read outside its arrays.
+ * SPMF_E_ARG for k outside 1..64, n_negatives outside 1..64, n_query < 0, n_ref outside 0..2^31 - 1,
+ * row0 < 0 or row0 + n_query > 2^32, epoch0 < 0, n_epochs < 0 or epoch0 + n_epochs > total_epochs,
+ * a <= 0, b <= 0, a non-finite or negative lr / repulsion / negative_rate, NULL idx / w / y_out with
+ * n_query > 0, NULL y_ref with n_ref > 0, NULL y_in with epoch0 > 0 (a continued schedule needs its
+ * positions); every error returns before any launch or write with "graph_transform: " in front of the
+ * message.  n_query == 0 returns SPMF_OK; with n_epochs == 0 the start is written, or y_in is copied
+ * when y_out differs.  The context's workspace is not touched.  Stream-ordered, synchronises nowhere. */
+int spmf_graph_transform(spmf_ctx* ctx, int64_t n_query, int k, const int32_t* idx, const float* w,
+                         const float* y_ref, int64_t n_ref, const float* y_in, float* y_out,
+                         int64_t row0, int epoch0, int n_epochs, int total_epochs, double lr, double a,
+                         double b, double repulsion, double negative_rate, int n_negatives,
+                         uint64_t seed, void* stream);
+
 /* Reductions of the non-finite rule (poisson.py:606-616) over a dense ll
  * buffer of n cells; io = double[3] on the device.
  *   pass 0: io[0] = min(io[0], min over finite cells)  (initialise io[0]=0:

@@ -191,6 +191,10 @@ SIGNATURES = {
                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                                     C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint64, C.c_void_p,
                                     C.c_size_t, C.c_void_p]),
+    "spmf_graph_transform": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                       C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
+                                       C.c_uint64, C.c_void_p]),
     "spmf_nonfinite_reduce": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
                                         C.c_void_p, C.c_void_p]),
     "spmf_comm_unique_id": (C.c_int, [C.c_void_p]),

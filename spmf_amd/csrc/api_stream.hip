@@ -1,5 +1,6 @@
 // api_stream.hip -- the streaming calls behind the C-ABI (include/spmf_hip.h): the draw stage, its consumers'
-// entries, spmf_knn, spmf_kmeans_step, spmf_silhouette and spmf_graph_layout.  Host-side orchestration only (ctx.h).
+// entries, spmf_knn, spmf_kmeans_step, spmf_silhouette, spmf_graph_layout and spmf_graph_transform.  Host-side
+// orchestration only (ctx.h).
 #include <stdlib.h>
 
 #include "ctx.h"
@@ -836,6 +837,53 @@ int spmf_graph_layout(spmf_ctx* c, int64_t n_rows, int64_t nnz, const int64_t* i
   ga.rate_over_m = (float)(negative_rate / (double)n_negatives);
   ga.seed_lo = (uint32_t)seed; ga.seed_hi = (uint32_t)(seed >> 32);
   launch_graph_layout(ga, st);
+  return launched(c, true, "");
+}
+
+// ---- new rows on a fitted 2-D layout (graph_transform.hip) --------------------------------------
+// No scratch: the one launch keeps a row's state in registers.
+int spmf_graph_transform(spmf_ctx* c, int64_t n_query, int k, const int32_t* idx, const float* w,
+    const float* y_ref, int64_t n_ref, const float* y_in, float* y_out, int64_t row0, int epoch0, int n_epochs,
+    int total_epochs, double lr, double a, double b, double repulsion, double negative_rate, int n_negatives,
+    uint64_t seed, void* stream) {
+  if (!c) return SPMF_E_ARG;
+  const std::string f = "graph_transform: ";
+  auto weight_ok = [](double v) { return v >= 0.0 && v <= 3.0e38; };          // finite, not negative, an fp32
+  if (k < 1 || k > 64) return fail(c, SPMF_E_ARG, f + "k must be in 1..64");
+  if (n_negatives < 1 || n_negatives > 64) return fail(c, SPMF_E_ARG, f + "n_negatives must be in 1..64");
+  if (n_query < 0) return fail(c, SPMF_E_ARG, f + "n_query is negative");
+  if (n_ref < 0 || n_ref > ((int64_t)1 << 31) - 1) return fail(c, SPMF_E_ARG, f + "n_ref must be in 0..2^31 - 1");
+  if (row0 < 0 || row0 > ((int64_t)1 << 32) || n_query > ((int64_t)1 << 32) - row0) return fail(c, SPMF_E_ARG,
+      f + "row0 >= 0 and row0 + n_query <= 2^32 must hold");
+  if (epoch0 < 0 || n_epochs < 0 || (int64_t)epoch0 + n_epochs > (int64_t)total_epochs) return fail(c, SPMF_E_ARG,
+      f + "epochs: epoch0 >= 0, n_epochs >= 0 and epoch0 + n_epochs <= total_epochs must hold");
+  if (!(a > 0.0) || !(b > 0.0) || !(a <= 3.0e38) || !(b <= 3.0e38)) return fail(c, SPMF_E_ARG, f + "a and b must be "
+      "positive and finite");
+  if (!weight_ok(lr) || !weight_ok(repulsion) || !weight_ok(negative_rate)) return fail(c, SPMF_E_ARG, f + "lr, "
+      "repulsion and negative_rate must be finite and not negative");
+  if ((n_query > 0 && (!idx || !w || !y_out)) || (n_ref > 0 && !y_ref)) return fail(c, SPMF_E_ARG,
+      f + "null argument");
+  if (!y_in && epoch0 > 0) return fail(c, SPMF_E_ARG, f + "y_in is null with epoch0 > 0: a continued schedule needs "
+      "its positions");
+  if (n_query == 0) return SPMF_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (n_epochs == 0 && y_in) {
+    if (y_out != y_in) HIPCHK(c, hipMemcpyAsync(y_out, y_in, (size_t)n_query * sizeof(float2),
+                                                hipMemcpyDeviceToDevice, st));
+    return SPMF_OK;
+  }
+  GraphTransformArgs ga{};
+  ga.n_query = n_query; ga.n_ref = n_ref; ga.row0 = row0; ga.k = k;
+  ga.idx = idx; ga.w = w;
+  ga.y_ref = (const float2*)y_ref; ga.y_in = (const float2*)y_in; ga.y_out = (float2*)y_out;
+  ga.epoch0 = epoch0; ga.n_epochs = n_epochs; ga.total_epochs = total_epochs; ga.n_negatives = n_negatives;
+  ga.lr = lr;
+  ga.a = (float)a; ga.b = (float)b;
+  ga.neg2b = (float)(-2.0 * b);
+  ga.two_gamma_b = (float)(2.0 * repulsion * b);
+  ga.rate_over_m = (float)(negative_rate / (double)n_negatives);
+  ga.seed_lo = (uint32_t)seed; ga.seed_hi = (uint32_t)(seed >> 32);
+  launch_graph_transform(ga, st);
   return launched(c, true, "");
 }
 

@@ -467,6 +467,25 @@ struct GraphLayoutArgs {
   uint32_t seed_lo, seed_hi;
 };
 void launch_graph_layout(const GraphLayoutArgs& a, hipStream_t st);
+// graph_transform.hip: the epochs of new rows on a fitted layout, the reference positions held fixed
+// (include/spmf_hip.h spmf_graph_transform has the definition).  One launch for all epochs of the call: a row keeps
+// its neighbours in registers and reads only y_ref.  The struct is the kernel's argument: the step of epoch e is
+// formed in the kernel from lr and total_epochs in fp64.  idx, w, y_ref and y_in are read as they stand: every
+// index, weight and position is checked in the kernel.
+struct GraphTransformArgs {
+  int64_t n_query, n_ref, row0;
+  int k;
+  const int32_t* idx;              // [n_query][k]
+  const float* w;                  // [n_query][k]
+  const float2* y_ref;             // [n_ref]
+  const float2* y_in;              // [n_query], or null: the weighted mean of the neighbours
+  float2* y_out;                   // [n_query]; may be y_in
+  int epoch0, n_epochs, total_epochs, n_negatives;
+  double lr;
+  float a, b, neg2b, two_gamma_b, rate_over_m;    // fp64 on the host, each rounded once
+  uint32_t seed_lo, seed_hi;
+};
+void launch_graph_transform(const GraphTransformArgs& a, hipStream_t st);
 // sets.hip: per row and column set the fp64 weighted sum over the set's listed columns of the posterior
 // predictive mean m_s, reduced over the draws: mean [B][ld] (column g = set g) and, where asked for, the unbiased
 // standard deviation over the draws (S >= 2).  set_ptr: HOST, [n_sets + 1], set g lists cols[set_ptr[g] ..

@@ -6,6 +6,10 @@ that the tests compare with.  Importable without a GPU; numpy and torch only.
 The graph and the starts are plain torch on the tensors' device, fp64: a start, not a hot path.  The epochs -- the
 hot path -- are the library's; ``layout_reference`` restates include/spmf_hip.h spmf_graph_layout in fp64 numpy,
 Philox in integer arithmetic and every skip rule included.
+
+New rows on a fitted layout (graph_transform / umap_transform, spmf_graph_transform, csrc/graph_transform.hip):
+``query_weights`` gives their memberships in their neighbours among the reference rows, ``transform_reference``
+restates the library's epochs with the reference held fixed, ``transform_negatives`` its draws.
 """
 from __future__ import annotations
 
@@ -18,19 +22,15 @@ _PHILOX_TAG = 0x554D4150          # the fourth counter word of a layout draw
 
 
 # ---- the fuzzy graph -----------------------------------------------------------------------------------------
-def _smooth_knn(dist, valid):
-    """umap-learn's smooth_knn_dist with local_connectivity 1, for all rows at once: ``dist`` fp64 [N,k] with the
-    invalid positions anything, ``valid`` bool [N,k] -> (sigma, rho) fp64 [N]."""
+def _bisect_sigma(excess, valid, n_valid):
+    """The 64 bisection steps of smooth_knn_dist for all rows at once: sigma with
+    sum_j exp(-excess_ij / sigma) = log2(n_valid_i) over the valid positions (lo = 0, hi = inf, sigma = 1, doubling
+    while hi is inf).  ``excess`` fp64 [N,k], 0 where invalid -> fp64 [N], not yet floored."""
     inf = float("inf")
-    n_valid = valid.sum(1)
-    positive = valid & (dist > 0)
-    rho = torch.where(positive, dist, torch.full_like(dist, inf)).amin(1)
-    rho = torch.where(torch.isfinite(rho), rho, torch.zeros_like(rho))
-    excess = torch.where(valid, (dist - rho[:, None]).clamp_min(0.0), torch.zeros_like(dist))
     target = torch.log2(n_valid.clamp_min(1).to(torch.float64))
-    lo = torch.zeros_like(rho)
-    hi = torch.full_like(rho, inf)
-    sigma = torch.ones_like(rho)
+    lo = torch.zeros_like(target)
+    hi = torch.full_like(target, inf)
+    sigma = torch.ones_like(target)
     for _ in range(64):
         # an excess of 0 is weight 1 whatever sigma is (0 / 0 never forms)
         w = torch.where(excess > 0, torch.exp(-excess / sigma[:, None]), torch.ones_like(excess))
@@ -40,6 +40,19 @@ def _smooth_knn(dist, valid):
         lo = torch.where(above, lo, sigma)
         sigma = torch.where(above | torch.isfinite(hi), 0.5 * (lo + torch.where(torch.isfinite(hi), hi, lo)),
                             2.0 * sigma)
+    return sigma
+
+
+def _smooth_knn(dist, valid):
+    """umap-learn's smooth_knn_dist with local_connectivity 1, for all rows at once: ``dist`` fp64 [N,k] with the
+    invalid positions anything, ``valid`` bool [N,k] -> (sigma, rho) fp64 [N]."""
+    inf = float("inf")
+    n_valid = valid.sum(1)
+    positive = valid & (dist > 0)
+    rho = torch.where(positive, dist, torch.full_like(dist, inf)).amin(1)
+    rho = torch.where(torch.isfinite(rho), rho, torch.zeros_like(rho))
+    excess = torch.where(valid, (dist - rho[:, None]).clamp_min(0.0), torch.zeros_like(dist))
+    sigma = _bisect_sigma(excess, valid, n_valid)
     total = int(n_valid.sum())
     d_valid = torch.where(valid, dist, torch.zeros_like(dist))
     mean_all = float(d_valid.sum() / total) if total else 0.0
@@ -129,6 +142,39 @@ def to_csr(g):
     ``obsp["connectivities"]``."""
     return (g["indptr"].detach().cpu().numpy().astype(np.int64), g["indices"].detach().cpu().numpy().astype(np.int32),
             g["weights"].detach().cpu().numpy().astype(np.float32))
+
+
+def query_weights(indices, distances):
+    """The memberships of new rows in their neighbours among the reference rows, as umap-learn's ``transform``
+    forms them: ``indices`` [Q,k] integers and ``distances`` [Q,k] floats as ``knn(points, queries=...)`` returns
+    them (padding -1 / +inf).  An entry is valid when its index is >= 0 and its distance finite and >= 0.
+
+    Per row with at least one valid entry, smooth_knn_dist with local connectivity 0, so rho_i = 0 throughout:
+    sigma_i from the 64 bisection steps of ``fuzzy_graph`` on sum_j exp(-d_ij / sigma) = log2(k_i), k_i the row's
+    valid entries, floored at 1e-3 x the mean of all valid distances; w_ij = exp(-d_ij / sigma_i) in fp64, rounded
+    to float32; an invalid entry has weight 0.  Nothing is symmetrised: the graph is bipartite and stays in the
+    dense [Q,k] form that ``graph_transform`` takes.
+
+    Returns {'weights': float32 [Q,k], 'sigma': fp64 [Q]} on the device of ``indices``."""
+    idx = torch.as_tensor(indices)
+    dist = torch.as_tensor(distances)
+    if idx.dim() != 2 or idx.shape != dist.shape:
+        raise ValueError(f"query_weights: indices and distances must be 2-D and of one shape, got "
+                         f"{tuple(idx.shape)} and {tuple(dist.shape)}")
+    if idx.dtype.is_floating_point or idx.dtype == torch.bool:
+        raise ValueError(f"query_weights: indices must hold integers, got {idx.dtype}")
+    if not dist.dtype.is_floating_point:
+        raise ValueError(f"query_weights: distances must be floating point, got {dist.dtype}")
+    dist = dist.to(device=idx.device, dtype=torch.float64)
+    valid = (idx >= 0) & torch.isfinite(dist) & (dist >= 0)
+    n_valid = valid.sum(1)
+    d = torch.where(valid, dist, torch.zeros_like(dist))
+    sigma = _bisect_sigma(d, valid, n_valid)
+    total = int(n_valid.sum())
+    mean_all = float(d.sum() / total) if total else 0.0
+    sigma = sigma.clamp_min(1e-3 * mean_all)
+    w = torch.where(d > 0, torch.exp(-d / sigma[:, None]), torch.ones_like(d))
+    return {"weights": torch.where(valid, w, torch.zeros_like(w)).to(torch.float32), "sigma": sigma}
 
 
 # ---- the curve ---------------------------------------------------------------------------------------------
@@ -307,6 +353,96 @@ def layout_reference(indptr, indices, weights, y, epoch0, n_epochs, total_epochs
         new = y.copy()
         with np.errstate(invalid="ignore", over="ignore"):
             new[moves] = y[moves] + alpha * F[moves] / np.maximum(1.0, W[moves])[:, None]
+        y = new
+    if details:
+        return y, (A.max(1) if A.ndim == 2 else A), W
+    return y
+
+
+# ---- new rows on a fitted layout: the fp64 reference -------------------------------------------------------------
+_TRANSFORM_TAG = 0x554D5854       # the fourth counter word of a transform draw
+
+
+def default_transform_epochs(n_query):
+    """umap-learn's rule for ``transform``: 100 epochs up to 10 000 query rows, 30 above."""
+    return 100 if int(n_query) <= 10000 else 30
+
+
+def transform_negatives(row0, n_query, n_ref, epoch, n_negatives, seed):
+    """The negative samples r(g, e, m) of the query rows g = row0 .. row0 + n_query - 1 in epoch ``epoch``, rows of
+    the reference: int64 [n_query, n_negatives].  With ``n_ref`` = 0 nothing is drawn: every entry is -1."""
+    q, M, n_ref, seed = int(n_query), int(n_negatives), int(n_ref), int(seed) & (2 ** 64 - 1)
+    if n_ref == 0:
+        return np.full((q, M), -1, dtype=np.int64)
+    blocks = (M + 3) // 4
+    ctr = np.zeros((q, blocks, 4), dtype=np.uint64)
+    ctr[..., 0] = ((np.arange(q, dtype=np.uint64) + np.uint64(int(row0))) & np.uint64(0xFFFFFFFF))[:, None]
+    ctr[..., 1] = np.arange(blocks, dtype=np.uint64)[None, :]
+    ctr[..., 2] = int(epoch) & 0xFFFFFFFF
+    ctr[..., 3] = _TRANSFORM_TAG
+    words = philox4x32_10(ctr, (seed & 0xFFFFFFFF, seed >> 32)).reshape(q, 4 * blocks)[:, :M]
+    return ((words.astype(np.uint64) * np.uint64(n_ref)) >> np.uint64(32)).astype(np.int64)
+
+
+def transform_reference(idx, w, y_ref, y_in, row0, epoch0, n_epochs, total_epochs, lr, a, b, repulsion=1.0,
+                        negative_rate=5.0, n_negatives=8, seed=0, details=False):
+    """The epochs ``epoch0 .. epoch0 + n_epochs - 1`` of include/spmf_hip.h spmf_graph_transform in fp64 numpy, from
+    its definition: ``idx`` / ``w`` [Q,k] (any integers, NaN / inf weights allowed), ``y_ref`` [n_ref,2] (NaN / inf
+    allowed), ``y_in`` [Q,2] or None for the weighted-mean start; the same skip rules, the same negatives, alpha_e
+    rounded to fp32 as the kernel forms it -> fp64 [Q,2].
+
+    ``details``: -> (y, A, W) with A_i the sum of the absolute values of the row's clipped contributions to F_i
+    (the larger of the two components) of the LAST epoch run and W_i: the scale of a per-row error bar."""
+    idx = np.asarray(idx, dtype=np.int64)
+    Q, k = idx.shape
+    w = np.asarray(w, dtype=np.float64).reshape(Q, k)
+    y_ref = np.asarray(y_ref, dtype=np.float64).reshape(-1, 2)
+    n_ref = y_ref.shape[0]
+    M, a, b = int(n_negatives), float(a), float(b)
+    ref_ok = np.isfinite(y_ref).all(1)
+    valid = (idx >= 0) & (idx < n_ref) & np.isfinite(w) & (w > 0)
+    j = np.where(valid, idx, 0)
+    if n_ref:
+        valid &= ref_ok[j]
+    wv = np.where(valid, w, 0.0)
+    yj = np.where(valid[..., None], y_ref[j] if n_ref else 0.0, 0.0)          # [Q,k,2]
+    W = wv.sum(1)
+    has = W > 0
+    if y_in is None:
+        y = np.full((Q, 2), np.nan)
+        y[has] = (wv[..., None] * yj).sum(1)[has] / W[has, None]
+    else:
+        y = np.array(y_in, dtype=np.float64).reshape(Q, 2)
+    A = np.zeros(Q)
+
+    def clipped(coef, delta):
+        with np.errstate(invalid="ignore", over="ignore"):
+            t = coef[..., None] * delta
+        return np.clip(np.where(np.isnan(t), 0.0, t), -4.0, 4.0)
+    for e in range(int(epoch0), int(epoch0) + int(n_epochs)):
+        alpha = float(np.float32(float(lr) * (1.0 - e / float(total_epochs))))
+        moves = has & np.isfinite(y).all(1)
+        ys = np.where(moves[:, None], y, 0.0)
+        delta = ys[:, None, :] - yj
+        d2 = (delta ** 2).sum(-1)
+        live = valid & moves[:, None] & (d2 > 0)
+        s = np.where(live, d2, 1.0)
+        ca = np.where(live, -2.0 * a * b * s ** (b - 1.0) / (1.0 + a * s ** b), 0.0)
+        term = wv[..., None] * clipped(ca, np.where(live[..., None], delta, 0.0))
+        F = term.sum(1)
+        A = np.abs(term).sum(1)
+        if n_ref:
+            neg = transform_negatives(row0, Q, n_ref, e, M, seed)
+            delta = ys[:, None, :] - np.where(ref_ok[neg][..., None], y_ref[neg], 0.0)
+            d2 = (delta ** 2).sum(-1)
+            live = ref_ok[neg] & moves[:, None] & (d2 > 0)
+            s = np.where(live, d2, 1.0)
+            cr = np.where(live, 2.0 * float(repulsion) * b / ((0.001 + s) * (1.0 + a * s ** b)), 0.0)
+            term = (float(negative_rate) * W / M)[:, None, None] * clipped(cr, np.where(live[..., None], delta, 0.0))
+            F = F + term.sum(1)
+            A = A + np.abs(term).sum(1)
+        new = y.copy()
+        new[moves] = y[moves] + alpha * F[moves] / np.maximum(1.0, W[moves])[:, None]
         y = new
     if details:
         return y, (A.max(1) if A.ndim == 2 else A), W

@@ -88,6 +88,57 @@ def brute_force(q, r, k, metric="euclidean", exclude_self=False, max_elements=1 
     return idx, dist
 
 
+def vote(indices, weights, labels, n_classes=None, max_elements=1 << 24):
+    """Label transfer over a neighbour result (scanpy's ``ingest``): per query row the class with the largest fp64
+    sum of ``weights`` [Q,k] among its neighbours ``indices`` [Q,k] (rows of the reference, padding -1), whose
+    classes are ``labels`` [n_ref] integers, and that class's share of the row's summed voting weight.
+
+    A neighbour votes when its index lies in [0, n_ref), its weight is finite and > 0 and its label lies in
+    [0, ``n_classes``) (default: the largest label + 1); a label -1 or one outside the range does not vote.  Equal
+    sums go to the smaller class; a row without a voting neighbour gets -1 / NaN.
+
+    Plain torch on the device of ``indices``: an equality mask per class and a sum over the k axis on chunks of at
+    most ``max_elements`` mask entries -- no scatter-add, so two runs give the same bits.
+    -> (labels int64 [Q], share fp64 [Q])."""
+    idx = torch.as_tensor(indices)
+    dev = idx.device
+    w = torch.as_tensor(weights).to(dev)
+    lab = torch.as_tensor(labels).to(dev)
+    if idx.dim() != 2 or idx.shape != w.shape:
+        raise ValueError(f"vote: indices and weights must be 2-D and of one shape, got {tuple(idx.shape)} and "
+                         f"{tuple(w.shape)}")
+    if idx.dtype.is_floating_point or idx.dtype == torch.bool:
+        raise ValueError(f"vote: indices must hold integers, got {idx.dtype}")
+    if lab.dim() != 1 or lab.dtype.is_floating_point or lab.dtype == torch.bool:
+        raise ValueError(f"vote: labels must be a 1-D tensor of integers, got {lab.dtype} {tuple(lab.shape)}")
+    if n_classes is not None and (isinstance(n_classes, bool) or not isinstance(n_classes, (int, np.integer))
+                                  or int(n_classes) < 0):
+        raise ValueError(f"vote: n_classes must be an integer >= 0, got {n_classes!r}")
+    idx, lab, w = idx.to(torch.int64), lab.to(torch.int64), w.to(torch.float64)
+    n_ref = int(lab.numel())
+    G = int(n_classes) if n_classes is not None else (max(int(lab.max()) + 1, 0) if n_ref else 0)
+    Q, k = int(idx.shape[0]), int(idx.shape[1])
+    out = torch.full((Q,), -1, dtype=torch.int64, device=dev)
+    share = torch.full((Q,), float("nan"), dtype=torch.float64, device=dev)
+    if Q == 0 or k == 0 or G == 0 or n_ref == 0:
+        return out, share
+    classes = torch.arange(G, device=dev, dtype=torch.int64)
+    step = max(1, int(max_elements) // (k * G))
+    for i0 in range(0, Q, step):
+        j, wi = idx[i0:i0 + step], w[i0:i0 + step]
+        ok = (j >= 0) & (j < n_ref) & torch.isfinite(wi) & (wi > 0)
+        cls = torch.where(ok, lab[j.clamp(0, n_ref - 1)], torch.full_like(j, -1))
+        ok = ok & (cls >= 0) & (cls < G)
+        wi = torch.where(ok, wi, torch.zeros_like(wi))
+        sums = (wi[:, :, None] * (cls[:, :, None] == classes[None, None, :])).sum(1)      # [rows, G]
+        top = sums.amax(1)
+        first = torch.where(sums == top[:, None], classes[None, :], torch.full_like(classes, G)[None, :]).amin(1)
+        voted = ok.any(1)
+        out[i0:i0 + step] = torch.where(voted, first, torch.full_like(first, -1))
+        share[i0:i0 + step] = torch.where(voted, top / wi.sum(1), torch.full_like(top, float("nan")))
+    return out, share
+
+
 def recall(indices, truth):
     """The share of the true neighbours found: over all rows, the entries of ``truth`` (padding -1 left
     out) that appear in the same row of ``indices``.  1.0 when ``truth`` holds no neighbour."""

@@ -1,7 +1,7 @@
 """The streaming posterior queries of the model classes: ``StreamingQueries`` is the mixin that gives
 PoissonFactorization (and through it the Bernoulli and mixed classes) waic_streaming, top_k, score_cells,
 rank_cells, predict, top_rows, group_means, set_scores, embed, knn, neighbors, kmeans, cluster, silhouette,
-fuzzy_graph, graph_layout and umap.
+fuzzy_graph, graph_layout, umap, graph_transform and umap_transform.
 
 Every draw-stage query is the same three pieces around its own kernel (include/spmf_hip.h, csrc/api_stream.hip "the
 draw stage"): ``_Draws``, the checked draws and the one place a library call is spelled; a driver that walks
@@ -865,9 +865,10 @@ class StreamingQueries:
 
     @staticmethod
     def _layout_args(name, n_epochs, min_dist, spread, a, b, n_negatives, negative_rate, repulsion, learning_rate,
-                     seed, init):
-        """The layout arguments of ``graph_layout`` / ``umap`` that need no graph, checked before any library
-        call -> namespace(n_epochs (or None), a, b, M, rate, gamma, lr, seed)."""
+                     seed, init, starts=None):
+        """The layout arguments of ``graph_layout`` / ``umap`` / ``graph_transform`` that need no graph, checked
+        before any library call -> namespace(n_epochs (or None), a, b, M, rate, gamma, lr, seed).  ``starts``: the
+        values of ``init`` beside a tensor (default: ``spmf_amd.graph.INITS``)."""
         from . import graph as _graph
 
         def integer(what, v, lo, hi):
@@ -895,8 +896,9 @@ class StreamingQueries:
                 raise ValueError(f"{name}: {e}") from None
         else:
             a, b = weight("a", a, positive=True), weight("b", b, positive=True)
-        if not isinstance(init, torch.Tensor) and not (isinstance(init, str) and init in _graph.INITS):
-            raise ValueError(f"{name}: init must be one of {_graph.INITS} or a float32 [N, 2] tensor, got {init!r}")
+        starts = _graph.INITS if starts is None else starts
+        if not isinstance(init, torch.Tensor) and not (isinstance(init, (str, type(None))) and init in starts):
+            raise ValueError(f"{name}: init must be one of {starts} or a float32 [N, 2] tensor, got {init!r}")
         return SimpleNamespace(n_epochs=n_epochs, a=a, b=b, M=M, rate=rate, gamma=gamma, lr=lr, seed=seed)
 
     def graph_layout(self, graph, init="pca", points=None, n_epochs=None, min_dist=0.1, spread=1.0, a=None, b=None,
@@ -1013,6 +1015,131 @@ class StreamingQueries:
                                 b=b, n_negatives=n_negatives, negative_rate=negative_rate, repulsion=repulsion,
                                 learning_rate=learning_rate, seed=seed)
         res.update(graph=g, latent=emb, indices=nn["indices"], distances=nn["distances"])
+        return res
+
+    def graph_transform(self, indices, distances, reference_layout, weights=None, init=None, n_epochs=None,
+                        min_dist=0.1, spread=1.0, a=None, b=None, n_negatives=8, negative_rate=5.0, repulsion=1.0,
+                        learning_rate=0.25, seed=0, row_offset=0):
+        """New rows on a fitted layout, the reference rows held where they are (umap-learn's ``transform``): all
+        epochs in one kernel launch (include/spmf_hip.h spmf_graph_transform has the definition,
+        csrc/graph_transform.hip).  A new row starts at the weighted mean of its neighbours' positions and is
+        then pulled towards them and pushed away from ``n_negatives`` reference rows drawn per epoch from
+        (``seed``, the row's number, epoch).  A row's position is a function of that row alone: rows may be mapped
+        in chunks of any size with the same bits, ``row_offset`` being the number of a chunk's first row.
+
+        ``indices`` int [Q, k] and ``distances`` float [Q, k]: what ``knn(reference_points, queries=...)`` returned
+        (k <= 64, padding -1 / +inf); ``reference_layout``: float32 [n_ref, 2], the 'embedding' of ``graph_layout``
+        / ``umap``; all on the model's device.  ``weights``: float32 [Q, k] memberships, None for
+        ``spmf_amd.graph.query_weights(indices, distances)``.  ``init``: None for the weighted mean, or a float32
+        [Q, 2] tensor.  ``n_epochs``: None is umap-learn's rule for transform, 100 up to 10 000 rows, else 30.
+        (``a``, ``b``) should be the reference layout's; None fits them to (``min_dist``, ``spread``).  The other
+        arguments as in ``graph_layout``; the default ``learning_rate`` is a quarter of its, as in umap-learn.
+
+        Returns {'embedding': float32 [Q, 2] on the device (NaN: a row without a valid neighbour), 'weights',
+        'sigma' (None with given ``weights``), 'a', 'b', 'n_epochs'}.  Bit-reproducible."""
+        from . import graph as _graph
+        name = "graph_transform"
+        la = self._layout_args(name, n_epochs, min_dist, spread, a, b, n_negatives, negative_rate, repulsion,
+                               learning_rate, seed, init, starts=(None,))
+        if isinstance(row_offset, bool) or not isinstance(row_offset, (int, np.integer)) or int(row_offset) < 0:
+            raise ValueError(f"{name}: row_offset must be an integer >= 0, got {row_offset!r}")
+        for what, t in (("indices", indices), ("distances", distances), ("reference_layout", reference_layout)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 2:
+                raise ValueError(f"{name}: {what} must be a 2-D torch tensor")
+        if indices.dtype.is_floating_point or indices.dtype == torch.bool:
+            raise ValueError(f"{name}: indices must hold integers, got {indices.dtype}")
+        if not distances.dtype.is_floating_point or distances.shape != indices.shape:
+            raise ValueError(f"{name}: distances must be floating point of the shape of indices "
+                             f"{tuple(indices.shape)}, got {distances.dtype} {tuple(distances.shape)}")
+        Q, k = int(indices.shape[0]), int(indices.shape[1])
+        if not 1 <= k <= 64:
+            raise ValueError(f"{name} needs 1 <= k <= 64 neighbours per row, got {k}")
+        if reference_layout.dtype != torch.float32 or int(reference_layout.shape[1]) != 2:
+            raise ValueError(f"{name}: reference_layout must be float32 of shape [n_ref, 2], got "
+                             f"{reference_layout.dtype} {tuple(reference_layout.shape)}")
+        n_ref = int(reference_layout.shape[0])
+        if n_ref > 2 ** 31 - 1:
+            raise ValueError(f"{name}: {n_ref} reference rows are beyond the int32 index of a neighbour")
+        if int(row_offset) + Q > 2 ** 32:
+            raise ValueError(f"{name}: row_offset + the {Q} rows must stay within 2^32, got row_offset={row_offset}")
+        if weights is not None:
+            if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 \
+                    or weights.shape != indices.shape:
+                raise ValueError(f"{name}: weights must be a float32 tensor of shape {tuple(indices.shape)}")
+        if isinstance(init, torch.Tensor) and (tuple(init.shape) != (Q, 2) or init.dtype != torch.float32):
+            raise ValueError(f"{name}: an init tensor must be float32 of shape {(Q, 2)}, got {init.dtype} "
+                             f"{tuple(init.shape)}")
+        dev = torch.device(self.device)
+        for what, t in (("indices", indices), ("distances", distances), ("reference_layout", reference_layout),
+                        ("weights", weights), ("init", init)):
+            if t is not None and (t.device.type != "cuda" or (dev.index is not None and t.device != dev)):
+                raise ValueError(f"{name}: {what} must be on the model's device {self.device}, got {t.device}")
+        total = _graph.default_transform_epochs(Q) if la.n_epochs is None else la.n_epochs
+        sigma = None
+        if weights is None:
+            qw = _graph.query_weights(indices, distances)
+            weights, sigma = qw["weights"], qw["sigma"]
+        # (an index beyond int32 is no row of the reference: it stays outside [0, n_ref) through the cast)
+        idx = indices.clamp(-1, n_ref).to(torch.int32).contiguous()
+        w, ref = weights.contiguous(), reference_layout.contiguous()
+        start = init.contiguous() if init is not None else None
+        lib, h = _lib.load(), self._handle()
+        out = torch.empty(Q, 2, dtype=torch.float32, device=idx.device)
+        _lib.check(h, lib.spmf_graph_transform(
+            h, Q, k, idx.data_ptr(), w.data_ptr(), ref.data_ptr(), n_ref,
+            start.data_ptr() if start is not None else None, out.data_ptr(), int(row_offset), 0, total, total,
+            la.lr, la.a, la.b, la.gamma, la.rate, la.M, la.seed,
+            torch.cuda.current_stream(idx.device).cuda_stream), "spmf_graph_transform")
+        return {"embedding": out, "weights": weights, "sigma": sigma, "a": la.a, "b": la.b, "n_epochs": total}
+
+    def umap_transform(self, data, reference, k=15, metric="euclidean", nsamples=32, draws=None, max_rows=None,
+                       labels=None, n_classes=None, n_epochs=None, learning_rate=0.25, n_negatives=8,
+                       negative_rate=5.0, repulsion=1.0, seed=0):
+        """The rows of ``data`` on the map of ``reference`` (what ``umap`` returned: its 'latent', 'embedding', 'a'
+        and 'b' are used): ``embed`` on ``data``, ``knn`` of the encodings among the reference's, then
+        ``graph_transform`` with the reference's curve -- umap-learn's ``transform``, scanpy's ``ingest``.  The
+        reference map does not move.  ``data``, ``nsamples`` / ``draws`` and ``max_rows`` as in ``embed``; ``k``
+        and ``metric`` as in ``knn``; the layout arguments as in ``graph_transform``.  ``labels``: an integer per
+        reference row (-1: none), e.g. the labels of ``cluster``; every new row then gets the class with the
+        largest summed membership among its neighbours (``spmf_amd.neighbors.vote``; ``n_classes`` as there).
+
+        Returns what ``graph_transform`` returns, bit for bit the calls made by hand, and 'latent' (the encoding,
+        float32 [Q, latent_dim]), the 'indices' / 'distances' of ``knn`` and, with ``labels``, 'labels' int64 [Q]
+        (-1: no voting neighbour) and 'label_share' fp64 [Q].  Bit-reproducible for given draws."""
+        from . import neighbors as _neighbors
+        name = "umap_transform"
+        self._knn_args(name, k, metric)
+        if not isinstance(reference, dict) or any(n not in reference for n in ("latent", "embedding", "a", "b")):
+            raise ValueError(f"{name}: reference must be what umap returned: a dict with 'latent', 'embedding', "
+                             f"'a' and 'b'")
+        self._layout_args(name, n_epochs, 0.1, 1.0, reference["a"], reference["b"], n_negatives, negative_rate,
+                          repulsion, learning_rate, seed, None, starts=(None,))
+        lat, ref = reference["latent"], reference["embedding"]
+        if not isinstance(lat, torch.Tensor) or lat.dim() != 2 or lat.dtype != torch.float32 \
+                or int(lat.shape[1]) != self.latent_dim:
+            raise ValueError(f"{name}: reference['latent'] must be a float32 [n_ref, {self.latent_dim}] tensor")
+        if not isinstance(ref, torch.Tensor) or ref.dtype != torch.float32 \
+                or tuple(ref.shape) != (int(lat.shape[0]), 2):
+            raise ValueError(f"{name}: reference['embedding'] must be a float32 {(int(lat.shape[0]), 2)} tensor")
+        if not 1 <= self.latent_dim <= 256:
+            raise ValueError(f"{name}: latent_dim {self.latent_dim} is beyond the 256 columns of knn")
+        if labels is not None:
+            labels = _vector(name, "labels", labels)
+            if int(labels.numel()) != int(lat.shape[0]):
+                raise ValueError(f"{name}: labels must have one entry per reference row, got {int(labels.numel())} "
+                                 f"for {int(lat.shape[0])} rows")
+            if n_classes is not None and (isinstance(n_classes, bool) or not isinstance(n_classes, (int, np.integer))
+                                          or int(n_classes) < 0):
+                raise ValueError(f"{name}: n_classes must be an integer >= 0, got {n_classes!r}")
+        emb = self.embed(data, nsamples=nsamples, draws=draws, max_rows=max_rows)["mean"]
+        nn = self.knn(lat, k=k, queries=emb, metric=metric)
+        res = self.graph_transform(nn["indices"], nn["distances"], ref, n_epochs=n_epochs, a=reference["a"],
+                                   b=reference["b"], n_negatives=n_negatives, negative_rate=negative_rate,
+                                   repulsion=repulsion, learning_rate=learning_rate, seed=seed)
+        res.update(latent=emb, indices=nn["indices"], distances=nn["distances"])
+        if labels is not None:
+            res["labels"], res["label_share"] = _neighbors.vote(nn["indices"], res["weights"],
+                                                                labels.to(emb.device), n_classes)
         return res
 
     def cluster(self, data, n_clusters, nsamples=32, draws=None, max_rows=None, init="k-means++", max_iter=100,
