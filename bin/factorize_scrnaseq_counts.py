@@ -43,6 +43,13 @@ With --umap (the 2-D map on which cells, clusters and factor scores are looked a
 from --umap-neighbors neighbours per cell, --umap-min-dist and --umap-epochs (default: 500 up to 10 000 cells,
 200 above), over the mean encoding of --cluster-draws posterior draws seeded by --cluster-seed (the encoding
 --clusters labels; the seed also draws the layout's negatives).  Without the flag nothing changes.
+--umap-init spectral starts the layout from the two leading non-trivial eigenvectors of the graph (umap-learn's
+default start) in place of the encoding's principal axes (--umap-init pca, the default).
+With --spectral N (the spectral embedding / diffusion-map coordinates of the cells, 1 <= N <= 12):
+  <stem>_spectral_<P>.npy        [cells, N] float32: the eigenvectors 1 .. N of D^-1/2 A D^-1/2 of the same fuzzy
+                                 neighbour graph (0: a cell without a neighbour)
+  <stem>_spectral_values_<P>.npy [N + 1] float64: the eigenvalues 0 .. N, descending, the first about 1
+over the same encoding, --umap-neighbors and seed.  Without the flag nothing changes.
 With --map-counts FILE beside --umap (new cells over the same genes, e.g. a second sample; .npy dense or .npz CSR):
   <stem>_UMAP_map_<P>.npy        [new cells, 2] float32: the new cells on the map above, which does not move (NaN:
                                  a cell without a finite encoding)
@@ -97,6 +104,10 @@ def build_parser():
     p.add_argument("--umap-neighbors", type=int, default=15, help="neighbours per cell of the layout's graph")
     p.add_argument("--umap-min-dist", type=float, default=0.1, help="min_dist of the layout's curve")
     p.add_argument("--umap-epochs", type=int, default=None, help="epochs of the layout (default: by size)")
+    p.add_argument("--umap-init", choices=("pca", "spectral"), default="pca", help="the layout's start: the "
+                   "encoding's principal axes, or the graph's leading eigenvectors")
+    p.add_argument("--spectral", type=int, default=None, help="N: writes the N leading non-trivial eigenvectors "
+                                                              "of the cells' neighbour graph and their eigenvalues")
     p.add_argument("--map-counts", default=None, help="FILE: new cells over the same genes; with --umap they are "
                                                       "placed on the map (and labelled with --clusters / --labels)")
     p.add_argument("--gene-sets", default=None, help="FILE.gmt: gene sets (name, description, members per line); "
@@ -130,6 +141,8 @@ def main(argv=None):
         parser.error("--silhouette needs --clusters or --labels")
     if args.map_counts is not None and not args.umap:
         parser.error("--map-counts needs --umap")
+    if args.spectral is not None and not 1 <= args.spectral <= 12:
+        parser.error("--spectral needs 1 <= N <= 12")
     if args.map_counts is not None and not os.path.exists(args.map_counts):
         sys.exit("File doesn't exist")
     if not os.path.exists(args.counts):
@@ -214,6 +227,8 @@ def main(argv=None):
             map_cells(factor, X_new, reference, known,
                       args.clusters if clusters is not None else None, f"{stem}_UMAP_map_{P}.npy",
                       f"{stem}_label_map_{P}.npy", args)
+    if args.spectral is not None:
+        spectral_cells(factor, X, f"{stem}_spectral_{P}.npy", f"{stem}_spectral_values_{P}.npy", args)
     if args.gene_sets is not None:
         gene_set_scores(factor, X, gene_names, f"{stem}_setscore_{P}.npy", f"{stem}_setscore_sd_{P}.npy", args)
     if args.gene_waic:
@@ -279,9 +294,12 @@ def umap_cells(factor, X, path, args):
     """The 2-D map of the cells (``umap`` on the encoding that ``cluster_cells`` works on: the same seed, the same
     draws): the coordinates as a file."""
     import torch
-    torch.manual_seed(args.cluster_seed)                  # the posterior draws of the encoding
-    res = factor.umap({factor.count_key: X}, k=args.umap_neighbors, nsamples=args.cluster_draws,
-                      n_epochs=args.umap_epochs, min_dist=args.umap_min_dist, seed=args.cluster_seed)
+    if args.umap_init == "spectral":
+        res = _umap_from_spectral(factor, X, args)
+    else:
+        torch.manual_seed(args.cluster_seed)              # the posterior draws of the encoding
+        res = factor.umap({factor.count_key: X}, k=args.umap_neighbors, nsamples=args.cluster_draws,
+                          n_epochs=args.umap_epochs, min_dist=args.umap_min_dist, seed=args.cluster_seed)
     y = res["embedding"].cpu().numpy()
     np.save(path, y)
     ok = np.isfinite(y).all(1)
@@ -290,6 +308,44 @@ def umap_cells(factor, X, path, args):
           f"epochs, a = {res['a']:.4f}, b = {res['b']:.4f}, extent {span:.3g}"
           + (f", {int((~ok).sum())} cells without a position" if not ok.all() else ""))
     return res
+
+
+def _cell_graph(factor, X, args):
+    """The encoding ``cluster_cells`` works on (the same seed, the same draws), its neighbours and their fuzzy graph:
+    the first three of ``umap``'s four calls -> (latent, knn result, graph)."""
+    import torch
+    torch.manual_seed(args.cluster_seed)                  # the posterior draws of the encoding
+    emb = factor.embed({factor.count_key: X}, nsamples=args.cluster_draws)["mean"]
+    nn = factor.knn(emb, k=args.umap_neighbors)
+    return emb, nn, factor.fuzzy_graph(nn["indices"], nn["distances"])
+
+
+def _umap_from_spectral(factor, X, args):
+    """``umap``'s four calls by hand with the spectral start between the third and the fourth -> what ``umap``
+    returns (the dict ``map_cells`` needs)."""
+    from spmf_amd import spectral
+    emb, nn, g = _cell_graph(factor, X, args)
+    eig = factor.spectral(g, n_components=2, seed=args.cluster_seed)
+    start = spectral.layout_init(eig["embedding"], seed=args.cluster_seed)
+    res = factor.graph_layout(g, init=start, n_epochs=args.umap_epochs, min_dist=args.umap_min_dist,
+                              seed=args.cluster_seed)
+    res.update(graph=g, latent=emb, indices=nn["indices"], distances=nn["distances"])
+    print(f"umap: spectral start after {eig['n_iter']} iterations and {eig['n_products']} products"
+          + ("" if eig["converged"] else " (not converged)"))
+    return res
+
+
+def spectral_cells(factor, X, path, values_path, args):
+    """The spectral embedding of the cells (``spectral`` on the fuzzy graph ``umap_cells`` lays out): the
+    eigenvectors and the eigenvalues as files."""
+    _, _, g = _cell_graph(factor, X, args)
+    res = factor.spectral(g, n_components=args.spectral, seed=args.cluster_seed)
+    np.save(path, res["embedding"].cpu().numpy())
+    np.save(values_path, np.asarray(res["values"], dtype=np.float64))
+    print(f"spectral: {args.spectral} eigenvectors of {int(g['indices'].numel())} graph entries after "
+          f"{res['n_iter']} iterations and {res['n_products']} products, largest residual "
+          f"{float(res['residuals'].max()):.2e}" + ("" if res["converged"] else " (not converged)")
+          + f", {res['n_unit']} eigenvalues at 1")
 
 
 def map_cells(factor, X_new, reference, labels, n_classes, path, label_path, args):

@@ -1040,6 +1040,57 @@ int spmf_graph_transform(spmf_ctx* ctx, int64_t n_query, int k, const int32_t* i
                          double b, double repulsion, double negative_rate, int n_negatives,
                          uint64_t seed, void* stream);
 
+/* ---- multiplying by the graph (added within ABI 6: five new entry points, no struct changed) ----
+ * What a deterministic eigensolver of S = D^-1/2 A D^-1/2 needs of the graph spmf_graph_layout takes
+ * (csrc/spectral.hip; spmf_amd/spectral.py is the solver): the scaling, the product with a tall block,
+ * and two small fp64 reductions over tall blocks.  A block is fp32 [n_rows][SPMF_BLOCK_COLS], row-major, on
+ * the device, 16-byte aligned: one row is one 64-byte segment; a caller with fewer columns leaves the rest zero.  The graph
+ * is read under spmf_graph_layout's rules: an indptr value is clamped to [0, nnz], a falling indptr is an
+ * empty row, an entry counts only if its index lies in [0, n_rows) and its weight is finite and > 0;
+ * n_rows <= 2^31 - 64.  No argument values make a kernel read outside its arrays.  None of the calls has
+ * an atomic: two calls return the same bits.  The context serves the error message and the device only.
+ *
+ * spmf_graph_scale: scale[i] = 1 / sqrt(d_i) with d_i the fp64 sum of row i's valid weights, rounded
+ *   once to fp32; 0 for a row without a valid entry.  Lane l of the row's 16 takes the entries l, l + 16,
+ *   .. in ascending order, then a fixed tree: the order is a function of the row's list length alone.
+ * spmf_graph_spmm: Y_i = c_s s_i sum_j w_ij s_j X_j + X_i o c_x + c_z Z_i over the valid entries of row
+ *   i in list order, s = 1 with scale == NULL.  c_x: HOST, SPMF_BLOCK_COLS doubles, read before the return
+ *   (one per column: with c_s = 1, c_x = -lambda the call forms the residual block S V - V Lambda).  c_s,
+ *   c_x and c_z are rounded to fp32 once on the host; everything else is fp32: t = w_ij s_j, acc =
+ *   fmaf(t, X_jl, acc) from 0, Y_il = fmaf(c_z, Z_il, fmaf(c_x[l], X_il, (c_s s_i) acc)).  A lane owns a
+ *   column, so an entry of Y is a function of its row's list alone.  z may be NULL when c_z = 0.  y may
+ *   be z (a row reads Z_i and writes Y_i itself); y == x is refused: other rows gather X.  Values of X
+ *   and Z are taken as given: a NaN reaches the rows that list it and no further.
+ * spmf_block_gram: g[a * 16 + b] = sum_r x_ra y_rb in fp64 (device, 256 doubles).  Rows are cut into chunks
+ *   of SPMF_GRAM_CHUNK_ROWS; a chunk's sum runs in ascending r, then the chunks' sums are added in ascending
+ *   order: the bits are a function of (x, y, n_rows).  x may be y.  scratch: 256-byte aligned, at least
+ *   spmf_block_gram_scratch_bytes(ctx, n_rows) bytes (a multiple of 256, non-decreasing in n_rows; 0 for
+ *   bad arguments).
+ * spmf_block_rotate: Y = X R, r HOST, 256 doubles row-major, read before the return: Y_ib = the fp64 sum
+ *   of X_ik r[k * 16 + b] in ascending k from 0, rounded once to fp32.  y may be x (a row is read whole
+ *   before it is written).
+ *
+ * SPMF_E_ARG for n_rows outside 0..2^31 - 64, nnz < 0, a NULL pointer where one is needed (indptr, the
+ * blocks and outputs with n_rows > 0; indices / weights with nnz > 0; c_x, r, g and the scratch always; z
+ * with c_z != 0), a non-finite coefficient (or one beyond fp32), y == x in spmf_graph_spmm ("aliases"), a
+ * misaligned scratch; then SPMF_E_WORKSPACE for a short one, naming the need; every error returns before
+ * any launch or copy with the entry's name ("graph_scale: ", "graph_spmm: ", "block_gram: ",
+ * "block_rotate: ") in front of the message.  n_rows == 0 returns SPMF_OK behind the checks (spmf_block_gram
+ * zero-fills g on the stream).  The context's workspace is not touched.  Stream-ordered, synchronises
+ * nowhere. */
+#define SPMF_BLOCK_COLS 16
+#define SPMF_GRAM_CHUNK_ROWS 512
+int spmf_graph_scale(spmf_ctx* ctx, int64_t n_rows, int64_t nnz, const int64_t* indptr,
+                     const int32_t* indices, const float* weights, float* scale, void* stream);
+int spmf_graph_spmm(spmf_ctx* ctx, int64_t n_rows, int64_t nnz, const int64_t* indptr,
+                    const int32_t* indices, const float* weights, const float* scale, const float* x,
+                    const float* z, float* y, double c_s, const double* c_x, double c_z, void* stream);
+size_t spmf_block_gram_scratch_bytes(const spmf_ctx* ctx, int64_t n_rows);
+int spmf_block_gram(spmf_ctx* ctx, int64_t n_rows, const float* x, const float* y, double* g,
+                    void* scratch, size_t scratch_bytes, void* stream);
+int spmf_block_rotate(spmf_ctx* ctx, int64_t n_rows, const float* x, const double* r, float* y,
+                      void* stream);
+
 /* Reductions of the non-finite rule (poisson.py:606-616) over a dense ll
  * buffer of n cells; io = double[3] on the device.
  *   pass 0: io[0] = min(io[0], min over finite cells)  (initialise io[0]=0:

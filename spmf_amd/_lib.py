@@ -195,6 +195,15 @@ SIGNATURES = {
                                        C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int,
                                        C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
                                        C.c_uint64, C.c_void_p]),
+    "spmf_graph_scale": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    "spmf_graph_spmm": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
+                                  C.c_double, C.c_void_p]),
+    "spmf_block_gram_scratch_bytes": (C.c_size_t, [C.c_void_p, C.c_int64]),
+    "spmf_block_gram": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_size_t, C.c_void_p]),
+    "spmf_block_rotate": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spmf_nonfinite_reduce": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
                                         C.c_void_p, C.c_void_p]),
     "spmf_comm_unique_id": (C.c_int, [C.c_void_p]),

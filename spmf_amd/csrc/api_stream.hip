@@ -1,5 +1,6 @@
 // api_stream.hip -- the streaming calls behind the C-ABI (include/spmf_hip.h): the draw stage, its consumers'
-// entries, spmf_knn, spmf_kmeans_step, spmf_silhouette, spmf_graph_layout and spmf_graph_transform.  Host-side
+// entries, spmf_knn, spmf_kmeans_step, spmf_silhouette, spmf_graph_layout, spmf_graph_transform and the graph
+// products of spectral.hip (spmf_graph_scale, spmf_graph_spmm, spmf_block_gram, spmf_block_rotate).  Host-side
 // orchestration only (ctx.h).
 #include <stdlib.h>
 
@@ -884,6 +885,100 @@ int spmf_graph_transform(spmf_ctx* c, int64_t n_query, int k, const int32_t* idx
   ga.rate_over_m = (float)(negative_rate / (double)n_negatives);
   ga.seed_lo = (uint32_t)seed; ga.seed_hi = (uint32_t)(seed >> 32);
   launch_graph_transform(ga, st);
+  return launched(c, true, "");
+}
+
+// ---- multiplying by the graph (spectral.hip) ----------------------------------------------------
+// The graph's checks of the two graph entries, graph_layout's; on SPMF_OK `g` is fit to launch on.
+static int graph_csr_check(spmf_ctx* c, const std::string& f, int64_t n_rows, int64_t nnz, const int64_t* indptr,
+    const int32_t* indices, const float* weights, GraphCsr& g) {
+  if (!graph_layout_rows_ok(n_rows)) return fail(c, SPMF_E_ARG, f + "n_rows must be in 0..2^31 - 64");
+  if (nnz < 0) return fail(c, SPMF_E_ARG, f + "nnz is negative");
+  if (n_rows > 0 && (!indptr || (nnz > 0 && (!indices || !weights)))) return fail(c, SPMF_E_ARG, f + "null argument");
+  g.n_rows = n_rows; g.nnz = nnz; g.indptr = indptr; g.indices = indices; g.weights = weights;
+  return SPMF_OK;
+}
+static bool coef_ok(double v) { return v >= -3.0e38 && v <= 3.0e38; }        // finite, an fp32
+
+int spmf_graph_scale(spmf_ctx* c, int64_t n_rows, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+    const float* weights, float* scale, void* stream) {
+  if (!c) return SPMF_E_ARG;
+  const std::string f = "graph_scale: ";
+  GraphCsr g{};
+  const int rc = graph_csr_check(c, f, n_rows, nnz, indptr, indices, weights, g);
+  if (rc) return rc;
+  if (n_rows > 0 && !scale) return fail(c, SPMF_E_ARG, f + "null argument");
+  if (n_rows == 0) return SPMF_OK;
+  launch_graph_scale(g, scale, (hipStream_t)stream);
+  return launched(c, true, "");
+}
+
+int spmf_graph_spmm(spmf_ctx* c, int64_t n_rows, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+    const float* weights, const float* scale, const float* x, const float* z, float* y, double c_s,
+    const double* c_x, double c_z, void* stream) {
+  if (!c) return SPMF_E_ARG;
+  const std::string f = "graph_spmm: ";
+  GraphCsr g{};
+  const int rc = graph_csr_check(c, f, n_rows, nnz, indptr, indices, weights, g);
+  if (rc) return rc;
+  if (!c_x || (n_rows > 0 && (!x || !y))) return fail(c, SPMF_E_ARG, f + "null argument");
+  if (!coef_ok(c_s) || !coef_ok(c_z)) return fail(c, SPMF_E_ARG, f + "c_s and c_z must be finite");
+  BlockCoef cx;
+  for (int k = 0; k < kBlockCols; ++k) {
+    if (!coef_ok(c_x[k])) return fail(c, SPMF_E_ARG, f + "c_x must be finite");
+    cx.cx[k] = (float)c_x[k];
+  }
+  if (n_rows > 0 && !z && c_z != 0.0) return fail(c, SPMF_E_ARG, f + "null argument: z with c_z != 0");
+  if (n_rows > 0 && y == x) return fail(c, SPMF_E_ARG, f + "y aliases x: other rows gather x (y may be z)");
+  if (n_rows == 0) return SPMF_OK;
+  launch_graph_spmm(g, scale, x, c_z != 0.0 ? z : nullptr, y, (float)c_s, cx, (float)c_z, (hipStream_t)stream);
+  return launched(c, true, "");
+}
+
+// Scratch of one block_gram: the chunks' partial sums.
+static double* block_gram_carve(Arena& a, int64_t rows) {
+  return a.take<double>((size_t)(rows > 0 ? gram_chunks(rows) : 1) * kBlockCols * kBlockCols);
+}
+
+size_t spmf_block_gram_scratch_bytes(const spmf_ctx* c, int64_t n_rows) {
+  if (!c || !graph_layout_rows_ok(n_rows)) return 0;
+  Arena a;
+  block_gram_carve(a, n_rows);
+  return a.used;
+}
+
+int spmf_block_gram(spmf_ctx* c, int64_t n_rows, const float* x, const float* y, double* g, void* scratch,
+    size_t scratch_bytes, void* stream) {
+  if (!c) return SPMF_E_ARG;
+  const std::string f = "block_gram: ";
+  if (!graph_layout_rows_ok(n_rows)) return fail(c, SPMF_E_ARG, f + "n_rows must be in 0..2^31 - 64");
+  if (!g || !scratch || (n_rows > 0 && (!x || !y))) return fail(c, SPMF_E_ARG, f + "null argument");
+  if ((uintptr_t)scratch & 255) return fail(c, SPMF_E_ARG, f + "scratch must be 256-byte aligned");
+  Arena a(scratch, scratch_bytes);
+  double* partial = block_gram_carve(a, n_rows);
+  if (!a.fits()) return scratch_too_small(c, "block_gram", a.used, scratch_bytes,
+      "n_rows=" + std::to_string((long long)n_rows));
+  hipStream_t st = (hipStream_t)stream;
+  if (n_rows == 0) {
+    HIPCHK(c, hipMemsetAsync(g, 0, (size_t)kBlockCols * kBlockCols * sizeof(double), st));
+    return SPMF_OK;
+  }
+  launch_block_gram(n_rows, x, y, partial, g, st);
+  return launched(c, true, "");
+}
+
+int spmf_block_rotate(spmf_ctx* c, int64_t n_rows, const float* x, const double* r, float* y, void* stream) {
+  if (!c) return SPMF_E_ARG;
+  const std::string f = "block_rotate: ";
+  if (!graph_layout_rows_ok(n_rows)) return fail(c, SPMF_E_ARG, f + "n_rows must be in 0..2^31 - 64");
+  if (!r || (n_rows > 0 && (!x || !y))) return fail(c, SPMF_E_ARG, f + "null argument");
+  BlockRot rot;
+  for (int k = 0; k < kBlockCols * kBlockCols; ++k) {
+    if (!(r[k] >= -1.7e308 && r[k] <= 1.7e308)) return fail(c, SPMF_E_ARG, f + "r must be finite");
+    rot.r[k] = r[k];
+  }
+  if (n_rows == 0) return SPMF_OK;
+  launch_block_rotate(n_rows, x, rot, y, (hipStream_t)stream);
   return launched(c, true, "");
 }
 

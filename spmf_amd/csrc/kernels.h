@@ -5,6 +5,8 @@
 
 #include <type_traits>
 
+#include "spmf_hip.h"   // SPMF_BLOCK_COLS, SPMF_GRAM_CHUNK_ROWS
+
 namespace spmf {
 
 // The latent widths the kernels are built for, MINKP, 2 MINKP, .., MAXKP: calls f with KP as a
@@ -486,6 +488,31 @@ struct GraphTransformArgs {
   uint32_t seed_lo, seed_hi;
 };
 void launch_graph_transform(const GraphTransformArgs& a, hipStream_t st);
+// spectral.hip: multiplying by the graph (include/spmf_hip.h spmf_graph_scale .. spmf_block_rotate have the
+// definitions).  A block is fp32 [n_rows][SPMF_BLOCK_COLS] row-major: a row is one 64-byte segment.  The graph is
+// read as it stands, under graph_layout's rules: every index, weight and indptr value is checked in the kernel.
+constexpr int kBlockCols = SPMF_BLOCK_COLS;
+constexpr int kGramChunk = SPMF_GRAM_CHUNK_ROWS;   // rows per partial of block_gram: a constant, never the grid's
+struct GraphCsr {
+  int64_t n_rows, nnz;
+  const int64_t* indptr;           // [n_rows + 1]
+  const int32_t* indices;          // [nnz]
+  const float* weights;            // [nnz]
+};
+struct BlockCoef {
+  float cx[kBlockCols];            // fp64 on the host, each rounded once
+};
+struct BlockRot {
+  double r[kBlockCols * kBlockCols];   // row-major: the kernel's argument (2 KiB)
+};
+void launch_graph_scale(const GraphCsr& g, float* scale, hipStream_t st);
+// y = c_s s_i sum_j w_ij s_j x_j + x_i o cx + c_z z_i; scale and z may be null; y may be z, never x
+void launch_graph_spmm(const GraphCsr& g, const float* scale, const float* x, const float* z, float* y, float cs,
+                       const BlockCoef& cx, float cz, hipStream_t st);
+inline int64_t gram_chunks(int64_t n_rows) { return (n_rows + kGramChunk - 1) / kGramChunk; }
+// g[256] = x^T y in fp64: partial [gram_chunks(n_rows)][256], then their sum in ascending chunk order
+void launch_block_gram(int64_t n_rows, const float* x, const float* y, double* partial, double* g, hipStream_t st);
+void launch_block_rotate(int64_t n_rows, const float* x, const BlockRot& r, float* y, hipStream_t st);
 // sets.hip: per row and column set the fp64 weighted sum over the set's listed columns of the posterior
 // predictive mean m_s, reduced over the draws: mean [B][ld] (column g = set g) and, where asked for, the unbiased
 // standard deviation over the draws (S >= 2).  set_ptr: HOST, [n_sets + 1], set g lists cols[set_ptr[g] ..

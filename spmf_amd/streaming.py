@@ -1,7 +1,7 @@
 """The streaming posterior queries of the model classes: ``StreamingQueries`` is the mixin that gives
 PoissonFactorization (and through it the Bernoulli and mixed classes) waic_streaming, top_k, score_cells,
 rank_cells, predict, top_rows, group_means, set_scores, embed, knn, neighbors, kmeans, cluster, silhouette,
-fuzzy_graph, graph_layout, umap, graph_transform and umap_transform.
+fuzzy_graph, graph_layout, umap, graph_transform, umap_transform, spectral and spectral_cluster.
 
 Every draw-stage query is the same three pieces around its own kernel (include/spmf_hip.h, csrc/api_stream.hip "the
 draw stage"): ``_Draws``, the checked draws and the one place a library call is spelled; a driver that walks
@@ -901,6 +901,49 @@ class StreamingQueries:
             raise ValueError(f"{name}: init must be one of {starts} or a float32 [N, 2] tensor, got {init!r}")
         return SimpleNamespace(n_epochs=n_epochs, a=a, b=b, M=M, rate=rate, gamma=gamma, lr=lr, seed=seed)
 
+    @staticmethod
+    def _graph_tensors(name, graph):
+        """The graph dict of ``graph_layout`` / ``spectral``, its types and shapes checked -> (indptr, indices,
+        weights, N, nnz)."""
+        if not isinstance(graph, dict) or any(n not in graph for n in ("indptr", "indices", "weights")):
+            raise ValueError(f"{name}: graph must be a dict with 'indptr', 'indices' and 'weights' (fuzzy_graph)")
+        want = {"indptr": torch.int64, "indices": torch.int32, "weights": torch.float32}
+        for n, dt in want.items():
+            t = graph[n]
+            if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != dt:
+                raise ValueError(f"{name}: graph['{n}'] must be a 1-D {dt} tensor")
+        indptr, indices, weights = (graph[n] for n in want)
+        if indptr.numel() < 1:
+            raise ValueError(f"{name}: graph['indptr'] must have N + 1 entries")
+        N, nnz = int(indptr.numel()) - 1, int(indices.numel())
+        if int(weights.numel()) != nnz:
+            raise ValueError(f"{name}: graph['weights'] has {int(weights.numel())} entries, graph['indices'] {nnz}")
+        if N > 2 ** 31 - 64:
+            raise ValueError(f"{name}: {N} rows are beyond one call of the library")
+        if indices.device != indptr.device or weights.device != indptr.device:
+            raise ValueError(f"{name}: the graph's tensors must be on one device")
+        return indptr, indices, weights, N, nnz
+
+    @staticmethod
+    def _graph_numbers(name, indptr, indices, N, nnz):
+        """The graph's numbers -- an indptr rising from 0 to nnz, indices in [0, N) -- checked before any library
+        call: one device-side reduction and one read-back."""
+        ends = torch.stack([indptr[0], indptr[-1]])
+        step = torch.diff(indptr).amin().reshape(1) if N else torch.zeros(1, dtype=torch.int64, device=indptr.device)
+        span = torch.stack(list(torch.aminmax(indices))).to(torch.int64) if nnz else \
+            torch.zeros(2, dtype=torch.int64, device=indptr.device)
+        first, last, step, lo, hi = torch.cat([ends, step, span]).tolist()
+        if first != 0 or last != nnz or step < 0:
+            raise ValueError(f"{name}: graph['indptr'] must rise from 0 to the {nnz} entries, got {first} .. {last}"
+                             + (" with a falling step" if step < 0 else ""))
+        if nnz and (lo < 0 or hi >= N):
+            raise ValueError(f"{name}: graph['indices'] must lie in [0, {N}), got {lo} .. {hi}")
+
+    def _graph_on_device(self, name, indptr):
+        dev = torch.device(self.device)
+        if indptr.device.type != "cuda" or (dev.index is not None and indptr.device != dev):
+            raise ValueError(f"{name}: the graph must be on the model's device {self.device}, got {indptr.device}")
+
     def graph_layout(self, graph, init="pca", points=None, n_epochs=None, min_dist=0.1, spread=1.0, a=None, b=None,
                      n_negatives=8, negative_rate=5.0, repulsion=1.0, learning_rate=1.0, seed=0):
         """A deterministic 2-D layout of a weighted graph: the full-batch form of UMAP's objective, one kernel
@@ -926,23 +969,7 @@ class StreamingQueries:
         name = "graph_layout"
         la = self._layout_args(name, n_epochs, min_dist, spread, a, b, n_negatives, negative_rate, repulsion,
                                learning_rate, seed, init)
-        if not isinstance(graph, dict) or any(n not in graph for n in ("indptr", "indices", "weights")):
-            raise ValueError(f"{name}: graph must be a dict with 'indptr', 'indices' and 'weights' (fuzzy_graph)")
-        want = {"indptr": torch.int64, "indices": torch.int32, "weights": torch.float32}
-        for n, dt in want.items():
-            t = graph[n]
-            if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != dt:
-                raise ValueError(f"{name}: graph['{n}'] must be a 1-D {dt} tensor")
-        indptr, indices, weights = (graph[n] for n in want)
-        if indptr.numel() < 1:
-            raise ValueError(f"{name}: graph['indptr'] must have N + 1 entries")
-        N, nnz = int(indptr.numel()) - 1, int(indices.numel())
-        if int(weights.numel()) != nnz:
-            raise ValueError(f"{name}: graph['weights'] has {int(weights.numel())} entries, graph['indices'] {nnz}")
-        if N > 2 ** 31 - 64:
-            raise ValueError(f"{name}: {N} rows are beyond one call of the library")
-        if indices.device != indptr.device or weights.device != indptr.device:
-            raise ValueError(f"{name}: the graph's tensors must be on one device")
+        indptr, indices, weights, N, nnz = self._graph_tensors(name, graph)
         if isinstance(init, torch.Tensor):
             if init.dim() != 2 or tuple(init.shape) != (N, 2) or init.dtype != torch.float32:
                 raise ValueError(f"{name}: an init tensor must be float32 of shape {(N, 2)}, got {init.dtype} "
@@ -957,20 +984,8 @@ class StreamingQueries:
             if points.device != indptr.device:
                 raise ValueError(f"{name}: points must be on the device of the graph {indptr.device}, got "
                                  f"{points.device}")
-        # the graph's numbers: one device-side reduction and one read-back, before any library call
-        ends = torch.stack([indptr[0], indptr[-1]])
-        step = torch.diff(indptr).amin().reshape(1) if N else torch.zeros(1, dtype=torch.int64, device=indptr.device)
-        span = torch.stack(list(torch.aminmax(indices))).to(torch.int64) if nnz else \
-            torch.zeros(2, dtype=torch.int64, device=indptr.device)
-        first, last, step, lo, hi = torch.cat([ends, step, span]).tolist()
-        if first != 0 or last != nnz or step < 0:
-            raise ValueError(f"{name}: graph['indptr'] must rise from 0 to the {nnz} entries, got {first} .. {last}"
-                             + (" with a falling step" if step < 0 else ""))
-        if nnz and (lo < 0 or hi >= N):
-            raise ValueError(f"{name}: graph['indices'] must lie in [0, {N}), got {lo} .. {hi}")
-        dev = torch.device(self.device)
-        if indptr.device.type != "cuda" or (dev.index is not None and indptr.device != dev):
-            raise ValueError(f"{name}: the graph must be on the model's device {self.device}, got {indptr.device}")
+        self._graph_numbers(name, indptr, indices, N, nnz)
+        self._graph_on_device(name, indptr)
         total = _graph.default_epochs(N) if la.n_epochs is None else la.n_epochs
         if isinstance(init, torch.Tensor):
             start = init.contiguous()
@@ -1016,6 +1031,65 @@ class StreamingQueries:
                                 learning_rate=learning_rate, seed=seed)
         res.update(graph=g, latent=emb, indices=nn["indices"], distances=nn["distances"])
         return res
+
+    def spectral(self, graph, n_components=2, tol=1e-4, max_iter=100, seed=0):
+        """The ``n_components`` + 1 leading eigenvectors of S = D^-1/2 A D^-1/2 of a weighted graph: the spectral
+        embedding of its rows (sklearn's ``SpectralEmbedding``, the start of umap-learn's layout, with
+        ``spmf_amd.spectral.diffusion_map`` scanpy's ``tl.diffmap``).  Chebyshev-filtered subspace iteration on a
+        block of 16 columns (``spmf_amd.spectral`` has the algorithm): the products with the graph and the two
+        small fp64 reductions are the library's (include/spmf_hip.h spmf_graph_spmm, csrc/spectral.hip), the
+        16 x 16 eigenproblems are ``eigh`` on the CPU.  No atomics and a seeded CPU start: two runs give the same
+        bits.
+
+        ``graph``: as in ``graph_layout``, what ``fuzzy_graph`` returns; it should be symmetric (an asymmetric one
+        is not refused, it does not converge).  1 <= ``n_components`` <= 12.  The iteration stops when
+        |S v - l v| <= ``tol`` for the n_components + 1 leading columns, or after ``max_iter`` outer iterations.
+        At least 32 rows must have a valid edge: below that a dense ``eigh`` is the tool.
+
+        Returns what ``spmf_amd.spectral.solve`` returns, tensors on the device: 'values', 'vectors', 'embedding'
+        (``vectors[:, 1:]``), 'residuals', 'converged', 'n_iter', 'n_products', 'scale', 'n_unit'.  In a degenerate
+        eigenspace the basis is whatever the seeded start gives: reproducible, not canonical.  Pass
+        ``spmf_amd.spectral.layout_init(res['embedding'], seed)`` as ``graph_layout(init=...)`` for the spectral
+        start of a layout."""
+        from . import spectral as _spectral
+        name = "spectral"
+        _spectral.check_args(name, n_components, tol, max_iter, seed)
+        indptr, indices, weights, N, nnz = self._graph_tensors(name, graph)
+        self._graph_numbers(name, indptr, indices, N, nnz)
+        # the rows with a valid edge, in plain torch: the library is not needed to refuse a small graph
+        ok = (torch.isfinite(weights) & (weights > 0)).to(torch.int64)
+        run = torch.cat([torch.zeros(1, dtype=torch.int64, device=ok.device), torch.cumsum(ok, 0)])
+        n_live = int(((run[indptr[1:]] - run[indptr[:-1]]) > 0).sum())
+        if n_live < _spectral.MIN_ROWS:
+            raise _spectral.too_few_rows(name, n_live)
+        self._graph_on_device(name, indptr)
+        ops = _spectral.LibraryOps(_lib.load(), self._handle(), indptr, indices, weights)
+        return _spectral.solve(ops, n_components, tol, max_iter, seed, name=name)
+
+    def spectral_cluster(self, graph, n_clusters, tol=1e-4, max_iter=100, seed=0, kmeans_init="k-means++",
+                         kmeans_max_iter=100):
+        """Spectral clustering of the rows of a graph (Ng, Jordan, Weiss): ``spectral(n_components =
+        n_clusters - 1)``, the rows of the ``n_clusters`` leading eigenvectors scaled to unit length
+        (``spmf_amd.spectral.cluster_features``), then ``kmeans`` of those rows.  It separates clusters that are
+        not convex in the latent space -- two concentric rings -- where ``cluster``'s k-means of the points
+        cannot.  2 <= ``n_clusters`` <= 13; a row without a valid edge gets the label -1.
+
+        Returns what ``kmeans`` returns (for the features) and 'spectral' (the result of ``spectral``) and
+        'features'.  Bit-reproducible for a given seed on one machine."""
+        from . import cluster as _cluster
+        from . import spectral as _spectral
+        name = "spectral_cluster"
+        if isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer)) \
+                or not 2 <= int(n_clusters) <= _spectral.MAX_COMPONENTS + 1:
+            raise ValueError(f"{name}: n_clusters must be an integer in 2..{_spectral.MAX_COMPONENTS + 1}, got "
+                             f"{n_clusters!r}")
+        _spectral.check_args(name, int(n_clusters) - 1, tol, max_iter, seed)
+        _cluster.check_args(name, int(n_clusters), kmeans_max_iter, kmeans_init)
+        res = self.spectral(graph, n_components=int(n_clusters) - 1, tol=tol, max_iter=max_iter, seed=seed)
+        feats = _spectral.cluster_features(res, int(n_clusters))
+        out = self.kmeans(feats, int(n_clusters), init=kmeans_init, max_iter=kmeans_max_iter, seed=seed)
+        out.update(spectral=res, features=feats)
+        return out
 
     def graph_transform(self, indices, distances, reference_layout, weights=None, init=None, n_epochs=None,
                         min_dist=0.1, spread=1.0, a=None, b=None, n_negatives=8, negative_rate=5.0, repulsion=1.0,
