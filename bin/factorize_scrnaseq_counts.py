@@ -50,6 +50,13 @@ With --spectral N (the spectral embedding / diffusion-map coordinates of the cel
                                  neighbour graph (0: a cell without a neighbour)
   <stem>_spectral_values_<P>.npy [N + 1] float64: the eigenvalues 0 .. N, descending, the first about 1
 over the same encoding, --umap-neighbors and seed.  Without the flag nothing changes.
+With --communities (Louvain clustering of the same fuzzy neighbour graph by modularity: the number of clusters is
+found, not given; --resolution R, default 1, larger for more and smaller communities):
+  <stem>_communities_<P>.npy     [cells] int64: the community of every cell, numbered by descending size (-1: a
+                                 cell without a neighbour)
+over the same encoding, --umap-neighbors and seed; with --umap the graph is built once.  The labels stand in for
+--clusters wherever those are used and --clusters is not given: the group table (without --labels), --silhouette
+and the labels of --map-counts.  Bit-reproducible for a given model.  Without the flag nothing changes.
 With --map-counts FILE beside --umap (new cells over the same genes, e.g. a second sample; .npy dense or .npz CSR):
   <stem>_UMAP_map_<P>.npy        [new cells, 2] float32: the new cells on the map above, which does not move (NaN:
                                  a cell without a finite encoding)
@@ -108,6 +115,9 @@ def build_parser():
                    "encoding's principal axes, or the graph's leading eigenvectors")
     p.add_argument("--spectral", type=int, default=None, help="N: writes the N leading non-trivial eigenvectors "
                                                               "of the cells' neighbour graph and their eigenvalues")
+    p.add_argument("--communities", action="store_true", help="writes the Louvain communities of the cells' neighbour "
+                                                              "graph (the number of clusters is found)")
+    p.add_argument("--resolution", type=float, default=1.0, help="R > 0: the resolution of --communities' modularity")
     p.add_argument("--map-counts", default=None, help="FILE: new cells over the same genes; with --umap they are "
                                                       "placed on the map (and labelled with --clusters / --labels)")
     p.add_argument("--gene-sets", default=None, help="FILE.gmt: gene sets (name, description, members per line); "
@@ -137,8 +147,10 @@ def load_counts(path):
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(sys.argv[1:] if argv is None else argv)
-    if args.silhouette and args.clusters is None and args.labels is None:
-        parser.error("--silhouette needs --clusters or --labels")
+    if args.silhouette and args.clusters is None and args.labels is None and not args.communities:
+        parser.error("--silhouette needs --clusters, --communities or --labels")
+    if not (args.resolution > 0 and args.resolution < float("inf")):
+        parser.error("--resolution needs a finite R > 0")
     if args.map_counts is not None and not args.umap:
         parser.error("--map-counts needs --umap")
     if args.spectral is not None and not 1 <= args.spectral <= 12:
@@ -208,24 +220,36 @@ def main(argv=None):
     clusters = None
     if args.clusters is not None:
         clusters = cluster_cells(factor, X, f"{stem}_cluster_{P}.npy", f"{stem}_centroid_{P}.npy", args)
+    reference, n_clusters = None, args.clusters
+    if args.communities:
+        # the graph once: with --umap the layout comes first and its graph is clustered
+        if args.umap:
+            reference = umap_cells(factor, X, f"{stem}_UMAP_{P}.npy", args)
+        found, n_found = community_cells(factor, X, reference["graph"] if reference is not None else None,
+                                         f"{stem}_communities_{P}.npy", args)
+        if clusters is None and n_found > 0:
+            clusters, n_clusters = found, n_found
     if args.labels is not None:
         group_table(factor, X, np.load(args.labels), gene_names, f"{stem}_groupmean_{P}.npy", args)
     elif clusters is not None:
-        group_table(factor, X, clusters, gene_names, f"{stem}_groupmean_{P}.npy", args, n_groups=args.clusters)
+        group_table(factor, X, clusters, gene_names, f"{stem}_groupmean_{P}.npy", args, n_groups=n_clusters)
     if args.silhouette:
         if clusters is not None:
-            silhouette_cells(factor, X, clusters, args.clusters, f"{stem}_silhouette_{P}.npy", args)
-        else:
+            silhouette_cells(factor, X, clusters, n_clusters, f"{stem}_silhouette_{P}.npy", args)
+        elif args.labels is not None:
             silhouette_cells(factor, X, np.load(args.labels), None, f"{stem}_silhouette_{P}.npy", args)
+        else:
+            print("silhouette: no cell has a community")
     if args.umap:
-        reference = umap_cells(factor, X, f"{stem}_UMAP_{P}.npy", args)
+        if reference is None:
+            reference = umap_cells(factor, X, f"{stem}_UMAP_{P}.npy", args)
         if args.map_counts is not None:
             known = clusters if clusters is not None else (np.load(args.labels) if args.labels is not None else None)
             X_new = load_counts(args.map_counts)
             if X_new.ndim != 2 or X_new.shape[1] != D:
                 sys.exit(f"--map-counts must hold [cells, {D}] counts over the genes of --counts, got {X_new.shape}")
             map_cells(factor, X_new, reference, known,
-                      args.clusters if clusters is not None else None, f"{stem}_UMAP_map_{P}.npy",
+                      n_clusters if clusters is not None else None, f"{stem}_UMAP_map_{P}.npy",
                       f"{stem}_label_map_{P}.npy", args)
     if args.spectral is not None:
         spectral_cells(factor, X, f"{stem}_spectral_{P}.npy", f"{stem}_spectral_values_{P}.npy", args)
@@ -346,6 +370,22 @@ def spectral_cells(factor, X, path, values_path, args):
           f"{res['n_iter']} iterations and {res['n_products']} products, largest residual "
           f"{float(res['residuals'].max()):.2e}" + ("" if res["converged"] else " (not converged)")
           + f", {res['n_unit']} eigenvalues at 1")
+
+
+def community_cells(factor, X, graph, path, args):
+    """Louvain clustering of the cells (``communities`` on the fuzzy graph ``umap_cells`` lays out; ``graph``: that
+    graph where the layout was made, else None and it is built here): the labels as a file; -> (the labels on the
+    device, as ``group_means`` and ``silhouette`` take them, and how many communities there are)."""
+    if graph is None:
+        _, _, graph = _cell_graph(factor, X, args)
+    res = factor.communities(graph, resolution=args.resolution)
+    np.save(path, res["labels"].cpu().numpy())
+    sizes = ", ".join(str(n) for n in res["sizes"].tolist())
+    alone = int((res["labels"] < 0).sum())
+    print(f"communities: {res['n_communities']} at resolution {res['resolution']:g}, modularity "
+          f"{res['modularity']:.6f}, sweeps per level {[lv['n_sweeps'] for lv in res['levels']]}, cells {sizes}"
+          + (f", {alone} without a community" if alone else ""))
+    return res["labels"], res["n_communities"]
 
 
 def map_cells(factor, X_new, reference, labels, n_classes, path, label_path, args):

@@ -1091,6 +1091,44 @@ int spmf_block_gram(spmf_ctx* ctx, int64_t n_rows, const float* x, const float* 
 int spmf_block_rotate(spmf_ctx* ctx, int64_t n_rows, const float* x, const double* r, float* y,
                       void* stream);
 
+/* ---- modularity moves on the graph (added within ABI 6: one new entry point, no struct changed) ----
+ * One Jacobi sweep of Louvain's local moving on a graph in CSR whose weights are int64 fixed point
+ * (csrc/graph_move.hip; spmf_amd/communities.py is the driver and has the whole algorithm).  Every sum is an
+ * int64 sum, exact and the same in any order; the score is four fp64 operations, each rounded on its own.
+ * No atomic, no scratch: two calls return the same bits, and a row's new label is a function of that row's
+ * list, labels_in and tot alone.
+ *
+ * indptr is read under spmf_graph_spmm's rules (clamped to [0, nnz], a falling indptr is an empty row).  An
+ * entry counts when its column lies in [0, n_rows) and wq >= 1.  For row i with a = labels_in[i]:
+ *   k_i   = the sum of the row's counting wq (a self entry (i, i) included),
+ *   e_ic  = the sum of wq over the counting entries j != i with labels_in[j] == c,
+ *   score(c) = double(e_ic) - ((gamma * double(k_i)) * double(tot'[c])) / double(m2),
+ *   tot'[a] = tot[a] - k_i, tot'[c] = tot[c] otherwise.
+ * Candidates are the labels c of the row's counting non-self entries with c in [0, n_rows); direction 0
+ * admits only c > a, direction 1 only c < a.  labels_out[i] is the admitted candidate of largest score, the
+ * smaller c on equal scores, if that score is strictly greater than score(a); else a.  A row with k_i = 0,
+ * and a row whose own label lies outside [0, n_rows), keeps its label.
+ *
+ * Two tilings of one method.  A row of at most SPMF_MOVE_GROUP_LEN entries is moved by a group of 16 lanes,
+ * four rows to a wave: the entries in registers, one broadcast step per entry.  A longer row is moved only if
+ * long_rows (device, int32 [n_long], any order, NULL with n_long == 0) lists it: one 256-thread workgroup per
+ * listed row, a thread per candidate of a 256-entry tile, the row streamed through LDS tiles of 256 for every
+ * candidate tile -- any length, no table, no capacity, at a cost of O(d^2 / 256) per row of d entries.  A
+ * long row left off the list keeps its label; a short row on it gets the value the group path writes; an
+ * entry of long_rows outside [0, n_rows) is skipped.
+ *
+ * SPMF_E_ARG for n_rows outside 0..2^31 - 64, nnz < 0, n_long outside 0..2^31 - 64, a NULL pointer where one
+ * is needed (indptr, labels_in, tot, labels_out with n_rows > 0; indices / wq with nnz > 0; long_rows with
+ * n_long > 0), gamma not finite and > 0, m2 <= 0, direction not 0 or 1, labels_out == labels_in ("aliases":
+ * other rows read labels_in); every error returns before any launch with "graph_move: " in front of the
+ * message.  n_rows == 0 returns SPMF_OK behind the checks.  The context's workspace is not touched.
+ * Stream-ordered, synchronises nowhere. */
+#define SPMF_MOVE_GROUP_LEN 64
+int spmf_graph_move(spmf_ctx* ctx, int64_t n_rows, int64_t nnz, const int64_t* indptr,
+                    const int32_t* indices, const int64_t* wq, const int32_t* labels_in,
+                    const int64_t* tot, const int32_t* long_rows, int64_t n_long, double gamma,
+                    int64_t m2, int direction, int32_t* labels_out, void* stream);
+
 /* Reductions of the non-finite rule (poisson.py:606-616) over a dense ll
  * buffer of n cells; io = double[3] on the device.
  *   pass 0: io[0] = min(io[0], min over finite cells)  (initialise io[0]=0:

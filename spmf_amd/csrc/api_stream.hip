@@ -1,7 +1,7 @@
 // api_stream.hip -- the streaming calls behind the C-ABI (include/spmf_hip.h): the draw stage, its consumers'
 // entries, spmf_knn, spmf_kmeans_step, spmf_silhouette, spmf_graph_layout, spmf_graph_transform and the graph
-// products of spectral.hip (spmf_graph_scale, spmf_graph_spmm, spmf_block_gram, spmf_block_rotate).  Host-side
-// orchestration only (ctx.h).
+// products of spectral.hip (spmf_graph_scale, spmf_graph_spmm, spmf_block_gram, spmf_block_rotate) and the sweep of
+// graph_move.hip (spmf_graph_move).  Host-side orchestration only (ctx.h).
 #include <stdlib.h>
 
 #include "ctx.h"
@@ -932,6 +932,32 @@ int spmf_graph_spmm(spmf_ctx* c, int64_t n_rows, int64_t nnz, const int64_t* ind
   if (n_rows > 0 && y == x) return fail(c, SPMF_E_ARG, f + "y aliases x: other rows gather x (y may be z)");
   if (n_rows == 0) return SPMF_OK;
   launch_graph_spmm(g, scale, x, c_z != 0.0 ? z : nullptr, y, (float)c_s, cx, (float)c_z, (hipStream_t)stream);
+  return launched(c, true, "");
+}
+
+// ---- modularity moves on the graph (graph_move.hip) ----------------------------------------------
+int spmf_graph_move(spmf_ctx* c, int64_t n_rows, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+    const int64_t* wq, const int32_t* labels_in, const int64_t* tot, const int32_t* long_rows, int64_t n_long,
+    double gamma, int64_t m2, int direction, int32_t* labels_out, void* stream) {
+  if (!c) return SPMF_E_ARG;
+  const std::string f = "graph_move: ";
+  if (!graph_layout_rows_ok(n_rows)) return fail(c, SPMF_E_ARG, f + "n_rows must be in 0..2^31 - 64");
+  if (nnz < 0) return fail(c, SPMF_E_ARG, f + "nnz is negative");
+  if (!graph_layout_rows_ok(n_long)) return fail(c, SPMF_E_ARG, f + "n_long must be in 0..2^31 - 64");
+  if (n_rows > 0 && (!indptr || !labels_in || !tot || !labels_out || (nnz > 0 && (!indices || !wq))))
+    return fail(c, SPMF_E_ARG, f + "null argument");
+  if (n_long > 0 && !long_rows) return fail(c, SPMF_E_ARG, f + "null argument: long_rows with n_long > 0");
+  if (!(gamma > 0.0 && gamma <= 1.7e308)) return fail(c, SPMF_E_ARG, f + "gamma must be finite and > 0");
+  if (m2 <= 0) return fail(c, SPMF_E_ARG, f + "m2 must be > 0");
+  if (direction != 0 && direction != 1) return fail(c, SPMF_E_ARG, f + "direction must be 0 (up) or 1 (down)");
+  if (n_rows > 0 && labels_out == labels_in)
+    return fail(c, SPMF_E_ARG, f + "labels_out aliases labels_in: other rows read labels_in");
+  if (n_rows == 0) return SPMF_OK;
+  MoveArgs ma{};
+  ma.n_rows = n_rows; ma.nnz = nnz; ma.indptr = indptr; ma.indices = indices; ma.wq = wq;
+  ma.labels_in = labels_in; ma.tot = tot; ma.long_rows = long_rows; ma.n_long = n_long;
+  ma.gamma = gamma; ma.m2 = (double)m2; ma.direction = direction; ma.labels_out = labels_out;
+  launch_graph_move(ma, (hipStream_t)stream);
   return launched(c, true, "");
 }
 

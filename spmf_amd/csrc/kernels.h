@@ -513,6 +513,25 @@ inline int64_t gram_chunks(int64_t n_rows) { return (n_rows + kGramChunk - 1) / 
 // g[256] = x^T y in fp64: partial [gram_chunks(n_rows)][256], then their sum in ascending chunk order
 void launch_block_gram(int64_t n_rows, const float* x, const float* y, double* partial, double* g, hipStream_t st);
 void launch_block_rotate(int64_t n_rows, const float* x, const BlockRot& r, float* y, hipStream_t st);
+// graph_move.hip: one Jacobi sweep of modularity moves (include/spmf_hip.h spmf_graph_move has the definition).
+// Weights are int64 fixed point, so every sum is exact; the score is four fp64 operations, each rounded once.
+// Rows of at most kMoveGroupLen entries are moved by a 16-lane group each, the rows of long_rows by a workgroup
+// each (O(d^2 / 256) per row of d entries); every other row keeps its label.
+constexpr int kMoveGroupLen = SPMF_MOVE_GROUP_LEN;
+struct MoveArgs {
+  int64_t n_rows, nnz;
+  const int64_t* indptr;           // [n_rows + 1]
+  const int32_t* indices;          // [nnz]
+  const int64_t* wq;               // [nnz]; an entry counts with wq >= 1
+  const int32_t* labels_in;        // [n_rows]
+  const int64_t* tot;              // [n_rows], by label
+  const int32_t* long_rows;        // [n_long], or null
+  int64_t n_long;
+  double gamma, m2;                // m2 rounded once on the host
+  int direction;                   // 0: only c > a is admitted, 1: only c < a
+  int32_t* labels_out;             // [n_rows]; never labels_in
+};
+void launch_graph_move(const MoveArgs& a, hipStream_t st);
 // sets.hip: per row and column set the fp64 weighted sum over the set's listed columns of the posterior
 // predictive mean m_s, reduced over the draws: mean [B][ld] (column g = set g) and, where asked for, the unbiased
 // standard deviation over the draws (S >= 2).  set_ptr: HOST, [n_sets + 1], set g lists cols[set_ptr[g] ..

@@ -1091,6 +1091,36 @@ class StreamingQueries:
         out.update(spectral=res, features=feats)
         return out
 
+    def communities(self, graph, resolution=1.0, max_levels=32, max_sweeps=100, tol=1e-7):
+        """Louvain clustering of the rows of a weighted graph by modularity (scanpy's ``tl.louvain`` /
+        ``tl.leiden`` on ``obsp["connectivities"]``): it finds the number of clusters itself, where ``cluster`` and
+        ``spectral_cluster`` are told it.  ``spmf_amd.communities`` has the algorithm: the weights become int64
+        fixed point (rint(w 2^24)), so every sum is exact in any order; a level is a run of synchronous sweeps, each
+        one library call (include/spmf_hip.h spmf_graph_move, csrc/graph_move.hip) that moves every row at once from
+        the labels of the sweep before, upwards in label on even sweeps and downwards on odd ones; between levels the
+        communities become the rows of a coarser graph.  No atomics on floats anywhere: two runs give the same
+        bits, which are also the bits of the numpy backend (``spmf_amd.communities.NumpyOps``).
+
+        ``graph``: as in ``graph_layout``, what ``fuzzy_graph`` returns; it should be symmetric (an asymmetric one
+        is not refused).  ``resolution`` > 0: the gamma of Q = in / M2 - gamma sum_c (tot_c / M2)^2, larger for
+        more and smaller communities.  A level keeps its best labelling (Q above the best so far by more than
+        ``tol``) and ends after an up and a down sweep that moved nothing, 4 sweeps without a new best or
+        ``max_sweeps``; the levels end when one merged nothing, or after ``max_levels``.
+
+        Returns what ``spmf_amd.communities.solve`` returns, tensors on the device: 'labels' int64 [N], communities
+        numbered by descending size (ties by smallest member row), -1 for a row without a valid entry -- what
+        ``group_means``, ``silhouette`` and ``neighbors.vote`` take; 'n_communities', 'sizes', 'modularity',
+        'levels' (per level 'n_nodes', 'n_communities', 'modularity', 'n_sweeps', 'hit_max_sweeps') and
+        'resolution'."""
+        from . import communities as _communities
+        name = "communities"
+        _communities.check_args(name, resolution, max_levels, max_sweeps, tol)
+        indptr, indices, weights, N, nnz = self._graph_tensors(name, graph)
+        self._graph_numbers(name, indptr, indices, N, nnz)
+        self._graph_on_device(name, indptr)
+        ops = _communities.LibraryOps(_lib.load(), self._handle(), indptr, indices, weights)
+        return _communities.solve(ops, resolution, max_levels, max_sweeps, tol, name=name)
+
     def graph_transform(self, indices, distances, reference_layout, weights=None, init=None, n_epochs=None,
                         min_dist=0.1, spread=1.0, a=None, b=None, n_negatives=8, negative_rate=5.0, repulsion=1.0,
                         learning_rate=0.25, seed=0, row_offset=0):
