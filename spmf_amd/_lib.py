@@ -9,6 +9,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 #: SPMF_LIB_PATH: another build of the same library (tools/build_variant.sh: kernel experiments)
 LIB_PATH = os.environ.get("SPMF_LIB_PATH") or os.path.join(_HERE, "libspmf_hip.so")
@@ -294,3 +296,30 @@ def check(ctx_handle, rc, what):
         msg = load().spmf_last_error(ctx_handle)
         raise SpmfError(f"{what} failed (rc={rc}): "
                         f"{msg.decode() if msg else '?'}")
+
+
+class Scratch:
+    """The grow-only device scratch of one call or one loop of calls."""
+
+    def __init__(self, device):
+        self.device, self.buf = device, None
+
+    def fit(self, need_bytes):
+        """-> (256-byte aligned pointer, usable bytes >= need_bytes).  An outgrown buffer is dropped
+        before the larger one is allocated."""
+        if self.buf is None or self.buf.numel() < need_bytes + 256:
+            self.buf = None
+            self.buf = torch.empty(need_bytes + 256, dtype=torch.uint8, device=self.device)
+        off = (-self.buf.data_ptr()) % 256
+        return self.buf.data_ptr() + off, self.buf.numel() - off
+
+
+def call(handle, fn, *args, device, scratch=None):
+    """The entry point ``fn`` on the context ``handle`` with ``args`` and, behind them, the current stream of
+    ``device``, checked.  ``scratch`` = (a ``Scratch``, the name of the entry's ``*_scratch_bytes``, its arguments
+    behind the handle): the fitted pointer and byte count go in front of the stream."""
+    lib = load()
+    if scratch is not None:
+        buf, size_fn, *size_args = scratch
+        args += buf.fit(getattr(lib, size_fn)(handle, *size_args))
+    check(handle, getattr(lib, fn)(handle, *args, torch.cuda.current_stream(device).cuda_stream), fn)

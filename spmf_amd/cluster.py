@@ -1,11 +1,10 @@
 """What surrounds the library's Lloyd step (include/spmf_hip.h spmf_kmeans_step): the starting centroids, the
-centroid update and the loop of ``StreamingQueries.kmeans``.  Plain torch around one library call per
+centroid update and the loop of ``AnalysisQueries.kmeans``.  Plain torch around one library call per
 iteration; the assignment and the sums -- the hot path -- are csrc/kmeans.hip behind csrc/knn.hip.
 """
-import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 INITS = ("k-means++", "first")
 MAX_CLUSTERS = 65536
@@ -14,12 +13,9 @@ MAX_CLUSTERS = 65536
 def check_args(name, n_clusters, max_iter, init):
     """``n_clusters``, ``max_iter`` and a named ``init`` of ``kmeans`` / ``cluster``, checked before any library
     call -> (G, max_iter)."""
-    if isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer)):
-        raise ValueError(f"{name}: n_clusters must be an integer, got {n_clusters!r}")
-    if not 1 <= int(n_clusters) <= MAX_CLUSTERS:
+    if not 1 <= _args.integer(name, "n_clusters", n_clusters) <= MAX_CLUSTERS:
         raise ValueError(f"{name} needs 1 <= n_clusters <= {MAX_CLUSTERS}, got {n_clusters}")
-    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or int(max_iter) < 1:
-        raise ValueError(f"{name}: max_iter must be an integer >= 1, got {max_iter!r}")
+    _args.integer(name, "max_iter", max_iter, 1)
     if not isinstance(init, torch.Tensor) and not (isinstance(init, str) and init in INITS):
         raise ValueError(f"{name}: init must be one of {INITS} or a float32 [n_clusters, width] tensor, got {init!r}")
     return int(n_clusters), int(max_iter)
@@ -101,8 +97,6 @@ def lloyd(h, points, centroids, max_iter):
     """The loop of ``kmeans`` on the context ``h``: a step on the current centroids, stop when no label changed,
     else the update; one read-back (the three statistics) per iteration.  Every output refers to the centroids of
     the last step."""
-    from .streaming import _Scratch
-    lib = _lib.load()
     N, width, G = int(points.shape[0]), int(points.shape[1]), int(centroids.shape[0])
     dev = points.device
     labels = [torch.empty(N, dtype=torch.int32, device=dev) for _ in range(2)]
@@ -110,17 +104,14 @@ def lloyd(h, points, centroids, max_iter):
     sums = torch.empty(G, width, dtype=torch.float64, device=dev)
     counts = torch.empty(G, dtype=torch.int64, device=dev)
     stats = torch.empty(3, dtype=torch.float64, device=dev)
-    scratch = _Scratch(dev)                         # named: it owns the buffer every step of the loop is handed
-    ptr, nbytes = scratch.fit(lib.spmf_kmeans_scratch_bytes(h, N, G, width))
-    stream = torch.cuda.current_stream(dev).cuda_stream
+    scratch = (_lib.Scratch(dev), "spmf_kmeans_scratch_bytes", N, G, width)     # one buffer for every step
     centroids = centroids.contiguous()
     converged, n_iter, st = False, 0, None
     for it in range(max_iter):
         cur, prev = labels[it & 1], labels[(it & 1) ^ 1]
-        _lib.check(h, lib.spmf_kmeans_step(
-            h, points.data_ptr(), N, width, centroids.data_ptr(), G, prev.data_ptr() if it else None,
-            cur.data_ptr(), dist.data_ptr(), sums.data_ptr(), counts.data_ptr(), stats.data_ptr(), ptr, nbytes,
-            stream), "spmf_kmeans_step")
+        _lib.call(h, "spmf_kmeans_step", points.data_ptr(), N, width, centroids.data_ptr(), G,
+                  prev.data_ptr() if it else None, cur.data_ptr(), dist.data_ptr(), sums.data_ptr(),
+                  counts.data_ptr(), stats.data_ptr(), device=dev, scratch=scratch)
         st = stats.tolist()                         # the iteration's one read-back
         n_iter = it + 1
         if st[1] == 0:

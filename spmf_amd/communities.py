@@ -40,6 +40,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import _args, _lib
+
 SHIFT = 24                 # wq = rint(w 2^SHIFT)
 GROUP_LEN = 64             # include/spmf_hip.h SPMF_MOVE_GROUP_LEN: longer rows go on the sweep's long_rows list
 M2_LIMIT = 2 ** 62
@@ -49,20 +51,10 @@ STALE_SWEEPS = 4           # sweeps in a row without a new best after which a le
 # ---- arguments ---------------------------------------------------------------------------------------------------
 def check_args(name, resolution, max_levels, max_sweeps, tol):
     """The arguments of ``solve`` / ``communities`` that need no graph -> (gamma, max_levels, max_sweeps, tol)."""
-    def integer(what, v, lo, hi):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
-            raise ValueError(f"{name}: {what} must be an integer in {lo}..{hi}, got {v!r}")
-        return int(v)
-
-    def number(what, v, positive):
-        ok = isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
-        if not ok or not np.isfinite(v) or v < 0 or (positive and v <= 0):
-            raise ValueError(f"{name}: {what} must be a finite number {'> 0' if positive else '>= 0'}, got {v!r}")
-        return float(v)
-    gamma = number("resolution", resolution, True)
-    max_levels = integer("max_levels", max_levels, 1, 2 ** 31 - 1)
-    max_sweeps = integer("max_sweeps", max_sweeps, 1, 2 ** 31 - 1)
-    return gamma, max_levels, max_sweeps, number("tol", tol, False)
+    gamma = _args.number(name, "resolution", resolution, positive=True)
+    max_levels = _args.integer(name, "max_levels", max_levels, 1, 2 ** 31 - 1)
+    max_sweeps = _args.integer(name, "max_sweeps", max_sweeps, 1, 2 ** 31 - 1)
+    return gamma, max_levels, max_sweeps, _args.number(name, "tol", tol)
 
 
 # ---- integers ------------------------------------------------------------------------------------------------------
@@ -256,11 +248,8 @@ class LibraryOps:
     The list of long rows is made once per level from indptr."""
 
     def __init__(self, lib, handle, indptr, indices, weights):
-        from . import _lib
-        self._check = _lib.check
         self.lib, self.h = lib, handle
         self.device = indptr.device
-        self.stream = torch.cuda.current_stream(self.device).cuda_stream
         self._graph = (indptr.contiguous(), indices.contiguous(), quantise(weights).contiguous())
 
     def edges(self):
@@ -273,10 +262,10 @@ class LibraryOps:
     def move(self, labels, tot, gamma, m2, direction):
         out = torch.empty_like(labels)
         n_long = int(self.long.numel())
-        self._check(self.h, self.lib.spmf_graph_move(
-            self.h, self.n, int(self.g[1].numel()), self.g[0].data_ptr(), self.g[1].data_ptr(), self.g[2].data_ptr(),
-            labels.data_ptr(), tot.data_ptr(), self.long.data_ptr() if n_long else None, n_long, float(gamma),
-            int(m2), int(direction), out.data_ptr(), self.stream), "spmf_graph_move")
+        _lib.call(self.h, "spmf_graph_move", self.n, int(self.g[1].numel()), self.g[0].data_ptr(),
+                  self.g[1].data_ptr(), self.g[2].data_ptr(), labels.data_ptr(), tot.data_ptr(),
+                  self.long.data_ptr() if n_long else None, n_long, float(gamma), int(m2), int(direction),
+                  out.data_ptr(), device=self.device)
         return out
 
 

@@ -3,8 +3,8 @@
 // Host-side orchestration only: argument checks, workspace carving, stream
 // ordered launches.  No device allocation, no host<->device copies, no
 // synchronisation on the hot path (timing taps excepted, off by default).
-// The step is api_step.hip, the streaming calls api_stream.hip, the collectives api_comm.hip, the VI kernels'
-// entries api_vi.hip; ctx.h is what they share.
+// The step is api_step.hip, the streaming calls api_stream.hip, the calls on rows and graphs as given api_points.hip
+// and api_graph.hip, the collectives api_comm.hip, the VI kernels' entries api_vi.hip; ctx.h is what they share.
 #include <stdio.h>
 #include <stdlib.h>
 

@@ -1,19 +1,66 @@
-// api_stream.hip -- the streaming calls behind the C-ABI (include/spmf_hip.h): the draw stage, its consumers'
-// entries, spmf_knn, spmf_kmeans_step, spmf_silhouette, spmf_graph_layout, spmf_graph_transform and the graph
-// products of spectral.hip (spmf_graph_scale, spmf_graph_spmm, spmf_block_gram, spmf_block_rotate) and the sweep of
-// graph_move.hip (spmf_graph_move).  Host-side orchestration only (ctx.h).
-#include <stdlib.h>
-
+// api_stream.hip -- the streaming calls behind the C-ABI (include/spmf_hip.h): the draw stage and its consumers'
+// entries, spmf_embed_rows included.  The calls on rows and graphs as given are api_points.hip and api_graph.hip;
+// the scratch and launch helpers they share with the entries here are defined first.  Host-side orchestration
+// only (ctx.h).
 #include "ctx.h"
 
 using namespace spmf;
+
+namespace spmf {
+
+int scratch_too_small(spmf_ctx* c, const char* fn, size_t need, size_t have, const std::string& detail) {
+  return fail(c, SPMF_E_WORKSPACE, std::string(fn) + ": scratch too small: need " + std::to_string(need) +
+      " bytes for " + detail + ", have " + std::to_string(have));
+}
+
+int launched(spmf_ctx* c, bool ok, const char* no_kernel) {
+  if (!ok) return fail(c, SPMF_E_UNSUPPORTED, no_kernel);
+  HIPCHK(c, hipGetLastError());
+  return SPMF_OK;
+}
+
+int device_cus(const spmf_ctx* c) {
+  int n = 0;
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || n < 1) {
+    (void)hipGetLastError();
+    n = 256;   // no device to ask (a host-only caller sizing a scratch): an MI355X
+  }
+  return n;
+}
+
+// Column slices (gridDim.y) of the select launch.  A workgroup owns 64 rows and sweeps the column blocks of its
+// slice, and two workgroups are resident per CU at the widest candidate buffer: with fewer than 2 * CUs row
+// blocks the columns are split until the grid has that many workgroups -- never into more slices than column
+// blocks or than the merge kernel holds (kTopkMaxSlices) -- and the count is then lowered to the slices that
+// ceil(blocks / slices) blocks each leave non-empty.  At 2 * CUs row blocks and above: one slice, no merge.
+int topk_slices(int64_t n_rows, int D, int cus) {
+  const int64_t rb = (n_rows + 63) / 64, cb = ((int64_t)D + 63) / 64;
+  if (rb < 1 || rb >= 2 * (int64_t)cus) return 1;
+  int64_t nsl = (2 * (int64_t)cus + rb - 1) / rb;
+  if (nsl > kTopkMaxSlices) nsl = kTopkMaxSlices;
+  if (nsl > cb) nsl = cb;
+  const int64_t per = (cb + nsl - 1) / nsl;
+  return (int)((cb + per - 1) / per);
+}
+
+void group_order_carve(Arena& a, int64_t rows, int G, int64_t chunks, int64_t NB, GroupOrder& o) {
+  const size_t nG = G;
+  o.tbl = a.take<int32_t>((size_t)chunks * nG);
+  o.lrank = a.take<int32_t>((size_t)rows);
+  o.cnt = a.take<int32_t>(nG);
+  o.boff = a.take<int32_t>(nG + 1);
+  o.fincl = a.take<int32_t>(nG);
+  o.rec = a.take<int4>((size_t)NB);
+  o.perm = a.take<int32_t>((size_t)NB * 64);
+}
+
+}  // namespace spmf
 
 extern "C" {
 
 // ---- the draw stage of the streaming calls ---------------------------------------------------
 // spmf_waic_accumulate (and its _cols form), spmf_topk_rows, spmf_score_cells, spmf_rank_cells, spmf_predict_columns,
-// spmf_toprows_columns, spmf_group_sums, spmf_set_scores and spmf_embed_rows are one stage and a consumer each (spmf_knn, at the end of the section,
-// takes rows as given and shares the scratch and launch helpers only).
+// spmf_toprows_columns, spmf_group_sums, spmf_set_scores and spmf_embed_rows are one stage and a consumer each.
 // The stage: for S draws the per-draw tables (prep) and the encoded rows z[S,B,KP] go into the caller's scratch;
 // the consumer kernel then reads z, V' and phi of every draw (kernels.h DrawTables).  The context's workspace is
 // not used, so a step that is bound (or half way: spmf_step_begin .. spmf_step_end) keeps everything it has.
@@ -40,20 +87,8 @@ static size_t draw_tables_bytes(const spmf_ctx* c, int64_t rows, int S) {
   return a.used;
 }
 
-// The SPMF_E_WORKSPACE failure of a call `fn` whose scratch holds `have` bytes where its layout takes `need` for
-// the shape `detail` ("rows=70 S=2").
-static int scratch_too_small(spmf_ctx* c, const char* fn, size_t need, size_t have, const std::string& detail) {
-  return fail(c, SPMF_E_WORKSPACE, std::string(fn) + ": scratch too small: need " + std::to_string(need) +
-      " bytes for " + detail + ", have " + std::to_string(have));
-}
 static std::string rows_S(const spmf_counts* ct, int S) {
   return "rows=" + std::to_string((long long)ct->n_rows) + " S=" + std::to_string(S);
-}
-// The end of every entry: `ok` is what its launcher returned, `no_kernel` the entry's text for false.
-static int launched(spmf_ctx* c, bool ok, const char* no_kernel) {
-  if (!ok) return fail(c, SPMF_E_UNSUPPORTED, no_kernel);
-  HIPCHK(c, hipGetLastError());
-  return SPMF_OK;
 }
 
 // What every streaming call `fn` checks before anything is launched: S in min_S..65535, the shared pointers, the
@@ -137,28 +172,6 @@ int spmf_waic_accumulate_cols(spmf_ctx* c, const spmf_counts* ct, int S, const f
 }
 
 // ---- streaming per-row top-k of the posterior predictive mean (topk.hip) ---------------------
-static int device_cus(const spmf_ctx* c) {
-  int n = 0;
-  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || n < 1) {
-    (void)hipGetLastError();
-    n = 256;   // no device to ask (a host-only caller sizing a scratch): an MI355X
-  }
-  return n;
-}
-// Column slices (gridDim.y) of the select launch.  A workgroup owns 64 rows and sweeps the column blocks of its
-// slice, and two workgroups are resident per CU at the widest candidate buffer: with fewer than 2 * CUs row
-// blocks the columns are split until the grid has that many workgroups -- never into more slices than column
-// blocks or than the merge kernel holds (kTopkMaxSlices) -- and the count is then lowered to the slices that
-// ceil(blocks / slices) blocks each leave non-empty.  At 2 * CUs row blocks and above: one slice, no merge.
-static int topk_slices(int64_t n_rows, int D, int cus) {
-  const int64_t rb = (n_rows + 63) / 64, cb = ((int64_t)D + 63) / 64;
-  if (rb < 1 || rb >= 2 * (int64_t)cus) return 1;
-  int64_t nsl = (2 * (int64_t)cus + rb - 1) / rb;
-  if (nsl > kTopkMaxSlices) nsl = kTopkMaxSlices;
-  if (nsl > cb) nsl = cb;
-  const int64_t per = (cb + nsl - 1) / nsl;
-  return (int)((cb + per - 1) / per);
-}
 // Scratch of rank_cells, and the head of top-k's: the draw tables and the bitmap of the stored cells of `rows` rows,
 // a bit per column in 32-bit words (topk_mark_kernel), whatever the call's flags; `slices` of the select launch
 static size_t stored_words(const spmf_ctx* c, int64_t rows) { return (size_t)rows * ((c->D + 31) / 32); }
@@ -345,8 +358,8 @@ int spmf_predict_columns(spmf_ctx* c, const spmf_counts* ct, int S, const float*
 // ---- streaming per-column top-k rows of the posterior predictive mean (toprows.hip) -------------
 // Scratch of one call: stored_layout (the draw tables and the bitmap, whatever the flags), the compacted tables of
 // a listed panel sized for n_cols (panel_tables), and the row slices' results (sized for k = kTopkMaxK: the size
-// does not depend on the call's k or flags).  The slices are topk_slices with the roles swapped, as in knn_layout:
-// the keys are the column blocks of the panel, the candidates the row blocks.
+// does not depend on the call's k or flags).  The slices are topk_slices with the roles swapped, as in knn_layout
+// (api_points.hip): the keys are the column blocks of the panel, the candidates the row blocks.
 static void toprows_layout(Arena& a, const spmf_ctx* c, int64_t rows, int S, int n_cols, Tables& T, TopRowsArgs& ra) {
   int topk_own;   // (the column slices of a top-k launch over these rows: not this call's)
   stored_layout(a, c, rows, S, T, ra.stored, topk_own);
@@ -410,15 +423,9 @@ int spmf_toprows_columns(spmf_ctx* c, const spmf_counts* ct, int S, const float*
 constexpr int32_t kGroupMaxGroups = 1 << 24;
 static void groups_layout(Arena& a, const spmf_ctx* c, int64_t rows, int S, int G, int C, Tables& T, GroupArgs& ga) {
   const GroupGeom q = group_geom(rows, S, G, C);
-  const size_t KP = c->KP, nS = S, nG = G, NB = (size_t)q.NB;
+  const size_t KP = c->KP, nS = S, NB = (size_t)q.NB;
   draw_tables(a, c, rows, S, T);
-  ga.tbl = a.take<int32_t>((size_t)q.chunks * nG);
-  ga.lrank = a.take<int32_t>((size_t)rows);
-  ga.cnt = a.take<int32_t>(nG);
-  ga.boff = a.take<int32_t>(nG + 1);
-  ga.fincl = a.take<int32_t>(nG);
-  ga.rec = a.take<int4>(NB);
-  ga.perm = a.take<int32_t>(NB * 64);
+  group_order_carve(a, rows, G, q.chunks, q.NB, ga.ord);
   ga.zs = a.take<float>(nS * NB * 64 * KP);
   panel_tables(a, c, S, C, ga.Vc, ga.phic, ga.ctc);
   ga.part = a.take<double>(q.part_bytes / sizeof(double));   // (whole doubles: group_geom)
@@ -553,458 +560,6 @@ int spmf_embed_rows(spmf_ctx* c, const spmf_counts* ct, int S, const float* cons
   rc = draw_stage(c, "embed_rows", ct, S, params, eta, T, st, dt);
   if (rc) return rc;
   launch_embed(dt, c->K, mean_out, sd_out, st);   // (one kernel for every K)
-  return launched(c, true, "");
-}
-
-// ---- exact k nearest rows (knn.hip) -----------------------------------------------------------
-// Scratch of one call: the working rows of the reference set and of the queries (sized for both, whether or not
-// the call passes one array as both), the biases, the centre and its per-block partial sums, and the slices'
-// results (sized for k = kTopkMaxK: the size does not depend on the call's k).
-static int knn_padded(int row_len) {
-  int kp = 4;
-  while (kp < row_len) kp *= 2;
-  return kp;
-}
-// The shape (the padded row length; the reference slices of the select launch, where the queries take the place
-// of top-k's rows and the reference rows that of its columns) and the scratch of a call, all into ka
-// (part_slots >= 0: the slots of the slices' results to carve instead of knn's own count -- kmeans_layout)
-static void knn_layout(Arena& a, const spmf_ctx* c, int64_t n_query, int64_t n_ref, int row_len, KnnArgs& ka,
-    int64_t part_slots = -1) {
-  ka.n_query = n_query; ka.n_ref = n_ref; ka.row_len = row_len;
-  ka.KP = knn_padded(row_len);
-  ka.slices = n_ref > 0 ? topk_slices(n_query, (int)n_ref, device_cus(c)) : 1;
-  const size_t nq = n_query, nr = n_ref, KP = ka.KP;
-  ka.rw = a.take<float>(nr * KP);
-  ka.bias = a.take<float>(nr);
-  ka.qw = a.take<float>(nq * KP);
-  ka.cpart = a.take<float>(kKnnCentreBlocks * KP);
-  ka.ccnt = a.take<int32_t>(kKnnCentreBlocks);
-  ka.centre = a.take<float>(KP);
-  const size_t part = part_slots >= 0 ? (size_t)part_slots : ka.slices > 1 ? (size_t)ka.slices * nq * kTopkMaxK : 0;
-  ka.part_idx = a.take<int32_t>(part);
-  ka.part_score = a.take<float>(part);
-}
-
-size_t spmf_knn_scratch_bytes(const spmf_ctx* c, int64_t n_query, int64_t n_ref, int row_len) {
-  if (!c || n_query < 0 || n_ref < 0 || n_ref > 0x7fffffffLL || row_len < 1 || row_len > 256) return 0;
-  Arena a;
-  KnnArgs ka{};
-  knn_layout(a, c, n_query, n_ref, row_len, ka);
-  return a.used;
-}
-
-// SPMF_KNN_TILE = 0 | 1 picks the tile function of the select kernel (knn.hip); both give the same bits
-static int knn_tile() {
-  const char* e = getenv("SPMF_KNN_TILE");
-  return e && e[0] == '1' ? 1 : (e && e[0] == '0' ? 0 : kKnnDefaultTile);
-}
-
-int spmf_knn(spmf_ctx* c, const float* q, int64_t n_query, const float* r, int64_t n_ref, int row_len, int k,
-    unsigned flags, int64_t self_offset, int32_t* idx_out, float* dist_out, void* scratch, size_t scratch_bytes,
-    void* stream) {
-  if (!c) return SPMF_E_ARG;
-  if (n_query < 0 || n_ref < 0) return fail(c, SPMF_E_ARG, "knn: n_query and n_ref must not be negative");
-  if (n_ref > 0x7fffffffLL) return fail(c, SPMF_E_ARG, "knn: n_ref above 2^31 - 1 (the indices are int32)");
-  if (n_query > ((int64_t)1 << 31) - 64) return fail(c, SPMF_E_ARG, "knn: too many queries in one call");
-  if (row_len < 1 || row_len > 256) return fail(c, SPMF_E_ARG, "knn: row_len must be in 1..256");
-  if (k < 1 || k > kTopkMaxK) return fail(c, SPMF_E_ARG, "knn: k must be in 1..64");
-  if (flags & ~1u) return fail(c, SPMF_E_ARG, "knn: unknown flag (bit 0: cosine)");
-  if (self_offset < -1) return fail(c, SPMF_E_ARG, "knn: self_offset must be -1 (none) or the reference row of "
-      "query 0");
-  if (!scratch) return fail(c, SPMF_E_ARG, "knn: null argument");
-  if ((n_query > 0 && (!q || !idx_out || !dist_out)) || (n_ref > 0 && !r)) return fail(c, SPMF_E_ARG,
-      "knn: null argument");
-  if ((uintptr_t)scratch & 255) return fail(c, SPMF_E_ARG, "knn: scratch must be 256-byte aligned");
-  KnnArgs ka{};
-  Arena a(scratch, scratch_bytes);
-  knn_layout(a, c, n_query, n_ref, row_len, ka);
-  if (!a.fits()) return scratch_too_small(c, "knn", a.used, scratch_bytes,
-      "n_query=" + std::to_string((long long)n_query) + " n_ref=" + std::to_string((long long)n_ref) + " row_len=" +
-      std::to_string(row_len));
-  if (n_query == 0) return SPMF_OK;
-  ka.k = k;
-  ka.cosine = (flags & 1u) != 0; ka.tile = knn_tile(); ka.self_offset = self_offset;
-  ka.q = q; ka.r = r;
-  if (q == r && n_query == n_ref) ka.qw = ka.rw;
-  ka.idx = idx_out; ka.dist = dist_out;
-  return launched(c, launch_knn(ka, (hipStream_t)stream), "knn: no kernel for this row_len / k");
-}
-
-// ---- one Lloyd step of k-means (kmeans.hip behind knn.hip and groups.hip's ordering) -----------
-// Scratch of one call: knn's carve for the rows as queries and the centroids as reference set, the refined
-// candidates [rows][4], the ordering of the rows by label (launch_group_order), the segments' partial sums and the
-// statistics' partial sums (kernels.h kmeans_geom bounds them).  knn's slices drop to one as the rows grow, and
-// their results with them; here they are carved at their bound over all row counts, slices * rows <= 64 * (2 CUs +
-// row blocks) with at most 4 candidates each, so that the size is non-decreasing in the rows.
-constexpr int32_t kKmeansMaxClusters = 65536;
-constexpr int kKmeansCand = 4;
-static void kmeans_layout(Arena& a, const spmf_ctx* c, int64_t rows, int G, int row_len, KnnArgs& ka, KmeansArgs& ma) {
-  const KmeansGeom q = kmeans_geom(rows, G);
-  const size_t nr = rows, nG = G, NB = (size_t)q.NB;
-  knn_layout(a, c, rows, G, row_len, ka, 64 * (2 * (int64_t)device_cus(c) + (rows + 63) / 64) * kKmeansCand);
-  ka.k = ma.kc = G < kKmeansCand ? G : kKmeansCand;
-  ka.idx = a.take<int32_t>(nr * kKmeansCand);
-  ka.dist = a.take<float>(nr * kKmeansCand);
-  ma.tbl = a.take<int32_t>((size_t)q.chunks * nG);
-  ma.lrank = a.take<int32_t>(nr);
-  ma.cnt = a.take<int32_t>(nG);
-  ma.boff = a.take<int32_t>(nG + 1);
-  ma.fincl = a.take<int32_t>(nG);
-  ma.rec = a.take<int4>(NB);
-  ma.perm = a.take<int32_t>(NB * 64);
-  ma.part = a.take<double>((size_t)q.nseg * row_len);
-  ma.spart = a.take<double>((size_t)q.sblocks * 3);
-}
-static bool kmeans_shape_ok(int64_t n_rows, int32_t G, int row_len) {
-  return n_rows >= 0 && n_rows <= ((int64_t)1 << 31) - 64 && G >= 1 && G <= kKmeansMaxClusters && row_len >= 1 &&
-      row_len <= 256;
-}
-
-size_t spmf_kmeans_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int32_t n_clusters, int row_len) {
-  if (!c || !kmeans_shape_ok(n_rows, n_clusters, row_len)) return 0;
-  Arena a;
-  KnnArgs ka{};
-  KmeansArgs ma{};
-  kmeans_layout(a, c, n_rows, n_clusters, row_len, ka, ma);
-  return a.used;
-}
-
-int spmf_kmeans_step(spmf_ctx* c, const float* x, int64_t n_rows, int row_len, const float* centroids,
-    int32_t n_clusters, const int32_t* prev_labels, int32_t* labels_out, float* dist_out, double* sums_out,
-    int64_t* counts_out, double* stats_out, void* scratch, size_t scratch_bytes, void* stream) {
-  if (!c) return SPMF_E_ARG;
-  const std::string f = "kmeans_step: ";
-  if (n_clusters < 1 || n_clusters > kKmeansMaxClusters) return fail(c, SPMF_E_ARG, f + "n_clusters must be in "
-      "1..65536");
-  if (row_len < 1 || row_len > 256) return fail(c, SPMF_E_ARG, f + "row_len must be in 1..256");
-  if (n_rows < 0 || n_rows > ((int64_t)1 << 31) - 64) return fail(c, SPMF_E_ARG, f + "n_rows must be in "
-      "0..2^31 - 64");
-  if (prev_labels && prev_labels == labels_out) return fail(c, SPMF_E_ARG, f + "prev_labels must not be labels_out");
-  if (!scratch) return fail(c, SPMF_E_ARG, f + "null argument");
-  if (!sums_out || !counts_out || !stats_out || (n_rows > 0 && (!x || !centroids || !labels_out))) return fail(c,
-      SPMF_E_ARG, f + "null argument");
-  if ((uintptr_t)scratch & 255) return fail(c, SPMF_E_ARG, f + "scratch must be 256-byte aligned");
-  KnnArgs ka{};
-  KmeansArgs ma{};
-  Arena a(scratch, scratch_bytes);
-  kmeans_layout(a, c, n_rows, n_clusters, row_len, ka, ma);
-  if (!a.fits()) return scratch_too_small(c, "kmeans_step", a.used, scratch_bytes,
-      "n_rows=" + std::to_string((long long)n_rows) + " n_clusters=" + std::to_string(n_clusters) + " row_len=" +
-      std::to_string(row_len));
-  hipStream_t st = (hipStream_t)stream;
-  if (n_rows == 0) {
-    HIPCHK(c, hipMemsetAsync(sums_out, 0, (size_t)n_clusters * row_len * sizeof(double), st));
-    HIPCHK(c, hipMemsetAsync(counts_out, 0, (size_t)n_clusters * sizeof(int64_t), st));
-    HIPCHK(c, hipMemsetAsync(stats_out, 0, 3 * sizeof(double), st));
-    return SPMF_OK;
-  }
-  // the assignment: spmf_knn's launches with q = x, r = centroids, k = min(4, G), Euclidean, no self
-  ka.cosine = false; ka.tile = knn_tile(); ka.self_offset = -1;
-  ka.q = x; ka.r = centroids;
-  if (!launch_knn(ka, st)) return fail(c, SPMF_E_UNSUPPORTED, f + "no kernel for this row_len");
-  ma.n_rows = n_rows; ma.row_len = row_len; ma.n_clusters = n_clusters;
-  ma.x = x; ma.cand_idx = ka.idx; ma.cand_dist = ka.dist; ma.prev = prev_labels;
-  ma.labels = labels_out; ma.dist = dist_out; ma.sums = sums_out; ma.counts = counts_out; ma.stats = stats_out;
-  launch_kmeans(ma, st);
-  return launched(c, true, "");
-}
-
-// ---- the silhouette of labelled rows (silhouette.hip behind groups.hip's ordering) -------------
-// Scratch of one call: the effective labels, the ordering of the members by label (launch_group_order), the
-// working rows and biases in that order, the centre with its partial sums, and the blocks' sums of s (kernels.h
-// silhouette_geom bounds the blocks).  Every region grows with the rows.
-static void silhouette_layout(Arena& a, int64_t rows, int G, int row_len, SilhouetteArgs& sa) {
-  const SilhouetteGeom q = silhouette_geom(rows, G);
-  sa.n_rows = rows; sa.row_len = row_len; sa.n_clusters = G;
-  sa.KP = knn_padded(row_len);
-  const size_t nr = rows, nG = G, NB = (size_t)q.NB, KP = sa.KP;
-  sa.eff = a.take<int32_t>(nr);
-  sa.tbl = a.take<int32_t>((size_t)q.chunks * nG);
-  sa.lrank = a.take<int32_t>(nr);
-  sa.cnt = a.take<int32_t>(nG);
-  sa.boff = a.take<int32_t>(nG + 1);
-  sa.fincl = a.take<int32_t>(nG);
-  sa.rec = a.take<int4>(NB);
-  sa.perm = a.take<int32_t>(NB * 64);
-  sa.w = a.take<float>(NB * 64 * KP);
-  sa.bias = a.take<float>(NB * 64);
-  sa.cpart = a.take<double>((size_t)kSilCentreBlocks * KP);
-  sa.ccnt = a.take<int32_t>(kSilCentreBlocks);
-  sa.centre = a.take<float>(KP);
-  sa.spart = a.take<double>(NB);
-}
-
-size_t spmf_silhouette_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int32_t n_clusters, int row_len) {
-  if (!c || !kmeans_shape_ok(n_rows, n_clusters, row_len)) return 0;
-  Arena a;
-  SilhouetteArgs sa{};
-  silhouette_layout(a, n_rows, n_clusters, row_len, sa);
-  return a.used;
-}
-
-int spmf_silhouette(spmf_ctx* c, const float* x, int64_t n_rows, int row_len, const int32_t* labels,
-    int32_t n_clusters, unsigned flags, float* sil_out, float* a_out, float* b_out, int32_t* nearest_out,
-    double* cluster_sum_out, int64_t* counts_out, void* scratch, size_t scratch_bytes, void* stream) {
-  if (!c) return SPMF_E_ARG;
-  const std::string f = "silhouette: ";
-  if (n_clusters < 1 || n_clusters > kKmeansMaxClusters) return fail(c, SPMF_E_ARG, f + "n_clusters must be in "
-      "1..65536");
-  if (row_len < 1 || row_len > 256) return fail(c, SPMF_E_ARG, f + "row_len must be in 1..256");
-  if (n_rows < 0 || n_rows > ((int64_t)1 << 31) - 64) return fail(c, SPMF_E_ARG, f + "n_rows must be in "
-      "0..2^31 - 64");
-  if (flags & ~1u) return fail(c, SPMF_E_ARG, f + "unknown flag (bit 0: cosine)");
-  if (!scratch) return fail(c, SPMF_E_ARG, f + "null argument");
-  if (!cluster_sum_out || !counts_out || (n_rows > 0 && (!x || !labels || !sil_out))) return fail(c, SPMF_E_ARG,
-      f + "null argument");
-  if ((uintptr_t)scratch & 255) return fail(c, SPMF_E_ARG, f + "scratch must be 256-byte aligned");
-  SilhouetteArgs sa{};
-  Arena a(scratch, scratch_bytes);
-  silhouette_layout(a, n_rows, n_clusters, row_len, sa);
-  if (!a.fits()) return scratch_too_small(c, "silhouette", a.used, scratch_bytes,
-      "n_rows=" + std::to_string((long long)n_rows) + " n_clusters=" + std::to_string(n_clusters) + " row_len=" +
-      std::to_string(row_len));
-  hipStream_t st = (hipStream_t)stream;
-  if (n_rows == 0) {
-    HIPCHK(c, hipMemsetAsync(cluster_sum_out, 0, (size_t)n_clusters * sizeof(double), st));
-    HIPCHK(c, hipMemsetAsync(counts_out, 0, (size_t)n_clusters * sizeof(int64_t), st));
-    return SPMF_OK;
-  }
-  sa.cosine = (flags & 1u) != 0;
-  sa.x = x; sa.labels = labels;
-  sa.sil = sil_out; sa.a = a_out; sa.b = b_out; sa.nearest = nearest_out;
-  sa.cluster_sum = cluster_sum_out; sa.counts = counts_out;
-  return launched(c, launch_silhouette(sa, st), "silhouette: no kernel for this row_len");
-}
-
-// ---- the epochs of a 2-D graph layout (graph_layout.hip) ---------------------------------------
-// Scratch of one call: the two position buffers the epochs alternate between; the first takes the start.
-static bool graph_layout_rows_ok(int64_t n_rows) { return n_rows >= 0 && n_rows <= ((int64_t)1 << 31) - 64; }
-static void graph_layout_carve(Arena& a, int64_t rows, GraphLayoutArgs& ga) {
-  const size_t n = rows > 0 ? (size_t)rows : 1;
-  ga.buf[0] = a.take<float2>(n);
-  ga.buf[1] = a.take<float2>(n);
-}
-
-size_t spmf_graph_layout_scratch_bytes(const spmf_ctx* c, int64_t n_rows) {
-  if (!c || !graph_layout_rows_ok(n_rows)) return 0;
-  Arena a;
-  GraphLayoutArgs ga{};
-  graph_layout_carve(a, n_rows, ga);
-  return a.used;
-}
-
-int spmf_graph_layout(spmf_ctx* c, int64_t n_rows, int64_t nnz, const int64_t* indptr, const int32_t* indices,
-    const float* weights, const float* y_in, float* y_out, int epoch0, int n_epochs, int total_epochs, double lr,
-    double a, double b, double repulsion, double negative_rate, int n_negatives, uint64_t seed, void* scratch,
-    size_t scratch_bytes, void* stream) {
-  if (!c) return SPMF_E_ARG;
-  const std::string f = "graph_layout: ";
-  auto weight_ok = [](double v) { return v >= 0.0 && v <= 3.0e38; };          // finite, not negative, an fp32
-  if (!graph_layout_rows_ok(n_rows)) return fail(c, SPMF_E_ARG, f + "n_rows must be in 0..2^31 - 64");
-  if (nnz < 0) return fail(c, SPMF_E_ARG, f + "nnz is negative");
-  if (n_negatives < 1 || n_negatives > 64) return fail(c, SPMF_E_ARG, f + "n_negatives must be in 1..64");
-  if (epoch0 < 0 || n_epochs < 0 || (int64_t)epoch0 + n_epochs > (int64_t)total_epochs) return fail(c, SPMF_E_ARG,
-      f + "epochs: epoch0 >= 0, n_epochs >= 0 and epoch0 + n_epochs <= total_epochs must hold");
-  if (!(a > 0.0) || !(b > 0.0) || !(a <= 3.0e38) || !(b <= 3.0e38)) return fail(c, SPMF_E_ARG, f + "a and b must be "
-      "positive and finite");
-  if (!weight_ok(lr) || !weight_ok(repulsion) || !weight_ok(negative_rate)) return fail(c, SPMF_E_ARG, f + "lr, "
-      "repulsion and negative_rate must be finite and not negative");
-  if (n_rows > 0 && (!indptr || !y_in || !y_out || (nnz > 0 && (!indices || !weights)))) return fail(c, SPMF_E_ARG,
-      f + "null argument");
-  if (!scratch) return fail(c, SPMF_E_ARG, f + "null argument");
-  if ((uintptr_t)scratch & 255) return fail(c, SPMF_E_ARG, f + "scratch must be 256-byte aligned");
-  GraphLayoutArgs ga{};
-  Arena ar(scratch, scratch_bytes);
-  graph_layout_carve(ar, n_rows, ga);
-  if (!ar.fits()) return scratch_too_small(c, "graph_layout", ar.used, scratch_bytes,
-      "n_rows=" + std::to_string((long long)n_rows));
-  if (n_rows == 0) return SPMF_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const size_t bytes = (size_t)n_rows * sizeof(float2);
-  if (n_epochs == 0) {
-    if (y_out != y_in) HIPCHK(c, hipMemcpyAsync(y_out, y_in, bytes, hipMemcpyDeviceToDevice, st));
-    return SPMF_OK;
-  }
-  // the prologue: the start goes into the first buffer, so no epoch reads y_in or y_out (they may be one)
-  HIPCHK(c, hipMemcpyAsync(ga.buf[0], y_in, bytes, hipMemcpyDeviceToDevice, st));
-  ga.n_rows = n_rows; ga.nnz = nnz;
-  ga.indptr = indptr; ga.indices = indices; ga.weights = weights;
-  ga.y_out = (float2*)y_out;
-  ga.epoch0 = epoch0; ga.n_epochs = n_epochs; ga.total_epochs = total_epochs; ga.n_negatives = n_negatives;
-  ga.lr = lr;
-  ga.a = (float)a; ga.b = (float)b;
-  ga.neg2b = (float)(-2.0 * b);
-  ga.two_gamma_b = (float)(2.0 * repulsion * b);
-  ga.rate_over_m = (float)(negative_rate / (double)n_negatives);
-  ga.seed_lo = (uint32_t)seed; ga.seed_hi = (uint32_t)(seed >> 32);
-  launch_graph_layout(ga, st);
-  return launched(c, true, "");
-}
-
-// ---- new rows on a fitted 2-D layout (graph_transform.hip) --------------------------------------
-// No scratch: the one launch keeps a row's state in registers.
-int spmf_graph_transform(spmf_ctx* c, int64_t n_query, int k, const int32_t* idx, const float* w,
-    const float* y_ref, int64_t n_ref, const float* y_in, float* y_out, int64_t row0, int epoch0, int n_epochs,
-    int total_epochs, double lr, double a, double b, double repulsion, double negative_rate, int n_negatives,
-    uint64_t seed, void* stream) {
-  if (!c) return SPMF_E_ARG;
-  const std::string f = "graph_transform: ";
-  auto weight_ok = [](double v) { return v >= 0.0 && v <= 3.0e38; };          // finite, not negative, an fp32
-  if (k < 1 || k > 64) return fail(c, SPMF_E_ARG, f + "k must be in 1..64");
-  if (n_negatives < 1 || n_negatives > 64) return fail(c, SPMF_E_ARG, f + "n_negatives must be in 1..64");
-  if (n_query < 0) return fail(c, SPMF_E_ARG, f + "n_query is negative");
-  if (n_ref < 0 || n_ref > ((int64_t)1 << 31) - 1) return fail(c, SPMF_E_ARG, f + "n_ref must be in 0..2^31 - 1");
-  if (row0 < 0 || row0 > ((int64_t)1 << 32) || n_query > ((int64_t)1 << 32) - row0) return fail(c, SPMF_E_ARG,
-      f + "row0 >= 0 and row0 + n_query <= 2^32 must hold");
-  if (epoch0 < 0 || n_epochs < 0 || (int64_t)epoch0 + n_epochs > (int64_t)total_epochs) return fail(c, SPMF_E_ARG,
-      f + "epochs: epoch0 >= 0, n_epochs >= 0 and epoch0 + n_epochs <= total_epochs must hold");
-  if (!(a > 0.0) || !(b > 0.0) || !(a <= 3.0e38) || !(b <= 3.0e38)) return fail(c, SPMF_E_ARG, f + "a and b must be "
-      "positive and finite");
-  if (!weight_ok(lr) || !weight_ok(repulsion) || !weight_ok(negative_rate)) return fail(c, SPMF_E_ARG, f + "lr, "
-      "repulsion and negative_rate must be finite and not negative");
-  if ((n_query > 0 && (!idx || !w || !y_out)) || (n_ref > 0 && !y_ref)) return fail(c, SPMF_E_ARG,
-      f + "null argument");
-  if (!y_in && epoch0 > 0) return fail(c, SPMF_E_ARG, f + "y_in is null with epoch0 > 0: a continued schedule needs "
-      "its positions");
-  if (n_query == 0) return SPMF_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (n_epochs == 0 && y_in) {
-    if (y_out != y_in) HIPCHK(c, hipMemcpyAsync(y_out, y_in, (size_t)n_query * sizeof(float2),
-                                                hipMemcpyDeviceToDevice, st));
-    return SPMF_OK;
-  }
-  GraphTransformArgs ga{};
-  ga.n_query = n_query; ga.n_ref = n_ref; ga.row0 = row0; ga.k = k;
-  ga.idx = idx; ga.w = w;
-  ga.y_ref = (const float2*)y_ref; ga.y_in = (const float2*)y_in; ga.y_out = (float2*)y_out;
-  ga.epoch0 = epoch0; ga.n_epochs = n_epochs; ga.total_epochs = total_epochs; ga.n_negatives = n_negatives;
-  ga.lr = lr;
-  ga.a = (float)a; ga.b = (float)b;
-  ga.neg2b = (float)(-2.0 * b);
-  ga.two_gamma_b = (float)(2.0 * repulsion * b);
-  ga.rate_over_m = (float)(negative_rate / (double)n_negatives);
-  ga.seed_lo = (uint32_t)seed; ga.seed_hi = (uint32_t)(seed >> 32);
-  launch_graph_transform(ga, st);
-  return launched(c, true, "");
-}
-
-// ---- multiplying by the graph (spectral.hip) ----------------------------------------------------
-// The graph's checks of the two graph entries, graph_layout's; on SPMF_OK `g` is fit to launch on.
-static int graph_csr_check(spmf_ctx* c, const std::string& f, int64_t n_rows, int64_t nnz, const int64_t* indptr,
-    const int32_t* indices, const float* weights, GraphCsr& g) {
-  if (!graph_layout_rows_ok(n_rows)) return fail(c, SPMF_E_ARG, f + "n_rows must be in 0..2^31 - 64");
-  if (nnz < 0) return fail(c, SPMF_E_ARG, f + "nnz is negative");
-  if (n_rows > 0 && (!indptr || (nnz > 0 && (!indices || !weights)))) return fail(c, SPMF_E_ARG, f + "null argument");
-  g.n_rows = n_rows; g.nnz = nnz; g.indptr = indptr; g.indices = indices; g.weights = weights;
-  return SPMF_OK;
-}
-static bool coef_ok(double v) { return v >= -3.0e38 && v <= 3.0e38; }        // finite, an fp32
-
-int spmf_graph_scale(spmf_ctx* c, int64_t n_rows, int64_t nnz, const int64_t* indptr, const int32_t* indices,
-    const float* weights, float* scale, void* stream) {
-  if (!c) return SPMF_E_ARG;
-  const std::string f = "graph_scale: ";
-  GraphCsr g{};
-  const int rc = graph_csr_check(c, f, n_rows, nnz, indptr, indices, weights, g);
-  if (rc) return rc;
-  if (n_rows > 0 && !scale) return fail(c, SPMF_E_ARG, f + "null argument");
-  if (n_rows == 0) return SPMF_OK;
-  launch_graph_scale(g, scale, (hipStream_t)stream);
-  return launched(c, true, "");
-}
-
-int spmf_graph_spmm(spmf_ctx* c, int64_t n_rows, int64_t nnz, const int64_t* indptr, const int32_t* indices,
-    const float* weights, const float* scale, const float* x, const float* z, float* y, double c_s,
-    const double* c_x, double c_z, void* stream) {
-  if (!c) return SPMF_E_ARG;
-  const std::string f = "graph_spmm: ";
-  GraphCsr g{};
-  const int rc = graph_csr_check(c, f, n_rows, nnz, indptr, indices, weights, g);
-  if (rc) return rc;
-  if (!c_x || (n_rows > 0 && (!x || !y))) return fail(c, SPMF_E_ARG, f + "null argument");
-  if (!coef_ok(c_s) || !coef_ok(c_z)) return fail(c, SPMF_E_ARG, f + "c_s and c_z must be finite");
-  BlockCoef cx;
-  for (int k = 0; k < kBlockCols; ++k) {
-    if (!coef_ok(c_x[k])) return fail(c, SPMF_E_ARG, f + "c_x must be finite");
-    cx.cx[k] = (float)c_x[k];
-  }
-  if (n_rows > 0 && !z && c_z != 0.0) return fail(c, SPMF_E_ARG, f + "null argument: z with c_z != 0");
-  if (n_rows > 0 && y == x) return fail(c, SPMF_E_ARG, f + "y aliases x: other rows gather x (y may be z)");
-  if (n_rows == 0) return SPMF_OK;
-  launch_graph_spmm(g, scale, x, c_z != 0.0 ? z : nullptr, y, (float)c_s, cx, (float)c_z, (hipStream_t)stream);
-  return launched(c, true, "");
-}
-
-// ---- modularity moves on the graph (graph_move.hip) ----------------------------------------------
-int spmf_graph_move(spmf_ctx* c, int64_t n_rows, int64_t nnz, const int64_t* indptr, const int32_t* indices,
-    const int64_t* wq, const int32_t* labels_in, const int64_t* tot, const int32_t* long_rows, int64_t n_long,
-    double gamma, int64_t m2, int direction, int32_t* labels_out, void* stream) {
-  if (!c) return SPMF_E_ARG;
-  const std::string f = "graph_move: ";
-  if (!graph_layout_rows_ok(n_rows)) return fail(c, SPMF_E_ARG, f + "n_rows must be in 0..2^31 - 64");
-  if (nnz < 0) return fail(c, SPMF_E_ARG, f + "nnz is negative");
-  if (!graph_layout_rows_ok(n_long)) return fail(c, SPMF_E_ARG, f + "n_long must be in 0..2^31 - 64");
-  if (n_rows > 0 && (!indptr || !labels_in || !tot || !labels_out || (nnz > 0 && (!indices || !wq))))
-    return fail(c, SPMF_E_ARG, f + "null argument");
-  if (n_long > 0 && !long_rows) return fail(c, SPMF_E_ARG, f + "null argument: long_rows with n_long > 0");
-  if (!(gamma > 0.0 && gamma <= 1.7e308)) return fail(c, SPMF_E_ARG, f + "gamma must be finite and > 0");
-  if (m2 <= 0) return fail(c, SPMF_E_ARG, f + "m2 must be > 0");
-  if (direction != 0 && direction != 1) return fail(c, SPMF_E_ARG, f + "direction must be 0 (up) or 1 (down)");
-  if (n_rows > 0 && labels_out == labels_in)
-    return fail(c, SPMF_E_ARG, f + "labels_out aliases labels_in: other rows read labels_in");
-  if (n_rows == 0) return SPMF_OK;
-  MoveArgs ma{};
-  ma.n_rows = n_rows; ma.nnz = nnz; ma.indptr = indptr; ma.indices = indices; ma.wq = wq;
-  ma.labels_in = labels_in; ma.tot = tot; ma.long_rows = long_rows; ma.n_long = n_long;
-  ma.gamma = gamma; ma.m2 = (double)m2; ma.direction = direction; ma.labels_out = labels_out;
-  launch_graph_move(ma, (hipStream_t)stream);
-  return launched(c, true, "");
-}
-
-// Scratch of one block_gram: the chunks' partial sums.
-static double* block_gram_carve(Arena& a, int64_t rows) {
-  return a.take<double>((size_t)(rows > 0 ? gram_chunks(rows) : 1) * kBlockCols * kBlockCols);
-}
-
-size_t spmf_block_gram_scratch_bytes(const spmf_ctx* c, int64_t n_rows) {
-  if (!c || !graph_layout_rows_ok(n_rows)) return 0;
-  Arena a;
-  block_gram_carve(a, n_rows);
-  return a.used;
-}
-
-int spmf_block_gram(spmf_ctx* c, int64_t n_rows, const float* x, const float* y, double* g, void* scratch,
-    size_t scratch_bytes, void* stream) {
-  if (!c) return SPMF_E_ARG;
-  const std::string f = "block_gram: ";
-  if (!graph_layout_rows_ok(n_rows)) return fail(c, SPMF_E_ARG, f + "n_rows must be in 0..2^31 - 64");
-  if (!g || !scratch || (n_rows > 0 && (!x || !y))) return fail(c, SPMF_E_ARG, f + "null argument");
-  if ((uintptr_t)scratch & 255) return fail(c, SPMF_E_ARG, f + "scratch must be 256-byte aligned");
-  Arena a(scratch, scratch_bytes);
-  double* partial = block_gram_carve(a, n_rows);
-  if (!a.fits()) return scratch_too_small(c, "block_gram", a.used, scratch_bytes,
-      "n_rows=" + std::to_string((long long)n_rows));
-  hipStream_t st = (hipStream_t)stream;
-  if (n_rows == 0) {
-    HIPCHK(c, hipMemsetAsync(g, 0, (size_t)kBlockCols * kBlockCols * sizeof(double), st));
-    return SPMF_OK;
-  }
-  launch_block_gram(n_rows, x, y, partial, g, st);
-  return launched(c, true, "");
-}
-
-int spmf_block_rotate(spmf_ctx* c, int64_t n_rows, const float* x, const double* r, float* y, void* stream) {
-  if (!c) return SPMF_E_ARG;
-  const std::string f = "block_rotate: ";
-  if (!graph_layout_rows_ok(n_rows)) return fail(c, SPMF_E_ARG, f + "n_rows must be in 0..2^31 - 64");
-  if (!r || (n_rows > 0 && (!x || !y))) return fail(c, SPMF_E_ARG, f + "null argument");
-  BlockRot rot;
-  for (int k = 0; k < kBlockCols * kBlockCols; ++k) {
-    if (!(r[k] >= -1.7e308 && r[k] <= 1.7e308)) return fail(c, SPMF_E_ARG, f + "r must be finite");
-    rot.r[k] = r[k];
-  }
-  if (n_rows == 0) return SPMF_OK;
-  launch_block_rotate(n_rows, x, rot, y, (hipStream_t)stream);
   return launched(c, true, "");
 }
 

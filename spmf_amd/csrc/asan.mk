@@ -8,7 +8,7 @@ ASAN_LIB = ../libspmf_hip_asan.so
 %_asan.o: %.hip $(HDRS)
 	$(HIPCC) $(CXXFLAGS) -O1 -g -Xarch_host -fsanitize=address -Xarch_host -fno-omit-frame-pointer -c $< -o $@
 # instrumented: the files with host-side logic behind the C-ABI
-HOST_SRCS = api_ctx.hip api_step.hip api_stream.hip api_comm.hip api_vi.hip layout.hip
+HOST_SRCS = api_ctx.hip api_step.hip api_stream.hip api_points.hip api_graph.hip api_comm.hip api_vi.hip layout.hip
 ASAN_OBJS = $(HOST_SRCS:.hip=_asan.o) $(filter-out $(HOST_SRCS:.hip=.o),$(OBJS))
 $(ASAN_LIB): $(ASAN_OBJS) exports.map
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -fsanitize=address -shared-libsan -Wl,--version-script=exports.map $(ASAN_OBJS) -o $@ -ldl

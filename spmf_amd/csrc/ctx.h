@@ -1,6 +1,7 @@
-// ctx.h -- host only: what the five files behind the C-ABI of libspmf_hip.so (api_ctx.hip, api_step.hip,
-// api_stream.hip, api_comm.hip, api_vi.hip; see include/spmf_hip.h) share: the context, the error return, the
-// likelihood code, the per-draw tables and the few functions one file defines for another.
+// ctx.h -- host only: what the seven files behind the C-ABI of libspmf_hip.so (api_ctx.hip, api_step.hip,
+// api_stream.hip, api_points.hip, api_graph.hip, api_comm.hip, api_vi.hip; see include/spmf_hip.h) share: the
+// context, the error return, the likelihood code, the per-draw tables, the scratch prologue of the calls on rows and
+// graphs as given, and the few functions one file defines for another.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -161,7 +162,39 @@ DetDraw det_layout(void* buf, size_t bytes, int KP, int64_t n_items);
 // api_step.hip
 int encode_rows(spmf_ctx* c, const char* fn, const spmf_counts* ct, int S, const Tables* T, const float* u,
     const float* v, const float* w, const float* s, const float* eta, hipStream_t st);
+// api_stream.hip
+// The SPMF_E_WORKSPACE failure of a call `fn` whose scratch holds `have` bytes where its layout takes `need` for
+// the shape `detail` ("rows=70 S=2").
+int scratch_too_small(spmf_ctx* c, const char* fn, size_t need, size_t have, const std::string& detail);
+// The end of every entry: `ok` is what its launcher returned, `no_kernel` the entry's text for false.
+int launched(spmf_ctx* c, bool ok, const char* no_kernel);
+int device_cus(const spmf_ctx* c);
+int topk_slices(int64_t n_rows, int D, int cus);
+// The ordering of `rows` rows by one of G labels (launch_group_order): chunks and NB are the call's geometry
+void group_order_carve(Arena& a, int64_t rows, int G, int64_t chunks, int64_t NB, GroupOrder& o);
 // api_comm.hip (spmf_ctx_destroy)
 void comm_release(spmf_ctx* c);
 void p2p_release(spmf_ctx* c);
+
+// ---- the calls on rows and graphs as given (api_points.hip, api_graph.hip) -----------------------
+// A row count that a launch takes as a 31-bit grid extent of 64-row blocks
+inline bool rows_ok(int64_t n) { return n >= 0 && n <= ((int64_t)1 << 31) - 64; }
+// The bytes of a layout: `layout(arena)` on an arena without memory
+template <class Layout>
+size_t layout_bytes(Layout&& layout) {
+  Arena a;
+  layout(a);
+  return a.used;
+}
+// The scratch of a call `fn`: not NULL, 256-byte aligned, and `layout(arena)` fits into its scratch_bytes;
+// `detail()` is the shape in the SPMF_E_WORKSPACE failure.  On SPMF_OK the layout's pointers are fit to launch on.
+template <class Layout, class Detail>
+int carve_scratch(spmf_ctx* c, const char* fn, void* scratch, size_t scratch_bytes, Layout&& layout,
+    Detail&& detail) {
+  if (!scratch) return fail(c, SPMF_E_ARG, std::string(fn) + ": null argument");
+  if ((uintptr_t)scratch & 255) return fail(c, SPMF_E_ARG, std::string(fn) + ": scratch must be 256-byte aligned");
+  Arena a(scratch, scratch_bytes);
+  layout(a);
+  return a.fits() ? SPMF_OK : scratch_too_small(c, fn, a.used, scratch_bytes, detail());
+}
 }  // namespace spmf

@@ -19,27 +19,10 @@
 //
 // Nothing here trusts the graph: an indptr value is clamped to [0, nnz], an index outside [0, n_rows) reads no
 // position, a negative is __umulhi(word, n_rows) < n_rows.
-#include "common.h"
 #include "kernels.h"
-#include "philox.h"
+#include "layout_force.h"
 
 namespace spmf {
-
-namespace {
-
-constexpr int kRowLanes = 16;
-constexpr int kRowsPerBlock = 256 / kRowLanes;
-
-__device__ __forceinline__ bool finite2(float2 v) { return isfinite(v.x) && isfinite(v.y); }
-// clamp to [-4, 4]; fmaxf / fminf return the other operand for a NaN (0 * inf of an overflowed distance)
-__device__ __forceinline__ float clip4(float v) { return fminf(fmaxf(v, -4.f), 4.f); }
-
-// a * d2^b for d2 > 0, capped where q / (1 + q) is 1 in fp32 anyway: an overflowed power stays out of inf / inf
-__device__ __forceinline__ float a_pow_b(float a, float b, float d2) {
-  return fminf(a * exp2f(b * log2f(d2)), 0x1p+60f);
-}
-
-}  // namespace
 
 __global__ __launch_bounds__(256) void graph_layout_kernel(int64_t n_rows, int64_t nnz,
                                                            const int64_t* __restrict__ indptr,
@@ -72,36 +55,18 @@ __global__ __launch_bounds__(256) void graph_layout_kernel(int64_t n_rows, int64
       const float2 yj = y[j];
       if (!finite2(yj)) continue;
       W += w;
-      const float dx = yi.x - yj.x, dy = yi.y - yj.y;
-      const float d2 = fmaf(dx, dx, dy * dy);
-      if (d2 > 0.f) {
-        const float q = a_pow_b(a, b, d2);
-        const float c = neg2b * q / (d2 * (1.f + q));             // -2ab d2^(b-1) / (1 + a d2^b)
-        fx = fmaf(w, clip4(c * dx), fx);
-        fy = fmaf(w, clip4(c * dy), fy);
-      }
+      attract(yi, yj, w, a, b, neg2b, fx, fy);
     }
   }
   // repulsion: this lane's negatives in ascending order
   float gx = 0.f, gy = 0.f;
   if (moves) {
     for (int m = sub; m < M; m += kRowLanes) {
-      const uint4 r4 = philox4x32_10(make_uint4((uint32_t)i, (uint32_t)(m >> 2), (uint32_t)epoch, 0x554D4150u),
-                                     make_uint2(seed_lo, seed_hi));
-      const int k = m & 3;
-      const uint32_t word = k == 0 ? r4.x : k == 1 ? r4.y : k == 2 ? r4.z : r4.w;
-      const uint32_t r = __umulhi(word, n32);              // < n_rows
+      const uint32_t r = negative_row((uint32_t)i, m, epoch, 0x554D4150u, seed_lo, seed_hi, n32);    // < n_rows
       if ((int64_t)r == i) continue;
       const float2 yr = y[r];
       if (!finite2(yr)) continue;
-      const float dx = yi.x - yr.x, dy = yi.y - yr.y;
-      const float d2 = fmaf(dx, dx, dy * dy);
-      if (d2 > 0.f) {
-        const float q = a_pow_b(a, b, d2);
-        const float c = two_gamma_b / ((0.001f + d2) * (1.f + q));
-        gx += clip4(c * dx);
-        gy += clip4(c * dy);
-      }
+      repel(yi, yr, a, b, two_gamma_b, gx, gy);
     }
   }
   W = group_sum<kRowLanes>(W);
@@ -122,14 +87,14 @@ __global__ __launch_bounds__(256) void graph_layout_kernel(int64_t n_rows, int64
 
 void launch_graph_layout(const GraphLayoutArgs& g, hipStream_t st) {
   const unsigned nb = (unsigned)((g.n_rows + kRowsPerBlock - 1) / kRowsPerBlock);   // < 2^27
-  for (int k = 0; k < g.n_epochs; ++k) {
+  for (int k = 0; k < g.s.n_epochs; ++k) {
     const float2* from = g.buf[k & 1];
-    float2* to = k == g.n_epochs - 1 ? g.y_out : g.buf[(k + 1) & 1];
-    const int e = g.epoch0 + k;
-    const float alpha = (float)(g.lr * (1.0 - (double)e / (double)g.total_epochs));
+    float2* to = k == g.s.n_epochs - 1 ? g.y_out : g.buf[(k + 1) & 1];
+    const int e = g.s.epoch0 + k;
+    const float alpha = (float)(g.s.lr * (1.0 - (double)e / (double)g.s.total_epochs));
     hipLaunchKernelGGL(graph_layout_kernel, dim3(nb), dim3(256), 0, st, g.n_rows, g.nnz, g.indptr, g.indices,
-                       g.weights, from, to, e, alpha, g.n_negatives, g.a, g.b, g.neg2b,
-                       g.two_gamma_b, g.rate_over_m, g.seed_lo, g.seed_hi);
+                       g.weights, from, to, e, alpha, g.s.n_negatives, g.s.a, g.s.b, g.s.neg2b,
+                       g.s.two_gamma_b, g.s.rate_over_m, g.s.seed_lo, g.s.seed_hi);
   }
 }
 

@@ -17,27 +17,13 @@
 //
 // Nothing here trusts the inputs: an index outside [0, n_ref) reads no position, a negative is
 // __umulhi(word, n_ref) < n_ref, with n_ref == 0 no negative is drawn and nothing of y_ref is read.
-#include "common.h"
 #include "kernels.h"
-#include "philox.h"
+#include "layout_force.h"
 
 namespace spmf {
 
 namespace {
-
-constexpr int kRowLanes = 16;
-constexpr int kRowsPerBlock = 256 / kRowLanes;
 constexpr int kLaneEntries = 4;                            // k <= 64 = kRowLanes * kLaneEntries
-
-__device__ __forceinline__ bool finite2(float2 v) { return isfinite(v.x) && isfinite(v.y); }
-// clamp to [-4, 4]; fmaxf / fminf return the other operand for a NaN (0 * inf of an overflowed distance)
-__device__ __forceinline__ float clip4(float v) { return fminf(fmaxf(v, -4.f), 4.f); }
-
-// a * d2^b for d2 > 0, capped where q / (1 + q) is 1 in fp32 anyway: an overflowed power stays out of inf / inf
-__device__ __forceinline__ float a_pow_b(float a, float b, float d2) {
-  return fminf(a * exp2f(b * log2f(d2)), 0x1p+60f);
-}
-
 }  // namespace
 
 // y_in and y_out may be one array: a row's group reads y_in[i] before its lane 0 writes y_out[i], and no other
@@ -86,43 +72,24 @@ __global__ __launch_bounds__(256) void graph_transform_kernel(GraphTransformArgs
     sy = group_sum<kRowLanes>(sy);
     yi = W > 0.f ? make_float2(sx / W, sy / W) : make_float2(__builtin_nanf(""), __builtin_nanf(""));
   }
-  const float s = g.rate_over_m * W, inv = fmaxf(1.f, W);
+  const float s = g.s.rate_over_m * W, inv = fmaxf(1.f, W);
   const uint32_t g32 = (uint32_t)(g.row0 + i);
 
-  for (int e = g.epoch0; e < g.epoch0 + g.n_epochs; ++e) {
+  for (int e = g.s.epoch0; e < g.s.epoch0 + g.s.n_epochs; ++e) {
     // a row without a valid entry and a row at a non-finite position keep their bits
     const bool moves = live && W > 0.f && finite2(yi);     // the same for the 16 lanes of a group
     float fx = 0.f, fy = 0.f, gx = 0.f, gy = 0.f;
     if (moves) {
 #pragma unroll
       for (int t = 0; t < kLaneEntries; ++t) {             // attraction: this lane's entries in ascending order
-        if (wj[t] > 0.f) {
-          const float dx = yi.x - yj[t].x, dy = yi.y - yj[t].y;
-          const float d2 = fmaf(dx, dx, dy * dy);
-          if (d2 > 0.f) {
-            const float q = a_pow_b(g.a, g.b, d2);
-            const float c = g.neg2b * q / (d2 * (1.f + q));           // -2ab d2^(b-1) / (1 + a d2^b)
-            fx = fmaf(wj[t], clip4(c * dx), fx);
-            fy = fmaf(wj[t], clip4(c * dy), fy);
-          }
-        }
+        if (wj[t] > 0.f) attract(yi, yj[t], wj[t], g.s.a, g.s.b, g.s.neg2b, fx, fy);
       }
       if (n32 > 0) {
-        for (int m = sub; m < g.n_negatives; m += kRowLanes) {       // repulsion: this lane's negatives
-          const uint4 r4 = philox4x32_10(make_uint4(g32, (uint32_t)(m >> 2), (uint32_t)e, 0x554D5854u),
-                                         make_uint2(g.seed_lo, g.seed_hi));
-          const int k = m & 3;
-          const uint32_t word = k == 0 ? r4.x : k == 1 ? r4.y : k == 2 ? r4.z : r4.w;
-          const float2 yr = y_ref[__umulhi(word, n32)];              // < n_ref
+        for (int m = sub; m < g.s.n_negatives; m += kRowLanes) {     // repulsion: this lane's negatives
+          // (a row below n_ref)
+          const float2 yr = y_ref[negative_row(g32, m, e, 0x554D5854u, g.s.seed_lo, g.s.seed_hi, n32)];
           if (!finite2(yr)) continue;
-          const float dx = yi.x - yr.x, dy = yi.y - yr.y;
-          const float d2 = fmaf(dx, dx, dy * dy);
-          if (d2 > 0.f) {
-            const float q = a_pow_b(g.a, g.b, d2);
-            const float c = g.two_gamma_b / ((0.001f + d2) * (1.f + q));
-            gx += clip4(c * dx);
-            gy += clip4(c * dy);
-          }
+          repel(yi, yr, g.s.a, g.s.b, g.s.two_gamma_b, gx, gy);
         }
       }
     }
@@ -131,7 +98,7 @@ __global__ __launch_bounds__(256) void graph_transform_kernel(GraphTransformArgs
     gx = group_sum<kRowLanes>(gx);
     gy = group_sum<kRowLanes>(gy);
     if (moves) {
-      const float alpha = (float)(g.lr * (1.0 - (double)e / (double)g.total_epochs));
+      const float alpha = (float)(g.s.lr * (1.0 - (double)e / (double)g.s.total_epochs));
       const float step = alpha / inv;
       yi.x = fmaf(step, fmaf(s, gx, fx), yi.x);
       yi.y = fmaf(step, fmaf(s, gy, fy), yi.y);

@@ -313,18 +313,18 @@ __global__ __launch_bounds__(256) void group_combine_kernel(int S, int G, int C,
 
 // The ordering alone (kmeans.hip orders its rows by label with it): tbl [ceil(B / kGroupRowChunk)][G], lrank [B],
 // cnt [G], boff [G + 1], fincl [G], perm [64 NB], rec [NB] with NB = ceil(B / 64) + G; RB numbers the segments.
-void launch_group_order(int64_t B, int G, int RB, const int32_t* labels, int32_t* tbl, int32_t* lrank, int32_t* cnt,
-                        int32_t* boff, int32_t* fincl, int32_t* perm, int4* rec, hipStream_t st) {
+void launch_group_order(int64_t B, int G, int RB, const int32_t* labels, const GroupOrder& o, hipStream_t st) {
   const int64_t chunks = (B + kGroupRowChunk - 1) / kGroupRowChunk;
   const int64_t NB = (B + 63) / 64 + G, NP = NB * 64;
-  launch_zero(tbl, (size_t)chunks * G * sizeof(int32_t), st);
-  hipLaunchKernelGGL(group_rank_kernel, dim3((unsigned)chunks), dim3(kGroupRowChunk), 0, st, B, G, labels, lrank, tbl);
-  hipLaunchKernelGGL(group_scan_kernel, dim3((unsigned)G), dim3(64), 0, st, chunks, G, tbl, cnt);
-  hipLaunchKernelGGL(group_offsets_kernel, dim3(1), dim3(256), 0, st, G, RB, cnt, boff, fincl);
-  hipLaunchKernelGGL(group_fill_kernel, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, st, NB, G, RB, cnt, boff,
-                     fincl, perm, rec);
-  hipLaunchKernelGGL(group_scatter_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, B, G, labels, lrank,
-                     tbl, boff, perm);
+  launch_zero(o.tbl, (size_t)chunks * G * sizeof(int32_t), st);
+  hipLaunchKernelGGL(group_rank_kernel, dim3((unsigned)chunks), dim3(kGroupRowChunk), 0, st, B, G, labels, o.lrank,
+                     o.tbl);
+  hipLaunchKernelGGL(group_scan_kernel, dim3((unsigned)G), dim3(64), 0, st, chunks, G, o.tbl, o.cnt);
+  hipLaunchKernelGGL(group_offsets_kernel, dim3(1), dim3(256), 0, st, G, RB, o.cnt, o.boff, o.fincl);
+  hipLaunchKernelGGL(group_fill_kernel, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, st, NB, G, RB, o.cnt, o.boff,
+                     o.fincl, o.perm, o.rec);
+  hipLaunchKernelGGL(group_scatter_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, B, G, labels, o.lrank,
+                     o.tbl, o.boff, o.perm);
 }
 
 bool launch_groups(const GroupArgs& a, hipStream_t st) {
@@ -334,11 +334,12 @@ bool launch_groups(const GroupArgs& a, hipStream_t st) {
   if (t.B <= 0 || C <= 0) return true;
   const GroupGeom q = group_geom(t.B, t.S, G, C);
   const int64_t NP = q.NB * 64;
+  const GroupOrder& o = a.ord;
 
-  launch_group_order(t.B, G, q.RB, a.labels, a.tbl, a.lrank, a.cnt, a.boff, a.fincl, a.perm, a.rec, st);
+  launch_group_order(t.B, G, q.RB, a.labels, o, st);
   const int64_t n4 = NP * (t.KP / 4);
   hipLaunchKernelGGL(group_gather_kernel, dim3((unsigned)((n4 + 255) / 256), (unsigned)t.S), dim3(256), 0, st, t.B,
-                     NP, t.KP, a.perm, t.z, a.zs);
+                     NP, t.KP, o.perm, t.z, a.zs);
   if (a.cols) {
     uint8_t* ctc = t.lik == 3 ? a.ctc : nullptr;
     launch_panel_gather(t, C, a.cols, a.Vc, a.phic, ctc, st);
@@ -356,8 +357,8 @@ bool launch_groups(const GroupArgs& a, hipStream_t st) {
       with_lik(t.lik, [&](auto lik) {
         auto go = [&](auto pz) {
           hipLaunchKernelGGL((group_kernel<decltype(kc)::value, decltype(lik)::value, decltype(pz)::value>), grid,
-                             dim3(256), 0, st, NP, C, t.KP, t.S, q.RB, c0, q.CR, a.zs, t.Vp, t.phi, t.ctype, a.rec,
-                             a.boff + G, part_sum, part_nz);
+                             dim3(256), 0, st, NP, C, t.KP, t.S, q.RB, c0, q.CR, a.zs, t.Vp, t.phi, t.ctype, o.rec,
+                             o.boff + G, part_sum, part_nz);
         };
         if (a.nonzero) go(std::true_type{});
         else go(std::false_type{});
@@ -365,7 +366,7 @@ bool launch_groups(const GroupArgs& a, hipStream_t st) {
     });
     const int64_t n = (int64_t)t.S * G * cw;
     hipLaunchKernelGGL(group_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, t.S, G, C, c0, cw,
-                       q.CR, a.cnt, a.boff, a.rec, part_sum, part_nz, a.sum, a.nonzero);
+                       q.CR, o.cnt, o.boff, o.rec, part_sum, part_nz, a.sum, a.nonzero);
   }
   return true;
 }

@@ -285,7 +285,7 @@ bool launch_toprows(const TopRowsArgs& a, hipStream_t st);
 // t.z[S,B,KP], unpadded: mean / sd [B][K].  Nothing is launched for B == 0.
 void launch_embed(const DrawTables& t, int K, float* mean, float* sd, hipStream_t st);
 // knn.hip: exact k nearest rows of r [n_ref][row_len] for every row of q [n_query][row_len] (include/spmf_hip.h
-// spmf_knn has the definition).  The scratch pointers are api_stream.hip's carve; qw == rw when q == r.  false: KP / k /
+// spmf_knn has the definition).  The scratch pointers are api_points.hip's carve; qw == rw when q == r.  false: KP / k /
 // slices not built (nothing launched).
 constexpr int kKnnCentreBlocks = 512;   // most per-block partial sums of the centre
 constexpr int kKnnDefaultTile = 1;      // the tile function without SPMF_KNN_TILE: the faster one
@@ -373,14 +373,17 @@ struct GroupGeom {
   size_t part_bytes;
 };
 GroupGeom group_geom(int64_t B, int S, int G, int C);
+struct GroupOrder {                // the ordering of B rows by label (launch_group_order), in the carve's order
+  int32_t *tbl, *lrank, *cnt, *boff, *fincl;   // [chunks][G], [B], [G], [G + 1], [G]
+  int4* rec; int32_t* perm;        // [NB], [64 NB]
+};
 struct GroupArgs {
   DrawTables t;
   int n_groups, n_cols;
   const int32_t* labels;           // [B]
   const int32_t* cols;             // [n_cols] or null
   double *sum, *nonzero;           // [S][n_groups][n_cols], accumulated; nonzero may be null
-  int32_t *tbl, *lrank, *cnt, *boff, *fincl, *perm;   // [chunks][G], [B], [G], [G + 1], [G], [64 NB]
-  int4* rec;                       // [NB]
+  GroupOrder ord;
   float* zs;                       // [S][64 NB][KP]
   float *Vc, *phic;                // as PanelArgs (cols set)
   uint8_t* ctc;
@@ -392,11 +395,10 @@ bool launch_groups(const GroupArgs& a, hipStream_t st);
 // [NB] (group, valid rows, segment, 0; group -1 for a surplus block), cnt [G], boff [G + 1] (first block of a
 // group, boff[G] = blocks in use), with NB = ceil(B / 64) + G; tbl [ceil(B / kGroupRowChunk)][G], lrank [B] and
 // fincl [G] are its working arrays.  A segment is the blocks of one group inside one run of RB blocks.  B > 0.
-void launch_group_order(int64_t B, int G, int RB, const int32_t* labels, int32_t* tbl, int32_t* lrank, int32_t* cnt,
-                        int32_t* boff, int32_t* fincl, int32_t* perm, int4* rec, hipStream_t st);
+void launch_group_order(int64_t B, int G, int RB, const int32_t* labels, const GroupOrder& o, hipStream_t st);
 // kmeans.hip: one Lloyd step behind launch_knn (include/spmf_hip.h spmf_kmeans_step has the definition).  cand_idx /
 // cand_dist [n_rows][kc] are launch_knn's refined result for q = x, r = centroids, k = kc = min(4, G).  The
-// scratch pointers are api_stream.hip's carve, sized from kmeans_geom, a pure function of (n_rows, G): the order
+// scratch pointers are api_points.hip's carve, sized from kmeans_geom, a pure function of (n_rows, G): the order
 // of every sum depends on (n_rows, the labels) alone.  n_rows > 0.
 constexpr int kKmeansTargetRuns = 2048;  // runs of row blocks aimed at (a constant: not the device's CU count)
 constexpr int kKmeansStatRows = 256;     // rows per partial sum of the statistics
@@ -417,14 +419,13 @@ struct KmeansArgs {
   double* sums;                    // [G][row_len]
   int64_t* counts;                 // [G]
   double* stats;                   // [3]
-  int32_t *tbl, *lrank, *cnt, *boff, *fincl, *perm;   // as launch_group_order
-  int4* rec;
+  GroupOrder ord;
   double* part;                    // [nseg][row_len]
   double* spart;                   // [sblocks][3]
 };
 void launch_kmeans(const KmeansArgs& a, hipStream_t st);
 // silhouette.hip: the silhouette of labelled rows over all pairs (include/spmf_hip.h spmf_silhouette has the
-// definition).  The scratch pointers are api_stream.hip's carve, sized from silhouette_geom; every order of
+// definition).  The scratch pointers are api_points.hip's carve, sized from silhouette_geom; every order of
 // additions depends on the members' labels alone.  false: KP not built or no row (nothing launched).
 constexpr int kSilCentreBlocks = 512;    // runs of blocks whose partial sums make the centre
 struct SilhouetteGeom {
@@ -442,8 +443,7 @@ struct SilhouetteArgs {
   double* cluster_sum;             // [G]
   int64_t* counts;                 // [G]
   int32_t* eff;                    // [n_rows]: the effective labels
-  int32_t *tbl, *lrank, *cnt, *boff, *fincl, *perm;   // as launch_group_order
-  int4* rec;
+  GroupOrder ord;
   float *w, *bias;                 // working rows [64 NB][KP] in group order, bias [64 NB]
   double* cpart;                   // [kSilCentreBlocks][KP]
   int32_t* ccnt;                   // [kSilCentreBlocks]
@@ -453,9 +453,15 @@ struct SilhouetteArgs {
 bool launch_silhouette(const SilhouetteArgs& a, hipStream_t st);
 // graph_layout.hip: the epochs of a 2-D layout of a CSR graph (include/spmf_hip.h spmf_graph_layout has the
 // definition).  One launch per epoch: epoch k reads every position of `from` and writes every row's position to
-// `to`, the last epoch into y_out; buf[0] / buf[1] are the api's two scratch buffers and buf[0] holds the start.
-// The step of epoch e is lr * (1 - e / total_epochs), formed in fp64 here and passed as fp32.  The graph is read as it stands: every index, weight
-// and indptr value is checked in the kernel.
+// `to`, the last epoch into y_out; buf[0] / buf[1] are api_graph.hip's two scratch buffers and buf[0] holds the
+// start.  The step of epoch e is lr * (1 - e / total_epochs), formed in fp64 here and passed as fp32.  The graph is
+// read as it stands: every index, weight and indptr value is checked in the kernel.
+struct LayoutSchedule {            // of both layout kernels: the call's epochs in the run, the force, the seed
+  int epoch0, n_epochs, total_epochs, n_negatives;
+  double lr;
+  float a, b, neg2b, two_gamma_b, rate_over_m;    // fp64 on the host, each rounded once
+  uint32_t seed_lo, seed_hi;
+};
 struct GraphLayoutArgs {
   int64_t n_rows, nnz;
   const int64_t* indptr;           // [n_rows + 1]
@@ -463,10 +469,7 @@ struct GraphLayoutArgs {
   const float* weights;            // [nnz]
   float2* buf[2];                  // [n_rows] each
   float2* y_out;                   // [n_rows]
-  int epoch0, n_epochs, total_epochs, n_negatives;
-  double lr;
-  float a, b, neg2b, two_gamma_b, rate_over_m;    // fp64 on the host, each rounded once
-  uint32_t seed_lo, seed_hi;
+  LayoutSchedule s;
 };
 void launch_graph_layout(const GraphLayoutArgs& a, hipStream_t st);
 // graph_transform.hip: the epochs of new rows on a fitted layout, the reference positions held fixed
@@ -482,10 +485,7 @@ struct GraphTransformArgs {
   const float2* y_ref;             // [n_ref]
   const float2* y_in;              // [n_query], or null: the weighted mean of the neighbours
   float2* y_out;                   // [n_query]; may be y_in
-  int epoch0, n_epochs, total_epochs, n_negatives;
-  double lr;
-  float a, b, neg2b, two_gamma_b, rate_over_m;    // fp64 on the host, each rounded once
-  uint32_t seed_lo, seed_hi;
+  LayoutSchedule s;
 };
 void launch_graph_transform(const GraphTransformArgs& a, hipStream_t st);
 // spectral.hip: multiplying by the graph (include/spmf_hip.h spmf_graph_scale .. spmf_block_rotate have the

@@ -159,17 +159,18 @@ __global__ __launch_bounds__(256) void kmeans_combine_kernel(int G, int Kx, cons
 void launch_kmeans(const KmeansArgs& a, hipStream_t st) {
   const KmeansGeom q = kmeans_geom(a.n_rows, a.n_clusters);
   const int G = a.n_clusters;
+  const GroupOrder& o = a.ord;
   int KP = 4;
   while (KP < a.row_len) KP *= 2;
   hipLaunchKernelGGL(kmeans_label_kernel, dim3((unsigned)q.sblocks), dim3(kKmeansStatRows), 0, st, a.n_rows, a.kc,
                      a.cand_idx, a.cand_dist, a.prev, a.labels, a.dist, a.spart);
   hipLaunchKernelGGL(kmeans_stats_kernel, dim3(1), dim3(256), 0, st, q.sblocks, a.spart, a.stats);
-  launch_group_order(a.n_rows, G, q.RB, a.labels, a.tbl, a.lrank, a.cnt, a.boff, a.fincl, a.perm, a.rec, st);
-  hipLaunchKernelGGL(kmeans_sums_kernel, dim3((unsigned)q.runs), dim3(256), 0, st, a.row_len, KP, q.RB, a.x, a.perm,
-                     a.rec, a.boff + G, a.part);
+  launch_group_order(a.n_rows, G, q.RB, a.labels, o, st);
+  hipLaunchKernelGGL(kmeans_sums_kernel, dim3((unsigned)q.runs), dim3(256), 0, st, a.row_len, KP, q.RB, a.x, o.perm,
+                     o.rec, o.boff + G, a.part);
   const int64_t n = (int64_t)G * a.row_len;
-  hipLaunchKernelGGL(kmeans_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, G, a.row_len, a.cnt,
-                     a.boff, a.rec, a.part, a.sums, a.counts);
+  hipLaunchKernelGGL(kmeans_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, G, a.row_len, o.cnt,
+                     o.boff, o.rec, a.part, a.sums, a.counts);
 }
 
 }  // namespace spmf

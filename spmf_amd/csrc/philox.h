@@ -1,5 +1,6 @@
 // philox.h -- device only: the counter-based generator of the kernels that draw on the device (surrogate.hip:
-// the base noise of the surrogate; graph_layout.hip and graph_transform.hip: the negative samples of an epoch).
+// the base noise of the surrogate; layout_force.h: the negative samples of an epoch of graph_layout.hip and
+// graph_transform.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -291,6 +291,7 @@ __global__ __launch_bounds__(256) void sil_combine_kernel(int G, const int32_t* 
 bool launch_silhouette(const SilhouetteArgs& a, hipStream_t st) {
   const SilhouetteGeom q = silhouette_geom(a.n_rows, a.n_clusters);
   const int G = a.n_clusters, cosine = a.cosine ? 1 : 0;
+  const GroupOrder& o = a.ord;
   if (a.row_len < 1 || a.row_len > a.KP || a.n_rows <= 0) return false;
   return with_kc(a.KP, [&](auto kc) {
     constexpr int KC = decltype(kc)::value;
@@ -298,17 +299,17 @@ bool launch_silhouette(const SilhouetteArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(sil_label_kernel, dim3((unsigned)((a.n_rows + 3) / 4)), dim3(256), 0, st, a.n_rows, a.row_len, G,
                        cosine, a.x, a.labels, a.eff, a.sil, a.a, a.b, a.nearest);
     // (RB = 1: the ordering's segments are the blocks themselves and are not used here)
-    launch_group_order(a.n_rows, G, 1, a.eff, a.tbl, a.lrank, a.cnt, a.boff, a.fincl, a.perm, a.rec, st);
+    launch_group_order(a.n_rows, G, 1, a.eff, o, st);
     if (!cosine) {
-      hipLaunchKernelGGL(sil_centre_kernel, dim3(kSilCentreBlocks), dim3(256), 0, st, a.row_len, a.KP, a.x, a.perm,
-                         a.rec, a.boff + G, a.cpart, a.ccnt);
+      hipLaunchKernelGGL(sil_centre_kernel, dim3(kSilCentreBlocks), dim3(256), 0, st, a.row_len, a.KP, a.x, o.perm,
+                         o.rec, o.boff + G, a.cpart, a.ccnt);
       hipLaunchKernelGGL(sil_centre_finish_kernel, dim3(1), dim3(256), 0, st, a.KP, a.cpart, a.ccnt, a.centre);
     }
     hipLaunchKernelGGL(sil_prepare_kernel, dim3((unsigned)((NP + 3) / 4)), dim3(256), 0, st, NP, a.row_len, a.KP,
-                       cosine, a.x, a.perm, a.centre, a.w, a.bias);
+                       cosine, a.x, o.perm, a.centre, a.w, a.bias);
     hipLaunchKernelGGL((sil_sweep_kernel<KC>), dim3((unsigned)q.NB), dim3(256), 0, st, a.KP, cosine, a.w, a.bias,
-                       a.perm, a.rec, a.cnt, a.boff + G, a.sil, a.a, a.b, a.nearest, a.spart);
-    hipLaunchKernelGGL(sil_combine_kernel, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, st, G, a.cnt, a.boff,
+                       o.perm, o.rec, o.cnt, o.boff + G, a.sil, a.a, a.b, a.nearest, a.spart);
+    hipLaunchKernelGGL(sil_combine_kernel, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, st, G, o.cnt, o.boff,
                        a.spart, a.cluster_sum, a.counts);
   });
 }

@@ -12,6 +12,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import _args
+
 METRICS = ("euclidean", "cosine")
 
 
@@ -111,9 +113,8 @@ def vote(indices, weights, labels, n_classes=None, max_elements=1 << 24):
         raise ValueError(f"vote: indices must hold integers, got {idx.dtype}")
     if lab.dim() != 1 or lab.dtype.is_floating_point or lab.dtype == torch.bool:
         raise ValueError(f"vote: labels must be a 1-D tensor of integers, got {lab.dtype} {tuple(lab.shape)}")
-    if n_classes is not None and (isinstance(n_classes, bool) or not isinstance(n_classes, (int, np.integer))
-                                  or int(n_classes) < 0):
-        raise ValueError(f"vote: n_classes must be an integer >= 0, got {n_classes!r}")
+    if n_classes is not None:
+        _args.integer("vote", "n_classes", n_classes, 0)
     idx, lab, w = idx.to(torch.int64), lab.to(torch.int64), w.to(torch.float64)
     n_ref = int(lab.numel())
     G = int(n_classes) if n_classes is not None else (max(int(lab.max()) + 1, 0) if n_ref else 0)

@@ -20,6 +20,7 @@ import torch
 from . import _lib
 from ._lib import PART_ORDER, VAR_ORDER, SpmfError
 from .sparse import SparseCounts
+from .analysis import AnalysisQueries
 from .streaming import StreamingQueries
 
 
@@ -34,7 +35,7 @@ def var_shapes(D: int, K: int) -> Dict[str, tuple]:
     }
 
 
-class PoissonFactorization(StreamingQueries):
+class PoissonFactorization(StreamingQueries, AnalysisQueries):
     """Sparse (horseshoe) poisson matrix factorization  (poisson.py:25-29).
 
     Constructor keywords are the reference's (poisson.py:56-64), including the

@@ -40,6 +40,8 @@ import math
 import numpy as np
 import torch
 
+from . import _args, _lib
+
 BLOCK = 16                 # include/spmf_hip.h SPMF_BLOCK_COLS
 MAX_COMPONENTS = 12
 MIN_ROWS = 32              # rows with a valid edge below which dense eigh is the tool
@@ -52,17 +54,10 @@ _MIN_HALF_WIDTH = 0.05     # of the filter's interval: a cut at -1 would leave n
 # ---- arguments ---------------------------------------------------------------------------------------------------
 def check_args(name, n_components, tol, max_iter, seed):
     """The arguments of ``solve`` / ``spectral`` that need no graph -> (m, tol, max_iter, seed)."""
-    def integer(what, v, lo, hi):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
-            raise ValueError(f"{name}: {what} must be an integer in {lo}..{hi}, got {v!r}")
-        return int(v)
-    m = integer("n_components", n_components, 1, MAX_COMPONENTS)
-    max_iter = integer("max_iter", max_iter, 1, 2 ** 31 - 1)
-    seed = integer("seed", seed, 0, 2 ** 63 - 1)
-    ok = isinstance(tol, (int, float, np.integer, np.floating)) and not isinstance(tol, bool)
-    if not ok or not np.isfinite(tol) or tol <= 0:
-        raise ValueError(f"{name}: tol must be a finite number > 0, got {tol!r}")
-    return m, float(tol), max_iter, seed
+    m = _args.integer(name, "n_components", n_components, 1, MAX_COMPONENTS)
+    max_iter = _args.integer(name, "max_iter", max_iter, 1, 2 ** 31 - 1)
+    seed = _args.integer(name, "seed", seed, 0, 2 ** 63 - 1)
+    return m, _args.number(name, "tol", tol, positive=True), max_iter, seed
 
 
 def too_few_rows(name, n_live):
@@ -178,19 +173,16 @@ class LibraryOps:
     ``gram`` reads its 256 doubles back (the one synchronisation of a step)."""
 
     def __init__(self, lib, handle, indptr, indices, weights):
-        from . import _lib
-        self._check = _lib.check
         self.lib, self.h = lib, handle
         self.g = (indptr.contiguous(), indices.contiguous(), weights.contiguous())
         self.n, self.nnz = int(indptr.numel()) - 1, int(indices.numel())
         self.device = indptr.device
-        self.stream = torch.cuda.current_stream(self.device).cuda_stream
         self._gram = torch.empty(BLOCK * BLOCK, dtype=torch.float64, device=self.device)
-        need = int(lib.spmf_block_gram_scratch_bytes(handle, self.n))
-        self._scratch = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-        self._ptr = self._scratch.data_ptr() + (-self._scratch.data_ptr()) % 256
-        self._need = need
+        self._scratch = _lib.Scratch(self.device)
         self._s = None
+
+    def _call(self, fn, *args, scratch=None):
+        _lib.call(self.h, fn, *args, device=self.device, scratch=scratch)
 
     def _graph(self):
         return (self.n, self.nnz, self.g[0].data_ptr(), self.g[1].data_ptr(), self.g[2].data_ptr())
@@ -207,31 +199,26 @@ class LibraryOps:
     def scale(self):
         if self._s is None:
             s = torch.empty(self.n, dtype=torch.float32, device=self.device)
-            self._check(self.h, self.lib.spmf_graph_scale(self.h, *self._graph(), s.data_ptr(), self.stream),
-                        "spmf_graph_scale")
+            self._call("spmf_graph_scale", *self._graph(), s.data_ptr())
             self._s = s
         return self._s
 
     def spmm(self, x, cs=1.0, cx=None, cz=0.0, z=None, out=None, scaled=True):
         out = torch.empty_like(x) if out is None else out
         c = (C.c_double * BLOCK)(*([0.0] * BLOCK if cx is None else [float(v) for v in cx]))
-        self._check(self.h, self.lib.spmf_graph_spmm(
-            self.h, *self._graph(), self.scale().data_ptr() if scaled else None, x.data_ptr(),
-            z.data_ptr() if z is not None else None, out.data_ptr(), float(cs), c, float(cz), self.stream),
-            "spmf_graph_spmm")
+        self._call("spmf_graph_spmm", *self._graph(), self.scale().data_ptr() if scaled else None, x.data_ptr(),
+                   z.data_ptr() if z is not None else None, out.data_ptr(), float(cs), c, float(cz))
         return out
 
     def gram(self, x, y):
-        self._check(self.h, self.lib.spmf_block_gram(self.h, self.n, x.data_ptr(), y.data_ptr(),
-                                                     self._gram.data_ptr(), self._ptr, self._need, self.stream),
-                    "spmf_block_gram")
+        self._call("spmf_block_gram", self.n, x.data_ptr(), y.data_ptr(), self._gram.data_ptr(),
+                   scratch=(self._scratch, "spmf_block_gram_scratch_bytes", self.n))
         return self._gram.cpu().numpy().reshape(BLOCK, BLOCK).copy()
 
     def rotate(self, x, r, out=None):
         out = torch.empty_like(x) if out is None else out
         r = np.ascontiguousarray(r, dtype=np.float64)
-        self._check(self.h, self.lib.spmf_block_rotate(self.h, self.n, x.data_ptr(), r.ctypes.data, out.data_ptr(),
-                                                       self.stream), "spmf_block_rotate")
+        self._call("spmf_block_rotate", self.n, x.data_ptr(), r.ctypes.data, out.data_ptr())
         return out
 
 

@@ -38,7 +38,6 @@ a = ap.parse_args()
 import torch  # noqa: E402
 
 from spmf_amd import PoissonFactorization, _lib  # noqa: E402
-from spmf_amd.streaming import _Scratch  # noqa: E402
 
 dev = torch.device("cuda", 0)
 m = PoissonFactorization(latent_dim=3, feature_dim=8, initialize_distributions=False, device=dev)
@@ -57,7 +56,7 @@ def step(cent):
     _lib.check(h, lib.spmf_kmeans_step(
         h, points.data_ptr(), N, W, cent.data_ptr(), G, None, out["labels"].data_ptr(), out["distances"].data_ptr(),
         out["sums"].data_ptr(), out["counts"].data_ptr(), out["stats"].data_ptr(),
-        *_Scratch(dev).fit(lib.spmf_kmeans_scratch_bytes(h, N, G, W)), torch.cuda.current_stream(dev).cuda_stream),
+        *_lib.Scratch(dev).fit(lib.spmf_kmeans_scratch_bytes(h, N, G, W)), torch.cuda.current_stream(dev).cuda_stream),
         "spmf_kmeans_step")
     return out
 
