@@ -57,6 +57,13 @@ found, not given; --resolution R, default 1, larger for more and smaller communi
 over the same encoding, --umap-neighbors and seed; with --umap the graph is built once.  The labels stand in for
 --clusters wherever those are used and --clusters is not given: the group table (without --labels), --silhouette
 and the labels of --map-counts.  Bit-reproducible for a given model.  Without the flag nothing changes.
+With --paga (the coarse graph of the clusters, scanpy's tl.paga, over the same fuzzy neighbour graph; the labels are
+those of --communities, else of --clusters, else of --labels, and one of the three is needed):
+  <stem>_paga_connectivities_<P>.npy  [groups, groups] float64: how much more than chance two groups touch, in [0, 1]
+  <stem>_paga_tree_<P>.npy            [groups, groups] float64: the maximum spanning forest of the connectivities
+  <stem>_paga_pos_<P>.npy             [groups, 2] float32: the layout of the coarse graph
+--umap-init paga (which implies --paga) starts the layout of --umap from those positions, every cell in the box half
+way from its group to the group's strongest neighbour (scanpy's init_pos='paga').  Without the flags nothing changes.
 With --map-counts FILE beside --umap (new cells over the same genes, e.g. a second sample; .npy dense or .npz CSR):
   <stem>_UMAP_map_<P>.npy        [new cells, 2] float32: the new cells on the map above, which does not move (NaN:
                                  a cell without a finite encoding)
@@ -111,13 +118,17 @@ def build_parser():
     p.add_argument("--umap-neighbors", type=int, default=15, help="neighbours per cell of the layout's graph")
     p.add_argument("--umap-min-dist", type=float, default=0.1, help="min_dist of the layout's curve")
     p.add_argument("--umap-epochs", type=int, default=None, help="epochs of the layout (default: by size)")
-    p.add_argument("--umap-init", choices=("pca", "spectral"), default="pca", help="the layout's start: the "
-                   "encoding's principal axes, or the graph's leading eigenvectors")
+    p.add_argument("--umap-init", choices=("pca", "spectral", "paga"), default="pca", help="the layout's start: the "
+                   "encoding's principal axes, the graph's leading eigenvectors, or the layout of the groups' "
+                   "coarse graph (implies --paga)")
     p.add_argument("--spectral", type=int, default=None, help="N: writes the N leading non-trivial eigenvectors "
                                                               "of the cells' neighbour graph and their eigenvalues")
     p.add_argument("--communities", action="store_true", help="writes the Louvain communities of the cells' neighbour "
                                                               "graph (the number of clusters is found)")
     p.add_argument("--resolution", type=float, default=1.0, help="R > 0: the resolution of --communities' modularity")
+    p.add_argument("--paga", action="store_true", help="with --communities, --clusters or --labels: writes the "
+                                                       "connectivities of those groups in the neighbour graph, "
+                                                       "their spanning forest and the coarse graph's layout")
     p.add_argument("--map-counts", default=None, help="FILE: new cells over the same genes; with --umap they are "
                                                       "placed on the map (and labelled with --clusters / --labels)")
     p.add_argument("--gene-sets", default=None, help="FILE.gmt: gene sets (name, description, members per line); "
@@ -149,6 +160,10 @@ def main(argv=None):
     args = parser.parse_args(sys.argv[1:] if argv is None else argv)
     if args.silhouette and args.clusters is None and args.labels is None and not args.communities:
         parser.error("--silhouette needs --clusters, --communities or --labels")
+    if args.umap_init == "paga":
+        args.paga = True
+    if args.paga and not args.communities and args.clusters is None and args.labels is None:
+        parser.error("--paga needs --communities, --clusters or --labels")
     if not (args.resolution > 0 and args.resolution < float("inf")):
         parser.error("--resolution needs a finite R > 0")
     if args.map_counts is not None and not args.umap:
@@ -221,14 +236,28 @@ def main(argv=None):
     if args.clusters is not None:
         clusters = cluster_cells(factor, X, f"{stem}_cluster_{P}.npy", f"{stem}_centroid_{P}.npy", args)
     reference, n_clusters = None, args.clusters
+    cells, paga_labels, paga_groups = None, None, None
+    if args.paga:
+        # the graph once, for the communities, the coarse graph and a layout that starts from it
+        cells = _cell_graph(factor, X, args)
+        if clusters is not None:
+            paga_labels, paga_groups = clusters, args.clusters
+        elif args.labels is not None:
+            paga_labels = np.load(args.labels)
     if args.communities:
         # the graph once: with --umap the layout comes first and its graph is clustered
-        if args.umap:
+        if args.umap and args.umap_init != "paga":
             reference = umap_cells(factor, X, f"{stem}_UMAP_{P}.npy", args)
-        found, n_found = community_cells(factor, X, reference["graph"] if reference is not None else None,
-                                         f"{stem}_communities_{P}.npy", args)
+        graph = reference["graph"] if reference is not None else cells[2] if cells is not None else None
+        found, n_found = community_cells(factor, X, graph, f"{stem}_communities_{P}.npy", args)
         if clusters is None and n_found > 0:
             clusters, n_clusters = found, n_found
+        if n_found > 0:
+            paga_labels, paga_groups = found, n_found
+    start = None
+    if args.paga:
+        start = paga_cells(factor, cells[2], paga_labels, paga_groups, f"{stem}_paga_connectivities_{P}.npy",
+                           f"{stem}_paga_tree_{P}.npy", f"{stem}_paga_pos_{P}.npy", args)
     if args.labels is not None:
         group_table(factor, X, np.load(args.labels), gene_names, f"{stem}_groupmean_{P}.npy", args)
     elif clusters is not None:
@@ -241,7 +270,9 @@ def main(argv=None):
         else:
             print("silhouette: no cell has a community")
     if args.umap:
-        if reference is None:
+        if reference is None and args.umap_init == "paga":
+            reference = umap_cells(factor, X, f"{stem}_UMAP_{P}.npy", args, start=(cells, start))
+        elif reference is None:
             reference = umap_cells(factor, X, f"{stem}_UMAP_{P}.npy", args)
         if args.map_counts is not None:
             known = clusters if clusters is not None else (np.load(args.labels) if args.labels is not None else None)
@@ -314,11 +345,17 @@ def silhouette_cells(factor, X, labels, n_clusters, path, args):
     print(f"silhouette: {res['score']:.4f} over {res['n_scored']} cells; per cluster {means}")
 
 
-def umap_cells(factor, X, path, args):
+def umap_cells(factor, X, path, args, start=None):
     """The 2-D map of the cells (``umap`` on the encoding that ``cluster_cells`` works on: the same seed, the same
-    draws): the coordinates as a file."""
+    draws): the coordinates as a file.  ``start``: (what ``_cell_graph`` returned, the start of ``paga_cells``) for
+    --umap-init paga."""
     import torch
-    if args.umap_init == "spectral":
+    if args.umap_init == "paga":
+        (emb, nn, g), init = start
+        res = factor.graph_layout(g, init=init, n_epochs=args.umap_epochs, min_dist=args.umap_min_dist,
+                                  seed=args.cluster_seed)
+        res.update(graph=g, latent=emb, indices=nn["indices"], distances=nn["distances"])
+    elif args.umap_init == "spectral":
         res = _umap_from_spectral(factor, X, args)
     else:
         torch.manual_seed(args.cluster_seed)              # the posterior draws of the encoding
@@ -386,6 +423,24 @@ def community_cells(factor, X, graph, path, args):
           f"{res['modularity']:.6f}, sweeps per level {[lv['n_sweeps'] for lv in res['levels']]}, cells {sizes}"
           + (f", {alone} without a community" if alone else ""))
     return res["labels"], res["n_communities"]
+
+
+def paga_cells(factor, graph, labels, n_groups, conn_path, tree_path, pos_path, args):
+    """The coarse graph of the groups (``paga_init`` on the fuzzy graph ``umap_cells`` lays out): the connectivities,
+    their spanning forest and the groups' positions as files; -> the start of a layout of the cells, on the device."""
+    if labels is None:
+        sys.exit("--paga: no cell has a community")
+    res = factor.paga_init(graph, labels, n_groups=n_groups, seed=args.cluster_seed)
+    conn = res["paga"]["connectivities"].cpu().numpy()
+    np.save(conn_path, conn)
+    np.save(tree_path, res["paga"]["connectivities_tree"].cpu().numpy())
+    np.save(pos_path, res["positions"].cpu().numpy())
+    G = res["paga"]["n_groups"]
+    pairs = int((np.triu(conn, 1) > 0).sum())
+    kept = int((np.triu(res["paga"]["connectivities_tree"].cpu().numpy(), 1) > 0).sum())
+    print(f"paga: {G} groups, {pairs} connected pairs of {G * (G - 1) // 2}, {kept} in the spanning forest"
+          + (f", largest connectivity {conn.max():.3f}" if pairs else ""))
+    return res["init"]
 
 
 def map_cells(factor, X_new, reference, labels, n_classes, path, label_path, args):

@@ -1129,6 +1129,46 @@ int spmf_graph_move(spmf_ctx* ctx, int64_t n_rows, int64_t nnz, const int64_t* i
                     const int64_t* tot, const int32_t* long_rows, int64_t n_long, double gamma,
                     int64_t m2, int direction, int32_t* labels_out, void* stream);
 
+/* ---- the entries summed by the groups of their two ends (added within ABI 6: two new entry points, no struct
+ * changed) ----
+ * The dense group-to-group tables of a labelled graph in CSR whose weights are int64 fixed point
+ * (csrc/graph_groups.hip; spmf_amd/paga.py is the driver and turns the integers into PAGA's connectivities).
+ * Every sum is an integer sum, exact and the same in any order: the kernel uses integer atomics in LDS and, per
+ * segment of one group's rows, at most n_groups 64-bit global atomics -- never one per entry -- and two calls
+ * return the same bits.  No floating-point arithmetic anywhere.
+ *
+ * indptr is read under spmf_graph_spmm's rules (clamped to [0, nnz], a falling indptr is an empty row).  With
+ * G = n_groups, take row i with a = labels[i].  Entry p of that row counts when all of these hold:
+ *   a lies in [0, G);  j = indices[p] lies in [0, n_rows);  wq[p] >= 1;  b = labels[j] lies in [0, G).
+ * Self entries and repeated columns count as listed.  Then
+ *   count_out[a * G + b]  = the number of counting entries,
+ *   weight_out[a * G + b] = the int64 sum of their wq,
+ *   size_out[a]           = the number of rows with label a, with or without entries.
+ * All three outputs (int64 [G][G], [G][G], [G]) are overwritten in full.  A label outside [0, G) is "no
+ * group": such a row is skipped as a source and as a target and counts in no size.
+ *
+ * The rows are ordered by label first (the ordering of spmf_group_sums, in the scratch); a workgroup then takes
+ * blocks of one group's rows and keeps that group's row of the two tables in LDS, 16 KB at
+ * SPMF_GROUP_EDGES_MAX_GROUPS; a row of any length is walked by 16 lanes, and entries inside the row's own
+ * group are summed in registers.
+ *
+ * scratch: 256-byte aligned, at least spmf_graph_group_edges_scratch_bytes(ctx, n_rows, n_groups) bytes (a
+ * multiple of 256, non-decreasing in n_rows; 0 for arguments the call refuses).
+ *
+ * SPMF_E_ARG for n_rows outside 0..2^31 - 64, nnz < 0, n_groups outside 1..SPMF_GROUP_EDGES_MAX_GROUPS, a NULL
+ * pointer where one is needed (the three outputs and the scratch always; indptr and labels with n_rows > 0;
+ * indices / wq with nnz > 0), an output that is one of indptr, indices, wq, labels or another output
+ * ("aliases"), a misaligned scratch; then SPMF_E_WORKSPACE for a short one, naming the need; every error
+ * returns before any launch or fill with "graph_group_edges: " in front of the message.  n_rows == 0 zero-fills
+ * the outputs on the stream and returns SPMF_OK behind the checks.  The context's workspace is not touched.
+ * Stream-ordered, synchronises nowhere. */
+#define SPMF_GROUP_EDGES_MAX_GROUPS 1024
+size_t spmf_graph_group_edges_scratch_bytes(const spmf_ctx* ctx, int64_t n_rows, int32_t n_groups);
+int spmf_graph_group_edges(spmf_ctx* ctx, int64_t n_rows, int64_t nnz, const int64_t* indptr,
+                           const int32_t* indices, const int64_t* wq, const int32_t* labels,
+                           int32_t n_groups, int64_t* count_out, int64_t* weight_out, int64_t* size_out,
+                           void* scratch, size_t scratch_bytes, void* stream);
+
 /* Reductions of the non-finite rule (poisson.py:606-616) over a dense ll
  * buffer of n cells; io = double[3] on the device.
  *   pass 0: io[0] = min(io[0], min over finite cells)  (initialise io[0]=0:

@@ -1,14 +1,14 @@
 """The analysis calls of the model classes on rows and graphs as given: ``AnalysisQueries`` is the mixin that gives
 PoissonFactorization (and through it the Bernoulli and mixed classes) knn, kmeans, silhouette, fuzzy_graph,
-graph_layout, graph_transform, spectral, spectral_cluster and communities, and the composites that start from
+graph_layout, graph_transform, spectral, spectral_cluster, communities, paga and paga_init, and the composites that start from
 ``StreamingQueries.embed``: neighbors, cluster, umap and umap_transform.
 
 None of the calls here runs the draw stage: each takes float32 points [N, Kx] or a CSR graph on the model's device
 (include/spmf_hip.h; csrc/api_points.hip and csrc/api_graph.hip).  A call is: the check of its arguments, which
 comes first (``_args.integer`` / ``_args.number``, ``_knn_rows``, ``_graph_tensors`` / ``_graph_numbers``,
 ``_on_device``), its output tensors, and ``_lib.call``, the one place a library call, its scratch and its stream
-are spelled.  The loops around a call are modules of their own: ``cluster`` (Lloyd), ``spectral`` and
-``communities`` (their ``LibraryOps``), ``graph`` and ``neighbors`` (plain torch).
+are spelled.  The loops around a call are modules of their own: ``cluster`` (Lloyd), ``spectral``,
+``communities`` and ``paga`` (their ``LibraryOps``), ``graph`` and ``neighbors`` (plain torch).
 """
 from __future__ import annotations
 
@@ -458,6 +458,70 @@ class AnalysisQueries:
         self._on_device(name, "the graph", indptr)
         ops = _communities.LibraryOps(_lib.load(), self._handle(), indptr, indices, weights)
         return _communities.solve(ops, resolution, max_levels, max_sweeps, tol, name=name)
+
+    def _paga_args(self, name, graph, labels, n_groups):
+        """The graph and the labels of ``paga`` / ``paga_init``, checked before any library load -> (indptr,
+        indices, weights, labels as a 1-D integer tensor)."""
+        from . import paga as _paga
+        labels = _vector(name, "labels", labels)
+        _paga.group_count(name, labels, n_groups)
+        indptr, indices, weights, N, nnz = self._graph_tensors(name, graph)
+        if int(labels.numel()) != N:
+            raise ValueError(f"{name}: labels must have one entry per row, got {int(labels.numel())} for {N} rows")
+        self._graph_numbers(name, indptr, indices, N, nnz)
+        self._on_device(name, "the graph", indptr)
+        return indptr, indices, weights, labels
+
+    def paga(self, graph, labels, n_groups=None):
+        """The coarse graph of the groups of a labelled graph (scanpy's ``tl.paga``): which groups touch in the
+        neighbour graph, and how much more than if every row's entries were spread over all other rows alike.
+        ``spmf_amd.paga`` has the definition: the weights become int64 fixed point, the entries are summed by
+        (label of row, label of column) into dense G x G tables in one library call (include/spmf_hip.h
+        spmf_graph_group_edges, csrc/graph_groups.hip) with integer atomics only, and one fp64 host function turns
+        the integers into connectivities.  Two runs give the same bits, which are also the bits of the numpy
+        backend (``spmf_amd.paga.NumpyOps``).
+
+        ``graph``: as in ``graph_layout``, what ``fuzzy_graph`` returns, or ``spmf_amd.paga.knn_graph`` of a ``knn``
+        result without padding.  ``labels``: 1-D integers (numpy or torch on any device), one per row, what
+        ``communities``, ``cluster`` or ``spectral_cluster`` return; negative is "no group".  ``n_groups`` (at
+        most 1024) defaults to max(labels) + 1.
+
+        Returns what ``spmf_amd.paga.solve`` returns, tensors on the device: 'connectivities',
+        'connectivities_tree' (its maximum spanning forest), 'expected' (fp64 [G, G]), 'edge_count', 'edge_weight'
+        (int64 [G, G]), 'sizes' (int64 [G]) and 'n_groups'."""
+        from . import paga as _paga
+        name = "paga"
+        indptr, indices, weights, labels = self._paga_args(name, graph, labels, n_groups)
+        ops = _paga.LibraryOps(_lib.load(), self._handle(), indptr, indices, weights)
+        return _paga.solve(ops, labels, n_groups, name=name)
+
+    def paga_init(self, graph, labels, n_groups=None, seed=0, threshold=0.0, n_epochs=None, min_dist=0.1, spread=1.0,
+                  a=None, b=None, n_negatives=8, negative_rate=5.0, repulsion=1.0, learning_rate=1.0):
+        """The PAGA start of a layout (scanpy's ``tl.umap(init_pos='paga')``): ``paga``, then ``graph_layout`` of
+        the coarse graph of the entries with connectivity > ``threshold`` from ``spmf_amd.paga.group_start`` (the
+        groups on a circle), then ``spmf_amd.paga.layout_init``: every row starts in the box half way from its
+        group's position to the group's strongest neighbour.  The layout arguments are ``graph_layout``'s, for the
+        coarse graph; ``seed`` draws its negatives and the rows' places in their boxes.
+
+        Returns {'init': float32 [N, 2] on the device, 'positions': float32 [G, 2], 'paga': the result of
+        ``paga``}.  ``graph_layout(graph, init=res['init'])`` is then the PAGA-initialised map, which keeps the
+        groups' global arrangement.  Bit-reproducible for a given seed on one machine."""
+        from . import paga as _paga
+        name = "paga_init"
+        la = self._layout_args(name, n_epochs, min_dist, spread, a, b, n_negatives, negative_rate, repulsion,
+                               learning_rate, seed, "random")
+        threshold = _args.number(name, "threshold", threshold)
+        _args.integer(name, "seed", seed, 0, 2 ** 63 - 1)
+        indptr, indices, weights, labels = self._paga_args(name, graph, labels, n_groups)
+        ops = _paga.LibraryOps(_lib.load(), self._handle(), indptr, indices, weights)
+        res = _paga.solve(ops, labels, n_groups, name=name)
+        conn = res["connectivities"]
+        coarse = _paga.coarse_graph(conn, threshold)
+        start = _paga.group_start(res["n_groups"]).to(conn.device)
+        lay = self.graph_layout(coarse, init=start, n_epochs=la.n_epochs, a=la.a, b=la.b, n_negatives=la.M,
+                                negative_rate=la.rate, repulsion=la.gamma, learning_rate=la.lr, seed=la.seed)
+        init = _paga.layout_init(labels, lay["embedding"], conn, seed=la.seed).to(conn.device)
+        return {"init": init, "positions": lay["embedding"], "paga": res}
 
     def graph_transform(self, indices, distances, reference_layout, weights=None, init=None, n_epochs=None,
                         min_dist=0.1, spread=1.0, a=None, b=None, n_negatives=8, negative_rate=5.0, repulsion=1.0,

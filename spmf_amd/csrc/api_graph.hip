@@ -1,7 +1,7 @@
 // api_graph.hip -- the calls on a graph as given behind the C-ABI (include/spmf_hip.h): the layout epochs
 // (spmf_graph_layout, spmf_graph_transform), the graph products and block operations of spectral.hip
-// (spmf_graph_scale, spmf_graph_spmm, spmf_block_gram, spmf_block_rotate) and the sweep of graph_move.hip
-// (spmf_graph_move).  None runs the draw stage (api_stream.hip).  An entry is: graph_csr_check where it takes the CSR
+// (spmf_graph_scale, spmf_graph_spmm, spmf_block_gram, spmf_block_rotate), the sweep of graph_move.hip
+// (spmf_graph_move) and the group-to-group sums of graph_groups.hip (spmf_graph_group_edges).  None runs the draw stage (api_stream.hip).  An entry is: graph_csr_check where it takes the CSR
 // triple, its own argument checks, carve_scratch where it has a scratch, its empty return, its launch, `launched`.
 // Host-side orchestration only (ctx.h).
 #include "ctx.h"
@@ -181,6 +181,59 @@ int spmf_graph_move(spmf_ctx* c, int64_t n_rows, int64_t nnz, const int64_t* ind
   ma.labels_in = labels_in; ma.tot = tot; ma.long_rows = long_rows; ma.n_long = n_long;
   ma.gamma = gamma; ma.m2 = (double)m2; ma.direction = direction; ma.labels_out = labels_out;
   launch_graph_move(ma, (hipStream_t)stream);
+  return launched(c, true, "");
+}
+
+// ---- the entries summed by the labels of their two ends (graph_groups.hip behind groups.hip's ordering) ----------
+// Scratch of one call: the ordering of the rows by label (launch_group_order); every region grows with the rows.
+static bool group_edges_groups_ok(int32_t G) { return G >= 1 && G <= kGroupEdgesMaxGroups; }
+static void group_edges_carve(Arena& a, int64_t rows, int G, GroupEdgesArgs& ga) {
+  const GroupEdgesGeom q = group_edges_geom(rows, G);
+  group_order_carve(a, rows, G, q.chunks, q.NB, ga.ord);
+}
+
+size_t spmf_graph_group_edges_scratch_bytes(const spmf_ctx* c, int64_t n_rows, int32_t n_groups) {
+  if (!c || !rows_ok(n_rows) || !group_edges_groups_ok(n_groups)) return 0;
+  GroupEdgesArgs ga{};
+  return layout_bytes([&](Arena& a) { group_edges_carve(a, n_rows, n_groups, ga); });
+}
+
+int spmf_graph_group_edges(spmf_ctx* c, int64_t n_rows, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+    const int64_t* wq, const int32_t* labels, int32_t n_groups, int64_t* count_out, int64_t* weight_out,
+    int64_t* size_out, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!c) return SPMF_E_ARG;
+  const std::string f = "graph_group_edges: ";
+  int rc = graph_csr_check(c, f, n_rows, nnz, indptr, indices, wq);
+  if (rc) return rc;
+  if (!group_edges_groups_ok(n_groups)) return fail(c, SPMF_E_ARG, f + "n_groups must be in 1..1024");
+  if (!count_out || !weight_out || !size_out || (n_rows > 0 && !labels)) return fail(c, SPMF_E_ARG,
+      f + "null argument");
+  const void* outs[3] = {count_out, weight_out, size_out};
+  const void* ins[4] = {indptr, indices, wq, labels};
+  for (int o = 0; o < 3; ++o) {
+    for (int i = 0; i < 4; ++i)
+      if (outs[o] == ins[i]) return fail(c, SPMF_E_ARG, f + "an output aliases an input: the kernel reads the graph "
+          "and the labels while it adds to the outputs");
+    for (int p = 0; p < o; ++p)
+      if (outs[o] == outs[p]) return fail(c, SPMF_E_ARG, f + "an output aliases another output");
+  }
+  GroupEdgesArgs ga{};
+  rc = carve_scratch(c, "graph_group_edges", scratch, scratch_bytes,
+      [&](Arena& a) { group_edges_carve(a, n_rows, n_groups, ga); },
+      [&] { return rows_shape(n_rows) + " n_groups=" + std::to_string(n_groups); });
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (n_rows == 0) {
+    const size_t table = (size_t)n_groups * n_groups * sizeof(int64_t);
+    HIPCHK(c, hipMemsetAsync(count_out, 0, table, st));
+    HIPCHK(c, hipMemsetAsync(weight_out, 0, table, st));
+    HIPCHK(c, hipMemsetAsync(size_out, 0, (size_t)n_groups * sizeof(int64_t), st));
+    return SPMF_OK;
+  }
+  ga.n_rows = n_rows; ga.nnz = nnz; ga.indptr = indptr; ga.indices = indices; ga.wq = wq;
+  ga.labels = labels; ga.n_groups = n_groups;
+  ga.count_out = count_out; ga.weight_out = weight_out; ga.size_out = size_out;
+  launch_group_edges(ga, st);
   return launched(c, true, "");
 }
 

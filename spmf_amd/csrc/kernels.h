@@ -532,6 +532,29 @@ struct MoveArgs {
   int32_t* labels_out;             // [n_rows]; never labels_in
 };
 void launch_graph_move(const MoveArgs& a, hipStream_t st);
+// graph_groups.hip: the graph's entries summed by (label of row, label of column) into dense [G][G] tables
+// (include/spmf_hip.h spmf_graph_group_edges has the definition).  Integers only: LDS and global integer atomics,
+// exact in any order.  ord is api_graph.hip's carve, sized from group_edges_geom, a pure function of (n_rows, G).
+// n_rows > 0.
+constexpr int kGroupEdgesMaxGroups = SPMF_GROUP_EDGES_MAX_GROUPS;
+constexpr int kGroupEdgesTargetRuns = 2048;   // runs of row blocks aimed at (a constant: not the device's CU count)
+struct GroupEdgesGeom {
+  int64_t NB, chunks;              // as GroupGeom
+  int runs, RB;
+};
+GroupEdgesGeom group_edges_geom(int64_t n_rows, int G);
+struct GroupEdgesArgs {
+  int64_t n_rows, nnz;
+  const int64_t* indptr;           // [n_rows + 1]
+  const int32_t* indices;          // [nnz]
+  const int64_t* wq;               // [nnz]; an entry counts with wq >= 1
+  const int32_t* labels;           // [n_rows]; outside [0, n_groups): no group
+  int n_groups;
+  int64_t *count_out, *weight_out; // [G][G]
+  int64_t* size_out;               // [G]
+  GroupOrder ord;
+};
+void launch_group_edges(const GroupEdgesArgs& a, hipStream_t st);
 // sets.hip: per row and column set the fp64 weighted sum over the set's listed columns of the posterior
 // predictive mean m_s, reduced over the draws: mean [B][ld] (column g = set g) and, where asked for, the unbiased
 // standard deviation over the draws (S >= 2).  set_ptr: HOST, [n_sets + 1], set g lists cols[set_ptr[g] ..
