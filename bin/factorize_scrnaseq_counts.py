@@ -64,6 +64,14 @@ those of --communities, else of --clusters, else of --labels, and one of the thr
   <stem>_paga_pos_<P>.npy             [groups, 2] float32: the layout of the coarse graph
 --umap-init paga (which implies --paga) starts the layout of --umap from those positions, every cell in the box half
 way from its group to the group's strongest neighbour (scanpy's init_pos='paga').  Without the flags nothing changes.
+With --pseudotime ROOT (how far along the cells' neighbour graph every cell is from cell number ROOT: the exact
+shortest-path distance over the symmetric graph of the same --umap-neighbors neighbours, their latent distances the
+lengths, divided by the largest one; the ordering put next to --paga):
+  <stem>_pseudotime_<P>.npy      [cells] float32 in [0, 1] (NaN: a cell the root does not reach)
+  <stem>_paga_pseudotime_<P>.npy [groups] float64, with --paga: the mean pseudotime of every group's reached cells
+                                 (NaN: a group without one)
+over the same encoding and seed; the neighbours --umap, --communities or --paga found in the same run are used again.
+Without the flag nothing changes.
 With --map-counts FILE beside --umap (new cells over the same genes, e.g. a second sample; .npy dense or .npz CSR):
   <stem>_UMAP_map_<P>.npy        [new cells, 2] float32: the new cells on the map above, which does not move (NaN:
                                  a cell without a finite encoding)
@@ -129,6 +137,9 @@ def build_parser():
     p.add_argument("--paga", action="store_true", help="with --communities, --clusters or --labels: writes the "
                                                        "connectivities of those groups in the neighbour graph, "
                                                        "their spanning forest and the coarse graph's layout")
+    p.add_argument("--pseudotime", type=int, default=None, metavar="ROOT", help="a cell number: writes every cell's "
+                   "distance from that cell along the neighbour graph, scaled to [0, 1] (with --paga also the "
+                   "groups' means)")
     p.add_argument("--map-counts", default=None, help="FILE: new cells over the same genes; with --umap they are "
                                                       "placed on the map (and labelled with --clusters / --labels)")
     p.add_argument("--gene-sets", default=None, help="FILE.gmt: gene sets (name, description, members per line); "
@@ -168,6 +179,8 @@ def main(argv=None):
         parser.error("--resolution needs a finite R > 0")
     if args.map_counts is not None and not args.umap:
         parser.error("--map-counts needs --umap")
+    if args.pseudotime is not None and args.pseudotime < 0:
+        parser.error("--pseudotime needs a cell number >= 0")
     if args.spectral is not None and not 1 <= args.spectral <= 12:
         parser.error("--spectral needs 1 <= N <= 12")
     if args.map_counts is not None and not os.path.exists(args.map_counts):
@@ -194,6 +207,8 @@ def main(argv=None):
     nb = N // B
     if nb == 0:
         sys.exit("fewer cells than one batch")
+    if args.pseudotime is not None and args.pseudotime >= N:
+        sys.exit(f"--pseudotime must be one of the {N} cells, got {args.pseudotime}")
     # shuffle once, batch with drop_remainder (:86-87); the batches stay resident on the device
     perm = np.random.default_rng(args.seed).permutation(N)
     batches = []
@@ -237,9 +252,10 @@ def main(argv=None):
         clusters = cluster_cells(factor, X, f"{stem}_cluster_{P}.npy", f"{stem}_centroid_{P}.npy", args)
     reference, n_clusters = None, args.clusters
     cells, paga_labels, paga_groups = None, None, None
-    if args.paga:
-        # the graph once, for the communities, the coarse graph and a layout that starts from it
+    if args.paga or (args.pseudotime is not None and not args.umap):
+        # the graph once, for the communities, the coarse graph, a layout that starts from it and the pseudotime
         cells = _cell_graph(factor, X, args)
+    if args.paga:
         if clusters is not None:
             paga_labels, paga_groups = clusters, args.clusters
         elif args.labels is not None:
@@ -282,6 +298,11 @@ def main(argv=None):
             map_cells(factor, X_new, reference, known,
                       n_clusters if clusters is not None else None, f"{stem}_UMAP_map_{P}.npy",
                       f"{stem}_label_map_{P}.npy", args)
+    if args.pseudotime is not None:
+        # the neighbours of the run: the layout's, else those of the graph made above
+        nn = reference if reference is not None else cells[1]
+        pseudotime_cells(factor, nn, args.pseudotime, f"{stem}_pseudotime_{P}.npy",
+                         paga_labels if args.paga else None, paga_groups, f"{stem}_paga_pseudotime_{P}.npy")
     if args.spectral is not None:
         spectral_cells(factor, X, f"{stem}_spectral_{P}.npy", f"{stem}_spectral_values_{P}.npy", args)
     if args.gene_sets is not None:
@@ -441,6 +462,32 @@ def paga_cells(factor, graph, labels, n_groups, conn_path, tree_path, pos_path, 
     print(f"paga: {G} groups, {pairs} connected pairs of {G * (G - 1) // 2}, {kept} in the spanning forest"
           + (f", largest connectivity {conn.max():.3f}" if pairs else ""))
     return res["init"]
+
+
+def pseudotime_cells(factor, nn, root, path, labels=None, n_groups=None, group_path=None):
+    """The pseudotime of the cells from cell ``root`` (``geodesic`` on ``spmf_amd.geodesic.length_graph`` of the kNN
+    result ``nn``, a dict with 'indices' and 'distances'; then ``spmf_amd.geodesic.pseudotime``) as a file; with
+    ``labels`` (the groups of --paga) also the mean over every group's reached cells -> the pseudotime on the device."""
+    import torch
+    from spmf_amd import geodesic
+    g = geodesic.length_graph(nn["indices"], nn["distances"])
+    res = factor.geodesic(g, torch.tensor([root]))
+    t = geodesic.pseudotime(res["distances"][:, 0])
+    np.save(path, t.cpu().numpy())
+    reached = torch.isfinite(t)
+    print(f"pseudotime: root {root}, {int(reached.sum())} of {int(t.numel())} cells reached over "
+          f"{int(g['indices'].numel())} graph entries, {res['n_sweeps']} sweeps"
+          + ("" if res["converged"] else " (not converged)")
+          + f", largest distance {float(res['distances'][:, 0][reached].max()) if bool(reached.any()) else 0.0:.4g}")
+    if labels is not None:
+        lab = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+        G = int(n_groups) if n_groups is not None else max(int(lab.max()) + 1, 1)
+        tn = t.cpu().numpy().astype(np.float64)
+        mean = np.array([tn[(lab == a) & np.isfinite(tn)].mean() if ((lab == a) & np.isfinite(tn)).any()
+                         else np.nan for a in range(G)], dtype=np.float64)
+        np.save(group_path, mean)
+        print("pseudotime: group means " + ", ".join(f"{v:.3f}" for v in mean.tolist()))
+    return t
 
 
 def map_cells(factor, X_new, reference, labels, n_classes, path, label_path, args):

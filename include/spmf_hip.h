@@ -1091,6 +1091,49 @@ int spmf_block_gram(spmf_ctx* ctx, int64_t n_rows, const float* x, const float* 
 int spmf_block_rotate(spmf_ctx* ctx, int64_t n_rows, const float* x, const double* r, float* y,
                       void* stream);
 
+/* ---- shortest-path sweeps on the graph (added within ABI 6: two new entry points, no struct changed) ----
+ * Single- and multi-source shortest paths on a CSR graph of edge lengths, as spmf_graph_spmm in the (min, +)
+ * semiring (csrc/graph_paths.hip; spmf_amd/geodesic.py is the driver that repeats the call to the fixed point).
+ * A block is fp32 [n_rows][SPMF_BLOCK_COLS] as above, a column per source or set of sources: the start holds 0 on
+ * a column's sources and +inf elsewhere.  The graph is read under spmf_graph_spmm's rules: an indptr value is
+ * clamped to [0, nnz], a falling indptr is an empty row, an entry counts only if its index lies in [0, n_rows)
+ * and its length is finite and > 0; n_rows <= 2^31 - 64.  No argument values make a kernel read outside its
+ * arrays.  No atomic: two calls return the same bits.
+ *
+ * One sweep X -> Y.  For row i and column l, with best = +inf and arg = -1, the counting entries (j, w_ij) of
+ *   the row are walked in list order: t = X_jl + w_ij, one fp32 addition; if t < best then best = t, arg = j.
+ *   Then Y_il = best < X_il ? best : X_il.  A lane owns a column, so Y_il is a function of row i's list and of
+ *   column l of X alone.  Values are taken as given: a NaN never wins a <, so it stays where it is and reaches
+ *   nobody.  fl(a + w) is monotone in a and a minimum does not depend on the order, so the fixed point of the
+ *   sweep is unique: bit for bit what an fp32 Dijkstra making the same left-to-right additions returns.
+ * n_sweeps >= 0 sweeps run as that many launches, alternating between the two blocks of the scratch; x_in is
+ *   copied into the first, so x_out may be x_in.  n_sweeps == 0 copies x_in to x_out.
+ * changed_out (device, one int32, may be NULL): zero-filled on the stream before the last sweep, then set to 1
+ *   by every lane whose Y_il differs from its X_il in that last sweep (a plain store; all writers store the
+ *   same word): 0 tells that x_out is the fixed point.  With n_sweeps == 0 it is zero-filled.
+ * pred_out (device, int32 [n_rows][SPMF_BLOCK_COLS], may be NULL): written by the last sweep only (not at all
+ *   with n_sweeps == 0): arg where best == Y_il, Y_il is finite and X_{arg,l} < Y_il; else -1.  On a converged
+ *   block that is the first entry in list order that attains the row's distance from a strictly nearer row:
+ *   the chain of predecessors strictly decreases in distance, so it is acyclic and ends at a source (which has
+ *   -1, all lengths being positive) or at -1.  A reached row that is no source gets -1 only where the addition
+ *   was absorbed -- w below half an ulp of the distance, fl(X_jl + w) == X_jl: such a row has the distance of
+ *   its neighbour and no strictly nearer one.
+ *
+ * scratch: 256-byte aligned, at least spmf_graph_relax_scratch_bytes(ctx, n_rows) bytes, a multiple of 256 and
+ * non-decreasing in n_rows (0 for n_rows outside the range).
+ *
+ * SPMF_E_ARG for n_rows outside 0..2^31 - 64, nnz < 0, n_sweeps < 0, a NULL pointer where one is needed (indptr,
+ * x_in, x_out with n_rows > 0; indices / lengths with nnz > 0; the scratch always), an output (x_out, pred_out,
+ * changed_out) that is one of indptr, indices, lengths or another output, or pred_out / changed_out == x_in
+ * ("aliases"), a misaligned scratch; then SPMF_E_WORKSPACE for a short one, naming the need; every error returns
+ * before any launch or write with "graph_relax: " in front of the message.  n_rows == 0 returns SPMF_OK behind
+ * the checks.  The context's workspace is not touched.  Stream-ordered, synchronises nowhere. */
+size_t spmf_graph_relax_scratch_bytes(const spmf_ctx* ctx, int64_t n_rows);
+int spmf_graph_relax(spmf_ctx* ctx, int64_t n_rows, int64_t nnz, const int64_t* indptr,
+                     const int32_t* indices, const float* lengths, const float* x_in, float* x_out,
+                     int32_t* pred_out, int32_t* changed_out, int n_sweeps, void* scratch,
+                     size_t scratch_bytes, void* stream);
+
 /* ---- modularity moves on the graph (added within ABI 6: one new entry point, no struct changed) ----
  * One Jacobi sweep of Louvain's local moving on a graph in CSR whose weights are int64 fixed point
  * (csrc/graph_move.hip; spmf_amd/communities.py is the driver and has the whole algorithm).  Every sum is an

@@ -1,19 +1,20 @@
 """The analysis calls of the model classes on rows and graphs as given: ``AnalysisQueries`` is the mixin that gives
 PoissonFactorization (and through it the Bernoulli and mixed classes) knn, kmeans, silhouette, fuzzy_graph,
-graph_layout, graph_transform, spectral, spectral_cluster, communities, paga and paga_init, and the composites that start from
-``StreamingQueries.embed``: neighbors, cluster, umap and umap_transform.
+graph_layout, graph_transform, spectral, spectral_cluster, communities, paga, paga_init and geodesic, and the
+composites that start from ``StreamingQueries.embed``: neighbors, cluster, umap, umap_transform and pseudotime.
 
 None of the calls here runs the draw stage: each takes float32 points [N, Kx] or a CSR graph on the model's device
 (include/spmf_hip.h; csrc/api_points.hip and csrc/api_graph.hip).  A call is: the check of its arguments, which
 comes first (``_args.integer`` / ``_args.number``, ``_knn_rows``, ``_graph_tensors`` / ``_graph_numbers``,
 ``_on_device``), its output tensors, and ``_lib.call``, the one place a library call, its scratch and its stream
 are spelled.  The loops around a call are modules of their own: ``cluster`` (Lloyd), ``spectral``,
-``communities`` and ``paga`` (their ``LibraryOps``), ``graph`` and ``neighbors`` (plain torch).
+``communities``, ``paga`` and ``geodesic`` (their ``LibraryOps``), ``graph`` and ``neighbors`` (plain torch).
 """
 from __future__ import annotations
 
 from types import SimpleNamespace
 
+import numpy as np
 import torch
 
 from . import _args, _lib
@@ -458,6 +459,77 @@ class AnalysisQueries:
         self._on_device(name, "the graph", indptr)
         ops = _communities.LibraryOps(_lib.load(), self._handle(), indptr, indices, weights)
         return _communities.solve(ops, resolution, max_levels, max_sweeps, tol, name=name)
+
+    def geodesic(self, graph, sources, predecessors=False, max_sweeps=None):
+        """Exact shortest-path distances along a graph of edge lengths from ``sources``: how far along the neighbour
+        graph every row is from a root -- the base of pseudotime, Isomap-style landmark distances, the distance to
+        the nearest row of a set.  ``spmf_amd.geodesic`` has the definition: synchronous relaxation in pull form,
+        16 sources to a block, one library launch per sweep (include/spmf_hip.h spmf_graph_relax,
+        csrc/graph_paths.hip: ``spmf_graph_spmm``'s access pattern in the (min, +) semiring, no atomic), repeated
+        until a sweep changes nothing.  The fixed point is unique, so two runs give the same bits, which are also
+        the bits of the numpy backend (``spmf_amd.geodesic.NumpyOps``) and of a float32 Dijkstra.
+
+        ``graph``: as in ``graph_layout``, but 'weights' are LENGTHS: ``spmf_amd.geodesic.length_graph`` of a
+        ``knn`` result, or ``spmf_amd.geodesic.lengths_from_weights`` of a ``fuzzy_graph``; an entry counts with a
+        finite length > 0.  ``sources``: a 1-D integer tensor of row numbers, one column each, or a list of such
+        tensors, one column per set (the distance to the nearest row of the set).  ``max_sweeps`` defaults to N;
+        reaching it is reported through 'converged'.
+
+        Returns what ``spmf_amd.geodesic.solve`` returns, tensors on the graph's device: 'distances' float32
+        [N, S] (+inf: unreached), 'predecessors' int32 [N, S] (with ``predecessors``; ``spmf_amd.geodesic.path``
+        walks them) or None, 'n_sweeps' and 'converged'.  A model on the CPU runs the numpy backend on a graph on
+        the CPU; a model on a device takes the graph on that device only."""
+        from . import geodesic as _geodesic
+        name = "geodesic"
+        indptr, indices, weights, N, nnz = self._graph_tensors(name, graph)
+        _geodesic.source_sets(name, sources, N)
+        if max_sweeps is not None:
+            _args.integer(name, "max_sweeps", max_sweeps, 1, 2 ** 31 - 1)
+        self._graph_numbers(name, indptr, indices, N, nnz)
+        if torch.device(self.device).type == "cpu":
+            if indptr.device.type != "cpu":
+                raise ValueError(f"{name}: the graph must be on the model's device {self.device}, got "
+                                 f"{indptr.device}")
+            ops = _geodesic.NumpyOps({"indptr": indptr, "indices": indices, "weights": weights})
+        else:
+            self._on_device(name, "the graph", indptr)
+            ops = _geodesic.LibraryOps(_lib.load(), self._handle(), indptr, indices, weights)
+        return _geodesic.solve(ops, sources, predecessors=bool(predecessors), max_sweeps=max_sweeps, name=name)
+
+    def pseudotime(self, data, root, k=15, metric="euclidean", nsamples=32, draws=None, max_rows=None):
+        """The pseudotime of the rows of ``data`` from ``root``: ``embed`` on ``data``, ``knn`` on the posterior mean
+        encodings, ``spmf_amd.geodesic.length_graph`` of their result, ``geodesic`` from the root and
+        ``spmf_amd.geodesic.pseudotime``: the distance along the neighbour graph divided by the largest finite one
+        (dpt's convention: values in [0, 1], NaN for rows the root does not reach).  ``root``: a row number, or a
+        1-D integer tensor of them, one column each.  ``data``, ``nsamples`` / ``draws`` and ``max_rows`` as in
+        ``embed`` (the rows of all batches are concatenated); ``k`` and ``metric`` as in ``knn``.
+
+        Returns {'pseudotime': float32 [N] (a row number) or [N, S] (a tensor), 'geodesic': float32 of that shape,
+        the distances, 'n_sweeps', 'converged', 'graph' (the graph of lengths), 'latent' (the encoding, float32
+        [N, latent_dim]) and the 'indices' / 'distances' of ``knn``} on the device, bit for bit the calls made by
+        hand.  Bit-reproducible for given draws.  Needs a model on a device: ``embed`` and ``knn`` are the
+        library's; on a CPU model the parts that have a numpy backend are called by hand (``geodesic`` on a graph of
+        ``spmf_amd.geodesic.length_graph``, then ``spmf_amd.geodesic.pseudotime``)."""
+        from . import geodesic as _geodesic
+        name = "pseudotime"
+        self._knn_args(name, k, metric)
+        single = isinstance(root, (int, np.integer)) and not isinstance(root, bool)
+        if not single and not isinstance(root, torch.Tensor):
+            raise ValueError(f"{name}: root must be a row number or a 1-D integer tensor of them, got "
+                             f"{type(root).__name__}")
+        roots = torch.tensor([int(root)], dtype=torch.int64) if single else root
+        _geodesic.source_sets(name, roots, 2 ** 63 - 1)          # the type and the sign; the range needs the rows
+        if not 1 <= self.latent_dim <= 256:
+            raise ValueError(f"{name}: latent_dim {self.latent_dim} is beyond the 256 columns of knn")
+        emb = self.embed(data, nsamples=nsamples, draws=draws, max_rows=max_rows)["mean"]
+        _geodesic.source_sets(name, roots, int(emb.shape[0]))
+        nn = self.knn(emb, k=k, metric=metric)
+        g = _geodesic.length_graph(nn["indices"], nn["distances"])
+        res = self.geodesic(g, roots)
+        dist = res["distances"][:, 0].contiguous() if single else res["distances"]
+        return {"pseudotime": _geodesic.pseudotime(dist), "geodesic": dist, "n_sweeps": res["n_sweeps"],
+                "converged": res["converged"], "graph": g, "latent": emb, "indices": nn["indices"],
+                "distances": nn["distances"]}
 
     def _paga_args(self, name, graph, labels, n_groups):
         """The graph and the labels of ``paga`` / ``paga_init``, checked before any library load -> (indptr,

@@ -1,7 +1,8 @@
 // api_graph.hip -- the calls on a graph as given behind the C-ABI (include/spmf_hip.h): the layout epochs
 // (spmf_graph_layout, spmf_graph_transform), the graph products and block operations of spectral.hip
 // (spmf_graph_scale, spmf_graph_spmm, spmf_block_gram, spmf_block_rotate), the sweep of graph_move.hip
-// (spmf_graph_move) and the group-to-group sums of graph_groups.hip (spmf_graph_group_edges).  None runs the draw stage (api_stream.hip).  An entry is: graph_csr_check where it takes the CSR
+// (spmf_graph_move), the group-to-group sums of graph_groups.hip (spmf_graph_group_edges) and the shortest-path
+// sweeps of graph_paths.hip (spmf_graph_relax).  None runs the draw stage (api_stream.hip).  An entry is: graph_csr_check where it takes the CSR
 // triple, its own argument checks, carve_scratch where it has a scratch, its empty return, its launch, `launched`.
 // Host-side orchestration only (ctx.h).
 #include "ctx.h"
@@ -156,6 +157,60 @@ int spmf_graph_spmm(spmf_ctx* c, int64_t n_rows, int64_t nnz, const int64_t* ind
   if (n_rows == 0) return SPMF_OK;
   launch_graph_spmm(GraphCsr{n_rows, nnz, indptr, indices, weights}, scale, x, c_z != 0.0 ? z : nullptr, y,
       (float)c_s, cx, (float)c_z, (hipStream_t)stream);
+  return launched(c, true, "");
+}
+
+// ---- shortest-path sweeps on the graph (graph_paths.hip) ------------------------------------------
+// Scratch of one call: the two blocks the sweeps alternate between; the first takes the start.
+static void graph_relax_carve(Arena& a, int64_t rows, GraphRelaxArgs& ga) {
+  const size_t n = (rows > 0 ? (size_t)rows : 1) * kBlockCols;
+  ga.buf[0] = a.take<float>(n);
+  ga.buf[1] = a.take<float>(n);
+}
+
+size_t spmf_graph_relax_scratch_bytes(const spmf_ctx* c, int64_t n_rows) {
+  if (!c || !rows_ok(n_rows)) return 0;
+  GraphRelaxArgs ga{};
+  return layout_bytes([&](Arena& a) { graph_relax_carve(a, n_rows, ga); });
+}
+
+int spmf_graph_relax(spmf_ctx* c, int64_t n_rows, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+    const float* lengths, const float* x_in, float* x_out, int32_t* pred_out, int32_t* changed_out, int n_sweeps,
+    void* scratch, size_t scratch_bytes, void* stream) {
+  if (!c) return SPMF_E_ARG;
+  const std::string f = "graph_relax: ";
+  GraphRelaxArgs ga{};
+  int rc = graph_csr_check(c, f, n_rows, nnz, indptr, indices, lengths);
+  if (rc) return rc;
+  if (n_sweeps < 0) return fail(c, SPMF_E_ARG, f + "n_sweeps is negative");
+  if (n_rows > 0 && (!x_in || !x_out)) return fail(c, SPMF_E_ARG, f + "null argument");
+  const void* outs[3] = {x_out, pred_out, changed_out};
+  const void* ins[4] = {indptr, indices, lengths, x_in};
+  for (int o = 0; o < 3; ++o) {
+    if (!outs[o]) continue;
+    for (int i = 0; i < 4; ++i)
+      if (outs[o] == ins[i] && !(o == 0 && i == 3)) return fail(c, SPMF_E_ARG, f + "an output aliases an input: "
+          "the sweeps read the graph while they write (only x_out may be x_in)");
+    for (int p = 0; p < o; ++p)
+      if (outs[o] == outs[p]) return fail(c, SPMF_E_ARG, f + "an output aliases another output");
+  }
+  rc = carve_scratch(c, "graph_relax", scratch, scratch_bytes,
+      [&](Arena& ar) { graph_relax_carve(ar, n_rows, ga); }, [&] { return rows_shape(n_rows); });
+  if (rc) return rc;
+  if (n_rows == 0) return SPMF_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t bytes = (size_t)n_rows * kBlockCols * sizeof(float);
+  if (n_sweeps == 0) {
+    if (x_out != x_in) HIPCHK(c, hipMemcpyAsync(x_out, x_in, bytes, hipMemcpyDeviceToDevice, st));
+    if (changed_out) launch_zero(changed_out, sizeof(int32_t), st);
+    return launched(c, true, "");
+  }
+  // the prologue: the start goes into the first buffer, so no sweep reads x_in or x_out (they may be one)
+  HIPCHK(c, hipMemcpyAsync(ga.buf[0], x_in, bytes, hipMemcpyDeviceToDevice, st));
+  ga.n_rows = n_rows; ga.nnz = nnz;
+  ga.indptr = indptr; ga.indices = indices; ga.lengths = lengths;
+  ga.x_out = x_out; ga.pred_out = pred_out; ga.changed_out = changed_out; ga.n_sweeps = n_sweeps;
+  launch_graph_relax(ga, st);
   return launched(c, true, "");
 }
 

@@ -513,6 +513,22 @@ inline int64_t gram_chunks(int64_t n_rows) { return (n_rows + kGramChunk - 1) / 
 // g[256] = x^T y in fp64: partial [gram_chunks(n_rows)][256], then their sum in ascending chunk order
 void launch_block_gram(int64_t n_rows, const float* x, const float* y, double* partial, double* g, hipStream_t st);
 void launch_block_rotate(int64_t n_rows, const float* x, const BlockRot& r, float* y, hipStream_t st);
+// graph_paths.hip: n_sweeps >= 1 sweeps of Y_il = min(X_il, min_j fl(X_jl + w_ij)) on fp32 [n_rows][16] blocks
+// (include/spmf_hip.h spmf_graph_relax has the definition), one launch each, graph_spmm's access pattern.  buf[0]
+// holds the start; the sweeps alternate between the two buffers and the last writes x_out, pred_out and
+// changed_out (zeroed on the stream in front of it); the last two may be null.  n_rows > 0.
+struct GraphRelaxArgs {
+  int64_t n_rows, nnz;
+  const int64_t* indptr;           // [n_rows + 1]
+  const int32_t* indices;          // [nnz]
+  const float* lengths;            // [nnz]; an entry counts with a finite length > 0
+  float* buf[2];                   // [n_rows][16] each
+  float* x_out;                    // [n_rows][16]
+  int32_t* pred_out;               // [n_rows][16], or null
+  int32_t* changed_out;            // one word, or null
+  int n_sweeps;
+};
+void launch_graph_relax(const GraphRelaxArgs& a, hipStream_t st);
 // graph_move.hip: one Jacobi sweep of modularity moves (include/spmf_hip.h spmf_graph_move has the definition).
 // Weights are int64 fixed point, so every sum is exact; the score is four fp64 operations, each rounded once.
 // Rows of at most kMoveGroupLen entries are moved by a 16-lane group each, the rows of long_rows by a workgroup

@@ -21,38 +21,18 @@
 // sums in ascending chunk order.  block_rotate reads a row whole, forms its 16 fp64 sums over ascending k against
 // R in LDS and rounds each once.
 //
-// Nothing here trusts the graph: an indptr value is clamped to [0, nnz], a falling indptr is an empty row.
+// Nothing here trusts the graph: an indptr value is clamped to [0, nnz], a falling indptr is an empty row
+// (graph_rows.h: the row of a lane group, shared with graph_paths.hip).
 #include "common.h"
+#include "graph_rows.h"
 #include "kernels.h"
 
 namespace spmf {
 
 namespace {
 
-constexpr int kRowLanes = kBlockCols;                 // a lane per column
-constexpr int kRowsPerBlock = 256 / kRowLanes;
-constexpr int kUnroll = 8;                            // entries of a row in flight per lane
 constexpr int kGramTile = 64;                         // rows of an LDS tile of block_gram
-static_assert(kBlockCols == 16 && kGramChunk % kGramTile == 0, "a row is a 16-lane group");
-
-__device__ __forceinline__ bool weight_counts(float w) { return w > 0.f && w < INFINITY; }
-
-// the row of a lane group and its clamped list [p0, p1): empty for a dead group and for a falling indptr
-struct RowList {
-  int64_t i, p0, p1;
-  bool live;
-};
-__device__ __forceinline__ RowList row_list(const GraphCsr& g) {
-  RowList r;
-  r.i = (int64_t)blockIdx.x * kRowsPerBlock + (threadIdx.x / kRowLanes);
-  r.live = r.i < g.n_rows;                            // the same for the 16 lanes of a group
-  r.p0 = r.p1 = 0;
-  if (r.live) {
-    r.p0 = min(max(g.indptr[r.i], (int64_t)0), g.nnz);
-    r.p1 = min(max(g.indptr[r.i + 1], (int64_t)0), g.nnz);
-  }
-  return r;
-}
+static_assert(kGramChunk % kGramTile == 0, "a chunk is whole tiles");
 
 // the fixed tree over an aligned group of 16 lanes, fp64: every lane ends up with the same bits
 __device__ __forceinline__ double group16_sum(double v) {
@@ -175,8 +155,6 @@ __global__ __launch_bounds__(256) void block_rotate_kernel(int64_t n_rows, const
   for (int k = 0; k < kBlockCols; ++k) acc = fma((double)xr[k], rs[k][b], acc);
   y[(size_t)i * kBlockCols + b] = (float)acc;
 }
-
-static unsigned row_blocks(int64_t n_rows) { return (unsigned)((n_rows + kRowsPerBlock - 1) / kRowsPerBlock); }   // < 2^27
 
 void launch_graph_scale(const GraphCsr& g, float* scale, hipStream_t st) {
   hipLaunchKernelGGL(graph_scale_kernel, dim3(row_blocks(g.n_rows)), dim3(256), 0, st, g, scale);
